@@ -8,15 +8,23 @@ resident in HBM when the timed region starts).
 N=1 workload (default): data/lecture5.sdl at 3840x2160 exactly as the scene
 file ships (AAEnabled: the reference's fixed 5-tap anti-aliasing, Phong +
 shadow rays + bitmap textures + CSG) — the frame BASELINE.json's north_star
-target (>= 1 Gray/s at 4K on one MI355X) is quoted on.  The other BASELINE
-configs (1 tap, 1080p, zaphod, 8K) are measured in the same run and reported
-under config.other_workloads.
+target (>= 1 Gray/s at 4K on one MI355X) is quoted on.  With --full, the other
+BASELINE configs (1 tap, 1080p, zaphod, 8K) are measured in the same run and
+reported under config.other_workloads.
 N>1 (one process per GPU, launched by torch.distributed.run): WEAK scaling —
 the frame keeps its 16:9 shape and grows to N x the N=1 pixel count, ranks
 render interleaved 8-row strips and one RCCL gather per frame brings them to
 rank 0, where a copy kernel de-interleaves them.
 Frames are double-buffered: the gather of frame i runs on RCCL's stream while
 frame i+1 renders; all K frames are complete inside the timed region.
+
+A plain run sets up, warms up, times the K steps and prints the headline
+figure.  --full adds everything else this file measures or checks: the
+per-frame kernel time (HIP events, a pass of its own) and the rooflines built
+on it, the other workloads, the host-boundary, sustained and two-frames-in-
+flight legs, the CPU baseline, and at N>1 the phase probe, the render-only
+scaling and the check of the assembled frame.  --dump-outputs DIR writes the
+frame of the last timed step as .npy files (see dump_outputs).
 
 Prints ONE JSON line on rank 0.
 """
@@ -376,7 +384,7 @@ class FramePipe:
 
 
 def measure(torch, dist, pipe, steps, warmup, world, dev):
-    """W untimed + exactly K timed steps between barriers; max over ranks."""
+    """W untimed + exactly K timed steps between barriers; max over ranks.  Returns seconds for the K steps."""
     def barrier():
         if world > 1:
             dist.barrier()
@@ -411,6 +419,16 @@ def measure(torch, dist, pipe, steps, warmup, world, dev):
     el = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
+    return float(el.item())
+
+
+def kernel_events(torch, dist, pipe, steps, world, dev):
+    """(--full) Per-frame kernel time of the same steps, measured after the timed loop."""
+    def barrier():
+        if world > 1:
+            dist.barrier()
+        torch.cuda.synchronize(dev)
+
     # kernel time: a SEPARATE, untimed pass of the same steps with a HIP event pair on the launch stream around
     # every frame's launches (>= 20 of them).  A bracket holds everything a frame launches (the ~6 us tile-mask
     # pre-pass in front of the frame kernel, both launches of a nested-CSG frame) plus the dispatch latency behind
@@ -426,7 +444,38 @@ def measure(torch, dist, pipe, steps, warmup, world, dev):
               "max_ms": per_frame[-1], "frames": n_ev,
               "how": "separate untimed pass; one HIP event pair per frame on the launch stream, around all launches of the frame "
                      "(tile-mask pre-pass + frame kernel [+ nested-CSG retry launch]); includes the dispatch latency behind the start marker"}
-    return float(el.item()), kernel
+    return kernel
+
+
+DUMP_WHOLE_MAX_BYTES = 48 << 20   # a frame up to this size is written whole ...
+DUMP_SAMPLE_PIXELS = 1 << 21      # ... a larger one as this many pixels, chosen with a fixed seed
+DUMP_SEED = 20240607
+
+
+def dump_outputs(torch, np, pipe, width, height, out_dir):
+    """Writes the frame the last timed step produced (rank 0's assembled frame at N>1) to out_dir:
+    frame.npy, float32 (H, W, 3), when it fits DUMP_WHOLE_MAX_BYTES; otherwise frame_sample.npy, float32 (n, 3),
+    the pixels at the flat indices y * W + x in frame_sample_pixel.npy (float64, sorted), drawn once from
+    DUMP_SEED.  An RGB32 wire frame (--gather rgb32) is written as its packed words in float64."""
+    frame = pipe.local[0][:height] if pipe.world == 1 else pipe.frame
+    name = "frame_rgb32" if pipe.rgb32 else "frame"
+    ch = 3 if frame.dim() == 3 else 1
+    n_pix = width * height
+    out = {}
+    if n_pix * (12 if ch == 3 else 8) <= DUMP_WHOLE_MAX_BYTES:   # bytes as written: float32 RGB / float64 words
+        out[name] = frame.cpu().numpy()
+    else:
+        pix = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pix, DUMP_SAMPLE_PIXELS, replace=False))
+        idx = torch.from_numpy(pix).to(frame.device)
+        sample = frame.reshape(n_pix, ch)[idx].cpu().numpy()
+        out[name + "_sample"] = sample if ch == 3 else sample[:, 0]
+        out[name + "_sample_pixel"] = pix.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        if a.dtype.kind in "iu":
+            a = a.astype(np.float64)   # exact: words and pixel indices stay below 2^53
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(a))
+    return sorted(out)
 
 
 def measure_pipelined(torch, c2, ctx, scene, cam, opts, steps, warmup, dev):
@@ -627,8 +676,14 @@ def main():
     ap.add_argument("--exchange", default="gather", choices=["gather", "p2p"],
                     help="N>1: one RCCL gather + de-interleave pass on rank 0 (default), or one receive per remote strip "
                          "straight into its place in the frame (no gather buffer, no de-interleave pass)")
-    ap.add_argument("--no-check", action="store_true", help="N>1: skip comparing the first assembled frame with a single-rank render of the whole frame (bit-exact)")
-    ap.add_argument("--check", action="store_true", help="(default since round 3; kept for old command lines)")
+    ap.add_argument("--no-check", action="store_true", help="N>1, with --full: skip comparing the first assembled frame with a single-rank render of the whole frame (bit-exact)")
+    ap.add_argument("--check", action="store_true", help="N>1: compare the assembled frame with a single-rank render even without --full")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beside the headline figure (kernel events and rooflines, other workloads, "
+                         "host boundary, sustained and two-frames-in-flight legs, CPU baseline; N>1: phases, render-only scaling, "
+                         "frame check, strong-scaling frame); the --no-* options above trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the frame of the last one to DIR as .npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -677,7 +732,7 @@ def main():
 
     ctx = c2.Context(local_rank)
 
-    def run(workload, steps, warmup, scaling=None):
+    def run(workload, steps, warmup, scaling=None, dump_dir=None):
         scene_file, w0, h0, taps, dof = WORKLOADS[workload]
         width, height = (weak_frame(w0, h0, world) if (scaling or args.scaling) == "weak" else (w0, h0))
         scene = c2.parseSceneFromFile(os.path.join(SCENES, scene_file))
@@ -706,17 +761,24 @@ def main():
         pipe = FramePipe(torch, dist, c2, ctx, scene, cam, taps, width, height, world, rank, strip_height, dev,
                          not args.no_overlap, args.backend, gather_format, args.exchange)
         primary, shadow = count_rays(torch, dist, ctx, scene, cam, pipe, taps, world, rank, dev)
-        elapsed, kernel = measure(torch, dist, pipe, steps, warmup, world, dev)
-        # ONE figure for the kernel time everywhere below (roofline.*, boundary_ms, other_workloads): the event mean,
-        # which at N=1 cannot exceed the wall clock of the event-free timed loop — the frames of that loop ARE these
-        # launches back to back — so it is clamped there and the raw figures stay in kernel_events
-        kernel_ms = kernel["mean_ms"]
-        if world == 1 and kernel_ms > elapsed / steps * 1e3:
-            kernel["clamped_to_ms_per_step"] = True
-            kernel_ms = elapsed / steps * 1e3
-        phases = phase_probe(torch, dist, pipe, world, dev) if world > 1 else None
-        render_only = None
-        if world > 1:
+        elapsed = measure(torch, dist, pipe, steps, warmup, world, dev)
+        dumped = None
+        if dump_dir and rank == 0:
+            import numpy as np
+
+            dumped = dump_outputs(torch, np, pipe, width, height, dump_dir)   # before anything renders into the buffers again
+        kernel = kernel_ms = phases = render_only = pipelined = None
+        if args.full:
+            kernel = kernel_events(torch, dist, pipe, steps, world, dev)
+            # ONE figure for the kernel time everywhere below (roofline.*, boundary_ms, other_workloads): the event mean,
+            # which at N=1 cannot exceed the wall clock of the event-free timed loop — the frames of that loop ARE these
+            # launches back to back — so it is clamped there and the raw figures stay in kernel_events
+            kernel_ms = kernel["mean_ms"]
+            if world == 1 and kernel_ms > elapsed / steps * 1e3:
+                kernel["clamped_to_ms_per_step"] = True
+                kernel_ms = elapsed / steps * 1e3
+        if world > 1 and args.full:
+            phases = phase_probe(torch, dist, pipe, world, dev)
             # compute scaling apart from the exchange (round-3 verdict, item 7b): the kernel time of the slowest rank's
             # strips against ONE GPU (rank 0) rendering the whole frame of this size alone, both by HIP events
             t = torch.tensor([kernel_ms], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
@@ -741,14 +803,13 @@ def main():
                            "render_only_speedup": float(one.item()) / max_rank_ms if max_rank_ms > 0 else None,
                            "note": "kernel time only, no exchange: one GPU rendering this whole frame alone / the slowest rank's strips; "
                                    "`value` and ms_per_step include the exchange"}
-        pipelined = None
-        if world == 1 and not args.no_pipelined:
+        if world == 1 and args.full and not args.no_pipelined:
             # (at least ~50 ms of frames: a 20-frame burst of 0.09 ms frames measures its own ramp)
             psteps = max(steps, min(500, int(0.05 / max(elapsed / steps, 1e-6))))
             pipelined = measure_pipelined(torch, c2, ctx, scene, cam, pipe.opts, psteps, warmup, dev) * steps / psteps
         return dict(scene=scene, cam=cam, pipe=pipe, scene_file=scene_file, width=width, height=height, taps=taps, dof=dof,
                     primary=primary, shadow=shadow, elapsed=elapsed, kernel_ms=kernel_ms, kernel_events=kernel, steps=steps, phases=phases,
-                    calib=calib, pipelined=pipelined, render_only=render_only)
+                    calib=calib, pipelined=pipelined, render_only=render_only, dumped=dumped)
 
     def check_frame(r):
         """N>1: the frame rank 0 assembled from every rank's strips must equal rank 0's own render of the WHOLE
@@ -771,13 +832,13 @@ def main():
             raise SystemExit("bench.py: the frame assembled from %d ranks differs from the single-rank frame" % world)
         return "assembled frame == rank 0's own render of the whole frame, bit for bit"
 
-    r = run(args.workload, args.steps, args.warmup)
+    r = run(args.workload, args.steps, args.warmup, dump_dir=args.dump_outputs)
     frame_check = None
-    if world > 1 and not args.no_check:
+    if world > 1 and (args.full or args.check) and not args.no_check:
         frame_check = check_frame(r)
 
     others = {}
-    if world > 1 and not args.no_others and not (args.workload == "lecture5_8k_4spp" and args.scaling == "strong"):
+    if world > 1 and args.full and not args.no_others and not (args.workload == "lecture5_8k_4spp" and args.scaling == "strong"):
         # BASELINE config 5 itself: data/lecture5.sdl at 7680x4320 x4, ONE frame sharded over the ranks (strong scaling)
         o = run("lecture5_8k_4spp", min(args.steps, 20), min(args.warmup, 3), scaling="strong")
         rays = o["primary"] + o["shadow"]
@@ -792,7 +853,7 @@ def main():
             "frame_check": check_frame(o) if not args.no_check else None,
         }
         del o
-    if world == 1 and not args.no_others:
+    if world == 1 and args.full and not args.no_others:
         for name in WORKLOADS:
             if name == args.workload:
                 continue
@@ -818,7 +879,7 @@ def main():
         ctx.uploadScene(r["scene"].desc)
 
     boundary = None
-    if world == 1 and rank == 0 and not args.no_boundary:
+    if world == 1 and rank == 0 and args.full and not args.no_boundary:
         import numpy as np
 
         try:
@@ -826,11 +887,10 @@ def main():
         except Exception as e:  # noqa: BLE001
             print("bench.py: host-output timings skipped (%s)" % e, file=sys.stderr)
 
-    if rank == 0:
+    def full_legs(out, r, rays_per_frame, ms_per_step, others, boundary):
+        """(--full) Adds to the result line what lies beside the headline figure: kernel time, rooflines, the other
+        workloads and legs measured above, and those measured here (sustained, CPU baseline)."""
         scene, pipe = r["scene"], r["pipe"]
-        rays_per_frame = r["primary"] + r["shadow"]
-        ms_per_step = r["elapsed"] / r["steps"] * 1e3
-        value = rays_per_frame * r["steps"] / r["elapsed"] / 1e6
         # algorithmic HBM bytes of one launch (SURVEY 8(d)): 12 B per pixel written + every bitmap texel once
         tex_bytes = int(scene.desc.contents.n_texels) * 12
         alg_bytes = pipe.my_rows * r["width"] * 12 + tex_bytes
@@ -853,61 +913,24 @@ def main():
                         prof_data.get("kernel_source_hash", "unknown (round-1 profile)"), khash)
             except Exception as e:  # noqa: BLE001
                 profile_state = "unreadable: %s" % e
-        out = {
-            "metric": "Mray/s (reference-equivalent rays per second: one primary ray per sample + one shadow ray per "
-                      "(hit, lit light), counted as the reference casts them; ms/frame in ms_per_step)",
-            "value": value,
-            "unit": "Mray/s",
-            "n_gpus": world,
-            "steps": r["steps"],
-            "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic: the reference's own scene file and textures (tests/golden/scenes), fixed camera",
-            "config": {
-                "workload": "%s %dx%d, %d tap(s)/pixel%s, dof %s%s" % (
-                    r["scene_file"], r["width"], r["height"], r["taps"],
-                    " (AAEnabled as shipped: reference 5-tap AA)" if r["taps"] == 5 else "",
-                    "on" if r["dof"] else "off",
-                    "" if world == 1 else "; %d ranks x interleaved %d-row strips + %s to rank 0 (%s, %s strips)" % (
-                        world, pipe.plan.strip_height,
-                        "per-strip RCCL send/recv into place" if pipe.p2p else "RCCL gather", "double-buffered" if pipe.overlap else "serial",
-                        "RGB32-encoded" if pipe.rgb32 else "float RGB")),
-                "name": args.workload,
-                "primary_rays_per_frame": r["primary"],
-                "shadow_rays_per_frame": r["shadow"],
-                "Msample_per_s": r["primary"] * r["steps"] / r["elapsed"] / 1e6,
-                "frames_per_s": r["steps"] / r["elapsed"],
-                "kernel_ms_rank0": r["kernel_ms"],
-                "kernel_events": r["kernel_events"],
-                "settle": "untimed frames in front of the W warm-up steps of every measurement (GPU clocks and queues back from idle): ~40 ms of them at N = 1, 16 frames at N > 1; W and K as asked",
-                "other_workloads": others,
-            },
-            "roofline": {
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "traffic": traffic,
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "kernel_ms": r["kernel_ms"],
-                "pmc_profile": profile_state,
-                "note": "by the numbers this path is fp64-VALU bound, not HBM bound (DESIGN.md 4.1): 12 B/pixel is all it must move",
-            },
+        out["config"]["kernel_ms_rank0"] = r["kernel_ms"]
+        out["config"]["kernel_events"] = r["kernel_events"]
+        out["config"]["other_workloads"] = others
+        out["roofline"] = {
+            "bound": "hbm",
+            "achieved": achieved,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS,
+            "traffic": traffic,
+            "algorithmic_bytes_per_launch": alg_bytes,
+            "kernel_ms": r["kernel_ms"],
+            "pmc_profile": profile_state,
+            "note": "by the numbers this path is fp64-VALU bound, not HBM bound (DESIGN.md 4.1): 12 B/pixel is all it must move",
         }
         if world > 1:
-            out["config"]["ranks_seen_by_collective"] = ranks_seen
-            out["config"]["devices"] = devices
             out["config"]["phases_ms"] = r["phases"]
             out["config"]["render_only"] = r["render_only"]
-            out["config"]["wire_format"] = "rgb32" if pipe.rgb32 else "float"
-            out["config"]["frame_check"] = frame_check
-            if r["calib"]:
-                out["config"]["wire_format_calibration"] = r["calib"]
         if boundary:
             # kernel-only / host float frame / host display frame, ms per frame (the reference's renderRT boundary is the host one)
             out["config"]["boundary_ms"] = dict(kernel_only_ms=r["kernel_ms"], **boundary)
@@ -952,6 +975,56 @@ def main():
                 }
         if world == 1 and not (r["kernel_ms"] <= ms_per_step * (1 + 1e-9)):
             raise SystemExit("bench.py: kernel_ms %.6f > ms_per_step %.6f — the line would contradict itself" % (r["kernel_ms"], ms_per_step))
+
+    if rank == 0:
+        pipe = r["pipe"]
+        rays_per_frame = r["primary"] + r["shadow"]
+        ms_per_step = r["elapsed"] / r["steps"] * 1e3
+        value = rays_per_frame * r["steps"] / r["elapsed"] / 1e6
+        out = {
+            "metric": "Mray/s (reference-equivalent rays per second: one primary ray per sample + one shadow ray per "
+                      "(hit, lit light), counted as the reference casts them; ms/frame in ms_per_step)",
+            "value": value,
+            "unit": "Mray/s",
+            "n_gpus": world,
+            "steps": r["steps"],
+            "warmup": args.warmup,
+            "ms_per_step": ms_per_step,
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic: the reference's own scene file and textures (tests/golden/scenes), fixed camera",
+            "config": {
+                "workload": "%s %dx%d, %d tap(s)/pixel%s, dof %s%s" % (
+                    r["scene_file"], r["width"], r["height"], r["taps"],
+                    " (AAEnabled as shipped: reference 5-tap AA)" if r["taps"] == 5 else "",
+                    "on" if r["dof"] else "off",
+                    "" if world == 1 else "; %d ranks x interleaved %d-row strips + %s to rank 0 (%s, %s strips)" % (
+                        world, pipe.plan.strip_height,
+                        "per-strip RCCL send/recv into place" if pipe.p2p else "RCCL gather", "double-buffered" if pipe.overlap else "serial",
+                        "RGB32-encoded" if pipe.rgb32 else "float RGB")),
+                "name": args.workload,
+                "primary_rays_per_frame": r["primary"],
+                "shadow_rays_per_frame": r["shadow"],
+                "Msample_per_s": r["primary"] * r["steps"] / r["elapsed"] / 1e6,
+                "frames_per_s": r["steps"] / r["elapsed"],
+                "settle": "untimed frames in front of the W warm-up steps of every measurement (GPU clocks and queues back from idle): ~40 ms of them at N = 1, 16 frames at N > 1; W and K as asked",
+                "full": args.full,
+            },
+        }
+        if world > 1:
+            out["config"]["ranks_seen_by_collective"] = ranks_seen
+            out["config"]["devices"] = devices
+            out["config"]["wire_format"] = "rgb32" if pipe.rgb32 else "float"
+            out["config"]["frame_check"] = frame_check
+            if r["calib"]:
+                out["config"]["wire_format_calibration"] = r["calib"]
+        if r["dumped"]:
+            out["outputs"] = {"dir": args.dump_outputs, "files": [k + ".npy" for k in r["dumped"]],
+                              "what": "the frame of the last timed step (rank 0's assembled frame at N > 1), whole or a seeded sample of pixels"}
+        if args.full:
+            full_legs(out, r, rays_per_frame, ms_per_step, others, boundary)
         print(json.dumps(out), flush=True)
 
     if world > 1:

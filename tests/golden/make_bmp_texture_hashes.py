@@ -3,11 +3,11 @@
 SURVEY.md 8(f3); the three that scenes of tests/golden/scenes use are committed there already) with the host
 decoder (the C++ mirror of imageio/bmp.d:60-193 behind c2rt_host_bmp_decode) and records, per file, the SHA-256
 of the FILE (so that the test knows it is looking at the same input), its header fields and the SHA-256 of the
-decoded float32 (H, W, 3) array.  Run in the build container, where /root/reference exists:
-    python tests/golden/make_bmp_texture_hashes.py > tests/golden/bmp_texture_hashes.json
-The BMP files themselves stay in /root/reference (5 MB of data the parity suite does not need on the GPU box)."""
+decoded float32 (H, W, 3) array.  The files are committed xz-compressed under tests/golden/textures/:
+    python tests/golden/make_bmp_texture_hashes.py > tests/golden/bmp_texture_hashes.json"""
 import hashlib
 import json
+import lzma
 import os
 import struct
 import sys
@@ -19,11 +19,12 @@ import chess2rt_amd as c2  # noqa: E402
 import oracle_lib as orc  # noqa: E402
 import numpy as np  # noqa: E402
 
-DIR = "/root/reference/data/texture"
+DIR = os.path.join(ROOT, "tests", "golden", "textures")
 FILES = ["heightfield.bmp", "hf_color.bmp", "lava.bmp", "wood.bmp", "zar-bump.bmp", "zar-texture.bmp"]
 out = {"source_dir": "data/texture (reference repository)", "files": {}}
 for f in FILES:
-    data = open(os.path.join(DIR, f), "rb").read()
+    with lzma.open(os.path.join(DIR, f + ".xz"), "rb") as fh:
+        data = fh.read()
     w, h = struct.unpack_from("<ii", data, 18)
     bpp, = struct.unpack_from("<H", data, 28)
     img = c2.loadBmpImage(data)

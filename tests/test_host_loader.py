@@ -211,17 +211,17 @@ def test_bmp_decode_of_the_references_other_textures(golden_dir):
     """data/texture/{heightfield (8-bpp), hf_color, wood, zar-bump, zar-texture (24-bpp), lava
     (32-bpp)}.bmp through the host decoder (imageio/bmp.d:60-193 mirrored) and the oracle's: equal each other and
     equal the committed SHA-256 of the decoded float frame (tests/golden/make_bmp_texture_hashes.py).  The files
-    are read where the reference keeps them; they exist in the build container only."""
+    are committed xz-compressed under tests/golden/textures/."""
     import hashlib
+    import lzma
 
     fx = json.load(open(os.path.join(golden_dir, "bmp_texture_hashes.json")))["files"]
-    src = "/root/reference/data/texture"
-    if not os.path.isdir(src):
-        pytest.skip("the reference's texture files are not on this machine")
+    src = os.path.join(golden_dir, "textures")
     assert sorted(fx) == ["heightfield.bmp", "hf_color.bmp", "lava.bmp", "wood.bmp", "zar-bump.bmp", "zar-texture.bmp"]
     assert {e["bpp"] for e in fx.values()} == {8, 24, 32}
     for f, e in fx.items():
-        data = open(os.path.join(src, f), "rb").read()
+        with lzma.open(os.path.join(src, f + ".xz"), "rb") as fh:
+            data = fh.read()
         assert hashlib.sha256(data).hexdigest() == e["file_sha256"], f
         a = c2.loadBmpImage(data)
         b, _ = orc.bmp_decode(data)
