@@ -95,6 +95,9 @@ struct c2rt_ctx {
     std::vector<double> node_box;  /* [n_nodes][8][3] */
     std::vector<double> light_pos; /* [n_lights][3] host copy for the per-frame shadow-cull thresholds */
     std::vector<uint8_t> node_boxed;
+    /* CsgDiff(primitive, Sphere) nodes under an identity matrix (translation allowed): the per-tile void test of the
+     * mask pre-pass (csg_void.h); VoidNode::r2 holds R here, the frame's margin is applied in void_cull_of */
+    std::vector<VoidNode> void_nodes;
 
     float *frame = nullptr;        /* staging frame for host-output renders */
     size_t frame_floats = 0;
@@ -610,8 +613,27 @@ int prepare_tile_masks(c2rt_ctx *ctx, RenderParams &p, const KernelVariant &v, h
         sc.tile_mask_entries = entries;
     }
     p.tile_masks = sc.tile_masks;
+    /* the void test's per-frame part: the ball's margin at this frame's scale (csg_void.h: void_margin) */
+    VoidCull vc{};
+    for (const VoidNode &seed : ctx->void_nodes) {
+        if (seed.node >= p.n_cull) continue;
+        VoidNode v = seed;
+        const double R = seed.r2;
+        double scale = R;
+        scale += std::max(std::fabs(v.c[0]), std::max(std::fabs(v.c[1]), std::fabs(v.c[2])));
+        scale += std::max(std::fabs(p.cam.pos[0]), std::max(std::fabs(p.cam.pos[1]), std::fabs(p.cam.pos[2])));
+        if (!ctx->light_pos.empty())
+            scale += std::max(std::fabs(ctx->light_pos[0]), std::max(std::fabs(ctx->light_pos[1]), std::fabs(ctx->light_pos[2])));
+        const double rm = R - void_margin(scale);
+        if (!(rm > 0) || !std::isfinite(scale)) continue;
+        v.r2 = rm * rm;
+        if (p.n_cull_lights == 0 || p.ground_node < 0) v.flags &= ~2u;
+        vc.v[vc.n++] = v;
+    }
+    if (!ctx->light_pos.empty())
+        for (int j = 0; j < 3; ++j) vc.light0[j] = ctx->light_pos[j];
     p.mask_entries = (uint32_t)entries;
-    return launch_tile_masks(p, sc.tile_masks, stream);
+    return launch_tile_masks(p, vc, sc.tile_masks, stream);
 }
 
 /* One frame launch.  Scenes with nested CsgOps (depth >= 2) run the kernel with a reduced hit-stack
@@ -1154,6 +1176,48 @@ static int upload_one(c2rt_ctx *ctx, const c2rt_scene_desc *s)
         }
         int st0;
         if ((st0 = upload(ctx, &ctx->shadow_rects, rects)) != C2RT_OK) return st0;
+    }
+
+    /* CsgDiff(L, Sphere) nodes whose tiles the pre-pass may find void (csg_void.h): L a Cube or a Sphere other than
+     * the subtracted one, the node's matrix the identity (its offset moves box and sphere alike), a finite sphere
+     * of positive radius.  Shadow test towards light 0 only where the ground refinement runs and the box lies
+     * strictly between the ground's side of the light's height and the light (no shadow ray meets it after
+     * passing the light). */
+    ctx->void_nodes.clear();
+    for (uint32_t n = 0; n < s->n_nodes && n < (uint32_t)kMaxCullNodes && ctx->void_nodes.size() < (size_t)kMaxVoidNodes; ++n) {
+        const DevNode &d = nodes[n];
+        if (!ctx->node_boxed[n] || !(d.flags & kNodeIdentityMatrix) || d.g.type != C2RT_GEOM_CSG_DIFF) continue;
+        const int32_t l = s->geom_child[2 * d.geom], r = s->geom_child[2 * d.geom + 1];
+        if (l == r || s->geom_type[r] != C2RT_GEOM_SPHERE) continue;
+        if (s->geom_type[l] != C2RT_GEOM_CUBE && s->geom_type[l] != C2RT_GEOM_SPHERE) continue;
+        if (!(geoms[l].flags & kGeomFinite) || !(geoms[r].flags & kGeomFinite)) continue;
+        const double *sp = s->geom_param + 4 * (size_t)r;
+        if (!(sp[3] > 0)) continue;
+        VoidNode v{};
+        for (int j = 0; j < 3; ++j) { v.lo[j] = HUGE_VAL; v.hi[j] = -HUGE_VAL; }
+        for (int k = 0; k < 8; ++k)
+            for (int j = 0; j < 3; ++j) {
+                const double w = ctx->node_box[((size_t)n * 8 + k) * 3 + j];
+                v.lo[j] = std::min(v.lo[j], w);
+                v.hi[j] = std::max(v.hi[j], w);
+            }
+        bool finite = true;
+        for (int j = 0; j < 3; ++j) {
+            v.c[j] = sp[j] + d.off[j];
+            finite = finite && std::isfinite(v.c[j]) && std::isfinite(v.lo[j]) && std::isfinite(v.hi[j]);
+        }
+        if (!finite) continue;
+        v.r2 = sp[3];
+        v.node = n;
+        v.flags = 1u;
+        if (ctx->ground_node >= 0 && s->n_lights > 0) {
+            const double *L = s->light_pos, gy = ctx->ground_y, h = L[1] - gy;
+            const double tol = 1e-6 + 1e-9 * (std::fabs(L[1]) + std::fabs(v.lo[1]) + std::fabs(v.hi[1]));
+            if (std::isfinite(L[0]) && std::isfinite(L[1]) && std::isfinite(L[2]) && std::isfinite(h) &&
+                ((h > 0 && v.hi[1] < L[1] - tol) || (h < 0 && v.lo[1] > L[1] + tol)))
+                v.flags |= 2u;
+        }
+        ctx->void_nodes.push_back(v);
     }
 
     int st;

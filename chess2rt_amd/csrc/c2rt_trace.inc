@@ -1166,7 +1166,7 @@ DEV uint32_t light_shadow_mask(const RenderParams &P, uint32_t mask_slot, uint32
     return ((const uint32_t C2RT_K *)P.tile_masks)[((size_t)P.mask_entries + mask_slot) * 4u + (l - 1u)];
 }
 
-DEV void tile_mask_entry(const RenderParams &P, KArgs K, uint32_t trow, uint32_t tcol, uint32_t out[8])
+DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, uint32_t trow, uint32_t tcol, uint32_t out[8])
 {
     typedef const int C2RT_K *KInt;
     typedef const char C2RT_K *KChar;
@@ -1213,6 +1213,18 @@ DEV void tile_mask_entry(const RenderParams &P, KArgs K, uint32_t trow, uint32_t
             }
         }
         if (rect_misses || off_hull) pmask &= ~(1u << n);
+        else if (V.n) {
+            /* a CsgDiff(L, Sphere) node that no primary ray of the tile can hit (csg_void.h): only for tiles whose
+             * rectangle and hull keep it */
+            for (uint32_t j = 0; j < V.n; ++j) {
+                const VoidNode &vn = V.v[j];
+                if (vn.node != n || !(vn.flags & 1u)) continue;
+                double cdir[4][3];
+                tile_corner_dirs(P.cam.pos, P.cam.up_left, P.cam_du, P.cam_dv, P.cam.frame_width, P.cam.frame_height,
+                                 tx0, tx0 + kTileW, ty0, ty1 + 1, cdir);
+                if (pyramid_void(P.cam.pos, cdir, vn)) pmask &= ~(1u << n);
+            }
+        }
         if (shadow_cull && ((in_left && r2 <= tx0) || (in_right && r0 >= sx1) || (in_top && r3 <= ty0) || (in_bottom && r1 >= sy1)))
             smask0 &= ~(1u << n);
     }
@@ -1251,6 +1263,14 @@ DEV void tile_mask_entry(const RenderParams &P, KArgs K, uint32_t trow, uint32_t
             for (uint32_t n = 0; n < nc; ++n) {
                 KDbl sr = rects_s + 4 * n;
                 if ((sr[1] < fx0 - padx) | (sr[0] > fx1 + padx) | (sr[3] < fz0 - padz) | (sr[2] > fz1 + padz)) smask0 &= ~(1u << n);
+            }
+            /* a CsgDiff(L, Sphere) node that no shadow ray towards light 0 from the footprint can hit (csg_void.h) */
+            for (uint32_t j = 0; j < V.n; ++j) {
+                const VoidNode &vn = V.v[j];
+                if (!((smask0 >> vn.node) & 1u) || !(vn.flags & 2u)) continue;
+                double sdir[4][3];
+                footprint_dirs(V.light0, gy, fx0, fx1, fz0, fz1, sdir);
+                if (pyramid_void(V.light0, sdir, vn)) smask0 &= ~(1u << vn.node);
             }
         }
         ground_only = (smask0 & (0xFFFFFFFFu >> (32u - nn))) == (1u << gnode);

@@ -1,0 +1,169 @@
+/*
+ * csg_void.h — per-tile "void" test for a CsgDiff(L, Sphere) node: the tile's rays provably get no hit on it.
+ * Shared by the mask pre-pass (c2rt_trace.inc: tile_mask_entry), the host that fills VoidCull
+ * (c2rt_api.cpp: prepare_tile_masks) and the host check library of the tests (tests/csg_void_check.cpp).
+ *
+ * Why a void ray gets no hit: CsgOp.intersect for Diff(L, R) (rt/geometry.d:292-332), R a Sphere.  Suppose that
+ * for one ray (1) findAllIntersections(R) yields exactly two hits R0 < R1, or one hit R1 with the origin inside
+ * the sphere, and (2) every hit of L, however many (grazing included), has a distance strictly inside (R0, R1)
+ * (resp. (0, R1)).  The walk starts with inR = (|R| odd): false before R0 / true from the origin; the first sorted
+ * event is R0 (or an L event while inR is already true), so inR is true at every L event and boolOp = inL && !inR
+ * stays false.  At R1 inL has been flipped |L| times from (|L| odd), so it is false, and the walk ends with no hit.
+ * No tie and no leaf-identity question arises: the L distances lie strictly between the R events.
+ *
+ * Sufficient condition for a whole tile: every point of box(L) inside the set the tile's rays sweep lies in the
+ * ball B(c, R - m).  Every L hit point is in box(L) (the padded world box, c2rt_api.cpp) on one of the rays, so it
+ * lies at least m inside the sphere, and the ray passes at least sqrt(2 R m) inside the sphere's rim: R0 and R1
+ * are far from a tangent, and the three 1e-6 steps of findAllIntersections (which shorten the recorded distances
+ * by at most 3e-6) and fp64 rounding of the distances (relative 1e-15 at the scene's scale, amplified by at most
+ * scale / sqrt(2 R m)) keep every L distance strictly between R0 and R1.  m = 1e-5 + 1e-6 * scale covers both
+ * with orders of magnitude to spare (void_margin).
+ *
+ * The swept set is a pyramid {apex + sum_k s_k dir_k, s_k >= 0} with four edge directions in cyclic order:
+ *  - primary rays: apex = eye, edges = the tile's corner rays widened by 1 px (the AA taps reach 0.6 px), exactly
+ *    the rays of the ground footprint (tile_mask_entry);
+ *  - shadow rays towards light 0 of a ground tile: they start within 1e-6 of the tile's footprint quad on the
+ *    ground and end at the light; the pyramid with apex = light through the padded footprint rectangle holds
+ *    them up to the light.  Beyond the light a shadow ray is outside that pyramid — its L hits there would break
+ *    the parity in (2) — so the shadow test requires the box to lie strictly on the ground's side of the light's
+ *    height (VoidNode::flags bit 1, host), where no ray continues after passing the light.
+ * box ∩ pyramid is bounded by a thick segment around the pyramid's axis (pyramid_void), which must lie in the ball.
+ */
+#ifndef C2RT_CSG_VOID_H
+#define C2RT_CSG_VOID_H
+
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define C2RT_VOID_FN __host__ __device__ inline
+#else
+#define C2RT_VOID_FN inline
+#endif
+
+namespace c2rt {
+
+constexpr int kMaxVoidNodes = 4; /* CsgDiff(L, Sphere) nodes tested per frame (the first ones among the culled) */
+
+struct VoidNode {
+    double lo[3], hi[3];           /* padded world box of the node (node_box: identity matrix => axis-aligned) */
+    double c[3];                   /* the subtracted sphere's world centre (object centre + node offset) */
+    double r2;                     /* (R - m)^2, m = void_margin */
+    uint32_t node;                 /* node index (< kMaxCullNodes) */
+    uint32_t flags;                /* bit 0: primary test; bit 1: shadow test towards light 0 (see above) */
+};
+
+/* the per-frame argument of the mask pre-pass (tile_masks_kernel) */
+struct VoidCull {
+    uint32_t n, pad;
+    double light0[3];              /* light 0 (the shadow pyramid's apex) */
+    VoidNode v[kMaxVoidNodes];
+};
+
+C2RT_VOID_FN double void_abs(double x) { return x < 0 ? -x : x; }
+
+/* margin of the ball for coordinates of magnitude up to `scale` (sum of |centre|, R, |eye|, |light| max-norms) */
+C2RT_VOID_FN double void_margin(double scale) { return 1e-5 + 1e-6 * scale; }
+
+/* true if every point of box(v) inside the pyramid (apex, dir[0..3]) lies in the ball (c, sqrt(r2)): the rays of the
+ * pyramid get no hit on the node (header comment).  false = keep the node.
+ *
+ * The test bounds box ∩ pyramid by a thick segment (a vertex enumeration of the polytope is exact but ~20x the
+ * work, a latency chain the single-lane-per-tile pre-pass cannot hide).  u = the pyramid's axis (unit), tan_t =
+ * max over the four edges of lateral / axial component: the circular cone of that half angle around u is convex
+ * and holds the four edges, hence the pyramid.  A point p of the pyramid at depth t = (p - apex).u is within
+ * rho(t) = t tan_t of q = apex + t u.  If p is also in the box, t <= t_far (the deepest box corner) and q lies in
+ * the box grown by rho = t_far tan_t on every axis, so on the axis' slab interval [t0, t1] of that grown box.  The
+ * ball is convex: both ends of that segment within R - m - rho of c put the segment there, and every such p
+ * within R - m.  The apex in the grown box, an empty or non-finite interval, or a pyramid of 90 degrees or more
+ * (an edge with axial component <= 0) refuse. */
+C2RT_VOID_FN bool pyramid_void(const double apex[3], const double dir[4][3], const VoidNode &v)
+{
+    double u[3] = {0, 0, 0};
+    for (int k = 0; k < 4; ++k) {
+        const double l2 = dir[k][0] * dir[k][0] + dir[k][1] * dir[k][1] + dir[k][2] * dir[k][2];
+        const double il = 1.0 / sqrt(l2);
+        for (int i = 0; i < 3; ++i) u[i] += dir[k][i] * il;
+    }
+    {
+        const double il = 1.0 / sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+        for (int i = 0; i < 3; ++i) u[i] *= il;
+    }
+    double tan_t = 0;
+    for (int k = 0; k < 4; ++k) {
+        const double a = dir[k][0] * u[0] + dir[k][1] * u[1] + dir[k][2] * u[2];
+        const double e0 = dir[k][0] - a * u[0], e1 = dir[k][1] - a * u[1], e2 = dir[k][2] - a * u[2];
+        const double lat = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+        if (!(a > 0)) return false;
+        const double t = lat / a;
+        tan_t = t > tan_t ? t : tan_t;
+    }
+    double t_far = 0;
+    for (int q = 0; q < 8; ++q) {
+        const double t = ((q & 1) ? v.hi[0] : v.lo[0]) * u[0] - apex[0] * u[0] + ((q & 2) ? v.hi[1] : v.lo[1]) * u[1] -
+                         apex[1] * u[1] + ((q & 4) ? v.hi[2] : v.lo[2]) * u[2] - apex[2] * u[2];
+        t_far = t > t_far ? t : t_far;
+    }
+    /* rounding of u, tan_t and t_far: relative 1e-15 each; 1e-9 relative and an absolute 1e-9 to spare */
+    const double rho = t_far * tan_t * (1 + 1e-9) + 1e-9 * t_far;
+    double t0 = 0, t1 = 1e300;
+    bool apex_in = true;
+    for (int i = 0; i < 3; ++i) {
+        const double lo = v.lo[i] - rho, hi = v.hi[i] + rho;
+        apex_in = apex_in && apex[i] >= lo && apex[i] <= hi;
+        if (u[i] == 0) {
+            if (!(apex[i] >= lo && apex[i] <= hi)) return false; /* parallel and outside: the pyramid misses the box */
+        } else {
+            double ta = (lo - apex[i]) / u[i], tb = (hi - apex[i]) / u[i];
+            if (ta > tb) { const double x = ta; ta = tb; tb = x; }
+            t0 = ta > t0 ? ta : t0;
+            t1 = tb < t1 ? tb : t1;
+        }
+    }
+    if (apex_in || !(t0 <= t1) || !(t1 < 1e300)) return false;
+    const double r = sqrt(v.r2) - rho;
+    if (!(r > 0)) return false;
+    bool ok = true;
+    for (int e = 0; e < 2; ++e) {
+        const double t = e ? t1 : t0;
+        const double d0 = apex[0] + u[0] * t - v.c[0], d1 = apex[1] + u[1] * t - v.c[1], d2 = apex[2] + u[2] * t - v.c[2];
+        ok = ok && d0 * d0 + d1 * d1 + d2 * d2 <= r * r * (1 - 1e-12);
+    }
+    return ok;
+}
+
+/* One tile's primary pyramid: the eye and the four corner rays of the pixel rectangle [x0 - 1, x1 + 1] x
+ * [y0 - 1, y1 + 1] (x1 = tx0 + kTileW, y1 = ty1 + 1: the tile's right / bottom pixel edges), in cyclic order —
+ * the same directions as tile_mask_entry's ground footprint. */
+C2RT_VOID_FN void tile_corner_dirs(const double pos[3], const double ul[3], const double du[3], const double dv[3],
+                                   double fw, double fh, int tx0, int tx1, int ty0, int ty1p1, double dir[4][3])
+{
+    for (int k = 0; k < 4; ++k) {
+        const bool right = k == 1 || k == 2, bottom = k >= 2;
+        const double sx = right ? (double)(tx1 + 1) : (double)(tx0 - 1);
+        const double sy = bottom ? (double)(ty1p1 + 1) : (double)(ty0 - 1);
+        const double cfx = sx / fw, cfy = sy / fh;
+        for (int i = 0; i < 3; ++i) dir[k][i] = ul[i] + du[i] * cfx + dv[i] * cfy - pos[i];
+    }
+}
+
+/* One ground tile's shadow pyramid towards light `L`: apex L, edges through the corners of the footprint rectangle
+ * [fx0, fx1] x [fz0, fz1] on the plane y = gy, grown by the shadow origins' 1e-6 offset along the normal seen
+ * from the light (1e-6 * horizontal / vertical extent) with a factor 10 to spare. */
+C2RT_VOID_FN void footprint_dirs(const double L[3], double gy, double fx0, double fx1, double fz0, double fz1, double dir[4][3])
+{
+    const double h = void_abs(L[1] - gy);
+    const double ext = void_abs(fx0 - L[0]) + void_abs(fx1 - L[0]) + void_abs(fz0 - L[2]) + void_abs(fz1 - L[2]);
+    const double pad = 1e-5 * (1.0 + ext / h) + 1e-9 * (void_abs(fx0) + void_abs(fx1) + void_abs(fz0) + void_abs(fz1));
+    const double x0 = fx0 - pad, x1 = fx1 + pad, z0 = fz0 - pad, z1 = fz1 + pad;
+    for (int k = 0; k < 4; ++k) {
+        const bool hx = k == 1 || k == 2, hz = k >= 2;
+        dir[k][0] = (hx ? x1 : x0) - L[0];
+        dir[k][1] = gy - L[1];
+        dir[k][2] = (hz ? z1 : z0) - L[2];
+    }
+}
+
+} // namespace c2rt
+
+#endif
