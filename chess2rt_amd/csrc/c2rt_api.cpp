@@ -595,25 +595,11 @@ FrameScratch &scratch_for(c2rt_ctx *ctx, hipStream_t stream)
     return *pick;
 }
 
-/* The tiles' culling masks for the local rows [p.row_offset, p.row_offset + p.local_rows), by the pre-pass kernel,
- * in front of the frame kernel on the same stream (one table per stream of the context: FrameScratch).  Sets p.tile_masks / mask_row0 / mask_rows; a no-op for frames without culling rectangles.
- * Returns a hipError_t. */
-int prepare_tile_masks(c2rt_ctx *ctx, RenderParams &p, const KernelVariant &v, hipStream_t stream)
+/* the void test's per-frame part (csg_void.h): the ball's margin at this frame's scale (void_margin), the nodes the
+ * frame culls, the shadow test only where the frame runs the ground refinement towards light 0.  flags_mask: every
+ * VoidNode::flags is ANDed with it (~0u for frames; the diagnostics readback c2rt_debug_tile_masks varies it). */
+VoidCull void_cull_of(const c2rt_ctx *ctx, const RenderParams &p, uint32_t flags_mask)
 {
-    p.tile_masks = nullptr;
-    p.mask_row0 = p.row_offset;
-    p.mask_rows = p.local_rows;
-    if (!p.n_cull || v.dof_or_stereo || !p.local_rows) return 0;
-    const size_t entries = tile_mask_entries(p);
-    FrameScratch &sc = scratch_for(ctx, stream);
-    if (entries > sc.tile_mask_entries) {
-        if (sc.tile_masks) { (void)hipFree(sc.tile_masks); sc.tile_masks = nullptr; sc.tile_mask_entries = 0; }
-        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&sc.tile_masks), entries * 8 * sizeof(uint32_t));
-        if (e != hipSuccess) return (int)e;
-        sc.tile_mask_entries = entries;
-    }
-    p.tile_masks = sc.tile_masks;
-    /* the void test's per-frame part: the ball's margin at this frame's scale (csg_void.h: void_margin) */
     VoidCull vc{};
     for (const VoidNode &seed : ctx->void_nodes) {
         if (seed.node >= p.n_cull) continue;
@@ -628,10 +614,37 @@ int prepare_tile_masks(c2rt_ctx *ctx, RenderParams &p, const KernelVariant &v, h
         if (!(rm > 0) || !std::isfinite(scale)) continue;
         v.r2 = rm * rm;
         if (p.n_cull_lights == 0 || p.ground_node < 0) v.flags &= ~2u;
+        v.flags &= flags_mask;
         vc.v[vc.n++] = v;
     }
     if (!ctx->light_pos.empty())
         for (int j = 0; j < 3; ++j) vc.light0[j] = ctx->light_pos[j];
+    return vc;
+}
+
+/* The tiles' culling masks for the local rows [p.row_offset, p.row_offset + p.local_rows), by the pre-pass kernel,
+ * in front of the frame kernel on the same stream (one table per stream of the context: FrameScratch).  Sets p.tile_masks / mask_row0 / mask_rows /
+ * mask_entries; a no-op for frames without culling rectangles (tile_masks = nullptr, mask_entries = 0).  vc_out
+ * (nullable): the VoidCull the pre-pass was given.  Returns a hipError_t. */
+int prepare_tile_masks(c2rt_ctx *ctx, RenderParams &p, const KernelVariant &v, hipStream_t stream,
+                       uint32_t void_flags_mask = ~0u, VoidCull *vc_out = nullptr)
+{
+    p.tile_masks = nullptr;
+    p.mask_entries = 0;
+    p.mask_row0 = p.row_offset;
+    p.mask_rows = p.local_rows;
+    if (!p.n_cull || v.dof_or_stereo || !p.local_rows) return 0;
+    const size_t entries = tile_mask_entries(p);
+    FrameScratch &sc = scratch_for(ctx, stream);
+    if (entries > sc.tile_mask_entries) {
+        if (sc.tile_masks) { (void)hipFree(sc.tile_masks); sc.tile_masks = nullptr; sc.tile_mask_entries = 0; }
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&sc.tile_masks), entries * 8 * sizeof(uint32_t));
+        if (e != hipSuccess) return (int)e;
+        sc.tile_mask_entries = entries;
+    }
+    p.tile_masks = sc.tile_masks;
+    const VoidCull vc = void_cull_of(ctx, p, void_flags_mask);
+    if (vc_out) *vc_out = vc;
     p.mask_entries = (uint32_t)entries;
     return launch_tile_masks(p, vc, sc.tile_masks, stream);
 }
@@ -1766,5 +1779,45 @@ int c2rt_encode_rgb32(c2rt_ctx *ctx, const float *frame_dev, uint32_t *out_dev, 
     if (e != 0) return fail(ctx, C2RT_ERR_HIP, "encode launch: %s", hipGetErrorString((hipError_t)e));
     return C2RT_OK;
 }
+
+#if C2RT_DIAG
+/* Diagnostics hook, in the diagnostics build only (the product library does not export it and include/c2rt.h does
+ * not declare it): the mask pre-pass of one frame, exactly as c2rt_render_frame runs it on this context's stream
+ * (fill_params, prepare_tile_masks), except that every VoidNode::flags of the frame is ANDed with void_flags_mask
+ * (0: no void test, 1: primary only, 3: as shipped).  Copies the FIRST table (4 words per entry, in the
+ * tile_mask_slot layout, mask_entries entries) to `out` and reports
+ *   info[0..5] = {tile columns (blocks_x * kWavesPerBlock), tile rows, mask_row0, mask_rows, tile rows per row class,
+ *                 mask_entries}
+ * and the VoidCull the pre-pass was given (`void_cull`, void_cull_bytes == sizeof(VoidCull)).  A frame without a
+ * table (no culled node, depth of field, stereo) returns C2RT_ERR_UNSUPPORTED; `out` too small: C2RT_ERR_LIMIT.
+ * tests/csg_void_device.py. */
+int c2rt_debug_tile_masks(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, uint32_t void_flags_mask,
+                          uint32_t *out, size_t out_words, uint32_t info[6], void *void_cull, size_t void_cull_bytes)
+{
+    int st = check_frame_args(ctx, cam, opts);
+    if (st != C2RT_OK) return st;
+    if (!out || !info || !void_cull) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    if (void_cull_bytes != sizeof(VoidCull)) return fail(ctx, C2RT_ERR_INVALID_ARG, "VoidCull is %zu bytes, not %zu", sizeof(VoidCull), void_cull_bytes);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    fill_params(ctx, cam, opts, p);
+    VoidCull vc{};
+    const int e = prepare_tile_masks(ctx, p, variant_of(ctx, cam), ctx->stream, void_flags_mask, &vc);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "tile-mask pre-pass launch: %s", hipGetErrorString((hipError_t)e));
+    if (!p.tile_masks) return fail(ctx, C2RT_ERR_UNSUPPORTED, "this frame has no tile-mask table");
+    const size_t words = (size_t)p.mask_entries * 4;
+    if (out_words < words) return fail(ctx, C2RT_ERR_LIMIT, "the table has %zu words, the buffer %zu", words, out_words);
+    HIP_TRY(ctx, hipMemcpyAsync(out, p.tile_masks, words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    info[0] = p.blocks_x * kWavesPerBlock;
+    info[1] = (p.mask_rows + kTileH - 1) / kTileH;
+    info[2] = p.mask_row0;
+    info[3] = p.mask_rows;
+    info[4] = (info[1] + 7u) / 8u;
+    info[5] = p.mask_entries;
+    std::memcpy(void_cull, &vc, sizeof vc);
+    return C2RT_OK;
+}
+#endif
 
 } /* extern "C" */

@@ -13,6 +13,7 @@ import ctypes as C
 import math
 import os
 import sys
+from collections import namedtuple
 
 import numpy as np
 
@@ -23,6 +24,10 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 GEOM_PLANE, GEOM_SPHERE, GEOM_CUBE, GEOM_DIFF = 0, 1, 2, 5
 TAPS = ((0.0, 0.0), (0.3, 0.3), (0.6, 0.0), (0.0, 0.6), (0.6, 0.6))  # rt/renderer.d:235-242
+MAX_VOID_NODES = 4   # csg_void.h: kMaxVoidNodes
+MAX_CULL_NODES = 32  # c2rt_device.h: kMaxCullNodes
+MAX_CULL_LIGHTS = 4  # c2rt_device.h: kMaxCullLights
+TILE = 8
 
 _lib = None
 
@@ -52,70 +57,208 @@ def _fields(desc):
     return desc.contents if hasattr(desc, "contents") else desc
 
 
-def void_candidates(desc):
-    """[(node, lo, hi, centre, R)] for the nodes the library tests: CsgDiff(Cube | Sphere, Sphere) under an identity
-    matrix (offset allowed), box = the left child's box plus the library's pad (c2rt_api.cpp, node boxes)."""
+class Cand(namedtuple("Cand", "node lo hi c R flags")):
+    """A CsgDiff(L, Sphere) node the library tests (c2rt_api.cpp, upload_one): its padded world box, the subtracted
+    sphere's world centre and radius, and its VoidNode::flags (bit 0 primary, bit 1 shadow towards light 0)."""
+
+
+_IDENTITY = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
+
+
+def _node_tr(desc, n):
+    tr = [desc.node_transform[30 * n + i] for i in range(30)]
+    return tr[0:9], tr[9:18], tr[18:27], tr[27:30]
+
+
+def _finite(*xs):
+    return all(math.isfinite(x) for x in xs)
+
+
+def ground_of(desc):
+    """(node, y) of the ground as the library picks it (upload_one, RenderParams::ground_node): the first Plane node
+    below kMaxCullNodes under an identity matrix with zero offset and a finite height, or (None, None)."""
     desc = _fields(desc)
-    out = []
-    for n in range(desc.n_nodes):
+    for n in range(min(desc.n_nodes, MAX_CULL_NODES)):
         g = desc.node_geom[n]
-        if desc.geom_type[g] != GEOM_DIFF:
+        m, inv, tinv, off = _node_tr(desc, n)
+        if desc.geom_type[g] == GEOM_PLANE and m == inv == tinv == _IDENTITY and off == [0, 0, 0] \
+                and math.isfinite(desc.geom_param[4 * g]):
+            return n, desc.geom_param[4 * g]
+    return None, None
+
+
+def _geom_finite(desc, g):
+    """DevGeom kGeomFinite of a Sphere / Cube: its parameters and derived values are finite"""
+    p = [desc.geom_param[4 * g + i] for i in range(4)]
+    if desc.geom_type[g] == GEOM_CUBE:
+        h = p[3] * 0.5
+        q = [p[i] + -1 * h for i in range(3)] + [p[i] + 1 * h for i in range(3)]
+    else:
+        q = [p[3] * p[3]]
+    return _finite(*p) and _finite(*q)
+
+
+def void_candidates(desc):
+    """[Cand] for the nodes the library tests, restated from c2rt_api.cpp (upload_one) operation for operation: the
+    first kMaxVoidNodes nodes below kMaxCullNodes that are CsgDiff(Cube | Sphere, Sphere) under an identity matrix
+    (offset allowed) with finite children and R > 0.  The box is the left child's (box_of: shortcut A) padded as for
+    every node (1e-6 ext + 1e-6 mag + 1e-9 + 4e-6 max(|M^-1|_F, 1)) and moved by the offset; the shadow flag needs
+    the ground and the box strictly on the ground's side of light 0's height."""
+    desc = _fields(desc)
+    gn, gy = ground_of(desc)
+    light = [desc.light_pos[i] for i in range(3)] if desc.n_lights else None
+    out = []
+    for n in range(min(desc.n_nodes, MAX_CULL_NODES)):
+        if len(out) >= MAX_VOID_NODES:
+            break
+        g = desc.node_geom[n]
+        m, inv, tinv, off = _node_tr(desc, n)
+        if desc.geom_type[g] != GEOM_DIFF or not (m == inv == tinv == _IDENTITY):
             continue
-        tr = [desc.node_transform[30 * n + i] for i in range(30)]
-        if tr[0:9] != [1.0, 0, 0, 0, 1.0, 0, 0, 0, 1.0] or tr[9:18] != tr[0:9]:
-            continue
-        off = tr[27:30]
         l, r = desc.geom_child[2 * g], desc.geom_child[2 * g + 1]
         if l == r or desc.geom_type[r] != GEOM_SPHERE or desc.geom_type[l] not in (GEOM_SPHERE, GEOM_CUBE):
+            continue
+        if not (_geom_finite(desc, l) and _geom_finite(desc, r)):
             continue
         pl = [desc.geom_param[4 * l + i] for i in range(4)]
         pr = [desc.geom_param[4 * r + i] for i in range(4)]
         if not pr[3] > 0:
             continue
+        # node_boxed: the Diff's bound (bound_of, the left child's) is finite and small enough, the offset finite
+        br = abs(pl[3]) if desc.geom_type[l] == GEOM_SPHERE else abs(pl[3]) * 0.5 * 1.7320508075688774
+        bmag = abs(pl[0]) + abs(pl[1]) + abs(pl[2]) + br
+        rp = br * (1 + 1e-6) + 1e-6 * bmag + 1e-9
+        if not (math.isfinite(rp) and rp * rp < 1e300) or not _finite(*off):
+            continue
         e = abs(pl[3]) if desc.geom_type[l] == GEOM_SPHERE else abs(pl[3]) * 0.5
         lo = [pl[i] - e for i in range(3)]
         hi = [pl[i] + e for i in range(3)]
-        mag = sum(max(abs(lo[i]), abs(hi[i])) for i in range(3))
-        pad = 1e-6 * (2 * e) + 1e-6 * mag + 1e-9 + 4e-6
-        out.append((n, [lo[i] - pad + off[i] for i in range(3)], [hi[i] + pad + off[i] for i in range(3)],
-                    [pr[i] + off[i] for i in range(3)], pr[3]))
+        inv_norm = 0.0
+        for x in inv:
+            inv_norm += x * x
+        inv_norm = math.sqrt(inv_norm)
+        mag = ext = 0.0
+        for i in range(3):
+            mag += max(abs(lo[i]), abs(hi[i]))
+            ext = max(ext, hi[i] - lo[i])
+        pad = 1e-6 * ext + 1e-6 * mag + 1e-9 + 4e-6 * (inv_norm if inv_norm > 1 else 1.0)
+        if not math.isfinite(pad):
+            continue
+        corners = []
+        for k in range(8):
+            q = [hi[0] + pad if k & 1 else lo[0] - pad, hi[1] + pad if k & 2 else lo[1] - pad, hi[2] + pad if k & 4 else lo[2] - pad]
+            corners.append([q[0] * m[0 + j] + q[1] * m[3 + j] + q[2] * m[6 + j] + off[j] for j in range(3)])
+        if not _finite(*[w for cw in corners for w in cw]):
+            continue
+        wlo = [min(cw[j] for cw in corners) for j in range(3)]
+        whi = [max(cw[j] for cw in corners) for j in range(3)]
+        c = [pr[j] + off[j] for j in range(3)]
+        if not _finite(*c, *wlo, *whi):
+            continue
+        flags = 1
+        if gn is not None and light is not None:
+            h = light[1] - gy
+            tol = 1e-6 + 1e-9 * (abs(light[1]) + abs(wlo[1]) + abs(whi[1]))
+            if _finite(*light, h) and ((h > 0 and whi[1] < light[1] - tol) or (h < 0 and wlo[1] > light[1] + tol)):
+                flags |= 2
+        out.append(Cand(n, wlo, whi, c, pr[3], flags))
     return out
 
 
-def ground_of(desc):
-    """(node, y) of the first Plane node under an identity matrix with zero offset, or (None, None)."""
+def frame_void_nodes(desc, cam, debug_cull=0):
+    """The VoidCull the library hands the mask pre-pass for this camera (c2rt_api.cpp, void_cull_of): per candidate
+    (node, lo, hi, c, r2 = (R - void_margin(scale))^2, flags), without bit 1 where the frame runs no shadow culling
+    or no ground refinement (the diagnostics build's C2RT_DEBUG_CULL bits 2 and 4).  None: the frame culls nothing
+    (C2RT_DEBUG_CULL bit 1)."""
     desc = _fields(desc)
-    for n in range(desc.n_nodes):
-        g = desc.node_geom[n]
-        tr = [desc.node_transform[30 * n + i] for i in range(30)]
-        if desc.geom_type[g] == GEOM_PLANE and tr[0:9] == [1.0, 0, 0, 0, 1.0, 0, 0, 0, 1.0] and tr[27:30] == [0, 0, 0]:
-            return n, desc.geom_param[4 * g]
-    return None, None
+    if debug_cull & 1:
+        return None
+    gn, _ = ground_of(desc)
+    n_cull_lights = 0 if debug_cull & 4 else min(desc.n_lights, MAX_CULL_LIGHTS)
+    if debug_cull & 2:
+        gn = None
+    out = []
+    for cand in void_candidates(desc):
+        scale = cand.R
+        scale += max(abs(cand.c[0]), abs(cand.c[1]), abs(cand.c[2]))
+        scale += max(abs(cam.pos[0]), abs(cam.pos[1]), abs(cam.pos[2]))
+        if desc.n_lights:
+            scale += max(abs(desc.light_pos[0]), abs(desc.light_pos[1]), abs(desc.light_pos[2]))
+        rm = cand.R - lib().c2rt_void_margin(scale)
+        if not (rm > 0) or not math.isfinite(scale):
+            continue
+        flags = cand.flags
+        if n_cull_lights == 0 or gn is None:
+            flags &= ~2
+        out.append(dict(node=cand.node, lo=cand.lo, hi=cand.hi, c=cand.c, r2=rm * rm, flags=flags))
+    return out
+
+
+def _scale_and_light(desc, cam, cand):
+    light = [desc.light_pos[i] for i in range(3)] if desc.n_lights else [0.0, 0.0, 0.0]
+    scale = cand.R + max(abs(x) for x in cand.c) + max(abs(x) for x in cam.pos) + (max(abs(x) for x in light) if desc.n_lights else 0)
+    return scale, light
+
+
+def _classify_args(desc, cam, cand, r_override):
+    desc = _fields(desc)
+    scale, light = _scale_and_light(desc, cam, cand)
+    rm = (cand.R if r_override is None else r_override) - lib().c2rt_void_margin(scale)
+    _, gy = ground_of(desc)
+    du = [cam.up_right[i] - cam.up_left[i] for i in range(3)]
+    dv = [cam.down_left[i] - cam.up_left[i] for i in range(3)]
+    head = (_a3(cam.pos), _a3(cam.up_left), _a3(du), _a3(dv), cam.frame_width, cam.frame_height)
+    tail = (_a3(cand.lo), _a3(cand.hi), _a3(cand.c), rm * rm, cand.flags, _a3(light), gy if gy is not None else 0.0)
+    return rm, head, tail
 
 
 def classify(desc, cam, W, H, cand, r_override=None):
-    """uint8 (tiles_y, tiles_x): bit 0 primary-void, bit 1 shadow-void (towards light 0 from the ground footprint)."""
-    n, lo, hi, c, R = cand
-    desc = _fields(desc)
-    light = [desc.light_pos[i] for i in range(3)] if desc.n_lights else [0.0, 0.0, 0.0]
-    scale = R + max(abs(x) for x in c) + max(abs(x) for x in cam.pos) + (max(abs(x) for x in light) if desc.n_lights else 0)
-    rm = (R if r_override is None else r_override) - lib().c2rt_void_margin(scale)
-    flags = 1
-    gn, gy = ground_of(desc)
-    if gn is not None and desc.n_lights:
-        h = light[1] - gy
-        tol = 1e-6 + 1e-9 * (abs(light[1]) + abs(lo[1]) + abs(hi[1]))
-        if (h > 0 and hi[1] < light[1] - tol) or (h < 0 and lo[1] > light[1] + tol):
-            flags |= 2
+    """uint8 (tiles_y, tiles_x) over the full-frame tile grid: bit 0 primary-void, bit 1 shadow-void (towards light 0
+    from the ground footprint; only for candidates with flag bit 1).  r_override: classify with this radius instead
+    of the sphere's (the mutation test)."""
     tw, th = (W + 7) // 8, (H + 7) // 8
     out = np.zeros((th, tw), dtype=np.uint8)
+    rm, head, tail = _classify_args(desc, cam, cand, r_override)
     if not rm > 0:
         return out
-    du = [cam.up_right[i] - cam.up_left[i] for i in range(3)]
-    dv = [cam.down_left[i] - cam.up_left[i] for i in range(3)]
-    lib().c2rt_void_classify(_a3(cam.pos), _a3(cam.up_left), _a3(du), _a3(dv), cam.frame_width, cam.frame_height, W, H,
-                             _a3(lo), _a3(hi), _a3(c), rm * rm, flags, _a3(light), gy if gy is not None else 0.0,
-                             out.ctypes.data_as(C.c_void_p))
+    lib().c2rt_void_classify(*head, W, H, *tail, out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def tile_bounds(trow, tcol, mask_row0, mask_rows, strip_height=1, strip_rank=0, strip_world=1):
+    """(tx0, ty0, ty1): the first pixel column and the first and last FRAME row of the tile in row `trow` (row 0 =
+    local row mask_row0) and column `tcol` of a mask table, restated from tile_mask_entry (c2rt_trace.inc): the
+    last tile row may be ragged; under strips (local rows dealt round-robin in strips of strip_height) the local rows
+    map to frame rows and a tile may span two strips, whose frame rows [ty0, ty1] then also hold other ranks' rows."""
+    lr_first = trow * TILE + mask_row0
+    lr_last = min(trow * TILE + TILE - 1, mask_rows - 1) + mask_row0
+    ty0, ty1 = lr_first, lr_last
+    if strip_world > 1:
+        sh = strip_height
+        ty0 = ((lr_first // sh) * strip_world + strip_rank) * sh + lr_first % sh
+        ty1 = ((lr_last // sh) * strip_world + strip_rank) * sh + lr_last % sh
+    return tcol * TILE, ty0, ty1
+
+
+def _classify_tiles_fn():
+    """c2rt_void_classify_tiles, bound on first use: lib() itself needs only the entry points every caller uses"""
+    fn = lib().c2rt_void_classify_tiles
+    if fn.restype is not None:
+        d3 = C.POINTER(C.c_double)
+        fn.argtypes = [d3, d3, d3, d3, C.c_double, C.c_double, C.c_size_t, C.c_void_p, d3, d3, d3, C.c_double, C.c_uint,
+                       d3, C.c_double, C.c_void_p]
+        fn.restype = None
+    return fn
+
+
+def classify_tiles(desc, cam, bounds, cand, r_override=None):
+    """uint8 [len(bounds)]: classify explicit tiles, bounds = [(tx0, ty0, ty1)] (tile_bounds)."""
+    out = np.zeros(len(bounds), dtype=np.uint8)
+    rm, head, tail = _classify_args(desc, cam, cand, r_override)
+    if not rm > 0 or not len(bounds):
+        return out
+    b = np.ascontiguousarray(np.asarray(bounds, dtype=np.int32).reshape(-1, 3))
+    _classify_tiles_fn()(*head, len(bounds), b.ctypes.data_as(C.c_void_p), *tail, out.ctypes.data_as(C.c_void_p))
     return out
 
 
@@ -146,17 +289,24 @@ def node_rect_tiles(cam, W, H, lo, hi):
 
 
 def check_tile(desc, cam, W, H, node, ty, tx, bits, light, ground):
-    """Oracle, every ray of one void tile: primary rays (5 taps) miss the node; with bit 1, for primary rays that hit
-    the ground, the shadow ray towards light 0 (from p + N*1e-6, rt/shader.d:88) gets no hit on the node before the
-    light.  Returns the number of rays checked; raises on a violation."""
+    """Oracle, every ray of one void tile of the full-frame grid (check_tile_bounds)."""
+    return check_tile_bounds(desc, cam, W, H, node, (tx * 8, ty * 8, min(ty * 8 + 7, H - 1)), bits, light, ground)
+
+
+def check_tile_bounds(desc, cam, W, H, node, bounds, bits, light, ground):
+    """Oracle, every ray of one void tile, bounds = (tx0, ty0, ty1) as tile_bounds has them (every frame row of
+    [ty0, ty1]): primary rays (5 taps) miss the node; with bit 1, for primary rays that hit the ground, the shadow
+    ray towards light 0 (from p + N*1e-6, rt/shader.d:88) gets no hit on the node before the light.  Returns the
+    number of rays checked; raises on a violation."""
     import oracle_lib
     from oracle_lib import OrcHit
 
     L = oracle_lib.lib()
     o, d = (C.c_double * 3)(), (C.c_double * 3)()
     n_rays = 0
-    for y in range(ty * 8, min(ty * 8 + 8, H)):
-        for x in range(tx * 8, min(tx * 8 + 8, W)):
+    tx0, ty0, ty1 = bounds
+    for y in range(ty0, min(ty1 + 1, H)):
+        for x in range(tx0, min(tx0 + 8, W)):
             for ox, oy in TAPS:
                 L.orc_screen_ray(C.byref(cam), x + ox, y + oy, o, d)
                 if bits & 1:
