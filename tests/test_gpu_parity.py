@@ -1048,6 +1048,96 @@ def test_zaphod_anchor_pixels_on_the_gpu(gpu_ctx, golden_dir):
         np.testing.assert_allclose(frame[px["y"], px["x"]], px["rgb"], atol=a["rgb_tolerance"], rtol=0)
 
 
+# child process on the diagnostics library: the mask pre-pass's table of the anchor frame with the void test off
+# (void_flags_mask 0) and on (3); prints, per tile, whether csgNode's primary bit is set in each
+_L5_TILES_CHILD = r'''
+import json, os, sys
+sys.path[:0] = [os.path.join(os.getcwd(), "tests"), os.path.join(os.getcwd(), "scripts")]
+import numpy as np
+import chess2rt_amd as c2, csg_void_device as dev
+scene_path, W, H, node = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
+scene = c2.parseSceneFromFile(scene_path)
+scene.setFrameSize(W, H); scene.setAA(False); scene.setDof(False)
+cam = scene.beginFrame()
+ctx = c2.Context(0)
+ctx.uploadScene(scene.desc)
+opts = scene.renderOpts()
+(m0, info, _), (m3, info3, _) = dev.read_tile_masks(ctx, cam, opts, 0), dev.read_tile_masks(ctx, cam, opts, 3)
+assert info == info3 and info["mask_row0"] == 0
+bit = lambda m: ((m[..., 0] >> np.uint32(node)) & 1).astype(int).tolist()
+print(json.dumps(dict(off=bit(m0), on=bit(m3))))
+print("ok")
+'''
+
+
+def test_lecture5_anchor_pixels_on_the_gpu(gpu_ctx, golden_dir):
+    """The independent lecture5 anchors (tests/golden/lecture5_anchors.json, derived by
+    tests/golden/make_lecture5_anchors.py without the oracle, the host mirror or the kernels; this test reads only
+    tests/golden/) against the HIP path: the probe kernel's node, leaf, ray, hit and colour at every anchored pixel;
+    the frame kernel at 640x480 (production and counting instances, bit-equal by the fixture), again after a second
+    uploadScene and as interleaved row strips of heights 8 and 12; the five-tap frame at the five-tap anchors.  The
+    void-tile pre-pass cannot be switched off, so the test shows instead that the anchors lie under it: the table
+    read back from the diagnostics library drops csgNode from the tile of a pixel seen through the cube's silhouette
+    and of a floor pixel in the cube's shadow, and keeps it in the tile of another pixel seen through the silhouette
+    (in a child process, as every read of that table: the hook exists only in the diagnostics library)."""
+    import subprocess
+    import sys
+
+    import torch
+
+    from test_oracle_golden import check_lecture5_colour, check_lecture5_probe, lecture5_anchor_scene
+
+    a = json.load(open(os.path.join(golden_dir, "lecture5_anchors.json")))
+    s, cam, node_of, geom_of = lecture5_anchor_scene(a)
+    W, H = a["width"], a["height"]
+    opts = s.renderOpts(count_rays=1)
+    assert opts.taps == c2.TAPS_1 and cam.dof == 0
+    gpu_ctx.uploadScene(s.desc)
+    for px in a["pixels"]:
+        check_lecture5_probe(gpu_ctx.renderPixel(cam, opts, px["x"], px["y"]), px, node_of, geom_of, "probe kernel")
+
+    def check_frame(frame, how):
+        assert frame.shape == (H, W, 3)
+        for px in a["pixels"]:
+            check_lecture5_colour(frame[px["y"], px["x"]], px["rgb"], px["rgb_tol"], "%s (%d, %d) %s" % (how, px["x"], px["y"], px["category"]))
+
+    full = gpu_ctx.renderFrame(cam, opts)
+    check_frame(full, "frame kernel")
+    gpu_ctx.uploadScene(s.desc)
+    check_frame(gpu_ctx.renderFrame(cam, opts), "frame kernel after a second uploadScene")
+    for world, sh in ((2, 8), (3, 12)):
+        gathered = torch.zeros((world, c2.local_rows(H, sh, 0, world), W, 3), dtype=torch.float32)   # rank 0 owns the most rows
+        for r in range(world):
+            o = s.renderOpts(count_rays=1, strip_height=sh, strip_rank=r, strip_world=world)
+            part = gpu_ctx.renderFrame(cam, o)
+            assert part.shape[0] == c2.local_rows(H, sh, r, world)
+            gathered[r, :part.shape[0]] = torch.from_numpy(part)
+        check_frame(c2.deinterleave_strips_torch(gathered, H, sh, world).numpy(), "strips of %d rows over %d ranks" % (sh, world))
+    # the five taps
+    s.setAA(True)
+    cam5 = s.beginFrame()
+    opts5 = s.renderOpts(count_rays=1)
+    assert opts5.taps == c2.TAPS_REF5
+    frame5 = gpu_ctx.renderFrame(cam5, opts5)
+    for t in a["five_tap"]:
+        check_lecture5_colour(frame5[t["y"], t["x"]], t["mean"], t["mean_tol"], "five-tap frame (%d, %d) %s" % (t["x"], t["y"], t["kind"]))
+    # the anchors lie under the void-tile pre-pass
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, "-c", _L5_TILES_CHILD, os.path.join(SCENES, a["scene"]), str(W), str(H), str(node_of["csgNode"])],
+                       capture_output=True, text=True, timeout=300, env=dict(os.environ, C2RT_LIB_VARIANT="diag"), cwd=root)
+    assert p.returncode == 0 and p.stdout.rstrip().endswith("ok"), p.stdout[-4000:] + p.stderr[-4000:]
+    tiles = json.loads([line for line in p.stdout.splitlines() if line.startswith("{")][0])
+    off, on = np.array(tiles["off"], dtype=bool), np.array(tiles["on"], dtype=bool)
+    assert off.shape == on.shape == ((H + 7) // 8, (W + 7) // 8) and not np.any(on & ~off)
+    dropped = lambda px: bool(off[px["y"] // 8, px["x"] // 8] and not on[px["y"] // 8, px["x"] // 8])
+    kept = lambda px: bool(on[px["y"] // 8, px["x"] // 8])
+    through = [px for px in a["pixels"] if px["through_cube_silhouette"]]
+    print("lecture5 anchors: %d pixels, %d seen through the silhouette (%d in dropped tiles, %d in kept tiles); tiles dropped: %d"
+          % (len(a["pixels"]), len(through), sum(map(dropped, through)), sum(map(kept, through)), int((off & ~on).sum())))
+    assert any(dropped(px) for px in through) and any(kept(px) for px in through)
+    assert any(dropped(px) for px in a["pixels"] if px["category"] == "floor_shadow_csg")
+
+
 LIBM_RESIDUAL = dict(seed=12023564, sizes=((64, 48), (128, 96), (200, 152), (320, 240)))
 
 

@@ -131,6 +131,136 @@ def test_zaphod_anchors_pin_yaw_roll_and_transform(golden_dir):
     assert [scene.desc.contents.node_transform[i] for i in range(30)] == list(t)
 
 
+L5_CATEGORIES = ("sky", "floor_lit", "floor_shadow_csg", "floor_shadow_other", "globe", "ball_S1", "ball_S2", "ball_S3",
+                 "ball_highlight", "cube_-z", "cube_+y", "cube_+x", "cavity_lit", "cavity_shadow")
+L5_MISREADINGS = ("no_flip", "reflect_sign", "exp79", "exp81", "no_strength", "specular_times_material", "shadow_offset_minus_n",
+                  "sphere_v_no_one_minus", "sphere_u_atan2_xz", "cube_uv_unpermuted", "root_swap", "rows_top_down", "no_srgb",
+                  "scaling_divides", "aa_divisor_4", "aa_offsets_quarter_half", "aa_offsets_half_threequarter")
+
+
+def lecture5_anchor_scene(a):
+    """lecture5.sdl through the host mirror at the anchors' frame size, AA and DOF off; checks that the anchors' node
+    and geometry names (file order of the .sdl) are the loaded scene's indices.  -> (scene, cam, node index, leaf index)"""
+    scene = c2.parseSceneFromFile(os.path.join(SCENES, a["scene"]))
+    scene.setFrameSize(a["width"], a["height"])
+    scene.setAA(False)
+    scene.setDof(False)
+    cam = scene.beginFrame()
+    d = scene.desc.contents
+    assert d.n_nodes == len(a["nodes"]) and d.n_geoms == len(a["geometries"])
+    node_of = {n: i for i, n in enumerate(a["nodes"])}
+    geom_of = {g: i for i, g in enumerate(a["geometries"])}
+    for n, g in a["node_geometry"].items():
+        assert d.node_geom[node_of[n]] == geom_of[g], (n, g)
+    node_of[None], geom_of[None] = -1, -1
+    return scene, cam, node_of, geom_of
+
+
+def check_lecture5_probe(r, px, node_of, geom_of, who):
+    """one probe result (oracle's or the kernel's TraceResult) against one anchored pixel, each quantity within the
+    tolerance the generator derived for it"""
+    tag = "%s (%d, %d) %s" % (who, px["x"], px["y"], px["category"])
+    assert r.closest_node == node_of[px["node"]], tag
+    assert r.leaf_geom == geom_of[px["leaf"]], tag
+    np.testing.assert_allclose(list(r.ray_dir), px["dir"], atol=px["dir_tol"], rtol=0, err_msg=tag)
+    if px["node"] is not None:
+        np.testing.assert_allclose(r.dist, px["t"], atol=px["t_tol"], rtol=0, err_msg=tag + " t")
+        np.testing.assert_allclose(list(r.p), px["p"], atol=px["p_tol"], rtol=0, err_msg=tag + " p")
+        np.testing.assert_allclose(list(r.normal), px["normal"], atol=px["normal_tol"], rtol=0, err_msg=tag + " normal")
+        np.testing.assert_allclose(r.u, px["u"], atol=px["u_tol"], rtol=0, err_msg=tag + " u")
+        np.testing.assert_allclose(r.v, px["v"], atol=px["v_tol"], rtol=0, err_msg=tag + " v")
+    check_lecture5_colour(list(r.color), px["rgb"], px["rgb_tol"], tag)
+
+
+def check_lecture5_colour(got, want, tol, tag):
+    for k in range(3):
+        assert abs(float(got[k]) - want[k]) <= tol[k], "%s channel %d: %r against %r +- %r" % (tag, k, float(got[k]), want[k], tol[k])
+
+
+def lecture5_void_tiles(scene, cam, a):
+    """bool (60, 80): tiles of the anchor frame that the host classifier (tests/libcsg_void_check.so) calls
+    primary-void for csgNode"""
+    sys_path_scripts()
+    import csg_void_tiles as cv
+
+    cands = [c for c in cv.void_candidates(scene.desc) if c.node == a["nodes"].index("csgNode")]
+    assert len(cands) == 1
+    return (cv.classify(scene.desc, cam, a["width"], a["height"], cands[0]) & 1) != 0
+
+
+def sys_path_scripts():
+    import sys
+
+    p = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts")
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def test_lecture5_anchors_pin_sphere_cube_csg_and_phong(golden_dir):
+    """Independent anchors for the headline scene (tests/golden/make_lecture5_anchors.py: the reference's algorithm
+    restated in 50-digit arithmetic, sharing no code with the oracle, the host mirror or the kernels): Sphere with its
+    u, v, Cube with the permuted u, v, the CsgDiff walk with the flipped cavity normal, translated nodes, Phong on and
+    off the highlight, shadows by the carved cube and the spheres, both bitmap paths, and the five taps.  Every
+    tolerance is the pixel's own, derived by the generator from binary64 / fp32 rounding, never from the oracle."""
+    a = jload(golden_dir, "lecture5_anchors.json")
+    scene, cam, node_of, geom_of = lecture5_anchor_scene(a)
+    hc = scene.camera
+    ocam = _abi.CameraFrame()
+    orc.lib().orc_camera_begin_frame(orc.vec3(*hc.pos), hc.yaw, hc.pitch, hc.roll, hc.fov, a["width"], a["height"], C.byref(ocam))
+    assert (list(hc.pos), hc.yaw, hc.pitch, hc.roll, hc.fov) == ([0.0, 165.0, 0.0], 0.0, -30.0, 0.0, 90.0)
+    for who, frame in (("host", cam), ("oracle", ocam)):
+        for k in ("up_left", "up_right", "down_left", "right_dir", "up_dir", "front_dir"):
+            np.testing.assert_allclose(list(getattr(frame, k)), a["camera"][k], atol=a["camera"]["tolerance"], rtol=0, err_msg=who + " " + k)
+    opts = scene.renderOpts()
+    assert cam.dof == 0 and opts.taps == c2.TAPS_1
+    # the table of categories: none empty, at least four pixels seen through the cube's silhouette
+    cats = [px["category"] for px in a["pixels"]]
+    assert all(c in cats for c in L5_CATEGORIES), [c for c in L5_CATEGORIES if c not in cats]
+    through = [px for px in a["pixels"] if px["through_cube_silhouette"]]
+    assert len(through) >= 4 and all(px["node"] != "csgNode" for px in through)
+    assert sorted(t["kind"] for t in a["five_tap"]) == ["interior", "rim", "silhouette"]
+    assert all(len(t["categories"]) >= 2 for t in a["five_tap"] if t["kind"] != "interior")
+    # the anchors bite: every named misreading moves some recorded quantity by >= 100 tolerances on every pixel it
+    # applies to, or is listed as not constrained with the reason
+    assert set(a["misreadings"]) | set(a["not_constrained"]) == set(L5_MISREADINGS)
+    for name, m in a["misreadings"].items():
+        assert m["min_ratio"] >= 100 and m["pixels"] >= 1, (name, m)
+    assert set(a["not_constrained"]) == {"no_strength"} and all(m["reason"] for m in a["not_constrained"].values())
+    # the probe
+    for px in a["pixels"]:
+        check_lecture5_probe(orc.render_pixel(scene.desc, cam, opts, px["x"], px["y"]), px, node_of, geom_of, "oracle probe")
+    # the whole frame at the anchored pixels (frame path == probe path)
+    frame = orc.render_frame(scene.desc, cam, opts, 0)
+    for px in a["pixels"]:
+        check_lecture5_colour(frame[px["y"], px["x"]], px["rgb"], px["rgb_tol"], "oracle frame (%d, %d) %s" % (px["x"], px["y"], px["category"]))
+    # the five taps
+    scene.setAA(True)
+    cam5 = scene.beginFrame()
+    opts5 = scene.renderOpts()
+    assert opts5.taps == c2.TAPS_REF5
+    frame5 = orc.render_frame(scene.desc, cam5, opts5, 0)
+    for t in a["five_tap"]:
+        check_lecture5_colour(frame5[t["y"], t["x"]], t["mean"], t["mean_tol"], "oracle five taps (%d, %d) %s" % (t["x"], t["y"], t["kind"]))
+    # the void-tile pre-pass is under the anchors: a category-5 pixel and a floor pixel in the carved cube's shadow in
+    # tiles the classifier drops csgNode from, and a category-5 pixel in a tile that keeps it
+    void = lecture5_void_tiles(scene, cam, a)
+    in_void = lambda px: bool(void[px["y"] // 8, px["x"] // 8])
+    assert any(in_void(px) for px in through) and any(not in_void(px) for px in through)
+    assert any(in_void(px) for px in a["pixels"] if px["category"] == "floor_shadow_csg")
+
+
+def test_lecture5_anchor_file_is_what_the_generator_writes(golden_dir):
+    """The committed JSON is the generator's output, value for value: it cannot be edited by hand to make a test
+    pass.  Needs no project code, only mpmath."""
+    pytest.importorskip("mpmath", reason="mpmath is needed to run tests/golden/make_lecture5_anchors.py")
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("make_lecture5_anchors", os.path.join(golden_dir, "make_lecture5_anchors.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    assert json.loads(json.dumps(gen.build())) == jload(golden_dir, "lecture5_anchors.json")
+
+
 # ---- (3) properties of the reference algorithm --------------------------------
 def _mini_scene(geoms, children=None):
     """A SceneDesc with only geometries (for Geometry.intersect calls)."""
