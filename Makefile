@@ -55,7 +55,7 @@ HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/dsc.o $(BUILD)/scene.o $(BUILD)/host_
 # over the SAME kernel objects; tests and scripts that need a hook load it with C2RT_LIB_VARIANT=diag
 DIAGNAME   := chess2rt_amd/libc2rt_diag.so
 
-all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so
+all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so
 
 $(BUILD):
 	mkdir -p $(BUILD)
@@ -87,6 +87,10 @@ tests/fp64_lean_check: tests/fp64_lean_check.hip $(CSRC)/fp64_lean.h
 tests/libcsg_void_check.so: tests/csg_void_check.cpp $(CSRC)/csg_void.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ $<
 
+# host build of the sphere-silhouette test of the mask pre-pass (tests/test_sphere_cull_tiles.py, scripts/sphere_cull_tiles.py)
+tests/libsphere_cull_check.so: tests/sphere_cull_check.cpp $(CSRC)/csg_void.h
+	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ $<
+
 # CPU oracle: plain C restatement of the reference algorithm (tests only)
 oracle/libc2rt_oracle.so: oracle/c2rt_oracle.c oracle/c2rt_oracle.h include/c2rt.h
 	$(CC) -O2 -std=gnu11 -fPIC -shared $(FPFLAGS) -Wall -o $@ oracle/c2rt_oracle.c -lm -lpthread
@@ -102,6 +106,6 @@ resource-usage: | $(BUILD)
 	    -c $(CSRC)/c2rt_kernels.hip -o $(BUILD)/ru_u$(u).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
 
 clean:
-	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so
+	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so
 
 .PHONY: all clean resource-usage

@@ -98,6 +98,10 @@ struct c2rt_ctx {
     /* CsgDiff(primitive, Sphere) nodes under an identity matrix (translation allowed): the per-tile void test of the
      * mask pre-pass (csg_void.h); VoidNode::r2 holds R here, the frame's margin is applied in void_cull_of */
     std::vector<VoidNode> void_nodes;
+    /* Sphere nodes under an identity matrix the pre-pass may drop from tiles outside their silhouette (csg_void.h);
+     * SphereNode::rp holds R here, the frame's margin is applied in sphere_cull_of */
+    std::vector<SphereNode> sphere_nodes;
+    uint32_t sphere_flags_mask = ~0u; /* ANDed into every SphereNode::flags (diagnostics: c2rt_debug_sphere_cull) */
 
     float *frame = nullptr;        /* staging frame for host-output renders */
     size_t frame_floats = 0;
@@ -455,7 +459,7 @@ void fill_params(const c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_r
     }
     /* diagnostics build only (like C2RT_CSG_FIRST_CAP; frames are unchanged by construction, slower): C2RT_DEBUG_CULL bit 0:
      * no culling rectangles at all; bit 1: no ground-plane refinement of the shadow mask; bit 2: no view-pyramid
-     * culling of shadow rays */
+     * culling of shadow rays; bit 3: no sphere-silhouette test in the mask pre-pass (sphere_cull_of) */
     static const int debug_cull = [] {
         const char *e = diag_env("C2RT_DEBUG_CULL");
         const int v = e ? std::atoi(e) : 0;
@@ -622,12 +626,47 @@ VoidCull void_cull_of(const c2rt_ctx *ctx, const RenderParams &p, uint32_t flags
     return vc;
 }
 
+/* the sphere test's per-frame part (csg_void.h): one scale for the frame (the largest R + |c| of its balls, the eye,
+ * light 0), which is also the reach of the shadow test; R + sphere_margin per ball; the shadow test only where the
+ * frame runs the ground refinement towards light 0 and the PADDED ball stays on the ground's side of the light's
+ * height.  flags_mask: every SphereNode::flags is ANDed with it (~0u for frames). */
+SphereCull sphere_cull_of(const c2rt_ctx *ctx, const RenderParams &p, uint32_t flags_mask)
+{
+    SphereCull sc{};
+    /* diagnostics build only: C2RT_DEBUG_CULL bit 3: no sphere-silhouette test (frames are unchanged, slower) */
+    static const bool no_sphere = [] { const char *e = diag_env("C2RT_DEBUG_CULL"); return e && (std::atoi(e) & 8); }();
+    if (no_sphere) flags_mask = 0;
+    double scale = 0;
+    for (const SphereNode &seed : ctx->sphere_nodes)
+        scale = std::max(scale, seed.rp + std::max(std::fabs(seed.c[0]), std::max(std::fabs(seed.c[1]), std::fabs(seed.c[2]))));
+    scale += std::max(std::fabs(p.cam.pos[0]), std::max(std::fabs(p.cam.pos[1]), std::fabs(p.cam.pos[2])));
+    if (!ctx->light_pos.empty())
+        scale += std::max(std::fabs(ctx->light_pos[0]), std::max(std::fabs(ctx->light_pos[1]), std::fabs(ctx->light_pos[2])));
+    if (!std::isfinite(scale) || !(flags_mask & 3u)) return sc;
+    sc.reach = scale;
+    for (const SphereNode &seed : ctx->sphere_nodes) {
+        if (seed.node >= p.n_cull) continue;
+        SphereNode s = seed;
+        s.rp = seed.rp + sphere_margin(scale, seed.rp);
+        if (!std::isfinite(s.rp)) continue;
+        if (p.n_cull_lights == 0 || p.ground_node < 0 || ctx->light_pos.empty()) s.flags &= ~2u;
+        if (s.flags & 2u) {
+            const double Ly = ctx->light_pos[1], h = Ly - p.ground_y;
+            const double tol = 1e-6 + 1e-9 * (std::fabs(Ly) + std::fabs(s.c[1]) + s.rp);
+            if (!((h > 0 && s.c[1] + s.rp < Ly - tol) || (h < 0 && s.c[1] - s.rp > Ly + tol))) s.flags &= ~2u;
+        }
+        s.flags &= flags_mask;
+        if (s.flags) sc.s[sc.n++] = s;
+    }
+    return sc;
+}
+
 /* The tiles' culling masks for the local rows [p.row_offset, p.row_offset + p.local_rows), by the pre-pass kernel,
  * in front of the frame kernel on the same stream (one table per stream of the context: FrameScratch).  Sets p.tile_masks / mask_row0 / mask_rows /
  * mask_entries; a no-op for frames without culling rectangles (tile_masks = nullptr, mask_entries = 0).  vc_out
- * (nullable): the VoidCull the pre-pass was given.  Returns a hipError_t. */
+ * / sc_out (nullable): the VoidCull / SphereCull the pre-pass was given.  Returns a hipError_t. */
 int prepare_tile_masks(c2rt_ctx *ctx, RenderParams &p, const KernelVariant &v, hipStream_t stream,
-                       uint32_t void_flags_mask = ~0u, VoidCull *vc_out = nullptr)
+                       uint32_t void_flags_mask = ~0u, VoidCull *vc_out = nullptr, SphereCull *sc_out = nullptr)
 {
     p.tile_masks = nullptr;
     p.mask_entries = 0;
@@ -645,8 +684,10 @@ int prepare_tile_masks(c2rt_ctx *ctx, RenderParams &p, const KernelVariant &v, h
     p.tile_masks = sc.tile_masks;
     const VoidCull vc = void_cull_of(ctx, p, void_flags_mask);
     if (vc_out) *vc_out = vc;
+    const SphereCull sph = sphere_cull_of(ctx, p, ctx->sphere_flags_mask);
+    if (sc_out) *sc_out = sph;
     p.mask_entries = (uint32_t)entries;
-    return launch_tile_masks(p, vc, sc.tile_masks, stream);
+    return launch_tile_masks(p, vc, sph, sc.tile_masks, stream);
 }
 
 /* One frame launch.  Scenes with nested CsgOps (depth >= 2) run the kernel with a reduced hit-stack
@@ -1233,6 +1274,33 @@ static int upload_one(c2rt_ctx *ctx, const c2rt_scene_desc *s)
         ctx->void_nodes.push_back(v);
     }
 
+    /* Sphere nodes the pre-pass may drop from tiles outside their silhouette (csg_void.h): the node's root geometry a
+     * finite Sphere of positive radius, its matrix the identity (the offset moves the centre).  The shadow test
+     * towards light 0 only where the ground refinement runs; whether the padded ball stays below the light's height
+     * depends on the frame's margin (sphere_cull_of). */
+    ctx->sphere_nodes.clear();
+    for (uint32_t n = 0; n < s->n_nodes && n < (uint32_t)kMaxCullNodes && ctx->sphere_nodes.size() < (size_t)kMaxSphereNodes; ++n) {
+        const DevNode &d = nodes[n];
+        if (!ctx->node_boxed[n] || !(d.flags & kNodeIdentityMatrix) || d.g.type != C2RT_GEOM_SPHERE) continue;
+        if (!(geoms[d.geom].flags & kGeomFinite)) continue;
+        const double *sp = s->geom_param + 4 * (size_t)d.geom;
+        if (!(sp[3] > 0)) continue;
+        SphereNode v{};
+        bool finite = true;
+        for (int j = 0; j < 3; ++j) {
+            v.c[j] = sp[j] + d.off[j];
+            finite = finite && std::isfinite(v.c[j]);
+        }
+        if (!finite) continue;
+        v.rp = sp[3];
+        v.node = n;
+        v.flags = 1u;
+        if (ctx->ground_node >= 0 && s->n_lights > 0 && std::isfinite(s->light_pos[0]) && std::isfinite(s->light_pos[1]) &&
+            std::isfinite(s->light_pos[2]))
+            v.flags |= 2u;
+        ctx->sphere_nodes.push_back(v);
+    }
+
     int st;
     if ((st = upload(ctx, &ctx->geoms, geoms)) != C2RT_OK) return st;
     if ((st = upload(ctx, &ctx->textures, textures)) != C2RT_OK) return st;
@@ -1816,6 +1884,27 @@ int c2rt_debug_tile_masks(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2r
     info[4] = (info[1] + 7u) / 8u;
     info[5] = p.mask_entries;
     std::memcpy(void_cull, &vc, sizeof vc);
+    return C2RT_OK;
+}
+
+/* Diagnostics hook: the sphere test's switch.  Every SphereNode::flags of the frames and pre-passes this context
+ * runs from now on is ANDed with `sphere_flags_mask` (0: no sphere test — the tables of the CsgDiff void test alone;
+ * 1: primary only; 3: as shipped, the initial value unless C2RT_DEBUG_CULL has bit 3 set), independently of
+ * c2rt_debug_tile_masks' void_flags_mask.  Writes the SphereCull a pre-pass of (cam, opts) is given under that mask
+ * to `sphere_cull` (nullable; sphere_cull_bytes == sizeof(SphereCull)).  tests/sphere_cull_device.py. */
+int c2rt_debug_sphere_cull(c2rt_ctx *ctx, uint32_t sphere_flags_mask, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                           void *sphere_cull, size_t sphere_cull_bytes)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    ctx->sphere_flags_mask = sphere_flags_mask;
+    if (!sphere_cull) return C2RT_OK;
+    int st = check_frame_args(ctx, cam, opts);
+    if (st != C2RT_OK) return st;
+    if (sphere_cull_bytes != sizeof(SphereCull)) return fail(ctx, C2RT_ERR_INVALID_ARG, "SphereCull is %zu bytes, not %zu", sizeof(SphereCull), sphere_cull_bytes);
+    RenderParams p;
+    fill_params(ctx, cam, opts, p);
+    const SphereCull sc = sphere_cull_of(ctx, p, sphere_flags_mask);
+    std::memcpy(sphere_cull, &sc, sizeof sc);
     return C2RT_OK;
 }
 #endif

@@ -268,7 +268,7 @@ int launch_probe(const RenderParams &p, const KernelVariant &v, void *stream);
 /* entries of RenderParams::tile_masks a launch of `p` reads (4 words each, twice that with several culled lights);
  * the pre-pass that fills them (vc: the frame's CsgDiff void tests, csg_void.h) */
 size_t tile_mask_entries(const RenderParams &p);
-int launch_tile_masks(const RenderParams &p, const VoidCull &vc, uint32_t *table, void *stream);
+int launch_tile_masks(const RenderParams &p, const VoidCull &vc, const SphereCull &sc, uint32_t *table, void *stream);
 int launch_deinterleave(const float *gathered, float *frame, uint32_t width, uint32_t height,
                         uint32_t strip_height, uint32_t world, uint32_t rows_pad, uint32_t words_per_pixel, void *stream);
 int launch_encode_rgb32(const float *frame, uint32_t *out, uint64_t n_pixels,

@@ -292,14 +292,16 @@ __global__ void encode_rgb32_kernel(const float *__restrict__ frame, uint32_t *_
 /* The culling masks of every tile of a frame's local rows, one lane per tile (c2rt_trace.inc: tile_mask_entry,
  * tile_mask_slot).  Runs once per frame whose camera leaves culling rectangles, in front of the frame kernel's
  * launch(es), on the same stream. */
-__global__ void __launch_bounds__(256) tile_masks_kernel(const RenderParams P, const VoidCull V, uint32_t *__restrict__ table, uint32_t tile_rows)
+static_assert(sizeof(RenderParams) + sizeof(VoidCull) + sizeof(SphereCull) + 16 <= 4096, "the kernel-argument segment holds at most 4 KiB");
+__global__ void __launch_bounds__(256) tile_masks_kernel(const RenderParams P, const VoidCull V, const SphereCull S,
+                                                         uint32_t *__restrict__ table, uint32_t tile_rows)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t cols = P.blocks_x * kWavesPerBlock;
     const uint32_t trow = i / cols, tcol = i % cols;
     if (trow >= tile_rows) return;
     uint32_t m[8];
-    exact::tile_mask_entry(P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), V, trow, tcol, m);
+    exact::tile_mask_entry(P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), V, S, trow, tcol, m);
     typedef uint32_t __attribute__((ext_vector_type(4))) u4_t;
     u4_t v, w;
     v.x = m[0]; v.y = m[1]; v.z = m[2]; v.w = m[3];
@@ -389,12 +391,12 @@ size_t tile_mask_entries(const RenderParams &p)
     return (size_t)((tile_rows + 7u) / 8u * 8u) * p.blocks_x * kWavesPerBlock;
 }
 
-int launch_tile_masks(const RenderParams &p, const VoidCull &vc, uint32_t *table, void *stream)
+int launch_tile_masks(const RenderParams &p, const VoidCull &vc, const SphereCull &sc, uint32_t *table, void *stream)
 {
     const uint32_t tile_rows = (p.mask_rows + kTileH - 1) / kTileH;
     const uint32_t lanes = tile_rows * p.blocks_x * kWavesPerBlock;
     if (!lanes) return 0;
-    hipLaunchKernelGGL(tile_masks_kernel, dim3((lanes + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream), p, vc, table, tile_rows);
+    hipLaunchKernelGGL(tile_masks_kernel, dim3((lanes + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream), p, vc, sc, table, tile_rows);
     return (int)hipGetLastError();
 }
 

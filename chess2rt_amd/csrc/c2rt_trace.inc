@@ -1166,7 +1166,7 @@ DEV uint32_t light_shadow_mask(const RenderParams &P, uint32_t mask_slot, uint32
     return ((const uint32_t C2RT_K *)P.tile_masks)[((size_t)P.mask_entries + mask_slot) * 4u + (l - 1u)];
 }
 
-DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, uint32_t trow, uint32_t tcol, uint32_t out[8])
+DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, const SphereCull &S, uint32_t trow, uint32_t tcol, uint32_t out[8])
 {
     typedef const int C2RT_K *KInt;
     typedef const char C2RT_K *KChar;
@@ -1196,6 +1196,14 @@ DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, uint
     const bool in_left = tx0 >= sd[0] && tx0 <= sd[1], in_right = sx1 >= sd[2] && sx1 <= sd[3];
     const bool in_top = ty0 >= sd[4] && ty0 <= sd[5], in_bottom = sy1 >= sd[6] && sy1 <= sd[7];
     uint32_t pmask = 0xFFFFFFFFu, smask0 = 0xFFFFFFFFu;
+    PyramidCone pcone;
+    bool have_pcone = false;
+    const auto primary_cone = [&]() {
+        double cdir[4][3];
+        tile_corner_dirs(P.cam.pos, P.cam.up_left, P.cam_du, P.cam_dv, P.cam.frame_width, P.cam.frame_height,
+                         tx0, tx0 + kTileW, ty0, ty1 + 1, cdir);
+        return pyramid_cone(cdir);
+    };
     for (uint32_t n = 0; n < nc; ++n) {
         const int r0 = rects[4 * n + 0], r1 = rects[4 * n + 1], r2 = rects[4 * n + 2], r3 = rects[4 * n + 3];
         /* the node's rectangle, then its hull (RenderParams::cull_hull): outside one padded edge with all four
@@ -1213,16 +1221,20 @@ DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, uint
             }
         }
         if (rect_misses || off_hull) pmask &= ~(1u << n);
-        else if (V.n) {
-            /* a CsgDiff(L, Sphere) node that no primary ray of the tile can hit (csg_void.h): only for tiles whose
-             * rectangle and hull keep it */
+        else if (V.n | S.n) {
+            /* a CsgDiff(L, Sphere) node, or a Sphere node, that no primary ray of the tile can hit (csg_void.h): only
+             * for tiles whose rectangle and hull keep it; the tile's cone is derived once, by the first node to ask */
             for (uint32_t j = 0; j < V.n; ++j) {
                 const VoidNode &vn = V.v[j];
                 if (vn.node != n || !(vn.flags & 1u)) continue;
-                double cdir[4][3];
-                tile_corner_dirs(P.cam.pos, P.cam.up_left, P.cam_du, P.cam_dv, P.cam.frame_width, P.cam.frame_height,
-                                 tx0, tx0 + kTileW, ty0, ty1 + 1, cdir);
-                if (pyramid_void(P.cam.pos, cdir, vn)) pmask &= ~(1u << n);
+                if (!have_pcone) { pcone = primary_cone(); have_pcone = true; }
+                if (pyramid_void(P.cam.pos, pcone, vn)) pmask &= ~(1u << n);
+            }
+            for (uint32_t j = 0; j < S.n; ++j) {
+                const SphereNode &sn = S.s[j];
+                if (sn.node != n || !(sn.flags & 1u)) continue;
+                if (!have_pcone) { pcone = primary_cone(); have_pcone = true; }
+                if (cone_misses_ball(P.cam.pos, pcone, sn.c, sn.rp)) pmask &= ~(1u << n);
             }
         }
         if (shadow_cull && ((in_left && r2 <= tx0) || (in_right && r0 >= sx1) || (in_top && r3 <= ty0) || (in_bottom && r1 >= sy1)))
@@ -1264,13 +1276,27 @@ DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, uint
                 KDbl sr = rects_s + 4 * n;
                 if ((sr[1] < fx0 - padx) | (sr[0] > fx1 + padx) | (sr[3] < fz0 - padz) | (sr[2] > fz1 + padz)) smask0 &= ~(1u << n);
             }
-            /* a CsgDiff(L, Sphere) node that no shadow ray towards light 0 from the footprint can hit (csg_void.h) */
+            /* a CsgDiff(L, Sphere) node, or a Sphere node, that no shadow ray towards light 0 from the footprint can
+             * hit (csg_void.h); the sphere test only for footprints within the reach its margin was derived for */
+            PyramidCone scone;
+            bool have_scone = false;
+            const auto shadow_cone = [&]() {
+                double sdir[4][3];
+                footprint_dirs(V.light0, gy, fx0, fx1, fz0, fz1, sdir);
+                return pyramid_cone(sdir);
+            };
             for (uint32_t j = 0; j < V.n; ++j) {
                 const VoidNode &vn = V.v[j];
                 if (!((smask0 >> vn.node) & 1u) || !(vn.flags & 2u)) continue;
-                double sdir[4][3];
-                footprint_dirs(V.light0, gy, fx0, fx1, fz0, fz1, sdir);
-                if (pyramid_void(V.light0, sdir, vn)) smask0 &= ~(1u << vn.node);
+                if (!have_scone) { scone = shadow_cone(); have_scone = true; }
+                if (pyramid_void(V.light0, scone, vn)) smask0 &= ~(1u << vn.node);
+            }
+            const bool in_reach = fmax(fabs(fx0), fabs(fx1)) + fmax(fabs(fz0), fabs(fz1)) + fabs(gy) <= S.reach;
+            for (uint32_t j = 0; j < S.n; ++j) {
+                const SphereNode &sn = S.s[j];
+                if (!in_reach || !((smask0 >> sn.node) & 1u) || !(sn.flags & 2u)) continue;
+                if (!have_scone) { scone = shadow_cone(); have_scone = true; }
+                if (cone_misses_ball(V.light0, scone, sn.c, sn.rp)) smask0 &= ~(1u << sn.node);
             }
         }
         ground_only = (smask0 & (0xFFFFFFFFu >> (32u - nn))) == (1u << gnode);

@@ -1,7 +1,8 @@
 /*
- * csg_void.h — per-tile "void" test for a CsgDiff(L, Sphere) node: the tile's rays provably get no hit on it.
- * Shared by the mask pre-pass (c2rt_trace.inc: tile_mask_entry), the host that fills VoidCull
- * (c2rt_api.cpp: prepare_tile_masks) and the host check library of the tests (tests/csg_void_check.cpp).
+ * csg_void.h — per-tile "void" test for a CsgDiff(L, Sphere) node, and silhouette test for a Sphere node (further
+ * down): the tile's rays provably get no hit on it.  Shared by the mask pre-pass (c2rt_trace.inc: tile_mask_entry),
+ * the host that fills VoidCull and SphereCull (c2rt_api.cpp: prepare_tile_masks) and the host check libraries of the
+ * tests (tests/csg_void_check.cpp, tests/sphere_cull_check.cpp).
  *
  * Why a void ray gets no hit: CsgOp.intersect for Diff(L, R) (rt/geometry.d:292-332), R a Sphere.  Suppose that
  * for one ray (1) findAllIntersections(R) yields exactly two hits R0 < R1, or one hit R1 with the origin inside
@@ -65,39 +66,64 @@ C2RT_VOID_FN double void_abs(double x) { return x < 0 ? -x : x; }
 /* margin of the ball for coordinates of magnitude up to `scale` (sum of |centre|, R, |eye|, |light| max-norms) */
 C2RT_VOID_FN double void_margin(double scale) { return 1e-5 + 1e-6 * scale; }
 
-/* true if every point of box(v) inside the pyramid (apex, dir[0..3]) lies in the ball (c, sqrt(r2)): the rays of the
- * pyramid get no hit on the node (header comment).  false = keep the node.
- *
- * The test bounds box ∩ pyramid by a thick segment (a vertex enumeration of the polytope is exact but ~20x the
- * work, a latency chain the single-lane-per-tile pre-pass cannot hide).  u = the pyramid's axis (unit), tan_t =
- * max over the four edges of lateral / axial component: the circular cone of that half angle around u is convex
- * and holds the four edges, hence the pyramid.  A point p of the pyramid at depth t = (p - apex).u is within
- * rho(t) = t tan_t of q = apex + t u.  If p is also in the box, t <= t_far (the deepest box corner) and q lies in
- * the box grown by rho = t_far tan_t on every axis, so on the axis' slab interval [t0, t1] of that grown box.  The
- * ball is convex: both ends of that segment within R - m - rho of c put the segment there, and every such p
- * within R - m.  The apex in the grown box, an empty or non-finite interval, or a pyramid of 90 degrees or more
- * (an edge with axial component <= 0) refuse. */
-C2RT_VOID_FN bool pyramid_void(const double apex[3], const double dir[4][3], const VoidNode &v)
+/* The circular cone around a pyramid (apex, dir[0..3]): u = the pyramid's axis (unit: the normalised sum of the unit
+ * edges), tan_t = max over the four edges of lateral / axial component.  The cone of that half angle around u is
+ * convex and holds the four edges, hence the pyramid.  ok = false for a pyramid of 90 degrees or more (an edge with
+ * axial component <= 0, or non-finite edges): every test refuses.  A tile computes it once per pyramid. */
+struct PyramidCone {
+    double u[3];
+    double tan_t;
+    bool ok;
+};
+
+C2RT_VOID_FN PyramidCone pyramid_cone(const double dir[4][3])
 {
+    PyramidCone k;
     double u[3] = {0, 0, 0};
-    for (int k = 0; k < 4; ++k) {
-        const double l2 = dir[k][0] * dir[k][0] + dir[k][1] * dir[k][1] + dir[k][2] * dir[k][2];
+    for (int e = 0; e < 4; ++e) {
+        const double l2 = dir[e][0] * dir[e][0] + dir[e][1] * dir[e][1] + dir[e][2] * dir[e][2];
         const double il = 1.0 / sqrt(l2);
-        for (int i = 0; i < 3; ++i) u[i] += dir[k][i] * il;
+        for (int i = 0; i < 3; ++i) u[i] += dir[e][i] * il;
     }
     {
         const double il = 1.0 / sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
         for (int i = 0; i < 3; ++i) u[i] *= il;
     }
     double tan_t = 0;
-    for (int k = 0; k < 4; ++k) {
-        const double a = dir[k][0] * u[0] + dir[k][1] * u[1] + dir[k][2] * u[2];
-        const double e0 = dir[k][0] - a * u[0], e1 = dir[k][1] - a * u[1], e2 = dir[k][2] - a * u[2];
+    bool ok = true;
+    for (int e = 0; e < 4; ++e) {
+        const double a = dir[e][0] * u[0] + dir[e][1] * u[1] + dir[e][2] * u[2];
+        const double e0 = dir[e][0] - a * u[0], e1 = dir[e][1] - a * u[1], e2 = dir[e][2] - a * u[2];
         const double lat = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
-        if (!(a > 0)) return false;
+        ok = ok && a > 0;
         const double t = lat / a;
         tan_t = t > tan_t ? t : tan_t;
     }
+    for (int i = 0; i < 3; ++i) k.u[i] = u[i];
+    k.tan_t = tan_t;
+    k.ok = ok;
+    return k;
+}
+
+/* true if every point of box(v) inside the pyramid (apex, cone k around it) lies in the ball (c, sqrt(r2)): the rays
+ * of the pyramid get no hit on the node (header comment).  false = keep the node.
+ *
+ * The test bounds box ∩ pyramid by a thick segment (a vertex enumeration of the polytope is exact but ~20x the
+ * work, a latency chain the single-lane-per-tile pre-pass cannot hide).  A point p of the pyramid at depth
+ * t = (p - apex).u is within rho(t) = t tan_t of q = apex + t u (pyramid_cone).  If p is also in the box, t <= t_far
+ * (the deepest box corner) and q lies in the box grown by rho = t_far tan_t on every axis, so on the axis' slab
+ * interval [t0, t1] of that grown box.  Every such p therefore lies in the conical frustum around the axis between
+ * the depths t0 and t1, of radius rho(t) = t tan_t at depth t: a convex set whose extreme points are its two rim
+ * circles, and a point of the rim at t_e is within |q(t_e) - c| + rho(t_e) of c.  The ball is convex: |q(t_e) - c|
+ * <= R - m - rho(t_e) at both ends puts the frustum, and every such p, within R - m.  (Until round 6 both ends were
+ * tested against rho(t_far), the cylinder around the frustum: 2.7 % fewer void tiles on lecture5 at 4K,
+ * profiles/r06_variants.md.)  The apex in the grown box, an empty or non-finite interval, or a pyramid of 90 degrees
+ * or more refuse. */
+C2RT_VOID_FN bool pyramid_void(const double apex[3], const PyramidCone &k, const VoidNode &v)
+{
+    if (!k.ok) return false;
+    const double *u = k.u;
+    const double tan_t = k.tan_t;
     double t_far = 0;
     for (int q = 0; q < 8; ++q) {
         const double t = ((q & 1) ? v.hi[0] : v.lo[0]) * u[0] - apex[0] * u[0] + ((q & 2) ? v.hi[1] : v.lo[1]) * u[1] -
@@ -121,15 +147,89 @@ C2RT_VOID_FN bool pyramid_void(const double apex[3], const double dir[4][3], con
         }
     }
     if (apex_in || !(t0 <= t1) || !(t1 < 1e300)) return false;
-    const double r = sqrt(v.r2) - rho;
-    if (!(r > 0)) return false;
     bool ok = true;
     for (int e = 0; e < 2; ++e) {
         const double t = e ? t1 : t0;
+        const double r = sqrt(v.r2) - (t * tan_t * (1 + 1e-9) + 1e-9 * t); /* R - m - rho(t_e) */
+        if (!(r > 0)) return false;
         const double d0 = apex[0] + u[0] * t - v.c[0], d1 = apex[1] + u[1] * t - v.c[1], d2 = apex[2] + u[2] * t - v.c[2];
         ok = ok && d0 * d0 + d1 * d1 + d2 * d2 <= r * r * (1 - 1e-12);
     }
     return ok;
+}
+
+C2RT_VOID_FN bool pyramid_void(const double apex[3], const double dir[4][3], const VoidNode &v)
+{
+    return pyramid_void(apex, pyramid_cone(dir), v);
+}
+
+/* ---- Sphere silhouette ---------------------------------------------------------------------------------------
+ * A node whose root geometry is a Sphere (c, R) under an identity matrix: the tile's rays provably get no hit on it
+ * when none of them passes within R + m of c.
+ *
+ * Why such a ray gets no hit: Sphere.intersect (rt/geometry.d:92-125) solves A t^2 + B t + C = 0 with A = dir.dir,
+ * B = 2 dir.(o - c), C = |o - c|^2 - R^2 and reports no hit when B^2 - 4 A C is negative.  For a unit direction the
+ * exact value is -4 (d^2 - R^2), d the ray's distance from c; d >= R + m makes it <= -4 (2 R m + m^2) < -8 R m.
+ * The computed value differs by the rounding of B^2 and 4 A C, each a few ulp of 4 |o - c|^2, of the direction's
+ * normalisation (|dir|^2 = 1 +- 1e-15: relative, the same order) and of the node offset's subtraction from the
+ * origin (1e-16 |o| in o, 1e-16 |o| |o - c| in C): together below 1e-14 |o - c|^2.  With scale = the frame's sum of
+ * max-norms (the largest R + |c| of the tested balls, the eye, light 0: SphereCull::reach), a primary ray has
+ * |o - c| <= scale; a shadow ray starts on the tile's footprint, which near the horizon is arbitrarily far away, so
+ * the shadow test refuses footprints that reach beyond `reach` from the origin (|o - c| <= 2 scale).  m >= 1e-9
+ * scale^2 / R puts 8 R m >= 8e-9 scale^2, five orders of magnitude above 4e-14 scale^2; the terms of void_margin
+ * (1e-5 + 1e-6 scale) on top cover the shadow origins' 1e-6 step off the ground and the rays' own rounding as they
+ * do for the void test.  The margin grows with scale^2 / R: a small ball far from the origin is culled late or
+ * not at all, never wrongly.
+ *
+ * The rays: the same two pyramids as the void test's — primary: apex = eye, the tile's corner rays widened by 1 px
+ * (tile_corner_dirs; the AA taps reach 0.6 px); shadow towards light 0 of a primary-ground tile: apex = light
+ * through the padded footprint (footprint_dirs), which holds the shadow segments up to the light.  Beyond the light
+ * a shadow ray leaves that pyramid (Sphere.intersect itself does not stop at the light), so the shadow test is only granted where the padded
+ * ball lies strictly on the ground's side of the light's height (SphereNode::flags bit 1, host): no ray continues
+ * into it after passing the light.  Each pyramid lies in its circular cone (pyramid_cone); cone_misses_ball decides
+ * for the cone. */
+constexpr int kMaxSphereNodes = 4; /* Sphere nodes tested per frame (the first ones among the culled) */
+
+struct SphereNode {
+    double c[3];                   /* world centre (object centre + node offset) */
+    double rp;                     /* R + m, m = sphere_margin */
+    uint32_t node;                 /* node index (< kMaxCullNodes) */
+    uint32_t flags;                /* bit 0: primary test; bit 1: shadow test towards light 0 */
+};
+
+/* the per-frame sphere argument of the mask pre-pass (tile_masks_kernel), next to VoidCull (whose light0 it uses) */
+struct SphereCull {
+    uint32_t n, pad;
+    double reach;                  /* the scale the margins were derived for: the shadow test's footprint limit */
+    SphereNode s[kMaxSphereNodes];
+};
+
+/* margin of a ball of radius R for coordinates of magnitude up to `scale` (derivation above) */
+C2RT_VOID_FN double sphere_margin(double scale, double R) { return void_margin(scale) + 1e-9 * scale * scale / R; }
+
+/* true only if no ray of the cone k around `apex` (any point apex + t w, t >= 0, w within the cone's half angle of
+ * u) passes within rp of c: the distance from c to the solid cone exceeds rp.  In the plane through the axis and c,
+ * with a = (c - apex).u and lat = the distance of c from the axis, the cone's rim is the ray (cos, sin) of the half
+ * angle theta, tan(theta) = tan_t.  Where c projects onto that rim ray (a + lat tan_t >= 0) its distance from the
+ * cone is lat cos - a sin = (lat - a tan_t) / sqrt(1 + tan_t^2) — which is > rp exactly when the angle between
+ * c - apex and u exceeds theta + asin(rp / |c - apex|) — and where it projects behind the apex (the ball lies
+ * wholly behind it) the distance is |c - apex|.  No inverse trigonometry.  Refuses (false = keep the node): the
+ * apex inside the padded ball, a pyramid of 90 degrees or more, any non-finite operand.  Rounding of u, tan_t, a
+ * and lat is relative 1e-15 of |c - apex|: 1e-9 relative and 1e-9 |c - apex| absolute to spare. */
+C2RT_VOID_FN bool cone_misses_ball(const double apex[3], const PyramidCone &k, const double c[3], double rp)
+{
+    if (!k.ok) return false;
+    const double w0 = c[0] - apex[0], w1 = c[1] - apex[1], w2 = c[2] - apex[2];
+    const double a = w0 * k.u[0] + w1 * k.u[1] + w2 * k.u[2];
+    const double e0 = w0 - a * k.u[0], e1 = w1 - a * k.u[1], e2 = w2 - a * k.u[2];
+    const double lat = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+    const double d = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+    const double sec = sqrt(1.0 + k.tan_t * k.tan_t);
+    if (!(d < 1e150) || !(rp < 1e150) || !(rp > 0) || !(sec < 1e150)) return false; /* non-finite or absurd */
+    const double need = rp * (1 + 1e-9) + 1e-9 * d;
+    if (!(d > need)) return false; /* the apex in (or at) the padded ball */
+    if (a + lat * k.tan_t >= 0) return lat - a * k.tan_t > need * sec;
+    return true; /* behind the apex, and farther from it than rp */
 }
 
 /* One tile's primary pyramid: the eye and the four corner rays of the pixel rectangle [x0 - 1, x1 + 1] x
