@@ -22,6 +22,7 @@ TAPS_1, TAPS_REF5, TAPS_4 = 1, 5, 4
 ABI_VERSION = 1
 MAX_CSG_DEPTH = 4
 MAX_CSG_HITS = 8
+MAX_BATCH_FRAMES = 256
 
 _i32p = C.POINTER(C.c_int32)
 _u32p = C.POINTER(C.c_uint32)
@@ -170,6 +171,8 @@ C2RT_SYMBOLS = {
     "c2rt_local_rows": (C.c_uint32, [_OPTS_P]),
     "c2rt_render_frame": (C.c_int, [_VP, _CAM_P, _OPTS_P, _VP, _VP]),
     "c2rt_render_frame_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, _VP, _VP]),
+    "c2rt_render_frames": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, _VP, _VP]),
+    "c2rt_render_frames_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, _VP, _VP]),
     "c2rt_pin_host_buffer": (C.c_int, [_VP, _VP, C.c_size_t]),
     "c2rt_unpin_host_buffer": (C.c_int, [_VP, _VP]),
     "c2rt_get_ray_stats": (C.c_int, [_VP, C.POINTER(RayStats)]),

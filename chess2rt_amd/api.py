@@ -196,6 +196,29 @@ class Context:
         """Enqueue a render into device memory (e.g. tensor.data_ptr())."""
         self._check(self._lib.c2rt_render_frame_device(self._h, C.byref(cam), C.byref(opts), C.c_void_p(out_ptr), C.c_void_p(stream)))
 
+    @staticmethod
+    def _camera_array(cams):
+        """(contiguous ctypes array, count) of a sequence of CameraFrame or of a ctypes array of them"""
+        if isinstance(cams, C.Array):
+            return cams, len(cams)
+        cams = list(cams)
+        return (CameraFrame * max(len(cams), 1))(*cams), len(cams)
+
+    def renderFrames(self, cams, opts, stop_flag=None):
+        """One call for a batch of cameras of the uploaded scene (c2rt_render_frames): a new host array of shape
+        (len(cams), local_rows, W, 3); frame i holds the bits renderFrame(cams[i], opts) returns.  No depth of field,
+        stereo, count_rays or prepass_bucket in a batch (C2rtError, status ERR_UNSUPPORTED)."""
+        arr, n = self._camera_array(cams)
+        out = np.empty((n, self.localRows(opts), opts.width, 3), dtype=np.float32)
+        stop = stop_flag.ctypes.data_as(C.c_void_p) if stop_flag is not None else None
+        self._check(self._lib.c2rt_render_frames(self._h, arr, n, C.byref(opts), out.ctypes.data_as(C.c_void_p), stop))
+        return out
+
+    def renderFramesDevice(self, cams, opts, out_ptr, stream=0):
+        """Enqueue the batch into device memory (len(cams) * local_rows * W * 3 floats at out_ptr) on `stream`."""
+        arr, n = self._camera_array(cams)
+        self._check(self._lib.c2rt_render_frames_device(self._h, arr, n, C.byref(opts), C.c_void_p(out_ptr), C.c_void_p(stream)))
+
     def rayStats(self):
         s = RayStats()
         self._check(self._lib.c2rt_get_ray_stats(self._h, C.byref(s)))

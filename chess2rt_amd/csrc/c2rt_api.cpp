@@ -32,7 +32,10 @@ constexpr int kMaxChunks = 16;     /* row chunks of a host-output frame */
  * stream handle (compared, never dereferenced).  Frames on one stream are in order and share a slot; frames on
  * different streams touch different slots, so they need no ordering at all: no event per frame (an event record
  * is a ~2 us gap in the queue: 6 % of a 1080p lecture4 frame) and frames of one context may overlap.  A 17th
- * stream recycles the least recently used slot after a device sync (the one place a frame call can block). */
+ * stream recycles the least recently used slot after a device sync (the one place a single-frame call can block).
+ * A batch (c2rt_render_frames_device) uses the same slot with the tables multiplied: n_frames mask tables and retry
+ * lists side by side in the same two allocations (a single frame on that stream uses the first of each; the stream
+ * orders them), plus the device table of the frames' parameter blocks.  Everything grows, nothing shrinks. */
 constexpr int kScratchSlots = 16;
 struct FrameScratch {
     const void *key = nullptr;
@@ -42,6 +45,10 @@ struct FrameScratch {
     size_t tile_mask_entries = 0;
     uint32_t *retry_list = nullptr; /* RenderParams::retry_list: [0] count, then tile (block) indices */
     size_t retry_words = 0;
+    /* batches: one RenderParams per frame (twice for nested CSG: first pass, retry pass), then one BatchCull per
+     * frame; uploaded per call with one stream-ordered copy from ctx->batch_host */
+    char *batch_table = nullptr;
+    size_t batch_bytes = 0;
 };
 
 /* Environment hooks (A/B measurement and test knobs: C2RT_EXACT, C2RT_NO_IDN, C2RT_DEBUG_CULL, C2RT_CSG_FIRST_CAP,
@@ -110,6 +117,9 @@ struct c2rt_ctx {
     uint8_t *srgb_lut = nullptr;   /* [4097] */
     FrameScratch scratch[kScratchSlots];
     uint64_t scratch_tick = 0;
+    /* host image of a batch's device table.  Pageable on purpose: a stream-ordered copy from pageable memory has
+     * read its source when the call returns, so the next batch call may overwrite it — no ring, no event */
+    std::vector<char> batch_host;
     uint32_t *tile_stats = nullptr; /* diagnostics (c2rt_debug_set_tile_stats): caller-owned device buffer */
     bool counters_valid = false;
     /* The ray counters are the one per-frame resource shared by all streams: COUNTED frames (opts->count_rays, a
@@ -756,6 +766,115 @@ int render_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render
     return C2RT_OK;
 }
 
+/* grows one of a scratch slot's allocations to `bytes` (never shrinks; hipFree waits for whatever still reads it) */
+template <typename T>
+hipError_t grow_scratch(T **buf, size_t *have, size_t want, size_t elem_bytes)
+{
+    if (want <= *have) return hipSuccess;
+    if (*buf) { (void)hipFree(*buf); *buf = nullptr; *have = 0; }
+    const hipError_t e = hipMalloc(reinterpret_cast<void **>(buf), want * elem_bytes);
+    if (e == hipSuccess) *have = want;
+    return e;
+}
+
+/* Why a batch refuses (cams, opts), decided before anything is enqueued; C2RT_OK otherwise. */
+int check_batch_args(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts)
+{
+    if (!cams || !opts) return fail(ctx, C2RT_ERR_INVALID_ARG, "null cameras or options");
+    if (n_frames > C2RT_MAX_BATCH_FRAMES)
+        return fail(ctx, C2RT_ERR_LIMIT, "%u frames in one batch, at most %u", n_frames, (unsigned)C2RT_MAX_BATCH_FRAMES);
+    if (!ctx->peers.empty())
+        return fail(ctx, C2RT_ERR_UNSUPPORTED, "a multi-device context renders frame by frame: no batch call");
+    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the counters belong to one frame, render counted frames one by one");
+    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: previews are rendered frame by frame");
+    for (uint32_t i = 0; i < n_frames; ++i) {
+        if (cams[i].dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "camera %u has depth of field: render it frame by frame", i);
+        if (cams[i].stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "camera %u is a stereo camera: render it frame by frame", i);
+        if (const int st = check_frame_args(ctx, &cams[i], opts)) return st;
+    }
+    return C2RT_OK;
+}
+
+/* n_frames frames of one scene under one set of options with one mask pre-pass launch and one frame launch (two for
+ * nested CSG), frame i into out_dev + i * local_rows * width * 3.  Each frame's parameter block is what render_device
+ * would launch it with — its own culling rectangles, row rotation, exact switch, mask table, retry list and output —
+ * so the frames hold the bits of n single-frame calls; the kernels read block blockIdx.y of the table in HBM.
+ * The arguments have passed check_batch_args. */
+int render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
+                         float *out_dev, hipStream_t stream)
+{
+    const int levels = ctx->csg_levels;
+    const KernelVariant variant = variant_of(ctx, &cams[0]);
+    const bool nested = levels >= 2;
+    /* the test hook of launch_frame, in the diagnostics build */
+    static const int forced_cap = [] { const char *e = diag_env("C2RT_CSG_FIRST_CAP"); return e ? std::atoi(e) : 0; }();
+    int first_cap = kCsgFirstCap(levels);
+    if (forced_cap > 0 && nested) first_cap = forced_cap < kCsgFullCap(levels) ? forced_cap : kCsgFullCap(levels);
+    const bool retry = nested && first_cap < kCsgFullCap(levels);
+
+    const size_t n = n_frames, n_blocks_tables = retry ? 2 * n : n;
+    const size_t culls_at = n_blocks_tables * sizeof(RenderParams), bytes = culls_at + n * sizeof(BatchCull);
+    static_assert(sizeof(RenderParams) % 8 == 0 && alignof(BatchCull) <= 8, "BatchCull follows the parameter blocks");
+    ctx->batch_host.resize(bytes);
+    RenderParams *hp = reinterpret_cast<RenderParams *>(ctx->batch_host.data());
+    BatchCull *hc = reinterpret_cast<BatchCull *>(ctx->batch_host.data() + culls_at);
+
+    bool any_masks = false;
+    for (size_t i = 0; i < n; ++i) {
+        RenderParams &p = hp[i];
+        fill_params(ctx, &cams[i], opts, p);
+        p.csg_cap = levels == 0 ? 0u : (uint32_t)first_cap;
+        p.redo_counter = ctx->counters + 3;
+        p.mask_row0 = p.row_offset;
+        p.mask_rows = p.local_rows;
+        any_masks = any_masks || p.n_cull != 0;
+    }
+    const RenderParams &p0 = hp[0];
+    if (p0.local_rows == 0) return C2RT_OK;
+    const size_t frame_floats = (size_t)p0.local_rows * p0.width * 3;
+    const size_t entries = tile_mask_entries(p0);
+    const size_t blocks = (size_t)p0.blocks_x * ((p0.tiles_y + 7u) / 8u * 8u);
+
+    FrameScratch &sc = scratch_for(ctx, stream);
+    hipError_t e = grow_scratch(&sc.batch_table, &sc.batch_bytes, bytes, 1);
+    if (e == hipSuccess && any_masks) e = grow_scratch(&sc.tile_masks, &sc.tile_mask_entries, entries * n, 8 * sizeof(uint32_t));
+    if (e == hipSuccess && nested) e = grow_scratch(&sc.retry_list, &sc.retry_words, (blocks + 1) * n, sizeof(uint32_t));
+    if (e != hipSuccess) return fail(ctx, C2RT_ERR_HIP, "batch scratch: %s", hipGetErrorString(e));
+
+    for (size_t i = 0; i < n; ++i) {
+        RenderParams &p = hp[i];
+        p.out = out_dev + i * frame_floats;
+        if (p.n_cull) {
+            p.tile_masks = sc.tile_masks + i * entries * 8;
+            p.mask_entries = (uint32_t)entries;
+            hc[i].v = void_cull_of(ctx, p, ~0u);
+            hc[i].s = sphere_cull_of(ctx, p, ctx->sphere_flags_mask);
+        } else {
+            std::memset(&hc[i], 0, sizeof hc[i]);
+        }
+        if (nested) {
+            p.retry_list = sc.retry_list + i * (blocks + 1);
+            p.retry_max = (uint32_t)blocks;
+        }
+        if (retry) {
+            hp[n + i] = p;
+            hp[n + i].retry_mode = 1;
+            hp[n + i].csg_cap = (uint32_t)kCsgFullCap(levels);
+        }
+    }
+    const RenderParams *table_dev = reinterpret_cast<const RenderParams *>(sc.batch_table);
+    const BatchCull *culls_dev = reinterpret_cast<const BatchCull *>(sc.batch_table + culls_at);
+    HIP_TRY(ctx, hipMemcpyAsync(sc.batch_table, ctx->batch_host.data(), bytes, hipMemcpyHostToDevice, stream));
+    int r = 0;
+    if (any_masks) r = launch_tile_masks_batch(p0, table_dev, culls_dev, n_frames, stream);
+    if (r != 0) return fail(ctx, C2RT_ERR_HIP, "tile-mask pre-pass launch: %s", hipGetErrorString((hipError_t)r));
+    if (nested) HIP_TRY(ctx, hipMemsetAsync(sc.retry_list, 0, (blocks + 1) * n * sizeof(uint32_t), stream));
+    r = launch_render_batch(p0, variant, table_dev, n_frames, stream);
+    if (r == 0 && retry) r = launch_render_batch(hp[n], variant, table_dev + n, n_frames, stream);
+    if (r != 0) return fail(ctx, C2RT_ERR_HIP, "render kernel launch: %s", hipGetErrorString((hipError_t)r));
+    return C2RT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -887,6 +1006,7 @@ void c2rt_destroy(c2rt_ctx *ctx)
     for (FrameScratch &f : ctx->scratch) {
         if (f.tile_masks) (void)hipFree(f.tile_masks);
         if (f.retry_list) (void)hipFree(f.retry_list);
+        if (f.batch_table) (void)hipFree(f.batch_table);
     }
     delete ctx;
 }
@@ -1659,6 +1779,37 @@ int c2rt_render_frame(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_re
     if (!ctx->peers.empty()) return render_to_host_multi(ctx, cam, opts, out_rgb, nullptr, stop_flag);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return render_to_host(ctx, cam, opts, out_rgb, nullptr, stop_flag);
+}
+
+int c2rt_render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
+                              float *out_rgb_dev, void *hip_stream)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (n_frames == 0) return C2RT_OK;
+    if (const int st = check_batch_args(ctx, cams, n_frames, opts)) return st;
+    if (!out_rgb_dev) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->counters_valid = false;
+    return render_frames_device(ctx, cams, n_frames, opts, out_rgb_dev, static_cast<hipStream_t>(hip_stream));
+}
+
+int c2rt_render_frames(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
+                       float *out_rgb, const volatile uint8_t *stop_flag)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (n_frames == 0) return C2RT_OK;
+    if (const int st = check_batch_args(ctx, cams, n_frames, opts)) return st;
+    if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    if (stop_flag && *stop_flag) return fail(ctx, C2RT_ERR_CANCELLED, "stop requested before the batch");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n_frames * c2rt_local_rows(opts) * opts->width * 3 * sizeof(float);
+    if (bytes == 0) return C2RT_OK;
+    if (const int st = ensure_staging(ctx, bytes)) return st;
+    ctx->counters_valid = false;
+    if (const int st = render_frames_device(ctx, cams, n_frames, opts, ctx->frame, ctx->stream)) return st;
+    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->frame, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return C2RT_OK;
 }
 
 /* nothing of this context (any stream of any device slot) may still be copying into a buffer whose pages are

@@ -265,6 +265,22 @@ template <> int launch_render_level<3>(const RenderParams &, bool, void *);
 template <> int launch_render_level<4>(const RenderParams &, bool, void *);
 int launch_render(const RenderParams &p, const KernelVariant &v, void *stream);
 int launch_probe(const RenderParams &p, const KernelVariant &v, void *stream);
+/* A batch of frames of one scene under one set of options (c2rt_render_frames_device): table_dev holds one
+ * RenderParams per frame in device memory and the kernels take block blockIdx.y of it; p0 is the host copy of any of
+ * them (grid, stack size and instance are the same for all).  culls_dev: each frame's pre-pass tests. */
+struct BatchCull {
+    VoidCull v;
+    SphereCull s;
+};
+template <int LEVELS>
+int launch_render_batch_level(const RenderParams &p0, const RenderParams *table_dev, uint32_t n_frames, void *stream);
+template <> int launch_render_batch_level<0>(const RenderParams &, const RenderParams *, uint32_t, void *);
+template <> int launch_render_batch_level<1>(const RenderParams &, const RenderParams *, uint32_t, void *);
+template <> int launch_render_batch_level<2>(const RenderParams &, const RenderParams *, uint32_t, void *);
+template <> int launch_render_batch_level<3>(const RenderParams &, const RenderParams *, uint32_t, void *);
+template <> int launch_render_batch_level<4>(const RenderParams &, const RenderParams *, uint32_t, void *);
+int launch_render_batch(const RenderParams &p0, const KernelVariant &v, const RenderParams *table_dev, uint32_t n_frames, void *stream);
+int launch_tile_masks_batch(const RenderParams &p0, const RenderParams *table_dev, const BatchCull *culls_dev, uint32_t n_frames, void *stream);
 /* entries of RenderParams::tile_masks a launch of `p` reads (4 words each, twice that with several culled lights);
  * the pre-pass that fills them (vc: the frame's CsgDiff void tests, csg_void.h) */
 size_t tile_mask_entries(const RenderParams &p);

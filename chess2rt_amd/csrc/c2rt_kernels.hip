@@ -216,6 +216,43 @@ __global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(0, DOF, false) rend
 /* (no identity-matrix variant of these: single-plane scenes take the straight-line ground trace, which has no matrix
  * code to lose — measured: zaphod x4 0.601 vs 0.606 ms, DOF 4.583 vs 4.582) */
 
+/* Batch entries (c2rt_render_frames_device): the same trace over a TABLE of parameter blocks in HBM, one per frame,
+ * blockIdx.y = frame.  A tile's whole identity is (parameter block, block index): blockIdx.x is what it is in the
+ * single-frame launch of that frame (so the tile lands on the same XCD class), and the block is read through a
+ * constant-address-space pointer exactly as the single-frame kernels re-read their kernel-argument segment — scalar
+ * loads, no VGPR.  The pointer goes through an empty asm so that the optimiser cannot fold the address-space casts
+ * back to the global pointer it was made from (loads through that one would be vector loads: the kernel stores to
+ * global memory, so nothing proves them invariant).  Only the instances a batch can reach: no counting, no depth of
+ * field.  Register budget, scratch and occupancy equal the single-frame twins' (profiles/frame_batch.md). */
+DEV KArgs batch_block(const RenderParams *table)
+{
+    KArgs K = (KArgs)table + blockIdx.y;
+    asm volatile("" : "+s"(K));
+    return K;
+}
+
+template <int LEVELS, bool MLC>
+__global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(LEVELS, 0, MLC) render_kernel_batch(const RenderParams *table)
+{
+    const KArgs K = batch_block(table);
+    render_body<LEVELS, 0, MLC, 0, false>(*(const RenderParams *)K, K);
+}
+
+template <int LEVELS>
+__global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(LEVELS, 0, false) render_kernel_idn_batch(const RenderParams *table)
+{
+    const KArgs K = batch_block(table);
+    render_body<LEVELS, 0, false, lean::kSpecIdentity, false>(*(const RenderParams *)K, K);
+}
+
+#if C2RT_UNIT == 0 /* (not a template: it would be compiled into every unit) */
+__global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(0, 0, false) render_kernel_planes_batch(const RenderParams *table)
+{
+    const KArgs K = batch_block(table);
+    render_body<0, 0, false, lean::kSpecPlanes, false>(*(const RenderParams *)K, K);
+}
+#endif
+
 /* renderPixel — rt/renderer.d:46-57: one lane, one sample, full trace result */
 template <int LEVELS, int DOF>
 __global__ void __launch_bounds__(kWave) probe_kernel(const RenderParams P)
@@ -310,6 +347,34 @@ __global__ void __launch_bounds__(256) tile_masks_kernel(const RenderParams P, c
     reinterpret_cast<u4_t *>(table)[slot] = v;
     if (P.n_cull_lights > 1u) reinterpret_cast<u4_t *>(table)[(size_t)P.mask_entries + slot] = w; /* lights 1..3 */
 }
+
+/* The same for every frame of a batch in one launch: blockIdx.y = frame; the frame's RenderParams and its VoidCull /
+ * SphereCull come from the tables (scalar loads, as from the kernel-argument segment above), its mask table from its
+ * own RenderParams::tile_masks.  Frames without culling rectangles have no table and return at once. */
+__global__ void __launch_bounds__(256) tile_masks_batch_kernel(const RenderParams *table, const BatchCull *culls)
+{
+    const KArgs K = batch_block(table);
+    const BatchCull C2RT_K *C = (const BatchCull C2RT_K *)culls + blockIdx.y;
+    asm volatile("" : "+s"(C));
+    const RenderParams &P = *(const RenderParams *)K;
+    if (!P.n_cull || !P.tile_masks) return;
+    const uint32_t tile_rows = (P.mask_rows + kTileH - 1) / kTileH;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t cols = P.blocks_x * kWavesPerBlock;
+    const uint32_t trow = i / cols, tcol = i % cols;
+    if (trow >= tile_rows) return;
+    uint32_t m[8];
+    const BatchCull &B = *(const BatchCull *)C;
+    exact::tile_mask_entry(P, (exact::KArgs)K, B.v, B.s, trow, tcol, m);
+    typedef uint32_t __attribute__((ext_vector_type(4))) u4_t;
+    u4_t v, w;
+    v.x = m[0]; v.y = m[1]; v.z = m[2]; v.w = m[3];
+    w.x = m[4]; w.y = m[5]; w.z = m[6]; w.w = m[7];
+    const size_t slot = exact::tile_mask_slot(P, trow, tcol);
+    uint32_t *out = const_cast<uint32_t *>(P.tile_masks);
+    reinterpret_cast<u4_t *>(out)[slot] = v;
+    if (P.n_cull_lights > 1u) reinterpret_cast<u4_t *>(out)[(size_t)P.mask_entries + slot] = w; /* lights 1..3 */
+}
 #endif /* C2RT_UNIT == 5 */
 
 } // namespace
@@ -371,7 +436,55 @@ int launch_render_level<C2RT_UNIT>(const RenderParams &p, bool dof_or_stereo, vo
     return (int)hipGetLastError();
 }
 
+/* One launch for the frames of a batch: p0 = any frame's block (host copy; the grid, the stack size and the instance
+ * are the same for all of them: one scene, one set of options, no depth of field), table_dev = the n_frames blocks in
+ * HBM.  The instance is the one launch_render_level picks for an uncounted frame without depth of field. */
+template <>
+int launch_render_batch_level<C2RT_UNIT>(const RenderParams &p0, const RenderParams *table_dev, uint32_t n_frames, void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+#if C2RT_XCD_SWIZZLE
+    const uint32_t tiles_y_pad = (p0.tiles_y + 7u) / 8u * 8u;
+#else
+    const uint32_t tiles_y_pad = p0.tiles_y;
+#endif
+    const dim3 grid(p0.retry_mode ? 2048u : p0.blocks_x * tiles_y_pad, n_frames), block(kBlockThreads);
+    const size_t lds = (size_t)p0.csg_cap * kCsgLdsPerEntry * kWavesPerBlock;
+#if C2RT_UNIT == 0
+    if (p0.planes_only && p0.n_lights <= 1) {
+        hipLaunchKernelGGL(render_kernel_planes_batch, grid, block, lds, s, table_dev);
+        return (int)hipGetLastError();
+    }
+#endif
+    if (p0.n_lights > 1) hipLaunchKernelGGL((render_kernel_batch<C2RT_UNIT, true>), grid, block, lds, s, table_dev);
+    else if (p0.all_identity) hipLaunchKernelGGL((render_kernel_idn_batch<C2RT_UNIT>), grid, block, lds, s, table_dev);
+    else hipLaunchKernelGGL((render_kernel_batch<C2RT_UNIT, false>), grid, block, lds, s, table_dev);
+    return (int)hipGetLastError();
+}
+
 #else /* C2RT_UNIT == 5 */
+
+int launch_render_batch(const RenderParams &p0, const KernelVariant &v, const RenderParams *table_dev, uint32_t n_frames, void *stream)
+{
+    if (v.dof_or_stereo || p0.ray_counters || !n_frames || n_frames > 65535u) return (int)hipErrorInvalidValue;
+    switch (v.csg_levels) {
+    case 0: return launch_render_batch_level<0>(p0, table_dev, n_frames, stream);
+    case 1: return launch_render_batch_level<1>(p0, table_dev, n_frames, stream);
+    case 2: return launch_render_batch_level<2>(p0, table_dev, n_frames, stream);
+    case 3: return launch_render_batch_level<3>(p0, table_dev, n_frames, stream);
+    case 4: return launch_render_batch_level<4>(p0, table_dev, n_frames, stream);
+    default: return (int)hipErrorInvalidValue;
+    }
+}
+
+int launch_tile_masks_batch(const RenderParams &p0, const RenderParams *table_dev, const BatchCull *culls_dev, uint32_t n_frames, void *stream)
+{
+    const uint32_t tile_rows = (p0.mask_rows + kTileH - 1) / kTileH;
+    const uint32_t lanes = tile_rows * p0.blocks_x * kWavesPerBlock;
+    if (!lanes || !n_frames) return 0;
+    hipLaunchKernelGGL(tile_masks_batch_kernel, dim3((lanes + 255u) / 256u, n_frames), dim3(256), 0, static_cast<hipStream_t>(stream), table_dev, culls_dev);
+    return (int)hipGetLastError();
+}
 
 int launch_render(const RenderParams &p, const KernelVariant &v, void *stream)
 {

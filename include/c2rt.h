@@ -314,6 +314,55 @@ int c2rt_render_frame_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam,
                              const c2rt_render_opts *opts, float *out_rgb_dev,
                              void *hip_stream);
 
+/* ---- a batch of frames: many cameras, one scene, one call ----------------- */
+
+/* Most frames one batch call takes (the per-stream table of parameter blocks
+ * is 3.4 KiB per frame); C2RT_ERR_LIMIT beyond. */
+#define C2RT_MAX_BATCH_FRAMES 256
+
+/* `n_frames` frames of the uploaded scene, one per camera of `cams`, under ONE
+ * set of options (same size, taps and strip assignment), with one mask
+ * pre-pass launch and one frame launch for all of them (two frame launches for
+ * scenes with nested CsgOps) instead of that per frame.  Frame i occupies
+ * out_rgb_dev + i * local_rows * width * 3 floats and holds exactly the bits
+ * c2rt_render_frame_device(ctx, &cams[i], opts, ...) writes there.  Row strips
+ * (opts->strip_world > 1) work as in the single-frame call.
+ *
+ * Enqueued on `hip_stream` without a host sync and without leaving an event
+ * in the queue, under the per-stream scratch rules of c2rt_render_frame_device
+ * (the batch uses the stream's slot, with the tables multiplied): batches and
+ * single frames on one stream stay ordered and may follow each other without a
+ * sync; batches on different streams are independent.  When the call can
+ * BLOCK: the per-frame parameter table goes to the device with a stream-ordered
+ * copy from pageable memory, which the runtime stages before it returns — so
+ * the call may wait, on the host, until work enqueued EARLIER on `hip_stream`
+ * has drained (never for later work, never for other streams); it also blocks,
+ * like every frame call, when the stream's scratch has to grow (first call,
+ * more frames, a larger frame) or a 17th stream recycles a slot.  The host
+ * work of the batch (culling set-up of every camera) is done before that copy.
+ *
+ * Statuses, all decided before anything is enqueued (the output is untouched):
+ * n_frames == 0 is C2RT_OK and writes nothing (`cams` is not read); null `cams`
+ * or `opts`: C2RT_ERR_INVALID_ARG; n_frames > C2RT_MAX_BATCH_FRAMES:
+ * C2RT_ERR_LIMIT; C2RT_ERR_UNSUPPORTED, with c2rt_last_error naming the cause,
+ * for a camera with `dof` or `stereo_separation != 0` (those kernel instances
+ * carry lens state and have no batch twin), opts->count_rays (the counters
+ * belong to one frame), opts->prepass_bucket, and a multi-device context.
+ * All of these stay available frame by frame.  c2rt_get_exact_redos counts a
+ * batch's tiles exactly as it counts single frames'. */
+int c2rt_render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams,
+                              uint32_t n_frames, const c2rt_render_opts *opts,
+                              float *out_rgb_dev, void *hip_stream);
+
+/* The same into HOST memory (n_frames * local_rows * width * 3 floats):
+ * rendered into the context's staging buffer on the context's own stream and
+ * returned with one copy; blocks until the frames are there.  `stop_flag`
+ * (nullable) is polled once, before the launches: C2RT_ERR_CANCELLED then
+ * leaves `out_rgb` untouched. */
+int c2rt_render_frames(c2rt_ctx *ctx, const c2rt_camera_frame *cams,
+                       uint32_t n_frames, const c2rt_render_opts *opts,
+                       float *out_rgb, const volatile uint8_t *stop_flag);
+
 /* Ray counters of the last render call made with opts->count_rays = 1
  * (waits, on the host, for that frame to complete). */
 int c2rt_get_ray_stats(c2rt_ctx *ctx, c2rt_ray_stats *out);

@@ -89,6 +89,13 @@ extern (C) nothrow @nogc
                                 const shared(ubyte)* stop_flag);
     /// tiles rendered a second time through the IEEE divide / sqrt path (a cost indicator; 0 on sane scenes)
     int c2rt_get_exact_redos(c2rt_ctx*, ulong* outCount);
+    /// many cameras, one scene, one call: frame i at out + i * local_rows * width * 3 floats, the bits of the
+    /// single-frame calls; no depth of field / stereo / counted / preview frames (C2RT_ERR_UNSUPPORTED)
+    enum C2RT_MAX_BATCH_FRAMES = 256;
+    int c2rt_render_frames_device(c2rt_ctx*, const c2rt_camera_frame* cams, uint nFrames, const c2rt_render_opts*,
+                                  float* out_rgb_dev, void* hip_stream);
+    int c2rt_render_frames(c2rt_ctx*, const c2rt_camera_frame* cams, uint nFrames, const c2rt_render_opts*,
+                           float* out_rgb, const shared(ubyte)* stop_flag);
 }
 
 /// Owns the flat tables for one uploaded scene (GC memory; c2rt_upload_scene copies them).
