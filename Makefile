@@ -49,13 +49,13 @@ LIBNAME    := chess2rt_amd/libc2rt$(if $(VARIANT),_$(VARIANT)).so
 
 UNITS      := 0 1 2 3 4 5
 KOBJS      := $(foreach u,$(UNITS),$(BUILD)/c2rt_kernels_u$(u).o)
-HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/dsc.o $(BUILD)/scene.o $(BUILD)/host_api.o
+HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/scene.o $(BUILD)/host_api.o
 
 # diagnostics build of the same library: c2rt_api.cpp with the environment hooks compiled in (-DC2RT_DIAG=1), linked
 # over the SAME kernel objects; tests and scripts that need a hook load it with C2RT_LIB_VARIANT=diag
 DIAGNAME   := chess2rt_amd/libc2rt_diag.so
 
-all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so
+all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so
 
 $(BUILD):
 	mkdir -p $(BUILD)
@@ -64,8 +64,12 @@ $(BUILD):
 $(BUILD)/c2rt_kernels_u%.o: $(CSRC)/c2rt_kernels.hip $(CSRC)/c2rt_trace.inc $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/x87.h $(CSRC)/fp64_lean.h include/c2rt.h Makefile | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_u$*) $(EXTRA_KERNEL_FLAGS) -DC2RT_UNIT=$* -c $< -o $@
 
-$(BUILD)/c2rt_api.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
+$(BUILD)/c2rt_api.o: $(CSRC)/c2rt_api.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -c $< -o $@
+
+# the HIP-free planner (scene validation and packing, per-frame culling decisions)
+$(BUILD)/scene_plan.o: $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
+	g++ $(CXXFLAGS) -c $< -o $@
 
 $(BUILD)/%.o: $(CSRC)/host/%.cpp $(CSRC)/host/scene.hpp $(CSRC)/host/dsc.hpp include/c2rt.h include/c2rt_host.h | $(BUILD)
 	g++ $(CXXFLAGS) -c $< -o $@
@@ -73,7 +77,7 @@ $(BUILD)/%.o: $(CSRC)/host/%.cpp $(CSRC)/host/scene.hpp $(CSRC)/host/dsc.hpp inc
 $(LIBNAME): $(KOBJS) $(HOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
-$(BUILD)/c2rt_api_diag.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
+$(BUILD)/c2rt_api_diag.o: $(CSRC)/c2rt_api.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -DC2RT_DIAG=1 -c $< -o $@
 
 $(DIAGNAME): $(KOBJS) $(BUILD)/c2rt_api_diag.o $(filter-out $(BUILD)/c2rt_api.o,$(HOBJS))
@@ -91,6 +95,11 @@ tests/libcsg_void_check.so: tests/csg_void_check.cpp $(CSRC)/csg_void.h
 tests/libsphere_cull_check.so: tests/sphere_cull_check.cpp $(CSRC)/csg_void.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ $<
 
+# host build of the planner, without ROCm on the include path: the build itself enforces that scene_plan.cpp is HIP-free
+# (tests/test_scene_plan.py holds it to the restatements in scripts/csg_void_tiles.py and scripts/sphere_cull_tiles.py)
+tests/libscene_plan_check.so: tests/scene_plan_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h
+	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/scene_plan_check.cpp $(CSRC)/scene_plan.cpp
+
 # CPU oracle: plain C restatement of the reference algorithm (tests only)
 oracle/libc2rt_oracle.so: oracle/c2rt_oracle.c oracle/c2rt_oracle.h include/c2rt.h
 	$(CC) -O2 -std=gnu11 -fPIC -shared $(FPFLAGS) -Wall -o $@ oracle/c2rt_oracle.c -lm -lpthread
@@ -106,6 +115,6 @@ resource-usage: | $(BUILD)
 	    -c $(CSRC)/c2rt_kernels.hip -o $(BUILD)/ru_u$(u).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
 
 clean:
-	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so
+	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so
 
 .PHONY: all clean resource-usage

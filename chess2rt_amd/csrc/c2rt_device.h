@@ -1,6 +1,7 @@
 /*
  * c2rt_device.h — device-side table layout and launch interface shared by
- * c2rt_kernels.hip (kernels) and c2rt_api.cpp (C-ABI implementation).
+ * c2rt_kernels.hip (kernels), scene_plan.cpp (HIP-free scene and frame planning)
+ * and c2rt_api.cpp (C-ABI implementation).
  *
  * The public SoA tables of c2rt_scene_desc are repacked at upload into small
  * 16-byte-aligned records: every lane of a wavefront walks the SAME node /
@@ -69,7 +70,7 @@ struct alignas(16) DevGeom {       /* 128 B */
     /* Conservative bounding sphere in object space: centre, radius^2, padded
      * by 1e-6 relative so that rounding in the reject test can only keep rays,
      * never drop one the reference would hit.  Built at upload
-     * (c2rt_api.cpp: cube = half diagonal, Union = both children, Inter/Diff =
+     * (scene_plan.cpp, bound_of: cube = half diagonal, Union = both children, Inter/Diff =
      * left child, Plane = unbounded). */
     double bound[4];
     /* Wave-uniform subexpressions of the intersection tests, evaluated once at upload with the same
@@ -174,7 +175,7 @@ struct RenderParams {
      * frame, indexed by FRAME row — the devices of a multi-device context store their strips straight
      * into the lead device's frame over xGMI (peer-mapped): no gather buffer, no de-interleave pass. */
     uint32_t frame_rows;
-    /* Per-frame screen-space culling of PRIMARY rays (host-computed, c2rt_api.cpp):
+    /* Per-frame screen-space culling of PRIMARY rays (host-computed, scene_plan.cpp: fill_params):
      * the pixel rectangle [x0, x1) x [y0, y1) outside of which no ray through a
      * sample of this frame can reach node n's padded bounding box.  n_cull = 0
      * disables it (depth of field, stereo, prepass). */
@@ -201,7 +202,7 @@ struct RenderParams {
     /* every node's matrix is the identity (translations allowed): the launcher picks the kSpecIdentity instances
      * (c2rt_trace.inc) for uncounted frames with at most one light and no stereo */
     uint32_t all_identity;
-    /* "Ground plane" shadow culling (c2rt_api.cpp: ground_shadow_rects).  ground_node >= 0: node
+    /* "Ground plane" shadow culling (scene_plan.cpp: plan_ground_rects).  ground_node >= 0: node
      * ground_node is a Plane under an identity matrix with zero offset, at height ground_y.  In a
      * tile whose primary rays can reach that node only, every hit point lies on the plane inside the
      * tile's footprint there, and a shadow ray towards light 0 can only meet node n if the footprint

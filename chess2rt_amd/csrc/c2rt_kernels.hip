@@ -328,17 +328,16 @@ __global__ void encode_rgb32_kernel(const float *__restrict__ frame, uint32_t *_
 
 /* The culling masks of every tile of a frame's local rows, one lane per tile (c2rt_trace.inc: tile_mask_entry,
  * tile_mask_slot).  Runs once per frame whose camera leaves culling rectangles, in front of the frame kernel's
- * launch(es), on the same stream. */
-static_assert(sizeof(RenderParams) + sizeof(VoidCull) + sizeof(SphereCull) + 16 <= 4096, "the kernel-argument segment holds at most 4 KiB");
-__global__ void __launch_bounds__(256) tile_masks_kernel(const RenderParams P, const VoidCull V, const SphereCull S,
-                                                         uint32_t *__restrict__ table, uint32_t tile_rows)
+ * launch(es), on the same stream.  One body for both entry points below, which only produce (P, K, V, S, table,
+ * tile_rows). */
+DEV void tile_masks_body(const RenderParams &P, KArgs K, const VoidCull &V, const SphereCull &S, uint32_t *table, uint32_t tile_rows)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t cols = P.blocks_x * kWavesPerBlock;
     const uint32_t trow = i / cols, tcol = i % cols;
     if (trow >= tile_rows) return;
     uint32_t m[8];
-    exact::tile_mask_entry(P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), V, S, trow, tcol, m);
+    exact::tile_mask_entry(P, (exact::KArgs)K, V, S, trow, tcol, m);
     typedef uint32_t __attribute__((ext_vector_type(4))) u4_t;
     u4_t v, w;
     v.x = m[0]; v.y = m[1]; v.z = m[2]; v.w = m[3];
@@ -346,6 +345,13 @@ __global__ void __launch_bounds__(256) tile_masks_kernel(const RenderParams P, c
     const size_t slot = exact::tile_mask_slot(P, trow, tcol);
     reinterpret_cast<u4_t *>(table)[slot] = v;
     if (P.n_cull_lights > 1u) reinterpret_cast<u4_t *>(table)[(size_t)P.mask_entries + slot] = w; /* lights 1..3 */
+}
+
+static_assert(sizeof(RenderParams) + sizeof(VoidCull) + sizeof(SphereCull) + 16 <= 4096, "the kernel-argument segment holds at most 4 KiB");
+__global__ void __launch_bounds__(256) tile_masks_kernel(const RenderParams P, const VoidCull V, const SphereCull S,
+                                                         uint32_t *__restrict__ table, uint32_t tile_rows)
+{
+    tile_masks_body(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), V, S, table, tile_rows);
 }
 
 /* The same for every frame of a batch in one launch: blockIdx.y = frame; the frame's RenderParams and its VoidCull /
@@ -358,22 +364,8 @@ __global__ void __launch_bounds__(256) tile_masks_batch_kernel(const RenderParam
     asm volatile("" : "+s"(C));
     const RenderParams &P = *(const RenderParams *)K;
     if (!P.n_cull || !P.tile_masks) return;
-    const uint32_t tile_rows = (P.mask_rows + kTileH - 1) / kTileH;
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t cols = P.blocks_x * kWavesPerBlock;
-    const uint32_t trow = i / cols, tcol = i % cols;
-    if (trow >= tile_rows) return;
-    uint32_t m[8];
     const BatchCull &B = *(const BatchCull *)C;
-    exact::tile_mask_entry(P, (exact::KArgs)K, B.v, B.s, trow, tcol, m);
-    typedef uint32_t __attribute__((ext_vector_type(4))) u4_t;
-    u4_t v, w;
-    v.x = m[0]; v.y = m[1]; v.z = m[2]; v.w = m[3];
-    w.x = m[4]; w.y = m[5]; w.z = m[6]; w.w = m[7];
-    const size_t slot = exact::tile_mask_slot(P, trow, tcol);
-    uint32_t *out = const_cast<uint32_t *>(P.tile_masks);
-    reinterpret_cast<u4_t *>(out)[slot] = v;
-    if (P.n_cull_lights > 1u) reinterpret_cast<u4_t *>(out)[(size_t)P.mask_entries + slot] = w; /* lights 1..3 */
+    tile_masks_body(P, K, B.v, B.s, const_cast<uint32_t *>(P.tile_masks), (P.mask_rows + kTileH - 1) / kTileH);
 }
 #endif /* C2RT_UNIT == 5 */
 
@@ -391,18 +383,25 @@ __global__ void __launch_bounds__(256) tile_masks_batch_kernel(const RenderParam
 
 #if C2RT_UNIT >= 0 && C2RT_UNIT <= C2RT_MAX_CSG_DEPTH
 
-template <>
-int launch_render_level<C2RT_UNIT>(const RenderParams &p, bool dof_or_stereo, void *stream)
+/* launch geometry of a frame kernel, single frame or batch: the grid's x extent (retry mode: a fixed grid walks the
+ * overflow list, render_body) and the LDS of the hit stacks */
+static uint32_t frame_grid_x(const RenderParams &p)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
 #if C2RT_XCD_SWIZZLE
     const uint32_t tiles_y_pad = (p.tiles_y + 7u) / 8u * 8u;
 #else
     const uint32_t tiles_y_pad = p.tiles_y;
 #endif
-    /* retry mode: a fixed grid walks the overflow list (render_body) */
-    const dim3 grid(p.retry_mode ? 2048u : p.blocks_x * tiles_y_pad), block(kBlockThreads);
-    const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry * kWavesPerBlock;
+    return p.retry_mode ? 2048u : p.blocks_x * tiles_y_pad;
+}
+static size_t frame_lds(const RenderParams &p) { return (size_t)p.csg_cap * kCsgLdsPerEntry * kWavesPerBlock; }
+
+template <>
+int launch_render_level<C2RT_UNIT>(const RenderParams &p, bool dof_or_stereo, void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dim3 grid(frame_grid_x(p)), block(kBlockThreads);
+    const size_t lds = frame_lds(p);
     const bool stereo = p.cam.stereo_separation != 0;
     const bool multi = p.n_lights > 1;
     /* identity matrices throughout and not a counted frame: the instances specialised for that */
@@ -443,13 +442,8 @@ template <>
 int launch_render_batch_level<C2RT_UNIT>(const RenderParams &p0, const RenderParams *table_dev, uint32_t n_frames, void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
-#if C2RT_XCD_SWIZZLE
-    const uint32_t tiles_y_pad = (p0.tiles_y + 7u) / 8u * 8u;
-#else
-    const uint32_t tiles_y_pad = p0.tiles_y;
-#endif
-    const dim3 grid(p0.retry_mode ? 2048u : p0.blocks_x * tiles_y_pad, n_frames), block(kBlockThreads);
-    const size_t lds = (size_t)p0.csg_cap * kCsgLdsPerEntry * kWavesPerBlock;
+    const dim3 grid(frame_grid_x(p0), n_frames), block(kBlockThreads);
+    const size_t lds = frame_lds(p0);
 #if C2RT_UNIT == 0
     if (p0.planes_only && p0.n_lights <= 1) {
         hipLaunchKernelGGL(render_kernel_planes_batch, grid, block, lds, s, table_dev);

@@ -58,7 +58,7 @@ def _fields(desc):
 
 
 class Cand(namedtuple("Cand", "node lo hi c R flags")):
-    """A CsgDiff(L, Sphere) node the library tests (c2rt_api.cpp, upload_one): its padded world box, the subtracted
+    """A CsgDiff(L, Sphere) node the library tests (scene_plan.cpp, plan_void_nodes): its padded world box, the subtracted
     sphere's world centre and radius, and its VoidNode::flags (bit 0 primary, bit 1 shadow towards light 0)."""
 
 
@@ -75,7 +75,7 @@ def _finite(*xs):
 
 
 def ground_of(desc):
-    """(node, y) of the ground as the library picks it (upload_one, RenderParams::ground_node): the first Plane node
+    """(node, y) of the ground as the library picks it (scene_plan.cpp, plan_ground_rects; RenderParams::ground_node): the first Plane node
     below kMaxCullNodes under an identity matrix with zero offset and a finite height, or (None, None)."""
     desc = _fields(desc)
     for n in range(min(desc.n_nodes, MAX_CULL_NODES)):
@@ -99,7 +99,7 @@ def _geom_finite(desc, g):
 
 
 def void_candidates(desc):
-    """[Cand] for the nodes the library tests, restated from c2rt_api.cpp (upload_one) operation for operation: the
+    """[Cand] for the nodes the library tests, restated from scene_plan.cpp (plan_world_boxes, plan_void_nodes) operation for operation: the
     first kMaxVoidNodes nodes below kMaxCullNodes that are CsgDiff(Cube | Sphere, Sphere) under an identity matrix
     (offset allowed) with finite children and R > 0.  The box is the left child's (box_of: shortcut A) padded as for
     every node (1e-6 ext + 1e-6 mag + 1e-9 + 4e-6 max(|M^-1|_F, 1)) and moved by the offset; the shadow flag needs
@@ -166,7 +166,7 @@ def void_candidates(desc):
 
 
 def frame_void_nodes(desc, cam, debug_cull=0):
-    """The VoidCull the library hands the mask pre-pass for this camera (c2rt_api.cpp, void_cull_of): per candidate
+    """The VoidCull the library hands the mask pre-pass for this camera (scene_plan.cpp, void_cull_of): per candidate
     (node, lo, hi, c, r2 = (R - void_margin(scale))^2, flags), without bit 1 where the frame runs no shadow culling
     or no ground refinement (the diagnostics build's C2RT_DEBUG_CULL bits 2 and 4).  None: the frame culls nothing
     (C2RT_DEBUG_CULL bit 1)."""

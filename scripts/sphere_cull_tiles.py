@@ -51,12 +51,12 @@ def lib():
 
 
 class Ball(namedtuple("Ball", "node c R flags")):
-    """A Sphere node the library tests (c2rt_api.cpp, upload_one): world centre, radius, and the flags it may get
+    """A Sphere node the library tests (scene_plan.cpp, plan_sphere_nodes): world centre, radius, and the flags it may get
     (bit 0 primary, bit 1 shadow towards light 0 where the scene has a ground and a finite light 0)."""
 
 
 def sphere_candidates(desc):
-    """[Ball], restated from c2rt_api.cpp (upload_one): the first kMaxSphereNodes nodes below kMaxCullNodes whose
+    """[Ball], restated from scene_plan.cpp (plan_sphere_nodes): the first kMaxSphereNodes nodes below kMaxCullNodes whose
     root geometry is a finite Sphere of positive radius under an identity matrix (offset allowed) and that are boxed
     (bound and padded box finite, as for every node: csg_void_tiles.void_candidates)."""
     desc = cv._fields(desc)
@@ -96,7 +96,7 @@ def sphere_candidates(desc):
 
 def frame_sphere_cull(desc, cam, debug_cull=0, flags_mask=3):
     """(reach, [dict(node, c, rp, flags)]): the SphereCull the library hands the mask pre-pass for this camera
-    (c2rt_api.cpp, sphere_cull_of), operation for operation.  None: the frame culls nothing."""
+    (scene_plan.cpp, sphere_cull_of), operation for operation.  None: the frame culls nothing."""
     desc = cv._fields(desc)
     if debug_cull & 1:
         return None
