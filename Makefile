@@ -39,6 +39,9 @@ KERNELFLAGS_u2 := -mllvm -enable-pre=false -mllvm -bonus-inst-threshold=4 -mllvm
 KERNELFLAGS_u3 := -mllvm -enable-pre=false -mllvm -bonus-inst-threshold=4
 KERNELFLAGS_u4 := -mllvm -enable-pre=false -mllvm -bonus-inst-threshold=4 -mllvm -amdgpu-sched-strategy=max-memory-clause
 KERNELFLAGS_u5 :=
+# unit 6: the ray / visibility query kernels, every CSG depth in one unit (exact:: only: a fraction of a frame unit's
+# code); the flags of the frame units were tuned on the frame kernels and have not been measured here
+KERNELFLAGS_u6 :=
 CXXFLAGS   := -O2 -std=c++17 -fPIC $(FPFLAGS) -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 CSRC       := chess2rt_amd/csrc
 # development knob: `make VARIANT=name EXTRA_HIPFLAGS=... EXTRA_KERNEL_FLAGS=...` builds chess2rt_amd/libc2rt_name.so
@@ -47,7 +50,7 @@ VARIANT    ?=
 BUILD      := build$(if $(VARIANT),_$(VARIANT))
 LIBNAME    := chess2rt_amd/libc2rt$(if $(VARIANT),_$(VARIANT)).so
 
-UNITS      := 0 1 2 3 4 5
+UNITS      := 0 1 2 3 4 5 6
 KOBJS      := $(foreach u,$(UNITS),$(BUILD)/c2rt_kernels_u$(u).o)
 HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/scene.o $(BUILD)/host_api.o
 

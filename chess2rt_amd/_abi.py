@@ -23,6 +23,7 @@ ABI_VERSION = 1
 MAX_CSG_DEPTH = 4
 MAX_CSG_HITS = 8
 MAX_BATCH_FRAMES = 256
+MAX_RAYS = 1 << 28
 
 _i32p = C.POINTER(C.c_int32)
 _u32p = C.POINTER(C.c_uint32)
@@ -118,6 +119,26 @@ class TraceResult(C.Structure):
     ]
 
 
+class Ray(C.Structure):
+    _fields_ = [("orig", C.c_double * 3), ("dir", C.c_double * 3)]
+
+
+class Segment(C.Structure):
+    _fields_ = [("from_", C.c_double * 3), ("to", C.c_double * 3)]
+
+
+class RayHit(C.Structure):
+    _fields_ = [
+        ("closest_node", C.c_int32),
+        ("leaf_geom", C.c_int32),
+        ("dist", C.c_double),
+        ("u", C.c_double),
+        ("v", C.c_double),
+        ("p", C.c_double * 3),
+        ("normal", C.c_double * 3),
+    ]
+
+
 class RayStats(C.Structure):
     _fields_ = [("primary_rays", C.c_uint64), ("shadow_rays", C.c_uint64)]
 
@@ -177,6 +198,10 @@ C2RT_SYMBOLS = {
     "c2rt_unpin_host_buffer": (C.c_int, [_VP, _VP]),
     "c2rt_get_ray_stats": (C.c_int, [_VP, C.POINTER(RayStats)]),
     "c2rt_render_pixel": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_int, C.c_int, C.POINTER(TraceResult)]),
+    "c2rt_trace_rays_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, _VP]),
+    "c2rt_trace_rays": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP]),
+    "c2rt_test_visibility_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP]),
+    "c2rt_test_visibility": (C.c_int, [_VP, _VP, C.c_uint64, _VP]),
     "c2rt_deinterleave_strips": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
     "c2rt_encode_rgb32": (C.c_int, [_VP, _VP, _VP, C.c_uint64, _VP]),
     "c2rt_render_frame_rgb32": (C.c_int, [_VP, _CAM_P, _OPTS_P, _VP, _VP]),

@@ -12,7 +12,16 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (CameraFrame, HostCamera, HostSettings, RayStats, RenderOpts, SceneDesc, TraceResult)
+from ._abi import (CameraFrame, HostCamera, HostSettings, Ray, RayHit, RayStats, RenderOpts, SceneDesc, Segment, TraceResult)
+
+# c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
+RAY_HIT_DTYPE = np.dtype({
+    "names": ["closest_node", "leaf_geom", "dist", "u", "v", "p", "normal"],
+    "formats": [np.int32, np.int32, np.float64, np.float64, np.float64, (np.float64, 3), (np.float64, 3)],
+    "offsets": [RayHit.closest_node.offset, RayHit.leaf_geom.offset, RayHit.dist.offset, RayHit.u.offset, RayHit.v.offset,
+                RayHit.p.offset, RayHit.normal.offset],
+    "itemsize": C.sizeof(RayHit),
+})
 
 
 class C2rtError(RuntimeError):
@@ -240,6 +249,40 @@ class Context:
         r = TraceResult()
         self._check(self._lib.c2rt_render_pixel(self._h, C.byref(cam), C.byref(opts), int(x), int(y), C.byref(r)))
         return r
+
+    def traceRays(self, rays, hits=True, colors=True):
+        """Closest hit and colour of caller-supplied rays (c2rt_trace_rays): `rays` is (n, 6) float64 — origin, then the
+        direction, used exactly as given.  Returns (records, rgb): a structured array of RAY_HIT_DTYPE (c2rt_ray_hit)
+        and an (n, 3) float32 array; the one switched off is None (colors=False casts no shadow ray)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays: expected shape (n, 6), got %r" % (rays.shape,))
+        n = rays.shape[0]
+        rec = np.empty(n, dtype=RAY_HIT_DTYPE) if hits else None
+        rgb = np.empty((n, 3), dtype=np.float32) if colors else None
+        self._check(self._lib.c2rt_trace_rays(self._h, rays.ctypes.data_as(C.c_void_p), n,
+                                              rec.ctypes.data_as(C.c_void_p) if hits else None,
+                                              rgb.ctypes.data_as(C.c_void_p) if colors else None))
+        return rec, rgb
+
+    def traceRaysDevice(self, rays_ptr, n, hits_ptr, rgb_ptr, stream=0):
+        """Enqueue the query on `stream` over device memory: n c2rt_ray at rays_ptr, n c2rt_ray_hit at hits_ptr and
+        n * 3 floats at rgb_ptr (either output may be 0 / None, not both)."""
+        self._check(self._lib.c2rt_trace_rays_device(self._h, C.c_void_p(rays_ptr), int(n), C.c_void_p(hits_ptr or None),
+                                                     C.c_void_p(rgb_ptr or None), C.c_void_p(stream)))
+
+    def testVisibility(self, segments):
+        """Scene.testVisibility for (n, 6) float64 segments (from, to): (n,) uint8, 1 = nothing in between."""
+        seg = np.ascontiguousarray(segments, dtype=np.float64)
+        if seg.ndim != 2 or seg.shape[1] != 6:
+            raise ValueError("segments: expected shape (n, 6), got %r" % (seg.shape,))
+        vis = np.empty(seg.shape[0], dtype=np.uint8)
+        self._check(self._lib.c2rt_test_visibility(self._h, seg.ctypes.data_as(C.c_void_p), seg.shape[0], vis.ctypes.data_as(C.c_void_p)))
+        return vis
+
+    def testVisibilityDevice(self, segments_ptr, n, visible_ptr, stream=0):
+        """Enqueue n visibility tests on `stream`: n c2rt_segment at segments_ptr, n bytes at visible_ptr."""
+        self._check(self._lib.c2rt_test_visibility_device(self._h, C.c_void_p(segments_ptr), int(n), C.c_void_p(visible_ptr), C.c_void_p(stream)))
 
     def deinterleaveStrips(self, gathered_ptr, frame_ptr, width, height, strip_height, world, stream=0):
         self._check(self._lib.c2rt_deinterleave_strips(self._h, C.c_void_p(gathered_ptr), C.c_void_p(frame_ptr), width, height,

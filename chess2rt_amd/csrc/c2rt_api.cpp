@@ -1088,6 +1088,123 @@ int c2rt_render_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_re
     return C2RT_OK;
 }
 
+/* ---- ray queries (kernel unit 6) ----------------------------------------------------------------------------- */
+
+/* What the query kernels read of a parameter block: the scene's tables and constants, the full-capacity hit stack
+ * (it cannot overflow: one launch, no retry list) and nothing of a frame — no camera, no culling rectangles
+ * (n_cull = 0: every mask is all ones), no ground node, no scratch. */
+static void query_params(const c2rt_ctx *ctx, RenderParams &p)
+{
+    std::memset(&p, 0, sizeof p);
+    p.geoms = ctx->dev.geoms;
+    p.nodes = ctx->dev.nodes;
+    p.shaders = ctx->dev.shaders;
+    p.textures = ctx->dev.textures;
+    p.lights = ctx->dev.lights;
+    p.texels = ctx->dev.texels;
+    p.n_nodes = ctx->plan.n_nodes;
+    p.n_lights = ctx->plan.n_lights;
+    std::memcpy(p.ambient, ctx->plan.ambient, sizeof p.ambient);
+    p.max_trace_depth = ctx->plan.max_trace_depth;
+    p.force_exact = 1;
+    p.ground_node = -1;
+    p.csg_cap = ctx->plan.csg_levels == 0 ? 0u : (uint32_t)kCsgFullCap(ctx->plan.csg_levels);
+    p.redo_counter = ctx->counters + 3;
+}
+
+/* the refusals shared by the four entry points, in the documented order; `in`: the input array, out_ok: a required
+ * output is there.  > 0: return that status; 0: go on; -1: n == 0, return C2RT_OK */
+static int check_query_args(c2rt_ctx *ctx, const void *in, uint64_t n, bool out_ok)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (n == 0) return -1;
+    if (!in) return fail(ctx, C2RT_ERR_INVALID_ARG, "null input array");
+    if (!out_ok) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    if (n > (uint64_t)C2RT_MAX_RAYS) return fail(ctx, C2RT_ERR_LIMIT, "%llu rays in one call (at most %u)", (unsigned long long)n, (unsigned)C2RT_MAX_RAYS);
+    if (!ctx->has_scene) return fail(ctx, C2RT_ERR_NO_SCENE, "no scene uploaded");
+    return 0;
+}
+
+int c2rt_trace_rays_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, c2rt_ray_hit *hits_dev, float *rgb_dev,
+                           void *hip_stream)
+{
+    if (const int st = check_query_args(ctx, rays_dev, n, hits_dev || rgb_dev)) return st < 0 ? C2RT_OK : st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    query_params(ctx, p);
+    const int e = launch_trace_rays(p, ctx->plan.csg_levels, rays_dev, n, hits_dev, rgb_dev, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "ray query kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+int c2rt_test_visibility_device(c2rt_ctx *ctx, const c2rt_segment *seg_dev, uint64_t n, uint8_t *visible_dev, void *hip_stream)
+{
+    if (const int st = check_query_args(ctx, seg_dev, n, visible_dev != nullptr)) return st < 0 ? C2RT_OK : st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    query_params(ctx, p);
+    const int e = launch_test_visibility(p, ctx->plan.csg_levels, seg_dev, n, visible_dev, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "visibility query kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+/* Host variants: chunks of at most kQueryChunk records through ONE staging allocation (the context's, shared with the
+ * host-output frames: calls on a context are serialised) laid out [inputs | hits | colours] for the chunk size and
+ * only for the outputs asked for — 12 MiB + 20 MiB + 3 MiB at most, whatever n is.  Copies from and to pageable
+ * memory are staged by the runtime; each chunk ends with a stream sync, so the call blocks as documented. */
+constexpr uint64_t kQueryChunk = 1u << 18;
+static size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
+
+int c2rt_trace_rays(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb)
+{
+    if (const int st = check_query_args(ctx, rays, n, hits || rgb)) return st < 0 ? C2RT_OK : st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t chunk = n < kQueryChunk ? n : kQueryChunk;
+    const size_t off_hits = align256(chunk * sizeof(c2rt_ray));
+    const size_t off_rgb = off_hits + (hits ? align256(chunk * sizeof(c2rt_ray_hit)) : 0);
+    const size_t bytes = off_rgb + (rgb ? chunk * 3 * sizeof(float) : 0);
+    if (const int st = ensure_staging(ctx, bytes)) return st;
+    char *base = reinterpret_cast<char *>(ctx->frame);
+    c2rt_ray *rays_dev = reinterpret_cast<c2rt_ray *>(base);
+    c2rt_ray_hit *hits_dev = hits ? reinterpret_cast<c2rt_ray_hit *>(base + off_hits) : nullptr;
+    float *rgb_dev = rgb ? reinterpret_cast<float *>(base + off_rgb) : nullptr;
+    RenderParams p;
+    query_params(ctx, p);
+    for (uint64_t i = 0; i < n; i += chunk) {
+        const uint64_t m = n - i < chunk ? n - i : chunk;
+        HIP_TRY(ctx, hipMemcpyAsync(rays_dev, rays + i, m * sizeof(c2rt_ray), hipMemcpyHostToDevice, ctx->stream));
+        const int e = launch_trace_rays(p, ctx->plan.csg_levels, rays_dev, m, hits_dev, rgb_dev, ctx->stream);
+        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "ray query kernel launch: %s", hipGetErrorString((hipError_t)e));
+        if (hits) HIP_TRY(ctx, hipMemcpyAsync(hits + i, hits_dev, m * sizeof(c2rt_ray_hit), hipMemcpyDeviceToHost, ctx->stream));
+        if (rgb) HIP_TRY(ctx, hipMemcpyAsync(rgb + 3 * i, rgb_dev, m * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return C2RT_OK;
+}
+
+int c2rt_test_visibility(c2rt_ctx *ctx, const c2rt_segment *seg, uint64_t n, uint8_t *visible)
+{
+    if (const int st = check_query_args(ctx, seg, n, visible != nullptr)) return st < 0 ? C2RT_OK : st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t chunk = n < kQueryChunk ? n : kQueryChunk;
+    const size_t off_vis = align256(chunk * sizeof(c2rt_segment));
+    if (const int st = ensure_staging(ctx, off_vis + chunk)) return st;
+    char *base = reinterpret_cast<char *>(ctx->frame);
+    c2rt_segment *seg_dev = reinterpret_cast<c2rt_segment *>(base);
+    uint8_t *vis_dev = reinterpret_cast<uint8_t *>(base + off_vis);
+    RenderParams p;
+    query_params(ctx, p);
+    for (uint64_t i = 0; i < n; i += chunk) {
+        const uint64_t m = n - i < chunk ? n - i : chunk;
+        HIP_TRY(ctx, hipMemcpyAsync(seg_dev, seg + i, m * sizeof(c2rt_segment), hipMemcpyHostToDevice, ctx->stream));
+        const int e = launch_test_visibility(p, ctx->plan.csg_levels, seg_dev, m, vis_dev, ctx->stream);
+        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "visibility query kernel launch: %s", hipGetErrorString((hipError_t)e));
+        HIP_TRY(ctx, hipMemcpyAsync(visible + i, vis_dev, m, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return C2RT_OK;
+}
+
 static int deinterleave_words(c2rt_ctx *ctx, const float *gathered_dev, float *frame_dev, uint32_t width, uint32_t height,
                               uint32_t strip_height, uint32_t world, uint32_t words_per_pixel, void *hip_stream)
 {

@@ -375,10 +375,11 @@ __global__ void __launch_bounds__(256) tile_masks_batch_kernel(const RenderParam
  * Instantiation is split over translation units so that the (slow) device
  * compiles run in parallel: the Makefile builds this file once per
  * C2RT_UNIT = 0..4 (the frame kernel for that many CSG nesting levels) and
- * once with C2RT_UNIT = 5 (probe, de-interleave, encode, dispatcher).
+ * once with C2RT_UNIT = 5 (probe, de-interleave, encode, dispatcher) and once
+ * with C2RT_UNIT = 6 (the ray and visibility queries, c2rt_trace_rays).
  */
 #ifndef C2RT_UNIT
-#error "compile with -DC2RT_UNIT=0..5 (see Makefile)"
+#error "compile with -DC2RT_UNIT=0..6 (see Makefile)"
 #endif
 
 #if C2RT_UNIT >= 0 && C2RT_UNIT <= C2RT_MAX_CSG_DEPTH
@@ -456,7 +457,7 @@ int launch_render_batch_level<C2RT_UNIT>(const RenderParams &p0, const RenderPar
     return (int)hipGetLastError();
 }
 
-#else /* C2RT_UNIT == 5 */
+#elif C2RT_UNIT == 5
 
 int launch_render_batch(const RenderParams &p0, const KernelVariant &v, const RenderParams *table_dev, uint32_t n_frames, void *stream)
 {
@@ -536,6 +537,216 @@ int launch_encode_rgb32(const float *frame, uint32_t *out, uint64_t n_pixels, co
     return (int)hipGetLastError();
 }
 
+#elif C2RT_UNIT == 6
+
+/*
+ * Ray and visibility queries (c2rt_trace_rays*, c2rt_test_visibility*): the caller's rays instead of a camera's.
+ * One ray per lane, 64 consecutive rays per wavefront, one wavefront per workgroup — the frame kernels' shape with
+ * the tile replaced by a run of the caller's array, so the trace below it is the same wave-synchronous code: scalar
+ * node loop, scalar record loads, one surface pass per distinct closest node.  exact:: arithmetic only (the probe's
+ * choice; bit-equal to what the frames compute), every culling mask all ones, no ground-tile shortcut.
+ *
+ * Lanes past n (the tail wave) are masked out by ordinary control flow BEFORE the trace, as the frame kernels mask the
+ * lanes past the frame's edge: __all / __ballot / readfirstlane below only ever see live lanes, so a dead lane can
+ * neither store nor steer a wave-uniform decision.  A lane holding garbage (NaN, zero direction, 1e300) is live and
+ * goes through the same bounded loops as a frame's lane does; what it computes stays in its own registers.
+ *
+ * CSG hit stack: kCsgFullCap(LEVELS) entries in one launch — it cannot overflow, so there is no retry list and no
+ * per-stream scratch.  That is 10 / 20 / 30 / 40 KiB of LDS per wave at depth 1 / 2 / 3 / 4: the LDS, not the
+ * registers, bounds the occupancy of the nested instances (8 / 5 / 4 workgroups per CU), hence two waves per SIMD as
+ * their register budget ("Ray queries").
+ *
+ * Memory: the ABI is array-of-structures.  Rays: three 16-byte loads per lane at a 48-byte stride — every 128-byte
+ * line a wave touches is consumed whole by the three loads together, the second and third hit in the vector L1, and
+ * nothing is written, so no transposition.  Colours: one 12-byte store per lane, 768 contiguous bytes per wave, as
+ * the frame kernels store pixels.  Hit records: 80 bytes per lane; stored by the lane itself that would be ten 8-byte
+ * stores at an 80-byte stride, each store instruction of the wave dirtying 8 of every 80 bytes of 40 lines.  Instead
+ * the wave stages its records in LDS — in the hit stack, which is dead between the closest-hit search and the first
+ * shadow ray — and writes them out as rows: lane l stores words l, l + 64, ... of the wave's 640 8-byte words, so each
+ * of the ten store instructions covers 512 contiguous bytes, four whole lines.  (8-byte rather than 16-byte rows:
+ * c2rt_ray_hit is only 8-byte aligned for a C caller.)  All of them plain vector stores.
+ */
+namespace {
+
+constexpr int kHitWords = (int)(sizeof(c2rt_ray_hit) / 8);
+static_assert(sizeof(c2rt_ray) == 48 && sizeof(c2rt_segment) == 48 && sizeof(c2rt_ray_hit) == 80 && kHitWords * 8 == sizeof(c2rt_ray_hit), "ABI layout of the query records");
+static_assert(__builtin_offsetof(c2rt_ray_hit, leaf_geom) == 4 && __builtin_offsetof(c2rt_ray_hit, dist) == 8 &&
+              __builtin_offsetof(c2rt_ray_hit, p) == 32 && __builtin_offsetof(c2rt_ray_hit, normal) == 56, "ABI layout of c2rt_ray_hit");
+static_assert(sizeof(RenderParams) + 64 <= 4096, "the kernel-argument segment holds at most 4 KiB");
+
+template <int LEVELS, bool MLC>
+constexpr int occ_query() { return LEVELS >= 2 ? 2 : occ_of<LEVELS, 0, MLC>(); }
+#define C2RT_OCC_QUERY(L, M) __attribute__((amdgpu_waves_per_eu(occ_query<L, M>(), occ_query<L, M>())))
+
+DEV void query_ctx(exact::Ctx &cx, const RenderParams &P, exact::KArgs K, char *lds, int lane)
+{
+    cx.geoms = (exact::GeomP)P.geoms;
+    cx.nodes = (exact::NodeP)P.nodes;
+    cx.n_nodes = P.n_nodes;
+    cx.kargs = K;
+    cx.lds = lds;
+    cx.lane = lane;
+    cx.csg_cap = (int)P.csg_cap;
+    cx.overflow = false;
+    exact::oob_init(cx.bad);
+    cx.trunc_counter = nullptr;
+#if C2RT_TILE_STATS
+    cx.lane_stats = nullptr;
+#endif
+    cx.block = 0;
+    cx.mask_slot = 0;
+    cx.primary_mask = 0xFFFFFFFFu;
+    cx.shadow_mask0 = 0xFFFFFFFFu;
+    cx.shadow_ground_only = false;
+    cx.primary_ground_only = false;
+    cx.ground_y = 0;
+}
+
+/* six doubles of an array-of-structures input record (c2rt_ray, c2rt_segment): three 16-byte loads where the
+ * hardware takes them at 8-byte alignment */
+typedef double __attribute__((ext_vector_type(2), aligned(8))) d2_t;
+DEV void load6(const void *rec, exact::D3 &a, exact::D3 &b)
+{
+    const d2_t *q = static_cast<const d2_t *>(rec);
+    const d2_t q0 = q[0], q1 = q[1], q2 = q[2];
+    a = exact::mk(q0.x, q0.y, q1.x);
+    b = exact::mk(q1.y, q2.x, q2.y);
+}
+
+/* Ray i = trace(ray, TraceType.Ray), rt/renderer.d:325-376, depth 0.  hits / rgb: nullable, not both (wave-uniform). */
+template <int LEVELS, bool MLC>
+__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, MLC)
+trace_rays_kernel(const RenderParams P, const c2rt_ray *__restrict__ rays, const uint64_t n, c2rt_ray_hit *__restrict__ hits, float *__restrict__ rgb)
+{
+    using namespace exact;
+    extern __shared__ __align__(16) char lds[];
+    const int lane = (int)threadIdx.x;
+    const uint64_t first = (uint64_t)blockIdx.x * kWave; /* < n: the grid is ceil(n / 64) */
+    const uint64_t i = first + (uint64_t)lane;
+    const bool live = i < n;
+    Ctx cx;
+    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
+    D3 o = mk(0, 0, 0), d = mk(0, 0, 0);
+    Hit best;
+    Surf surf;
+    Mat mat;
+    int closest = -1;
+    unsigned long long *stage = reinterpret_cast<unsigned long long *>(lds); /* [64][kHitWords] */
+    if (live) {
+        load6(rays + i, o, d);
+        closest = trace_closest<LEVELS>(cx, o, d, hits != nullptr, best, surf, mat);
+        if (hits) {
+            unsigned long long *rec = stage + lane * kHitWords;
+            const int leaf = closest >= 0 ? best.g : -1;
+            rec[0] = (unsigned long long)(uint32_t)closest | ((unsigned long long)(uint32_t)leaf << 32);
+            rec[1] = (unsigned long long)__double_as_longlong(best.dist);
+            rec[2] = (unsigned long long)__double_as_longlong(surf.u);
+            rec[3] = (unsigned long long)__double_as_longlong(surf.v);
+            rec[4] = (unsigned long long)__double_as_longlong(surf.p.x);
+            rec[5] = (unsigned long long)__double_as_longlong(surf.p.y);
+            rec[6] = (unsigned long long)__double_as_longlong(surf.p.z);
+            rec[7] = (unsigned long long)__double_as_longlong(surf.n.x);
+            rec[8] = (unsigned long long)__double_as_longlong(surf.n.y);
+            rec[9] = (unsigned long long)__double_as_longlong(surf.n.z);
+        }
+    }
+    if (hits) {
+        /* every lane of the wave, live or not: the rows of the records of the live lanes (LDS operations of one
+         * wave complete in order; the workgroup is this wave) */
+        __builtin_amdgcn_wave_barrier();
+        const uint64_t left = n - first;
+        const uint32_t words = (uint32_t)(left < (uint64_t)kWave ? left : (uint64_t)kWave) * (uint32_t)kHitWords;
+        unsigned long long *out = reinterpret_cast<unsigned long long *>(hits + first);
+#pragma unroll
+        for (int k = 0; k < kHitWords; ++k) {
+            const uint32_t w = (uint32_t)lane + (uint32_t)(k * kWave);
+            if (w < words) out[w] = stage[w];
+        }
+        __builtin_amdgcn_wave_barrier(); /* the shadow rays below reuse the stack */
+    }
+    if (live && rgb) {
+        F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
+        uint32_t shadow_rays = 0;
+        if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
+        typedef float __attribute__((ext_vector_type(3), aligned(4))) f3_t;
+        f3_t v3;
+        v3.x = c.r;
+        v3.y = c.g;
+        v3.z = c.b;
+        *reinterpret_cast<f3_t *>(rgb + i * 3) = v3;
+    }
+}
+
+/* Segment i = Scene.testVisibility(from, to), rt/scene.d:62-78: full node mask, no ground shortcut */
+template <int LEVELS>
+__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, false)
+test_visibility_kernel(const RenderParams P, const c2rt_segment *__restrict__ seg, const uint64_t n, uint8_t *__restrict__ visible)
+{
+    using namespace exact;
+    extern __shared__ __align__(16) char lds[];
+    const int lane = (int)threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * kWave + (uint64_t)lane;
+    if (i >= n) return; /* nothing after the trace needs the whole wave */
+    Ctx cx;
+    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
+    D3 from, to;
+    load6(seg + i, from, to);
+    const bool vis = test_visibility<LEVELS, 0>(cx, from, to, 0xFFFFFFFFu, false);
+    visible[i] = vis ? (uint8_t)1 : (uint8_t)0;
+}
+
+template <int LEVELS>
+int launch_trace_rays_level(const RenderParams &p, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb, hipStream_t s)
+{
+    const dim3 grid((uint32_t)((n + kWave - 1) / kWave)), block(kWave);
+    const size_t stack = (size_t)p.csg_cap * kCsgLdsPerEntry, stage = hits ? (size_t)kWave * sizeof(c2rt_ray_hit) : 0;
+    const size_t lds = stack > stage ? stack : stage;
+    if (p.n_lights > 1) hipLaunchKernelGGL((trace_rays_kernel<LEVELS, true>), grid, block, lds, s, p, rays, n, hits, rgb);
+    else hipLaunchKernelGGL((trace_rays_kernel<LEVELS, false>), grid, block, lds, s, p, rays, n, hits, rgb);
+    return (int)hipGetLastError();
+}
+
+template <int LEVELS>
+int launch_test_visibility_level(const RenderParams &p, const c2rt_segment *seg, uint64_t n, uint8_t *visible, hipStream_t s)
+{
+    const dim3 grid((uint32_t)((n + kWave - 1) / kWave)), block(kWave);
+    hipLaunchKernelGGL((test_visibility_kernel<LEVELS>), grid, block, (size_t)p.csg_cap * kCsgLdsPerEntry, s, p, seg, n, visible);
+    return (int)hipGetLastError();
+}
+
+} // namespace
+
+/* the instance of the scene's CSG depth, as the frame kernels are chosen at upload; p.csg_cap = kCsgFullCap(levels) */
+int launch_trace_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb, void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!n || n > C2RT_MAX_RAYS || (!hits && !rgb)) return (int)hipErrorInvalidValue;
+    switch (csg_levels) {
+    case 0: return launch_trace_rays_level<0>(p, rays, n, hits, rgb, s);
+    case 1: return launch_trace_rays_level<1>(p, rays, n, hits, rgb, s);
+    case 2: return launch_trace_rays_level<2>(p, rays, n, hits, rgb, s);
+    case 3: return launch_trace_rays_level<3>(p, rays, n, hits, rgb, s);
+    case 4: return launch_trace_rays_level<4>(p, rays, n, hits, rgb, s);
+    default: return (int)hipErrorInvalidValue;
+    }
+}
+
+int launch_test_visibility(const RenderParams &p, int csg_levels, const c2rt_segment *seg, uint64_t n, uint8_t *visible, void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!n || n > C2RT_MAX_RAYS) return (int)hipErrorInvalidValue;
+    switch (csg_levels) {
+    case 0: return launch_test_visibility_level<0>(p, seg, n, visible, s);
+    case 1: return launch_test_visibility_level<1>(p, seg, n, visible, s);
+    case 2: return launch_test_visibility_level<2>(p, seg, n, visible, s);
+    case 3: return launch_test_visibility_level<3>(p, seg, n, visible, s);
+    case 4: return launch_test_visibility_level<4>(p, seg, n, visible, s);
+    default: return (int)hipErrorInvalidValue;
+    }
+}
+
+#else
+#error "C2RT_UNIT out of range"
 #endif
 
 } // namespace c2rt

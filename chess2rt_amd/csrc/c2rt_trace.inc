@@ -1781,6 +1781,46 @@ DEV F3 raytrace(const RenderParams &P, const Ctx &cx, D3 o, D3 raw, Counters &cn
     return shade<LEVELS, MLC, PO>(P, cx, mat, d, surf, cnt.shadow);
 }
 
+/* The first half of `trace` (rt/renderer.d:325-338) for a CALLER's ray (c2rt_trace_rays; c2rt_kernels.hip,
+ * trace_rays_kernel): data.dist = 1e99, every node in file order, the last one that returns true is the closest.
+ * Unlike raytrace() above, whose argument is the camera's un-normalised screen ray, the direction is used exactly
+ * as given — the reference's trace() does not normalise either (Camera.getScreenRay has, by then), and Node.intersect
+ * (rt/node.d:34-36) takes the magnitude of whatever it is handed: make_ray's sqrt and reciprocal are that magnitude
+ * and the factor of that normalize() for any length in exact::, which is the only namespace this is instantiated
+ * in (len_inv_unit's lean shortcut presumes a unit vector).  No culling mask, no ground-tile shortcut, no
+ * plane_points_away: caller rays share no eye, so every node is tested.
+ * record (wave-uniform): the caller reads best.dist, so the last node's division is not skipped, and the surface
+ * carries u, v for untextured nodes too.  Returns the closest node or -1; without a hit `surf` is all zeros and
+ * best.dist is 1e99 — the record the probe reports. */
+template <int LEVELS>
+DEV int trace_closest(const Ctx &cx, D3 o, D3 d, bool record, Hit &best, Surf &surf, Mat &mat)
+{
+    const uint32_t nn = cx.n_nodes;
+    best.dist = 1e99;
+    best.g = -1;
+    best.code = 0;
+    best.p = mk(0, 0, 0);
+    surf.p = surf.n = mk(0, 0, 0);
+    surf.u = surf.v = 0;
+    int closest = -1;
+    const RayW ray = make_ray(cx.bad, o, d);
+    for (uint32_t n = 0; n < nn; ++n) /* scalar loop, file order */
+        if (node_intersect<LEVELS, kFull, 0>(cx, cx.nodes + n, ray, best, n + 1 >= nn && !record)) closest = (int)n;
+    /* one pass per distinct closest node of the wave, as in raytrace() */
+    mat.tex_type = -1;
+    bool todo = closest >= 0;
+    while (todo) {
+        const int cn = __builtin_amdgcn_readfirstlane(closest);
+        if (closest == cn) {
+            NodeP N = cx.nodes + cn;
+            load_mat(N, mat);
+            hit_surface<0>(cx, N, best, record || mat.tex_type >= 0, surf);
+            todo = false;
+        }
+    }
+    return closest;
+}
+
 /* adjustSaturation + combineStereo — rt/color.d:10-15,77-83 */
 DEV F3 desaturate(F3 c, float amount)
 {

@@ -393,6 +393,61 @@ int c2rt_render_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam,
                       const c2rt_render_opts *opts, int x, int y,
                       c2rt_trace_result *out);
 
+/* ---- ray queries: the caller's rays instead of a camera's ------------------ */
+
+/* Most rays / segments one call takes; C2RT_ERR_LIMIT beyond. */
+#define C2RT_MAX_RAYS (1u << 28)
+
+typedef struct c2rt_ray     { double orig[3], dir[3]; } c2rt_ray;      /* 48 B */
+typedef struct c2rt_segment { double from[3], to[3];  } c2rt_segment;  /* 48 B */
+typedef struct c2rt_ray_hit {                                          /* 80 B */
+    int32_t closest_node;          /* -1: no hit */
+    int32_t leaf_geom;             /* IntersectionData.g (leaf geometry index), -1 without a hit */
+    double dist, u, v;
+    double p[3], normal[3];
+} c2rt_ray_hit;
+
+/* Ray i is `Renderer.trace(ray, TraceType.Ray)` (rt/renderer.d:325-376) with ray.orig = rays[i].orig, ray.dir =
+ * rays[i].dir and depth 0, against the uploaded scene: data.dist starts at 1e99 (rt/renderer.d:333), the nodes are
+ * tested in file order and the last one that returns true is the closest (rt/renderer.d:336-338).
+ *   - `dir` is used EXACTLY AS GIVEN.  The reference's trace() does not normalise: Camera.getScreenRay has done so by
+ *     then (rt/camera.d:144-147).  A caller who passes unit vectors built like getScreenRay's gets the frame's own
+ *     rays — and the frame's own bits: the queries run the arithmetic the frames are held to.  For other lengths
+ *     `dist` is whatever Node.intersect (rt/node.d:23-49) makes of them: it scales data.dist by the length of the
+ *     direction in the node's space, normalises for Geometry.intersect and divides the hit distance by that length
+ *     again, so `dist` counts lengths of `dir`; the shaders see `dir` as ray.dir (rt/shader.d:67-105,197-250).
+ *   - hits[i] (nullable) is the TraceResult's record as c2rt_render_pixel reports it; without a hit closest_node and
+ *     leaf_geom are -1, dist is 1e99 and the rest is 0.
+ *   - rgb[i] (nullable; 3 floats per ray) is raytrace_impl's colour (rt/renderer.d:361-376): the closest node's
+ *     shader's `shade`, with a shadow ray (Scene.testVisibility) towards every light, or the environment's black
+ *     (rt/environment.d:7-10) without a hit.
+ *   - a null `rgb` skips shading and its shadow rays altogether, a null `hits` the record stores; both null is
+ *     C2RT_ERR_INVALID_ARG.
+ * A ray made of NaNs, infinities or zeros terminates (every loop of the trace is bounded, C2RT_MAX_CSG_HITS) and
+ * changes no other ray's result; its own record is whatever IEEE arithmetic makes of the reference's statements.
+ *
+ * Statuses, all decided before anything is enqueued or any caller pointer is read (the outputs are untouched):
+ * n == 0 is C2RT_OK whatever the pointers; null `rays`, or both outputs null: C2RT_ERR_INVALID_ARG;
+ * n > C2RT_MAX_RAYS: C2RT_ERR_LIMIT; no scene: C2RT_ERR_NO_SCENE.
+ *
+ * The _device variant takes device pointers and enqueues ONE kernel on `hip_stream` (a hipStream_t, NULL = default
+ * stream): no host sync, no event left in the queue, ordered with the frames and queries on the same stream,
+ * independent of those on other streams.  It needs no per-stream scratch (no tile masks, no retry list: the CSG
+ * hit stacks have their full capacity) and keeps no reference to the stream.  On a multi-device context the queries
+ * run on the lead device, as c2rt_render_pixel does. */
+int c2rt_trace_rays_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n,
+                           c2rt_ray_hit *hits_dev, float *rgb_dev, void *hip_stream);
+/* The same from and into HOST memory: staged through the context's own stream in chunks of at most 2^18 rays (the
+ * staging buffer holds one chunk of what is actually asked for, never n * 140 B); blocks until the results are there. */
+int c2rt_trace_rays(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb);
+
+/* Segment i is `Scene.testVisibility(from, to)` (rt/scene.d:62-78): visible[i] = 1 when no node intersects the ray
+ * from `from` towards `to` closer than |to - from|, else 0.  Statuses, streams and staging as above (`visible` is
+ * required). */
+int c2rt_test_visibility_device(c2rt_ctx *ctx, const c2rt_segment *seg_dev, uint64_t n,
+                                uint8_t *visible_dev, void *hip_stream);
+int c2rt_test_visibility(c2rt_ctx *ctx, const c2rt_segment *seg, uint64_t n, uint8_t *visible);
+
 /* Rank-0 side of the multi-GPU gather: `gathered_dev` holds `world`
  * consecutive compact strip buffers (rank-major, as ncclGather leaves them);
  * writes the de-interleaved full frame to `frame_dev`.  Both device

@@ -96,6 +96,19 @@ extern (C) nothrow @nogc
                                   float* out_rgb_dev, void* hip_stream);
     int c2rt_render_frames(c2rt_ctx*, const c2rt_camera_frame* cams, uint nFrames, const c2rt_render_opts*,
                            float* out_rgb, const shared(ubyte)* stop_flag);
+    /// ray queries: Renderer.trace (rt/renderer.d:325-376) and Scene.testVisibility (rt/scene.d:62-78) for the
+    /// caller's own rays, one per GPU lane; `dir` is used as given (trace() does not normalise); hits / rgb nullable,
+    /// not both; Vector is three doubles, so a Ray's orig and dir map onto c2rt_ray as they stand
+    enum C2RT_MAX_RAYS = 1u << 28;
+    struct c2rt_ray     { double[3] orig, dir; }
+    struct c2rt_segment { double[3] from, to; }
+    struct c2rt_ray_hit { int closest_node, leaf_geom; double dist, u, v; double[3] p, normal; }
+    int c2rt_trace_rays_device(c2rt_ctx*, const c2rt_ray* rays_dev, ulong n, c2rt_ray_hit* hits_dev, float* rgb_dev,
+                               void* hip_stream);
+    int c2rt_trace_rays(c2rt_ctx*, const c2rt_ray* rays, ulong n, c2rt_ray_hit* hits, float* rgb);
+    int c2rt_test_visibility_device(c2rt_ctx*, const c2rt_segment* seg_dev, ulong n, ubyte* visible_dev,
+                                    void* hip_stream);
+    int c2rt_test_visibility(c2rt_ctx*, const c2rt_segment* seg, ulong n, ubyte* visible);
 }
 
 /// Owns the flat tables for one uploaded scene (GC memory; c2rt_upload_scene copies them).
