@@ -1,0 +1,212 @@
+"""Build-authored scene text and seeded ray sets for tests/test_shade_reference.py (CPU) and tests/test_gpu_shade.py.
+
+One base scene at object scale ~10 (reads tests/golden/scenes/floor.bmp only), five light lists as variants of it.
+Nodes: 0 ground plane (Lambert + bitmap, scaling 0.05) | 1 raised plane y = 30 (Lambert + checker 0.75; the camera sees
+it from below, rays from above it from the other side) | 2 plane y = -8 (Phong + Procedure2, frequencies to 40; planes
+are unbounded and horizontal, so at most two can face one camera: this one is reached by the crafted and the random
+rays, and lit by the light below the ground that L5 and L33 have) | 3 sphere Phong + Procedure2 | 4 sphere Phong
+exponent 2.04391 strength 0.35 | 5 cube Phong 16, strength 0 | 6 sphere Phong 64, strength 1 | 7 CsgDiff cube - sphere,
+Lambert.  Solids float 0.5 above the ground so that vertical rays from y = 0.25 always reach the plane.
+
+Shadows the conditions of test_shade_reference rely on: lights 0.. sit in a cluster at (-45, 22, 0) and the cube (5)
+shades a strip of the ground to +x from ALL of them; lights "A" (25, 20, -45) and "B" (25, 20, 45) both see that strip,
+except where the CsgDiff (7) shades it from A alone."""
+import functools
+import os
+import shutil
+import tempfile
+
+import numpy as np
+
+import chess2rt_amd as c2
+from chess2rt_amd import _abi
+from golden_configs import SCENES
+from ray_query_util import eyeless_rays, screen_rays
+
+W, H = 61, 47
+VARIANTS = ("L1", "L2", "L4", "L5", "L33")
+AMBIENT = {"L1": "0 0 0", "L2": "0.08 0.1 0.12", "L4": "0.08 0.1 0.12", "L5": "0.08 0.1 0.12", "L33": "0.05 0.04 0.06"}
+GROUND, CEILING, PROC_PLANE, PROC_SPHERE, SOFT_SPHERE, CUBE, SHINY_SPHERE, CSG = range(8)
+PLANE_Y = {GROUND: 0.0, CEILING: 30.0, PROC_PLANE: -8.0}
+BMP_SCALING, CHECKER_SIZE = 0.05, 0.75
+FREQ_U, FREQ_V = (0.7, 13.0, 40.0), (1.3, 0.05, 37.0)
+CLUSTER, POS_A, POS_B, POS_DARK, POS_BELOW = (-45.0, 22.0, 0.0), (25.0, 20.0, -45.0), (25.0, 20.0, 45.0), (0.0, 25.0, -20.0), (10.0, -3.0, 5.0)
+
+_TMP = tempfile.mkdtemp(prefix="c2rt_shade_")
+shutil.copy(os.path.join(SCENES, "floor.bmp"), os.path.join(_TMP, "floor.bmp"))
+
+
+def _light(name, pos, color, power):
+    return 'PointLight "%s" { pos %r %r %r; color %s; power %s }' % (name, float(pos[0]), float(pos[1]), float(pos[2]), color, power)
+
+
+def lights_of(variant):
+    l0 = _light("l0", CLUSTER, "1 0.95 0.9", 2600)
+    la = _light("la", POS_A, "0.7 0.8 1", 2200)
+    dark = _light("dark", POS_DARK, "0 0 0", 5000)
+    lb = _light("lb", POS_B, "0.9 1e-30 0.6", 2400)          # 1e-30 * 2400 < 2^-60: the lean fp32 division is off for it
+    below = _light("below", POS_BELOW, "0.8 1 0.7", 900)
+    if variant == "L1":
+        return [l0]
+    if variant == "L2":
+        return [l0, la]
+    if variant == "L4":
+        return [l0, la, dark, lb]
+    if variant == "L5":
+        return [l0, la, dark, lb, below]
+    rng = np.random.RandomState(33)
+    out = []
+    for i in range(31):
+        col = "%.3f %.3f %.3f" % tuple(rng.uniform(0.3, 1.0, size=3))
+        if i == 16:
+            out.append(_light("c16", POS_BELOW, col, 900))
+        else:
+            off = rng.uniform(-1.5, 1.5, size=3)
+            out.append(_light("c%d" % i, tuple(np.round(np.array(CLUSTER) + off, 3)), col, 120))
+    out.append(_light("l31", POS_A, "0.7 0.8 1", 1500))
+    out.append(_light("l32", POS_B, "1 0.75 0.5", 1700))
+    return out
+
+
+def scene_text(variant, libm_free=False):
+    geoms = ['Plane "ground" { y 0 }', 'Plane "ceiling" { y 30 }', 'Plane "deep" { y -8 }',
+             'Sphere "s_proc" { center -5 8 28; R 7.5 }', 'Sphere "s_soft" { center -20 7 -30; R 6.5 }',
+             'Cube "k1" { center -15 8.5 0; side 16 }', 'Sphere "s_shiny" { center 4 6 -38; R 5.5 }',
+             'Cube "k2" { center 25 6.5 -20; side 12 }', 'Sphere "k2s" { center 25 9 -23; R 6.5 }',
+             'CsgDiff "diff" { left "k2"; right "k2s" }']
+    textures = ['BitmapTexture "bmp" { file "floor.bmp"; scaling %r }' % BMP_SCALING,
+                'Checker "chk" { color1 0.9 0.1 0.2; color2 0.15 0.8 0.95; size %r }' % CHECKER_SIZE,
+                'Procedure2 "proc" { freqU %r %r %r; freqV %r %r %r; colorU { color 0.3 0.05 0.1; color 0.1 0.25 0.05; color 0.05 0.1 0.2 }; '
+                'colorV { color 0.2 0.1 0.02; color 0.02 0.2 0.15; color 0.12 0.03 0.3 } }' % (FREQ_U + FREQ_V)]
+    shaders = ['Lambert "sh_ground" { texture "bmp" }', 'Lambert "sh_ceiling" { texture "chk" }',
+               'Phong "sh_deep" { texture "proc"; exponent 24; strength 0.6 }',
+               'Phong "sh_proc" { texture "proc"; exponent 9.5; strength 0.8 }',
+               'Phong "sh_soft" { color 0.2 0.6 0.3; exponent 2.04391; strength 0.35 }',
+               'Phong "sh_cube" { color 0.7 0.5 0.2; exponent 16; strength 0 }',
+               'Phong "sh_shiny" { color 0.1 0.2 0.7; exponent 64; strength 1 }',
+               'Lambert "sh_csg" { color 0.8 0.7 0.6 }']
+    nodes = [("ground", "sh_ground"), ("ceiling", "sh_ceiling"), ("deep", "sh_deep"), ("s_proc", "sh_proc"), ("s_soft", "sh_soft"),
+             ("k1", "sh_cube"), ("s_shiny", "sh_shiny"), ("diff", "sh_csg")]
+    if libm_free:   # no Phong, no Procedure2: no pow and no sin on the path
+        nodes = [n for n in nodes if n[1] in ("sh_ground", "sh_ceiling", "sh_csg")]
+    return "\n".join([
+        "Scene {", '  Name "shade_%s"' % variant,
+        "  GlobalSettings { frameWidth %d; frameHeight %d; AAEnabled false; ambientLightColor %s }" % (W, H, AMBIENT[variant]),
+        "  Camera { pos 5 24 -72; yaw 0; pitch -17; roll 0; fov 78 }",
+        "  Lights {\n    " + "\n    ".join(lights_of(variant)) + "\n  }",
+        "  Geometries {\n    " + "\n    ".join(geoms) + "\n  }",
+        "  Textures {\n    " + "\n    ".join(textures) + "\n  }",
+        "  Shaders {\n    " + "\n    ".join(shaders) + "\n  }",
+        "  Nodes {\n    " + "\n    ".join('Node "n%d" { geometry "%s"; shader "%s" }' % (i, g, s) for i, (g, s) in enumerate(nodes)) + "\n  }",
+        "}", ""])
+
+
+@functools.lru_cache(maxsize=None)
+def load(variant, libm_free=False):
+    """(scene, camera frame, one-tap options) of a variant at 61x47; computed once, treated as read-only"""
+    path = os.path.join(_TMP, "shade_%s%s.sdl" % (variant, "_nolibm" if libm_free else ""))
+    with open(path, "w") as f:
+        f.write(scene_text(variant, libm_free))
+    scene = c2.parseSceneFromFile(path)
+    scene.setFrameSize(W, H)
+    scene.setAA(False)
+    scene.setDof(False)
+    cam = scene.beginFrame()
+    return scene, cam, scene.renderOpts(taps=_abi.TAPS_1)
+
+
+# ---- crafted texture coordinates -----------------------------------------------------------------------------------------
+
+
+def _ulps(x):
+    x = np.asarray(x, dtype=np.float64)
+    return np.concatenate([x, np.nextafter(x, np.inf), np.nextafter(x, -np.inf)])
+
+
+def bitmap_uv():
+    """(u, v) on the ground plane; floor.bmp is 256 x 256, `scaling` as the float the loader holds"""
+    s = np.float64(np.float32(BMP_SCALING))
+    size = 256
+    edges = np.array([0, 1, 2, size - 2, size - 1, size], dtype=np.float64) / size
+    bounds = _ulps(np.concatenate([(edges + m) / s for m in (0.0, 3.0, -2.0)]))              # texel boundaries, +- 1 ulp
+    rng = np.random.RandomState(11)
+    inside = (rng.uniform(0, 1, size=len(bounds)) + 7.0) / s
+    u = [bounds, inside]
+    v = [inside, bounds]
+    j = np.arange(1, 41)
+    red = (2.0 - j * 1e-10) / s                                                              # (float) frac rounds to 1: red
+    u += [red, inside[:40]]
+    v += [inside[:40], red]
+    u += [np.full(8, -1e-18), rng.uniform(0, 20, 8)]
+    v += [rng.uniform(0, 20, 8), np.full(8, -1e-18)]
+    neg = -rng.uniform(0.01, 300, size=60)                                                   # negative coordinates
+    u += [neg, rng.uniform(-300, 300, 60)]
+    v += [rng.uniform(-300, 300, 60), neg]
+    g = (np.arange(9) + 0.5) / 9
+    for (cx, cy) in ((size - 1, size - 1), (0, 0), (size - 1, 3), (100, size - 1)):          # 9x9 inside one texel
+        gu, gv = np.meshgrid((cx + g) / size / s, (cy + g) / size / s)
+        u.append(gu.ravel())
+        v.append(gv.ravel())
+    return np.concatenate(u), np.concatenate(v)
+
+
+def checker_uv():
+    k = np.concatenate([np.arange(-12, 13), [1000, -1000, 4001, -4001]]).astype(np.float64)
+    exact = _ulps(k * CHECKER_SIZE)                                                          # u / size integral, +- 1 ulp
+    big = np.array([3e9, -3e9, 2.0 ** 31, 2.0 ** 31 - 1, -(2.0 ** 31), -(2.0 ** 31) - 1, 2.0 ** 31 + 1, 1e12, -1e12, 2.0 ** 32 + 1,
+                    2.0 ** 33 + 3, -(2.0 ** 32) - 2]) * CHECKER_SIZE
+    # further out still, 2^34 .. 2^53 squares away: there the shadow segment towards a light that lies BELOW this plane
+    # leaves a point just above it at a slope under 1e-9, which Plane.intersect calls the horizon (geometry.d:35), so the
+    # light is visible from the side that faces away from it — the samples with cosTheta <= 0 and the light visible
+    k = np.arange(34, 54)
+    horizon = np.concatenate([2.0 ** k + 1, -(2.0 ** k) - 3, 3 * 2.0 ** k + 2, -3 * 2.0 ** k]) * CHECKER_SIZE
+    rng = np.random.RandomState(12)
+    u = np.concatenate([exact, big, rng.uniform(-40, 40, len(exact) + len(big)), big, horizon, rng.uniform(-40, 40, len(horizon))])
+    v = np.concatenate([rng.uniform(-40, 40, len(exact) + len(big)), exact, big, big[::-1], rng.uniform(-40, 40, len(horizon)), horizon])
+    return u, v
+
+
+def procedure2_uv():
+    tiny = np.array([0.0, -0.0, 5e-324, -5e-324, 1e-300, -1e-300, 1e-20, -1e-20])
+    mult = []
+    for f in FREQ_U + FREQ_V:
+        kmax = int(300 * f / np.pi)
+        ks = np.unique(np.concatenate([np.arange(1, min(kmax, 6) + 1), np.linspace(1, kmax, 12).astype(int)])) if kmax >= 1 else np.array([1])
+        mult.append(ks * np.pi / f)
+    mult = np.concatenate(mult)
+    mult = np.concatenate([mult, -mult])
+    far = np.array([300.0, -300.0, 299.999, -299.5, 287.3, -263.1])
+    special = np.concatenate([tiny, mult, far])
+    rng = np.random.RandomState(13)
+    other = rng.uniform(-300, 300, len(special))
+    return np.concatenate([special, other, far]), np.concatenate([other, special, far[::-1]])
+
+
+CRAFTED = {GROUND: bitmap_uv, CEILING: checker_uv, PROC_PLANE: procedure2_uv}
+
+
+def crafted_rays():
+    """vertical rays d = (0, -1, 0) from 0.25 above each textured plane: u = x and v = z exactly (geometry.d:54-55).
+    -> (rays (n, 6), node each ray is meant for (n,))"""
+    rays, target = [], []
+    for node in (GROUND, CEILING, PROC_PLANE):
+        u, v = CRAFTED[node]()
+        r = np.zeros((len(u), 6))
+        r[:, 0], r[:, 1], r[:, 2], r[:, 4] = u, PLANE_Y[node] + 0.25, v, -1.0
+        rays.append(r)
+        target.append(np.full(len(u), node))
+    return np.ascontiguousarray(np.vstack(rays)), np.concatenate(target)
+
+
+RAY_SETS = ("screen", "crafted", "random")
+RANDOM_SEED = 14
+
+
+@functools.lru_cache(maxsize=None)
+def ray_set(variant, name):
+    scene, cam, _ = load(variant)
+    if name == "screen":
+        return screen_rays(cam, W, H)
+    if name == "crafted":
+        return crafted_rays()[0]
+    return eyeless_rays(scene.desc, RANDOM_SEED, 1500)
