@@ -42,6 +42,8 @@ KERNELFLAGS_u5 :=
 # unit 6: the ray / visibility query kernels, every CSG depth in one unit (exact:: only: a fraction of a frame unit's
 # code); the flags of the frame units were tuned on the frame kernels and have not been measured here
 KERNELFLAGS_u6 :=
+# unit 7: the hit planes of a camera frame (c2rt_render_hits), every CSG depth; exact:: only, as unit 6
+KERNELFLAGS_u7 :=
 CXXFLAGS   := -O2 -std=c++17 -fPIC $(FPFLAGS) -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 CSRC       := chess2rt_amd/csrc
 # development knob: `make VARIANT=name EXTRA_HIPFLAGS=... EXTRA_KERNEL_FLAGS=...` builds chess2rt_amd/libc2rt_name.so
@@ -50,7 +52,7 @@ VARIANT    ?=
 BUILD      := build$(if $(VARIANT),_$(VARIANT))
 LIBNAME    := chess2rt_amd/libc2rt$(if $(VARIANT),_$(VARIANT)).so
 
-UNITS      := 0 1 2 3 4 5 6
+UNITS      := 0 1 2 3 4 5 6 7
 KOBJS      := $(foreach u,$(UNITS),$(BUILD)/c2rt_kernels_u$(u).o)
 HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/scene.o $(BUILD)/host_api.o
 

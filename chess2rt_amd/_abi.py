@@ -139,6 +139,19 @@ class RayHit(C.Structure):
     ]
 
 
+class HitPlanes(C.Structure):
+    """c2rt_hit_planes: one nullable pointer per plane (host or device memory, by entry point)"""
+    _fields_ = [
+        ("node", C.c_void_p),
+        ("leaf", C.c_void_p),
+        ("dist", C.c_void_p),
+        ("uv", C.c_void_p),
+        ("p", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("rgb", C.c_void_p),
+    ]
+
+
 class RayStats(C.Structure):
     _fields_ = [("primary_rays", C.c_uint64), ("shadow_rays", C.c_uint64)]
 
@@ -202,6 +215,8 @@ C2RT_SYMBOLS = {
     "c2rt_trace_rays": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP]),
     "c2rt_test_visibility_device": (C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP]),
     "c2rt_test_visibility": (C.c_int, [_VP, _VP, C.c_uint64, _VP]),
+    "c2rt_render_hits_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(HitPlanes), _VP]),
+    "c2rt_render_hits": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(HitPlanes)]),
     "c2rt_deinterleave_strips": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
     "c2rt_encode_rgb32": (C.c_int, [_VP, _VP, _VP, C.c_uint64, _VP]),
     "c2rt_render_frame_rgb32": (C.c_int, [_VP, _CAM_P, _OPTS_P, _VP, _VP]),
@@ -227,6 +242,7 @@ C2RT_HOST_SYMBOLS = {
     "c2rt_host_render_scene_async": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "c2rt_host_render_wait": (C.c_int, [_VP]),
     "c2rt_host_render_pixel": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.POINTER(TraceResult)]),
+    "c2rt_host_render_hits": (C.c_int, [_VP, _VP, C.POINTER(HitPlanes)]),
     "c2rt_host_bmp_decode": (C.c_int, [_VP, C.c_size_t, _u32p, _u32p, C.POINTER(_f32p)]),
     "c2rt_host_texture_gamma": (None, [_VP, C.c_size_t, C.c_float]),
     "c2rt_host_bmp_encode": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),

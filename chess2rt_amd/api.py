@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (CameraFrame, HostCamera, HostSettings, Ray, RayHit, RayStats, RenderOpts, SceneDesc, Segment, TraceResult)
+from ._abi import (CameraFrame, HitPlanes, HostCamera, HostSettings, Ray, RayHit, RayStats, RenderOpts, SceneDesc, Segment, TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
 RAY_HIT_DTYPE = np.dtype({
@@ -22,6 +22,25 @@ RAY_HIT_DTYPE = np.dtype({
                 RayHit.p.offset, RayHit.normal.offset],
     "itemsize": C.sizeof(RayHit),
 })
+
+
+# c2rt_hit_planes: plane name -> (dtype, components per pixel), in the order of the struct's members
+HIT_PLANES = {"node": (np.int32, 1), "leaf": (np.int32, 1), "dist": (np.float64, 1), "uv": (np.float64, 2),
+              "p": (np.float64, 3), "normal": (np.float64, 3), "rgb": (np.float32, 3)}
+
+
+def _new_hit_planes(names, rows, width):
+    """(HitPlanes of fresh host arrays, {name: array}) for the planes named; the others stay null"""
+    names = tuple(names)
+    for n in names:
+        if n not in HIT_PLANES:
+            raise ValueError("unknown hit plane %r (one of %s)" % (n, ", ".join(HIT_PLANES)))
+    out, pl = {}, HitPlanes()
+    for n in names:
+        dtype, comps = HIT_PLANES[n]
+        out[n] = np.empty((rows, width) if comps == 1 else (rows, width, comps), dtype=dtype)
+        setattr(pl, n, out[n].ctypes.data)
+    return pl, out
 
 
 class C2rtError(RuntimeError):
@@ -271,6 +290,25 @@ class Context:
         self._check(self._lib.c2rt_trace_rays_device(self._h, C.c_void_p(rays_ptr), int(n), C.c_void_p(hits_ptr or None),
                                                      C.c_void_p(rgb_ptr or None), C.c_void_p(stream)))
 
+    def renderHits(self, cam, opts, planes=("node", "leaf", "dist", "uv", "p", "normal", "rgb")):
+        """What every pixel of the frame hit (c2rt_render_hits): a dict of numpy arrays for the planes named — node,
+        leaf (int32) and dist (float64) of shape (local_rows, W), uv (local_rows, W, 2), p and normal (local_rows, W, 3)
+        float64, rgb (local_rows, W, 3) float32: renderPixel(x, y)'s record at [y, x].  Planes not named are neither
+        computed nor stored.  No depth of field, stereo, count_rays or prepass_bucket (C2rtError, ERR_UNSUPPORTED)."""
+        pl, out = _new_hit_planes(planes, self.localRows(opts), opts.width)
+        self._check(self._lib.c2rt_render_hits(self._h, C.byref(cam), C.byref(opts), C.byref(pl)))
+        return out
+
+    def renderHitsDevice(self, cam, opts, ptrs, stream=0):
+        """Enqueue the hit planes on `stream` into device memory: `ptrs` maps plane names (HIT_PLANES) to device
+        pointers of local_rows * W * components elements; planes left out (or 0 / None) are not written."""
+        pl = HitPlanes()
+        for n, ptr in dict(ptrs).items():
+            if n not in HIT_PLANES:
+                raise ValueError("unknown hit plane %r (one of %s)" % (n, ", ".join(HIT_PLANES)))
+            setattr(pl, n, ptr or None)
+        self._check(self._lib.c2rt_render_hits_device(self._h, C.byref(cam), C.byref(opts), C.byref(pl), C.c_void_p(stream)))
+
     def testVisibility(self, segments):
         """Scene.testVisibility for (n, 6) float64 segments (from, to): (n,) uint8, 1 = nothing in between."""
         seg = np.ascontiguousarray(segments, dtype=np.float64)
@@ -338,6 +376,15 @@ class Renderer:
         r = TraceResult()
         self.ctx._check(self._lib.c2rt_host_render_pixel(self.ctx.handle, self.scene._h, int(x), int(y), C.byref(r)))
         return r
+
+
+    def renderHits(self, planes=("node", "leaf", "dist", "uv", "p", "normal", "rgb")):
+        """Context.renderHits for the scene's own camera and frame size (c2rt_host_render_hits); a camera with depth
+        of field or stereo is refused (C2rtError, ERR_UNSUPPORTED)."""
+        s = self.scene.settings
+        pl, out = _new_hit_planes(planes, s.frame_height, s.frame_width)
+        self.ctx._check(self._lib.c2rt_host_render_hits(self.ctx.handle, self.scene._h, C.byref(pl)))
+        return out
 
 
 def renderPixel(scene, x, y, ctx=None):

@@ -21,6 +21,12 @@
 
 #include "scene_plan.h"
 
+namespace c2rt {
+/* c2rt_kernels.hip, unit 7 (declared here: c2rt_device.h is a prerequisite of every frame-kernel unit).  Rows [row0,
+ * row0 + rows) of the frame's local rows into planes whose first row is row0; returns a hipError_t as int. */
+int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream);
+} // namespace c2rt
+
 using namespace c2rt;
 
 constexpr int kMaxChunks = 16;     /* row chunks of a host-output frame */
@@ -1200,6 +1206,101 @@ int c2rt_test_visibility(c2rt_ctx *ctx, const c2rt_segment *seg, uint64_t n, uin
         const int e = launch_test_visibility(p, ctx->plan.csg_levels, seg_dev, m, vis_dev, ctx->stream);
         if (e != 0) return fail(ctx, C2RT_ERR_HIP, "visibility query kernel launch: %s", hipGetErrorString((hipError_t)e));
         HIP_TRY(ctx, hipMemcpyAsync(visible + i, vis_dev, m, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return C2RT_OK;
+}
+
+/* ---- hit planes of a camera frame (kernel unit 7) ---------------------------------------------------------------- */
+
+static bool any_plane(const c2rt_hit_planes *pl) { return pl->node || pl->leaf || pl->dist || pl->uv || pl->p || pl->normal || pl->rgb; }
+
+/* the refusals of both entry points, in the documented order: a frame call's, then the planes', then the modes in which
+ * a pixel is not one ray */
+static int check_hit_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_hit_planes *planes)
+{
+    if (const int st = check_frame_args(ctx, cam, opts)) return st;
+    if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
+    if (!any_plane(planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all seven pointers of c2rt_hit_planes are null");
+    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: a pixel's record is one ray's, a lens has many per pixel");
+    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: a pixel's record is one ray's, a stereo camera has two per pixel");
+    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the hit planes do not count rays");
+    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
+    return C2RT_OK;
+}
+
+/* The frame's parameter block for its camera, strips and size, with the query settings on top (query_params): exact::
+ * arithmetic, full-capacity hit stack, no culling rectangles (every mask all ones), no ground node, one tap. */
+static void hit_params(const c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, RenderParams &p)
+{
+    frame_params(ctx, cam, opts, p);
+    p.force_exact = 1;
+    p.taps = 1;
+    p.seed = 0;
+    p.n_cull = 0;
+    p.n_cull_lights = 0;
+    p.ground_node = -1;
+    p.row_group_start = 0;
+    p.csg_cap = ctx->plan.csg_levels == 0 ? 0u : (uint32_t)kCsgFullCap(ctx->plan.csg_levels);
+    p.redo_counter = ctx->counters + 3;
+}
+
+int c2rt_render_hits_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                            const c2rt_hit_planes *planes_dev, void *hip_stream)
+{
+    if (const int st = check_hit_args(ctx, cam, opts, planes_dev)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    if (p.local_rows == 0) return C2RT_OK;
+    const int e = launch_hit_planes(p, ctx->plan.csg_levels, *planes_dev, 0, p.local_rows, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "hit plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+/* Host variant: chunks of whole rows, at most kQueryChunk pixels each, through the context's staging allocation laid
+ * out plane after plane for the chunk size and only for the planes asked for — 92 B per pixel, 23 MiB at most,
+ * whatever the frame size.  Each chunk ends with a stream sync, so the call blocks as documented. */
+int c2rt_render_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_hit_planes *planes_host)
+{
+    if (const int st = check_hit_args(ctx, cam, opts, planes_host)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    const uint32_t rows = p.local_rows, width = p.width;
+    if (rows == 0) return C2RT_OK;
+    uint32_t chunk_rows = (uint32_t)(kQueryChunk / width); /* width <= 2^16: at least four rows */
+    if (chunk_rows > rows) chunk_rows = rows;
+    const size_t chunk_px = (size_t)chunk_rows * width;
+    /* bytes per pixel of the seven planes, in the order of the struct's members */
+    char *const host[7] = {reinterpret_cast<char *>(planes_host->node), reinterpret_cast<char *>(planes_host->leaf),
+                           reinterpret_cast<char *>(planes_host->dist), reinterpret_cast<char *>(planes_host->uv),
+                           reinterpret_cast<char *>(planes_host->p), reinterpret_cast<char *>(planes_host->normal),
+                           reinterpret_cast<char *>(planes_host->rgb)};
+    const size_t px_bytes[7] = {4, 4, 8, 16, 24, 24, 12};
+    size_t off[7], bytes = 0;
+    for (int k = 0; k < 7; ++k) {
+        off[k] = bytes;
+        if (host[k]) bytes += align256(chunk_px * px_bytes[k]);
+    }
+    if (const int st = ensure_staging(ctx, bytes)) return st;
+    char *base = reinterpret_cast<char *>(ctx->frame);
+    const auto dev = [&](int k) { return host[k] ? base + off[k] : nullptr; };
+    c2rt_hit_planes d;
+    d.node = reinterpret_cast<int32_t *>(dev(0));
+    d.leaf = reinterpret_cast<int32_t *>(dev(1));
+    d.dist = reinterpret_cast<double *>(dev(2));
+    d.uv = reinterpret_cast<double *>(dev(3));
+    d.p = reinterpret_cast<double *>(dev(4));
+    d.normal = reinterpret_cast<double *>(dev(5));
+    d.rgb = reinterpret_cast<float *>(dev(6));
+    for (uint32_t r0 = 0; r0 < rows; r0 += chunk_rows) {
+        const uint32_t m = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
+        const int e = launch_hit_planes(p, ctx->plan.csg_levels, d, r0, m, ctx->stream);
+        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "hit plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+        const size_t first = (size_t)r0 * width, px = (size_t)m * width;
+        for (int k = 0; k < 7; ++k)
+            if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k] + first * px_bytes[k], base + off[k], px * px_bytes[k], hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     return C2RT_OK;

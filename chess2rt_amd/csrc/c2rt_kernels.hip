@@ -375,11 +375,12 @@ __global__ void __launch_bounds__(256) tile_masks_batch_kernel(const RenderParam
  * Instantiation is split over translation units so that the (slow) device
  * compiles run in parallel: the Makefile builds this file once per
  * C2RT_UNIT = 0..4 (the frame kernel for that many CSG nesting levels) and
- * once with C2RT_UNIT = 5 (probe, de-interleave, encode, dispatcher) and once
- * with C2RT_UNIT = 6 (the ray and visibility queries, c2rt_trace_rays).
+ * once with C2RT_UNIT = 5 (probe, de-interleave, encode, dispatcher), once
+ * with C2RT_UNIT = 6 (the ray and visibility queries, c2rt_trace_rays) and once
+ * with C2RT_UNIT = 7 (the hit planes of a camera frame, c2rt_render_hits).
  */
 #ifndef C2RT_UNIT
-#error "compile with -DC2RT_UNIT=0..6 (see Makefile)"
+#error "compile with -DC2RT_UNIT=0..7 (see Makefile)"
 #endif
 
 #if C2RT_UNIT >= 0 && C2RT_UNIT <= C2RT_MAX_CSG_DEPTH
@@ -537,7 +538,7 @@ int launch_encode_rgb32(const float *frame, uint32_t *out, uint64_t n_pixels, co
     return (int)hipGetLastError();
 }
 
-#elif C2RT_UNIT == 6
+#elif C2RT_UNIT == 6 || C2RT_UNIT == 7 /* the query units: what they share, then one or the other */
 
 /*
  * Ray and visibility queries (c2rt_trace_rays*, c2rt_test_visibility*): the caller's rays instead of a camera's.
@@ -601,6 +602,11 @@ DEV void query_ctx(exact::Ctx &cx, const RenderParams &P, exact::KArgs K, char *
     cx.primary_ground_only = false;
     cx.ground_y = 0;
 }
+
+} // namespace
+
+#if C2RT_UNIT == 6
+namespace {
 
 /* six doubles of an array-of-structures input record (c2rt_ray, c2rt_segment): three 16-byte loads where the
  * hardware takes them at 8-byte alignment */
@@ -744,6 +750,189 @@ int launch_test_visibility(const RenderParams &p, int csg_levels, const c2rt_seg
     default: return (int)hipErrorInvalidValue;
     }
 }
+
+#else /* C2RT_UNIT == 7 */
+
+/*
+ * Hit planes (c2rt_render_hits*): the closest-hit record of the ray through the integer corner of every pixel of a
+ * camera frame, one plane per field.  The query kernel above with the caller's ray array replaced by the camera: the
+ * lane builds its own screen ray (screen_ray<false>, normalized — the operations the frame kernels and the probe
+ * apply to (x, y)), so nothing is read but the scene, and only the planes asked for are written.  exact:: arithmetic,
+ * every culling mask all ones, full-capacity hit stack, one wavefront per workgroup, no scratch.
+ *
+ * Pixel -> lane (C2RT_HIT_MAP; the output does not depend on it): 0 = a run of 64 pixels of one row — every store
+ * instruction of a scalar plane covers 256 / 512 contiguous bytes; 1 = the frames' 8x8 tile (kept); 2 = 16x4.
+ * lecture5.sdl 1080p, all seven planes / node + dist / all but rgb: 117.9 / 62.6 / 65.3 us for the run, 112.8 / 60.1 /
+ * 62.0 for the 8x8 tile, 112.5 / 59.9 / 62.1 for 16x4 (profiles/hit_planes.md): coherent rays and fewer distinct
+ * closest nodes per wave are worth more than the wider stores.  Lanes past the right or bottom edge are masked out by
+ * control flow before the trace, as the query kernel masks its tail.
+ *
+ * Stores (C2RT_HIT_ROWSTORE): 0 = each lane stores its own values, the three-component planes as three 8-byte stores
+ * at a 24-byte stride (kept); 1 = uv / p / normal are staged in the dead hit stack and written as rows, lane l storing
+ * words l, l + 64, ... of each tile row's contiguous run (the query kernel's record store) — SLOWER here, 67.2
+ * against 62.0 us for all but rgb (8x8), 70.1 against 65.3 (run of 64): a plane's values of a tile row are already
+ * adjacent lanes' and the L2 merges the partial lines, so the LDS round trip and the two barriers per plane buy
+ * nothing.  All plain vector stores.
+ *
+ * The planes and the row window of a host chunk are kernel arguments of their own behind the parameter block:
+ * RenderParams is the frame kernels' and does not change.  `out` points at row `row0` of the (compact) planes.
+ */
+#ifndef C2RT_HIT_MAP
+#define C2RT_HIT_MAP 1
+#endif
+#ifndef C2RT_HIT_ROWSTORE
+#define C2RT_HIT_ROWSTORE 0
+#endif
+namespace {
+
+constexpr int kHitTileW = C2RT_HIT_MAP == 0 ? 64 : (C2RT_HIT_MAP == 1 ? 8 : 16), kHitTileH = kWave / kHitTileW;
+constexpr size_t kHitStageBytes = C2RT_HIT_ROWSTORE ? (size_t)kWave * 3 * 8 : 0;
+static_assert(sizeof(RenderParams) + sizeof(c2rt_hit_planes) + 16 <= 4096, "the kernel-argument segment holds at most 4 KiB");
+static_assert(sizeof(c2rt_hit_planes) == 56, "ABI layout of c2rt_hit_planes");
+
+/* one C-component plane of doubles, as rows: the wave's tile is kHitTileH runs of kHitTileW * C contiguous words.
+ * Every lane of the wave takes part, live or not; words of dead pixels are not stored (they were never staged). */
+template <int C>
+DEV void store_rows(double *plane, unsigned long long *stage, int lane, bool live, const double (&v)[C],
+                    uint32_t width, uint32_t rows, uint32_t x0, uint32_t r0)
+{
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < C; ++k) stage[lane * C + k] = (unsigned long long)__double_as_longlong(v[k]);
+    }
+    __builtin_amdgcn_wave_barrier(); /* LDS operations of one wave complete in order; the workgroup is this wave */
+    unsigned long long *out = reinterpret_cast<unsigned long long *>(plane);
+    constexpr uint32_t run = (uint32_t)kHitTileW * C;
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        const uint32_t w = (uint32_t)lane + (uint32_t)(k * kWave);
+        const uint32_t tr = w / run, c = w % run;
+        const uint32_t r = r0 + tr, col = x0 * C + c;
+        if (r < rows && col < width * C) out[(size_t)r * width * C + col] = stage[w];
+    }
+    __builtin_amdgcn_wave_barrier(); /* the next plane, then the shadow rays, reuse the stack */
+}
+
+template <int LEVELS, bool MLC>
+__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, MLC)
+hit_planes_kernel(const RenderParams P, const c2rt_hit_planes out, const uint32_t row0, const uint32_t rows, const uint32_t tiles_x)
+{
+    using namespace exact;
+    extern __shared__ __align__(16) char lds[];
+    const int lane = (int)threadIdx.x;
+    const uint32_t trow = blockIdx.x / tiles_x, tcol = blockIdx.x % tiles_x; /* the grid is tiles_x * ceil(rows / kHitTileH) */
+    const uint32_t x0 = tcol * kHitTileW, r0 = trow * kHitTileH;
+    const uint32_t x = x0 + (uint32_t)(lane % kHitTileW);
+    const uint32_t r = r0 + (uint32_t)(lane / kHitTileW); /* row within this launch */
+    const bool live = x < P.width && r < rows;
+    const bool record = out.dist || out.uv || out.p || out.normal; /* wave-uniform: best.dist and the surface are read */
+    Ctx cx;
+    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
+    D3 d = mk(0, 0, 0);
+    Hit best;
+    Surf surf;
+    Mat mat;
+    int closest = -1;
+    const size_t idx = (size_t)r * P.width + x;
+    if (live) {
+        /* local row -> frame row under interleaved strips, as render_tile maps it */
+        const uint32_t lr = r + row0;
+        uint32_t y = lr;
+        if (P.strip_world > 1) {
+            const uint32_t sh = P.strip_height;
+            y = ((lr / sh) * P.strip_world + P.strip_rank) * sh + lr % sh;
+        }
+        Rng rng = {0u, 0, 0};
+        D3 o, raw;
+        screen_ray<false>(cx.bad, P, (double)x, (double)y, 0, rng, o, raw);
+        d = normalized(cx.bad, raw); /* raytrace(): rt/camera.d:144-147 */
+        closest = trace_closest<LEVELS>(cx, o, d, record, best, surf, mat);
+        if (out.node) out.node[idx] = closest;
+        if (out.leaf) out.leaf[idx] = closest >= 0 ? best.g : -1;
+        if (out.dist) out.dist[idx] = best.dist;
+#if !C2RT_HIT_ROWSTORE
+        if (out.uv) {
+            typedef double __attribute__((ext_vector_type(2), aligned(8))) d2_t;
+            d2_t uv;
+            uv.x = surf.u;
+            uv.y = surf.v;
+            *reinterpret_cast<d2_t *>(out.uv + idx * 2) = uv;
+        }
+        if (out.p) {
+            out.p[idx * 3 + 0] = surf.p.x;
+            out.p[idx * 3 + 1] = surf.p.y;
+            out.p[idx * 3 + 2] = surf.p.z;
+        }
+        if (out.normal) {
+            out.normal[idx * 3 + 0] = surf.n.x;
+            out.normal[idx * 3 + 1] = surf.n.y;
+            out.normal[idx * 3 + 2] = surf.n.z;
+        }
+#endif
+    }
+#if C2RT_HIT_ROWSTORE
+    {
+        unsigned long long *stage = reinterpret_cast<unsigned long long *>(lds); /* [64][3] */
+        if (out.uv) {
+            const double v[2] = {surf.u, surf.v};
+            store_rows<2>(out.uv, stage, lane, live, v, P.width, rows, x0, r0);
+        }
+        if (out.p) {
+            const double v[3] = {surf.p.x, surf.p.y, surf.p.z};
+            store_rows<3>(out.p, stage, lane, live, v, P.width, rows, x0, r0);
+        }
+        if (out.normal) {
+            const double v[3] = {surf.n.x, surf.n.y, surf.n.z};
+            store_rows<3>(out.normal, stage, lane, live, v, P.width, rows, x0, r0);
+        }
+    }
+#endif
+    if (live && out.rgb) {
+        F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
+        uint32_t shadow_rays = 0;
+        if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
+        typedef float __attribute__((ext_vector_type(3), aligned(4))) f3_t;
+        f3_t v3;
+        v3.x = c.r;
+        v3.y = c.g;
+        v3.z = c.b;
+        *reinterpret_cast<f3_t *>(out.rgb + idx * 3) = v3;
+    }
+}
+
+template <int LEVELS>
+int launch_hit_planes_level(const RenderParams &p, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, hipStream_t s)
+{
+    const uint32_t tiles_x = (p.width + kHitTileW - 1) / kHitTileW, tiles_y = (rows + kHitTileH - 1) / kHitTileH;
+    const dim3 grid(tiles_x * tiles_y), block(kWave); /* at most 2^16 x 2^16 pixels / 64 */
+    const size_t stack = (size_t)p.csg_cap * kCsgLdsPerEntry;
+    const size_t lds = stack > kHitStageBytes ? stack : kHitStageBytes;
+    if (p.n_lights > 1) hipLaunchKernelGGL((hit_planes_kernel<LEVELS, true>), grid, block, lds, s, p, out, row0, rows, tiles_x);
+    else hipLaunchKernelGGL((hit_planes_kernel<LEVELS, false>), grid, block, lds, s, p, out, row0, rows, tiles_x);
+    return (int)hipGetLastError();
+}
+
+} // namespace
+
+/* Rows [row0, row0 + rows) of the local rows of the frame `p` describes (frame_params with the query settings on top:
+ * force_exact, csg_cap = kCsgFullCap(csg_levels), no culling, no ground node) into planes whose first row is row0;
+ * device pointers, at least one of them non-null, rows > 0.  Declared in c2rt_api.cpp: c2rt_device.h is the frame
+ * units' and stays as it is. */
+int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!rows || !p.width || !(out.node || out.leaf || out.dist || out.uv || out.p || out.normal || out.rgb)) return (int)hipErrorInvalidValue;
+    switch (csg_levels) {
+    case 0: return launch_hit_planes_level<0>(p, out, row0, rows, s);
+    case 1: return launch_hit_planes_level<1>(p, out, row0, rows, s);
+    case 2: return launch_hit_planes_level<2>(p, out, row0, rows, s);
+    case 3: return launch_hit_planes_level<3>(p, out, row0, rows, s);
+    case 4: return launch_hit_planes_level<4>(p, out, row0, rows, s);
+    default: return (int)hipErrorInvalidValue;
+    }
+}
+
+#endif /* C2RT_UNIT == 6 / 7 */
 
 #else
 #error "C2RT_UNIT out of range"

@@ -248,6 +248,20 @@ int c2rt_host_render_pixel(c2rt_ctx *ctx, c2rt_host_scene *s, int x, int y, c2rt
     return c2rt_render_pixel(ctx, &cam, &o, x, y, out);
 }
 
+int c2rt_host_render_hits(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_hit_planes *planes)
+{
+    if (!ctx || !s) return C2RT_ERR_INVALID_ARG;
+    // the probe's set-up (c2rt_host_render_pixel) for every pixel at once; a camera with depth of field or
+    // stereo, and null planes, are refused by c2rt_render_hits with the ABI's statuses
+    c2rt_camera_frame cam;
+    c2rt_host_scene_begin_frame(s, &cam);
+    Renderer r{ctx, s, nullptr, nullptr, nullptr};
+    const int st = r.ensureUploaded();
+    if (st != C2RT_OK) return st;
+    const c2rt_render_opts o = opts_of(*s->scene);
+    return c2rt_render_hits(ctx, &cam, &o, planes);
+}
+
 int c2rt_host_bmp_decode(const uint8_t *bytes, size_t len, uint32_t *width, uint32_t *height, float **out_rgb)
 {
     if (!bytes || !width || !height || !out_rgb) return C2RT_ERR_INVALID_ARG;

@@ -448,6 +448,52 @@ int c2rt_test_visibility_device(c2rt_ctx *ctx, const c2rt_segment *seg_dev, uint
                                 uint8_t *visible_dev, void *hip_stream);
 int c2rt_test_visibility(c2rt_ctx *ctx, const c2rt_segment *seg, uint64_t n, uint8_t *visible);
 
+/* ---- hit planes: what every pixel of a camera frame hit -------------------- */
+
+/* One plane per field of the TraceResult (rt/renderer.d:15-21) of the sample at integer (x, y) of every pixel:
+ * what c2rt_render_pixel(x, y) reports, for the whole frame.  Row-major, local_rows x width, no padding.
+ * Every pointer is nullable; at least one must be given.  A plane that is null is neither computed nor stored. */
+typedef struct c2rt_hit_planes {
+    int32_t *node;    /* [rows][W]     closest node, -1: no hit                         */
+    int32_t *leaf;    /* [rows][W]     IntersectionData.g (leaf geometry), -1 without a hit */
+    double  *dist;    /* [rows][W]     1e99 without a hit                               */
+    double  *uv;      /* [rows][W][2]  0 without a hit                                  */
+    double  *p;       /* [rows][W][3]                                                    */
+    double  *normal;  /* [rows][W][3]  the geometric normal as the probe reports it (not face-forwarded) */
+    float   *rgb;     /* [rows][W][3]  raytrace_impl's colour of that sample = the C2RT_TAPS_1 frame */
+} c2rt_hit_planes;
+
+/* Pixel (x, y) is the ray Camera.getScreenRay(x, y) (rt/camera.d:123-147: the pixel's integer corner, no 0.5), built
+ * on the device from `cam` with the frame kernels' own arithmetic, sent through `trace` (rt/renderer.d:325-338) and,
+ * for `rgb`, through raytrace_impl (rt/renderer.d:361-376): the values c2rt_render_pixel reports for a pinhole
+ * camera, and the bits c2rt_trace_rays computes for that ray — without the 48 B per ray going in and without the
+ * 80-byte records coming out for a caller who wants one field.
+ *   - A pixel without a hit holds c2rt_ray_hit's record: node and leaf -1, dist 1e99, uv / p / normal 0; rgb is the
+ *     environment's black (rt/environment.d:7-10).
+ *   - opts: width, height, strip_height, strip_rank and strip_world mean what they mean for frames; with
+ *     strip_world > 1 the planes hold this rank's rows only, compact, c2rt_local_rows(opts) of them.  `taps` must be a
+ *     valid mode and is otherwise ignored (the sample at (x, y) is the first tap of every mode); `seed` is ignored.
+ *   - rgb alone skips nothing of the trace but every record store; no rgb casts no shadow ray.
+ *
+ * Statuses, all decided before anything is enqueued or any plane is written, in this order: those of a frame call
+ * (null camera or options, no scene: C2RT_ERR_NO_SCENE, bad size / tap mode / strip rank); null `planes`, or all seven
+ * pointers null: C2RT_ERR_INVALID_ARG, each with its own message; C2RT_ERR_UNSUPPORTED with the cause named in
+ * c2rt_last_error for cam->dof ("depth of field"), cam->stereo_separation != 0 ("stereo"), opts->count_rays
+ * ("count_rays") and opts->prepass_bucket ("prepass_bucket"): a pixel's record is ONE ray's, and those modes have
+ * many rays per pixel (or none of its own).
+ *
+ * The _device variant takes device pointers and enqueues ONE kernel on `hip_stream` (a hipStream_t, NULL = default
+ * stream) under the rules of c2rt_trace_rays_device: no host sync, no event left in the queue, no per-stream scratch,
+ * no reference kept to the stream; ordered with the frames and queries on the same stream.  On a multi-device context
+ * it runs on the lead device, as c2rt_render_pixel and the queries do. */
+int c2rt_render_hits_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                            const c2rt_hit_planes *planes_dev, void *hip_stream);
+/* The same into HOST memory: staged through the context's staging buffer on the context's own stream in chunks of
+ * whole rows of at most 2^18 pixels (the buffer holds one chunk of the planes actually asked for, at most 92 B per
+ * pixel, whatever the frame size); blocks until the planes are there. */
+int c2rt_render_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                     const c2rt_hit_planes *planes_host);
+
 /* Rank-0 side of the multi-GPU gather: `gathered_dev` holds `world`
  * consecutive compact strip buffers (rank-major, as ncclGather leaves them);
  * writes the de-interleaved full frame to `frame_dev`.  Both device

@@ -97,6 +97,12 @@ int c2rt_host_render_wait(c2rt_host_scene *scene);
 int c2rt_host_render_pixel(c2rt_ctx *ctx, c2rt_host_scene *scene, int x, int y,
                            c2rt_trace_result *out);
 
+/* The hit planes of the scene's own camera at its frame size (c2rt_render_hits: one plane per field of the probe's
+ * record, frame_height x frame_width, host pointers, every one nullable): uploads the scene if needed and calls
+ * beginFrame, as c2rt_host_render_pixel does.  A scene whose camera has depth of field or stereo is refused with
+ * C2RT_ERR_UNSUPPORTED (c2rt_last_error names the cause); the AA setting does not matter (one sample per pixel). */
+int c2rt_host_render_hits(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt_hit_planes *planes);
+
 /* loadBmpImage!Color: malloc'd width*height*3 floats (free with
  * c2rt_host_free); y = 0 is the top row.  No gamma decode. */
 int c2rt_host_bmp_decode(const uint8_t *bytes, size_t len, uint32_t *width, uint32_t *height,

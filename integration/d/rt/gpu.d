@@ -109,6 +109,19 @@ extern (C) nothrow @nogc
     int c2rt_test_visibility_device(c2rt_ctx*, const c2rt_segment* seg_dev, ulong n, ubyte* visible_dev,
                                     void* hip_stream);
     int c2rt_test_visibility(c2rt_ctx*, const c2rt_segment* seg, ulong n, ubyte* visible);
+    /// hit planes: renderPixel's TraceResult for every pixel of a frame in one call, one plane per field, row-major
+    /// local_rows x width; every pointer nullable (a null plane is neither computed nor stored), at least one given;
+    /// no depth of field / stereo / counted / preview frames (C2RT_ERR_UNSUPPORTED)
+    struct c2rt_hit_planes
+    {
+        int* node, leaf;            /// closest node / leaf geometry, -1 without a hit
+        double* dist;               /// 1e99 without a hit
+        double* uv, p, normal;      /// [2], [3], [3] per pixel; 0 without a hit
+        float* rgb;                 /// [3] per pixel: the one-tap frame
+    }
+    int c2rt_render_hits_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*,
+                                const c2rt_hit_planes* planes_dev, void* hip_stream);
+    int c2rt_render_hits(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_hit_planes* planes_host);
 }
 
 /// Owns the flat tables for one uploaded scene (GC memory; c2rt_upload_scene copies them).
