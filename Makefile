@@ -44,6 +44,9 @@ KERNELFLAGS_u5 :=
 KERNELFLAGS_u6 :=
 # unit 7: the hit planes of a camera frame (c2rt_render_hits), every CSG depth; exact:: only, as unit 6
 KERNELFLAGS_u7 :=
+# unit 8: adaptive anti-aliasing (c2rt_render_frame_adaptive): the detection kernel and the refinement kernel of every
+# CSG depth; exact:: only, as units 6 and 7
+KERNELFLAGS_u8 :=
 CXXFLAGS   := -O2 -std=c++17 -fPIC $(FPFLAGS) -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 CSRC       := chess2rt_amd/csrc
 # development knob: `make VARIANT=name EXTRA_HIPFLAGS=... EXTRA_KERNEL_FLAGS=...` builds chess2rt_amd/libc2rt_name.so
@@ -52,7 +55,7 @@ VARIANT    ?=
 BUILD      := build$(if $(VARIANT),_$(VARIANT))
 LIBNAME    := chess2rt_amd/libc2rt$(if $(VARIANT),_$(VARIANT)).so
 
-UNITS      := 0 1 2 3 4 5 6 7
+UNITS      := 0 1 2 3 4 5 6 7 8
 KOBJS      := $(foreach u,$(UNITS),$(BUILD)/c2rt_kernels_u$(u).o)
 HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/scene.o $(BUILD)/host_api.o
 

@@ -24,6 +24,7 @@ MAX_CSG_DEPTH = 4
 MAX_CSG_HITS = 8
 MAX_BATCH_FRAMES = 256
 MAX_RAYS = 1 << 28
+AA_THRESHOLD_REF = 0.1     # C2RT_AA_THRESHOLD_REF (0.1f: passed as a C float)
 
 _i32p = C.POINTER(C.c_int32)
 _u32p = C.POINTER(C.c_uint32)
@@ -217,6 +218,8 @@ C2RT_SYMBOLS = {
     "c2rt_test_visibility": (C.c_int, [_VP, _VP, C.c_uint64, _VP]),
     "c2rt_render_hits_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(HitPlanes), _VP]),
     "c2rt_render_hits": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(HitPlanes)]),
+    "c2rt_render_frame_adaptive_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
+    "c2rt_render_frame_adaptive": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_deinterleave_strips": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
     "c2rt_encode_rgb32": (C.c_int, [_VP, _VP, _VP, C.c_uint64, _VP]),
     "c2rt_render_frame_rgb32": (C.c_int, [_VP, _CAM_P, _OPTS_P, _VP, _VP]),
@@ -243,6 +246,7 @@ C2RT_HOST_SYMBOLS = {
     "c2rt_host_render_wait": (C.c_int, [_VP]),
     "c2rt_host_render_pixel": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.POINTER(TraceResult)]),
     "c2rt_host_render_hits": (C.c_int, [_VP, _VP, C.POINTER(HitPlanes)]),
+    "c2rt_host_render_rt_adaptive": (C.c_int, [_VP, _VP, _VP, _VP]),
     "c2rt_host_bmp_decode": (C.c_int, [_VP, C.c_size_t, _u32p, _u32p, C.POINTER(_f32p)]),
     "c2rt_host_texture_gamma": (None, [_VP, C.c_size_t, C.c_float]),
     "c2rt_host_bmp_encode": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),

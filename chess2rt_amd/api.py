@@ -247,6 +247,24 @@ class Context:
         arr, n = self._camera_array(cams)
         self._check(self._lib.c2rt_render_frames_device(self._h, arr, n, C.byref(opts), C.c_void_p(out_ptr), C.c_void_p(stream)))
 
+    def renderFrameAdaptive(self, cam, opts, threshold=_abi.AA_THRESHOLD_REF, stop_flag=None):
+        """Adaptive anti-aliasing (c2rt_render_frame_adaptive; opts.taps must be TAPS_REF5): (frame, mask) — the
+        (H, W, 3) float32 frame and the (H, W) uint8 flags of the reference's edge test at `threshold`.  A flagged pixel
+        holds the bits of the five-tap frame, an unflagged one the bits of the one-tap frame.  No depth of field, stereo,
+        count_rays, prepass_bucket, strips or multi-device context (C2rtError, ERR_UNSUPPORTED)."""
+        frame = np.empty((opts.height, opts.width, 3), dtype=np.float32)
+        mask = np.empty((opts.height, opts.width), dtype=np.uint8)
+        stop = stop_flag.ctypes.data_as(C.c_void_p) if stop_flag is not None else None
+        self._check(self._lib.c2rt_render_frame_adaptive(self._h, C.byref(cam), C.byref(opts), float(threshold),
+                                                         frame.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p), stop))
+        return frame, mask
+
+    def renderFrameAdaptiveDevice(self, cam, opts, out_ptr, mask_ptr, threshold=_abi.AA_THRESHOLD_REF, stream=0):
+        """Enqueue the adaptive frame on `stream` into device memory: H * W * 3 floats at out_ptr, H * W bytes at
+        mask_ptr (required: it is the buffer between the detection and the refinement kernel)."""
+        self._check(self._lib.c2rt_render_frame_adaptive_device(self._h, C.byref(cam), C.byref(opts), float(threshold),
+                                                                C.c_void_p(out_ptr or None), C.c_void_p(mask_ptr or None), C.c_void_p(stream)))
+
     def rayStats(self):
         s = RayStats()
         self._check(self._lib.c2rt_get_ray_stats(self._h, C.byref(s)))
@@ -362,6 +380,16 @@ class Renderer:
         stop = stop_flag.ctypes.data_as(C.c_void_p) if stop_flag is not None else None
         self.ctx._check(self._lib.c2rt_host_render_rt(self.ctx.handle, self.scene._h, out.ctypes.data_as(C.c_void_p), stop))
         return out
+
+    def renderRTAdaptive(self):
+        """Context.renderFrameAdaptive for the scene's own camera and frame size at the reference's threshold
+        (c2rt_host_render_rt_adaptive): (frame, mask).  A camera with depth of field or stereo is refused."""
+        s = self.scene.settings
+        frame = np.empty((s.frame_height, s.frame_width, 3), dtype=np.float32)
+        mask = np.empty((s.frame_height, s.frame_width), dtype=np.uint8)
+        self.ctx._check(self._lib.c2rt_host_render_rt_adaptive(self.ctx.handle, self.scene._h, frame.ctypes.data_as(C.c_void_p),
+                                                               mask.ctypes.data_as(C.c_void_p)))
+        return frame, mask
 
     def renderSceneAsync(self, out, is_rendering, needs_rendering=None):
         """renderSceneAsync (rt/renderer.d:23-44); `out`, flags: numpy arrays kept alive by the caller."""

@@ -25,6 +25,10 @@ namespace c2rt {
 /* c2rt_kernels.hip, unit 7 (declared here: c2rt_device.h is a prerequisite of every frame-kernel unit).  Rows [row0,
  * row0 + rows) of the frame's local rows into planes whose first row is row0; returns a hipError_t as int. */
 int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream);
+/* c2rt_kernels.hip, unit 8 (adaptive anti-aliasing), declared here for the same reason: the flag image of a whole one-tap
+ * frame, and the flagged pixels of that frame from their one-tap to their five-tap value, in place; hipError_t as int. */
+int launch_aa_detect(const float *frame, uint8_t *needs_aa, uint32_t width, uint32_t height, float threshold, void *stream);
+int launch_aa_refine(const RenderParams &p, int csg_levels, float *frame, const uint8_t *needs_aa, void *stream);
 } // namespace c2rt
 
 using namespace c2rt;
@@ -1303,6 +1307,73 @@ int c2rt_render_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_ren
             if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k] + first * px_bytes[k], base + off[k], px * px_bytes[k], hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
+    return C2RT_OK;
+}
+
+/* ---- adaptive anti-aliasing (kernel unit 8) ----------------------------------------------------------------------- */
+
+/* the refusals of both entry points, in the documented order: a frame call's, then the arguments of this call, then the
+ * modes in which a pixel is not five rays of its own or its neighbours are not in this frame */
+static int check_adaptive_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, float threshold,
+                               const void *out_rgb, bool mask_ok)
+{
+    if (const int st = check_frame_args(ctx, cam, opts)) return st;
+    if (opts->taps != C2RT_TAPS_REF5) return fail(ctx, C2RT_ERR_INVALID_ARG, "adaptive anti-aliasing refines to C2RT_TAPS_REF5: taps is %u", (unsigned)opts->taps);
+    if (!(threshold >= 0.0f)) return fail(ctx, C2RT_ERR_INVALID_ARG, "threshold %g: neither negative nor NaN", (double)threshold);
+    if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    if (!mask_ok) return fail(ctx, C2RT_ERR_INVALID_ARG, "null needs_aa: the device variant keeps the flags in the caller's buffer");
+    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: the flags compare one ray per pixel, a lens has many");
+    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: the flags compare one ray per pixel, a stereo camera has two");
+    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the refinement does not count rays");
+    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
+    if (opts->strip_world > 1) return fail(ctx, C2RT_ERR_UNSUPPORTED, "strip_world > 1: the rows above and below a strip belong to other ranks");
+    if (!ctx->peers.empty()) return fail(ctx, C2RT_ERR_UNSUPPORTED, "multi-device context: the rows above and below a strip are on other devices");
+    return C2RT_OK;
+}
+
+/* The three steps on `stream`, device pointers: the one-tap frame through the frame path as it is (pre-pass, lean / exact
+ * redo, nested-CSG retry, the stream's scratch slot), the flags, the refinement of the flagged pixels in place.  The
+ * caller's mask is the only buffer between detection and refinement: no scratch of this call's own. */
+static int adaptive_enqueue(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, float threshold,
+                            float *out_dev, uint8_t *mask_dev, hipStream_t stream)
+{
+    c2rt_render_opts one = *opts;
+    one.taps = C2RT_TAPS_1;
+    if (const int st = render_device(ctx, cam, &one, out_dev, stream)) return st;
+    int e = launch_aa_detect(out_dev, mask_dev, opts->width, opts->height, threshold, stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "adaptive AA detection kernel launch: %s", hipGetErrorString((hipError_t)e));
+    RenderParams p;
+    hit_params(ctx, cam, &one, p);
+    e = launch_aa_refine(p, ctx->plan.csg_levels, out_dev, mask_dev, stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "adaptive AA refinement kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+int c2rt_render_frame_adaptive_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, float threshold,
+                                      float *out_rgb_dev, uint8_t *needs_aa_dev, void *hip_stream)
+{
+    if (const int st = check_adaptive_args(ctx, cam, opts, threshold, out_rgb_dev, needs_aa_dev != nullptr)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return adaptive_enqueue(ctx, cam, opts, threshold, out_rgb_dev, needs_aa_dev, static_cast<hipStream_t>(hip_stream));
+}
+
+/* Host variant: frame and mask side by side in the context's staging allocation, on the context's stream; one copy
+ * back per output, then a stream sync. */
+int c2rt_render_frame_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, float threshold,
+                               float *out_rgb, uint8_t *needs_aa, const volatile uint8_t *stop_flag)
+{
+    if (const int st = check_adaptive_args(ctx, cam, opts, threshold, out_rgb, true)) return st;
+    /* isStopReq() before the pass — rt/renderer.d:129 */
+    if (stop_flag && *stop_flag) return fail(ctx, C2RT_ERR_CANCELLED, "stop requested before the frame");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)opts->width * opts->height;
+    const size_t off_mask = align256(px * 3 * sizeof(float));
+    if (const int st = ensure_staging(ctx, off_mask + px)) return st;
+    uint8_t *mask_dev = reinterpret_cast<uint8_t *>(ctx->frame) + off_mask;
+    if (const int st = adaptive_enqueue(ctx, cam, opts, threshold, ctx->frame, mask_dev, ctx->stream)) return st;
+    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->frame, px * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (needs_aa) HIP_TRY(ctx, hipMemcpyAsync(needs_aa, mask_dev, px, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return C2RT_OK;
 }
 

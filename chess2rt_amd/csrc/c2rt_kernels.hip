@@ -377,10 +377,11 @@ __global__ void __launch_bounds__(256) tile_masks_batch_kernel(const RenderParam
  * C2RT_UNIT = 0..4 (the frame kernel for that many CSG nesting levels) and
  * once with C2RT_UNIT = 5 (probe, de-interleave, encode, dispatcher), once
  * with C2RT_UNIT = 6 (the ray and visibility queries, c2rt_trace_rays) and once
- * with C2RT_UNIT = 7 (the hit planes of a camera frame, c2rt_render_hits).
+ * with C2RT_UNIT = 7 (the hit planes of a camera frame, c2rt_render_hits) and once
+ * with C2RT_UNIT = 8 (adaptive anti-aliasing, c2rt_render_frame_adaptive).
  */
 #ifndef C2RT_UNIT
-#error "compile with -DC2RT_UNIT=0..7 (see Makefile)"
+#error "compile with -DC2RT_UNIT=0..8 (see Makefile)"
 #endif
 
 #if C2RT_UNIT >= 0 && C2RT_UNIT <= C2RT_MAX_CSG_DEPTH
@@ -538,7 +539,7 @@ int launch_encode_rgb32(const float *frame, uint32_t *out, uint64_t n_pixels, co
     return (int)hipGetLastError();
 }
 
-#elif C2RT_UNIT == 6 || C2RT_UNIT == 7 /* the query units: what they share, then one or the other */
+#elif C2RT_UNIT == 6 || C2RT_UNIT == 7 || C2RT_UNIT == 8 /* the query units: what they share, then one of them */
 
 /*
  * Ray and visibility queries (c2rt_trace_rays*, c2rt_test_visibility*): the caller's rays instead of a camera's.
@@ -751,7 +752,7 @@ int launch_test_visibility(const RenderParams &p, int csg_levels, const c2rt_seg
     }
 }
 
-#else /* C2RT_UNIT == 7 */
+#elif C2RT_UNIT == 7
 
 /*
  * Hit planes (c2rt_render_hits*): the closest-hit record of the ray through the integer corner of every pixel of a
@@ -932,7 +933,206 @@ int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_plan
     }
 }
 
-#endif /* C2RT_UNIT == 6 / 7 */
+#else /* C2RT_UNIT == 8 */
+
+/*
+ * Adaptive anti-aliasing (c2rt_render_frame_adaptive*): Renderer.renderRT's three passes with the third one run where
+ * the second raised its flag, which is what rt/renderer.d:150-188 computes the flag for and then does not do.  The
+ * one-tap frame is the frame kernels' (c2rt_api.cpp calls the frame path with taps = 1); this unit holds the two
+ * kernels behind it on the same stream.
+ *
+ * aa_detect_kernel — rt/renderer.d:154-177 with tooDifferent (rt/color.d:18-23): one lane per pixel over 8x8 tiles,
+ * fifteen floats in (the pixel and its four neighbours, clamped at the frame's edges as the reference clamps them), one
+ * byte out.  fp32 in the reference's order, no fma (the build has contraction off).  Memory-bound: 12 B read and 1 B
+ * written per pixel from HBM, the neighbours come out of the caches.
+ *
+ * aa_refine_kernel — renderPixelAA (rt/renderer.d:233-251) for the flagged pixels: the hit-plane kernel's wave (one
+ * wavefront per workgroup, one 8x8 tile, exact:: arithmetic, every culling mask all ones, full-capacity hit stack, no
+ * ground shortcut) with the work items of the tile PACKED into lanes.  A tile with k flagged pixels has 4k items
+ * (pixel j, tap 1 + i % 4); lane l of round r takes item 64 r + l, so a tile with up to 16 flagged pixels — an edge
+ * crossing it — is ONE round of the trace at 4k / 64 occupancy instead of four rounds at k / 64.  The list of flagged
+ * lanes is built in LDS from the ballot's prefix count; each item leaves its colour in an LDS array [pixel][tap] (3 KiB,
+ * behind the hit stack), and the pixel's own lane then adds the four to out[y][x] in tap order and divides by 5.0f:
+ * render_tile's statements (c2rt_trace.inc), hence the bits of the C2RT_TAPS_REF5 frame.  Lanes without an item are
+ * masked out by control flow before the trace, as the query kernel masks its tail.  All plain vector stores.
+ *
+ * Detection is a launch of its own: it reads the neighbours' ONE-TAP values, and refinement overwrites pixels in
+ * place; the caller's mask is the buffer between the two.  Refinement reads and writes its own pixel and the mask only.
+ *
+ * C2RT_AA_PACKED = 0 builds the plain variant instead: every flagged lane loops over its four taps, the others sit out
+ * (A/B: profiles/adaptive_aa.md).
+ */
+#ifndef C2RT_AA_PACKED
+#define C2RT_AA_PACKED 1
+#endif
+namespace {
+
+static_assert(sizeof(RenderParams) + 64 <= 4096, "the kernel-argument segment holds at most 4 KiB");
+static_assert(kTileW * kTileH == kWave, "one wavefront, one tile");
+constexpr int kAaDetectWaves = 4; /* tiles (wavefronts) per workgroup of the detection kernel */
+
+__global__ void __launch_bounds__(kWave * kAaDetectWaves)
+aa_detect_kernel(const float *__restrict__ frame, uint8_t *__restrict__ needs_aa, const uint32_t width, const uint32_t height,
+                 const uint32_t tiles_x, const uint32_t n_tiles, const float threshold)
+{
+    const uint32_t tile = blockIdx.x * kAaDetectWaves + threadIdx.x / kWave;
+    if (tile >= n_tiles) return;
+    const uint32_t lane = threadIdx.x % kWave;
+    const uint32_t x = (tile % tiles_x) * kTileW + lane % kTileW, y = (tile / tiles_x) * kTileH + lane / kTileW;
+    if (x >= width || y >= height) return;
+    const uint32_t xs[5] = {x, x > 0 ? x - 1 : x, x + 1 < width ? x + 1 : x, x, x};
+    const uint32_t ys[5] = {y, y, y, y > 0 ? y - 1 : y, y + 1 < height ? y + 1 : y};
+    float n[5][3];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const float *q = frame + ((size_t)ys[i] * width + xs[i]) * 3;
+        n[i][0] = q[0];
+        n[i][1] = q[1];
+        n[i][2] = q[2];
+    }
+    bool flag = false;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float average = 0.0f; /* Color average = Color(0, 0, 0); foreach: average += neighs[i] */
+#pragma unroll
+        for (int i = 0; i < 5; ++i) average = average + n[i][c];
+        average = average / 5.0f;
+#pragma unroll
+        for (int i = 0; i < 5; ++i) flag = flag | (fabsf(n[i][c] - average) > threshold); /* a NaN compares false */
+    }
+    needs_aa[(size_t)y * width + x] = flag ? (uint8_t)1 : (uint8_t)0;
+}
+
+constexpr size_t kAaColourBytes = (size_t)kWave * 4 * 3 * sizeof(float), kAaListBytes = kWave;
+
+template <int LEVELS, bool MLC>
+__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, MLC)
+aa_refine_kernel(const RenderParams P, float *__restrict__ frame, const uint8_t *__restrict__ needs_aa, const uint32_t tiles_x)
+{
+    using namespace exact;
+    extern __shared__ __align__(16) char lds[];
+    const int lane = (int)threadIdx.x;
+    const uint32_t x0 = (blockIdx.x % tiles_x) * kTileW, y0 = (blockIdx.x / tiles_x) * kTileH; /* the grid is tiles_x * tiles_y */
+    const uint32_t x = x0 + (uint32_t)(lane % kTileW), y = y0 + (uint32_t)(lane / kTileW);
+    const size_t idx = (size_t)y * P.width + x;
+    const bool flagged = x < P.width && y < P.height && needs_aa[idx] != 0;
+    const unsigned long long flags = __ballot(flagged);
+    if (!flags) return;
+    const size_t stack = (size_t)P.csg_cap * kCsgLdsPerEntry;
+    float *colour = reinterpret_cast<float *>(lds + stack); /* [pixel's lane][tap - 1][3] */
+    Ctx cx;
+    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
+    Rng rng = {0u, 0, 0};
+#if C2RT_AA_PACKED
+    uint8_t *list = reinterpret_cast<uint8_t *>(lds + stack + kAaColourBytes); /* the flagged lanes, ascending */
+    if (flagged) list[__popcll(flags & ((1ull << lane) - 1ull))] = (uint8_t)lane;
+    __builtin_amdgcn_wave_barrier(); /* LDS operations of one wave complete in order; the workgroup is this wave */
+    const int items = 4 * __popcll(flags);
+#pragma unroll 1
+    for (int first = 0; first < items; first += kWave) {
+        const int i = first + lane;
+        if (i < items) {
+            const int pl = (int)list[i >> 2], t = 1 + (i & 3);
+            const uint32_t px = x0 + (uint32_t)(pl % kTileW), py = y0 + (uint32_t)(pl / kTileW);
+            D3 o, raw;
+            screen_ray<false>(cx.bad, P, (double)px + k_aa_x[t], (double)py + k_aa_y[t], 0, rng, o, raw);
+            const D3 d = normalized(cx.bad, raw); /* raytrace(): rt/camera.d:144-147 */
+            Hit best;
+            Surf surf;
+            Mat mat;
+            const int closest = trace_closest<LEVELS>(cx, o, d, false, best, surf, mat);
+            F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
+            uint32_t shadow_rays = 0;
+            if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
+            float *slot = colour + (pl * 4 + (t - 1)) * 3;
+            slot[0] = c.r;
+            slot[1] = c.g;
+            slot[2] = c.b;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+#else
+    if (flagged) {
+#pragma unroll 1
+        for (int t = 1; t <= 4; ++t) {
+            D3 o, raw;
+            screen_ray<false>(cx.bad, P, (double)x + k_aa_x[t], (double)y + k_aa_y[t], 0, rng, o, raw);
+            const D3 d = normalized(cx.bad, raw);
+            Hit best;
+            Surf surf;
+            Mat mat;
+            const int closest = trace_closest<LEVELS>(cx, o, d, false, best, surf, mat);
+            F3 c = mkf(0, 0, 0);
+            uint32_t shadow_rays = 0;
+            if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
+            float *slot = colour + (lane * 4 + (t - 1)) * 3;
+            slot[0] = c.r;
+            slot[1] = c.g;
+            slot[2] = c.b;
+        }
+    }
+#endif
+    if (flagged) {
+        /* renderPixelAA: accum = the pixel's one-tap colour, += the four samples in tap order, / 5 — Color / float */
+        typedef float __attribute__((ext_vector_type(3), aligned(4))) f3_t;
+        f3_t *out = reinterpret_cast<f3_t *>(frame + idx * 3);
+        const f3_t v0 = *out;
+        F3 accum = mkf(v0.x, v0.y, v0.z);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float *slot = colour + (lane * 4 + t) * 3;
+            accum = accum + mkf(slot[0], slot[1], slot[2]);
+        }
+        accum = accum / 5.0f;
+        f3_t v3;
+        v3.x = accum.r;
+        v3.y = accum.g;
+        v3.z = accum.b;
+        *out = v3;
+    }
+}
+
+template <int LEVELS>
+int launch_aa_refine_level(const RenderParams &p, float *frame, const uint8_t *needs_aa, hipStream_t s)
+{
+    const uint32_t tiles_x = (p.width + kTileW - 1) / kTileW, tiles_y = (p.height + kTileH - 1) / kTileH;
+    const dim3 grid(tiles_x * tiles_y), block(kWave); /* at most 2^16 x 2^16 pixels / 64 */
+    const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry + kAaColourBytes + kAaListBytes;
+    if (p.n_lights > 1) hipLaunchKernelGGL((aa_refine_kernel<LEVELS, true>), grid, block, lds, s, p, frame, needs_aa, tiles_x);
+    else hipLaunchKernelGGL((aa_refine_kernel<LEVELS, false>), grid, block, lds, s, p, frame, needs_aa, tiles_x);
+    return (int)hipGetLastError();
+}
+
+} // namespace
+
+/* needs_aa[y][x] of the whole width x height frame at `frame` (device pointers).  Declared in c2rt_api.cpp, as
+ * launch_hit_planes is. */
+int launch_aa_detect(const float *frame, uint8_t *needs_aa, uint32_t width, uint32_t height, float threshold, void *stream)
+{
+    if (!width || !height || !frame || !needs_aa) return (int)hipErrorInvalidValue;
+    const uint32_t tiles_x = (width + kTileW - 1) / kTileW, n_tiles = tiles_x * ((height + kTileH - 1) / kTileH);
+    hipLaunchKernelGGL(aa_detect_kernel, dim3((n_tiles + kAaDetectWaves - 1) / kAaDetectWaves), dim3(kWave * kAaDetectWaves), 0,
+                       static_cast<hipStream_t>(stream), frame, needs_aa, width, height, tiles_x, n_tiles, threshold);
+    return (int)hipGetLastError();
+}
+
+/* The flagged pixels of the whole frame `p` describes (hit_params' settings: exact::, csg_cap = kCsgFullCap(csg_levels),
+ * no culling, no ground node; no strips) from their one-tap to their five-tap value, in place. */
+int launch_aa_refine(const RenderParams &p, int csg_levels, float *frame, const uint8_t *needs_aa, void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!p.width || !p.height || !frame || !needs_aa) return (int)hipErrorInvalidValue;
+    switch (csg_levels) {
+    case 0: return launch_aa_refine_level<0>(p, frame, needs_aa, s);
+    case 1: return launch_aa_refine_level<1>(p, frame, needs_aa, s);
+    case 2: return launch_aa_refine_level<2>(p, frame, needs_aa, s);
+    case 3: return launch_aa_refine_level<3>(p, frame, needs_aa, s);
+    case 4: return launch_aa_refine_level<4>(p, frame, needs_aa, s);
+    default: return (int)hipErrorInvalidValue;
+    }
+}
+
+#endif /* C2RT_UNIT == 6 / 7 / 8 */
 
 #else
 #error "C2RT_UNIT out of range"

@@ -262,6 +262,20 @@ int c2rt_host_render_hits(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_hit_plan
     return c2rt_render_hits(ctx, &cam, &o, planes);
 }
 
+int c2rt_host_render_rt_adaptive(c2rt_ctx *ctx, c2rt_host_scene *s, float *out_rgb, uint8_t *needs_aa)
+{
+    if (!ctx || !s || !out_rgb) return C2RT_ERR_INVALID_ARG;
+    // renderRT's passes 2, 3a and 3b (rt/renderer.d:132-188) with 3b on the flagged pixels only
+    c2rt_camera_frame cam;
+    c2rt_host_scene_begin_frame(s, &cam);
+    Renderer r{ctx, s, nullptr, nullptr, nullptr};
+    const int st = r.ensureUploaded();
+    if (st != C2RT_OK) return st;
+    c2rt_render_opts o = opts_of(*s->scene);
+    o.taps = C2RT_TAPS_REF5;
+    return c2rt_render_frame_adaptive(ctx, &cam, &o, C2RT_AA_THRESHOLD_REF, out_rgb, needs_aa, nullptr);
+}
+
 int c2rt_host_bmp_decode(const uint8_t *bytes, size_t len, uint32_t *width, uint32_t *height, float **out_rgb)
 {
     if (!bytes || !width || !height || !out_rgb) return C2RT_ERR_INVALID_ARG;

@@ -494,6 +494,46 @@ int c2rt_render_hits_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c
 int c2rt_render_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
                      const c2rt_hit_planes *planes_host);
 
+/* ---- adaptive anti-aliasing: refine only the pixels the edge test flags ----- */
+
+/* tooDifferent's default threshold — rt/color.d:18 */
+#define C2RT_AA_THRESHOLD_REF 0.1f
+
+/* Renderer.renderRT's three passes (rt/renderer.d:132-188) with the third run where the second raised its flag.  The
+ * reference computes needsAA[x, y] and then refines every pixel; the flag is dead there, so no reference output pins
+ * it, and what is specified here is the reference's statements read as written.  For a pinhole, mono camera, the
+ * whole frame and opts->taps == C2RT_TAPS_REF5:
+ *   1. out[y][x] is the C2RT_TAPS_1 frame: the bits c2rt_render_frame_device writes for `cam` with taps = 1.
+ *   2. Detection (rt/renderer.d:154-177, tooDifferent rt/color.d:18-23).  neighs = { out[x, y], out[x > 0 ? x - 1 : x, y],
+ *      out[x + 1 < W ? x + 1 : x, y], out[x, y > 0 ? y - 1 : y], out[x, y + 1 < H ? y + 1 : y] }; per channel, in fp32,
+ *      average = ((((0 + n0) + n1) + n2) + n3) + n4, then / 5.0f; needs_aa[y][x] = 1 when for some i and channel
+ *      fabsf(neighs[i].c - average.c) > threshold (the difference rounded to fp32; a NaN difference does not flag),
+ *      else 0.  All five neighbours are values of step 1.
+ *   3. Refinement (renderPixelAA, rt/renderer.d:233-251) of the flagged pixels only: accum = out[y][x]; accum +=
+ *      sample(x + dx[s], y + dy[s]) for s = 1..4 in that order; out[y][x] = accum / 5.0f.
+ * So a flagged pixel holds the bits of the C2RT_TAPS_REF5 frame and an unflagged pixel the bits of the C2RT_TAPS_1
+ * frame.  needs_aa is W * H bytes, row-major, every byte written 0 or 1.
+ *
+ * Statuses, all decided before anything is enqueued or written, in this order: those of a frame call (null camera or
+ * options, no scene: C2RT_ERR_NO_SCENE, bad size / tap mode / strip rank); C2RT_ERR_INVALID_ARG for taps !=
+ * C2RT_TAPS_REF5, a threshold that is negative or NaN, a null output (needs_aa_dev included); C2RT_ERR_UNSUPPORTED with
+ * the cause named in c2rt_last_error for cam->dof ("depth of field"), cam->stereo_separation != 0 ("stereo"),
+ * opts->count_rays ("count_rays"), opts->prepass_bucket ("prepass_bucket"), opts->strip_world > 1 ("strip_world": the
+ * neighbour rows belong to other ranks) and a context of c2rt_init_multi ("multi-device").
+ *
+ * The _device variant takes device pointers and enqueues, in order, on `hip_stream` (a hipStream_t, NULL = default
+ * stream): the one-tap frame exactly as c2rt_render_frame_device does (tile-mask pre-pass, nested-CSG retry and the
+ * stream's scratch slot included), the detection kernel and the refinement kernel.  No host sync, no event left in the
+ * queue, no reference kept to the stream, and no scratch beyond the frame call's: the caller's needs_aa_dev is the
+ * buffer between detection and refinement, which is why it is required here. */
+int c2rt_render_frame_adaptive_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                                      float threshold, float *out_rgb_dev, uint8_t *needs_aa_dev, void *hip_stream);
+/* The same into HOST memory: frame and flags are staged in the context's staging buffer on the context's own stream and
+ * copied back once each (`needs_aa` is nullable here); blocks until they are there.  `stop_flag` is polled once, before
+ * the launches; C2RT_ERR_CANCELLED leaves the outputs untouched. */
+int c2rt_render_frame_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                               float threshold, float *out_rgb, uint8_t *needs_aa, const volatile uint8_t *stop_flag);
+
 /* Rank-0 side of the multi-GPU gather: `gathered_dev` holds `world`
  * consecutive compact strip buffers (rank-major, as ncclGather leaves them);
  * writes the de-interleaved full frame to `frame_dev`.  Both device

@@ -103,6 +103,12 @@ int c2rt_host_render_pixel(c2rt_ctx *ctx, c2rt_host_scene *scene, int x, int y,
  * C2RT_ERR_UNSUPPORTED (c2rt_last_error names the cause); the AA setting does not matter (one sample per pixel). */
 int c2rt_host_render_hits(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt_hit_planes *planes);
 
+/* Renderer.renderRT with adaptive anti-aliasing (c2rt_render_frame_adaptive) for the scene's own camera at its frame
+ * size, with the reference's threshold (C2RT_AA_THRESHOLD_REF) and C2RT_TAPS_REF5 whatever the AA setting: uploads the
+ * scene if needed and calls beginFrame.  `out_rgb`: frameWidth * frameHeight * 3 floats; `needs_aa` (nullable):
+ * frameWidth * frameHeight bytes.  Depth of field and stereo are refused with C2RT_ERR_UNSUPPORTED. */
+int c2rt_host_render_rt_adaptive(c2rt_ctx *ctx, c2rt_host_scene *scene, float *out_rgb, uint8_t *needs_aa);
+
 /* loadBmpImage!Color: malloc'd width*height*3 floats (free with
  * c2rt_host_free); y = 0 is the top row.  No gamma decode. */
 int c2rt_host_bmp_decode(const uint8_t *bytes, size_t len, uint32_t *width, uint32_t *height,

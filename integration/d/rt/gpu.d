@@ -122,6 +122,11 @@ extern (C) nothrow @nogc
     int c2rt_render_hits_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*,
                                 const c2rt_hit_planes* planes_dev, void* hip_stream);
     int c2rt_render_hits(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_hit_planes* planes_host);
+    enum float C2RT_AA_THRESHOLD_REF = 0.1f; /// tooDifferent's default
+    int c2rt_render_frame_adaptive_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
+                                          float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
+    int c2rt_render_frame_adaptive(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
+                                   float* out_rgb, ubyte* needs_aa, const(ubyte)* stop_flag);
 }
 
 /// Owns the flat tables for one uploaded scene (GC memory; c2rt_upload_scene copies them).
