@@ -39,14 +39,11 @@ KERNELFLAGS_u2 := -mllvm -enable-pre=false -mllvm -bonus-inst-threshold=4 -mllvm
 KERNELFLAGS_u3 := -mllvm -enable-pre=false -mllvm -bonus-inst-threshold=4
 KERNELFLAGS_u4 := -mllvm -enable-pre=false -mllvm -bonus-inst-threshold=4 -mllvm -amdgpu-sched-strategy=max-memory-clause
 KERNELFLAGS_u5 :=
-# unit 6: the ray / visibility query kernels, every CSG depth in one unit (exact:: only: a fraction of a frame unit's
-# code); the flags of the frame units were tuned on the frame kernels and have not been measured here
-KERNELFLAGS_u6 :=
-# unit 7: the hit planes of a camera frame (c2rt_render_hits), every CSG depth; exact:: only, as unit 6
-KERNELFLAGS_u7 :=
-# unit 8: adaptive anti-aliasing (c2rt_render_frame_adaptive): the detection kernel and the refinement kernel of every
-# CSG depth; exact:: only, as units 6 and 7
-KERNELFLAGS_u8 :=
+# the query kernels, one object per file, every CSG depth in it (exact:: only: a fraction of a frame unit's code) —
+# c2rt_rays (ray / visibility queries, c2rt_trace_rays), c2rt_hit_planes (the hit planes of a camera frame,
+# c2rt_render_hits), c2rt_adaptive (adaptive anti-aliasing, c2rt_render_frame_adaptive: detection and refinement); the
+# flags of the frame units were tuned on the frame kernels and have not been measured here
+KERNELFLAGS_QUERY :=
 CXXFLAGS   := -O2 -std=c++17 -fPIC $(FPFLAGS) -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 CSRC       := chess2rt_amd/csrc
 # development knob: `make VARIANT=name EXTRA_HIPFLAGS=... EXTRA_KERNEL_FLAGS=...` builds chess2rt_amd/libc2rt_name.so
@@ -55,8 +52,9 @@ VARIANT    ?=
 BUILD      := build$(if $(VARIANT),_$(VARIANT))
 LIBNAME    := chess2rt_amd/libc2rt$(if $(VARIANT),_$(VARIANT)).so
 
-UNITS      := 0 1 2 3 4 5 6 7 8
-KOBJS      := $(foreach u,$(UNITS),$(BUILD)/c2rt_kernels_u$(u).o)
+UNITS      := 0 1 2 3 4 5
+QUERIES    := c2rt_rays c2rt_hit_planes c2rt_adaptive
+KOBJS      := $(foreach u,$(UNITS),$(BUILD)/c2rt_kernels_u$(u).o) $(foreach q,$(QUERIES),$(BUILD)/$(q).o)
 HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/scene.o $(BUILD)/host_api.o
 
 # diagnostics build of the same library: c2rt_api.cpp with the environment hooks compiled in (-DC2RT_DIAG=1), linked
@@ -69,10 +67,14 @@ $(BUILD):
 	mkdir -p $(BUILD)
 
 # (the Makefile is a prerequisite: the arithmetic and code-generation flags are part of what a kernel object is)
-$(BUILD)/c2rt_kernels_u%.o: $(CSRC)/c2rt_kernels.hip $(CSRC)/c2rt_trace.inc $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/x87.h $(CSRC)/fp64_lean.h include/c2rt.h Makefile | $(BUILD)
+TRACE_DEPS := $(CSRC)/c2rt_trace_common.inc $(CSRC)/c2rt_trace.inc $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/x87.h $(CSRC)/fp64_lean.h include/c2rt.h Makefile
+$(BUILD)/c2rt_kernels_u%.o: $(CSRC)/c2rt_kernels.hip $(TRACE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_u$*) $(EXTRA_KERNEL_FLAGS) -DC2RT_UNIT=$* -c $< -o $@
 
-$(BUILD)/c2rt_api.o: $(CSRC)/c2rt_api.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
+$(foreach q,$(QUERIES),$(BUILD)/$(q).o): $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/c2rt_query.inc $(CSRC)/c2rt_query.h $(TRACE_DEPS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_QUERY) $(EXTRA_KERNEL_FLAGS) -c $< -o $@
+
+$(BUILD)/c2rt_api.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -c $< -o $@
 
 # the HIP-free planner (scene validation and packing, per-frame culling decisions)
@@ -85,7 +87,7 @@ $(BUILD)/%.o: $(CSRC)/host/%.cpp $(CSRC)/host/scene.hpp $(CSRC)/host/dsc.hpp inc
 $(LIBNAME): $(KOBJS) $(HOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
-$(BUILD)/c2rt_api_diag.o: $(CSRC)/c2rt_api.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
+$(BUILD)/c2rt_api_diag.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -DC2RT_DIAG=1 -c $< -o $@
 
 $(DIAGNAME): $(KOBJS) $(BUILD)/c2rt_api_diag.o $(filter-out $(BUILD)/c2rt_api.o,$(HOBJS))
@@ -121,6 +123,8 @@ oracle/libc2rt_oracle_count.so: oracle/c2rt_oracle.c oracle/c2rt_oracle.h includ
 resource-usage: | $(BUILD)
 	@$(foreach u,$(UNITS),$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_u$(u)) $(EXTRA_KERNEL_FLAGS) -DC2RT_UNIT=$(u) -Rpass-analysis=kernel-resource-usage \
 	    -c $(CSRC)/c2rt_kernels.hip -o $(BUILD)/ru_u$(u).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
+	@$(foreach q,$(QUERIES),$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_QUERY) $(EXTRA_KERNEL_FLAGS) -Rpass-analysis=kernel-resource-usage \
+	    -c $(CSRC)/$(q).hip -o $(BUILD)/ru_$(q).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
 
 clean:
 	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so

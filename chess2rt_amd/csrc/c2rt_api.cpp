@@ -19,17 +19,8 @@
 #include <utility>
 #include <vector>
 
+#include "c2rt_query.h"
 #include "scene_plan.h"
-
-namespace c2rt {
-/* c2rt_kernels.hip, unit 7 (declared here: c2rt_device.h is a prerequisite of every frame-kernel unit).  Rows [row0,
- * row0 + rows) of the frame's local rows into planes whose first row is row0; returns a hipError_t as int. */
-int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream);
-/* c2rt_kernels.hip, unit 8 (adaptive anti-aliasing), declared here for the same reason: the flag image of a whole one-tap
- * frame, and the flagged pixels of that frame from their one-tap to their five-tap value, in place; hipError_t as int. */
-int launch_aa_detect(const float *frame, uint8_t *needs_aa, uint32_t width, uint32_t height, float threshold, void *stream);
-int launch_aa_refine(const RenderParams &p, int csg_levels, float *frame, const uint8_t *needs_aa, void *stream);
-} // namespace c2rt
 
 using namespace c2rt;
 
@@ -1098,7 +1089,7 @@ int c2rt_render_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_re
     return C2RT_OK;
 }
 
-/* ---- ray queries (kernel unit 6) ----------------------------------------------------------------------------- */
+/* ---- ray queries (c2rt_rays.hip) ------------------------------------------------------------------------------ */
 
 /* What the query kernels read of a parameter block: the scene's tables and constants, the full-capacity hit stack
  * (it cannot overflow: one launch, no retry list) and nothing of a frame — no camera, no culling rectangles
@@ -1215,7 +1206,7 @@ int c2rt_test_visibility(c2rt_ctx *ctx, const c2rt_segment *seg, uint64_t n, uin
     return C2RT_OK;
 }
 
-/* ---- hit planes of a camera frame (kernel unit 7) ---------------------------------------------------------------- */
+/* ---- hit planes of a camera frame (c2rt_hit_planes.hip) ---------------------------------------------------------- */
 
 static bool any_plane(const c2rt_hit_planes *pl) { return pl->node || pl->leaf || pl->dist || pl->uv || pl->p || pl->normal || pl->rgb; }
 
@@ -1310,7 +1301,7 @@ int c2rt_render_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_ren
     return C2RT_OK;
 }
 
-/* ---- adaptive anti-aliasing (kernel unit 8) ----------------------------------------------------------------------- */
+/* ---- adaptive anti-aliasing (c2rt_adaptive.hip) ------------------------------------------------------------------- */
 
 /* the refusals of both entry points, in the documented order: a frame call's, then the arguments of this call, then the
  * modes in which a pixel is not five rays of its own or its neighbours are not in this frame */

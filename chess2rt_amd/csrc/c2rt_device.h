@@ -256,7 +256,7 @@ struct KernelVariant {
     bool dof_or_stereo;
 };
 
-/* implemented in c2rt_kernels.hip; return hipError_t as int */
+/* implemented in c2rt_kernels.hip; return hipError_t as int (the query kernels' launchers: c2rt_query.h) */
 template <int LEVELS>
 int launch_render_level(const RenderParams &p, bool dof_or_stereo, void *stream);
 template <> int launch_render_level<0>(const RenderParams &, bool, void *);
@@ -286,11 +286,6 @@ int launch_tile_masks_batch(const RenderParams &p0, const RenderParams *table_de
  * the pre-pass that fills them (vc: the frame's CsgDiff void tests, csg_void.h) */
 size_t tile_mask_entries(const RenderParams &p);
 int launch_tile_masks(const RenderParams &p, const VoidCull &vc, const SphereCull &sc, uint32_t *table, void *stream);
-/* Ray and visibility queries (c2rt_trace_rays*, c2rt_test_visibility*; kernel unit 6): `p` carries the scene tables
- * and csg_cap = kCsgFullCap(csg_levels) — no camera, no culling, no scratch; device pointers; 0 < n <= C2RT_MAX_RAYS;
- * hits / rgb nullable, not both */
-int launch_trace_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb, void *stream);
-int launch_test_visibility(const RenderParams &p, int csg_levels, const c2rt_segment *seg, uint64_t n, uint8_t *visible, void *stream);
 int launch_deinterleave(const float *gathered, float *frame, uint32_t width, uint32_t height,
                         uint32_t strip_height, uint32_t world, uint32_t rows_pad, uint32_t words_per_pixel, void *stream);
 int launch_encode_rgb32(const float *frame, uint32_t *out, uint64_t n_pixels,

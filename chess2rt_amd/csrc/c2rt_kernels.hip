@@ -20,97 +20,20 @@
  *     (built with -ffp-contract=off), because checker edges, shadow
  *     terminators and CSG boundaries flip on 1-ulp differences.
  *
- * This file holds the kernel entry points and launchers.  The trace itself is
- * c2rt_trace.inc, included twice below: lean:: (divide / sqrt / normalise through
+ * This file holds the entry points and launchers of the FRAME kernels, the pixel probe, the tile-mask pre-pass,
+ * de-interleave and encode; the query kernels (caller's rays, hit planes, adaptive anti-aliasing) have files of their
+ * own: c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_adaptive.hip.  The trace itself is
+ * c2rt_trace.inc, included twice by c2rt_trace_common.inc: lean:: (divide / sqrt / normalise through
  * the shortened correctly rounded sequences of fp64_lean.h, optimistically) and
  * exact:: (the compiler's IEEE expansions); render_one() runs a tile through
  * lean:: and again through exact:: when an operand left the lean windows.
  *
  * What each function restates is cited as file:line of /root/reference/source.
  */
-#include <hip/hip_runtime.h>
-
-#include "c2rt_device.h"
-#include "fp64_lean.h"
-#include "x87.h"
+#include "c2rt_trace_common.inc"
 
 namespace c2rt {
 namespace {
-
-#define DEV __device__ __forceinline__
-
-/* fp64 libm is only reached by a few lanes (sphere u,v, the Phong lobe,
- * Procedure2) but, inlined, its ~70 live registers set the whole kernel's
- * budget; as real calls the trace stays under 168 VGPRs without spills. */
-__device__ __noinline__ double c2_pow(double a, double b) { return pow(a, b); }
-__device__ __noinline__ double c2_atan2(double a, double b) { return atan2(a, b); }
-__device__ __noinline__ double c2_asin(double a) { return asin(a); }
-__device__ __noinline__ double c2_sin(double a) { return sin(a); }
-__device__ __noinline__ double c2_cos(double a) { return cos(a); }
-/* Sphere.intersect's u,v (rt/geometry.d:118-120) out of line as well: the x87 emulation (x87.h) is ~500 integer
- * instructions with ~40 live registers, reached by textured sphere hits only; inlined (twice: lean:: and exact::)
- * it was where the headline instance spilled. */
-struct UV { double u, v; };
-__device__ __noinline__ UV c2_sphere_uv(double dx, double dz, double w)
-{
-    constexpr double PI = 3.14159265358979323846;
-    const double angle = atan2(dz, dx);
-    const double as = asin(w);
-    UV r;
-    r.u = fabs(angle) <= 4.0 ? x87_sphere_u(angle) : (PI + angle) / (2 * PI);
-    r.v = fabs(as) <= 2.0 ? x87_sphere_v(as) : 1.0 - (PI / 2 + as) / PI;
-    return r;
-}
-/* Register budget per kernel instance, as waves per SIMD (512 VGPRs per lane and SIMD: 128 at 4 waves,
- * 168 at 3, 256 at 2).  With no hint hipcc takes all 512 registers and runs one wave per SIMD (1.8x
- * slower).  Chosen per instance from the compiler's resource remarks (`make resource-usage`; profiles/r04_resource_usage.md)
- * so that NO instance spills VGPRs to scratch, except where a measurement says otherwise:
- *   depth 0 (no CSG), planes-only: 4 waves (111-127 VGPRs);
- *   depth 1, at most one light: 4 waves — 128 VGPRs since the cube / sphere face tables moved to the upload
- *     and the hit's lighting terms are evaluated before the shadow test (was 149 at 3 waves);
- *   depth 1, several lights (the hit stays live across the light loop) and depth-1 DOF: 3 waves (144-162);
- *   depth 2 / 3 / 4: THREE waves (168 VGPRs) although they then spill (depth 4 multi-light: 136 VGPRs, 240 B of
- *     scratch per lane; at two waves it needs 230 and spills none): a wave of these instances issues one
- *     instruction at a time and a third of its instructions are scalar, so with two waves per SIMD the VALU idles
- *     half the time (VALU busy 0.53) — the third wave is worth more than the spills cost: csg_stress.sdl cut to
- *     depth 2 / 3 / 4: 2.33 -> 1.88, 4.60 -> 3.97, 10.21 -> 8.53 ms (scripts/depth_occupancy.sh; four waves:
- *     2.59 / 5.48 / 10.5).  The hit stacks have to fit three workgroups per CU too: kCsgFirstCap, c2rt_device.h. */
-#ifndef C2RT_OCC_U1
-#define C2RT_OCC_U1 4
-#endif
-#ifndef C2RT_OCC_DEEP
-#define C2RT_OCC_DEEP 3
-#endif
-#ifndef C2RT_OCC_U2
-#define C2RT_OCC_U2 3
-#endif
-#ifndef C2RT_OCC_U3
-#define C2RT_OCC_U3 C2RT_OCC_DEEP
-#endif
-template <int LEVELS, int DOF, bool MLC>
-constexpr int occ_of()
-{
-#ifndef C2RT_OCC_U0
-#define C2RT_OCC_U0 4
-#endif
-    return LEVELS == 0 ? (DOF ? 4 : C2RT_OCC_U0) : (LEVELS == 1 ? ((DOF || MLC) ? 3 : C2RT_OCC_U1) : (LEVELS == 2 ? C2RT_OCC_U2 : (LEVELS == 3 ? C2RT_OCC_U3 : C2RT_OCC_DEEP)));
-}
-#define C2RT_OCC_OF(L, D, M) __attribute__((amdgpu_waves_per_eu(occ_of<L, D, M>(), occ_of<L, D, M>())))
-#ifndef C2RT_TILE_STATS
-#define C2RT_TILE_STATS 0 /* diagnostics: per-tile wave cycles + class (RenderParams::tile_stats) */
-#endif
-#ifndef C2RT_XCD_SWIZZLE
-#define C2RT_XCD_SWIZZLE 1
-#endif
-
-namespace lean {
-constexpr bool kLean = true;
-#include "c2rt_trace.inc"
-} // namespace lean
-namespace exact {
-constexpr bool kLean = false;
-#include "c2rt_trace.inc"
-} // namespace exact
 
 #ifndef C2RT_LEAN
 #define C2RT_LEAN 1 /* 0: the production instances run exact:: only (A/B builds) */
@@ -121,7 +44,6 @@ constexpr bool kLean = false;
 #ifndef C2RT_LEAN_MAX_LEVELS
 #define C2RT_LEAN_MAX_LEVELS 3
 #endif
-typedef const RenderParams __attribute__((address_space(4))) *KArgs;
 
 /* One tile: optimistically through lean::, and again through exact:: — by the same wave, with all of its
  * lanes — if a lane reported an operand outside a lean window (c2rt_trace.inc).  The instances launched when
@@ -261,26 +183,7 @@ __global__ void __launch_bounds__(kWave) probe_kernel(const RenderParams P)
     extern __shared__ __align__(16) char lds[];
     if (threadIdx.x != 0) return;
     Ctx cx;
-    cx.geoms = (GeomP)P.geoms;
-    cx.nodes = (NodeP)P.nodes;
-    cx.n_nodes = P.n_nodes;
-    cx.kargs = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
-    cx.lds = lds;
-    cx.lane = 0;
-    cx.csg_cap = (int)P.csg_cap;
-    cx.overflow = false;
-    oob_init(cx.bad);
-    cx.trunc_counter = nullptr;
-#if C2RT_TILE_STATS
-    cx.lane_stats = nullptr;
-#endif
-    cx.block = 0;
-    cx.mask_slot = 0;
-    cx.primary_mask = 0xFFFFFFFFu;
-    cx.shadow_mask0 = 0xFFFFFFFFu;
-    cx.shadow_ground_only = false;
-    cx.primary_ground_only = false;
-    cx.ground_y = 0;
+    query_ctx(cx, P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, 0);
     Counters cnt = {0, 0};
     const uint64_t pixel = (uint64_t)P.probe_y * P.width + (uint64_t)P.probe_x;
     const F3 c = render_sample<LEVELS, DOF, true, false>(P, cx, (double)P.probe_x, (double)P.probe_y, 1, 1, pixel, 0, cnt, P.probe_out); /* MLC: any number of lights (n_cull = 0: no masks) */
@@ -375,13 +278,10 @@ __global__ void __launch_bounds__(256) tile_masks_batch_kernel(const RenderParam
  * Instantiation is split over translation units so that the (slow) device
  * compiles run in parallel: the Makefile builds this file once per
  * C2RT_UNIT = 0..4 (the frame kernel for that many CSG nesting levels) and
- * once with C2RT_UNIT = 5 (probe, de-interleave, encode, dispatcher), once
- * with C2RT_UNIT = 6 (the ray and visibility queries, c2rt_trace_rays) and once
- * with C2RT_UNIT = 7 (the hit planes of a camera frame, c2rt_render_hits) and once
- * with C2RT_UNIT = 8 (adaptive anti-aliasing, c2rt_render_frame_adaptive).
+ * once with C2RT_UNIT = 5 (probe, mask pre-pass, de-interleave, encode, dispatchers).
  */
 #ifndef C2RT_UNIT
-#error "compile with -DC2RT_UNIT=0..8 (see Makefile)"
+#error "compile with -DC2RT_UNIT=0..5 (see Makefile)"
 #endif
 
 #if C2RT_UNIT >= 0 && C2RT_UNIT <= C2RT_MAX_CSG_DEPTH
@@ -464,14 +364,7 @@ int launch_render_batch_level<C2RT_UNIT>(const RenderParams &p0, const RenderPar
 int launch_render_batch(const RenderParams &p0, const KernelVariant &v, const RenderParams *table_dev, uint32_t n_frames, void *stream)
 {
     if (v.dof_or_stereo || p0.ray_counters || !n_frames || n_frames > 65535u) return (int)hipErrorInvalidValue;
-    switch (v.csg_levels) {
-    case 0: return launch_render_batch_level<0>(p0, table_dev, n_frames, stream);
-    case 1: return launch_render_batch_level<1>(p0, table_dev, n_frames, stream);
-    case 2: return launch_render_batch_level<2>(p0, table_dev, n_frames, stream);
-    case 3: return launch_render_batch_level<3>(p0, table_dev, n_frames, stream);
-    case 4: return launch_render_batch_level<4>(p0, table_dev, n_frames, stream);
-    default: return (int)hipErrorInvalidValue;
-    }
+    return for_csg_levels(v.csg_levels, [&](auto L) { return launch_render_batch_level<decltype(L)::value>(p0, table_dev, n_frames, stream); });
 }
 
 int launch_tile_masks_batch(const RenderParams &p0, const RenderParams *table_dev, const BatchCull *culls_dev, uint32_t n_frames, void *stream)
@@ -485,14 +378,7 @@ int launch_tile_masks_batch(const RenderParams &p0, const RenderParams *table_de
 
 int launch_render(const RenderParams &p, const KernelVariant &v, void *stream)
 {
-    switch (v.csg_levels) {
-    case 0: return launch_render_level<0>(p, v.dof_or_stereo, stream);
-    case 1: return launch_render_level<1>(p, v.dof_or_stereo, stream);
-    case 2: return launch_render_level<2>(p, v.dof_or_stereo, stream);
-    case 3: return launch_render_level<3>(p, v.dof_or_stereo, stream);
-    case 4: return launch_render_level<4>(p, v.dof_or_stereo, stream);
-    default: return (int)hipErrorInvalidValue;
-    }
+    return for_csg_levels(v.csg_levels, [&](auto L) { return launch_render_level<decltype(L)::value>(p, v.dof_or_stereo, stream); });
 }
 
 size_t tile_mask_entries(const RenderParams &p)
@@ -539,600 +425,6 @@ int launch_encode_rgb32(const float *frame, uint32_t *out, uint64_t n_pixels, co
     return (int)hipGetLastError();
 }
 
-#elif C2RT_UNIT == 6 || C2RT_UNIT == 7 || C2RT_UNIT == 8 /* the query units: what they share, then one of them */
-
-/*
- * Ray and visibility queries (c2rt_trace_rays*, c2rt_test_visibility*): the caller's rays instead of a camera's.
- * One ray per lane, 64 consecutive rays per wavefront, one wavefront per workgroup — the frame kernels' shape with
- * the tile replaced by a run of the caller's array, so the trace below it is the same wave-synchronous code: scalar
- * node loop, scalar record loads, one surface pass per distinct closest node.  exact:: arithmetic only (the probe's
- * choice; bit-equal to what the frames compute), every culling mask all ones, no ground-tile shortcut.
- *
- * Lanes past n (the tail wave) are masked out by ordinary control flow BEFORE the trace, as the frame kernels mask the
- * lanes past the frame's edge: __all / __ballot / readfirstlane below only ever see live lanes, so a dead lane can
- * neither store nor steer a wave-uniform decision.  A lane holding garbage (NaN, zero direction, 1e300) is live and
- * goes through the same bounded loops as a frame's lane does; what it computes stays in its own registers.
- *
- * CSG hit stack: kCsgFullCap(LEVELS) entries in one launch — it cannot overflow, so there is no retry list and no
- * per-stream scratch.  That is 10 / 20 / 30 / 40 KiB of LDS per wave at depth 1 / 2 / 3 / 4: the LDS, not the
- * registers, bounds the occupancy of the nested instances (8 / 5 / 4 workgroups per CU), hence two waves per SIMD as
- * their register budget ("Ray queries").
- *
- * Memory: the ABI is array-of-structures.  Rays: three 16-byte loads per lane at a 48-byte stride — every 128-byte
- * line a wave touches is consumed whole by the three loads together, the second and third hit in the vector L1, and
- * nothing is written, so no transposition.  Colours: one 12-byte store per lane, 768 contiguous bytes per wave, as
- * the frame kernels store pixels.  Hit records: 80 bytes per lane; stored by the lane itself that would be ten 8-byte
- * stores at an 80-byte stride, each store instruction of the wave dirtying 8 of every 80 bytes of 40 lines.  Instead
- * the wave stages its records in LDS — in the hit stack, which is dead between the closest-hit search and the first
- * shadow ray — and writes them out as rows: lane l stores words l, l + 64, ... of the wave's 640 8-byte words, so each
- * of the ten store instructions covers 512 contiguous bytes, four whole lines.  (8-byte rather than 16-byte rows:
- * c2rt_ray_hit is only 8-byte aligned for a C caller.)  All of them plain vector stores.
- */
-namespace {
-
-constexpr int kHitWords = (int)(sizeof(c2rt_ray_hit) / 8);
-static_assert(sizeof(c2rt_ray) == 48 && sizeof(c2rt_segment) == 48 && sizeof(c2rt_ray_hit) == 80 && kHitWords * 8 == sizeof(c2rt_ray_hit), "ABI layout of the query records");
-static_assert(__builtin_offsetof(c2rt_ray_hit, leaf_geom) == 4 && __builtin_offsetof(c2rt_ray_hit, dist) == 8 &&
-              __builtin_offsetof(c2rt_ray_hit, p) == 32 && __builtin_offsetof(c2rt_ray_hit, normal) == 56, "ABI layout of c2rt_ray_hit");
-static_assert(sizeof(RenderParams) + 64 <= 4096, "the kernel-argument segment holds at most 4 KiB");
-
-template <int LEVELS, bool MLC>
-constexpr int occ_query() { return LEVELS >= 2 ? 2 : occ_of<LEVELS, 0, MLC>(); }
-#define C2RT_OCC_QUERY(L, M) __attribute__((amdgpu_waves_per_eu(occ_query<L, M>(), occ_query<L, M>())))
-
-DEV void query_ctx(exact::Ctx &cx, const RenderParams &P, exact::KArgs K, char *lds, int lane)
-{
-    cx.geoms = (exact::GeomP)P.geoms;
-    cx.nodes = (exact::NodeP)P.nodes;
-    cx.n_nodes = P.n_nodes;
-    cx.kargs = K;
-    cx.lds = lds;
-    cx.lane = lane;
-    cx.csg_cap = (int)P.csg_cap;
-    cx.overflow = false;
-    exact::oob_init(cx.bad);
-    cx.trunc_counter = nullptr;
-#if C2RT_TILE_STATS
-    cx.lane_stats = nullptr;
-#endif
-    cx.block = 0;
-    cx.mask_slot = 0;
-    cx.primary_mask = 0xFFFFFFFFu;
-    cx.shadow_mask0 = 0xFFFFFFFFu;
-    cx.shadow_ground_only = false;
-    cx.primary_ground_only = false;
-    cx.ground_y = 0;
-}
-
-} // namespace
-
-#if C2RT_UNIT == 6
-namespace {
-
-/* six doubles of an array-of-structures input record (c2rt_ray, c2rt_segment): three 16-byte loads where the
- * hardware takes them at 8-byte alignment */
-typedef double __attribute__((ext_vector_type(2), aligned(8))) d2_t;
-DEV void load6(const void *rec, exact::D3 &a, exact::D3 &b)
-{
-    const d2_t *q = static_cast<const d2_t *>(rec);
-    const d2_t q0 = q[0], q1 = q[1], q2 = q[2];
-    a = exact::mk(q0.x, q0.y, q1.x);
-    b = exact::mk(q1.y, q2.x, q2.y);
-}
-
-/* Ray i = trace(ray, TraceType.Ray), rt/renderer.d:325-376, depth 0.  hits / rgb: nullable, not both (wave-uniform). */
-template <int LEVELS, bool MLC>
-__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, MLC)
-trace_rays_kernel(const RenderParams P, const c2rt_ray *__restrict__ rays, const uint64_t n, c2rt_ray_hit *__restrict__ hits, float *__restrict__ rgb)
-{
-    using namespace exact;
-    extern __shared__ __align__(16) char lds[];
-    const int lane = (int)threadIdx.x;
-    const uint64_t first = (uint64_t)blockIdx.x * kWave; /* < n: the grid is ceil(n / 64) */
-    const uint64_t i = first + (uint64_t)lane;
-    const bool live = i < n;
-    Ctx cx;
-    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
-    D3 o = mk(0, 0, 0), d = mk(0, 0, 0);
-    Hit best;
-    Surf surf;
-    Mat mat;
-    int closest = -1;
-    unsigned long long *stage = reinterpret_cast<unsigned long long *>(lds); /* [64][kHitWords] */
-    if (live) {
-        load6(rays + i, o, d);
-        closest = trace_closest<LEVELS>(cx, o, d, hits != nullptr, best, surf, mat);
-        if (hits) {
-            unsigned long long *rec = stage + lane * kHitWords;
-            const int leaf = closest >= 0 ? best.g : -1;
-            rec[0] = (unsigned long long)(uint32_t)closest | ((unsigned long long)(uint32_t)leaf << 32);
-            rec[1] = (unsigned long long)__double_as_longlong(best.dist);
-            rec[2] = (unsigned long long)__double_as_longlong(surf.u);
-            rec[3] = (unsigned long long)__double_as_longlong(surf.v);
-            rec[4] = (unsigned long long)__double_as_longlong(surf.p.x);
-            rec[5] = (unsigned long long)__double_as_longlong(surf.p.y);
-            rec[6] = (unsigned long long)__double_as_longlong(surf.p.z);
-            rec[7] = (unsigned long long)__double_as_longlong(surf.n.x);
-            rec[8] = (unsigned long long)__double_as_longlong(surf.n.y);
-            rec[9] = (unsigned long long)__double_as_longlong(surf.n.z);
-        }
-    }
-    if (hits) {
-        /* every lane of the wave, live or not: the rows of the records of the live lanes (LDS operations of one
-         * wave complete in order; the workgroup is this wave) */
-        __builtin_amdgcn_wave_barrier();
-        const uint64_t left = n - first;
-        const uint32_t words = (uint32_t)(left < (uint64_t)kWave ? left : (uint64_t)kWave) * (uint32_t)kHitWords;
-        unsigned long long *out = reinterpret_cast<unsigned long long *>(hits + first);
-#pragma unroll
-        for (int k = 0; k < kHitWords; ++k) {
-            const uint32_t w = (uint32_t)lane + (uint32_t)(k * kWave);
-            if (w < words) out[w] = stage[w];
-        }
-        __builtin_amdgcn_wave_barrier(); /* the shadow rays below reuse the stack */
-    }
-    if (live && rgb) {
-        F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
-        uint32_t shadow_rays = 0;
-        if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
-        typedef float __attribute__((ext_vector_type(3), aligned(4))) f3_t;
-        f3_t v3;
-        v3.x = c.r;
-        v3.y = c.g;
-        v3.z = c.b;
-        *reinterpret_cast<f3_t *>(rgb + i * 3) = v3;
-    }
-}
-
-/* Segment i = Scene.testVisibility(from, to), rt/scene.d:62-78: full node mask, no ground shortcut */
-template <int LEVELS>
-__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, false)
-test_visibility_kernel(const RenderParams P, const c2rt_segment *__restrict__ seg, const uint64_t n, uint8_t *__restrict__ visible)
-{
-    using namespace exact;
-    extern __shared__ __align__(16) char lds[];
-    const int lane = (int)threadIdx.x;
-    const uint64_t i = (uint64_t)blockIdx.x * kWave + (uint64_t)lane;
-    if (i >= n) return; /* nothing after the trace needs the whole wave */
-    Ctx cx;
-    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
-    D3 from, to;
-    load6(seg + i, from, to);
-    const bool vis = test_visibility<LEVELS, 0>(cx, from, to, 0xFFFFFFFFu, false);
-    visible[i] = vis ? (uint8_t)1 : (uint8_t)0;
-}
-
-template <int LEVELS>
-int launch_trace_rays_level(const RenderParams &p, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb, hipStream_t s)
-{
-    const dim3 grid((uint32_t)((n + kWave - 1) / kWave)), block(kWave);
-    const size_t stack = (size_t)p.csg_cap * kCsgLdsPerEntry, stage = hits ? (size_t)kWave * sizeof(c2rt_ray_hit) : 0;
-    const size_t lds = stack > stage ? stack : stage;
-    if (p.n_lights > 1) hipLaunchKernelGGL((trace_rays_kernel<LEVELS, true>), grid, block, lds, s, p, rays, n, hits, rgb);
-    else hipLaunchKernelGGL((trace_rays_kernel<LEVELS, false>), grid, block, lds, s, p, rays, n, hits, rgb);
-    return (int)hipGetLastError();
-}
-
-template <int LEVELS>
-int launch_test_visibility_level(const RenderParams &p, const c2rt_segment *seg, uint64_t n, uint8_t *visible, hipStream_t s)
-{
-    const dim3 grid((uint32_t)((n + kWave - 1) / kWave)), block(kWave);
-    hipLaunchKernelGGL((test_visibility_kernel<LEVELS>), grid, block, (size_t)p.csg_cap * kCsgLdsPerEntry, s, p, seg, n, visible);
-    return (int)hipGetLastError();
-}
-
-} // namespace
-
-/* the instance of the scene's CSG depth, as the frame kernels are chosen at upload; p.csg_cap = kCsgFullCap(levels) */
-int launch_trace_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb, void *stream)
-{
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!n || n > C2RT_MAX_RAYS || (!hits && !rgb)) return (int)hipErrorInvalidValue;
-    switch (csg_levels) {
-    case 0: return launch_trace_rays_level<0>(p, rays, n, hits, rgb, s);
-    case 1: return launch_trace_rays_level<1>(p, rays, n, hits, rgb, s);
-    case 2: return launch_trace_rays_level<2>(p, rays, n, hits, rgb, s);
-    case 3: return launch_trace_rays_level<3>(p, rays, n, hits, rgb, s);
-    case 4: return launch_trace_rays_level<4>(p, rays, n, hits, rgb, s);
-    default: return (int)hipErrorInvalidValue;
-    }
-}
-
-int launch_test_visibility(const RenderParams &p, int csg_levels, const c2rt_segment *seg, uint64_t n, uint8_t *visible, void *stream)
-{
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!n || n > C2RT_MAX_RAYS) return (int)hipErrorInvalidValue;
-    switch (csg_levels) {
-    case 0: return launch_test_visibility_level<0>(p, seg, n, visible, s);
-    case 1: return launch_test_visibility_level<1>(p, seg, n, visible, s);
-    case 2: return launch_test_visibility_level<2>(p, seg, n, visible, s);
-    case 3: return launch_test_visibility_level<3>(p, seg, n, visible, s);
-    case 4: return launch_test_visibility_level<4>(p, seg, n, visible, s);
-    default: return (int)hipErrorInvalidValue;
-    }
-}
-
-#elif C2RT_UNIT == 7
-
-/*
- * Hit planes (c2rt_render_hits*): the closest-hit record of the ray through the integer corner of every pixel of a
- * camera frame, one plane per field.  The query kernel above with the caller's ray array replaced by the camera: the
- * lane builds its own screen ray (screen_ray<false>, normalized — the operations the frame kernels and the probe
- * apply to (x, y)), so nothing is read but the scene, and only the planes asked for are written.  exact:: arithmetic,
- * every culling mask all ones, full-capacity hit stack, one wavefront per workgroup, no scratch.
- *
- * Pixel -> lane (C2RT_HIT_MAP; the output does not depend on it): 0 = a run of 64 pixels of one row — every store
- * instruction of a scalar plane covers 256 / 512 contiguous bytes; 1 = the frames' 8x8 tile (kept); 2 = 16x4.
- * lecture5.sdl 1080p, all seven planes / node + dist / all but rgb: 117.9 / 62.6 / 65.3 us for the run, 112.8 / 60.1 /
- * 62.0 for the 8x8 tile, 112.5 / 59.9 / 62.1 for 16x4 (profiles/hit_planes.md): coherent rays and fewer distinct
- * closest nodes per wave are worth more than the wider stores.  Lanes past the right or bottom edge are masked out by
- * control flow before the trace, as the query kernel masks its tail.
- *
- * Stores (C2RT_HIT_ROWSTORE): 0 = each lane stores its own values, the three-component planes as three 8-byte stores
- * at a 24-byte stride (kept); 1 = uv / p / normal are staged in the dead hit stack and written as rows, lane l storing
- * words l, l + 64, ... of each tile row's contiguous run (the query kernel's record store) — SLOWER here, 67.2
- * against 62.0 us for all but rgb (8x8), 70.1 against 65.3 (run of 64): a plane's values of a tile row are already
- * adjacent lanes' and the L2 merges the partial lines, so the LDS round trip and the two barriers per plane buy
- * nothing.  All plain vector stores.
- *
- * The planes and the row window of a host chunk are kernel arguments of their own behind the parameter block:
- * RenderParams is the frame kernels' and does not change.  `out` points at row `row0` of the (compact) planes.
- */
-#ifndef C2RT_HIT_MAP
-#define C2RT_HIT_MAP 1
-#endif
-#ifndef C2RT_HIT_ROWSTORE
-#define C2RT_HIT_ROWSTORE 0
-#endif
-namespace {
-
-constexpr int kHitTileW = C2RT_HIT_MAP == 0 ? 64 : (C2RT_HIT_MAP == 1 ? 8 : 16), kHitTileH = kWave / kHitTileW;
-constexpr size_t kHitStageBytes = C2RT_HIT_ROWSTORE ? (size_t)kWave * 3 * 8 : 0;
-static_assert(sizeof(RenderParams) + sizeof(c2rt_hit_planes) + 16 <= 4096, "the kernel-argument segment holds at most 4 KiB");
-static_assert(sizeof(c2rt_hit_planes) == 56, "ABI layout of c2rt_hit_planes");
-
-/* one C-component plane of doubles, as rows: the wave's tile is kHitTileH runs of kHitTileW * C contiguous words.
- * Every lane of the wave takes part, live or not; words of dead pixels are not stored (they were never staged). */
-template <int C>
-DEV void store_rows(double *plane, unsigned long long *stage, int lane, bool live, const double (&v)[C],
-                    uint32_t width, uint32_t rows, uint32_t x0, uint32_t r0)
-{
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < C; ++k) stage[lane * C + k] = (unsigned long long)__double_as_longlong(v[k]);
-    }
-    __builtin_amdgcn_wave_barrier(); /* LDS operations of one wave complete in order; the workgroup is this wave */
-    unsigned long long *out = reinterpret_cast<unsigned long long *>(plane);
-    constexpr uint32_t run = (uint32_t)kHitTileW * C;
-#pragma unroll
-    for (int k = 0; k < C; ++k) {
-        const uint32_t w = (uint32_t)lane + (uint32_t)(k * kWave);
-        const uint32_t tr = w / run, c = w % run;
-        const uint32_t r = r0 + tr, col = x0 * C + c;
-        if (r < rows && col < width * C) out[(size_t)r * width * C + col] = stage[w];
-    }
-    __builtin_amdgcn_wave_barrier(); /* the next plane, then the shadow rays, reuse the stack */
-}
-
-template <int LEVELS, bool MLC>
-__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, MLC)
-hit_planes_kernel(const RenderParams P, const c2rt_hit_planes out, const uint32_t row0, const uint32_t rows, const uint32_t tiles_x)
-{
-    using namespace exact;
-    extern __shared__ __align__(16) char lds[];
-    const int lane = (int)threadIdx.x;
-    const uint32_t trow = blockIdx.x / tiles_x, tcol = blockIdx.x % tiles_x; /* the grid is tiles_x * ceil(rows / kHitTileH) */
-    const uint32_t x0 = tcol * kHitTileW, r0 = trow * kHitTileH;
-    const uint32_t x = x0 + (uint32_t)(lane % kHitTileW);
-    const uint32_t r = r0 + (uint32_t)(lane / kHitTileW); /* row within this launch */
-    const bool live = x < P.width && r < rows;
-    const bool record = out.dist || out.uv || out.p || out.normal; /* wave-uniform: best.dist and the surface are read */
-    Ctx cx;
-    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
-    D3 d = mk(0, 0, 0);
-    Hit best;
-    Surf surf;
-    Mat mat;
-    int closest = -1;
-    const size_t idx = (size_t)r * P.width + x;
-    if (live) {
-        /* local row -> frame row under interleaved strips, as render_tile maps it */
-        const uint32_t lr = r + row0;
-        uint32_t y = lr;
-        if (P.strip_world > 1) {
-            const uint32_t sh = P.strip_height;
-            y = ((lr / sh) * P.strip_world + P.strip_rank) * sh + lr % sh;
-        }
-        Rng rng = {0u, 0, 0};
-        D3 o, raw;
-        screen_ray<false>(cx.bad, P, (double)x, (double)y, 0, rng, o, raw);
-        d = normalized(cx.bad, raw); /* raytrace(): rt/camera.d:144-147 */
-        closest = trace_closest<LEVELS>(cx, o, d, record, best, surf, mat);
-        if (out.node) out.node[idx] = closest;
-        if (out.leaf) out.leaf[idx] = closest >= 0 ? best.g : -1;
-        if (out.dist) out.dist[idx] = best.dist;
-#if !C2RT_HIT_ROWSTORE
-        if (out.uv) {
-            typedef double __attribute__((ext_vector_type(2), aligned(8))) d2_t;
-            d2_t uv;
-            uv.x = surf.u;
-            uv.y = surf.v;
-            *reinterpret_cast<d2_t *>(out.uv + idx * 2) = uv;
-        }
-        if (out.p) {
-            out.p[idx * 3 + 0] = surf.p.x;
-            out.p[idx * 3 + 1] = surf.p.y;
-            out.p[idx * 3 + 2] = surf.p.z;
-        }
-        if (out.normal) {
-            out.normal[idx * 3 + 0] = surf.n.x;
-            out.normal[idx * 3 + 1] = surf.n.y;
-            out.normal[idx * 3 + 2] = surf.n.z;
-        }
-#endif
-    }
-#if C2RT_HIT_ROWSTORE
-    {
-        unsigned long long *stage = reinterpret_cast<unsigned long long *>(lds); /* [64][3] */
-        if (out.uv) {
-            const double v[2] = {surf.u, surf.v};
-            store_rows<2>(out.uv, stage, lane, live, v, P.width, rows, x0, r0);
-        }
-        if (out.p) {
-            const double v[3] = {surf.p.x, surf.p.y, surf.p.z};
-            store_rows<3>(out.p, stage, lane, live, v, P.width, rows, x0, r0);
-        }
-        if (out.normal) {
-            const double v[3] = {surf.n.x, surf.n.y, surf.n.z};
-            store_rows<3>(out.normal, stage, lane, live, v, P.width, rows, x0, r0);
-        }
-    }
-#endif
-    if (live && out.rgb) {
-        F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
-        uint32_t shadow_rays = 0;
-        if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
-        typedef float __attribute__((ext_vector_type(3), aligned(4))) f3_t;
-        f3_t v3;
-        v3.x = c.r;
-        v3.y = c.g;
-        v3.z = c.b;
-        *reinterpret_cast<f3_t *>(out.rgb + idx * 3) = v3;
-    }
-}
-
-template <int LEVELS>
-int launch_hit_planes_level(const RenderParams &p, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, hipStream_t s)
-{
-    const uint32_t tiles_x = (p.width + kHitTileW - 1) / kHitTileW, tiles_y = (rows + kHitTileH - 1) / kHitTileH;
-    const dim3 grid(tiles_x * tiles_y), block(kWave); /* at most 2^16 x 2^16 pixels / 64 */
-    const size_t stack = (size_t)p.csg_cap * kCsgLdsPerEntry;
-    const size_t lds = stack > kHitStageBytes ? stack : kHitStageBytes;
-    if (p.n_lights > 1) hipLaunchKernelGGL((hit_planes_kernel<LEVELS, true>), grid, block, lds, s, p, out, row0, rows, tiles_x);
-    else hipLaunchKernelGGL((hit_planes_kernel<LEVELS, false>), grid, block, lds, s, p, out, row0, rows, tiles_x);
-    return (int)hipGetLastError();
-}
-
-} // namespace
-
-/* Rows [row0, row0 + rows) of the local rows of the frame `p` describes (frame_params with the query settings on top:
- * force_exact, csg_cap = kCsgFullCap(csg_levels), no culling, no ground node) into planes whose first row is row0;
- * device pointers, at least one of them non-null, rows > 0.  Declared in c2rt_api.cpp: c2rt_device.h is the frame
- * units' and stays as it is. */
-int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream)
-{
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!rows || !p.width || !(out.node || out.leaf || out.dist || out.uv || out.p || out.normal || out.rgb)) return (int)hipErrorInvalidValue;
-    switch (csg_levels) {
-    case 0: return launch_hit_planes_level<0>(p, out, row0, rows, s);
-    case 1: return launch_hit_planes_level<1>(p, out, row0, rows, s);
-    case 2: return launch_hit_planes_level<2>(p, out, row0, rows, s);
-    case 3: return launch_hit_planes_level<3>(p, out, row0, rows, s);
-    case 4: return launch_hit_planes_level<4>(p, out, row0, rows, s);
-    default: return (int)hipErrorInvalidValue;
-    }
-}
-
-#else /* C2RT_UNIT == 8 */
-
-/*
- * Adaptive anti-aliasing (c2rt_render_frame_adaptive*): Renderer.renderRT's three passes with the third one run where
- * the second raised its flag, which is what rt/renderer.d:150-188 computes the flag for and then does not do.  The
- * one-tap frame is the frame kernels' (c2rt_api.cpp calls the frame path with taps = 1); this unit holds the two
- * kernels behind it on the same stream.
- *
- * aa_detect_kernel — rt/renderer.d:154-177 with tooDifferent (rt/color.d:18-23): one lane per pixel over 8x8 tiles,
- * fifteen floats in (the pixel and its four neighbours, clamped at the frame's edges as the reference clamps them), one
- * byte out.  fp32 in the reference's order, no fma (the build has contraction off).  Memory-bound: 12 B read and 1 B
- * written per pixel from HBM, the neighbours come out of the caches.
- *
- * aa_refine_kernel — renderPixelAA (rt/renderer.d:233-251) for the flagged pixels: the hit-plane kernel's wave (one
- * wavefront per workgroup, one 8x8 tile, exact:: arithmetic, every culling mask all ones, full-capacity hit stack, no
- * ground shortcut) with the work items of the tile PACKED into lanes.  A tile with k flagged pixels has 4k items
- * (pixel j, tap 1 + i % 4); lane l of round r takes item 64 r + l, so a tile with up to 16 flagged pixels — an edge
- * crossing it — is ONE round of the trace at 4k / 64 occupancy instead of four rounds at k / 64.  The list of flagged
- * lanes is built in LDS from the ballot's prefix count; each item leaves its colour in an LDS array [pixel][tap] (3 KiB,
- * behind the hit stack), and the pixel's own lane then adds the four to out[y][x] in tap order and divides by 5.0f:
- * render_tile's statements (c2rt_trace.inc), hence the bits of the C2RT_TAPS_REF5 frame.  Lanes without an item are
- * masked out by control flow before the trace, as the query kernel masks its tail.  All plain vector stores.
- *
- * Detection is a launch of its own: it reads the neighbours' ONE-TAP values, and refinement overwrites pixels in
- * place; the caller's mask is the buffer between the two.  Refinement reads and writes its own pixel and the mask only.
- *
- * C2RT_AA_PACKED = 0 builds the plain variant instead: every flagged lane loops over its four taps, the others sit out
- * (A/B: profiles/adaptive_aa.md).
- */
-#ifndef C2RT_AA_PACKED
-#define C2RT_AA_PACKED 1
-#endif
-namespace {
-
-static_assert(sizeof(RenderParams) + 64 <= 4096, "the kernel-argument segment holds at most 4 KiB");
-static_assert(kTileW * kTileH == kWave, "one wavefront, one tile");
-constexpr int kAaDetectWaves = 4; /* tiles (wavefronts) per workgroup of the detection kernel */
-
-__global__ void __launch_bounds__(kWave * kAaDetectWaves)
-aa_detect_kernel(const float *__restrict__ frame, uint8_t *__restrict__ needs_aa, const uint32_t width, const uint32_t height,
-                 const uint32_t tiles_x, const uint32_t n_tiles, const float threshold)
-{
-    const uint32_t tile = blockIdx.x * kAaDetectWaves + threadIdx.x / kWave;
-    if (tile >= n_tiles) return;
-    const uint32_t lane = threadIdx.x % kWave;
-    const uint32_t x = (tile % tiles_x) * kTileW + lane % kTileW, y = (tile / tiles_x) * kTileH + lane / kTileW;
-    if (x >= width || y >= height) return;
-    const uint32_t xs[5] = {x, x > 0 ? x - 1 : x, x + 1 < width ? x + 1 : x, x, x};
-    const uint32_t ys[5] = {y, y, y, y > 0 ? y - 1 : y, y + 1 < height ? y + 1 : y};
-    float n[5][3];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const float *q = frame + ((size_t)ys[i] * width + xs[i]) * 3;
-        n[i][0] = q[0];
-        n[i][1] = q[1];
-        n[i][2] = q[2];
-    }
-    bool flag = false;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float average = 0.0f; /* Color average = Color(0, 0, 0); foreach: average += neighs[i] */
-#pragma unroll
-        for (int i = 0; i < 5; ++i) average = average + n[i][c];
-        average = average / 5.0f;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) flag = flag | (fabsf(n[i][c] - average) > threshold); /* a NaN compares false */
-    }
-    needs_aa[(size_t)y * width + x] = flag ? (uint8_t)1 : (uint8_t)0;
-}
-
-constexpr size_t kAaColourBytes = (size_t)kWave * 4 * 3 * sizeof(float), kAaListBytes = kWave;
-
-template <int LEVELS, bool MLC>
-__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, MLC)
-aa_refine_kernel(const RenderParams P, float *__restrict__ frame, const uint8_t *__restrict__ needs_aa, const uint32_t tiles_x)
-{
-    using namespace exact;
-    extern __shared__ __align__(16) char lds[];
-    const int lane = (int)threadIdx.x;
-    const uint32_t x0 = (blockIdx.x % tiles_x) * kTileW, y0 = (blockIdx.x / tiles_x) * kTileH; /* the grid is tiles_x * tiles_y */
-    const uint32_t x = x0 + (uint32_t)(lane % kTileW), y = y0 + (uint32_t)(lane / kTileW);
-    const size_t idx = (size_t)y * P.width + x;
-    const bool flagged = x < P.width && y < P.height && needs_aa[idx] != 0;
-    const unsigned long long flags = __ballot(flagged);
-    if (!flags) return;
-    const size_t stack = (size_t)P.csg_cap * kCsgLdsPerEntry;
-    float *colour = reinterpret_cast<float *>(lds + stack); /* [pixel's lane][tap - 1][3] */
-    Ctx cx;
-    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
-    Rng rng = {0u, 0, 0};
-#if C2RT_AA_PACKED
-    uint8_t *list = reinterpret_cast<uint8_t *>(lds + stack + kAaColourBytes); /* the flagged lanes, ascending */
-    if (flagged) list[__popcll(flags & ((1ull << lane) - 1ull))] = (uint8_t)lane;
-    __builtin_amdgcn_wave_barrier(); /* LDS operations of one wave complete in order; the workgroup is this wave */
-    const int items = 4 * __popcll(flags);
-#pragma unroll 1
-    for (int first = 0; first < items; first += kWave) {
-        const int i = first + lane;
-        if (i < items) {
-            const int pl = (int)list[i >> 2], t = 1 + (i & 3);
-            const uint32_t px = x0 + (uint32_t)(pl % kTileW), py = y0 + (uint32_t)(pl / kTileW);
-            D3 o, raw;
-            screen_ray<false>(cx.bad, P, (double)px + k_aa_x[t], (double)py + k_aa_y[t], 0, rng, o, raw);
-            const D3 d = normalized(cx.bad, raw); /* raytrace(): rt/camera.d:144-147 */
-            Hit best;
-            Surf surf;
-            Mat mat;
-            const int closest = trace_closest<LEVELS>(cx, o, d, false, best, surf, mat);
-            F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
-            uint32_t shadow_rays = 0;
-            if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
-            float *slot = colour + (pl * 4 + (t - 1)) * 3;
-            slot[0] = c.r;
-            slot[1] = c.g;
-            slot[2] = c.b;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-#else
-    if (flagged) {
-#pragma unroll 1
-        for (int t = 1; t <= 4; ++t) {
-            D3 o, raw;
-            screen_ray<false>(cx.bad, P, (double)x + k_aa_x[t], (double)y + k_aa_y[t], 0, rng, o, raw);
-            const D3 d = normalized(cx.bad, raw);
-            Hit best;
-            Surf surf;
-            Mat mat;
-            const int closest = trace_closest<LEVELS>(cx, o, d, false, best, surf, mat);
-            F3 c = mkf(0, 0, 0);
-            uint32_t shadow_rays = 0;
-            if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
-            float *slot = colour + (lane * 4 + (t - 1)) * 3;
-            slot[0] = c.r;
-            slot[1] = c.g;
-            slot[2] = c.b;
-        }
-    }
-#endif
-    if (flagged) {
-        /* renderPixelAA: accum = the pixel's one-tap colour, += the four samples in tap order, / 5 — Color / float */
-        typedef float __attribute__((ext_vector_type(3), aligned(4))) f3_t;
-        f3_t *out = reinterpret_cast<f3_t *>(frame + idx * 3);
-        const f3_t v0 = *out;
-        F3 accum = mkf(v0.x, v0.y, v0.z);
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const float *slot = colour + (lane * 4 + t) * 3;
-            accum = accum + mkf(slot[0], slot[1], slot[2]);
-        }
-        accum = accum / 5.0f;
-        f3_t v3;
-        v3.x = accum.r;
-        v3.y = accum.g;
-        v3.z = accum.b;
-        *out = v3;
-    }
-}
-
-template <int LEVELS>
-int launch_aa_refine_level(const RenderParams &p, float *frame, const uint8_t *needs_aa, hipStream_t s)
-{
-    const uint32_t tiles_x = (p.width + kTileW - 1) / kTileW, tiles_y = (p.height + kTileH - 1) / kTileH;
-    const dim3 grid(tiles_x * tiles_y), block(kWave); /* at most 2^16 x 2^16 pixels / 64 */
-    const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry + kAaColourBytes + kAaListBytes;
-    if (p.n_lights > 1) hipLaunchKernelGGL((aa_refine_kernel<LEVELS, true>), grid, block, lds, s, p, frame, needs_aa, tiles_x);
-    else hipLaunchKernelGGL((aa_refine_kernel<LEVELS, false>), grid, block, lds, s, p, frame, needs_aa, tiles_x);
-    return (int)hipGetLastError();
-}
-
-} // namespace
-
-/* needs_aa[y][x] of the whole width x height frame at `frame` (device pointers).  Declared in c2rt_api.cpp, as
- * launch_hit_planes is. */
-int launch_aa_detect(const float *frame, uint8_t *needs_aa, uint32_t width, uint32_t height, float threshold, void *stream)
-{
-    if (!width || !height || !frame || !needs_aa) return (int)hipErrorInvalidValue;
-    const uint32_t tiles_x = (width + kTileW - 1) / kTileW, n_tiles = tiles_x * ((height + kTileH - 1) / kTileH);
-    hipLaunchKernelGGL(aa_detect_kernel, dim3((n_tiles + kAaDetectWaves - 1) / kAaDetectWaves), dim3(kWave * kAaDetectWaves), 0,
-                       static_cast<hipStream_t>(stream), frame, needs_aa, width, height, tiles_x, n_tiles, threshold);
-    return (int)hipGetLastError();
-}
-
-/* The flagged pixels of the whole frame `p` describes (hit_params' settings: exact::, csg_cap = kCsgFullCap(csg_levels),
- * no culling, no ground node; no strips) from their one-tap to their five-tap value, in place. */
-int launch_aa_refine(const RenderParams &p, int csg_levels, float *frame, const uint8_t *needs_aa, void *stream)
-{
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!p.width || !p.height || !frame || !needs_aa) return (int)hipErrorInvalidValue;
-    switch (csg_levels) {
-    case 0: return launch_aa_refine_level<0>(p, frame, needs_aa, s);
-    case 1: return launch_aa_refine_level<1>(p, frame, needs_aa, s);
-    case 2: return launch_aa_refine_level<2>(p, frame, needs_aa, s);
-    case 3: return launch_aa_refine_level<3>(p, frame, needs_aa, s);
-    case 4: return launch_aa_refine_level<4>(p, frame, needs_aa, s);
-    default: return (int)hipErrorInvalidValue;
-    }
-}
-
-#endif /* C2RT_UNIT == 6 / 7 / 8 */
 
 #else
 #error "C2RT_UNIT out of range"

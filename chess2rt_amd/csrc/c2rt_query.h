@@ -1,0 +1,29 @@
+/*
+ * c2rt_query.h — launch interface of the query kernels (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_adaptive.hip), shared
+ * by those files and c2rt_api.cpp.  A header of its own: c2rt_device.h is a prerequisite of every frame-kernel object,
+ * and query work should not rebuild them.  All return hipError_t as int; every pointer is a device pointer.
+ *
+ * `p` is the frame path's parameter block with the query settings on top (c2rt_api.cpp: query_params / hit_params):
+ * force_exact, csg_cap = kCsgFullCap(csg_levels), no culling, no ground node, no scratch.
+ */
+#ifndef C2RT_QUERY_H
+#define C2RT_QUERY_H
+
+#include "c2rt_device.h"
+
+namespace c2rt {
+
+/* Ray and visibility queries (c2rt_trace_rays*, c2rt_test_visibility*): no camera; 0 < n <= C2RT_MAX_RAYS; hits / rgb
+ * nullable, not both */
+int launch_trace_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb, void *stream);
+int launch_test_visibility(const RenderParams &p, int csg_levels, const c2rt_segment *seg, uint64_t n, uint8_t *visible, void *stream);
+/* Hit planes (c2rt_render_hits*): rows [row0, row0 + rows) of the local rows of the frame `p` describes, into planes
+ * whose first row is row0; at least one plane non-null, rows > 0 */
+int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream);
+/* Adaptive anti-aliasing (c2rt_render_frame_adaptive*): the flag image needs_aa[y][x] of a whole one-tap frame, then
+ * the flagged pixels of the whole frame `p` describes (no strips) from their one-tap to their five-tap value, in place */
+int launch_aa_detect(const float *frame, uint8_t *needs_aa, uint32_t width, uint32_t height, float threshold, void *stream);
+int launch_aa_refine(const RenderParams &p, int csg_levels, float *frame, const uint8_t *needs_aa, void *stream);
+
+} // namespace c2rt
+#endif

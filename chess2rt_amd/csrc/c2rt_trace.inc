@@ -2,7 +2,8 @@
  * c2rt_trace.inc — the trace itself: vectors, primitives, CSG, nodes, culling masks, textures, shading,
  * camera and the per-tile renderer (SURVEY.md section 8(a), rows a1-a26).
  *
- * Included TWICE by c2rt_kernels.hip, into two namespaces:
+ * Included by c2rt_trace_common.inc into two namespaces (the frame file c2rt_kernels.hip takes both, the query files
+ * c2rt_rays.hip, c2rt_hit_planes.hip and c2rt_adaptive.hip exact:: only):
  *   lean::  (kLean = true)   divide / sqrt / normalise through fp64_lean.h, OPTIMISTICALLY: every use tests
  *           its operands' window with two integer instructions and folds the outcome into Ctx::bad instead of
  *           branching to a fallback; results of a lane whose operand was outside a window are garbage (never
@@ -93,22 +94,10 @@ struct Oob {
 };
 constexpr int kWinLo = -240, kWinHi = 240;
 DEV void oob_init(Oob &b) { b.t = 0; }
-#ifndef C2RT_OOB_FORM
-#define C2RT_OOB_FORM 1
-#endif
-#if C2RT_OOB_FORM == 0
-constexpr int kOobShift = 21;
-DEV void oob_note(Oob &b, double x)
-{
-    const uint32_t t = ((uint32_t)__double2hiint(x) << 1) - ((uint32_t)(kWinLo + 1023) << 21);
-    b.t = b.t > t ? b.t : t;
-}
-DEV void oob_note_nonneg(Oob &b, double x) { oob_note(b, x); }
-#else
 /* t in units of the high word itself (exponent at bit 20): sign masked off, low bound subtracted, running
  * maximum — three instructions.  (Written as `(hi << 1) - (LO << 21)` the compiler extracts the shifted word
- * with a 64-bit shift by 31 and a mask, v_alignbit_b32 + v_and_b32: four.)  The first instruction is spelled
- * out so that the high word stays a 32-bit value of its own. */
+ * with a 64-bit shift by 31 and a mask, v_alignbit_b32 + v_and_b32: four; that form was a build switch up to
+ * commit f0eed4f.)  The first instruction is spelled out so that the high word stays a 32-bit value of its own. */
 constexpr int kOobShift = 20;
 DEV void oob_note(Oob &b, double x)
 {
@@ -125,7 +114,6 @@ DEV void oob_note_nonneg(Oob &b, double x)
     asm("v_subrev_u32_e32 %0, %2, %1" : "=v"(t) : "v"(__double2hiint(x)), "n"((uint32_t)(kWinLo + 1023) << 20));
     b.t = b.t > t ? b.t : t;
 }
-#endif
 DEV bool oob_any(const Oob &b) { return b.t >= ((uint32_t)(kWinHi - kWinLo) << kOobShift); }
 /* an fp32 operand (window 2^+-60, fp64_lean.h: f32_ok) folded into the same accumulator: outside -> all ones */
 DEV void oob_note_f32(Oob &b, float x)
@@ -299,6 +287,32 @@ struct Ctx {
     double ground_y;
 };
 
+/* The context of a lane that traces outside a frame tile (the pixel probe and the query kernels: caller's rays, hit
+ * planes, adaptive refinement): no culling — every mask all ones —, no ground shortcut, nothing counted. */
+DEV void query_ctx(Ctx &cx, const RenderParams &P, KArgs K, char *lds, int lane)
+{
+    cx.geoms = (GeomP)P.geoms;
+    cx.nodes = (NodeP)P.nodes;
+    cx.n_nodes = P.n_nodes;
+    cx.kargs = K;
+    cx.lds = lds;
+    cx.lane = lane;
+    cx.csg_cap = (int)P.csg_cap;
+    cx.overflow = false;
+    oob_init(cx.bad);
+    cx.trunc_counter = nullptr;
+#if C2RT_TILE_STATS
+    cx.lane_stats = nullptr;
+#endif
+    cx.block = 0;
+    cx.mask_slot = 0;
+    cx.primary_mask = 0xFFFFFFFFu;
+    cx.shadow_mask0 = 0xFFFFFFFFu;
+    cx.shadow_ground_only = false;
+    cx.primary_ground_only = false;
+    cx.ground_y = 0;
+}
+
 /* A ray in some object space: origin, unit direction and A = |d|^2 exactly as
  * Sphere.intersect computes it (rt/geometry.d:96) — the direction is shared by
  * every geometry under a node and by all steps of findAllIntersections, so A
@@ -383,9 +397,6 @@ DEV bool sphere_intersect(Oob &bad, GeomP G, int gid, const ORay &r, Hit &h, boo
  * `mult < 0` is decided from the operand signs (an IEEE quotient is negative
  * iff exactly one operand is and the numerator is non-zero), which skips the
  * division for every face behind the origin. */
-#ifndef C2RT_CUBE_DEFER_P
-#define C2RT_CUBE_DEFER_P 1
-#endif
 template <int NEED, int AXIS>
 DEV bool cube_sides(Oob &bad, double oy, double dy, double rden, double ylo, double yhi, double ox, double dx, double xlo, double xhi,
                     double oz, double dz, double zlo, double zhi, D3 o, D3 d, Hit &h, bool full)
@@ -413,9 +424,6 @@ DEV bool cube_sides(Oob &bad, double oy, double dy, double rden, double ylo, dou
         const bool reject = (!kLean & (mult < 0)) | (mult > h.dist) | (px < xlo) | (px > xhi) | (pz < zlo) | (pz > zhi);
         if (reject) continue;
         h.dist = mult;
-#if !C2RT_CUBE_DEFER_P
-        if (NEED >= kPoint) h.p = o + d * mult;
-#endif
         /* Vector(0, side, 0) un-permuted is the face normal along AXIS; u = px - cx, v = pz - cz are
          * components of p - center (px, pz are h.p's permuted components): hit_surface */
         if (C2RT_WANT_FULL(NEED, full)) h.code = AXIS | (side > 0 ? kCodeSide : 0);
@@ -424,42 +432,27 @@ DEV bool cube_sides(Oob &bad, double oy, double dy, double rden, double ylo, dou
     return found;
 }
 
-/* Cube.intersect — rt/geometry.d:172-196 */
-#ifndef C2RT_CUBE_AWAY
-#define C2RT_CUBE_AWAY 0 /* see cube_away below */
-#endif
+/* Cube.intersect — rt/geometry.d:172-196 (an early-out in front of it was measured and rejected: see below) */
 template <int NEED>
 DEV bool cube_intersect(Oob &bad, GeomP G, int gid, const ORay &r, Hit &h, bool full)
 {
     const D3 o = r.o, d = r.d;
     const D3 lo = ld3(G->q), hi = ld3(G->q + 3);
-#if C2RT_CUBE_AWAY == 3
-    /* variant 3 of the early-out below, INSIDE the test (no face plane lives longer than it already does): a
-     * kPoint caller (the stepping loops of a CsgOp) passes "this is the third step or later" in `full`, which
-     * kPoint does not otherwise read */
-    if (NEED == kPoint && full && (G->flags & kGeomFinite)) {
-        const bool away = ((o.x > hi.x) & (d.x > 0)) | ((o.x < lo.x) & (d.x < 0)) | ((o.y > hi.y) & (d.y > 0)) | ((o.y < lo.y) & (d.y < 0)) |
-                          ((o.z > hi.z) & (d.z > 0)) | ((o.z < lo.z) & (d.z < 0));
-        const double s = ((o.x + o.y) + o.z) + ((d.x + d.y) + d.z);
-        if (away & (bool)__builtin_isfinite(s)) return false;
-    }
-#endif
     /* Y faces; X faces = project(1,0,2): (y,x,z); Z faces = project(0,2,1): (x,z,y) */
     bool found = cube_sides<NEED, 1>(bad, o.y, d.y, r.ry, lo.y, hi.y, o.x, d.x, lo.x, hi.x, o.z, d.z, lo.z, hi.z, o, d, h, full);
     found |= cube_sides<NEED, 0>(bad, o.x, d.x, r.rx, lo.x, hi.x, o.y, d.y, lo.y, hi.y, o.z, d.z, lo.z, hi.z, o, d, h, full);
     found |= cube_sides<NEED, 2>(bad, o.z, d.z, r.rz, lo.z, hi.z, o.x, d.x, lo.x, hi.x, o.y, d.y, lo.y, hi.y, o, d, h, full);
     if (found) {
-#if C2RT_CUBE_DEFER_P
         /* the point of the face that won, once per cube instead of once per accepted face: the same
          * `o + d * mult` on the same operands (h.dist IS that face's mult) */
         if (NEED >= kPoint) h.p = o + d * h.dist;
-#endif
         if (NEED >= kPoint) h.g = gid;
     }
     return found;
 }
 
-/* Cube.intersect returns false — EXACTLY, not conservatively — for a ray whose origin lies beyond one face pair's
+/* MEASURED AND REJECTED: an early-out in front of Cube.intersect for the stepping loops of a CsgOp.
+ * Cube.intersect returns false — EXACTLY, not conservatively — for a ray whose origin lies beyond one face pair's
  * slab and which moves further away along that axis (o.x > hi.x and d.x > 0, or the mirror image, on any axis):
  *   faces of that axis (rt/geometry.d:208-216): both numerators o.x - face are > 0 (the difference of distinct doubles
  *     is never zero; lo <= hi, or the cube is empty and nothing is ever accepted) over the denominator -d.x < 0:
@@ -467,25 +460,17 @@ DEV bool cube_intersect(Oob &bad, GeomP G, int gid, const ORay &r, Hit &h, bool 
  *   faces of the other two axes: an accepted candidate has 0 <= mult <= +inf (NaN excluded below), so d.x * mult >= 0
  *     and px = RN(o.x + d.x * mult) >= o.x > hi.x by the monotonicity of rounding: rejected by `px > xhi`.
  * The premise is ordered arithmetic: a NaN origin component, direction component or face plane makes the literal
- * code ACCEPT candidates (every comparison with NaN is false), so the shortcut is only taken for finite cubes
+ * code ACCEPT candidates (every comparison with NaN is false), so the shortcut was only taken for finite cubes
  * (kGeomFinite, scalar) and lanes whose origin and direction are finite (one class test on their sum: a finite sum
  * has no NaN or infinite term).  This is the step on which findAllIntersections (rt/geometry.d:271-290) ends after a
- * ray has left a cube — a third of all Cube.intersect calls under a CsgOp: ~16 instructions instead of ~70. */
-DEV bool cube_away(GeomP G, const ORay &r)
-{
-    const D3 o = r.o, d = r.d;
-    const D3 lo = ld3(G->q), hi = ld3(G->q + 3);
-    const bool away = ((o.x > hi.x) & (d.x > 0)) | ((o.x < lo.x) & (d.x < 0)) | ((o.y > hi.y) & (d.y > 0)) | ((o.y < lo.y) & (d.y < 0)) |
-                      ((o.z > hi.z) & (d.z > 0)) | ((o.z < lo.z) & (d.z < 0));
-    const double s = ((o.x + o.y) + o.z) + ((d.x + d.y) + d.z);
-    return away & (bool)__builtin_isfinite(s);
-}
-/* MEASURED AND REJECTED (profiles/r04_variants.md, step 1): exact and bit-identical on the whole suite, but the
- * kernels are slower with it — lecture5 4K x5 1.010 -> 1.054 ms, csg_stress 8.40 -> 9.11 ms: the headline instance
- * goes from 122 to 124 VGPRs and from 151 to 190 SGPRs spilled to VGPR lanes (the cube's six face planes live across
- * the stepping loop), which costs more than the ~55 instructions the early-out saves per evaluation.  Off by default;
- * -DC2RT_CUBE_AWAY=1 (on the terminating step) / =2 (also on a child's first step) rebuild the A/B. */
-/* (variant 3, inside cube_intersect: see there) */
+ * ray has left a cube — a third of all Cube.intersect calls under a CsgOp: ~16 instructions instead of ~70.
+ * Exact and bit-identical on the whole suite (profiles/r04_variants.md, step 1), but the kernels are slower with
+ * it — lecture5 4K x5 1.010 -> 1.054 ms, csg_stress 8.40 -> 9.11 ms: the headline instance goes from 122 to 124 VGPRs
+ * and from 151 to 190 SGPRs spilled to VGPR lanes (the cube's six face planes live across the stepping loop), which
+ * costs more than the ~55 instructions the early-out saves per evaluation.  Three placements were tried: on the
+ * terminating step of a child's stepping loop, also on its first step, and inside cube_intersect itself (where no
+ * face plane lives longer than it already does).  The code (cube_away and its three call sites) is in commit
+ * f0eed4f. */
 
 /* Conservative reject: true when the ray cannot reach the geometry's padded
  * bounding sphere (DevGeom::bound), in which case Geometry.intersect would
@@ -595,12 +580,12 @@ __device__ __forceinline__ bool csg_intersect(const Ctx &cx, GeomP G, const ORay
         if (replay && wside != side) continue; /* this lane's winner came from the other child */
         const int limit = replay ? wk + 1 : kMaxCsgHits;
         const bool child_cube = cx.geoms[child].type == C2RT_GEOM_CUBE && (cx.geoms[child].flags & kGeomFinite); /* scalar */
+        (void)child_cube; /* see csg_intersect_leaf */
         ORay rr = ray;
         double cur = 0;
         int k = 0;
         while (k < limit) {
             t.dist = 1e99;
-            if (C2RT_CUBE_AWAY && C2RT_CUBE_AWAY < 3 && child_cube && !replay && (C2RT_CUBE_AWAY == 2 ? k != 1 : k >= 2) && cube_away(cx.geoms + child, rr)) break;
             /* the child's lists go above this list's top; a replay no longer needs this list */
             if (!geom_intersect<LEVEL - 1, kRt>(cx, child, rr, t, replay && k == wk && want_full, replay ? base : base + n + k)) break;
             t.dist += cur;
@@ -664,9 +649,6 @@ __device__ __forceinline__ bool csg_intersect(const Ctx &cx, GeomP G, const ORay
     return true;
 }
 
-#ifndef C2RT_CSG_FIRST_HIT
-#define C2RT_CSG_FIRST_HIT 1
-#endif
 /* The same for a CSG whose children are both primitives (the innermost level, by
  * far the most executed one): the three stepping loops are written out, with
  * compile-time NEED for the collect loops — measurably faster than the single
@@ -692,7 +674,11 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
 #pragma unroll 1
     for (int side = 0; side < 2; ++side) {
         const int child = side ? right : left;
+        /* Unused since the cube early-out went (cube_intersect's comment), and kept: this read is where the compiler
+         * places the scalar load of the child's record, which geom_intersect needs anyway — without it the load moves
+         * and every instance is scheduled differently from the code all measurements were taken on. */
         const bool child_cube = cx.geoms[child].type == C2RT_GEOM_CUBE && (cx.geoms[child].flags & kGeomFinite); /* scalar */
+        (void)child_cube;
         ORay rr = ray;
         double cur = 0;
         int k = 0;
@@ -705,23 +691,14 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
                 if (cx.lane == (int)__builtin_ctzll(act)) { atomicAdd(cx.lane_stats + 2, (unsigned long long)__builtin_popcountll(act)); atomicAdd(cx.lane_stats + 3, 64ull); }
             }
 #endif
-            if (C2RT_CUBE_AWAY && child_cube && (C2RT_CUBE_AWAY == 2 ? k != 1 : k >= 2) && C2RT_CUBE_AWAY < 3 && cube_away(cx.geoms + child, rr)) break; /* (k == 1: the origin is inside the cube) */
-#if C2RT_CSG_FIRST_HIT
             /* (the face code of every collected hit goes into its tag: see the winner below) */
             if (!geom_intersect<0, kFull>(cx, child, rr, t, false, 0)) break;
-#else
-            if (!geom_intersect<0, kPoint>(cx, child, rr, t, C2RT_CUBE_AWAY == 3 && k >= 2, 0)) break;
-#endif
             t.dist += cur;
             cur = t.dist;
             rr.o = t.p + d * 1e-6;
             if (n + k >= room) { cx.overflow = true; break; }
             ldist[(n + k) * kWave] = t.dist;
-#if C2RT_CSG_FIRST_HIT
             ltag[(n + k) * kWave] = csg_tag(t.code & (kCodeAxis | kCodeSide), side, k); /* the leaf IS the child: `side` names it */
-#else
-            ltag[(n + k) * kWave] = csg_tag(t.g, side, k);
-#endif
             ++k;
         }
         if (side == 0) nL = k; else nR = k;
@@ -769,9 +746,7 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
             wside = candL0 ? 0 : 1;
             wk = candR1 ? 1 : 0;
             wdist = candL0 ? L0 : (candR0 ? R0 : R1);
-#if C2RT_CSG_FIRST_HIT
             if (have) wcode = ltag[((wside ? nL : 0) + wk) * kWave] >> 4;
-#endif
         }
     }
     if (!regular) {
@@ -795,11 +770,7 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
         int win = -1;
         for (int i = 0; i < n; ++i) {
             const uint32_t tag = ltag[i * kWave];
-#if C2RT_CSG_FIRST_HIT
             const bool isL = (left == right) | (((tag >> 3) & 1u) == 0); /* `current.g is left`: the leaf is the child itself */
-#else
-            const bool isL = (int)(tag >> 4) == left;
-#endif
             inL ^= isL;
             inR ^= !isL;
             const bool in = type == C2RT_GEOM_CSG_UNION ? (inL | inR)
@@ -823,7 +794,6 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
     C2RT_REGION_BEGIN(cx, kRegReplay)
     const int child = wside ? right : left;
     Hit t;
-#if C2RT_CSG_FIRST_HIT
     /* The winner is its child's FIRST hit (a CsgUnion's and a CsgInter's always, a CsgDiff's when the left
      * child's entry point lies outside the right child): its record needs no replay.  The stepping loop met it
      * with the unmoved ray and cur = 0, so its distance is the primitive's own `mult` (mult + 0.0 == mult), its
@@ -834,9 +804,7 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
         t.p = ray.o + d * wdist;
         t.g = child;
         t.code = (int)wcode;
-    } else
-#endif
-    {
+    } else {
         ORay rr = ray;
         double cur = 0;
         for (int i = 0; i < wk; ++i) {
@@ -1781,7 +1749,7 @@ DEV F3 raytrace(const RenderParams &P, const Ctx &cx, D3 o, D3 raw, Counters &cn
     return shade<LEVELS, MLC, PO>(P, cx, mat, d, surf, cnt.shadow);
 }
 
-/* The first half of `trace` (rt/renderer.d:325-338) for a CALLER's ray (c2rt_trace_rays; c2rt_kernels.hip,
+/* The first half of `trace` (rt/renderer.d:325-338) for a CALLER's ray (c2rt_trace_rays; c2rt_rays.hip,
  * trace_rays_kernel): data.dist = 1e99, every node in file order, the last one that returns true is the closest.
  * Unlike raytrace() above, whose argument is the camera's un-normalised screen ray, the direction is used exactly
  * as given — the reference's trace() does not normalise either (Camera.getScreenRay has, by then), and Node.intersect
@@ -1834,9 +1802,6 @@ DEV F3 combine_stereo(F3 l, F3 r)
     return l * mkf(1, 0, 0) + r * mkf(0, 1, 1);
 }
 
-#ifndef C2RT_LENS_RELOAD
-#define C2RT_LENS_RELOAD 1
-#endif
 /* renderSample — rt/renderer.d:254-313 */
 template <int LEVELS, int DOF, bool MLC, int PO>
 DEV F3 render_sample(const RenderParams &P, const Ctx &cx, double x, double y, int dx, int dy, uint64_t pixel, uint32_t tap,
@@ -1862,15 +1827,11 @@ DEV F3 render_sample(const RenderParams &P, const Ctx &cx, double x, double y, i
         for (uint32_t i = 0; i < ns; ++i) {
             rng.sample = i;
             rng.dim = 0;
-#if C2RT_LENS_RELOAD
             /* as in render_tile's tap loop: what a lens sample reads of the kernel arguments is loaded inside
-             * the sample, not ahead of the loop */
+             * the sample, not ahead of the loop (reading `P` itself was a build switch up to commit f0eed4f) */
             KArgs Ks = cx.kargs;
             asm volatile("" : "+s"(Ks));
             const RenderParams &Ps = *(const RenderParams *)Ks;
-#else
-            const RenderParams &Ps = P;
-#endif
             for (int e = 0; e < eyes; ++e) {
                 double sx = x, sy = y;
                 if (dof) {
@@ -2016,18 +1977,10 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
          * to VGPR lanes that is a v_writelane per value and tile and a v_readlane per use.  Loaded where they
          * are used (scalar loads that hit the scalar cache) they die early: render_kernel_idn<1> holds 97
          * spill-lane instructions in its lean half instead of 191; lecture5.sdl 4K x5 0.986 -> 0.944 ms
-         * (profiles/r04_variants.md, step 14). */
-#ifndef C2RT_TAP_RELOAD
-#define C2RT_TAP_RELOAD 1
-#endif
-#if C2RT_TAP_RELOAD
+         * (profiles/r04_variants.md, step 14; reading `P` itself was a build switch up to commit f0eed4f). */
         KArgs Kt = K;
         asm volatile("" : "+s"(Kt));
         const RenderParams &Pt = *(const RenderParams *)Kt;
-#else
-        const RenderParams &Pt = P;
-#endif
-#if C2RT_TAP_RELOAD
         /* likewise the table pointers and scalars the tracer keeps in its context — in the instances without
          * nested CsgOps only: lecture5.sdl 1080p +1 %, 4K x5 -0.4 %; csg_stress.sdl (latency-bound, VALU busy
          * 0.64: more scalar loads to wait for) 8.06 -> 8.40 ms with it (step 15) */
@@ -2039,7 +1992,6 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
             cx.csg_cap = (int)Pt.csg_cap;
             cx.ground_y = Pt.ground_y;
         }
-#endif
         const F3 c = render_sample<LEVELS, DOF, MLC, PO>(Pt, cx, (double)sx + k_aa_x[s], (double)sy + k_aa_y[s], jdx, jdy, pixel, s, cnt, nullptr);
         accum = s == 0 ? c : accum + c;
     }

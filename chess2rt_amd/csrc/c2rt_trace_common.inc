@@ -1,0 +1,111 @@
+/*
+ * c2rt_trace_common.inc — what a device translation unit needs before it can write a kernel: the HIP runtime header and
+ * the device tables, the out-of-line libm wrappers, the register budget per instance (occ_of), the diagnostics knobs,
+ * the trace itself (c2rt_trace.inc) and the host helper that picks an instance by CSG depth.  Included once, at file
+ * scope, by the frame file (c2rt_kernels.hip: lean:: and exact::) and by the query files (c2rt_rays.hip,
+ * c2rt_hit_planes.hip, c2rt_adaptive.hip), which define C2RT_TRACE_EXACT_ONLY first: they run exact:: arithmetic only
+ * and need no lean:: copy of the trace (the emitted code is the same either way, and so is the compile time, about
+ * 25 s per query object: the unused copy is only parsed).
+ */
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "c2rt_device.h"
+#include "fp64_lean.h"
+#include "x87.h"
+
+namespace c2rt {
+namespace {
+
+#define DEV __device__ __forceinline__
+
+/* fp64 libm is only reached by a few lanes (sphere u,v, the Phong lobe,
+ * Procedure2) but, inlined, its ~70 live registers set the whole kernel's
+ * budget; as real calls the trace stays under 168 VGPRs without spills. */
+__device__ __noinline__ double c2_pow(double a, double b) { return pow(a, b); }
+__device__ __noinline__ double c2_atan2(double a, double b) { return atan2(a, b); }
+__device__ __noinline__ double c2_asin(double a) { return asin(a); }
+__device__ __noinline__ double c2_sin(double a) { return sin(a); }
+__device__ __noinline__ double c2_cos(double a) { return cos(a); }
+/* Sphere.intersect's u,v (rt/geometry.d:118-120) out of line as well: the x87 emulation (x87.h) is ~500 integer
+ * instructions with ~40 live registers, reached by textured sphere hits only; inlined (twice: lean:: and exact::)
+ * it was where the headline instance spilled. */
+struct UV { double u, v; };
+__device__ __noinline__ UV c2_sphere_uv(double dx, double dz, double w)
+{
+    constexpr double PI = 3.14159265358979323846;
+    const double angle = atan2(dz, dx);
+    const double as = asin(w);
+    UV r;
+    r.u = fabs(angle) <= 4.0 ? x87_sphere_u(angle) : (PI + angle) / (2 * PI);
+    r.v = fabs(as) <= 2.0 ? x87_sphere_v(as) : 1.0 - (PI / 2 + as) / PI;
+    return r;
+}
+/* Register budget per kernel instance, as waves per SIMD (512 VGPRs per lane and SIMD: 128 at 4 waves,
+ * 168 at 3, 256 at 2).  With no hint hipcc takes all 512 registers and runs one wave per SIMD (1.8x
+ * slower).  Chosen per instance from the compiler's resource remarks (`make resource-usage`; profiles/r04_resource_usage.md)
+ * so that NO instance spills VGPRs to scratch, except where a measurement says otherwise:
+ *   depth 0 (no CSG), planes-only: 4 waves (111-127 VGPRs);
+ *   depth 1, at most one light: 4 waves — 128 VGPRs since the cube / sphere face tables moved to the upload
+ *     and the hit's lighting terms are evaluated before the shadow test (was 149 at 3 waves);
+ *   depth 1, several lights (the hit stays live across the light loop) and depth-1 DOF: 3 waves (144-162);
+ *   depth 2 / 3 / 4: THREE waves (168 VGPRs) although they then spill (depth 4 multi-light: 136 VGPRs, 240 B of
+ *     scratch per lane; at two waves it needs 230 and spills none): a wave of these instances issues one
+ *     instruction at a time and a third of its instructions are scalar, so with two waves per SIMD the VALU idles
+ *     half the time (VALU busy 0.53) — the third wave is worth more than the spills cost: csg_stress.sdl cut to
+ *     depth 2 / 3 / 4: 2.33 -> 1.88, 4.60 -> 3.97, 10.21 -> 8.53 ms (scripts/depth_occupancy.sh; four waves:
+ *     2.59 / 5.48 / 10.5).  The hit stacks have to fit three workgroups per CU too: kCsgFirstCap, c2rt_device.h. */
+#ifndef C2RT_OCC_U1
+#define C2RT_OCC_U1 4
+#endif
+#ifndef C2RT_OCC_DEEP
+#define C2RT_OCC_DEEP 3
+#endif
+#ifndef C2RT_OCC_U2
+#define C2RT_OCC_U2 3
+#endif
+#ifndef C2RT_OCC_U3
+#define C2RT_OCC_U3 C2RT_OCC_DEEP
+#endif
+template <int LEVELS, int DOF, bool MLC>
+constexpr int occ_of()
+{
+#ifndef C2RT_OCC_U0
+#define C2RT_OCC_U0 4
+#endif
+    return LEVELS == 0 ? (DOF ? 4 : C2RT_OCC_U0) : (LEVELS == 1 ? ((DOF || MLC) ? 3 : C2RT_OCC_U1) : (LEVELS == 2 ? C2RT_OCC_U2 : (LEVELS == 3 ? C2RT_OCC_U3 : C2RT_OCC_DEEP)));
+}
+#define C2RT_OCC_OF(L, D, M) __attribute__((amdgpu_waves_per_eu(occ_of<L, D, M>(), occ_of<L, D, M>())))
+#ifndef C2RT_TILE_STATS
+#define C2RT_TILE_STATS 0 /* diagnostics: per-tile wave cycles + class (RenderParams::tile_stats) */
+#endif
+#ifndef C2RT_XCD_SWIZZLE
+#define C2RT_XCD_SWIZZLE 1
+#endif
+
+#ifndef C2RT_TRACE_EXACT_ONLY
+namespace lean {
+constexpr bool kLean = true;
+#include "c2rt_trace.inc"
+} // namespace lean
+#endif
+namespace exact {
+constexpr bool kLean = false;
+#include "c2rt_trace.inc"
+} // namespace exact
+
+typedef const RenderParams __attribute__((address_space(4))) *KArgs;
+
+/* The instance of a scene's CSG depth (KernelVariant::csg_levels, chosen at upload): f(std::integral_constant<int, L>)
+ * for L = levels, an error for a depth no instance was built for.  Host side. */
+template <int L = 0, class F>
+int for_csg_levels(int levels, F &&f)
+{
+    if (levels == L) return f(std::integral_constant<int, L>{});
+    if constexpr (L < C2RT_MAX_CSG_DEPTH) return for_csg_levels<L + 1>(levels, f);
+    else return (int)hipErrorInvalidValue;
+}
+
+} // namespace
+} // namespace c2rt

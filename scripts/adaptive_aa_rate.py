@@ -8,8 +8,8 @@ of the same camera, everything resident in HBM:
 Legs per case: the C2RT_TAPS_REF5 frame, the C2RT_TAPS_1 frame, the adaptive call; the flagged share of the mask is
 printed with them.  Every timed window holds at least --window-ms of work behind a settling phase and ends in a device
 sync; the legs are interleaved --rounds times and the median, minimum and maximum are printed.  The library variant under
-test is the one C2RT_LIB_VARIANT names: the default build packs the refinement's work items into lanes, `make
-VARIANT=aaplain EXTRA_KERNEL_FLAGS=-DC2RT_AA_PACKED=0` builds the plain refinement kernel (profiles/adaptive_aa.md).
+test is the one C2RT_LIB_VARIANT names (the plain refinement kernel the packed one was measured against,
+profiles/adaptive_aa.md, is no longer built).
 
   python scripts/adaptive_aa_rate.py [--rounds 5] [--json out.json]
   python scripts/adaptive_aa_rate.py --once          one adaptive call per case and nothing else (under rocprofv3

@@ -3,7 +3,8 @@
 statement each instruction was generated from (the most recent `.loc` line of a -gline-tables-only build; the
 whole trace is inlined into the kernel, so the line's enclosing function in c2rt_kernels.hip names the region).
 
-usage: isa_census.py <unit> <mangled-name-substring> [lean|exact]
+usage: isa_census.py <unit> <mangled-name-substring> [lean|exact]      unit: 0..5 (c2rt_kernels.hip), or rays / hit_planes /
+                                                                    adaptive (the query file c2rt_<unit>.hip)
 The production instances hold the trace twice (c2rt_trace.inc: lean:: first, then — after the atomic that counts a
 redo — exact::); `lean` / `exact` restricts the census to that half.
 Builds build/isa/u<unit>g.s with the Makefile's flags + -gline-tables-only (code generation is unchanged).
@@ -22,7 +23,7 @@ TRACE = os.path.join(ROOT, "chess2rt_amd/csrc/c2rt_trace.inc")
 def make_flags():
     flags = {}
     for line in open(os.path.join(ROOT, "Makefile")):
-        m = re.match(r"^(FPFLAGS|KERNELFLAGS|KERNELFLAGS_u\d)\s*:=\s*(.*)$", line)
+        m = re.match(r"^(FPFLAGS|KERNELFLAGS|KERNELFLAGS_u\d|KERNELFLAGS_QUERY)\s*:=\s*(.*)$", line)
         if m:
             flags[m.group(1)] = m.group(2).strip()
     return flags
@@ -96,14 +97,16 @@ def main():
     flags = make_flags()
     out = os.path.join(ROOT, "build", "isa", "u%sg.s" % unit)
     os.makedirs(os.path.dirname(out), exist_ok=True)
+    query = not unit.isdigit()
+    src = os.path.join(os.path.dirname(SRC), "c2rt_%s.hip" % unit) if query else SRC
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + flags["FPFLAGS"].split() + \
-          ["-fhip-fp32-correctly-rounded-divide-sqrt"] + flags["KERNELFLAGS"].split() + flags.get("KERNELFLAGS_u%s" % unit, "").split() + \
-          ["-DC2RT_UNIT=%s" % unit, "-gline-tables-only", "--offload-device-only", "-S", SRC, "-o", out, "-I" + os.path.join(ROOT, "include")]
+          ["-fhip-fp32-correctly-rounded-divide-sqrt"] + flags["KERNELFLAGS"].split() + flags.get("KERNELFLAGS_QUERY" if query else "KERNELFLAGS_u%s" % unit, "").split() + \
+          ([] if query else ["-DC2RT_UNIT=%s" % unit]) + ["-gline-tables-only", "--offload-device-only", "-S", src, "-o", out, "-I" + os.path.join(ROOT, "include")]
     csrc = os.path.dirname(SRC)
     newest = max(os.path.getmtime(os.path.join(csrc, f)) for f in os.listdir(csrc) if f.endswith(('.hip', '.inc', '.h')))
     if not os.path.exists(out) or os.path.getmtime(out) < newest:
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-    spans = {"c2rt_kernels.hip": function_spans(SRC), "c2rt_trace.inc": function_spans(TRACE)}
+    spans = {os.path.basename(p): function_spans(p) for p in (src, TRACE, os.path.join(csrc, "c2rt_query.inc"), os.path.join(csrc, "c2rt_trace_common.inc"))}
 
     files = {}
     for raw in open(out):
@@ -124,7 +127,7 @@ def main():
                 return fn
         if name == "c2rt_trace.inc":
             return "vector helpers (D3 / F3 operators, dot, sqmag)" if line < 140 else "(file scope)"
-        return "kernel entry (c2rt_kernels.hip)"
+        return "kernel entry (%s)" % name
 
     per_region = collections.defaultdict(collections.Counter)
     total = collections.Counter()

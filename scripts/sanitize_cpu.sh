@@ -11,7 +11,7 @@ gcc $SAN -std=gnu11 -fPIC -shared -o $T/oracle.so oracle/c2rt_oracle.c -lm -lpth
 for f in chess2rt_amd/csrc/c2rt_api.cpp chess2rt_amd/csrc/host/dsc.cpp chess2rt_amd/csrc/host/scene.cpp chess2rt_amd/csrc/host/host_api.cpp; do
   g++ $SAN -std=c++17 -fPIC -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -c $f -o $T/$(basename $f .cpp).o
 done
-hipcc --offload-arch=gfx950 -shared -fPIC -o chess2rt_amd/libc2rt_san.so build/c2rt_kernels_u*.o $T/*.o -lpthread
+hipcc --offload-arch=gfx950 -shared -fPIC -o chess2rt_amd/libc2rt_san.so build/c2rt_kernels_u*.o build/c2rt_rays.o build/c2rt_hit_planes.o build/c2rt_adaptive.o $T/*.o -lpthread
 cp oracle/libc2rt_oracle.so $T/orig.so
 trap 'cp $T/orig.so oracle/libc2rt_oracle.so; rm -f chess2rt_amd/libc2rt_san.so' EXIT
 cp $T/oracle.so oracle/libc2rt_oracle.so
