@@ -83,6 +83,18 @@ size_t c2rt_plan_facts(const void *plan, PlanFacts *out, uint8_t *node_boxed, si
     return sizeof *out;
 }
 
+/* one node of the plan: its DevNode flags (c2rt_device.h), whether plan_world_boxes boxed it and the eight world corners
+ * of its padded box; 0 when n is out of range */
+int c2rt_plan_node(const void *plan, uint32_t n, uint32_t *flags, uint8_t *boxed, double corners[24])
+{
+    const ScenePlan &p = *static_cast<const ScenePlan *>(plan);
+    if (n >= p.nodes.size()) return 0;
+    *flags = p.nodes[n].flags;
+    *boxed = p.node_boxed[n];
+    std::memcpy(corners, &p.node_box[(size_t)n * 24], 24 * sizeof(double));
+    return 1;
+}
+
 /* the frame as the library plans it: check_frame, fill_params under C2RT_DEBUG_CULL = debug_cull, and the VoidCull /
  * SphereCull of the pre-pass with every flags word ANDed with void_mask / sphere_mask */
 size_t c2rt_plan_frame(const void *plan, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, int debug_cull,
