@@ -61,7 +61,7 @@ HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/
 # over the SAME kernel objects; tests and scripts that need a hook load it with C2RT_LIB_VARIANT=diag
 DIAGNAME   := chess2rt_amd/libc2rt_diag.so
 
-all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so
+all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so
 
 $(BUILD):
 	mkdir -p $(BUILD)
@@ -110,6 +110,11 @@ tests/libsphere_cull_check.so: tests/sphere_cull_check.cpp $(CSRC)/csg_void.h
 tests/libscene_plan_check.so: tests/scene_plan_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/scene_plan_check.cpp $(CSRC)/scene_plan.cpp
 
+# host build of the pose-and-replan step behind c2rt_update_scene and c2rt_render_frames_posed (tests/test_scene_update_plan.py),
+# without ROCm like the planner's: what it drives is scene_plan.cpp's own update_scene_plan, not a copy of it
+tests/libscene_update_check.so: tests/scene_update_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h
+	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/scene_update_check.cpp $(CSRC)/scene_plan.cpp
+
 # CPU oracle: plain C restatement of the reference algorithm (tests only)
 oracle/libc2rt_oracle.so: oracle/c2rt_oracle.c oracle/c2rt_oracle.h include/c2rt.h
 	$(CC) -O2 -std=gnu11 -fPIC -shared $(FPFLAGS) -Wall -o $@ oracle/c2rt_oracle.c -lm -lpthread
@@ -127,6 +132,6 @@ resource-usage: | $(BUILD)
 	    -c $(CSRC)/$(q).hip -o $(BUILD)/ru_$(q).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
 
 clean:
-	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so
+	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so
 
 .PHONY: all clean resource-usage

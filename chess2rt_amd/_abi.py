@@ -153,6 +153,20 @@ class HitPlanes(C.Structure):
     ]
 
 
+class ScenePose(C.Structure):
+    """c2rt_scene_pose: new transforms ([n_nodes][30] doubles) and light values for some nodes / lights of the uploaded scene"""
+    _fields_ = [
+        ("n_nodes", C.c_uint32),
+        ("node_index", _u32p),
+        ("node_transform", _f64p),
+        ("n_lights", C.c_uint32),
+        ("light_index", _u32p),
+        ("light_pos", _f64p),
+        ("light_color", _f32p),
+        ("light_power", _f32p),
+    ]
+
+
 class RayStats(C.Structure):
     _fields_ = [("primary_rays", C.c_uint64), ("shadow_rays", C.c_uint64)]
 
@@ -188,6 +202,7 @@ class HostCamera(C.Structure):
 _SCENE_P = C.POINTER(SceneDesc)
 _CAM_P = C.POINTER(CameraFrame)
 _OPTS_P = C.POINTER(RenderOpts)
+_POSE_P = C.POINTER(ScenePose)
 _VP = C.c_void_p
 
 # every symbol include/c2rt.h declares: name -> (restype, argtypes)
@@ -203,11 +218,14 @@ C2RT_SYMBOLS = {
     "c2rt_status_string": (C.c_char_p, [C.c_int]),
     "c2rt_abi_version": (C.c_uint32, []),
     "c2rt_upload_scene": (C.c_int, [_VP, _SCENE_P]),
+    "c2rt_update_scene": (C.c_int, [_VP, _POSE_P, _VP]),
     "c2rt_local_rows": (C.c_uint32, [_OPTS_P]),
     "c2rt_render_frame": (C.c_int, [_VP, _CAM_P, _OPTS_P, _VP, _VP]),
     "c2rt_render_frame_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, _VP, _VP]),
     "c2rt_render_frames": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, _VP, _VP]),
     "c2rt_render_frames_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, _VP, _VP]),
+    "c2rt_render_frames_posed": (C.c_int, [_VP, _CAM_P, _POSE_P, C.c_uint32, _OPTS_P, _VP, _VP]),
+    "c2rt_render_frames_posed_device": (C.c_int, [_VP, _CAM_P, _POSE_P, C.c_uint32, _OPTS_P, _VP, _VP]),
     "c2rt_pin_host_buffer": (C.c_int, [_VP, _VP, C.c_size_t]),
     "c2rt_unpin_host_buffer": (C.c_int, [_VP, _VP]),
     "c2rt_get_ray_stats": (C.c_int, [_VP, C.POINTER(RayStats)]),
@@ -252,6 +270,15 @@ C2RT_HOST_SYMBOLS = {
     "c2rt_host_bmp_encode": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),
     "c2rt_host_color_to_rgb32": (C.c_uint32, [_f32p]),
     "c2rt_host_free": (None, [_VP]),
+    "c2rt_host_scene_node_index": (C.c_int, [_VP, C.c_char_p]),
+    "c2rt_host_scene_light_index": (C.c_int, [_VP, C.c_char_p]),
+    "c2rt_host_node_transform_get": (C.c_int, [_VP, C.c_char_p, _f64p]),
+    "c2rt_host_node_transform_set": (C.c_int, [_VP, _VP, C.c_char_p, _f64p]),
+    "c2rt_host_node_transform_reset": (C.c_int, [_VP, _VP, C.c_char_p]),
+    "c2rt_host_node_transform_scale": (C.c_int, [_VP, _VP, C.c_char_p, C.c_double, C.c_double, C.c_double]),
+    "c2rt_host_node_transform_rotate": (C.c_int, [_VP, _VP, C.c_char_p, C.c_double, C.c_double, C.c_double]),
+    "c2rt_host_node_transform_translate": (C.c_int, [_VP, _VP, C.c_char_p, _f64p]),
+    "c2rt_host_light_set": (C.c_int, [_VP, _VP, C.c_char_p, _f64p, _f32p, _f32p]),
     "c2rt_host_transform_reset": (None, [_f64p]),
     "c2rt_host_transform_scale": (None, [_f64p, C.c_double, C.c_double, C.c_double]),
     "c2rt_host_transform_rotate": (None, [_f64p, C.c_double, C.c_double, C.c_double]),

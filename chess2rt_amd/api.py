@@ -12,7 +12,8 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (CameraFrame, HitPlanes, HostCamera, HostSettings, Ray, RayHit, RayStats, RenderOpts, SceneDesc, Segment, TraceResult)
+from ._abi import (CameraFrame, HitPlanes, HostCamera, HostSettings, Ray, RayHit, RayStats, RenderOpts, SceneDesc, ScenePose, Segment,
+                   TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
 RAY_HIT_DTYPE = np.dtype({
@@ -41,6 +42,39 @@ def _new_hit_planes(names, rows, width):
         out[n] = np.empty((rows, width) if comps == 1 else (rows, width, comps), dtype=dtype)
         setattr(pl, n, out[n].ctypes.data)
     return pl, out
+
+
+def makePose(nodes=None, lights=None):
+    """c2rt_scene_pose from ``nodes = {index: transform}`` (30 doubles each, the layout of SceneDesc.node_transform:
+    transform, inverseTransform, transposedInverse, offset) and ``lights = {index: dict(pos=, color=, power=)}``.  The
+    light arrays of a pose are per pose, not per light: every light listed gives the same keys.  Entries keep the
+    order of the dicts.  The arrays live as long as the ScenePose returned."""
+    nodes, lights = dict(nodes or {}), dict(lights or {})
+    pose = ScenePose()
+    keep = []
+    if nodes:
+        idx = np.array(list(nodes), dtype=np.uint32)
+        xf = np.ascontiguousarray([np.asarray(t, dtype=np.float64).reshape(30) for t in nodes.values()])
+        pose.n_nodes = len(idx)
+        pose.node_index = idx.ctypes.data_as(_abi._u32p)
+        pose.node_transform = xf.ctypes.data_as(_abi._f64p)
+        keep += [idx, xf]
+    if lights:
+        keys = {tuple(sorted(v)) for v in lights.values()}
+        if len(keys) != 1 or not set(next(iter(keys))) <= {"pos", "color", "power"}:
+            raise ValueError("lights: every entry gives the same keys out of pos, color, power")
+        idx = np.array(list(lights), dtype=np.uint32)
+        pose.n_lights = len(idx)
+        pose.light_index = idx.ctypes.data_as(_abi._u32p)
+        keep.append(idx)
+        for key, field, dtype, ptr in (("pos", "light_pos", np.float64, _abi._f64p), ("color", "light_color", np.float32, _abi._f32p),
+                                       ("power", "light_power", np.float32, _abi._f32p)):
+            if key in next(iter(keys)):
+                a = np.ascontiguousarray([np.asarray(v[key], dtype=dtype).reshape(-1) for v in lights.values()])
+                setattr(pose, field, a.ctypes.data_as(ptr))
+                keep.append(a)
+    pose._keep = keep
+    return pose
 
 
 class C2rtError(RuntimeError):
@@ -116,6 +150,64 @@ class Scene:
 
     def rotateCamera(self, dyaw, droll, dpitch):
         self._lib.c2rt_host_camera_rotate(self._h, dyaw, droll, dpitch)
+
+    def nodeIndex(self, name):
+        """index of the named node in the flat tables (and in a c2rt_scene_pose); -1: no such node"""
+        return int(self._lib.c2rt_host_scene_node_index(self._h, name.encode()))
+
+    def lightIndex(self, name):
+        return int(self._lib.c2rt_host_scene_light_index(self._h, name.encode()))
+
+    def nodeTransform(self, name):
+        """the named node's Transform as 30 doubles (transform, inverseTransform, transposedInverse, offset): edit it with
+        the c2rt_host_transform_* calls (rt/transform.d's scale / rotate / translate / reset) and hand it back"""
+        t = np.empty(30, dtype=np.float64)
+        if self._lib.c2rt_host_node_transform_get(self._h, name.encode(), t.ctypes.data_as(_abi._f64p)) != _abi.OK:
+            raise KeyError(name)
+        return t
+
+    def setNodeTransform(self, name, transform, ctx=None):
+        """Sets the named node's Transform on the host object; with `ctx`, and if that context still holds this scene's
+        upload, also pushes the change to it (one c2rt_update_scene, on the default stream); otherwise the next render
+        through a Renderer re-uploads."""
+        t = np.ascontiguousarray(transform, dtype=np.float64).reshape(30)
+        st = self._lib.c2rt_host_node_transform_set(ctx.handle if ctx is not None else None, self._h, name.encode(),
+                                                          t.ctypes.data_as(_abi._f64p))
+        if st != _abi.OK:
+            raise C2rtError(st, ctx._lib.c2rt_last_error(ctx.handle).decode(errors="replace") if ctx is not None and st != _abi.ERR_INVALID_ARG
+                            else "no node named %r" % name)
+
+    def _node_verb(self, fn, name, ctx, *args):
+        st = fn(ctx.handle if ctx is not None else None, self._h, name.encode(), *args)
+        if st != _abi.OK:
+            raise C2rtError(st, ctx._lib.c2rt_last_error(ctx.handle).decode(errors="replace") if ctx is not None and st != _abi.ERR_INVALID_ARG
+                            else "no node named %r" % name)
+
+    def resetNode(self, name, ctx=None):
+        """Transform.reset (rt/transform.d:24-29) on the named node; `ctx` as in setNodeTransform"""
+        self._node_verb(self._lib.c2rt_host_node_transform_reset, name, ctx)
+
+    def scaleNode(self, name, x, y, z, ctx=None):
+        self._node_verb(self._lib.c2rt_host_node_transform_scale, name, ctx, x, y, z)
+
+    def rotateNode(self, name, yaw, pitch, roll, ctx=None):
+        self._node_verb(self._lib.c2rt_host_node_transform_rotate, name, ctx, yaw, pitch, roll)
+
+    def translateNode(self, name, v, ctx=None):
+        self._node_verb(self._lib.c2rt_host_node_transform_translate, name, ctx, (C.c_double * 3)(*v))
+
+    def setLight(self, name, pos=None, color=None, power=None, ctx=None):
+        """Sets the named light's position, colour and power (None: unchanged); `ctx` as in setNodeTransform."""
+        p = np.ascontiguousarray(pos, dtype=np.float64).reshape(3) if pos is not None else None
+        c = np.ascontiguousarray(color, dtype=np.float32).reshape(3) if color is not None else None
+        w = np.array([power], dtype=np.float32) if power is not None else None
+        st = self._lib.c2rt_host_light_set(ctx.handle if ctx is not None else None, self._h, name.encode(),
+                                                 p.ctypes.data_as(_abi._f64p) if p is not None else None,
+                                                 c.ctypes.data_as(_abi._f32p) if c is not None else None,
+                                                 w.ctypes.data_as(_abi._f32p) if w is not None else None)
+        if st != _abi.OK:
+            raise C2rtError(st, ctx._lib.c2rt_last_error(ctx.handle).decode(errors="replace") if ctx is not None and st != _abi.ERR_INVALID_ARG
+                            else "no light named %r" % name)
 
     def renderOpts(self, **kw):
         s = self.settings
@@ -195,6 +287,47 @@ class Context:
         if isinstance(desc, SceneDesc):
             desc = C.pointer(desc)
         self._check(self._lib.c2rt_upload_scene(self._h, desc))
+
+    def updateScene(self, nodes=None, lights=None, stream=None):
+        """Moves nodes and lights of the uploaded scene without re-uploading it (c2rt_update_scene): ``nodes = {index:
+        transform}`` (30 doubles, see makePose), ``lights = {index: dict(pos=, color=, power=)}``.  The table copies are
+        ordered on `stream` (None: the default stream): frames enqueued there before the call see the old scene, frames
+        after it the new one, with no sync in between.  The context then behaves as after a fresh upload of the patched
+        description; sceneGeneration does not change."""
+        self.updateScenePose(makePose(nodes, lights), stream)
+
+    def updateScenePose(self, pose, stream=None):
+        self._check(self._lib.c2rt_update_scene(self._h, C.byref(pose), C.c_void_p(stream or None)))
+
+    @staticmethod
+    def _pose_array(poses):
+        """(contiguous ctypes array, count, what keeps its arrays alive) of a sequence of ScenePose or (nodes, lights) pairs"""
+        if isinstance(poses, C.Array):
+            return poses, len(poses), None
+        poses = [p if isinstance(p, ScenePose) else makePose(*p) for p in poses]
+        return (ScenePose * max(len(poses), 1))(*poses), len(poses), poses
+
+    def renderFramesPosed(self, cams, poses, opts, stop_flag=None):
+        """An animation in one call (c2rt_render_frames_posed): frame i is the current scene with poses[i] applied — a
+        ScenePose or a (nodes, lights) pair as for updateScene, each relative to the current scene — seen through
+        cams[i]: the bits of updateScene(poses[i]) + renderFrame(cams[i]).  The context's scene is unchanged.  A new
+        host array of shape (len(cams), local_rows, W, 3)."""
+        arr, n = self._camera_array(cams)
+        parr, np_, keep = self._pose_array(poses)
+        if np_ != n:
+            raise ValueError("%d cameras, %d poses" % (n, np_))
+        out = np.empty((n, self.localRows(opts), opts.width, 3), dtype=np.float32)
+        stop = stop_flag.ctypes.data_as(C.c_void_p) if stop_flag is not None else None
+        self._check(self._lib.c2rt_render_frames_posed(self._h, arr, parr, n, C.byref(opts), out.ctypes.data_as(C.c_void_p), stop))
+        return out
+
+    def renderFramesPosedDevice(self, cams, poses, opts, out_ptr, stream=0):
+        """Enqueue the posed batch into device memory (len(cams) * local_rows * W * 3 floats at out_ptr) on `stream`."""
+        arr, n = self._camera_array(cams)
+        parr, np_, keep = self._pose_array(poses)
+        if np_ != n:
+            raise ValueError("%d cameras, %d poses" % (n, np_))
+        self._check(self._lib.c2rt_render_frames_posed_device(self._h, arr, parr, n, C.byref(opts), C.c_void_p(out_ptr), C.c_void_p(stream)))
 
     def localRows(self, opts):
         return int(self._lib.c2rt_local_rows(C.byref(opts)))

@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -45,7 +46,8 @@ struct FrameScratch {
     uint32_t *retry_list = nullptr; /* RenderParams::retry_list: [0] count, then tile (block) indices */
     size_t retry_words = 0;
     /* batches: one RenderParams per frame (twice for nested CSG: first pass, retry pass), then one BatchCull per
-     * frame; uploaded per call with one stream-ordered copy from ctx->batch_host */
+     * frame, then (c2rt_render_frames_posed) the node, light and shadow-rectangle tables of the frames whose pose
+     * changes them; uploaded per call with one stream-ordered copy from ctx->batch_host */
     char *batch_table = nullptr;
     size_t batch_bytes = 0;
 };
@@ -97,6 +99,7 @@ struct c2rt_ctx {
 
     bool has_scene = false;
     ScenePlan plan;                /* the uploaded scene (scene_plan.h); meaningful while has_scene */
+    SceneCopy scene;               /* its description without the texels: what c2rt_update_scene patches and plans again */
     DeviceTables dev;              /* where its tables live on this device */
     uint32_t sphere_flags_mask = ~0u; /* ANDed into every SphereNode::flags (diagnostics: c2rt_debug_sphere_cull) */
 
@@ -237,14 +240,15 @@ void frame_needs(RenderParams &p, size_t &entries, size_t &blocks)
 }
 
 /* Wires frame i of the frames that share scratch slot `sc` (a single frame: i = 0; a batch: n tables and lists side by
- * side, frame_needs of any of them) into its filled parameter block: first-pass stack capacity, redo counter, mask
+ * side, frame_needs of any of them; `plan`: the frame's scene, the context's own unless the frame is posed) into its
+ * filled parameter block: first-pass stack capacity, redo counter, mask
  * table over the local rows [row_offset, row_offset + local_rows), retry list.  cull: the tests its pre-pass is given
  * (void_flags_mask: ANDed into every VoidNode::flags, ~0u for frames; the context's sphere_flags_mask likewise).
  * This is the one place a frame's launch state is decided: batch frame i gets the bits of the single-frame call. */
-void wire_frame(const c2rt_ctx *ctx, RenderParams &p, const FrameScratch &sc, size_t i, size_t entries, size_t blocks,
-                uint32_t void_flags_mask, BatchCull &cull)
+void wire_frame(const c2rt_ctx *ctx, const ScenePlan &plan, RenderParams &p, const FrameScratch &sc, size_t i, size_t entries,
+                size_t blocks, uint32_t void_flags_mask, BatchCull &cull)
 {
-    const int levels = ctx->plan.csg_levels;
+    const int levels = plan.csg_levels;
     p.csg_cap = levels == 0 ? 0u : (uint32_t)first_cap(levels, diag_knobs());
     p.retry_mode = 0;
     p.redo_counter = ctx->counters + 3;
@@ -253,8 +257,8 @@ void wire_frame(const c2rt_ctx *ctx, RenderParams &p, const FrameScratch &sc, si
     const bool masks = entries && p.n_cull;
     p.tile_masks = masks ? sc.tile_masks + i * entries * 8 : nullptr;
     p.mask_entries = masks ? (uint32_t)entries : 0u;
-    cull.v = void_cull_of(ctx->plan, p, void_flags_mask);
-    cull.s = sphere_cull_of(ctx->plan, diag_knobs(), p, ctx->sphere_flags_mask);
+    cull.v = void_cull_of(plan, p, void_flags_mask);
+    cull.s = sphere_cull_of(plan, diag_knobs(), p, ctx->sphere_flags_mask);
     if (levels >= 2) {
         p.retry_list = sc.retry_list + i * (blocks + 1);
         p.retry_max = (uint32_t)blocks;
@@ -275,7 +279,7 @@ int prepare_frame(c2rt_ctx *ctx, RenderParams &p, hipStream_t stream, uint32_t v
     if (e == hipSuccess && nested) e = grow_scratch(&sc.retry_list, &sc.retry_words, blocks + 1, sizeof(uint32_t));
     if (e != hipSuccess) return (int)e;
     BatchCull cull;
-    wire_frame(ctx, p, sc, 0, entries, blocks, void_flags_mask, cull);
+    wire_frame(ctx, ctx->plan, p, sc, 0, entries, blocks, void_flags_mask, cull);
     if (cull_out) *cull_out = cull;
     return entries ? launch_tile_masks(p, cull.v, cull.s, sc.tile_masks, stream) : 0;
 }
@@ -345,33 +349,104 @@ int check_batch_args(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_fr
     return C2RT_OK;
 }
 
-/* n_frames frames of one scene under one set of options with one mask pre-pass launch and one frame launch (two for
+/* A frame of a posed batch (c2rt_render_frames_posed): its scene as planned for its pose, and which of its three
+ * posable tables differ from the context's and therefore travel with the batch. */
+struct PosedFrame {
+    ScenePlan plan;
+    bool own_nodes = false, own_lights = false, own_rects = false;
+};
+
+template <typename T>
+bool same_bytes(const std::vector<T> &a, const std::vector<T> &b)
+{
+    return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
+}
+
+size_t align16(size_t b) { return (b + 15u) & ~(size_t)15u; }
+
+/* Plans frame i of a posed batch for every i: ctx->scene under poses[i], put back afterwards.  posed[i] stays null for
+ * a frame of the scene as it is.  The poses have passed check_scene_pose. */
+int plan_posed_frames(c2rt_ctx *ctx, const c2rt_scene_pose *poses, uint32_t n_frames, std::vector<std::unique_ptr<PosedFrame>> &posed)
+{
+    posed.resize(n_frames);
+    PoseUndo undo;
+    for (uint32_t i = 0; i < n_frames; ++i) {
+        if (poses[i].n_nodes == 0 && poses[i].n_lights == 0) continue;
+        std::unique_ptr<PosedFrame> f(new PosedFrame());
+        std::string err;
+        pose_scene(ctx->scene, &poses[i], undo);
+        const int st = replan_scene(ctx->scene, f->plan, err);
+        unpose_scene(ctx->scene, &poses[i], undo);
+        if (st != C2RT_OK) return fail(ctx, st, "frame %u: %s", i, err.c_str());
+        f->own_nodes = !same_bytes(f->plan.nodes, ctx->plan.nodes);
+        f->own_lights = !same_bytes(f->plan.lights, ctx->plan.lights);
+        f->own_rects = !same_bytes(f->plan.shadow_rects, ctx->plan.shadow_rects);
+        posed[i] = std::move(f);
+    }
+    return C2RT_OK;
+}
+
+/* n_frames frames under one set of options with one mask pre-pass launch and one frame launch (two for
  * nested CSG), frame i into out_dev + i * local_rows * width * 3: the n-frame case of wire_frame, launched through the
  * table kernels.  Each frame's parameter block is what render_device
  * would launch it with — its own culling rectangles, row rotation, exact switch, mask table, retry list and output —
  * so the frames hold the bits of n single-frame calls; the kernels read block blockIdx.y of the table in HBM.
- * The arguments have passed check_batch_args. */
-int render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
-                         float *out_dev, hipStream_t stream)
+ * The arguments have passed check_batch_args.
+ *
+ * posed (nullable; c2rt_render_frames_posed): frame i's own scene where posed[i] is set — its block is planned from
+ * that plan and names the copies of its changed tables behind the BatchCulls, in the same allocation and the same
+ * copy.  One launch runs one instance: the frames are laid out in the table as up to two groups by what the launcher
+ * cannot share — the plane instances of a single-light scene (launch_render_batch_level) — and a group that mixes
+ * identity-only frames with others runs the general instance (the launcher's copy of a block says so; the instances
+ * are held to the same bits, C2RT_NO_IDN). */
+int render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const std::vector<std::unique_ptr<PosedFrame>> *posed,
+                         uint32_t n_frames, const c2rt_render_opts *opts, float *out_dev, hipStream_t stream)
 {
-    const int levels = ctx->plan.csg_levels;
+    const int levels = ctx->plan.csg_levels; /* geometries are not posed: the same for every frame */
     const KernelVariant variant = variant_of(ctx->plan, &cams[0]);
     const bool nested = levels >= 2;
     const bool retry = nested && first_cap(levels, diag_knobs()) < kCsgFullCap(levels);
+    const auto plan_of = [&](size_t i) -> const ScenePlan & { return posed && (*posed)[i] ? (*posed)[i]->plan : ctx->plan; };
+    const auto plane_instance = [&](size_t i) { return plan_of(i).planes_only && plan_of(i).n_lights <= 1; };
 
-    const size_t n = n_frames, n_blocks_tables = retry ? 2 * n : n;
-    const size_t culls_at = n_blocks_tables * sizeof(RenderParams), bytes = culls_at + n * sizeof(BatchCull);
+    /* table order: the frames that share frame 0's instance first, then the others */
+    const size_t n = n_frames;
+    std::vector<uint32_t> order;
+    order.reserve(n);
+    for (uint32_t i = 0; i < n_frames; ++i)
+        if (plane_instance(i) == plane_instance(0)) order.push_back(i);
+    const size_t n_first = order.size();
+    for (uint32_t i = 0; i < n_frames; ++i)
+        if (plane_instance(i) != plane_instance(0)) order.push_back(i);
+
+    const size_t n_blocks_tables = retry ? 2 * n : n;
+    const size_t culls_at = n_blocks_tables * sizeof(RenderParams);
+    size_t bytes = culls_at + n * sizeof(BatchCull);
     static_assert(sizeof(RenderParams) % 8 == 0 && alignof(BatchCull) <= 8, "BatchCull follows the parameter blocks");
+    const size_t posed_at = align16(bytes);
+    if (posed) {
+        bytes = posed_at;
+        for (size_t i = 0; i < n; ++i)
+            if (const PosedFrame *f = (*posed)[i].get())
+                bytes += (f->own_nodes ? align16(f->plan.nodes.size() * sizeof(DevNode)) : 0) +
+                         (f->own_lights ? align16(f->plan.lights.size() * sizeof(DevLight)) : 0) +
+                         (f->own_rects ? align16(f->plan.shadow_rects.size() * sizeof(double)) : 0);
+    }
     ctx->batch_host.resize(bytes);
     RenderParams *hp = reinterpret_cast<RenderParams *>(ctx->batch_host.data());
     BatchCull *hc = reinterpret_cast<BatchCull *>(ctx->batch_host.data() + culls_at);
 
-    for (size_t i = 0; i < n; ++i) frame_params(ctx, &cams[i], opts, hp[i]);
-    const RenderParams &p0 = hp[0];
-    if (p0.local_rows == 0) return C2RT_OK;
-    const size_t frame_floats = (size_t)p0.local_rows * p0.width * 3;
-    size_t entries, blocks; /* the same for every frame: one scene, one set of options, no depth of field */
-    frame_needs(hp[0], entries, blocks);
+    for (size_t j = 0; j < n; ++j) fill_params(plan_of(order[j]), ctx->dev, diag_knobs(), &cams[order[j]], opts, hp[j]);
+    if (hp[0].local_rows == 0) return C2RT_OK;
+    const size_t frame_floats = (size_t)hp[0].local_rows * hp[0].width * 3;
+    /* the same for every frame with culling rectangles (one set of options, no depth of field); a posed frame may
+     * have none where others do */
+    size_t entries = 0, blocks = 0;
+    for (size_t j = 0; j < n; ++j) {
+        size_t e;
+        frame_needs(hp[j], e, blocks);
+        if (e > entries) entries = e;
+    }
     const bool any_masks = entries != 0;
 
     FrameScratch &sc = scratch_for(ctx, stream);
@@ -380,26 +455,85 @@ int render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t 
     if (e == hipSuccess && nested) e = grow_scratch(&sc.retry_list, &sc.retry_words, (blocks + 1) * n, sizeof(uint32_t));
     if (e != hipSuccess) return fail(ctx, C2RT_ERR_HIP, "batch scratch: %s", hipGetErrorString(e));
 
-    for (size_t i = 0; i < n; ++i) {
-        RenderParams &p = hp[i];
+    size_t at = posed_at;
+    /* one of a posed frame's own tables: into the host image, its device address into the frame's block */
+    const auto place = [&](const void *src, size_t table_bytes) {
+        std::memcpy(ctx->batch_host.data() + at, src, table_bytes);
+        const char *dev = sc.batch_table + at;
+        at += align16(table_bytes);
+        return dev;
+    };
+    for (size_t j = 0; j < n; ++j) {
+        const size_t i = order[j];
+        RenderParams &p = hp[j];
+        if (const PosedFrame *f = posed ? (*posed)[i].get() : nullptr) {
+            if (f->own_nodes) p.nodes = reinterpret_cast<const DevNode *>(place(f->plan.nodes.data(), f->plan.nodes.size() * sizeof(DevNode)));
+            if (f->own_lights) p.lights = reinterpret_cast<const DevLight *>(place(f->plan.lights.data(), f->plan.lights.size() * sizeof(DevLight)));
+            if (f->own_rects) p.shadow_rects = reinterpret_cast<const double *>(place(f->plan.shadow_rects.data(), f->plan.shadow_rects.size() * sizeof(double)));
+        }
         p.out = out_dev + i * frame_floats;
-        wire_frame(ctx, p, sc, i, entries, blocks, ~0u, hc[i]);
+        wire_frame(ctx, plan_of(i), p, sc, j, entries, blocks, ~0u, hc[j]);
         if (retry) {
-            hp[n + i] = p;
-            hp[n + i].retry_mode = 1;
-            hp[n + i].csg_cap = (uint32_t)kCsgFullCap(levels);
+            hp[n + j] = p;
+            hp[n + j].retry_mode = 1;
+            hp[n + j].csg_cap = (uint32_t)kCsgFullCap(levels);
         }
     }
     const RenderParams *table_dev = reinterpret_cast<const RenderParams *>(sc.batch_table);
     const BatchCull *culls_dev = reinterpret_cast<const BatchCull *>(sc.batch_table + culls_at);
     HIP_TRY(ctx, hipMemcpyAsync(sc.batch_table, ctx->batch_host.data(), bytes, hipMemcpyHostToDevice, stream));
     int r = 0;
-    if (any_masks) r = launch_tile_masks_batch(p0, table_dev, culls_dev, n_frames, stream);
+    if (any_masks) r = launch_tile_masks_batch(hp[0], table_dev, culls_dev, n_frames, stream);
     if (r != 0) return fail(ctx, C2RT_ERR_HIP, "tile-mask pre-pass launch: %s", hipGetErrorString((hipError_t)r));
     if (nested) HIP_TRY(ctx, hipMemsetAsync(sc.retry_list, 0, (blocks + 1) * n * sizeof(uint32_t), stream));
-    r = launch_render_batch(p0, variant, table_dev, n_frames, stream);
-    if (r == 0 && retry) r = launch_render_batch(hp[n], variant, table_dev + n, n_frames, stream);
+    const size_t group_at[3] = {0, n_first, n};
+    for (int g = 0; g < 2 && r == 0; ++g) {
+        const size_t a = group_at[g], count = group_at[g + 1] - a;
+        if (!count) continue;
+        /* the launcher's copy of a block of the group: the instance every frame of the group can run */
+        RenderParams first = hp[a], again = retry ? hp[n + a] : hp[a];
+        for (size_t j = a; j < a + count; ++j)
+            if (!hp[j].all_identity) first.all_identity = again.all_identity = 0;
+        r = launch_render_batch(first, variant, table_dev + a, (uint32_t)count, stream);
+        if (r == 0 && retry) r = launch_render_batch(again, variant, table_dev + n + a, (uint32_t)count, stream);
+    }
     if (r != 0) return fail(ctx, C2RT_ERR_HIP, "render kernel launch: %s", hipGetErrorString((hipError_t)r));
+    return C2RT_OK;
+}
+
+/* Why a posed batch refuses its poses (after check_batch_args), naming the frame; C2RT_OK otherwise. */
+int check_posed_args(c2rt_ctx *ctx, const c2rt_scene_pose *poses, uint32_t n_frames)
+{
+    if (!poses) return fail(ctx, C2RT_ERR_INVALID_ARG, "null poses");
+    for (uint32_t i = 0; i < n_frames; ++i) {
+        std::string err;
+        if (const int st = check_scene_pose(ctx->scene, &poses[i], err)) return fail(ctx, st, "frame %u: %s", i, err.c_str());
+    }
+    return C2RT_OK;
+}
+
+/* One device slot's half of c2rt_update_scene: plans the posed scene (update_scene_plan), then copies to the device,
+ * in stream order, the node records, the light table and the shadow rectangles whose bytes changed.  The sources are
+ * pageable: the runtime has read them when each call returns. */
+int update_one(c2rt_ctx *c, const c2rt_scene_pose *pose, hipStream_t stream)
+{
+    const std::vector<DevNode> nodes = c->plan.nodes;
+    const std::vector<DevLight> lights = c->plan.lights;
+    const std::vector<double> rects = c->plan.shadow_rects;
+    if (const int st = update_scene_plan(c->scene, c->plan, pose, c->err)) return st;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const std::vector<DevNode> &now = c->plan.nodes;
+    for (size_t a = 0; a < now.size();) { /* runs of changed records */
+        if (std::memcmp(&now[a], &nodes[a], sizeof(DevNode)) == 0) { ++a; continue; }
+        size_t b = a + 1;
+        while (b < now.size() && std::memcmp(&now[b], &nodes[b], sizeof(DevNode)) != 0) ++b;
+        HIP_TRY(c, hipMemcpyAsync(c->dev.nodes + a, &now[a], (b - a) * sizeof(DevNode), hipMemcpyHostToDevice, stream));
+        a = b;
+    }
+    if (!same_bytes(c->plan.lights, lights))
+        HIP_TRY(c, hipMemcpyAsync(c->dev.lights, c->plan.lights.data(), lights.size() * sizeof(DevLight), hipMemcpyHostToDevice, stream));
+    if (!same_bytes(c->plan.shadow_rects, rects))
+        HIP_TRY(c, hipMemcpyAsync(c->dev.shadow_rects, c->plan.shadow_rects.data(), rects.size() * sizeof(double), hipMemcpyHostToDevice, stream));
     return C2RT_OK;
 }
 
@@ -580,9 +714,32 @@ static int upload_one(c2rt_ctx *ctx, const c2rt_scene_desc *s)
     if ((st = upload(ctx, &ctx->dev.lights, plan.lights)) != C2RT_OK) return st;
     if ((st = upload(ctx, &ctx->dev.nodes, plan.nodes)) != C2RT_OK) return st;
     ctx->plan = std::move(plan);
+    ctx->scene.assign(s);
     ctx->has_scene = true;
     ctx->err.clear();
     return C2RT_OK;
+}
+
+int c2rt_update_scene(c2rt_ctx *ctx, const c2rt_scene_pose *pose, void *hip_stream)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (!ctx->has_scene) return fail(ctx, C2RT_ERR_NO_SCENE, "no scene uploaded");
+    if (const int st = check_scene_pose(ctx->scene, pose, ctx->err)) return st;
+    if (!ctx->peers.empty() && hip_stream)
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "a multi-device context orders every slot's copies on the slot's own stream: hip_stream must be null");
+    if (pose->n_nodes == 0 && pose->n_lights == 0) return C2RT_OK;
+    int st = update_one(ctx, pose, static_cast<hipStream_t>(hip_stream));
+    if (st != C2RT_OK) return st;
+    /* no stream named: the next frame may be a host-output one, which runs on the context's own stream and is not
+     * ordered behind the default stream: the copies are waited for (that one stream only) */
+    if (!hip_stream) HIP_TRY(ctx, hipStreamSynchronize(nullptr));
+    for (size_t i = 0; i < ctx->peers.size() && st == C2RT_OK; ++i) {
+        c2rt_ctx *c = ctx->peers[i];
+        st = update_one(c, pose, c->stream);
+        if (st != C2RT_OK) st = fail(ctx, st, "device slot %zu: %s", i + 1, c->err.c_str());
+    }
+    (void)hipSetDevice(ctx->device);
+    return st;
 }
 
 /* Host-output frames (c2rt_render_frame: float RGB; c2rt_render_frame_rgb32: Color.toRGB32 words).
@@ -937,7 +1094,7 @@ int c2rt_render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint
     if (!out_rgb_dev) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ctx->counters_valid = false;
-    return render_frames_device(ctx, cams, n_frames, opts, out_rgb_dev, static_cast<hipStream_t>(hip_stream));
+    return render_frames_device(ctx, cams, nullptr, n_frames, opts, out_rgb_dev, static_cast<hipStream_t>(hip_stream));
 }
 
 int c2rt_render_frames(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
@@ -953,7 +1110,44 @@ int c2rt_render_frames(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_
     if (bytes == 0) return C2RT_OK;
     if (const int st = ensure_staging(ctx, bytes)) return st;
     ctx->counters_valid = false;
-    if (const int st = render_frames_device(ctx, cams, n_frames, opts, ctx->frame, ctx->stream)) return st;
+    if (const int st = render_frames_device(ctx, cams, nullptr, n_frames, opts, ctx->frame, ctx->stream)) return st;
+    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->frame, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return C2RT_OK;
+}
+
+int c2rt_render_frames_posed_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, uint32_t n_frames,
+                                    const c2rt_render_opts *opts, float *out_rgb_dev, void *hip_stream)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (n_frames == 0) return C2RT_OK;
+    if (const int st = check_batch_args(ctx, cams, n_frames, opts)) return st;
+    if (const int st = check_posed_args(ctx, poses, n_frames)) return st;
+    if (!out_rgb_dev) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    std::vector<std::unique_ptr<PosedFrame>> posed;
+    if (const int st = plan_posed_frames(ctx, poses, n_frames, posed)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ctx->counters_valid = false;
+    return render_frames_device(ctx, cams, &posed, n_frames, opts, out_rgb_dev, static_cast<hipStream_t>(hip_stream));
+}
+
+int c2rt_render_frames_posed(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, uint32_t n_frames,
+                             const c2rt_render_opts *opts, float *out_rgb, const volatile uint8_t *stop_flag)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (n_frames == 0) return C2RT_OK;
+    if (const int st = check_batch_args(ctx, cams, n_frames, opts)) return st;
+    if (const int st = check_posed_args(ctx, poses, n_frames)) return st;
+    if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    if (stop_flag && *stop_flag) return fail(ctx, C2RT_ERR_CANCELLED, "stop requested before the batch");
+    std::vector<std::unique_ptr<PosedFrame>> posed;
+    if (const int st = plan_posed_frames(ctx, poses, n_frames, posed)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t bytes = (size_t)n_frames * c2rt_local_rows(opts) * opts->width * 3 * sizeof(float);
+    if (bytes == 0) return C2RT_OK;
+    if (const int st = ensure_staging(ctx, bytes)) return st;
+    ctx->counters_valid = false;
+    if (const int st = render_frames_device(ctx, cams, &posed, n_frames, opts, ctx->frame, ctx->stream)) return st;
     HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->frame, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return C2RT_OK;
@@ -1483,7 +1677,7 @@ int c2rt_debug_sphere_cull(c2rt_ctx *ctx, uint32_t sphere_flags_mask, const c2rt
     size_t entries, blocks;
     frame_needs(p, entries, blocks);
     BatchCull cull;
-    wire_frame(ctx, p, FrameScratch(), 0, entries, blocks, ~0u, cull); /* (the mask is the context's, set above) */
+    wire_frame(ctx, ctx->plan, p, FrameScratch(), 0, entries, blocks, ~0u, cull); /* (the mask is the context's, set above) */
     std::memcpy(sphere_cull, &cull.s, sizeof cull.s);
     return C2RT_OK;
 }

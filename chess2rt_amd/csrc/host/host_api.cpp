@@ -330,6 +330,116 @@ void transform_store(double t[30], const Transform &x)
     t[27] = x.offset.x, t[28] = x.offset.y, t[29] = x.offset.z;
 }
 } // namespace
+// ---- moving a node or a light of a loaded scene ----
+namespace {
+int find_node(const c2rt_host_scene *s, const char *name)
+{
+    if (!s || !name) return -1;
+    for (size_t i = 0; i < s->scene->nodes.size(); ++i)
+        if (s->scene->nodes[i].name == name) return (int)i;
+    return -1;
+}
+int find_light(const c2rt_host_scene *s, const char *name)
+{
+    if (!s || !name) return -1;
+    for (size_t i = 0; i < s->scene->lights.size(); ++i)
+        if (s->scene->lights[i].name == name) return (int)i;
+    return -1;
+}
+// The host object has changed.  A context that still holds this scene's upload takes the change as one
+// c2rt_update_scene on the default stream (the generation stays this scene's own); without one, or when the context has
+// moved on to another scene, or when the update is refused, the next render through this scene re-uploads.
+int push_pose(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_scene_pose &pose)
+{
+    if (ctx && s->desc && s->uploaded_to == ctx && s->uploaded_gen != 0 && c2rt_scene_generation(ctx) == s->uploaded_gen) {
+        const int st = c2rt_update_scene(ctx, &pose, nullptr);
+        if (st != C2RT_OK) s->uploaded_gen = 0;
+        return st;
+    }
+    s->uploaded_gen = 0;
+    return C2RT_OK;
+}
+int node_changed(c2rt_ctx *ctx, c2rt_host_scene *s, int n)
+{
+    s->scene->reflattenNode((size_t)n);
+    double t[30];
+    transform_store(t, s->scene->nodes[(size_t)n].transform);
+    const uint32_t index = (uint32_t)n;
+    c2rt_scene_pose pose;
+    std::memset(&pose, 0, sizeof pose);
+    pose.n_nodes = 1;
+    pose.node_index = &index;
+    pose.node_transform = t;
+    return push_pose(ctx, s, pose);
+}
+} // namespace
+
+int c2rt_host_scene_node_index(const c2rt_host_scene *s, const char *node) { return find_node(s, node); }
+int c2rt_host_scene_light_index(const c2rt_host_scene *s, const char *light) { return find_light(s, light); }
+
+int c2rt_host_node_transform_get(const c2rt_host_scene *s, const char *node, double t[30])
+{
+    const int n = find_node(s, node);
+    if (n < 0 || !t) return C2RT_ERR_INVALID_ARG;
+    transform_store(t, s->scene->nodes[(size_t)n].transform);
+    return C2RT_OK;
+}
+int c2rt_host_node_transform_set(c2rt_ctx *ctx, c2rt_host_scene *s, const char *node, const double t[30])
+{
+    const int n = find_node(s, node);
+    if (n < 0 || !t) return C2RT_ERR_INVALID_ARG;
+    s->scene->nodes[(size_t)n].transform = transform_load(t);
+    return node_changed(ctx, s, n);
+}
+int c2rt_host_node_transform_reset(c2rt_ctx *ctx, c2rt_host_scene *s, const char *node)
+{
+    const int n = find_node(s, node);
+    if (n < 0) return C2RT_ERR_INVALID_ARG;
+    s->scene->nodes[(size_t)n].transform.reset();
+    return node_changed(ctx, s, n);
+}
+int c2rt_host_node_transform_scale(c2rt_ctx *ctx, c2rt_host_scene *s, const char *node, double x, double y, double z)
+{
+    const int n = find_node(s, node);
+    if (n < 0) return C2RT_ERR_INVALID_ARG;
+    s->scene->nodes[(size_t)n].transform.scale(x, y, z);
+    return node_changed(ctx, s, n);
+}
+int c2rt_host_node_transform_rotate(c2rt_ctx *ctx, c2rt_host_scene *s, const char *node, double yaw, double pitch, double roll)
+{
+    const int n = find_node(s, node);
+    if (n < 0) return C2RT_ERR_INVALID_ARG;
+    s->scene->nodes[(size_t)n].transform.rotate(yaw, pitch, roll);
+    return node_changed(ctx, s, n);
+}
+int c2rt_host_node_transform_translate(c2rt_ctx *ctx, c2rt_host_scene *s, const char *node, const double v[3])
+{
+    const int n = find_node(s, node);
+    if (n < 0 || !v) return C2RT_ERR_INVALID_ARG;
+    s->scene->nodes[(size_t)n].transform.translate(Vector(v[0], v[1], v[2]));
+    return node_changed(ctx, s, n);
+}
+int c2rt_host_light_set(c2rt_ctx *ctx, c2rt_host_scene *s, const char *light, const double *pos, const float *color, const float *power)
+{
+    const int l = find_light(s, light);
+    if (l < 0) return C2RT_ERR_INVALID_ARG;
+    if (!pos && !color && !power) return C2RT_OK;
+    Light &lt = s->scene->lights[(size_t)l];
+    if (pos) lt.pos = Vector(pos[0], pos[1], pos[2]);
+    if (color) lt.lightColor = Color{color[0], color[1], color[2]};
+    if (power) lt.lightPower = *power;
+    s->scene->reflattenLight((size_t)l);
+    const uint32_t index = (uint32_t)l;
+    c2rt_scene_pose pose;
+    std::memset(&pose, 0, sizeof pose);
+    pose.n_lights = 1;
+    pose.light_index = &index;
+    pose.light_pos = pos;
+    pose.light_color = color;
+    pose.light_power = power;
+    return push_pose(ctx, s, pose);
+}
+
 void c2rt_host_transform_reset(double t[30])
 {
     Transform x;

@@ -673,6 +673,29 @@ std::unique_ptr<Scene> parseSceneFromFile(const std::string &filename)
 }
 
 // ------------------------------------------------------------------ flatten
+void Scene::reflattenNode(size_t n)
+{
+    if (!flat_ || n >= nodes.size()) return;
+    const Transform &t = nodes[n].transform;
+    double *out = &flat_->node_transform[30 * n];
+    const Matrix *ms[3] = {&t.transform, &t.inverseTransform, &t.transposedInverse};
+    for (const Matrix *m : ms)
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) *out++ = m->c[i][j];
+    out[0] = t.offset.x, out[1] = t.offset.y, out[2] = t.offset.z;
+}
+
+void Scene::reflattenLight(size_t l)
+{
+    if (!flat_ || l >= lights.size()) return;
+    const Light &lt = lights[l];
+    const double pos[3] = {lt.pos.x, lt.pos.y, lt.pos.z};
+    const float col[3] = {lt.lightColor.r, lt.lightColor.g, lt.lightColor.b};
+    std::memcpy(&flat_->light_pos[3 * l], pos, sizeof pos);
+    std::memcpy(&flat_->light_color[3 * l], col, sizeof col);
+    flat_->light_power[l] = lt.lightPower;
+}
+
 const c2rt_scene_desc *Scene::flatten()
 {
     flat_.reset(new Flat());

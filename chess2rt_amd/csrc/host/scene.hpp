@@ -148,6 +148,9 @@ struct Scene {
 
     // Scene -> c2rt_scene_desc (tables owned by this object)
     const c2rt_scene_desc *flatten();
+    // nodes[n].transform / lights[l] were changed: rewrite their entries of the flat view in place (if there is one)
+    void reflattenNode(size_t n);
+    void reflattenLight(size_t l);
 
     // identity of the uploaded tables, so that Renderer uploads once per scene
     uint64_t upload_generation = 1;

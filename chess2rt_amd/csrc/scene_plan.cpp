@@ -186,8 +186,9 @@ int plan_geoms(const c2rt_scene_desc *s, ScenePlan &p, std::string &err)
     return C2RT_OK;
 }
 
-/* textures: texel pool repacked to float4 */
-int plan_textures(const c2rt_scene_desc *s, ScenePlan &p, std::string &err)
+/* textures: texel pool repacked to float4 (with_texels = false, a replan of a posed scene: the pool is not read and
+ * texels4 stays empty) */
+int plan_textures(const c2rt_scene_desc *s, ScenePlan &p, std::string &err, bool with_texels)
 {
     std::vector<DevTex> &textures = p.textures;
     textures.resize(s->n_textures);
@@ -209,6 +210,7 @@ int plan_textures(const c2rt_scene_desc *s, ScenePlan &p, std::string &err)
             if (d.width >= (1u << 24) || d.height >= (1u << 24)) return fail(err, C2RT_ERR_LIMIT, "texture %u too large", t);
         }
     }
+    if (!with_texels) return C2RT_OK;
     std::vector<float> &texels4 = p.texels4;
     texels4.resize((size_t)s->n_texels * 4);
     for (uint64_t i = 0; i < s->n_texels; ++i) {
@@ -596,13 +598,15 @@ int check_scene_desc(const c2rt_scene_desc *s, std::string &err)
     return C2RT_OK;
 }
 
-int plan_scene(const c2rt_scene_desc *s, ScenePlan &plan, std::string &err)
+namespace {
+
+/* plan_scene behind its header check; with_texels = false: replan_scene */
+int plan_checked_scene(const c2rt_scene_desc *s, ScenePlan &plan, std::string &err, bool with_texels)
 {
     int st;
-    if ((st = check_scene_desc(s, err)) != C2RT_OK) return st;
     ScenePlan p;
     if ((st = plan_geoms(s, p, err)) != C2RT_OK) return st;
-    if ((st = plan_textures(s, p, err)) != C2RT_OK) return st;
+    if ((st = plan_textures(s, p, err, with_texels)) != C2RT_OK) return st;
     if ((st = plan_shaders(s, p, err)) != C2RT_OK) return st;
     if ((st = plan_lights(s, p, err)) != C2RT_OK) return st;
     if ((st = plan_nodes(s, p, err)) != C2RT_OK) return st;
@@ -616,6 +620,133 @@ int plan_scene(const c2rt_scene_desc *s, ScenePlan &plan, std::string &err)
     std::memcpy(p.ambient, s->ambient, sizeof p.ambient);
     p.max_trace_depth = s->max_trace_depth;
     plan = std::move(p);
+    return C2RT_OK;
+}
+
+template <typename T>
+const T *copy_table(std::vector<T> &dst, const T *src, size_t n)
+{
+    if (src && n) dst.assign(src, src + n);
+    else dst.clear();
+    return dst.empty() ? nullptr : dst.data();
+}
+
+} // namespace
+
+int plan_scene(const c2rt_scene_desc *s, ScenePlan &plan, std::string &err)
+{
+    if (const int st = check_scene_desc(s, err)) return st;
+    return plan_checked_scene(s, plan, err, true);
+}
+
+/* ---- posing an uploaded scene ---- */
+void SceneCopy::assign(const c2rt_scene_desc *s)
+{
+    desc = *s;
+    const size_t g = s->n_geoms, t = s->n_textures, sh = s->n_shaders, l = s->n_lights, n = s->n_nodes;
+    desc.geom_type = copy_table(geom_type, s->geom_type, g);
+    desc.geom_param = copy_table(geom_param, s->geom_param, 4 * g);
+    desc.geom_child = copy_table(geom_child, s->geom_child, 2 * g);
+    desc.tex_type = copy_table(tex_type, s->tex_type, t);
+    desc.tex_color = copy_table(tex_color, s->tex_color, 18 * t);
+    desc.tex_param = copy_table(tex_param, s->tex_param, 6 * t);
+    desc.tex_scaling = copy_table(tex_scaling, s->tex_scaling, t);
+    desc.tex_width = copy_table(tex_width, s->tex_width, t);
+    desc.tex_height = copy_table(tex_height, s->tex_height, t);
+    desc.tex_offset = copy_table(tex_offset, s->tex_offset, t);
+    desc.texels = nullptr; /* n_texels stays: plan_textures checks every bitmap's range against it */
+    desc.shader_type = copy_table(shader_type, s->shader_type, sh);
+    desc.shader_color = copy_table(shader_color, s->shader_color, 3 * sh);
+    desc.shader_texture = copy_table(shader_texture, s->shader_texture, sh);
+    desc.shader_exponent = copy_table(shader_exponent, s->shader_exponent, sh);
+    desc.shader_strength = copy_table(shader_strength, s->shader_strength, sh);
+    desc.light_type = copy_table(light_type, s->light_type, l);
+    desc.light_pos = copy_table(light_pos, s->light_pos, 3 * l);
+    desc.light_color = copy_table(light_color, s->light_color, 3 * l);
+    desc.light_power = copy_table(light_power, s->light_power, l);
+    desc.node_geom = copy_table(node_geom, s->node_geom, n);
+    desc.node_shader = copy_table(node_shader, s->node_shader, n);
+    desc.node_bump = nullptr; /* the planner does not read it (base modifyNormal is a no-op) */
+    desc.node_transform = copy_table(node_transform, s->node_transform, 30 * n);
+}
+
+int check_scene_pose(const SceneCopy &scene, const c2rt_scene_pose *pose, std::string &err)
+{
+    if (!pose) return fail(err, C2RT_ERR_INVALID_ARG, "null pose");
+    if (pose->n_nodes && !pose->node_index) return fail(err, C2RT_ERR_INVALID_ARG, "pose: %u nodes with a null node_index", pose->n_nodes);
+    if (pose->n_lights && !pose->light_index) return fail(err, C2RT_ERR_INVALID_ARG, "pose: %u lights with a null light_index", pose->n_lights);
+    if (pose->n_nodes && !pose->node_transform) return fail(err, C2RT_ERR_INVALID_ARG, "pose: %u nodes with a null node_transform", pose->n_nodes);
+    if (pose->n_lights && !pose->light_pos && !pose->light_color && !pose->light_power)
+        return fail(err, C2RT_ERR_INVALID_ARG, "pose: %u lights with null light_pos, light_color and light_power", pose->n_lights);
+    const uint32_t have[2] = {scene.desc.n_nodes, scene.desc.n_lights}, n[2] = {pose->n_nodes, pose->n_lights};
+    const uint32_t *index[2] = {pose->node_index, pose->light_index};
+    static const char *const what[2] = {"node", "light"};
+    for (int k = 0; k < 2; ++k)
+        for (uint32_t i = 0; i < n[k]; ++i)
+            if (index[k][i] >= have[k])
+                return fail(err, C2RT_ERR_INVALID_ARG, "pose: %s_index[%u] = %u out of range (the scene has %u %ss)", what[k], i, index[k][i], have[k], what[k]);
+    for (int k = 0; k < 2; ++k) {
+        std::vector<uint8_t> seen(have[k], 0);
+        for (uint32_t i = 0; i < n[k]; ++i) {
+            if (seen[index[k][i]]) return fail(err, C2RT_ERR_INVALID_ARG, "pose: %s_index[%u] = %u is listed twice", what[k], i, index[k][i]);
+            seen[index[k][i]] = 1;
+        }
+    }
+    return C2RT_OK;
+}
+
+int replan_scene(const SceneCopy &scene, ScenePlan &plan, std::string &err)
+{
+    return plan_checked_scene(&scene.desc, plan, err, false);
+}
+
+void pose_scene(SceneCopy &scene, const c2rt_scene_pose *pose, PoseUndo &undo)
+{
+    undo.node_transform.resize(30 * (size_t)pose->n_nodes);
+    undo.light_pos.resize(3 * (size_t)pose->n_lights);
+    undo.light_color.resize(3 * (size_t)pose->n_lights);
+    undo.light_power.resize(pose->n_lights);
+    for (uint32_t i = 0; i < pose->n_nodes; ++i) {
+        double *t = &scene.node_transform[30 * (size_t)pose->node_index[i]];
+        std::memcpy(&undo.node_transform[30 * (size_t)i], t, 30 * sizeof(double));
+        std::memcpy(t, pose->node_transform + 30 * (size_t)i, 30 * sizeof(double));
+    }
+    for (uint32_t i = 0; i < pose->n_lights; ++i) {
+        const size_t l = pose->light_index[i];
+        std::memcpy(&undo.light_pos[3 * (size_t)i], &scene.light_pos[3 * l], 3 * sizeof(double));
+        std::memcpy(&undo.light_color[3 * (size_t)i], &scene.light_color[3 * l], 3 * sizeof(float));
+        undo.light_power[i] = scene.light_power[l];
+        if (pose->light_pos) std::memcpy(&scene.light_pos[3 * l], pose->light_pos + 3 * (size_t)i, 3 * sizeof(double));
+        if (pose->light_color) std::memcpy(&scene.light_color[3 * l], pose->light_color + 3 * (size_t)i, 3 * sizeof(float));
+        if (pose->light_power) scene.light_power[l] = pose->light_power[i];
+    }
+}
+
+void unpose_scene(SceneCopy &scene, const c2rt_scene_pose *pose, const PoseUndo &undo)
+{
+    for (uint32_t i = 0; i < pose->n_nodes; ++i)
+        std::memcpy(&scene.node_transform[30 * (size_t)pose->node_index[i]], &undo.node_transform[30 * (size_t)i], 30 * sizeof(double));
+    for (uint32_t i = 0; i < pose->n_lights; ++i) {
+        const size_t l = pose->light_index[i];
+        std::memcpy(&scene.light_pos[3 * l], &undo.light_pos[3 * (size_t)i], 3 * sizeof(double));
+        std::memcpy(&scene.light_color[3 * l], &undo.light_color[3 * (size_t)i], 3 * sizeof(float));
+        scene.light_power[l] = undo.light_power[i];
+    }
+}
+
+int update_scene_plan(SceneCopy &scene, ScenePlan &plan, const c2rt_scene_pose *pose, std::string &err)
+{
+    if (const int st = check_scene_pose(scene, pose, err)) return st;
+    if (pose->n_nodes == 0 && pose->n_lights == 0) return C2RT_OK;
+    PoseUndo undo;
+    pose_scene(scene, pose, undo);
+    ScenePlan next;
+    if (const int st = replan_scene(scene, next, err)) {
+        unpose_scene(scene, pose, undo);
+        return st;
+    }
+    next.texels4 = std::move(plan.texels4);
+    plan = std::move(next);
     return C2RT_OK;
 }
 

@@ -58,6 +58,49 @@ int check_scene_desc(const c2rt_scene_desc *s, std::string &err);
  * reason in `err`, and `plan` untouched. */
 int plan_scene(const c2rt_scene_desc *s, ScenePlan &plan, std::string &err);
 
+/* ---- posing an uploaded scene (c2rt_update_scene, c2rt_render_frames_posed) ---- */
+
+/* A deep copy of a planned description without its texels: `desc` points into the vectors (texels null, n_texels
+ * kept for the textures' range check).  What a pose patches — node_transform, light_pos, light_color, light_power —
+ * is patched here, and the plan is derived from it again by the planner itself. */
+struct SceneCopy {
+    c2rt_scene_desc desc{};
+    std::vector<int32_t> geom_type, geom_child, tex_type, shader_type, shader_texture, light_type, node_geom, node_shader;
+    std::vector<double> geom_param, tex_param, shader_exponent, light_pos, node_transform;
+    std::vector<float> tex_color, tex_scaling, shader_color, shader_strength, light_color, light_power;
+    std::vector<uint32_t> tex_width, tex_height;
+    std::vector<uint64_t> tex_offset;
+
+    SceneCopy() = default;
+    SceneCopy(const SceneCopy &) = delete;
+    SceneCopy &operator=(const SceneCopy &) = delete;
+    /* `s` has passed check_scene_desc */
+    void assign(const c2rt_scene_desc *s);
+};
+
+/* Why `pose` cannot be applied to `scene`, in the documented order (c2rt.h); C2RT_OK otherwise.  Reads the pose's
+ * counts, pointers and indices only. */
+int check_scene_pose(const SceneCopy &scene, const c2rt_scene_pose *pose, std::string &err);
+
+/* plan_scene(&scene.desc) with the texel conversion skipped: plan.texels4 comes out empty, everything else is what
+ * plan_scene derives. */
+int replan_scene(const SceneCopy &scene, ScenePlan &plan, std::string &err);
+
+/* What a pose overwrites in a SceneCopy, saved so that it can be put back (pose_scene / unpose_scene: a refused
+ * update, a frame of a posed batch). */
+struct PoseUndo {
+    std::vector<double> node_transform, light_pos;
+    std::vector<float> light_color, light_power;
+};
+/* Applies a checked pose to `scene` in the order its entries are listed, remembering what it overwrote. */
+void pose_scene(SceneCopy &scene, const c2rt_scene_pose *pose, PoseUndo &undo);
+void unpose_scene(SceneCopy &scene, const c2rt_scene_pose *pose, const PoseUndo &undo);
+
+/* The whole step behind c2rt_update_scene: check, patch, plan again.  C2RT_OK: `scene` is the patched description and
+ * `plan` its plan, with the texels4 it had (moved, not converted again).  Anything else: the status, the reason in
+ * `err`, `scene` and `plan` as they were. */
+int update_scene_plan(SceneCopy &scene, ScenePlan &plan, const c2rt_scene_pose *pose, std::string &err);
+
 /* where the uploaded tables of a ScenePlan live (device pointers; the planner only copies them into RenderParams) */
 struct DeviceTables {
     DevGeom *geoms = nullptr;

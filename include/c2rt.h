@@ -270,6 +270,57 @@ int c2rt_upload_scene(c2rt_ctx *ctx, const c2rt_scene_desc *scene);
  * re-uploads when the context has moved on to another scene. */
 uint64_t c2rt_scene_generation(const c2rt_ctx *ctx);
 
+/* ---- posing the uploaded scene: node transforms and lights ---------------- */
+
+/* New values for some node transforms and lights of the uploaded scene.  Everything else of the description —
+ * geometries, shaders, textures, texels, the counts — is what was uploaded; changing those is a re-upload. */
+typedef struct c2rt_scene_pose {
+    uint32_t n_nodes;              /* entries below; 0: no node changes */
+    const uint32_t *node_index;    /* [n_nodes] indices into the uploaded scene's nodes */
+    /* [n_nodes][30], the layout of c2rt_scene_desc::node_transform: transform[9], inverseTransform[9],
+     * transposedInverse[9], offset[3].  All four parts are the caller's, as at upload: the library never inverts a
+     * matrix, the inverse's bits are those of the caller's own Transform (rt/transform.d:24-55). */
+    const double   *node_transform;
+    uint32_t n_lights;
+    const uint32_t *light_index;   /* [n_lights] */
+    const double   *light_pos;     /* [n_lights][3], nullable: positions unchanged */
+    const float    *light_color;   /* [n_lights][3], nullable */
+    const float    *light_power;   /* [n_lights],   nullable */
+} c2rt_scene_pose;
+
+/* Patches the uploaded scene in place.  Afterwards the context behaves, in every entry point and in every bit, as if
+ * c2rt_upload_scene had been called with the uploaded description patched by `pose`: the library keeps a copy of that
+ * description (without the texels), patches it, plans it again on the host — which instance a frame runs, the ground
+ * plane, the shadow rectangles, the candidates of the mask pre-pass all follow — and copies to the device the node
+ * records, the light table and the shadow rectangles whose bytes changed.  Poses accumulate: each update patches the
+ * scene the one before it left.
+ *
+ * c2rt_scene_generation does NOT change: it names the upload, and this is the same description posed differently.  A
+ * host-side scene object that moved its own node keeps its generation and needs no re-upload.
+ *
+ * Ordering.  The table copies are stream-ordered copies from pageable host memory on `hip_stream` (a hipStream_t,
+ * NULL = default stream): the runtime has read their source when the call returns, and they run after everything
+ * enqueued earlier on that stream.  Frames, batches and queries enqueued on `hip_stream` BEFORE the call see the old
+ * scene, those enqueued AFTER it the new one, with no host sync in between.  The host-side plan changes when the call
+ * returns.  Work of this context on OTHER streams is not ordered against the update by the library: a frame still
+ * running there may read either table — the caller's hazard, like two frames into one buffer.  The call may wait, on the
+ * host, until work enqueued earlier on `hip_stream` has drained (as c2rt_render_frames_device may); it never waits for
+ * other streams, synchronises the device, allocates, frees, records or waits for an event, touches the texel pool,
+ * or keeps `hip_stream`.  With `hip_stream` NULL the call also waits, on the host, for its own copies on the default
+ * stream: the host-output entry points (c2rt_render_frame, c2rt_render_frames, the queries) run on the context's own
+ * stream, which is not ordered behind the default stream, and must see the new scene when the call has returned.
+ *
+ * Statuses, all decided before anything is enqueued or changed — a refused update leaves the scene exactly as it was
+ * (unlike c2rt_upload_scene): no scene: C2RT_ERR_NO_SCENE; C2RT_ERR_INVALID_ARG for a null `pose`, a count > 0 with a
+ * null index array, n_nodes > 0 with a null node_transform, n_lights > 0 with all three light arrays null, an index
+ * out of range or listed twice (c2rt_last_error names the entry); whatever the scene planner answers to the patched
+ * description, with its message.  A pose with both counts 0 is C2RT_OK and enqueues nothing.
+ *
+ * A context of c2rt_init_multi patches every device slot; `hip_stream` must be NULL there (C2RT_ERR_INVALID_ARG
+ * otherwise).  Each further slot's copies are ordered on that slot's own stream, as its frames are; the lead slot's
+ * go to the default stream and are waited for, as above. */
+int c2rt_update_scene(c2rt_ctx *ctx, const c2rt_scene_pose *pose, void *hip_stream);
+
 /* ---- rendering ---------------------------------------------------------- */
 
 /* Number of rows this rank renders under `opts` striping (== opts->height
@@ -362,6 +413,32 @@ int c2rt_render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams,
 int c2rt_render_frames(c2rt_ctx *ctx, const c2rt_camera_frame *cams,
                        uint32_t n_frames, const c2rt_render_opts *opts,
                        float *out_rgb, const volatile uint8_t *stop_flag);
+
+/* An animation in one call: c2rt_render_frames_device with a pose per frame.  Frame i is the context's current scene
+ * with poses[i] applied — each pose relative to the current scene, not to the frame before it — seen through cams[i],
+ * and holds exactly the bits c2rt_update_scene(&poses[i]) followed by c2rt_render_frame_device(&cams[i]) writes.  A
+ * pose with both counts 0 is a frame of the scene as it is.  The context's scene is unchanged by the call.
+ *
+ * Every frame is planned on the host like an update (instance, ground plane, shadow rectangles, pre-pass candidates,
+ * culling rectangles); the node, light and rectangle tables of the frames that differ from the context's travel to
+ * the device beside the batch's parameter table, in the stream's scratch slot, with the same stream-ordered copy.
+ * One launch runs one kernel instance: frames whose poses leave every matrix the identity and frames whose poses do
+ * not share the general instance, which the library holds to the same bits as the identity instance; a batch whose
+ * poses differ in whether every node is an axis plane (the plane instances of single-light scenes) is rendered as
+ * two groups of frames that agree, one launch pair per group.
+ *
+ * Blocking, streams and scratch: as c2rt_render_frames_device.  Statuses, all decided before anything is enqueued (the
+ * output is untouched): those of c2rt_render_frames_device; null `poses` with n_frames > 0: C2RT_ERR_INVALID_ARG;
+ * those of c2rt_update_scene for every poses[i], with "frame i: " in front of the message. */
+int c2rt_render_frames_posed_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams,
+                                    const c2rt_scene_pose *poses, uint32_t n_frames,
+                                    const c2rt_render_opts *opts, float *out_rgb_dev,
+                                    void *hip_stream);
+/* The same into HOST memory, as c2rt_render_frames is to c2rt_render_frames_device. */
+int c2rt_render_frames_posed(c2rt_ctx *ctx, const c2rt_camera_frame *cams,
+                             const c2rt_scene_pose *poses, uint32_t n_frames,
+                             const c2rt_render_opts *opts, float *out_rgb,
+                             const volatile uint8_t *stop_flag);
 
 /* Ray counters of the last render call made with opts->count_rays = 1
  * (waits, on the host, for that frame to complete). */

@@ -109,6 +109,31 @@ int c2rt_host_render_hits(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt_hit_
  * frameWidth * frameHeight bytes.  Depth of field and stereo are refused with C2RT_ERR_UNSUPPORTED. */
 int c2rt_host_render_rt_adaptive(c2rt_ctx *ctx, c2rt_host_scene *scene, float *out_rgb, uint8_t *needs_aa);
 
+/* ---- moving a node or a light of a loaded scene ----------------------------- */
+
+/* Index of the named node / light in the flat tables (and in a c2rt_scene_pose); -1: no such name. */
+int c2rt_host_scene_node_index(const c2rt_host_scene *scene, const char *node);
+int c2rt_host_scene_light_index(const c2rt_host_scene *scene, const char *light);
+
+/* The named node's Transform (rt/node.d:9, rt/transform.d:11-14) with the reference's own verbs: reset (:24-29), scale
+ * (:31-39), rotate (:41-50, the real one: see c2rt_host_transform_rotate), translate (:52-55); _get / _set hand the 30
+ * doubles of c2rt_scene_desc::node_transform over whole.  Each call patches the host object and its flat view in place
+ * (c2rt_host_scene_desc stays valid).  If `ctx` (nullable) still holds this scene's own upload, the call also pushes
+ * the change with one c2rt_update_scene on the default stream and the generation stays this scene's: the next render
+ * shows the moved node without a re-upload.  Without a context, with a context that has moved on to another scene, or
+ * after a refused update, the next render through this scene re-uploads, as it always did.  C2RT_ERR_INVALID_ARG: no
+ * such node; otherwise c2rt_update_scene's status. */
+int c2rt_host_node_transform_get(const c2rt_host_scene *scene, const char *node, double t[30]);
+int c2rt_host_node_transform_set(c2rt_ctx *ctx, c2rt_host_scene *scene, const char *node, const double t[30]);
+int c2rt_host_node_transform_reset(c2rt_ctx *ctx, c2rt_host_scene *scene, const char *node);
+int c2rt_host_node_transform_scale(c2rt_ctx *ctx, c2rt_host_scene *scene, const char *node, double x, double y, double z);
+int c2rt_host_node_transform_rotate(c2rt_ctx *ctx, c2rt_host_scene *scene, const char *node, double yaw, double pitch, double roll);
+int c2rt_host_node_transform_translate(c2rt_ctx *ctx, c2rt_host_scene *scene, const char *node, const double v[3]);
+/* The named light's PointLight.pos, Light.lightColor and Light.lightPower (rt/light.d); a null pointer leaves that
+ * field as it is.  `ctx` as above. */
+int c2rt_host_light_set(c2rt_ctx *ctx, c2rt_host_scene *scene, const char *light, const double *pos, const float *color,
+                        const float *power);
+
 /* loadBmpImage!Color: malloc'd width*height*3 floats (free with
  * c2rt_host_free); y = 0 is the top row.  No gamma decode. */
 int c2rt_host_bmp_decode(const uint8_t *bytes, size_t len, uint32_t *width, uint32_t *height,

@@ -96,6 +96,18 @@ extern (C) nothrow @nogc
                                   float* out_rgb_dev, void* hip_stream);
     int c2rt_render_frames(c2rt_ctx*, const c2rt_camera_frame* cams, uint nFrames, const c2rt_render_opts*,
                            float* out_rgb, const shared(ubyte)* stop_flag);
+    /// move nodes and lights of the uploaded scene without re-uploading it: node_transform is [n_nodes][30] in the
+    /// layout of c2rt_scene_desc.node_transform; the copies are ordered on hip_stream, the generation stays
+    struct c2rt_scene_pose {
+        uint n_nodes; const(uint)* node_index; const(double)* node_transform;
+        uint n_lights; const(uint)* light_index; const(double)* light_pos; const(float)* light_color; const(float)* light_power;
+    }
+    int c2rt_update_scene(c2rt_ctx*, const c2rt_scene_pose* pose, void* hip_stream);
+    /// an animation in one call: frame i is the current scene under poses[i], seen through cams[i]
+    int c2rt_render_frames_posed_device(c2rt_ctx*, const c2rt_camera_frame* cams, const c2rt_scene_pose* poses, uint nFrames,
+                                        const c2rt_render_opts*, float* out_rgb_dev, void* hip_stream);
+    int c2rt_render_frames_posed(c2rt_ctx*, const c2rt_camera_frame* cams, const c2rt_scene_pose* poses, uint nFrames,
+                                 const c2rt_render_opts*, float* out_rgb, const shared(ubyte)* stop_flag);
     /// ray queries: Renderer.trace (rt/renderer.d:325-376) and Scene.testVisibility (rt/scene.d:62-78) for the
     /// caller's own rays, one per GPU lane; `dir` is used as given (trace() does not normalise); hits / rgb nullable,
     /// not both; Vector is three doubles, so a Ray's orig and dir map onto c2rt_ray as they stand
