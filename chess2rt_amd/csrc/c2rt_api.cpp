@@ -1270,6 +1270,7 @@ int c2rt_render_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_re
     RenderParams p;
     frame_params(ctx, cam, opts, p);
     p.n_cull = 0; /* the probe launch has no tile: never cull */
+    p.ground_fast = 0;
     p.n_cull_lights = 0;
     p.csg_cap = (uint32_t)kCsgFullCap(C2RT_MAX_CSG_DEPTH); /* the probe instance handles every depth */
     p.probe_x = x;

@@ -230,6 +230,11 @@ struct RenderParams {
     const uint32_t *tile_masks;
     uint32_t mask_row0, mask_rows;
     uint32_t mask_entries;         /* entries of the (first) table: tile_mask_entries() */
+    /* 1: tiles whose primary AND shadow rays can reach the ground plane only (bit 1 of the table's third word) are
+     * rendered by lean::ground_tile (c2rt_trace.inc) — decided per frame on the host (scene_plan.cpp, fill_params): a
+     * mask table, a ground node whose shader is Lambert over a bitmap, a checker or no texture, at most one light,
+     * no depth of field, no stereo, not a counted frame.  (Sits in what was padding: no other member moves.) */
+    uint32_t ground_fast;
     /* diagnostics build only (make VARIANT=tilestats EXTRA_HIPFLAGS=-DC2RT_TILE_STATS=1, scripts/tile_stats.py):
      * per tile {shader-clock cycles the wave spent on it, class bits}; never read by the product build */
     uint32_t *tile_stats;

@@ -1362,16 +1362,37 @@ DEV void load_mat(NodeP N, Mat &m)
     for (int i = 0; i < 8; ++i) m.td[i] = M->texdata[i];
 }
 
+/* Checker.getTexColor — rt/texture.d:36-54 */
+DEV F3 checker_color(const Mat &m, double u, double v)
+{
+    const double size = __hiloint2double((int)m.td[7], (int)m.td[6]);
+    const int x = d2i_x86(floor(u / size));
+    const int y = d2i_x86(floor(v / size));
+    const int white = (int)((uint32_t)x + (uint32_t)y) % 2;
+    return white ? mkf(__uint_as_float(m.td[3]), __uint_as_float(m.td[4]), __uint_as_float(m.td[5]))
+                 : mkf(__uint_as_float(m.td[0]), __uint_as_float(m.td[1]), __uint_as_float(m.td[2]));
+}
+
+/* BitmapTexture.getTexColor — rt/texture.d:116-126 */
+DEV F3 bitmap_color(const RenderParams &P, const Mat &m, double u, double v)
+{
+    const double s = (double)__uint_as_float(m.td[2]);
+    u *= s;
+    v *= s;
+    u = u - floor(u);
+    v = v - floor(v);
+    const uint32_t w = m.td[0], hgt = m.td[1];
+    const float tx = (float)u * (float)w;
+    const float ty = (float)v * (float)hgt;
+    const uint64_t offset = (uint64_t)m.td[4] | ((uint64_t)m.td[5] << 32);
+    return bitmap_filtered(reinterpret_cast<const float4 *>(P.texels) + offset, w, hgt, tx, ty);
+}
+
 DEV F3 tex_color(const RenderParams &P, const Mat &m, double u, double v)
 {
     const int type = m.tex_type;
-    if (type == C2RT_TEX_CHECKER) { /* Checker.getTexColor — rt/texture.d:36-54 */
-        const double size = __hiloint2double((int)m.td[7], (int)m.td[6]);
-        const int x = d2i_x86(floor(u / size));
-        const int y = d2i_x86(floor(v / size));
-        const int white = (int)((uint32_t)x + (uint32_t)y) % 2;
-        return white ? mkf(__uint_as_float(m.td[3]), __uint_as_float(m.td[4]), __uint_as_float(m.td[5]))
-                     : mkf(__uint_as_float(m.td[0]), __uint_as_float(m.td[1]), __uint_as_float(m.td[2]));
+    if (type == C2RT_TEX_CHECKER) {
+        return checker_color(m, u, v);
     } else if (type == C2RT_TEX_PROCEDURE2) { /* Procedure2.getTexColor — rt/texture.d:77-86 */
         TexP T = (TexP)P.textures + m.tex;
         F3 result = mkf(0, 0, 0);
@@ -1380,17 +1401,8 @@ DEV F3 tex_color(const RenderParams &P, const Mat &m, double u, double v)
             result = result + (ldf3(T->color + 3 * i) * (float)c2_sin(u * T->param[i]) +
                                ldf3(T->color + 9 + 3 * i) * (float)c2_sin(v * T->param[3 + i]));
         return result;
-    } else { /* BitmapTexture.getTexColor — rt/texture.d:116-126 */
-        const double s = (double)__uint_as_float(m.td[2]);
-        u *= s;
-        v *= s;
-        u = u - floor(u);
-        v = v - floor(v);
-        const uint32_t w = m.td[0], hgt = m.td[1];
-        const float tx = (float)u * (float)w;
-        const float ty = (float)v * (float)hgt;
-        const uint64_t offset = (uint64_t)m.td[4] | ((uint64_t)m.td[5] << 32);
-        return bitmap_filtered(reinterpret_cast<const float4 *>(P.texels) + offset, w, hgt, tx, ty);
+    } else {
+        return bitmap_color(P, m, u, v);
     }
 }
 
@@ -1404,6 +1416,19 @@ DEV F3 tex_color(const RenderParams &P, const Mat &m, double u, double v)
  * nothing of the hit has to stay live for a next light, so the hit point, normal and view direction
  * die before the shadow test (below). */
 /* What one visible light adds (rt/shader.d:88-103, 219-243): avgColor / avgSpecular of that light. */
+/* lightColor / float(d^2), rt/shader.d:97: three channels over one denominator.  lean::: the refined
+ * reciprocal once (fp64_lean.h, fp32 part) when the host has found the light's three numerators in
+ * range (DevLight::lit bit 1: each +0 or within 2^+-60); the denominator's own window is tested here */
+DEV F3 base_light(Oob &bad, LightP L, double r2)
+{
+    const float r2f = (float)r2;
+    if (kLean && (L->lit & 2u)) {
+        oob_note_f32(bad, r2f);
+        const float rr = rcp_refined_f32(r2f);
+        return mkf(div_with_f32(L->color[0], r2f, rr), div_with_f32(L->color[1], r2f, rr), div_with_f32(L->color[2], r2f, rr));
+    }
+    return ldf3(L->color) / r2f;
+}
 DEV void light_terms(const Ctx &cx, LightP L, D3 lightPos, D3 p, D3 N, D3 rd, bool phong, double &cosTheta, F3 &baseLight, double &cosGamma)
 {
     /* squaredMagnitude(p - lightPos) == squaredMagnitude(lightPos - p) bit for bit (IEEE a - b is
@@ -1415,17 +1440,7 @@ DEV void light_terms(const Ctx &cx, LightP L, D3 lightPos, D3 p, D3 N, D3 rd, bo
     len_inv(cx.bad, r2, rlen, rinv);
     const D3 lightDir = mk(lv.x * rinv, lv.y * rinv, lv.z * rinv);
     cosTheta = dot(lightDir, N);
-    /* lightColor / float(d^2), rt/shader.d:97: three channels over one denominator.  lean::: the refined
-     * reciprocal once (fp64_lean.h, fp32 part) when the host has found the light's three numerators in
-     * range (DevLight::lit bit 1: each +0 or within 2^+-60); the denominator's own window is tested here */
-    const float r2f = (float)r2;
-    if (kLean && (L->lit & 2u)) {
-        oob_note_f32(cx.bad, r2f);
-        const float rr = rcp_refined_f32(r2f);
-        baseLight = mkf(div_with_f32(L->color[0], r2f, rr), div_with_f32(L->color[1], r2f, rr), div_with_f32(L->color[2], r2f, rr));
-    } else {
-        baseLight = ldf3(L->color) / r2f;
-    }
+    baseLight = base_light(cx.bad, L, r2);
     cosGamma = 0;
     if (phong) {
         /* reflect(-lightDir, N) — rt/imported_types.d:62-67 */
@@ -1854,6 +1869,158 @@ DEV F3 render_sample(const RenderParams &P, const Ctx &cx, double x, double y, i
 __constant__ double k_aa_x[5] = {0.0, 0.3, 0.6, 0.0, 0.6};
 __constant__ double k_aa_y[5] = {0.0, 0.3, 0.0, 0.6, 0.6};
 
+/* Two steps of render_tile for ground_tile.  (render_tile keeps its own lines: taking them from here reorders
+ * instructions in instances that have no ground path, and those are to stay what every measurement was taken on.) */
+/* local row -> frame row under interleaved strips */
+DEV uint32_t frame_row(const RenderParams &P, const uint32_t lr)
+{
+    uint32_t y = lr;
+    if (P.strip_world > 1) {
+        const uint32_t sh = P.strip_height;
+        y = ((lr / sh) * P.strip_world + P.strip_rank) * sh + lr % sh;
+    }
+    return y;
+}
+
+/* a finished pixel, float RGB or display-encoded */
+DEV void store_pixel(const RenderParams &P, const size_t pixel_index, const F3 accum)
+{
+    if (P.out_rgb32) { /* wave-uniform */
+        /* Color.toRGB32 via convertTo8bit_sRGB_Cached (rt/color.d:154-162,209-214), fused: the display frame
+         * needs neither a float frame in HBM nor a second kernel (c2rt_render_frame_rgb32) */
+        const float c3[3] = {accum.r, accum.g, accum.b};
+        uint32_t ch[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ch[c] = !(c3[c] > 0) ? 0u : (c3[c] >= 1 ? 255u : (uint32_t)P.srgb_lut[(int)(c3[c] * 4096.0f)]);
+        P.out_rgb32[pixel_index] = ch[2] | (ch[1] << 8) | (ch[0] << 16);
+    } else {
+        /* one 12-byte store per lane (global_store_dwordx3): 8 lanes cover a tile row's 96 contiguous bytes */
+        typedef float __attribute__((ext_vector_type(3), aligned(4))) f3_t;
+        f3_t v3;
+        v3.x = accum.r;
+        v3.y = accum.g;
+        v3.z = accum.b;
+        *reinterpret_cast<f3_t *>(P.out + pixel_index * 3) = v3;
+    }
+}
+
+/* ------------------------------------------------------------------ */
+/* ground-only tiles: a straight-line path of their own (lean:: only)     */
+/* ------------------------------------------------------------------ */
+/*
+ * A tile whose primary rays AND shadow rays towards the one light can reach the ground plane only (bit 1 of the
+ * mask table's third word), in a frame the host found eligible (RenderParams::ground_fast: Lambert over a bitmap, a
+ * checker or a plain colour, at most one light), rendered whole — tap loop, samples, store — by code that knows all of
+ * that.  It performs the IEEE operations of the general path for such a tile, on the same operands, in the same
+ * order: screen_ray, normalized, the ground branch of raytrace(), the texture, shade() / light_terms for the one
+ * light, the ground_only pre-check of test_visibility, the tap accumulation, the store; and every oob_note of that
+ * path, so that a lane outside a lean window sends the tile to exact:: as before.  What it does not carry: a Hit, a
+ * Surf, `closest`, the node loop, the surface pass, CSG, LDS, the Phong and Procedure2 code and their libm calls.
+ * Nothing joins a general path behind the trace, so the ground node's material, its texture descriptor and the light
+ * are wave-uniform values in scalar registers — read once per sample through the re-read kernel-argument pointer,
+ * as render_tile's tap loop does —, texture type and light are scalar branches and the texel addresses are built
+ * from a scalar width, height and offset.
+ *
+ * Three folds through the known normal n = (0, 1, 0).  Each holds for every lane whose operands passed the lean
+ * windows (any other lane voids the tile; none of this can fault):
+ *   d  (the normalised screen ray) and lightDir are FINITE: sqmag(raw) and |lightPos - p|^2 are noted by
+ *     normalized() / len_inv and lie in [2^-240, 2^240), so the components are finite and so is the reciprocal length.
+ *   dot(d, n) < 0  <=>  d.y < 0:  dot = (d.x * 0 + d.y * 1) + d.z * 0; the outer products are zeros of some sign,
+ *     d.y * 1 is d.y, and x + (+-0) is x for x != 0.  For d.y == +-0 the sum is a zero and both sides are false.
+ *   N * 1e-6 = (+-0, +-1e-6, +-0):  1 * 1e-6 and -1 * 1e-6 are exact.  `from` enters the pre-check only: from.y as
+ *     computed there; from.x, from.z through |lightPos.x - (p.x + (+-0))| < 1e150, and p.x + (+-0) differs from p.x
+ *     at most in the sign of a zero, which changes lightPos.x - from.x at most in the sign of a zero: |lv.x| decides.
+ *   cosTheta = dot(lightDir, N) is read as `cosTheta > 0` and, when that holds, (float)cosTheta:
+ *     dot = (lightDir.x * (+-0) + lightDir.y * (+-1)) + lightDir.z * (+-0) = +-lightDir.y when that is not zero, and
+ *     a zero of some sign (not > 0, never converted) when it is.  lightDir.x and lightDir.z are not needed at all.
+ *
+ * Bail-out: when the pre-check fails for a sample (`__all` over the lanes that hit the plane: the light on the far
+ * side of the floor from the eye, a lane with raw.y out of range) the function returns kGroundBail before anything
+ * is written and the same wave renders the tile through the code below, as if the path did not exist.
+ * Returns per lane; the lanes inside the frame agree (a lane outside it reports kGroundDone: it has nothing to do).
+ */
+enum { kGroundDone = 0, kGroundRedo = 1, kGroundBail = 2 };
+template <int PO>
+DEV int ground_tile(const RenderParams &P, KArgs K, const uint32_t trow, const uint32_t bcol)
+{
+    static_assert(!(PO & kSpecPlanes), "the planes-only instances have no mask table");
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const uint32_t tcol = bcol * kWavesPerBlock + wave; /* (trow, bcol: the tile, trow < P.tiles_y — render_tile) */
+    const uint32_t x = tcol * kTileW + (lane % kTileW);
+    const uint32_t lr0 = trow * kTileH + (lane / kTileW);
+    if (x >= P.width || lr0 >= P.local_rows) return kGroundDone;
+    const uint32_t lr = lr0 + P.row_offset;
+    const uint32_t y = frame_row(P, lr);
+    const uint32_t ntaps = P.taps;
+
+    Oob bad;
+    oob_init(bad);
+    F3 accum = mkf(0, 0, 0);
+#pragma unroll 1
+    for (uint32_t s = 0; s < ntaps; ++s) {
+        KArgs Kt = K;
+        asm volatile("" : "+s"(Kt));
+        const RenderParams &Pt = *(const RenderParams *)Kt;
+        Rng rng = {0u, 0, 0};
+        D3 o, raw;
+        screen_ray<0>(bad, Pt, (double)x + k_aa_x[s], (double)y + k_aa_y[s], 0, rng, o, raw);
+        const D3 d = normalized(bad, raw);
+        /* Node.intersect + Plane.intersect on the ground node: raytrace()'s ground branch */
+        NodeP N = (NodeP)Pt.nodes + Pt.ground_node;
+        double len, inv;
+        len_inv_unit(bad, sqmag(d), len, inv);
+        const D3 dn = mk(d.x * inv, d.y * inv, d.z * inv);
+        const double gy = N->g.p[0], limit = N->g.p[1];
+        const bool away = ((o.y > gy) & (dn.y > -1e-9)) | ((o.y < gy) & (dn.y < 1e-9));
+        const double rden = rcp_refined(-dn.y);
+        const double mult = div_r(bad, o.y - gy, -dn.y, rden);
+        const D3 p = o + dn * mult;
+        const bool miss = away | (mult > 1e99 * len) | (fabs(p.x) > limit) | (fabs(p.z) > limit);
+        F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
+        bool bail = false;
+        if (!miss) {
+            /* shade(): Lambert, u = p.x, v = p.z, N = faceforward((0, 1, 0)) */
+            Mat mat;
+            load_mat(N, mat);
+            const F3 diffuse = mat.tex_type == C2RT_TEX_CHECKER ? checker_color(mat, p.x, p.z)
+                             : (mat.tex_type >= 0 ? bitmap_color(Pt, mat, p.x, p.z) : mat.color);
+            F3 lightContrib = mkf(Pt.ambient[0], Pt.ambient[1], Pt.ambient[2]);
+            if (Pt.n_lights) {
+                LightP L = (LightP)Pt.lights;
+                F3 avgColor = mkf(0, 0, 0);
+                if (L->lit & 1u) {
+                    const bool up = d.y < 0; /* N = (0, 1, 0); otherwise (-0, -1, -0) */
+                    const D3 lightPos = ld3(L->pos);
+                    const double from_y = p.y + (up ? 1e-6 : -1e-6);
+                    /* light_terms */
+                    const D3 lv = lightPos - p;
+                    const double r2 = sqmag(lv);
+                    double rlen, rinv;
+                    len_inv(bad, r2, rlen, rinv);
+                    const double ldy = lv.y * rinv;
+                    const double cosTheta = up ? ldy : -ldy;
+                    const F3 baseLight = base_light(bad, L, r2);
+                    /* test_visibility's ground_only pre-check: plane_points_away for the ground plane */
+                    const double raw_y = lightPos.y - from_y, ground_y = Pt.ground_y;
+                    const bool sane = (fabs(lv.x) < 1e150) & (fabs(lv.z) < 1e150);
+                    const bool rises = (raw_y > 1e-150) & (raw_y < 1e150), falls = (raw_y < -1e-150) & (raw_y > -1e150);
+                    bail = !__all(sane & (((from_y > ground_y) & rises) | ((from_y < ground_y) & falls)));
+                    if (cosTheta > 0) avgColor = avgColor + baseLight * (float)cosTheta;
+                }
+                lightContrib = lightContrib + avgColor;
+            }
+            c = diffuse * lightContrib;
+        }
+        if (__ballot(bail)) return kGroundBail;
+        accum = s == 0 ? c : accum + c;
+    }
+    if (ntaps > 1) accum = accum / (float)ntaps;
+    if (__ballot(oob_any(bad))) return kGroundRedo;
+    store_pixel(P, (size_t)(P.frame_rows ? y : lr) * P.width + x, accum);
+    return kGroundDone;
+}
+
 /*
  * Frame kernel: Renderer.renderRT passes 2 and 3b (rt/renderer.d:133-142,
  * 183-186) fused — all taps of a pixel are accumulated in registers in the
@@ -1907,6 +2074,20 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
             smask0 = m.y;
             primary_ground = (m.z & 1u) != 0;
             ground_only = (m.z & 2u) != 0;
+        }
+    }
+
+    /* Ground-only tile of an eligible frame: ground_tile renders it, unless a sample's shadow pre-check fails — then
+     * nothing has been written and the tile goes on below.  The call takes nothing but the kernel-argument pointer and
+     * the tile's row and block column, through an empty asm, so that the path shares no value with the code below and
+     * nothing of it stays live on its behalf (as render_one does for exact::). */
+    if constexpr (kLean && LEVELS <= 1 && !DOF && !MLC && !CNT && !(PO & kSpecPlanes) && !C2RT_TILE_STATS) {
+        if (P.ground_fast && ground_only) { /* wave-uniform */
+            KArgs Kg = K;
+            uint32_t trow_g = trow, bcol_g = bcol;
+            asm volatile("" : "+s"(Kg), "+s"(trow_g), "+s"(bcol_g));
+            const int g = ground_tile<PO>(*(const RenderParams *)Kg, Kg, trow_g, bcol_g);
+            if (!__ballot(g == kGroundBail)) return g == kGroundRedo;
         }
     }
 

@@ -909,6 +909,18 @@ void fill_params(const ScenePlan &plan, const DeviceTables &dev, const DiagKnobs
     if (debug_cull & 1) p.n_cull = 0;
     if (debug_cull & 2) p.ground_node = -1;
     if (debug_cull & 4) p.n_cull_lights = 0;
+    /* Ground-only tiles through lean::ground_tile (c2rt_trace.inc): only where the frame has a mask table (which rules
+     * out depth of field, stereo and the prepass preview) and a ground node, at most one light (the instances that
+     * carry the path), no counted rays (those frames run exact:: throughout), and a floor the path is specialised
+     * for — Lambert over a bitmap, a checker or a plain colour: no libm call (Phong's pow, Procedure2's sin) enters
+     * it.  Diagnostics build: C2RT_DEBUG_CULL bit 4 leaves every tile to the general path (A/B runs, tests). */
+    p.ground_fast = 0;
+    if (p.n_cull && p.ground_node >= 0 && (uint32_t)p.ground_node < plan.nodes.size() && plan.n_lights <= 1 && !o->count_rays &&
+        !cam->dof && cam->stereo_separation == 0 && !(debug_cull & 16)) {
+        const DevMat &m = plan.nodes[(size_t)p.ground_node].mat;
+        const bool tex_ok = m.tex_type < 0 || m.tex_type == C2RT_TEX_CHECKER || m.tex_type == C2RT_TEX_BITMAP;
+        p.ground_fast = (m.shader_type == C2RT_SHADER_LAMBERT && tex_ok) ? 1u : 0u;
+    }
 }
 
 /* Screen rectangle of a node for this frame: the projection of the 8 world-space
