@@ -71,7 +71,7 @@ aa_detect_kernel(const float *__restrict__ frame, uint8_t *__restrict__ needs_aa
 constexpr size_t kAaColourBytes = (size_t)kWave * 4 * 3 * sizeof(float), kAaListBytes = kWave;
 
 template <int LEVELS, bool MLC>
-__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, MLC)
+__global__ void __launch_bounds__(kWave) C2RT_WAVES_QUERY(LEVELS, MLC)
 aa_refine_kernel(const RenderParams P, float *__restrict__ frame, const uint8_t *__restrict__ needs_aa, const uint32_t tiles_x)
 {
     using namespace exact;

@@ -52,8 +52,8 @@ struct FrameScratch {
     size_t batch_bytes = 0;
 };
 
-/* Environment hooks (A/B measurement and test knobs: C2RT_EXACT, C2RT_NO_IDN, C2RT_DEBUG_CULL, C2RT_CSG_FIRST_CAP,
- * C2RT_HOST_*) exist in the DIAGNOSTICS build only — chess2rt_amd/libc2rt_diag.so, this file compiled with
+/* Environment hooks (A/B measurement and test knobs: C2RT_EXACT, C2RT_DEBUG_CULL, C2RT_CSG_FIRST_CAP,
+ * C2RT_HOST_DIRECT_STORE) exist in the DIAGNOSTICS build only — chess2rt_amd/libc2rt_diag.so, this file compiled with
  * -DC2RT_DIAG=1 over the same kernel objects (Makefile).  The product library reads no environment variable: a
  * drop-in renderer does not change kernels on a stray variable (tests/test_abi_exports.py checks that libc2rt.so
  * does not even import getenv). */
@@ -72,7 +72,6 @@ static const DiagKnobs &diag_knobs()
     static const DiagKnobs k = [] {
         DiagKnobs v;
         if (const char *e = diag_env("C2RT_EXACT")) v.exact = e[0] == '1';
-        if (const char *e = diag_env("C2RT_NO_IDN")) v.no_idn = e[0] == '1';
         if (const char *e = diag_env("C2RT_DEBUG_CULL")) v.debug_cull = std::atoi(e);
         if (const char *e = diag_env("C2RT_CSG_FIRST_CAP")) v.csg_first_cap = std::atoi(e);
         if (v.debug_cull) std::fprintf(stderr, "libc2rt: diagnostics hook C2RT_DEBUG_CULL=%d is active (culling partly disabled; frames are unchanged, slower)\n", v.debug_cull);
@@ -94,7 +93,6 @@ struct c2rt_ctx {
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;              /* D2H of finished chunks */
     hipEvent_t chunk_done[kMaxChunks] = {};
-    hipStream_t copy_stream2 = nullptr; /* chunks alternate between two copy streams (two SDMA engines) */
     std::vector<std::pair<float *, size_t>> pinned; /* c2rt_pin_host_buffer */
 
     bool has_scene = false;
@@ -236,7 +234,7 @@ void frame_needs(RenderParams &p, size_t &entries, size_t &blocks)
 {
     p.mask_rows = p.local_rows;
     entries = p.n_cull && p.local_rows ? tile_mask_entries(p) : 0;
-    blocks = (size_t)p.blocks_x * ((p.tiles_y + 7u) / 8u * 8u);
+    blocks = padded_grid_blocks(p.tiles_y, p.blocks_x);
 }
 
 /* Wires frame i of the frames that share scratch slot `sc` (a single frame: i = 0; a batch: n tables and lists side by
@@ -398,7 +396,7 @@ int plan_posed_frames(c2rt_ctx *ctx, const c2rt_scene_pose *poses, uint32_t n_fr
  * copy.  One launch runs one instance: the frames are laid out in the table as up to two groups by what the launcher
  * cannot share — the plane instances of a single-light scene (launch_render_batch_level) — and a group that mixes
  * identity-only frames with others runs the general instance (the launcher's copy of a block says so; the instances
- * are held to the same bits, C2RT_NO_IDN). */
+ * are held to the same bits: counted frames run the general one, tests/conftest.py). */
 int render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const std::vector<std::unique_ptr<PosedFrame>> *posed,
                          uint32_t n_frames, const c2rt_render_opts *opts, float *out_dev, hipStream_t stream)
 {
@@ -576,7 +574,6 @@ int c2rt_init(int device, c2rt_ctx **out)
     HIP_TRY(ctx, hipSetDevice(device));
     HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
-    HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy_stream2, hipStreamNonBlocking));
     for (int i = 0; i < kMaxChunks; ++i) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->chunk_done[i], hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_ready, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming));
@@ -657,7 +654,6 @@ void c2rt_destroy(c2rt_ctx *ctx)
     if (ctx->ev_inflight) (void)hipEventDestroy(ctx->ev_inflight);
     if (ctx->stream) { (void)hipStreamSynchronize(ctx->stream); (void)hipStreamDestroy(ctx->stream); }
     if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); }
-    if (ctx->copy_stream2) { (void)hipStreamSynchronize(ctx->copy_stream2); (void)hipStreamDestroy(ctx->copy_stream2); }
     for (hipEvent_t e : ctx->chunk_done)
         if (e) (void)hipEventDestroy(e);
     for (const auto &pb : ctx->pinned) (void)hipHostUnregister(pb.first);
@@ -749,24 +745,20 @@ int c2rt_update_scene(c2rt_ctx *ctx, const c2rt_scene_pose *pose, void *hip_stre
  * pageable memory: one launch, one copy — chunked copies into pageable memory are slower than one
  * (measured).  ctx->frame (ensure_staging) holds the float rows OR the display words, whichever is asked for;
  * a frame the kernel stores straight into the page-locked destination has no staging buffer at all. */
-/* Host-output pipeline parameters (defaults measured on MI355X, profiles/r03_variants.md); the environment
- * variables exist for that measurement, in the diagnostics build only: C2RT_HOST_CHUNK_MB, C2RT_HOST_FIRST_FRAC,
- * C2RT_HOST_COPY_STREAMS, C2RT_HOST_DIRECT_STORE. */
+/* Host-output pipeline, measured on MI355X (profiles/r03_variants.md).  Chunk size, 4K float frame (99.5 MB), ms by
+ * chunk count: 10 chunks 2.12, 9 2.04, 8 (this) 1.96, 7 1.98, 6 1.98, 5 2.02, 4 2.19 (copy alone: 1.75).  A smaller
+ * first chunk and a second copy stream: no gain (the pipeline is copy-bound from the first copy on). */
+constexpr size_t kHostChunkBytes = 13u << 20;
 struct HostKnobs {
-    size_t chunk_bytes = 13u << 20; /* 4K float frame (99.5 MB), ms by chunk count: 10 chunks 2.12, 9 2.04, 8 (this) 1.96, 7 1.98, 6 1.98, 5 2.02, 4 2.19 (copy alone: 1.75) */
-    double first_frac = 1.0;        /* a smaller first chunk: no gain (the pipeline is copy-bound from the first copy on) */
-    int copy_streams = 1;           /* two copy streams: no gain */
     /* kernel stores straight into the page-locked frame: 0 never, 1 the display-word frame (4 B/pixel: 1.30 ms
-     * against 1.60 chunked; the float frame's 12-byte stores reach only 44 GB/s: 2.27 against 2.02), 2 both */
+     * against 1.60 chunked; the float frame's 12-byte stores reach only 44 GB/s: 2.27 against 2.02), 2 both.
+     * C2RT_HOST_DIRECT_STORE sets it in the diagnostics build (tests/test_gpu_parity.py) */
     int direct_store = 1;
 };
 static const HostKnobs &host_knobs()
 {
     static const HostKnobs k = [] {
         HostKnobs v;
-        if (const char *e = diag_env("C2RT_HOST_CHUNK_MB")) { const double mb = std::atof(e); if (mb >= 0.25 && mb <= 1024) v.chunk_bytes = (size_t)(mb * (1u << 20)); }
-        if (const char *e = diag_env("C2RT_HOST_FIRST_FRAC")) { const double f = std::atof(e); if (f > 0 && f <= 1) v.first_frac = f; }
-        if (const char *e = diag_env("C2RT_HOST_COPY_STREAMS")) v.copy_streams = std::atoi(e) > 1 ? 2 : 1;
         if (const char *e = diag_env("C2RT_HOST_DIRECT_STORE")) v.direct_store = std::atoi(e);
         return v;
     }();
@@ -844,24 +836,17 @@ static int render_to_host(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2r
     if (const int st = ensure_staging(ctx, (size_t)rows * row_px * px_bytes)) return st;
     char *staging = reinterpret_cast<char *>(ctx->frame);
     if (out_rgb) p.out = ctx->frame; else p.out_rgb32 = reinterpret_cast<uint32_t *>(ctx->frame);
-    /* Into a page-locked frame: row chunks, chunk i crossing PCIe on a copy stream while chunk i+1 renders.
+    /* Into a page-locked frame: equal row chunks, chunk i crossing PCIe on the copy stream while chunk i+1 renders.
      * The copy (99.5 MB of float frame at ~57 GB/s = 1.75 ms at 4K) is longer than the render (1.15 ms), so
-     * the frame time is the first chunk's render + the copies back to back + whatever keeps them from being
-     * back to back: a SMALL first chunk, then equal ones; two copy streams so that one copy's setup hides
-     * behind the other's transfer.  Into pageable memory: one launch, one copy (chunked copies into pageable
-     * memory are slower than one, measured).  The stop flag is polled between chunks. */
+     * the frame time is the first chunk's render + the copies back to back.  Into pageable memory: one launch,
+     * one copy (chunked copies into pageable memory are slower than one, measured).  The stop flag is polled
+     * between chunks. */
     const size_t total_bytes = (size_t)rows * dst_row_bytes;
-    uint32_t want = (uint32_t)((total_bytes + knobs.chunk_bytes - 1) / knobs.chunk_bytes);
+    uint32_t want = (uint32_t)((total_bytes + kHostChunkBytes - 1) / kHostChunkBytes);
     if (want < 1) want = 1;
     if (want > (uint32_t)kMaxChunks - 1) want = kMaxChunks - 1;
     uint32_t chunk = is_pinned ? ((rows + want - 1) / want + kTileH - 1) / kTileH * kTileH : rows;
     if (chunk < 64) chunk = 64;
-    uint32_t first = chunk;
-    if (is_pinned && want > 1) {
-        first = (uint32_t)(chunk * knobs.first_frac + kTileH - 1) / kTileH * kTileH;
-        if (first < 64) first = 64;
-        if (first > chunk) first = chunk;
-    }
     bool cancelled = false;
     int n_chunks = 0;
     { /* one mask table for the whole frame: every chunk's launch reads its rows of it */
@@ -870,7 +855,7 @@ static int render_to_host(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2r
     }
     for (uint32_t off = 0; off < rows && n_chunks < kMaxChunks; ++n_chunks) {
         if (stop_flag && *stop_flag) { cancelled = true; break; }
-        uint32_t n = n_chunks == 0 ? first : chunk;
+        uint32_t n = chunk;
         if (n > rows - off || n_chunks == kMaxChunks - 1) n = rows - off;
         p.row_offset = off;
         p.local_rows = n;
@@ -878,15 +863,13 @@ static int render_to_host(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2r
         if (n < rows) p.row_group_start = 0; /* the rotation is relative to the whole frame's rows */
         const int e = launch_prepared(ctx, p, variant, ctx->stream);
         if (e != 0) return fail(ctx, C2RT_ERR_HIP, "render kernel launch: %s", hipGetErrorString((hipError_t)e));
-        hipStream_t cs = (knobs.copy_streams > 1 && (n_chunks & 1)) ? ctx->copy_stream2 : ctx->copy_stream;
         HIP_TRY(ctx, hipEventRecord(ctx->chunk_done[n_chunks], ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(cs, ctx->chunk_done[n_chunks], 0));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->copy_stream, ctx->chunk_done[n_chunks], 0));
         HIP_TRY(ctx, hipMemcpyAsync(dst + (size_t)off * dst_row_bytes, staging + (size_t)off * dst_row_bytes, (size_t)n * dst_row_bytes,
-                                    hipMemcpyDeviceToHost, cs));
+                                    hipMemcpyDeviceToHost, ctx->copy_stream));
         off += n;
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->copy_stream2));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (cancelled) return fail(ctx, C2RT_ERR_CANCELLED, "stop requested during the frame");
     if (opts->count_rays) ctx->counters_valid = true;

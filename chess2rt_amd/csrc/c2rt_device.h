@@ -12,6 +12,7 @@
 #ifndef C2RT_DEVICE_H
 #define C2RT_DEVICE_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/c2rt.h"
@@ -21,21 +22,16 @@ namespace c2rt {
 
 constexpr int kMaxCsgHits = C2RT_MAX_CSG_HITS; /* per CSG child per ray */
 constexpr int kCsgEntries = 2 * kMaxCsgHits;
-#ifndef C2RT_TILE_W
-#define C2RT_TILE_W 8
-#endif
-constexpr int kTileW = C2RT_TILE_W, kTileH = 64 / C2RT_TILE_W; /* one wavefront = one 8x8 pixel tile */
+constexpr int kTileW = 8, kTileH = 8; /* one wavefront = one 8x8 pixel tile */
 constexpr int kWave = 64;
+/* Blocks of a frame kernel's grid over `tile_rows` tile rows of `blocks_x` blocks: blocks b and b + 8 run on the same
+ * XCD, which renders tile rows x, x + 8, ... (c2rt_trace.inc: render_tile), so the rows are rounded up to whole groups
+ * of eight.  Retry lists and mask tables are sized by it.  Host code only. */
+inline size_t padded_grid_blocks(uint32_t tile_rows, uint32_t blocks_x) { return (size_t)((tile_rows + 7u) / 8u * 8u) * blocks_x; }
 constexpr int kMaxCullNodes = 32;  /* nodes beyond this are always tested */
 constexpr int kHullEdges = 6;      /* a projected box is at most a hexagon */
-#ifndef C2RT_MAX_CULL_LIGHTS
-#define C2RT_MAX_CULL_LIGHTS 4
-#endif
-constexpr int kMaxCullLights = C2RT_MAX_CULL_LIGHTS; /* lights beyond this get no shadow-ray culling */
-#ifndef C2RT_WAVES_PER_BLOCK
-#define C2RT_WAVES_PER_BLOCK 1
-#endif
-constexpr int kWavesPerBlock = C2RT_WAVES_PER_BLOCK; /* horizontally adjacent tiles per workgroup */
+constexpr int kMaxCullLights = 4;  /* lights beyond this get no shadow-ray culling */
+constexpr int kWavesPerBlock = 1;  /* horizontally adjacent tiles per workgroup */
 constexpr int kBlockThreads = kWave * kWavesPerBlock;
 /* LDS bytes per entry of a wavefront's CSG hit stack: dist[64] (8 B) + tag[64] (2 B) */
 constexpr int kCsgLdsPerEntry = kWave * (8 + 2);

@@ -33,7 +33,7 @@ static_assert(sizeof(RenderParams) + sizeof(c2rt_hit_planes) + 16 <= 4096, "the 
 static_assert(sizeof(c2rt_hit_planes) == 56, "ABI layout of c2rt_hit_planes");
 
 template <int LEVELS, bool MLC>
-__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, MLC)
+__global__ void __launch_bounds__(kWave) C2RT_WAVES_QUERY(LEVELS, MLC)
 hit_planes_kernel(const RenderParams P, const c2rt_hit_planes out, const uint32_t row0, const uint32_t rows, const uint32_t tiles_x)
 {
     using namespace exact;

@@ -35,35 +35,26 @@
 namespace c2rt {
 namespace {
 
-#ifndef C2RT_LEAN
-#define C2RT_LEAN 1 /* 0: the production instances run exact:: only (A/B builds) */
-#endif
 /* The deepest CSG nesting whose instances carry the lean:: copy.  Depth 4 does not: measured with and without it
  * at two waves per SIMD (10.39 / 10.42 ms on csg_stress) and at three (8.60 / 8.56) — no difference, twice the
  * code. */
-#ifndef C2RT_LEAN_MAX_LEVELS
-#define C2RT_LEAN_MAX_LEVELS 3
-#endif
+constexpr int kLeanMaxLevels = 3;
 
 /* One tile: optimistically through lean::, and again through exact:: — by the same wave, with all of its
  * lanes — if a lane reported an operand outside a lean window (c2rt_trace.inc).  The instances launched when
  * rays are being counted (CNT; tests/conftest.py renders every counted frame with BOTH instances and insists
  * on the same bits) run exact:: only, so that suite compares the two. */
-/* 1: in the instances named below the cold half reads its arguments through a kernarg pointer the optimiser
- * cannot see through, so that nothing but that pointer and the tile index stays live across the lean half on its
- * behalf.  Without it values both halves use (kernel arguments, table pointers) are kept in SGPRs from the top
+/* In the instances render_one names (depth 0 and 1, no depth of field, not plane-only) the cold half reads its
+ * arguments through a kernarg pointer the optimiser cannot see through, so that nothing but that pointer and the
+ * tile index stays live across the lean half on its behalf.  Without it values both halves use (kernel arguments, table pointers) are kept in SGPRs from the top
  * of the kernel and the lean half spills around them: render_kernel_idn<1> holds 254 v_writelane / v_readlane in
  * its lean half without, 191 with (lean:: compiled alone: 184); lecture5.sdl 4K at 1 sample per pixel 0.245 ->
  * 0.239 ms, 1080p 72 -> 71 us, 4K x5 0.999 -> 0.996 ms.  Depth-of-field, plane-only and nested-CSG instances
  * are allocated no better or worse with it (profiles/r04_variants.md, step 12) and keep the plain call. */
-#ifndef C2RT_REDO_OPAQUE
-#define C2RT_REDO_OPAQUE 1
-#endif
-
 template <int LEVELS, int DOF, bool MLC, int PO, bool CNT>
 DEV void render_one(const RenderParams &P, KArgs K, const uint32_t b)
 {
-    if constexpr (CNT || !C2RT_LEAN || LEVELS > C2RT_LEAN_MAX_LEVELS) {
+    if constexpr (CNT || LEVELS > kLeanMaxLevels) {
         exact::render_tile<LEVELS, DOF, MLC, PO, CNT>(P, (exact::KArgs)K, b);
     } else {
         if (!P.force_exact) { /* wave-uniform */
@@ -71,7 +62,7 @@ DEV void render_one(const RenderParams &P, KArgs K, const uint32_t b)
             if (!__ballot(redo)) return;
             if (threadIdx.x % kWave == 0) atomicAdd(P.redo_counter, 1ull); /* c2rt_get_exact_redos */
         }
-        if constexpr (C2RT_REDO_OPAQUE && LEVELS <= 1 && !DOF && PO != lean::kSpecPlanes) {
+        if constexpr (LEVELS <= 1 && !DOF && PO != lean::kSpecPlanes) {
             KArgs K2 = K;
             uint32_t b2 = b;
             asm volatile("" : "+s"(K2), "+s"(b2));
@@ -106,7 +97,7 @@ DEV void render_body(const RenderParams &P, KArgs K)
 }
 
 template <int LEVELS, int DOF, bool MLC, bool CNT>
-__global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(LEVELS, DOF, MLC) render_kernel(const RenderParams P)
+__global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(LEVELS, DOF, MLC) render_kernel(const RenderParams P)
 {
     render_body<LEVELS, DOF, MLC, 0, CNT>(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr());
 }
@@ -115,15 +106,15 @@ __global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(LEVELS, DOF, MLC) r
  * reference ships) with at most one light and no depth of field: lean::kSpecIdentity (c2rt_trace.inc) — production
  * instances only; counted frames run the general instance, and the tests compare the two. */
 template <int LEVELS>
-__global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(LEVELS, 0, false) render_kernel_idn(const RenderParams P)
+__global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(LEVELS, 0, false) render_kernel_idn(const RenderParams P)
 {
     render_body<LEVELS, 0, false, lean::kSpecIdentity, false>(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr());
 }
 
 /* The depth-of-field / stereo instance carries the lens sampling state on top of
- * the tracer's and has its own register budget (C2RT_OCC_DOF). */
+ * the tracer's and has its own register budget (occ_of). */
 template <int LEVELS, bool MLC, int MODE, bool CNT>
-__global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(LEVELS, MODE, MLC) render_kernel_dof(const RenderParams P)
+__global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(LEVELS, MODE, MLC) render_kernel_dof(const RenderParams P)
 {
     render_body<LEVELS, MODE, MLC, 0, CNT>(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr());
 }
@@ -131,7 +122,7 @@ __global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(LEVELS, MODE, MLC) 
 /* Scenes made of axis planes only (RenderParams::planes_only — lecture4.sdl, zaphod.sdl): the
  * instances in which a plane's miss is decided before the ray is normalised (plane_points_away). */
 template <int DOF, bool CNT>
-__global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(0, DOF, false) render_kernel_planes(const RenderParams P)
+__global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(0, DOF, false) render_kernel_planes(const RenderParams P)
 {
     render_body<0, DOF, false, lean::kSpecPlanes, CNT>(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr()); /* at most one light (launch_render_level); planes have no boxes, hence no culling masks */
 }
@@ -154,21 +145,21 @@ DEV KArgs batch_block(const RenderParams *table)
 }
 
 template <int LEVELS, bool MLC>
-__global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(LEVELS, 0, MLC) render_kernel_batch(const RenderParams *table)
+__global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(LEVELS, 0, MLC) render_kernel_batch(const RenderParams *table)
 {
     const KArgs K = batch_block(table);
     render_body<LEVELS, 0, MLC, 0, false>(*(const RenderParams *)K, K);
 }
 
 template <int LEVELS>
-__global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(LEVELS, 0, false) render_kernel_idn_batch(const RenderParams *table)
+__global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(LEVELS, 0, false) render_kernel_idn_batch(const RenderParams *table)
 {
     const KArgs K = batch_block(table);
     render_body<LEVELS, 0, false, lean::kSpecIdentity, false>(*(const RenderParams *)K, K);
 }
 
 #if C2RT_UNIT == 0 /* (not a template: it would be compiled into every unit) */
-__global__ void __launch_bounds__(kBlockThreads) C2RT_OCC_OF(0, 0, false) render_kernel_planes_batch(const RenderParams *table)
+__global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(0, 0, false) render_kernel_planes_batch(const RenderParams *table)
 {
     const KArgs K = batch_block(table);
     render_body<0, 0, false, lean::kSpecPlanes, false>(*(const RenderParams *)K, K);
@@ -290,12 +281,7 @@ __global__ void __launch_bounds__(256) tile_masks_batch_kernel(const RenderParam
  * overflow list, render_body) and the LDS of the hit stacks */
 static uint32_t frame_grid_x(const RenderParams &p)
 {
-#if C2RT_XCD_SWIZZLE
-    const uint32_t tiles_y_pad = (p.tiles_y + 7u) / 8u * 8u;
-#else
-    const uint32_t tiles_y_pad = p.tiles_y;
-#endif
-    return p.retry_mode ? 2048u : p.blocks_x * tiles_y_pad;
+    return p.retry_mode ? 2048u : (uint32_t)padded_grid_blocks(p.tiles_y, p.blocks_x);
 }
 static size_t frame_lds(const RenderParams &p) { return (size_t)p.csg_cap * kCsgLdsPerEntry * kWavesPerBlock; }
 
@@ -384,7 +370,7 @@ int launch_render(const RenderParams &p, const KernelVariant &v, void *stream)
 size_t tile_mask_entries(const RenderParams &p)
 {
     const uint32_t tile_rows = (p.mask_rows + kTileH - 1) / kTileH;
-    return (size_t)((tile_rows + 7u) / 8u * 8u) * p.blocks_x * kWavesPerBlock;
+    return padded_grid_blocks(tile_rows, p.blocks_x) * kWavesPerBlock;
 }
 
 int launch_tile_masks(const RenderParams &p, const VoidCull &vc, const SphereCull &sc, uint32_t *table, void *stream)

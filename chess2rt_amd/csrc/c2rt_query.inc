@@ -17,7 +17,7 @@ static_assert(sizeof(RenderParams) + 64 <= 4096, "the kernel-argument segment ho
 
 template <int LEVELS, bool MLC>
 constexpr int occ_query() { return LEVELS >= 2 ? 2 : occ_of<LEVELS, 0, MLC>(); }
-#define C2RT_OCC_QUERY(L, M) __attribute__((amdgpu_waves_per_eu(occ_query<L, M>(), occ_query<L, M>())))
+#define C2RT_WAVES_QUERY(L, M) __attribute__((amdgpu_waves_per_eu(occ_query<L, M>(), occ_query<L, M>())))
 
 
 /* The ray through the screen point (x, y) — a pixel's integer corner, plus its tap offset where there is one — of the

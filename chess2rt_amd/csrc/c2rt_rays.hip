@@ -45,7 +45,7 @@ DEV void load6(const void *rec, exact::D3 &a, exact::D3 &b)
 
 /* Ray i = trace(ray, TraceType.Ray), rt/renderer.d:325-376, depth 0.  hits / rgb: nullable, not both (wave-uniform). */
 template <int LEVELS, bool MLC>
-__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, MLC)
+__global__ void __launch_bounds__(kWave) C2RT_WAVES_QUERY(LEVELS, MLC)
 trace_rays_kernel(const RenderParams P, const c2rt_ray *__restrict__ rays, const uint64_t n, c2rt_ray_hit *__restrict__ hits, float *__restrict__ rgb)
 {
     using namespace exact;
@@ -104,7 +104,7 @@ trace_rays_kernel(const RenderParams P, const c2rt_ray *__restrict__ rays, const
 
 /* Segment i = Scene.testVisibility(from, to), rt/scene.d:62-78: full node mask, no ground shortcut */
 template <int LEVELS>
-__global__ void __launch_bounds__(kWave) C2RT_OCC_QUERY(LEVELS, false)
+__global__ void __launch_bounds__(kWave) C2RT_WAVES_QUERY(LEVELS, false)
 test_visibility_kernel(const RenderParams P, const c2rt_segment *__restrict__ seg, const uint64_t n, uint8_t *__restrict__ visible)
 {
     using namespace exact;

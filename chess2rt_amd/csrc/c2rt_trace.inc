@@ -193,12 +193,6 @@ DEV F3 operator*(F3 a, F3 b) { return mkf(a.r * b.r, a.g * b.g, a.b * b.b); }
 DEV F3 operator*(F3 a, float f) { return mkf(a.r * f, a.g * f, a.b * f); }
 DEV F3 operator/(F3 a, float f) { return mkf(a.r / f, a.g / f, a.b / f); }
 
-/* a double held by lane `l`, as a wave-uniform value */
-DEV double read_lane(double v, int l)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-
 /* x86 cvttsd2si / cvttss2si results for out-of-range inputs, which is what
  * the reference binary computes for cast(int) / cast(size_t). */
 DEV int d2i_x86(double d)
@@ -1073,36 +1067,6 @@ DEV void hit_surface(const Ctx &cx, NodeP N, const Hit &h, bool want_uv, Surf &s
 /* per-frame culling masks (host-computed rectangles, RenderParams)      */
 /* ------------------------------------------------------------------ */
 
-/* Frame-space pixel bounds of this wave's tile: x in [tx0, tx0 + 8), rows
- * ty0..ty1 (the strip map is monotonic in the local row). */
-DEV void tile_bounds(const RenderParams &P, uint32_t b, uint32_t wave, int &tx0, int &ty0, int &ty1)
-{
-#if C2RT_XCD_SWIZZLE
-    const uint32_t xcd = b & 7u, j = b >> 3;
-    /* row groups are walked starting at P.row_group_start (where the boxed nodes begin on screen):
-     * the expensive tiles are dispatched first and the launch ends on cheap ones */
-    const uint32_t groups = (P.tiles_y + 7u) / 8u;
-    uint32_t grp = j / P.blocks_x + P.row_group_start;
-    if (grp >= groups) grp -= groups;
-    const uint32_t trow = grp * 8u + xcd, bcol = j % P.blocks_x;
-#else
-    const uint32_t trow = b / P.blocks_x, bcol = b % P.blocks_x;
-#endif
-    const uint32_t tcol = bcol * kWavesPerBlock + wave;
-    tx0 = (int)(tcol * kTileW);
-    const uint32_t lr_first = trow * kTileH + P.row_offset;
-    uint32_t lr_last = trow * kTileH + kTileH - 1;
-    if (lr_last >= P.local_rows) lr_last = P.local_rows - 1;
-    lr_last += P.row_offset;
-    ty0 = (int)lr_first;
-    ty1 = (int)lr_last;
-    if (P.strip_world > 1) {
-        const uint32_t sh = P.strip_height;
-        ty0 = (int)(((lr_first / sh) * P.strip_world + P.strip_rank) * sh + lr_first % sh);
-        ty1 = (int)(((lr_last / sh) * P.strip_world + P.strip_rank) * sh + lr_last % sh);
-    }
-}
-
 /* The culling masks of ONE tile, evaluated by ONE lane (the pre-pass kernel, c2rt_kernels.hip: tile_masks_kernel):
  * which nodes the tile's primary rays can reach, which can occlude its shadow rays towards light 0, and whether
  * only the ground plane is left in either.  Until round 3 every wave of the frame kernel derived this for its own
@@ -1114,7 +1078,7 @@ DEV void tile_bounds(const RenderParams &P, uint32_t b, uint32_t wave, int &tx0,
  * bit 0 = primary rays reach the ground plane only | bit 1 = and so do the shadow rays, 0}. */
 /* Where the tile in tile row `trow` of the table (row 0 = local row RenderParams::mask_row0), tile column `tcol`
  * keeps its four words: tile rows r, r + 8, r + 16, ... of a launch run on the same XCD (round-robin dispatch,
- * tile_bounds), so the table is laid out in eight row classes — each L2 fetches its own eighth once instead of
+ * render_tile), so the table is laid out in eight row classes — each L2 fetches its own eighth once instead of
  * sharing every 128-byte line with a neighbour. */
 DEV size_t tile_mask_slot(const RenderParams &P, uint32_t trow, uint32_t tcol)
 {
@@ -1138,7 +1102,7 @@ DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, cons
 {
     typedef const int C2RT_K *KInt;
     typedef const char C2RT_K *KChar;
-    /* frame-space bounds of the tile, as tile_bounds has them for the launch that renders it */
+    /* frame-space bounds of the tile, as render_tile has them for the launch that renders it */
     int tx0 = (int)(tcol * kTileW), ty0, ty1;
     {
         const uint32_t lr_first = trow * kTileH + P.mask_row0;
@@ -2041,7 +2005,6 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
      * dispatch), so XCD x gets tile rows x, x+8, x+16, ... and walks them
      * left to right.  A block is kWavesPerBlock horizontally adjacent 8x8
      * tiles, one per wavefront. */
-#if C2RT_XCD_SWIZZLE
     const uint32_t xcd = b & 7u, j = b >> 3;
     /* row groups are walked starting at P.row_group_start (where the boxed nodes begin on screen):
      * the expensive tiles are dispatched first and the launch ends on cheap ones */
@@ -2049,9 +2012,6 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
     uint32_t grp = j / P.blocks_x + P.row_group_start;
     if (grp >= groups) grp -= groups;
     const uint32_t trow = grp * 8u + xcd, bcol = j % P.blocks_x;
-#else
-    const uint32_t trow = b / P.blocks_x, bcol = b % P.blocks_x;
-#endif
     if (trow >= P.tiles_y) return false;
     const uint32_t tcol = bcol * kWavesPerBlock + wave;
 #if C2RT_TILE_STATS

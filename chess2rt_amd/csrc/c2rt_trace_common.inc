@@ -24,10 +24,7 @@ namespace {
  * Procedure2) but, inlined, its ~70 live registers set the whole kernel's
  * budget; as real calls the trace stays under 168 VGPRs without spills. */
 __device__ __noinline__ double c2_pow(double a, double b) { return pow(a, b); }
-__device__ __noinline__ double c2_atan2(double a, double b) { return atan2(a, b); }
-__device__ __noinline__ double c2_asin(double a) { return asin(a); }
 __device__ __noinline__ double c2_sin(double a) { return sin(a); }
-__device__ __noinline__ double c2_cos(double a) { return cos(a); }
 /* Sphere.intersect's u,v (rt/geometry.d:118-120) out of line as well: the x87 emulation (x87.h) is ~500 integer
  * instructions with ~40 live registers, reached by textured sphere hits only; inlined (twice: lean:: and exact::)
  * it was where the headline instance spilled. */
@@ -56,32 +53,14 @@ __device__ __noinline__ UV c2_sphere_uv(double dx, double dz, double w)
  *     half the time (VALU busy 0.53) — the third wave is worth more than the spills cost: csg_stress.sdl cut to
  *     depth 2 / 3 / 4: 2.33 -> 1.88, 4.60 -> 3.97, 10.21 -> 8.53 ms (scripts/depth_occupancy.sh; four waves:
  *     2.59 / 5.48 / 10.5).  The hit stacks have to fit three workgroups per CU too: kCsgFirstCap, c2rt_device.h. */
-#ifndef C2RT_OCC_U1
-#define C2RT_OCC_U1 4
-#endif
-#ifndef C2RT_OCC_DEEP
-#define C2RT_OCC_DEEP 3
-#endif
-#ifndef C2RT_OCC_U2
-#define C2RT_OCC_U2 3
-#endif
-#ifndef C2RT_OCC_U3
-#define C2RT_OCC_U3 C2RT_OCC_DEEP
-#endif
 template <int LEVELS, int DOF, bool MLC>
 constexpr int occ_of()
 {
-#ifndef C2RT_OCC_U0
-#define C2RT_OCC_U0 4
-#endif
-    return LEVELS == 0 ? (DOF ? 4 : C2RT_OCC_U0) : (LEVELS == 1 ? ((DOF || MLC) ? 3 : C2RT_OCC_U1) : (LEVELS == 2 ? C2RT_OCC_U2 : (LEVELS == 3 ? C2RT_OCC_U3 : C2RT_OCC_DEEP)));
+    return LEVELS == 0 ? 4 : (LEVELS == 1 ? ((DOF || MLC) ? 3 : 4) : 3);
 }
-#define C2RT_OCC_OF(L, D, M) __attribute__((amdgpu_waves_per_eu(occ_of<L, D, M>(), occ_of<L, D, M>())))
+#define C2RT_WAVES_OF(L, D, M) __attribute__((amdgpu_waves_per_eu(occ_of<L, D, M>(), occ_of<L, D, M>())))
 #ifndef C2RT_TILE_STATS
 #define C2RT_TILE_STATS 0 /* diagnostics: per-tile wave cycles + class (RenderParams::tile_stats) */
-#endif
-#ifndef C2RT_XCD_SWIZZLE
-#define C2RT_XCD_SWIZZLE 1
 #endif
 
 #ifndef C2RT_TRACE_EXACT_ONLY

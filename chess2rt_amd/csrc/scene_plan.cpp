@@ -870,7 +870,7 @@ void fill_params(const ScenePlan &plan, const DeviceTables &dev, const DiagKnobs
     p.tile_stats = dev.tile_stats;
     p.row_group_start = 0;
     p.planes_only = plan.planes_only;
-    p.all_identity = knobs.no_idn ? 0u : plan.all_identity;
+    p.all_identity = plan.all_identity;
     p.ground_node = plan.ground_node;
     p.ground_y = plan.ground_y;
     p.shadow_rects = dev.shadow_rects;

@@ -117,7 +117,6 @@ struct DeviceTables {
  * environment fills them; the planner reads none. */
 struct DiagKnobs {
     bool exact = false;                /* C2RT_EXACT=1: every tile through exact:: */
-    bool no_idn = false;               /* C2RT_NO_IDN=1: the general instances for identity-matrix scenes */
     /* C2RT_DEBUG_CULL (frames are unchanged by construction, slower): bit 0: no culling rectangles at all; bit 1: no
      * ground-plane refinement of the shadow mask; bit 2: no view-pyramid culling of shadow rays; bit 3: no
      * sphere-silhouette test in the mask pre-pass; bit 4: no ground-tile path (RenderParams::ground_fast stays 0) */

@@ -23,8 +23,7 @@
  *     the caller (the reference has a single render thread).
  *
  * Environment: the product library (libc2rt.so) reads NO environment variable.
- * The measurement / test knobs of earlier rounds (C2RT_EXACT, C2RT_NO_IDN,
- * C2RT_HOST_CHUNK_MB / _FIRST_FRAC / _COPY_STREAMS / _DIRECT_STORE,
+ * The measurement / test knobs (C2RT_EXACT, C2RT_HOST_DIRECT_STORE,
  * C2RT_CSG_FIRST_CAP, C2RT_DEBUG_CULL — none changes a pixel) exist only in the
  * diagnostics build, chess2rt_amd/libc2rt_diag.so (`make`: c2rt_api.cpp with
  * -DC2RT_DIAG=1 over the same kernel objects), where each is read once per

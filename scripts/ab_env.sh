@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of environment knobs of ONE library on the GPU box: scripts/ab_env.sh "<VAR=val|-> ..." [bench args]
-# e.g. scripts/ab_env.sh "- C2RT_PALETTE=0" --workload zaphod_4k_dof25   ("-" = no variable set)
+# e.g. scripts/ab_env.sh "- C2RT_EXACT=1" --workload zaphod_4k_dof25   ("-" = no variable set)
 VARS=$1; shift
 for v in $VARS; do
   if [ "$v" = "-" ]; then pre=""; else pre="$v"; fi

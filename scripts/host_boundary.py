@@ -1,8 +1,7 @@
 #!/usr/bin/env python3
 """ms per frame at the reference's actual boundary (renderRT writes the caller's HOST Image!Color): c2rt_render_frame
-into a pinned float frame and c2rt_render_frame_rgb32 into pinned display words, lecture5 4K x5, for the pipeline
-parameters in the environment (C2RT_HOST_CHUNK_MB, C2RT_HOST_FIRST_FRAC, C2RT_HOST_COPY_STREAMS,
-C2RT_HOST_DIRECT_STORE).  Prints one line."""
+into a pinned float frame and c2rt_render_frame_rgb32 into pinned display words, lecture5 4K x5, for the library
+C2RT_LIB_VARIANT names and the one pipeline knob of the diagnostics library, C2RT_HOST_DIRECT_STORE.  Prints one line."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -15,7 +14,7 @@ scene_file, w, h, taps, dof = WORKLOADS[name]
 s = c2.parseSceneFromFile(os.path.join(SCENES, scene_file)); s.setFrameSize(w, h); s.setDof(dof)
 cam = s.beginFrame(); ctx = c2.Context(0); ctx.uploadScene(s.desc)
 b = boundary_timings(np, ctx, cam, s.renderOpts(taps=taps), n=20)
-tag = " ".join("%s=%s" % (k[10:], v) for k, v in sorted(os.environ.items()) if k.startswith("C2RT_HOST_"))
+tag = " ".join("%s=%s" % (k[5:], os.environ[k]) for k in ("C2RT_LIB_VARIANT", "C2RT_HOST_DIRECT_STORE") if k in os.environ)
 print("%-60s float %.3f ms  rgb32 %.3f ms" % (tag or "(defaults)", b["host_float_pinned_ms"], b["host_rgb32_pinned_ms"]))
 if os.environ.get("C2RT_HOST_MEASURE_COPY"):
     import torch
