@@ -181,7 +181,7 @@ typedef struct c2rt_camera_frame {
 typedef enum c2rt_tap_mode {
     C2RT_TAPS_1 = 1,      /* AAEnabled=false: one sample at (x, y)            */
     C2RT_TAPS_REF5 = 5,   /* AAEnabled=true: reference 5-tap table, sum / 5   */
-    C2RT_TAPS_4 = 4       /* build-defined "4 spp": taps 1..4 of the table / 4 */
+    C2RT_TAPS_4 = 4       /* build-defined "4 spp": the first four entries of the table, (0, 0) included, sum / 4 */
 } c2rt_tap_mode;
 
 typedef struct c2rt_render_opts {

@@ -152,8 +152,9 @@ class Case:
 
 
 @functools.lru_cache(maxsize=None)
-def load(variant):
-    path = os.path.join(_TMP, "geom_%s.sdl" % variant)
+def load(variant, tag=None):
+    """`tag`: a loaded scene of the caller's own (its camera and frame size may be set); None is the shared, read-only one"""
+    path = os.path.join(_TMP, "geom_%s%s.sdl" % (variant, "_" + tag if tag else ""))
     with open(path, "w") as f:
         f.write(scene_text(variant))
     scene = c2.parseSceneFromFile(path)

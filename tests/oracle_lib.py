@@ -76,6 +76,8 @@ def lib():
         L.orc_take_csg_truncations.restype = C.c_ulonglong
         L.orc_rng_uniform.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32]
         L.orc_rng_uniform.restype = C.c_double
+        L.orc_lens_sincos2pi.argtypes = [C.c_double, d3, d3]
+        L.orc_lens_sincos2pi.restype = None
         _lib = L
     return _lib
 

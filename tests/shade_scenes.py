@@ -30,6 +30,7 @@ GROUND, CEILING, PROC_PLANE, PROC_SPHERE, SOFT_SPHERE, CUBE, SHINY_SPHERE, CSG =
 PLANE_Y = {GROUND: 0.0, CEILING: 30.0, PROC_PLANE: -8.0}
 BMP_SCALING, CHECKER_SIZE = 0.05, 0.75
 FREQ_U, FREQ_V = (0.7, 13.0, 40.0), (1.3, 0.05, 37.0)
+HIGH_LIGHT = (-45.0, 60.0, 0.0)
 CLUSTER, POS_A, POS_B, POS_DARK, POS_BELOW = (-45.0, 22.0, 0.0), (25.0, 20.0, -45.0), (25.0, 20.0, 45.0), (0.0, 25.0, -20.0), (10.0, -3.0, 5.0)
 
 _TMP = tempfile.mkdtemp(prefix="c2rt_shade_")
@@ -68,7 +69,7 @@ def lights_of(variant):
     return out
 
 
-def scene_text(variant, libm_free=False):
+def scene_text(variant, libm_free=False, floor_only=False):
     geoms = ['Plane "ground" { y 0 }', 'Plane "ceiling" { y 30 }', 'Plane "deep" { y -8 }',
              'Sphere "s_proc" { center -5 8 28; R 7.5 }', 'Sphere "s_soft" { center -20 7 -30; R 6.5 }',
              'Cube "k1" { center -15 8.5 0; side 16 }', 'Sphere "s_shiny" { center 4 6 -38; R 5.5 }',
@@ -89,11 +90,16 @@ def scene_text(variant, libm_free=False):
              ("k1", "sh_cube"), ("s_shiny", "sh_shiny"), ("diff", "sh_csg")]
     if libm_free:   # no Phong, no Procedure2: no pow and no sin on the path
         nodes = [n for n in nodes if n[1] in ("sh_ground", "sh_ceiling", "sh_csg")]
+    lights = lights_of(variant)
+    if floor_only:  # the ground is the one plane: an unbounded plane is in every tile's mask, and a tile whose rays can
+        nodes = [n for n in nodes if n[0] not in ("ceiling", "deep")]      # reach another node is not ground-only;
+        assert variant == "L1"                                             # and the light stands higher: shorter shadows
+        lights = [_light("l0", HIGH_LIGHT, "1 0.95 0.9", 2600)]            # leave tiles of the floor no node can shade
     return "\n".join([
         "Scene {", '  Name "shade_%s"' % variant,
         "  GlobalSettings { frameWidth %d; frameHeight %d; AAEnabled false; ambientLightColor %s }" % (W, H, AMBIENT[variant]),
         "  Camera { pos 5 24 -72; yaw 0; pitch -17; roll 0; fov 78 }",
-        "  Lights {\n    " + "\n    ".join(lights_of(variant)) + "\n  }",
+        "  Lights {\n    " + "\n    ".join(lights) + "\n  }",
         "  Geometries {\n    " + "\n    ".join(geoms) + "\n  }",
         "  Textures {\n    " + "\n    ".join(textures) + "\n  }",
         "  Shaders {\n    " + "\n    ".join(shaders) + "\n  }",
@@ -102,11 +108,12 @@ def scene_text(variant, libm_free=False):
 
 
 @functools.lru_cache(maxsize=None)
-def load(variant, libm_free=False):
-    """(scene, camera frame, one-tap options) of a variant at 61x47; computed once, treated as read-only"""
-    path = os.path.join(_TMP, "shade_%s%s.sdl" % (variant, "_nolibm" if libm_free else ""))
+def load(variant, libm_free=False, tag=None, floor_only=False):
+    """(scene, camera frame, one-tap options) of a variant at 61x47; computed once, treated as read-only.  `tag`: a loaded
+    scene of the caller's own (its camera and frame size may be set); `floor_only`: without the two other planes"""
+    path = os.path.join(_TMP, "shade_%s%s%s%s.sdl" % (variant, "_nolibm" if libm_free else "", "_floor" if floor_only else "", "_" + tag if tag else ""))
     with open(path, "w") as f:
-        f.write(scene_text(variant, libm_free))
+        f.write(scene_text(variant, libm_free, floor_only))
     scene = c2.parseSceneFromFile(path)
     scene.setFrameSize(W, H)
     scene.setAA(False)

@@ -3,7 +3,9 @@ precomputed world normal of a rotated Plane, a finite Plane limit and Union / In
 matrices, against tests/geom_reference.py — a typed numpy restatement of the reference's geometry stage written from the
 D source, which tests/test_geom_reference.py holds against the oracle on the CPU.  With tests/shade_reference.py behind
 it the frames below are compared with a frame that has no oracle anywhere in it: rays -> records -> visibility ->
-colour.  Scene and rays: tests/geom_scenes.py (61x47: partial 8x8 tiles on both edges; 2000 eyeless rays).
+colour; and with tests/camera_reference.py in front of it the five-tap frame is computed from the camera's frame alone:
+sub-pixel rays -> records -> visibility -> colour -> the fp32 sum / 5.  Scene and rays: tests/geom_scenes.py (61x47:
+partial 8x8 tiles on both edges; 2000 eyeless rays).
 
 Tolerances are the ones the project already holds the device to (ray_query_util.assert_records_match_oracle): node and
 leaf equal, dist and p bit for bit, normal within 1e-15, u, v within 1e-12; visibility byte for byte; frames under
@@ -13,6 +15,8 @@ import functools
 import numpy as np
 import pytest
 
+import camera_reference as cr
+import camera_scenes as cs
 import chess2rt_amd as c2
 import geom_reference as gr
 import geom_scenes as gs
@@ -45,6 +49,13 @@ def reference(variant, name):
     r.vis, r.occluder = vis.reshape(len(r.rays), -1), occ.reshape(len(r.rays), -1)
     r.shaded = sr.shade(r.Ts, r.rays[:, 3:], r.recs, r.vis) if name == "screen" else None
     return r
+
+
+@functools.lru_cache(maxsize=None)
+def five_tap_reference(variant):
+    """camera_reference.render_frame of the variant's camera frame at five taps — once, read-only"""
+    scene = gs.load(variant)
+    return cr.render_frame((gr.Tables(scene.desc), sr.Tables(scene.desc)), cs.from_abi(scene.cam), cr.Opts(gs.W, gs.H, taps=cr.TAPS_REF5))
 
 
 _gpu_cases = {}
@@ -99,8 +110,8 @@ def test_hit_planes_equal_the_query_of_the_screen_rays(gpu_ctx, variant):
 def test_frame_equals_the_frame_computed_without_the_oracle(gpu_ctx, variant):
     """renderFrame, one tap: the lean instance with every cull active (screen rectangles and hulls of the sheared world
     boxes, ground shadow rectangles, void tiles of DIFF_ID, the silhouette of SPHERE_ID), against shade_reference.shade
-    of the REFERENCE's records and visibility.  Five taps are compared with the oracle under the suite's TOL: the
-    sub-pixel rays are not in the reference's ray sets."""
+    of the REFERENCE's records and visibility.  Five taps are compared with camera_reference.render_frame, which makes
+    the sub-pixel rays itself, under its interval rule (both counts 0), and with the oracle under the suite's TOL."""
     scene = gs.load(variant)
     gpu_case(gpu_ctx, variant)
     r = reference(variant, "screen")
@@ -118,7 +129,15 @@ def test_frame_equals_the_frame_computed_without_the_oracle(gpu_ctx, variant):
         single = frame if i == 0 else gpu_ctx.renderFrame(cam, scene.opts)
         assert np.array_equal(_bits32(batch[i]), _bits32(single)), (variant, i)
     opts5 = scene.scene.renderOpts(taps=_abi.TAPS_REF5)
-    md, nbad, nne = maxdiff(gpu_ctx.renderFrame(scene.cam, opts5), orc.render_frame(scene.desc, scene.cam, opts5, 0))
+    frame5 = gpu_ctx.renderFrame(scene.cam, opts5)
+    five = five_tap_reference(variant)
+    held = float((five.ambiguous | five.wide).mean())
+    plain5, outside5 = cr.compare(frame5, five)
+    print("%s five taps against the reference: %d pixels held to an interval, %d floats differ, %d outside their bounds"
+          % (variant, int((five.ambiguous | five.wide).sum()), plain5, outside5))
+    assert held <= 5 * AMBIGUOUS_CAP
+    assert plain5 == 0 and outside5 == 0, (variant, plain5, outside5)
+    md, nbad, nne = maxdiff(frame5, orc.render_frame(scene.desc, scene.cam, opts5, 0))
     print("%s five taps against the oracle: max|d|=%.3g, differing floats: %d" % (variant, md, nne))
     assert md <= TOL and nbad == 0
 

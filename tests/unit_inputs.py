@@ -139,5 +139,9 @@ def unit_cases(orc, c2):
 
     # build-defined counter RNG (depth of field only)
     out["rng_uniform"] = [{"seed": s, "pixel": p, "tap": t, "sample": k, "dim": d, "u": L.orc_rng_uniform(s, p, t, k, d)}
-                          for (s, p, t, k, d) in [(0, 0, 0, 0, 0), (7, 12345, 0, 3, 2), (7, 12345, 4, 24, 3), (2 ** 63 + 5, 2 ** 31, 1, 100, 7)]]
+                          for (s, p, t, k, d) in RNG_INPUTS]
     return out
+
+
+# (seed, pixel, tap, sample, dim)
+RNG_INPUTS = [(0, 0, 0, 0, 0), (7, 12345, 0, 3, 2), (7, 12345, 4, 24, 3), (2 ** 63 + 5, 2 ** 31, 1, 100, 7)]
