@@ -61,7 +61,7 @@ HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/
 # over the SAME kernel objects; tests and scripts that need a hook load it with C2RT_LIB_VARIANT=diag
 DIAGNAME   := chess2rt_amd/libc2rt_diag.so
 
-all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so
+all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so
 
 $(BUILD):
 	mkdir -p $(BUILD)
@@ -119,6 +119,11 @@ tests/libscene_update_check.so: tests/scene_update_check.cpp $(CSRC)/scene_plan.
 tests/libground_fast_check.so: tests/ground_fast_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/ground_fast_check.cpp $(CSRC)/scene_plan.cpp
 
+# host build of the dark-tile test of the mask pre-pass and of the planner's part of it (tests/test_ground_dark_tiles.py,
+# scripts/ground_dark_tiles.py), without ROCm
+tests/libground_dark_check.so: tests/ground_dark_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h
+	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/ground_dark_check.cpp $(CSRC)/scene_plan.cpp
+
 # CPU oracle: plain C restatement of the reference algorithm (tests only)
 oracle/libc2rt_oracle.so: oracle/c2rt_oracle.c oracle/c2rt_oracle.h include/c2rt.h
 	$(CC) -O2 -std=gnu11 -fPIC -shared $(FPFLAGS) -Wall -o $@ oracle/c2rt_oracle.c -lm -lpthread
@@ -136,6 +141,6 @@ resource-usage: | $(BUILD)
 	    -c $(CSRC)/$(q).hip -o $(BUILD)/ru_$(q).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
 
 clean:
-	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so
+	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so
 
 .PHONY: all clean resource-usage

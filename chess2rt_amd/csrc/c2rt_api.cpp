@@ -257,6 +257,7 @@ void wire_frame(const c2rt_ctx *ctx, const ScenePlan &plan, RenderParams &p, con
     p.mask_entries = masks ? (uint32_t)entries : 0u;
     cull.v = void_cull_of(plan, p, void_flags_mask);
     cull.s = sphere_cull_of(plan, diag_knobs(), p, ctx->sphere_flags_mask);
+    cull.d = dark_cull_of(plan, diag_knobs(), p);
     if (levels >= 2) {
         p.retry_list = sc.retry_list + i * (blocks + 1);
         p.retry_max = (uint32_t)blocks;
@@ -279,7 +280,7 @@ int prepare_frame(c2rt_ctx *ctx, RenderParams &p, hipStream_t stream, uint32_t v
     BatchCull cull;
     wire_frame(ctx, ctx->plan, p, sc, 0, entries, blocks, void_flags_mask, cull);
     if (cull_out) *cull_out = cull;
-    return entries ? launch_tile_masks(p, cull.v, cull.s, sc.tile_masks, stream) : 0;
+    return entries ? launch_tile_masks(p, cull.v, cull.s, cull.d.n ? ctx->dev.dark : nullptr, sc.tile_masks, stream) : 0;
 }
 
 /* The frame launch of prepared parameters (a chunked frame: once per chunk, over the chunk's rows).  Scenes with
@@ -511,13 +512,14 @@ int check_posed_args(c2rt_ctx *ctx, const c2rt_scene_pose *poses, uint32_t n_fra
 }
 
 /* One device slot's half of c2rt_update_scene: plans the posed scene (update_scene_plan), then copies to the device,
- * in stream order, the node records, the light table and the shadow rectangles whose bytes changed.  The sources are
+ * in stream order, the node records, the light table, the shadow rectangles and the dark-tile table whose bytes changed.  The sources are
  * pageable: the runtime has read them when each call returns. */
 int update_one(c2rt_ctx *c, const c2rt_scene_pose *pose, hipStream_t stream)
 {
     const std::vector<DevNode> nodes = c->plan.nodes;
     const std::vector<DevLight> lights = c->plan.lights;
     const std::vector<double> rects = c->plan.shadow_rects;
+    const DarkCull dark = c->plan.dark;
     if (const int st = update_scene_plan(c->scene, c->plan, pose, c->err)) return st;
     HIP_TRY(c, hipSetDevice(c->device));
     const std::vector<DevNode> &now = c->plan.nodes;
@@ -532,6 +534,8 @@ int update_one(c2rt_ctx *c, const c2rt_scene_pose *pose, hipStream_t stream)
         HIP_TRY(c, hipMemcpyAsync(c->dev.lights, c->plan.lights.data(), lights.size() * sizeof(DevLight), hipMemcpyHostToDevice, stream));
     if (!same_bytes(c->plan.shadow_rects, rects))
         HIP_TRY(c, hipMemcpyAsync(c->dev.shadow_rects, c->plan.shadow_rects.data(), rects.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+    if (std::memcmp(&c->plan.dark, &dark, sizeof dark) != 0)
+        HIP_TRY(c, hipMemcpyAsync(c->dev.dark, &c->plan.dark, sizeof dark, hipMemcpyHostToDevice, stream));
     return C2RT_OK;
 }
 
@@ -658,7 +662,7 @@ void c2rt_destroy(c2rt_ctx *ctx)
         if (e) (void)hipEventDestroy(e);
     for (const auto &pb : ctx->pinned) (void)hipHostUnregister(pb.first);
     void *bufs[] = {ctx->dev.geoms, ctx->dev.nodes, ctx->dev.shaders, ctx->dev.textures, ctx->dev.lights, ctx->dev.texels,
-                    ctx->frame, ctx->counters, ctx->probe, ctx->srgb_lut, ctx->dev.shadow_rects};
+                    ctx->frame, ctx->counters, ctx->probe, ctx->srgb_lut, ctx->dev.shadow_rects, ctx->dev.dark};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     for (FrameScratch &f : ctx->scratch) {
@@ -703,6 +707,7 @@ static int upload_one(c2rt_ctx *ctx, const c2rt_scene_desc *s)
     /* frames enqueued on callers' streams may still be reading the tables about to be replaced */
     HIP_TRY(ctx, hipDeviceSynchronize());
     if ((st = upload(ctx, &ctx->dev.shadow_rects, plan.shadow_rects)) != C2RT_OK) return st;
+    if ((st = upload(ctx, &ctx->dev.dark, std::vector<DarkCull>(1, plan.dark))) != C2RT_OK) return st;
     if ((st = upload(ctx, &ctx->dev.geoms, plan.geoms)) != C2RT_OK) return st;
     if ((st = upload(ctx, &ctx->dev.textures, plan.textures)) != C2RT_OK) return st;
     if ((st = upload(ctx, &ctx->dev.texels, plan.texels4)) != C2RT_OK) return st;

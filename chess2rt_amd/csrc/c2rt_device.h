@@ -273,6 +273,7 @@ int launch_probe(const RenderParams &p, const KernelVariant &v, void *stream);
 struct BatchCull {
     VoidCull v;
     SphereCull s;
+    DarkCull d;
 };
 template <int LEVELS>
 int launch_render_batch_level(const RenderParams &p0, const RenderParams *table_dev, uint32_t n_frames, void *stream);
@@ -284,9 +285,10 @@ template <> int launch_render_batch_level<4>(const RenderParams &, const RenderP
 int launch_render_batch(const RenderParams &p0, const KernelVariant &v, const RenderParams *table_dev, uint32_t n_frames, void *stream);
 int launch_tile_masks_batch(const RenderParams &p0, const RenderParams *table_dev, const BatchCull *culls_dev, uint32_t n_frames, void *stream);
 /* entries of RenderParams::tile_masks a launch of `p` reads (4 words each, twice that with several culled lights);
- * the pre-pass that fills them (vc: the frame's CsgDiff void tests, csg_void.h) */
+ * the pre-pass that fills them (vc: the frame's CsgDiff void tests, csg_void.h; dark_dev: the scene's dark-tile table in
+ * device memory, null for a frame that runs no dark test) */
 size_t tile_mask_entries(const RenderParams &p);
-int launch_tile_masks(const RenderParams &p, const VoidCull &vc, const SphereCull &sc, uint32_t *table, void *stream);
+int launch_tile_masks(const RenderParams &p, const VoidCull &vc, const SphereCull &sc, const DarkCull *dark_dev, uint32_t *table, void *stream);
 int launch_deinterleave(const float *gathered, float *frame, uint32_t width, uint32_t height,
                         uint32_t strip_height, uint32_t world, uint32_t rows_pad, uint32_t words_per_pixel, void *stream);
 int launch_encode_rgb32(const float *frame, uint32_t *out, uint64_t n_pixels,

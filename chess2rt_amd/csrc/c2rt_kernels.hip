@@ -224,14 +224,14 @@ __global__ void encode_rgb32_kernel(const float *__restrict__ frame, uint32_t *_
  * tile_mask_slot).  Runs once per frame whose camera leaves culling rectangles, in front of the frame kernel's
  * launch(es), on the same stream.  One body for both entry points below, which only produce (P, K, V, S, table,
  * tile_rows). */
-DEV void tile_masks_body(const RenderParams &P, KArgs K, const VoidCull &V, const SphereCull &S, uint32_t *table, uint32_t tile_rows)
+DEV void tile_masks_body(const RenderParams &P, KArgs K, const VoidCull &V, const SphereCull &S, const DarkCull *D, uint32_t *table, uint32_t tile_rows)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t cols = P.blocks_x * kWavesPerBlock;
     const uint32_t trow = i / cols, tcol = i % cols;
     if (trow >= tile_rows) return;
     uint32_t m[8];
-    exact::tile_mask_entry(P, (exact::KArgs)K, V, S, trow, tcol, m);
+    exact::tile_mask_entry(P, (exact::KArgs)K, V, S, D, trow, tcol, m);
     typedef uint32_t __attribute__((ext_vector_type(4))) u4_t;
     u4_t v, w;
     v.x = m[0]; v.y = m[1]; v.z = m[2]; v.w = m[3];
@@ -241,11 +241,13 @@ DEV void tile_masks_body(const RenderParams &P, KArgs K, const VoidCull &V, cons
     if (P.n_cull_lights > 1u) reinterpret_cast<u4_t *>(table)[(size_t)P.mask_entries + slot] = w; /* lights 1..3 */
 }
 
-static_assert(sizeof(RenderParams) + sizeof(VoidCull) + sizeof(SphereCull) + 16 <= 4096, "the kernel-argument segment holds at most 4 KiB");
-__global__ void __launch_bounds__(256) tile_masks_kernel(const RenderParams P, const VoidCull V, const SphereCull S,
+static_assert(sizeof(RenderParams) + sizeof(VoidCull) + sizeof(SphereCull) + 24 <= 4096, "the kernel-argument segment holds at most 4 KiB");
+__global__ void __launch_bounds__(256) tile_masks_kernel(const RenderParams P, const VoidCull V, const SphereCull S, const DarkCull *dark,
                                                          uint32_t *__restrict__ table, uint32_t tile_rows)
 {
-    tile_masks_body(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), V, S, table, tile_rows);
+    /* the dark-tile table does not fit the argument segment: a scene table (nullable), read with scalar loads */
+    const DarkCull C2RT_K *D = (const DarkCull C2RT_K *)dark;
+    tile_masks_body(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), V, S, (const DarkCull *)D, table, tile_rows);
 }
 
 /* The same for every frame of a batch in one launch: blockIdx.y = frame; the frame's RenderParams and its VoidCull /
@@ -259,7 +261,7 @@ __global__ void __launch_bounds__(256) tile_masks_batch_kernel(const RenderParam
     const RenderParams &P = *(const RenderParams *)K;
     if (!P.n_cull || !P.tile_masks) return;
     const BatchCull &B = *(const BatchCull *)C;
-    tile_masks_body(P, K, B.v, B.s, const_cast<uint32_t *>(P.tile_masks), (P.mask_rows + kTileH - 1) / kTileH);
+    tile_masks_body(P, K, B.v, B.s, &B.d, const_cast<uint32_t *>(P.tile_masks), (P.mask_rows + kTileH - 1) / kTileH);
 }
 #endif /* C2RT_UNIT == 5 */
 
@@ -373,12 +375,12 @@ size_t tile_mask_entries(const RenderParams &p)
     return padded_grid_blocks(tile_rows, p.blocks_x) * kWavesPerBlock;
 }
 
-int launch_tile_masks(const RenderParams &p, const VoidCull &vc, const SphereCull &sc, uint32_t *table, void *stream)
+int launch_tile_masks(const RenderParams &p, const VoidCull &vc, const SphereCull &sc, const DarkCull *dark_dev, uint32_t *table, void *stream)
 {
     const uint32_t tile_rows = (p.mask_rows + kTileH - 1) / kTileH;
     const uint32_t lanes = tile_rows * p.blocks_x * kWavesPerBlock;
     if (!lanes) return 0;
-    hipLaunchKernelGGL(tile_masks_kernel, dim3((lanes + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream), p, vc, sc, table, tile_rows);
+    hipLaunchKernelGGL(tile_masks_kernel, dim3((lanes + 255u) / 256u), dim3(256), 0, static_cast<hipStream_t>(stream), p, vc, sc, dark_dev, table, tile_rows);
     return (int)hipGetLastError();
 }
 

@@ -1075,7 +1075,8 @@ DEV void hit_surface(const Ctx &cx, NodeP N, const Hit &h, bool want_uv, Surf &s
  * dependent kernel-argument, rectangle, hull and shadow-rectangle loads in front of every tile).  Here a lane owns
  * a tile and loops over the nodes (their rectangles and hulls are scalar loads), 64 tiles per wave; the frame
  * kernel reads the four words with one scalar load.  out: {primary mask, shadow mask for light 0,
- * bit 0 = primary rays reach the ground plane only | bit 1 = and so do the shadow rays, 0}. */
+ * bit 0 = primary rays reach the ground plane only | bit 1 = and so do the shadow rays | bit 2 = primary-ground and every
+ * shadow ray occluded (dark), 0}. */
 /* Where the tile in tile row `trow` of the table (row 0 = local row RenderParams::mask_row0), tile column `tcol`
  * keeps its four words: tile rows r, r + 8, r + 16, ... of a launch run on the same XCD (round-robin dispatch,
  * render_tile), so the table is laid out in eight row classes — each L2 fetches its own eighth once instead of
@@ -1098,7 +1099,7 @@ DEV uint32_t light_shadow_mask(const RenderParams &P, uint32_t mask_slot, uint32
     return ((const uint32_t C2RT_K *)P.tile_masks)[((size_t)P.mask_entries + mask_slot) * 4u + (l - 1u)];
 }
 
-DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, const SphereCull &S, uint32_t trow, uint32_t tcol, uint32_t out[8])
+DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, const SphereCull &S, const DarkCull *Dp, uint32_t trow, uint32_t tcol, uint32_t out[8])
 {
     typedef const int C2RT_K *KInt;
     typedef const char C2RT_K *KChar;
@@ -1177,7 +1178,7 @@ DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, cons
      * — the convex image of the pixel rectangle (+1 px all round; the AA taps reach 0.6 px),
      * provided all four corner rays meet the plane in front of the eye — and a node whose
      * shadow rectangle misses the footprint's bounding rectangle cannot occlude any of them. */
-    bool primary_ground = false, ground_only = false;
+    bool primary_ground = false, ground_only = false, dark = false;
     const int gnode = P.ground_node;
     const uint32_t nn = P.n_nodes;
     if (gnode >= 0 && nn <= 32u && (pmask & (0xFFFFFFFFu >> (32u - nn))) == (1u << gnode)) {
@@ -1230,12 +1231,27 @@ DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, cons
                 if (!have_scone) { scone = shadow_cone(); have_scone = true; }
                 if (cone_misses_ball(V.light0, scone, sn.c, sn.rp)) smask0 &= ~(1u << sn.node);
             }
+            /* dark tile: one node occludes every shadow ray from the footprint (csg_void.h, "Dark ground tiles"); asked
+             * of the nodes whose shadow rectangle meets the footprint, whatever the tests above were allowed to do */
+            if (Dp && Dp->n) { /* (a null table: the frame runs no dark test) */
+                const DarkCull &D = *Dp;
+                double sdir[4][3];
+                footprint_dirs(V.light0, gy, fx0, fx1, fz0, fz1, sdir);
+                const bool dark_reach = fmax(fabs(fx0), fabs(fx1)) + fmax(fabs(fz0), fabs(fz1)) + fabs(gy) <= D.reach;
+                for (uint32_t j = 0; j < D.n; ++j) {
+                    const DarkNode &dn = D.d[j];
+                    if (dn.node >= nc) continue;
+                    KDbl sr = rects_s + 4 * dn.node;
+                    if ((sr[1] < fx0 - padx) | (sr[0] > fx1 + padx) | (sr[3] < fz0 - padz) | (sr[2] > fz1 + padz)) continue;
+                    if (tile_dark_by(V.light0, sdir, dark_reach, dn)) dark = true;
+                }
+            }
         }
         ground_only = (smask0 & (0xFFFFFFFFu >> (32u - nn))) == (1u << gnode);
     }
     out[0] = pmask;
     out[1] = smask0;
-    out[2] = (primary_ground ? 1u : 0u) | (ground_only ? 2u : 0u);
+    out[2] = (primary_ground ? 1u : 0u) | (ground_only ? 2u : 0u) | (dark ? 4u : 0u);
     /* shadow masks of the further culled lights (second table): the same predicate as light 0's view-pyramid part */
     out[3] = 0;
     out[4] = out[5] = out[6] = 0xFFFFFFFFu;
@@ -1904,8 +1920,16 @@ DEV void store_pixel(const RenderParams &P, const size_t pixel_index, const F3 a
  * Returns per lane; the lanes inside the frame agree (a lane outside it reports kGroundDone: it has nothing to do).
  */
 enum { kGroundDone = 0, kGroundRedo = 1, kGroundBail = 2 };
+/* dark (wave-uniform, a scalar branch per sample): the tile's third mask word has bit 2 — every shadow ray of the tile
+ * towards the one light is provably occluded (csg_void.h, "Dark ground tiles"), so test_visibility is false for every
+ * sample, shade() adds avgColor = (0, 0, 0) to the ambient term and nothing else of the light reaches the pixel.  The
+ * sample is then ray, normalisation, plane hit, texture and diffuse * (ambient + (0, 0, 0)) — the addition stays, an
+ * ambient of -0 becomes +0 as it does in shade() —: no light_terms, no base_light, no pre-check, no bail-out.  The
+ * oob_notes of the skipped light arithmetic go with it.  That is sound: a lane outside a lean window only ever sent the
+ * tile to exact::, which computes the same bits as lean:: inside the windows, and the values those windows guard are
+ * never read here. */
 template <int PO>
-DEV int ground_tile(const RenderParams &P, KArgs K, const uint32_t trow, const uint32_t bcol)
+DEV int ground_tile(const RenderParams &P, KArgs K, const uint32_t trow, const uint32_t bcol, const bool dark)
 {
     static_assert(!(PO & kSpecPlanes), "the planes-only instances have no mask table");
     const int lane = threadIdx.x & (kWave - 1);
@@ -1950,7 +1974,9 @@ DEV int ground_tile(const RenderParams &P, KArgs K, const uint32_t trow, const u
             const F3 diffuse = mat.tex_type == C2RT_TEX_CHECKER ? checker_color(mat, p.x, p.z)
                              : (mat.tex_type >= 0 ? bitmap_color(Pt, mat, p.x, p.z) : mat.color);
             F3 lightContrib = mkf(Pt.ambient[0], Pt.ambient[1], Pt.ambient[2]);
-            if (Pt.n_lights) {
+            if (dark) { /* wave-uniform */
+                lightContrib = lightContrib + mkf(0, 0, 0);
+            } else if (Pt.n_lights) {
                 LightP L = (LightP)Pt.lights;
                 F3 avgColor = mkf(0, 0, 0);
                 if (L->lit & 1u) {
@@ -2022,7 +2048,7 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
      * light, and is the ground plane all that is left?  One scalar load from the table the pre-pass kernel
      * wrote for this frame (tile_mask_entry). */
     uint32_t pmask = 0xFFFFFFFFu, smask0 = 0xFFFFFFFFu, mask_slot = 0;
-    bool ground_only = false, primary_ground = false;
+    bool ground_only = false, primary_ground = false, dark = false;
     Oob tile_bad;
     oob_init(tile_bad);
     if constexpr (!DOF) {
@@ -2034,19 +2060,21 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
             smask0 = m.y;
             primary_ground = (m.z & 1u) != 0;
             ground_only = (m.z & 2u) != 0;
+            dark = (m.z & 4u) != 0;
         }
     }
 
-    /* Ground-only tile of an eligible frame: ground_tile renders it, unless a sample's shadow pre-check fails — then
+    /* Ground-only tile of an eligible frame, or dark tile (bit 2: primary rays reach the ground only and every shadow
+     * ray is occluded): ground_tile renders it, unless a sample's shadow pre-check fails (never for a dark tile) — then
      * nothing has been written and the tile goes on below.  The call takes nothing but the kernel-argument pointer and
      * the tile's row and block column, through an empty asm, so that the path shares no value with the code below and
      * nothing of it stays live on its behalf (as render_one does for exact::). */
     if constexpr (kLean && LEVELS <= 1 && !DOF && !MLC && !CNT && !(PO & kSpecPlanes) && !C2RT_TILE_STATS) {
-        if (P.ground_fast && ground_only) { /* wave-uniform */
+        if (P.ground_fast && (ground_only || dark)) { /* wave-uniform */
             KArgs Kg = K;
-            uint32_t trow_g = trow, bcol_g = bcol;
-            asm volatile("" : "+s"(Kg), "+s"(trow_g), "+s"(bcol_g));
-            const int g = ground_tile<PO>(*(const RenderParams *)Kg, Kg, trow_g, bcol_g);
+            uint32_t trow_g = trow, bcol_g = bcol, dark_g = (uint32_t)__builtin_amdgcn_readfirstlane(dark && !ground_only ? 1 : 0);
+            asm volatile("" : "+s"(Kg), "+s"(trow_g), "+s"(bcol_g), "+s"(dark_g));
+            const int g = ground_tile<PO>(*(const RenderParams *)Kg, Kg, trow_g, bcol_g, dark_g != 0);
             if (!__ballot(g == kGroundBail)) return g == kGroundRedo;
         }
     }

@@ -264,6 +264,159 @@ C2RT_VOID_FN void footprint_dirs(const double L[3], double gy, double fx0, doubl
     }
 }
 
+/* ---- Dark ground tiles ---------------------------------------------------------------------------------------
+ * The opposite claim: EVERY shadow ray towards light 0 from a primary-ground tile gets a hit on one and the same node
+ * before the light, so testVisibility (rt/scene.d:62-78) is false for every sample of the tile and the light adds
+ * nothing to it.  (Whatever the nodes in front of that one in the scene's list report: a hit ends the loop with the
+ * same answer, a miss leaves the distance limit alone.)
+ *
+ * The tool.  Let h = light.y - ground_y > 0 (h < 0: mirrored), K a convex set with ground_y + m < y < light.y - m for
+ * all its points, and K_m its erosion by m (the points whose m-ball lies in K).  Central projection from the light
+ * onto the ground plane is a projective map that is regular on the half space y < light.y, so the ground points g
+ * whose segment light -> g meets K_m form a convex set.  If it holds the four corners of the tile's padded footprint
+ * rectangle (footprint_dirs: the rectangle grown by ten times what the shadow origins' 1e-6 step off the ground
+ * moves a projected point), it holds the rectangle.  A shadow ray starts at from = p + N * 1e-6, p in the footprint;
+ * the line light -> from meets the ground plane at a point g of the padded rectangle, from lies on the segment
+ * light -> g, below every point of K, so the point q of K_m on that segment lies between `from` and the light, at
+ * least m from either along the ray.  The ray therefore has a chord of at least 2 m around q inside K, all of it in
+ * front of the light.  The tests below clip against K eroded by 2 m: the second m pays for their own rounding
+ * (relative 1e-15 of the scale, against m >= 1e-5 + 1e-6 scale).
+ *
+ * Sphere node (identity matrix, offset allowed), K = the ball (c, R), m = sphere_margin: the ray passes within R - m
+ * of c, so the exact discriminant of Sphere.intersect is 4 (R^2 - d^2) >= 4 (2 R m - m^2) > 4 R m for a unit
+ * direction, against a rounding below 1e-14 |o - c|^2 (cone_misses_ball's bound, |o - c| <= 2 scale for footprints
+ * within `reach`) — the same five orders of magnitude.  Both ends of the ray's segment lie outside the ball by more
+ * than m (the ground below it, the light above it), so both roots lie in (m, |light - from| - m); the near root is
+ * positive, below the distance limit, and the hit is reported.
+ *
+ * CsgDiff(Cube, Sphere) node (identity matrix, offset allowed), m = void_margin.  The solid is not convex; for a
+ * corner s in {-1, +1}^3 of the cube, n = s / sqrt(3),
+ *     K = {p in the cube shrunk by pad (the node box's padding) : n.(p - c) >= R + m}
+ * is convex (a box cut by a half space: a tetrahedron at the corner when the ball swallows the cube's edges), lies in
+ * the cube and outside the subtracted ball by m.  Take a ray with a point q of K_m on it, and let every ray of the
+ * tile satisfy n.w > 0, w its direction towards the light (linear in the origin: tested at the four corners).
+ * CsgOp.intersect (rt/geometry.d:292-332) walks the sorted events of both children, starting from inL = |L| odd,
+ * inR = |R| odd, and reports the first event after which inL && !inR:
+ *  - R, the ball.  Every recorded event point lies on the sphere up to rounding, so n.(p - c) <= R + 1e-9, while
+ *    n.(q - c) >= R + m: with n.w > 0 every R event precedes q by at least m - 1e-9 in distance (n.w <= 1).  So
+ *    however many events findAllIntersections recorded (none; one, the origin inside the ball — on lecture5 the
+ *    subtracted ball dips below the floor; two; any other small number for a grazing ray whose 1e-6 steps land on
+ *    either side of the sphere; the device's cap of 8 is not approached), all of them are flipped before q and inR,
+ *    having started at their parity, is false at q.
+ *  - L, the cube.  The origin is outside it: the box lies above the ground by more than m, the origin within 1e-6 of
+ *    it.  q is at least m from every face, so the face the ray enters (leaves) through is crossed with a direction
+ *    component of at least m / diameter >= 5e-7 (Cube.intersect skips an axis only below 1e-9), and the 1e-6 step
+ *    past the entry carries the origin 5e-13 past that face, far above the rounding of the recorded point: exactly
+ *    two events, the entry before q by at least m and the exit after it.  inL starts false and is true at q.
+ *  So just before q the state is inL && !inR, and the walk — which stops at the first event that produces that state —
+ *  has stopped at an event at or before q: a hit at a distance below dist(q) <= |light - from| - m, the distance
+ *  limit of the shadow ray.  Equal distances need no tie rule: every order ends in that state before q.
+ *
+ * One corner per tile: the one whose octant (about the ball's centre) holds the point where the footprint centre's
+ * segment from the light enters the shrunk cube — with n.w > 0 the corner pieces towards the light are the ones
+ * that can qualify.
+ *
+ * Host (scene_plan.cpp: plan_dark_nodes, dark_cull_of): light 0 lit and finite, eye and light on the same side of the
+ * ground, every K strictly between the ground and the light's height by more than m; the margins are derived once per
+ * scene, for a scale that covers every eye within DarkCull::eye_max of the origin.  The result does not depend on the
+ * void or silhouette tests' switches; the pre-pass sets the bit for primary-ground tiles only. */
+constexpr int kMaxDarkNodes = 8; /* kMaxSphereNodes + kMaxVoidNodes */
+
+struct DarkNode {
+    double lo[3], hi[3];           /* kind 1: the Cube shrunk by pad + 2 m */
+    double c[3];                   /* kind 0: the ball's centre; kind 1: the subtracted ball's */
+    double r;                      /* kind 0: R - 2 m; kind 1: R + 2 m, the cuts' distance from the ball's centre */
+    uint32_t node;                 /* node index (< kMaxCullNodes) */
+    uint32_t kind;                 /* 0: Sphere node, 1: CsgDiff(Cube, Sphere) node */
+};
+
+/* the dark-tile table of the mask pre-pass, next to VoidCull (whose light0 it uses).  It does not fit the kernel-argument
+ * segment beside the other two: a scene table in device memory, or part of a batch frame's BatchCull */
+struct DarkCull {
+    uint32_t n, pad;
+    double reach;                  /* the scale the margins were derived for: footprint limit of the Sphere kind */
+    double eye_max;                /* ... with the eye within this max-norm of the origin (host: dark_cull_of) */
+    DarkNode d[kMaxDarkNodes];
+};
+
+/* the segment light -> light + d passes within r of c */
+C2RT_VOID_FN bool segment_meets_ball(const double L[3], const double d[3], const double c[3], double r)
+{
+    const double w0 = c[0] - L[0], w1 = c[1] - L[1], w2 = c[2] - L[2];
+    const double dd = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    double t = (w0 * d[0] + w1 * d[1] + w2 * d[2]) / dd;
+    if (!(t >= 0)) t = 0; /* (NaN: refused below) */
+    if (t > 1) t = 1;
+    const double e0 = w0 - t * d[0], e1 = w1 - t * d[1], e2 = w2 - t * d[2];
+    return r > 0 && dd > 0 && e0 * e0 + e1 * e1 + e2 * e2 <= r * r * (1 - 1e-9);
+}
+
+/* the parameter interval [t0, t1] of the segment light -> light + d inside the box [lo, hi]; false: empty */
+C2RT_VOID_FN bool segment_clip_box(const double L[3], const double d[3], const double lo[3], const double hi[3], double &t0, double &t1)
+{
+    t0 = 0;
+    t1 = 1;
+    for (int i = 0; i < 3; ++i) {
+        if (d[i] == 0) {
+            if (!(L[i] >= lo[i] && L[i] <= hi[i])) return false;
+        } else {
+            double ta = (lo[i] - L[i]) / d[i], tb = (hi[i] - L[i]) / d[i];
+            if (ta > tb) { const double x = ta; ta = tb; tb = x; }
+            if (!(ta <= tb)) return false; /* non-finite */
+            t0 = ta > t0 ? ta : t0;
+            t1 = tb < t1 ? tb : t1;
+        }
+    }
+    return t0 <= t1;
+}
+
+/* the cuts of kind 1: the corner's own normal (1, 1, 1) and its neighbours, signs by the corner */
+constexpr int kDarkCuts = 10;
+
+/* One primary-ground tile with the shadow pyramid's edges sdir (footprint_dirs: light -> the padded footprint's
+ * corners) and the footprint's reach measure (tile_mask_entry: in_reach): every shadow ray of the tile towards
+ * `light` is occluded by node k (derivation above). */
+C2RT_VOID_FN bool tile_dark_by(const double light[3], const double sdir[4][3], bool in_reach, const DarkNode &k)
+{
+    if (k.kind == 0u) {
+        if (!in_reach) return false;
+        bool ok = true;
+        for (int e = 0; e < 4; ++e) ok = ok && segment_meets_ball(light, sdir[e], k.c, k.r);
+        return ok;
+    }
+    double mid[3], sg[3], t0, t1;
+    for (int i = 0; i < 3; ++i) mid[i] = 0.25 * (sdir[0][i] + sdir[1][i] + sdir[2][i] + sdir[3][i]);
+    if (!segment_clip_box(light, mid, k.lo, k.hi, t0, t1)) return false;
+    for (int i = 0; i < 3; ++i) sg[i] = light[i] + t0 * mid[i] >= k.c[i] ? 1.0 : -1.0;
+    const double w[kDarkCuts][3] = {{1, 1, 1}, {2, 1, 1}, {1, 2, 1}, {1, 1, 2}, {2, 2, 1}, {2, 1, 2}, {1, 2, 2}, {3, 1, 1}, {1, 3, 1}, {1, 1, 3}};
+    const double len[kDarkCuts] = {1.7320508075688774, 2.4494897427831783, 2.4494897427831783, 2.4494897427831783, 3, 3, 3,
+                                   3.3166247903554, 3.3166247903554, 3.3166247903554};
+    /* Per corner segment e, once: its interval [te0, te1] inside the shrunk cube.  Per cut, with s not normalised and r
+     * scaled to match: the segment meets {s.(p - c) >= r} inside that interval iff a + t b >= 0 at t = te0, given b =
+     * s.d < 0 (towards the light the ray climbs along s: the n.w > 0 of the derivation, with 1e-5 relative to spare for
+     * the origins' 1e-6 step) — no division in the loop: the pre-pass evaluates this in one lane per tile. */
+    double te0[4];
+    for (int e = 0; e < 4; ++e) {
+        double te1;
+        if (!segment_clip_box(light, sdir[e], k.lo, k.hi, te0[e], te1)) return false;
+    }
+    double rel[3]; /* light - c */
+    for (int i = 0; i < 3; ++i) rel[i] = light[i] - k.c[i];
+    bool dark = false;
+    for (int q = 0; q < kDarkCuts; ++q) {
+        const double s0 = sg[0] * w[q][0], s1 = sg[1] * w[q][1], s2 = sg[2] * w[q][2];
+        const double a = s0 * rel[0] + s1 * rel[1] + s2 * rel[2] - k.r * len[q] * (1 + 1e-12);
+        bool ok = true;
+        for (int e = 0; e < 4; ++e) {
+            const double b0 = s0 * sdir[e][0], b1 = s1 * sdir[e][1], b2 = s2 * sdir[e][2];
+            const double b = b0 + b1 + b2;
+            ok = ok && b < -1e-5 * (void_abs(b0) + void_abs(b1) + void_abs(b2)) && a + te0[e] * b >= 0;
+        }
+        dark = dark || ok;
+    }
+    return dark;
+}
+
 } // namespace c2rt
 
 #endif

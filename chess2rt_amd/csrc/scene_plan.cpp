@@ -578,6 +578,75 @@ void plan_sphere_nodes(const c2rt_scene_desc *s, ScenePlan &p)
     }
 }
 
+/* The dark-tile test's table (csg_void.h, "Dark ground tiles"): the Sphere nodes above and the CsgDiff nodes above
+ * whose left child is a Cube, with their convex sets eroded by the margins.  The table belongs to the scene — it is
+ * uploaded with it and refreshed by c2rt_update_scene like the shadow rectangles —, so the margins are derived for
+ * every eye within DarkCull::eye_max of the origin (max-norm; four times the scene's own scale, at least 1000), and
+ * a frame whose eye lies farther out goes without the test (dark_cull_of).  Only where the scene has a ground, light 0
+ * is finite and lit, and the node's convex set lies strictly between the ground and the light's height by more than
+ * its margin. */
+void plan_dark_nodes(const c2rt_scene_desc *s, ScenePlan &p)
+{
+    p.dark = DarkCull{};
+    if (p.ground_node < 0 || s->n_lights == 0 || p.lights.empty() || !(p.lights[0].lit & 1u)) return;
+    const double *L = s->light_pos, gy = p.ground_y, h = L[1] - gy;
+    if (!(std::isfinite(L[0]) && std::isfinite(L[1]) && std::isfinite(L[2]) && std::isfinite(h)) || h == 0) return;
+    const double light_mag = std::max(std::fabs(L[0]), std::max(std::fabs(L[1]), std::fabs(L[2])));
+    double base = 0; /* the largest R + |c| of the tested balls */
+    for (const SphereNode &b : p.sphere_nodes)
+        base = std::max(base, b.rp + std::max(std::fabs(b.c[0]), std::max(std::fabs(b.c[1]), std::fabs(b.c[2]))));
+    for (const VoidNode &v : p.void_nodes)
+        base = std::max(base, v.r2 + std::max(std::fabs(v.c[0]), std::max(std::fabs(v.c[1]), std::fabs(v.c[2]))));
+    const double eye_max = std::max(1000.0, 4 * (base + light_mag));
+    const double scale = base + light_mag + eye_max; /* at least every scale void_cull_of / sphere_cull_of derive */
+    if (!std::isfinite(scale)) return;
+    DarkCull dc{};
+    dc.eye_max = eye_max;
+    dc.reach = scale;
+    const auto between = [&](double klo, double khi) { /* the set's extent in y, already grown by the margin */
+        const double tol = 1e-6 + 1e-9 * (std::fabs(L[1]) + std::fabs(gy) + std::fabs(klo) + std::fabs(khi));
+        return std::isfinite(klo) && std::isfinite(khi) &&
+               ((h > 0 && klo > gy + tol && khi < L[1] - tol) || (h < 0 && khi < gy - tol && klo > L[1] + tol));
+    };
+    for (const SphereNode &b : p.sphere_nodes) {
+        if (dc.n >= (uint32_t)kMaxDarkNodes) break;
+        const double R = b.rp, m = sphere_margin(scale, R); /* (R: plan_sphere_nodes) */
+        DarkNode k{};
+        for (int j = 0; j < 3; ++j) k.c[j] = b.c[j];
+        k.r = R - 2 * m;
+        k.node = b.node;
+        k.kind = 0u;
+        if (!(k.r > 0) || !std::isfinite(k.r) || !between(k.c[1] - R - m, k.c[1] + R + m)) continue;
+        dc.d[dc.n++] = k;
+    }
+    for (const VoidNode &v : p.void_nodes) {
+        if (dc.n >= (uint32_t)kMaxDarkNodes) break;
+        const DevNode &d = p.nodes[v.node];
+        const int32_t l = s->geom_child[2 * d.geom];
+        if (s->geom_type[l] != C2RT_GEOM_CUBE) continue;
+        const double *cp = s->geom_param + 4 * (size_t)l;
+        const double half = std::fabs(cp[3]) * 0.5, R = v.r2, m = void_margin(scale); /* (R: plan_void_nodes) */
+        DarkNode k{};
+        bool ok = half > 0;
+        for (int j = 0; j < 3; ++j) {
+            /* the cube's own faces moved inwards by the node box's padding (a bound of every rounding the box
+             * carries), then by 2 m */
+            const double clo = cp[j] - half + d.off[j], chi = cp[j] + half + d.off[j];
+            const double pad = std::max(std::fabs(clo - v.lo[j]), std::fabs(v.hi[j] - chi));
+            k.lo[j] = clo + pad + 2 * m;
+            k.hi[j] = chi - pad - 2 * m;
+            k.c[j] = v.c[j];
+            ok = ok && std::isfinite(k.lo[j]) && std::isfinite(k.hi[j]) && k.lo[j] < k.hi[j];
+        }
+        k.r = R + 2 * m;
+        k.node = v.node;
+        k.kind = 1u;
+        if (!ok || !(k.r > 0) || !std::isfinite(k.r) || !between(v.lo[1] - m, v.hi[1] + m)) continue;
+        dc.d[dc.n++] = k;
+    }
+    if (dc.n) p.dark = dc;
+}
+
 } // namespace
 
 int check_scene_desc(const c2rt_scene_desc *s, std::string &err)
@@ -615,6 +684,7 @@ int plan_checked_scene(const c2rt_scene_desc *s, ScenePlan &plan, std::string &e
     plan_ground_rects(s, p);
     plan_void_nodes(s, p);
     plan_sphere_nodes(s, p);
+    plan_dark_nodes(s, p);
     p.n_nodes = s->n_nodes;
     p.n_lights = s->n_lights;
     std::memcpy(p.ambient, s->ambient, sizeof p.ambient);
@@ -1087,6 +1157,24 @@ SphereCull sphere_cull_of(const ScenePlan &plan, const DiagKnobs &knobs, const R
         if (s.flags) sc.s[sc.n++] = s;
     }
     return sc;
+}
+
+/* the dark-tile test's per-frame part (csg_void.h): the scene's table (plan_dark_nodes), or none — where the frame
+ * runs no ground refinement, where the eye is not on the light's side of the ground, or lies beyond the distance the
+ * table's margins were derived for.  Independent of the void and silhouette tests' switches.  Diagnostics build only:
+ * C2RT_DEBUG_CULL bit 5: no dark-tile test (frames are unchanged, slower). */
+bool dark_frame_ok(const ScenePlan &plan, const DiagKnobs &knobs, const RenderParams &p)
+{
+    if ((knobs.debug_cull & 32) || !plan.dark.n || p.ground_node < 0 || !p.n_cull || plan.light_pos.size() < 3) return false;
+    const double h = plan.light_pos[1] - p.ground_y, eye = p.cam.pos[1] - p.ground_y;
+    if (!((h > 0 && eye > 0) || (h < 0 && eye < 0))) return false;
+    const double cam_mag = std::max(std::fabs(p.cam.pos[0]), std::max(std::fabs(p.cam.pos[1]), std::fabs(p.cam.pos[2])));
+    return cam_mag <= plan.dark.eye_max;
+}
+
+DarkCull dark_cull_of(const ScenePlan &plan, const DiagKnobs &knobs, const RenderParams &p)
+{
+    return dark_frame_ok(plan, knobs, p) ? plan.dark : DarkCull{};
 }
 
 } // namespace c2rt

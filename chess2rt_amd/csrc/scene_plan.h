@@ -48,6 +48,9 @@ struct ScenePlan {
     /* Sphere nodes under an identity matrix the pre-pass may drop from tiles outside their silhouette (csg_void.h);
      * SphereNode::rp holds R here, the frame's margin is applied in sphere_cull_of */
     std::vector<SphereNode> sphere_nodes;
+    /* the dark-tile test's table (csg_void.h): the nodes whose shadow may make a primary-ground tile dark, margins
+     * applied; a scene table like shadow_rects (uploaded, refreshed by c2rt_update_scene); n = 0: none */
+    DarkCull dark{};
 };
 
 /* The refusals that look at the description's header and table pointers only (null scene, ABI version, GI, a null
@@ -110,6 +113,7 @@ struct DeviceTables {
     DevLight *lights = nullptr;
     float *texels = nullptr;
     double *shadow_rects = nullptr;    /* [kMaxCullNodes][4] */
+    DarkCull *dark = nullptr;          /* ScenePlan::dark */
     uint32_t *tile_stats = nullptr;    /* diagnostics (c2rt_debug_set_tile_stats): caller-owned device buffer */
 };
 
@@ -119,7 +123,8 @@ struct DiagKnobs {
     bool exact = false;                /* C2RT_EXACT=1: every tile through exact:: */
     /* C2RT_DEBUG_CULL (frames are unchanged by construction, slower): bit 0: no culling rectangles at all; bit 1: no
      * ground-plane refinement of the shadow mask; bit 2: no view-pyramid culling of shadow rays; bit 3: no
-     * sphere-silhouette test in the mask pre-pass; bit 4: no ground-tile path (RenderParams::ground_fast stays 0) */
+     * sphere-silhouette test in the mask pre-pass; bit 4: no ground-tile path (RenderParams::ground_fast stays 0); bit 5: no
+     * dark-tile test in the mask pre-pass (dark_cull_of) */
     int debug_cull = 0;
     int csg_first_cap = 0;             /* C2RT_CSG_FIRST_CAP=<entries>: the first pass's hit-stack capacity */
 };
@@ -138,6 +143,8 @@ void fill_params(const ScenePlan &plan, const DeviceTables &dev, const DiagKnobs
                  const c2rt_render_opts *o, RenderParams &p);
 VoidCull void_cull_of(const ScenePlan &plan, const RenderParams &p, uint32_t flags_mask);
 SphereCull sphere_cull_of(const ScenePlan &plan, const DiagKnobs &knobs, const RenderParams &p, uint32_t flags_mask);
+bool dark_frame_ok(const ScenePlan &plan, const DiagKnobs &knobs, const RenderParams &p);
+DarkCull dark_cull_of(const ScenePlan &plan, const DiagKnobs &knobs, const RenderParams &p);
 KernelVariant variant_of(const ScenePlan &plan, const c2rt_camera_frame *cam);
 
 } // namespace c2rt
