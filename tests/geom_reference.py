@@ -19,12 +19,20 @@ Inputs are the scene descriptor's tables (include/c2rt.h) and rays / segments; n
     later pair overrides an earlier one at EQUAL distance; u, v are taken in the projected frame;
   - findAllIntersections restarts from p + dir * 1e-6 and sums the lengths without those steps; it is capped at
     MAX_CSG_HITS hits per child as the ABI documents (the reference loops `while (true)`); `Trace.truncations` counts
-    the lists that reached the cap — the tests require 0;
-  - the CsgOp walk sorts by dist.  The reference uses a shell sort (util/array.d:95-111), which is NOT stable; what is
-    relied on here is only that a comparison sort of DISTINCT keys has one result.  `Trace.ties` counts equal
-    neighbouring distances in a sorted list (the tests require 0; the stable sort used here would keep the order of
-    chain(left, right) for them).  Parities come from the list lengths; `current.g is left` compares the LEAF, so the
-    entries of a nested CsgOp left child toggle inR; `data = current` copies the whole record;
+    the lists that reached the cap (0 on tests/geom_scenes.py; one tree of tests/csg_edge_scenes.py is built to reach it);
+  - the CsgOp walk sorts chain(leftData[], rightData[]) by dist with the reference's shell sort, restated literally
+    from util/array.d:95-111 (`shell_sort`: gap n / 2, insertion by gap with the `ref i` index rewound by the inner
+    `while`, `inc == 2 ? 1 : cast(int)(inc * 5.0 / 11)`, strict `>` on dist), which is NOT stable.  A comparison sort
+    of DISTINCT keys has one result, so the rows whose stable order has no equal finite neighbours (and no NaN) are
+    sorted by numpy's stable argsort, and only the others — the tied lists — go through the literal sort, row by
+    row: the reference is defined on ties.  `Trace.ties` counts equal neighbouring distances in a sorted list, a
+    statistic (tests/geom_scenes.py's tests require 0 on their scene; tests/csg_edge_scenes.py is built to have
+    many).  Parities come from the list lengths; `current.g is left` compares the LEAF, so the entries of a nested
+    CsgOp left child toggle inR, an entry of the right list whose leaf is `left` toggles inL, and in Op(a, a) every
+    entry toggles inL; `data = current` copies the whole record;
+  - per-ray flags of the walk (Trace.flags, and Trace.node_flags per node): tied_list (a sorted list with equal
+    neighbours was walked), odd_list (a child list of odd length), long_list (a child list of more than two),
+    capped_list, right_entry_toggles_left, left_entry_toggles_right (the last two for entries the walk visited);
   - sphere u, v are the one place with libm and the reference's 80-bit PI: they are evaluated with mpmath at 50 digits
     from the typed object-space p (the subtractions and the division by R in double, as written) and rounded ONCE; as
     nothing in the geometry stage reads u or v, this is done once, for the record that survives;
@@ -41,9 +49,18 @@ GEOM_PLANE, GEOM_SPHERE, GEOM_CUBE, GEOM_CSG_UNION, GEOM_CSG_INTER, GEOM_CSG_DIF
 MAX_CSG_HITS = 8            # C2RT_MAX_CSG_HITS, include/c2rt.h
 
 # the named misreadings of test_geom_reference's mutation check (each changes ONE statement below)
-MUTATIONS = ("column_vector_product", "inverse_for_normal", "transform_for_undo", "normal_not_renormalised", "dist_not_rescaled",
-             "point_offset_before_matrix", "cube_uv_unprojected", "cube_equal_distance_keeps_first", "csg_identity_by_subtree",
-             "restart_length_includes_step", "diff_flip_probes_left", "plane_limit_ignored", "visibility_uses_1e99")
+GEOM_MUTATIONS = ("column_vector_product", "inverse_for_normal", "transform_for_undo", "normal_not_renormalised", "dist_not_rescaled",
+                  "point_offset_before_matrix", "cube_uv_unprojected", "cube_equal_distance_keeps_first", "csg_identity_by_subtree",
+                  "restart_length_includes_step", "diff_flip_probes_left", "plane_limit_ignored", "visibility_uses_1e99")
+# those of test_csg_edge_reference's (tests/csg_edge_scenes.py: ties, shared leaves, Op(a, a), Plane operands): the chain
+# is (right, left); `>=` in the sort's inner while; Plane.isInside true below the plane; inL, inR start false whatever the
+# list lengths; in Op(a, a) the right list toggles inR
+CSG_EDGE_MUTATIONS = ("chain_right_first", "sort_not_strict", "plane_is_inside_below", "parity_starts_outside", "op_aa_by_list")
+MUTATIONS = GEOM_MUTATIONS + CSG_EDGE_MUTATIONS
+# Variants that are REPORTED, not required to be seen: a stable sort in place of the shell sort (a trial over 50 tie trees
+# changed no record: key patterns on which the two differ need a first hit equal to a second hit, and a second hit is a
+# restart's 1e-6 short)
+VARIANTS = ("stable_sort",)
 
 RECORD = np.dtype([("closest_node", np.int32), ("leaf_geom", np.int32), ("dist", F64), ("u", F64), ("v", F64),
                    ("p", F64, 3), ("normal", F64, 3)])
@@ -147,16 +164,25 @@ class Hits:
 
 
 class Trace:
-    """what one evaluation leaves behind: flags (name -> (n,) bool per input ray), truncations, ties"""
+    """what one evaluation leaves behind: flags (name -> (n,) bool per input ray), node_flags ((name, node) -> the same
+    for what happened under that node), truncations, ties and both per node"""
 
     def __init__(self, T, n, mut):
         self.T, self.mut, self.n = T, mut, n
-        self.flags = {}
+        self.flags, self.node_flags = {}, {}
         self.truncations = 0
         self.ties = 0
+        self.node = -1
+        self.node_truncations = np.zeros(T.n_nodes, dtype=np.int64)
+        self.node_ties = np.zeros(T.n_nodes, dtype=np.int64)
 
     def note(self, name, rows):
         self.flags.setdefault(name, np.zeros(self.n, dtype=bool))[rows] = True
+        self.node_flags.setdefault((name, self.node), np.zeros(self.n, dtype=bool))[rows] = True
+
+    def flag(self, name, node=None):
+        z = np.zeros(self.n, dtype=bool)
+        return self.flags.get(name, z) if node is None else self.node_flags.get((name, node), z)
 
 
 # ---- geometry.d ---------------------------------------------------------------------------------------------------------------
@@ -285,7 +311,37 @@ def _find_all(S, geom, o, d, rows):
         full.put(hit, t)
         present[hit, k] = True
     S.truncations += int(active.sum())          # these lists reached the cap
+    S.node_truncations[S.node] += int(active.sum())
+    S.note("capped_list", rows[active])
     return entries, present
+
+
+def shell_sort(keys, strict=True):
+    """util/array.d:95-111 on a list of keys -> the permutation it leaves (indices into `keys`).  `foreach (ref i, elem;
+    arr)`: elem is a copy of arr[i] taken when the iteration starts, i is the loop's own index, so what the inner
+    `while` takes off it is kept and the `foreach` goes on from there.  (`strict=False`, the misreading `>=`: with the
+    rewound index two equal keys would change places for ever, so that variant inserts with an index of its own.)"""
+    arr = list(range(len(keys)))
+    inc = len(arr) // 2
+    while inc:
+        i = 0
+        while i < len(arr):
+            elem = arr[i]
+            if strict:
+                while i >= inc and keys[arr[i - inc]] > keys[elem]:
+                    arr[i] = arr[i - inc]
+                    i -= inc
+                arr[i] = elem
+                i += 1
+            else:
+                j = i
+                while j >= inc and keys[arr[j - inc]] >= keys[elem]:
+                    arr[j] = arr[j - inc]
+                    j -= inc
+                arr[j] = elem
+                i += 1
+        inc = 1 if inc == 2 else int(inc * 5.0 / 11)
+    return arr
 
 
 def _csg_base(S, g, o, d, data, rows):
@@ -300,21 +356,40 @@ def _csg_base(S, g, o, d, data, rows):
     for k, e in enumerate(entries):
         dist[present[:, k], k] = e.dist[present[:, k]]
         leaf[:, k] = e.g
-    order = np.argsort(dist, axis=1, kind="stable")                 # sort(allData[]) by opCmp: dist
+    chain = np.arange(2 * MAX_CSG_HITS)
+    if S.mut == "chain_right_first":
+        chain = np.concatenate([chain[MAX_CSG_HITS:], chain[:MAX_CSG_HITS]])
+    order = chain[np.argsort(dist[:, chain], axis=1, kind="stable")]  # sort(allData[]) by opCmp: dist, where it has one result
     sd = np.take_along_axis(dist, order, axis=1)
-    S.ties += int((np.isfinite(sd[:, 1:]) & (sd[:, 1:] == sd[:, :-1])).sum())
-    in_l = lp.sum(axis=1) % 2 == 1
-    in_r = rp.sum(axis=1) % 2 == 1
+    tied = np.isfinite(sd[:, 1:]) & (sd[:, 1:] == sd[:, :-1])
+    S.ties += int(tied.sum())
+    S.node_ties[S.node] += int(tied.sum())
+    S.note("tied_list", rows[tied.any(axis=1)])
+    if S.mut != "stable_sort":
+        for r in np.nonzero(tied.any(axis=1) | (np.isnan(dist) & present).any(axis=1))[0]:      # util/array.d:95-111
+            slots = chain[present[r, chain]]
+            perm = shell_sort([dist[r, k] for k in slots], S.mut != "sort_not_strict")
+            order[r, :len(slots)] = slots[perm]
+            order[r, len(slots):] = chain[~present[r, chain]]
+    nl, nr = lp.sum(axis=1), rp.sum(axis=1)
+    S.note("odd_list", rows[(nl % 2 == 1) | (nr % 2 == 1)])
+    S.note("long_list", rows[(nl > 2) | (nr > 2)])
+    in_l = nl % 2 == 1
+    in_r = nr % 2 == 1
+    if S.mut == "parity_starts_outside":
+        in_l, in_r = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
     done = np.zeros(n, dtype=bool)
     chosen = np.full(n, -1, dtype=np.int64)
     ar = np.arange(n)
     for k in range(2 * MAX_CSG_HITS):
         slot = order[:, k]
         valid = present[ar, slot] & ~done
-        if S.mut == "csg_identity_by_subtree":
+        if S.mut == "csg_identity_by_subtree" or (S.mut == "op_aa_by_list" and left == right):
             is_left = slot < MAX_CSG_HITS
         else:
             is_left = leaf[ar, slot] == left                         # `current.g is left`
+        S.note("right_entry_toggles_left", rows[valid & is_left & (slot >= MAX_CSG_HITS)])
+        S.note("left_entry_toggles_right", rows[valid & ~is_left & (slot < MAX_CSG_HITS)])
         in_l = np.where(valid & is_left, ~in_l, in_l)
         in_r = np.where(valid & ~is_left, ~in_r, in_r)
         fire = valid & _bool_op(S.T.geom_type[g], in_l, in_r)
@@ -339,7 +414,7 @@ def _csg_diff(S, g, o, d, data, rows):
     f = np.nonzero(found)[0]
     if len(f):
         step = d[f] * F64(1e-6)
-        flip = is_inside(S.T, probe, data.p[f] - step) != is_inside(S.T, probe, data.p[f] + step)
+        flip = is_inside(S.T, probe, data.p[f] - step, S.mut) != is_inside(S.T, probe, data.p[f] + step, S.mut)
         data.normal[f[flip]] = -data.normal[f[flip]]
         data.flip[f] = flip
     return found
@@ -358,10 +433,12 @@ def _geom(S, g, o, d, data, rows):
     return _csg_base(S, g, o, d, data, rows)
 
 
-def is_inside(T, g, p):
+def is_inside(T, g, p, mut=None):
     """isInside, geometry.d:25-28 (Plane: false), 127-130 (Sphere: <), 165-170 (Cube: <=), 334-337 (CsgOp)"""
     t = T.geom_type[g]
     if t == GEOM_PLANE:
+        if mut == "plane_is_inside_below":
+            return p[:, 1] < T.geom_param[g, 0]
         return np.zeros(len(p), dtype=bool)
     c, s = T.geom_param[g, :3], T.geom_param[g, 3]
     with np.errstate(invalid="ignore"):
@@ -371,7 +448,7 @@ def is_inside(T, g, p):
         if t == GEOM_CUBE:
             h = s * F64(0.5)
             return (np.abs(p[:, 0] - c[0]) <= h) & (np.abs(p[:, 1] - c[1]) <= h) & (np.abs(p[:, 2] - c[2]) <= h)
-    return _bool_op(t, is_inside(T, T.geom_child[g][0], p), is_inside(T, T.geom_child[g][1], p))
+    return _bool_op(t, is_inside(T, T.geom_child[g][0], p, mut), is_inside(T, T.geom_child[g][1], p, mut))
 
 
 # ---- node.d, transform.d --------------------------------------------------------------------------------------------------
@@ -445,6 +522,7 @@ def trace(T, rays, mut=None):
     data = Hits(n, 1e99)                                             # result.data.dist = 1e99
     closest = np.full(n, -1, dtype=np.int64)
     for node in range(T.n_nodes):                                    # foreach (node; scene.nodes)
+        S.node = node
         f = _node(S, node, o, d, data, rows)
         closest[f] = node                                            # the last node that returns true
     hit = closest >= 0
@@ -480,6 +558,7 @@ def test_visibility(T, segments, mut=None):
         if not len(idx):
             break
         sub = data.take(idx)
+        S.node = node
         f = _node(S, node, frm[idx], d[idx], sub, rows[idx])
         data.put(idx, sub)
         occluder[idx[f]] = node

@@ -147,7 +147,7 @@ def test_shadows_of_the_rotated_cube_and_the_sheared_sphere_fall_on_the_ground()
 # ---- (c) mutations -------------------------------------------------------------------------------------------------------------
 
 
-@pytest.mark.parametrize("mutation", gr.MUTATIONS)
+@pytest.mark.parametrize("mutation", gr.GEOM_MUTATIONS)
 def test_the_ray_sets_see_each_named_misreading(mutation):
     """a record counts when any of its bits changes, or the visibility of its shadow segments does (the segments are
     those of the UNMUTATED records, so that a changed answer is the visibility statement's own)"""
