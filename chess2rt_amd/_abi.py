@@ -238,6 +238,10 @@ C2RT_SYMBOLS = {
     "c2rt_render_hits": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(HitPlanes)]),
     "c2rt_render_frame_adaptive_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frame_adaptive": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
+    "c2rt_render_frames_adaptive_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
+    "c2rt_render_frames_adaptive": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
+    "c2rt_render_frames_posed_adaptive_device": (C.c_int, [_VP, _CAM_P, _POSE_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
+    "c2rt_render_frames_posed_adaptive": (C.c_int, [_VP, _CAM_P, _POSE_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_deinterleave_strips": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
     "c2rt_encode_rgb32": (C.c_int, [_VP, _VP, _VP, C.c_uint64, _VP]),
     "c2rt_render_frame_rgb32": (C.c_int, [_VP, _CAM_P, _OPTS_P, _VP, _VP]),

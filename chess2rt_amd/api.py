@@ -398,6 +398,50 @@ class Context:
         self._check(self._lib.c2rt_render_frame_adaptive_device(self._h, C.byref(cam), C.byref(opts), float(threshold),
                                                                 C.c_void_p(out_ptr or None), C.c_void_p(mask_ptr or None), C.c_void_p(stream)))
 
+    def renderFramesAdaptive(self, cams, opts, threshold=_abi.AA_THRESHOLD_REF, stop_flag=None):
+        """Adaptive anti-aliasing for a batch of cameras (c2rt_render_frames_adaptive; opts.taps must be TAPS_REF5):
+        (frames, masks) of shapes (len(cams), H, W, 3) float32 and (len(cams), H, W) uint8; frame i and mask i hold
+        the bits renderFrameAdaptive(cams[i], opts, threshold) returns.  One detection and one refinement launch for
+        all frames.  What a batch and what an adaptive frame refuse, this refuses (C2rtError)."""
+        arr, n = self._camera_array(cams)
+        frames = np.empty((n, opts.height, opts.width, 3), dtype=np.float32)
+        masks = np.empty((n, opts.height, opts.width), dtype=np.uint8)
+        stop = stop_flag.ctypes.data_as(C.c_void_p) if stop_flag is not None else None
+        self._check(self._lib.c2rt_render_frames_adaptive(self._h, arr, n, C.byref(opts), float(threshold),
+                                                          frames.ctypes.data_as(C.c_void_p), masks.ctypes.data_as(C.c_void_p), stop))
+        return frames, masks
+
+    def renderFramesAdaptiveDevice(self, cams, opts, out_ptr, mask_ptr, threshold=_abi.AA_THRESHOLD_REF, stream=0):
+        """Enqueue the adaptive batch on `stream` into device memory: len(cams) * H * W * 3 floats at out_ptr and
+        len(cams) * H * W bytes at mask_ptr (required)."""
+        arr, n = self._camera_array(cams)
+        self._check(self._lib.c2rt_render_frames_adaptive_device(self._h, arr, n, C.byref(opts), float(threshold),
+                                                                 C.c_void_p(out_ptr or None), C.c_void_p(mask_ptr or None), C.c_void_p(stream)))
+
+    def renderFramesPosedAdaptive(self, cams, poses, opts, threshold=_abi.AA_THRESHOLD_REF, stop_flag=None):
+        """An anti-aliased animation in one call (c2rt_render_frames_posed_adaptive): renderFramesAdaptive with poses[i]
+        — given as renderFramesPosed takes them, each relative to the current scene — applied to frame i.  The
+        context's scene is unchanged."""
+        arr, n = self._camera_array(cams)
+        parr, np_, keep = self._pose_array(poses)
+        if np_ != n:
+            raise ValueError("%d cameras, %d poses" % (n, np_))
+        frames = np.empty((n, opts.height, opts.width, 3), dtype=np.float32)
+        masks = np.empty((n, opts.height, opts.width), dtype=np.uint8)
+        stop = stop_flag.ctypes.data_as(C.c_void_p) if stop_flag is not None else None
+        self._check(self._lib.c2rt_render_frames_posed_adaptive(self._h, arr, parr, n, C.byref(opts), float(threshold),
+                                                                frames.ctypes.data_as(C.c_void_p), masks.ctypes.data_as(C.c_void_p), stop))
+        return frames, masks
+
+    def renderFramesPosedAdaptiveDevice(self, cams, poses, opts, out_ptr, mask_ptr, threshold=_abi.AA_THRESHOLD_REF, stream=0):
+        """Enqueue the posed adaptive batch on `stream` into device memory, laid out as for renderFramesAdaptiveDevice."""
+        arr, n = self._camera_array(cams)
+        parr, np_, keep = self._pose_array(poses)
+        if np_ != n:
+            raise ValueError("%d cameras, %d poses" % (n, np_))
+        self._check(self._lib.c2rt_render_frames_posed_adaptive_device(self._h, arr, parr, n, C.byref(opts), float(threshold),
+                                                                       C.c_void_p(out_ptr or None), C.c_void_p(mask_ptr or None), C.c_void_p(stream)))
+
     def rayStats(self):
         s = RayStats()
         self._check(self._lib.c2rt_get_ray_stats(self._h, C.byref(s)))

@@ -22,6 +22,12 @@
  * Detection is a launch of its own: it reads the neighbours' ONE-TAP values, and refinement overwrites pixels in
  * place; the caller's mask is the buffer between the two.  Refinement reads and writes its own pixel and the mask only.
  *
+ * Batches (c2rt_render_frames_adaptive*): detection takes a frame stride and blockIdx.y = frame (stride 0 and one row of
+ * blocks in the single-frame call); aa_refine_batch_kernel is the same wave over a TABLE of parameter blocks in HBM, one
+ * per frame, read through a constant-address-space pointer as render_kernel_batch reads its own (c2rt_kernels.hip):
+ * scalar loads, no VGPR.  A frame's block names the frame (RenderParams::out); its flags are the frame's slice of the
+ * batch's mask.  The flagged tiles of every frame share one grid, so one tile's trace latency overlaps the others'.
+ *
  * The plain variant — every flagged lane loops over its four taps, the others sit out — was measured against the packed
  * one and rejected (profiles/adaptive_aa.md; DESIGN.md, "Adaptive anti-aliasing"); it was a build switch up to commit
  * f0eed4f, c2rt_kernels.hip.
@@ -37,9 +43,13 @@ static_assert(kTileW * kTileH == kWave, "one wavefront, one tile");
 constexpr int kAaDetectWaves = 4; /* tiles (wavefronts) per workgroup of the detection kernel */
 
 __global__ void __launch_bounds__(kWave * kAaDetectWaves)
-aa_detect_kernel(const float *__restrict__ frame, uint8_t *__restrict__ needs_aa, const uint32_t width, const uint32_t height,
-                 const uint32_t tiles_x, const uint32_t n_tiles, const float threshold)
+aa_detect_kernel(const float *__restrict__ frames, uint8_t *__restrict__ masks, const size_t frame_px, const uint32_t width,
+                 const uint32_t height, const uint32_t tiles_x, const uint32_t n_tiles, const float threshold)
 {
+    /* blockIdx.y = frame; frame_px = pixels from one frame (and its flags) to the next, 0 in the single-frame call.  The
+     * neighbours below are clamped at this frame's own edges */
+    const float *__restrict__ frame = frames + (size_t)blockIdx.y * frame_px * 3;
+    uint8_t *__restrict__ needs_aa = masks + (size_t)blockIdx.y * frame_px;
     const uint32_t tile = blockIdx.x * kAaDetectWaves + threadIdx.x / kWave;
     if (tile >= n_tiles) return;
     const uint32_t lane = threadIdx.x % kWave;
@@ -70,9 +80,11 @@ aa_detect_kernel(const float *__restrict__ frame, uint8_t *__restrict__ needs_aa
 
 constexpr size_t kAaColourBytes = (size_t)kWave * 4 * 3 * sizeof(float), kAaListBytes = kWave;
 
+/* The packed wave over tile blockIdx.x of the frame `P` describes: one body for both entry points below, which only
+ * produce (P, K, frame, needs_aa). */
 template <int LEVELS, bool MLC>
-__global__ void __launch_bounds__(kWave) C2RT_WAVES_QUERY(LEVELS, MLC)
-aa_refine_kernel(const RenderParams P, float *__restrict__ frame, const uint8_t *__restrict__ needs_aa, const uint32_t tiles_x)
+DEV void aa_refine_body(const RenderParams &P, exact::KArgs K, float *__restrict__ frame, const uint8_t *__restrict__ needs_aa,
+                        const uint32_t tiles_x)
 {
     using namespace exact;
     extern __shared__ __align__(16) char lds[];
@@ -86,7 +98,7 @@ aa_refine_kernel(const RenderParams P, float *__restrict__ frame, const uint8_t 
     const size_t stack = (size_t)P.csg_cap * kCsgLdsPerEntry;
     float *colour = reinterpret_cast<float *>(lds + stack); /* [pixel's lane][tap - 1][3] */
     Ctx cx;
-    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
+    query_ctx(cx, P, K, lds, lane);
     uint8_t *list = reinterpret_cast<uint8_t *>(lds + stack + kAaColourBytes); /* the flagged lanes, ascending */
     if (flagged) list[__popcll(flags & ((1ull << lane) - 1ull))] = (uint8_t)lane;
     __builtin_amdgcn_wave_barrier(); /* LDS operations of one wave complete in order; the workgroup is this wave */
@@ -128,26 +140,62 @@ aa_refine_kernel(const RenderParams P, float *__restrict__ frame, const uint8_t 
     }
 }
 
+template <int LEVELS, bool MLC>
+__global__ void __launch_bounds__(kWave) C2RT_WAVES_QUERY(LEVELS, MLC)
+aa_refine_kernel(const RenderParams P, float *__restrict__ frame, const uint8_t *__restrict__ needs_aa, const uint32_t tiles_x)
+{
+    aa_refine_body<LEVELS, MLC>(P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), frame, needs_aa, tiles_x);
+}
+
+/* batch_block of c2rt_kernels.hip, restated (that file's objects stay as they are): block blockIdx.y of the table
+ * through a constant-address-space pointer; the empty asm keeps the optimiser from folding the casts back to the global
+ * pointer, loads through which would be vector loads. */
+DEV KArgs batch_block(const RenderParams *table)
+{
+    KArgs K = (KArgs)table + blockIdx.y;
+    asm volatile("" : "+s"(K));
+    return K;
+}
+
+/* The same over a batch: blockIdx.y = frame, blockIdx.x = tile.  frame_px = the pixels of one frame. */
+template <int LEVELS, bool MLC>
+__global__ void __launch_bounds__(kWave) C2RT_WAVES_QUERY(LEVELS, MLC)
+aa_refine_batch_kernel(const RenderParams *table, const uint8_t *__restrict__ masks, const size_t frame_px, const uint32_t tiles_x)
+{
+    const KArgs K = batch_block(table);
+    const RenderParams &P = *(const RenderParams *)K;
+    aa_refine_body<LEVELS, MLC>(P, (exact::KArgs)K, P.out, masks + (size_t)blockIdx.y * frame_px, tiles_x);
+}
+
+/* table_dev null: the single-frame kernel with `p` as its argument, into `frame`; otherwise the n_frames blocks at
+ * table_dev, of which `p` is any one's host copy (the grid, the stack and the instance are the same for all of them) */
 template <int LEVELS>
-int launch_aa_refine_level(const RenderParams &p, float *frame, const uint8_t *needs_aa, hipStream_t s)
+int launch_aa_refine_level(const RenderParams &p, const RenderParams *table_dev, uint32_t n_frames, float *frame, const uint8_t *needs_aa,
+                           hipStream_t s)
 {
     const uint32_t tiles_x = (p.width + kTileW - 1) / kTileW, tiles_y = (p.height + kTileH - 1) / kTileH;
-    const dim3 grid(tiles_x * tiles_y), block(kWave); /* at most 2^16 x 2^16 pixels / 64 */
+    const dim3 grid(tiles_x * tiles_y, n_frames), block(kWave); /* at most 2^16 x 2^16 pixels / 64 */
     const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry + kAaColourBytes + kAaListBytes;
-    if (p.n_lights > 1) hipLaunchKernelGGL((aa_refine_kernel<LEVELS, true>), grid, block, lds, s, p, frame, needs_aa, tiles_x);
+    const size_t frame_px = (size_t)p.width * p.height;
+    if (table_dev) {
+        if (p.n_lights > 1) hipLaunchKernelGGL((aa_refine_batch_kernel<LEVELS, true>), grid, block, lds, s, table_dev, needs_aa, frame_px, tiles_x);
+        else hipLaunchKernelGGL((aa_refine_batch_kernel<LEVELS, false>), grid, block, lds, s, table_dev, needs_aa, frame_px, tiles_x);
+    } else if (p.n_lights > 1) hipLaunchKernelGGL((aa_refine_kernel<LEVELS, true>), grid, block, lds, s, p, frame, needs_aa, tiles_x);
     else hipLaunchKernelGGL((aa_refine_kernel<LEVELS, false>), grid, block, lds, s, p, frame, needs_aa, tiles_x);
     return (int)hipGetLastError();
 }
 
 } // namespace
 
-/* needs_aa[y][x] of the whole width x height frame at `frame` (device pointers). */
-int launch_aa_detect(const float *frame, uint8_t *needs_aa, uint32_t width, uint32_t height, float threshold, void *stream)
+/* needs_aa[y][x] of the n_frames whole width x height frames side by side at `frames`, their flags side by side at
+ * `needs_aa` (device pointers), in one launch. */
+int launch_aa_detect(const float *frames, uint8_t *needs_aa, uint32_t width, uint32_t height, uint32_t n_frames, float threshold, void *stream)
 {
-    if (!width || !height || !frame || !needs_aa) return (int)hipErrorInvalidValue;
+    if (!width || !height || !n_frames || n_frames > C2RT_MAX_BATCH_FRAMES || !frames || !needs_aa) return (int)hipErrorInvalidValue;
     const uint32_t tiles_x = (width + kTileW - 1) / kTileW, n_tiles = tiles_x * ((height + kTileH - 1) / kTileH);
-    hipLaunchKernelGGL(aa_detect_kernel, dim3((n_tiles + kAaDetectWaves - 1) / kAaDetectWaves), dim3(kWave * kAaDetectWaves), 0,
-                       static_cast<hipStream_t>(stream), frame, needs_aa, width, height, tiles_x, n_tiles, threshold);
+    const size_t frame_px = n_frames > 1 ? (size_t)width * height : 0;
+    hipLaunchKernelGGL(aa_detect_kernel, dim3((n_tiles + kAaDetectWaves - 1) / kAaDetectWaves, n_frames), dim3(kWave * kAaDetectWaves), 0,
+                       static_cast<hipStream_t>(stream), frames, needs_aa, frame_px, width, height, tiles_x, n_tiles, threshold);
     return (int)hipGetLastError();
 }
 
@@ -157,7 +205,17 @@ int launch_aa_refine(const RenderParams &p, int csg_levels, float *frame, const 
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!p.width || !p.height || !frame || !needs_aa) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) { return launch_aa_refine_level<decltype(L)::value>(p, frame, needs_aa, s); });
+    return for_csg_levels(csg_levels, [&](auto L) { return launch_aa_refine_level<decltype(L)::value>(p, nullptr, 1, frame, needs_aa, s); });
+}
+
+/* The same for the n_frames frames of a batch in one launch: table_dev holds their blocks (p0: any one's host copy),
+ * block i names frame i (RenderParams::out); needs_aa holds their flags side by side. */
+int launch_aa_refine_batch(const RenderParams &p0, int csg_levels, const RenderParams *table_dev, uint32_t n_frames, const uint8_t *needs_aa,
+                           void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!p0.width || !p0.height || !table_dev || !n_frames || n_frames > C2RT_MAX_BATCH_FRAMES || !needs_aa) return (int)hipErrorInvalidValue;
+    return for_csg_levels(csg_levels, [&](auto L) { return launch_aa_refine_level<decltype(L)::value>(p0, table_dev, n_frames, nullptr, needs_aa, s); });
 }
 
 } // namespace c2rt

@@ -47,7 +47,8 @@ struct FrameScratch {
     size_t retry_words = 0;
     /* batches: one RenderParams per frame (twice for nested CSG: first pass, retry pass), then one BatchCull per
      * frame, then (c2rt_render_frames_posed) the node, light and shadow-rectangle tables of the frames whose pose
-     * changes them; uploaded per call with one stream-ordered copy from ctx->batch_host */
+     * changes them, then (c2rt_render_frames_adaptive) one refinement block per frame; uploaded per call with one
+     * stream-ordered copy from ctx->batch_host */
     char *batch_table = nullptr;
     size_t batch_bytes = 0;
 };
@@ -330,6 +331,29 @@ int render_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render
     return C2RT_OK;
 }
 
+/* The hit-plane and refinement kernels' settings on top of a frame's filled parameter block (hit_params;
+ * render_frames_device's refinement blocks): exact:: arithmetic, full-capacity hit stack, no culling rectangles (every
+ * mask all ones), no ground node, one tap.  The CSG depth is the geometries', which no pose changes. */
+void hit_settings(const c2rt_ctx *ctx, RenderParams &p)
+{
+    p.force_exact = 1;
+    p.taps = 1;
+    p.seed = 0;
+    p.n_cull = 0;
+    p.n_cull_lights = 0;
+    p.ground_node = -1;
+    p.row_group_start = 0;
+    p.csg_cap = ctx->plan.csg_levels == 0 ? 0u : (uint32_t)kCsgFullCap(ctx->plan.csg_levels);
+    p.redo_counter = ctx->counters + 3;
+}
+
+/* What turns a one-tap batch into an adaptive one (c2rt_render_frames_adaptive*): the flags of frame i at mask_dev +
+ * i * width * height. */
+struct AdaptiveBatch {
+    float threshold;
+    uint8_t *mask_dev;
+};
+
 /* Why a batch refuses (cams, opts), decided before anything is enqueued; C2RT_OK otherwise. */
 int check_batch_args(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts)
 {
@@ -397,9 +421,16 @@ int plan_posed_frames(c2rt_ctx *ctx, const c2rt_scene_pose *poses, uint32_t n_fr
  * copy.  One launch runs one instance: the frames are laid out in the table as up to two groups by what the launcher
  * cannot share — the plane instances of a single-light scene (launch_render_batch_level) — and a group that mixes
  * identity-only frames with others runs the general instance (the launcher's copy of a block says so; the instances
- * are held to the same bits: counted frames run the general one, tests/conftest.py). */
+ * are held to the same bits: counted frames run the general one, tests/conftest.py).
+ *
+ * adaptive (nullable; c2rt_render_frames_adaptive, opts->taps == C2RT_TAPS_1, no strips): behind the frames, one
+ * detection launch and one refinement launch for all of them.  Frame i's refinement block is what hit_params makes for
+ * it — from its own plan, naming its own node and light tables and its own frame — and sits at index i behind the
+ * posed tables, in the same allocation and the same copy: the frames, the flags and these blocks go by FRAME, only the
+ * one-tap blocks by `order`.  Without it the call enqueues what it always has. */
 int render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const std::vector<std::unique_ptr<PosedFrame>> *posed,
-                         uint32_t n_frames, const c2rt_render_opts *opts, float *out_dev, hipStream_t stream)
+                         uint32_t n_frames, const c2rt_render_opts *opts, float *out_dev, hipStream_t stream,
+                         const AdaptiveBatch *adaptive = nullptr)
 {
     const int levels = ctx->plan.csg_levels; /* geometries are not posed: the same for every frame */
     const KernelVariant variant = variant_of(ctx->plan, &cams[0]);
@@ -431,8 +462,11 @@ int render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const std
                          (f->own_lights ? align16(f->plan.lights.size() * sizeof(DevLight)) : 0) +
                          (f->own_rects ? align16(f->plan.shadow_rects.size() * sizeof(double)) : 0);
     }
+    const size_t refine_at = align16(bytes);
+    if (adaptive) bytes = refine_at + n * sizeof(RenderParams);
     ctx->batch_host.resize(bytes);
     RenderParams *hp = reinterpret_cast<RenderParams *>(ctx->batch_host.data());
+    RenderParams *hr = reinterpret_cast<RenderParams *>(ctx->batch_host.data() + refine_at); /* [frame], not [order] */
     BatchCull *hc = reinterpret_cast<BatchCull *>(ctx->batch_host.data() + culls_at);
 
     for (size_t j = 0; j < n; ++j) fill_params(plan_of(order[j]), ctx->dev, diag_knobs(), &cams[order[j]], opts, hp[j]);
@@ -471,6 +505,10 @@ int render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const std
             if (f->own_rects) p.shadow_rects = reinterpret_cast<const double *>(place(f->plan.shadow_rects.data(), f->plan.shadow_rects.size() * sizeof(double)));
         }
         p.out = out_dev + i * frame_floats;
+        if (adaptive) {
+            hr[i] = p;
+            hit_settings(ctx, hr[i]);
+        }
         wire_frame(ctx, plan_of(i), p, sc, j, entries, blocks, ~0u, hc[j]);
         if (retry) {
             hp[n + j] = p;
@@ -497,6 +535,11 @@ int render_frames_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const std
         if (r == 0 && retry) r = launch_render_batch(again, variant, table_dev + n + a, (uint32_t)count, stream);
     }
     if (r != 0) return fail(ctx, C2RT_ERR_HIP, "render kernel launch: %s", hipGetErrorString((hipError_t)r));
+    if (!adaptive) return C2RT_OK;
+    r = launch_aa_detect(out_dev, adaptive->mask_dev, hr[0].width, hr[0].height, n_frames, adaptive->threshold, stream);
+    if (r != 0) return fail(ctx, C2RT_ERR_HIP, "adaptive AA detection kernel launch: %s", hipGetErrorString((hipError_t)r));
+    r = launch_aa_refine_batch(hr[0], levels, reinterpret_cast<const RenderParams *>(sc.batch_table + refine_at), n_frames, adaptive->mask_dev, stream);
+    if (r != 0) return fail(ctx, C2RT_ERR_HIP, "adaptive AA refinement kernel launch: %s", hipGetErrorString((hipError_t)r));
     return C2RT_OK;
 }
 
@@ -1412,15 +1455,7 @@ static int check_hit_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2r
 static void hit_params(const c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, RenderParams &p)
 {
     frame_params(ctx, cam, opts, p);
-    p.force_exact = 1;
-    p.taps = 1;
-    p.seed = 0;
-    p.n_cull = 0;
-    p.n_cull_lights = 0;
-    p.ground_node = -1;
-    p.row_group_start = 0;
-    p.csg_cap = ctx->plan.csg_levels == 0 ? 0u : (uint32_t)kCsgFullCap(ctx->plan.csg_levels);
-    p.redo_counter = ctx->counters + 3;
+    hit_settings(ctx, p);
 }
 
 int c2rt_render_hits_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
@@ -1514,7 +1549,7 @@ static int adaptive_enqueue(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c
     c2rt_render_opts one = *opts;
     one.taps = C2RT_TAPS_1;
     if (const int st = render_device(ctx, cam, &one, out_dev, stream)) return st;
-    int e = launch_aa_detect(out_dev, mask_dev, opts->width, opts->height, threshold, stream);
+    int e = launch_aa_detect(out_dev, mask_dev, opts->width, opts->height, 1, threshold, stream);
     if (e != 0) return fail(ctx, C2RT_ERR_HIP, "adaptive AA detection kernel launch: %s", hipGetErrorString((hipError_t)e));
     RenderParams p;
     hit_params(ctx, cam, &one, p);
@@ -1549,6 +1584,97 @@ int c2rt_render_frame_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cam, cons
     if (needs_aa) HIP_TRY(ctx, hipMemcpyAsync(needs_aa, mask_dev, px, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return C2RT_OK;
+}
+
+/* The refusals of the four batch entry points, in the documented order: a batch call's, then the arguments of this
+ * call, then strips; for the posed calls (poses_given), then the poses'.  Depth of field, stereo, count_rays,
+ * prepass_bucket and a multi-device context are among the batch call's. */
+static int check_adaptive_batch_args(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, bool poses_given,
+                                     uint32_t n_frames, const c2rt_render_opts *opts, float threshold, const void *out_rgb, bool mask_ok)
+{
+    if (const int st = check_batch_args(ctx, cams, n_frames, opts)) return st;
+    if (opts->taps != C2RT_TAPS_REF5) return fail(ctx, C2RT_ERR_INVALID_ARG, "adaptive anti-aliasing refines to C2RT_TAPS_REF5: taps is %u", (unsigned)opts->taps);
+    if (!(threshold >= 0.0f)) return fail(ctx, C2RT_ERR_INVALID_ARG, "threshold %g: neither negative nor NaN", (double)threshold);
+    if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    if (!mask_ok) return fail(ctx, C2RT_ERR_INVALID_ARG, "null needs_aa: the device variant keeps the flags in the caller's buffer");
+    if (opts->strip_world > 1) return fail(ctx, C2RT_ERR_UNSUPPORTED, "strip_world > 1: the rows above and below a strip belong to other ranks");
+    if (poses_given)
+        if (const int st = check_posed_args(ctx, poses, n_frames)) return st;
+    return C2RT_OK;
+}
+
+/* Both device variants; poses_given: the posed one.  The arguments have passed check_adaptive_batch_args. */
+static int adaptive_batch_enqueue(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, bool poses_given,
+                                  uint32_t n_frames, const c2rt_render_opts *opts, float threshold, float *out_dev, uint8_t *mask_dev,
+                                  hipStream_t stream)
+{
+    std::vector<std::unique_ptr<PosedFrame>> posed;
+    if (poses_given)
+        if (const int st = plan_posed_frames(ctx, poses, n_frames, posed)) return st;
+    c2rt_render_opts one = *opts;
+    one.taps = C2RT_TAPS_1;
+    const AdaptiveBatch adaptive = {threshold, mask_dev};
+    ctx->counters_valid = false;
+    return render_frames_device(ctx, cams, poses_given ? &posed : nullptr, n_frames, &one, out_dev, stream, &adaptive);
+}
+
+/* Both host variants: frames and masks side by side in the context's staging allocation, on the context's stream; one
+ * copy back per output, then a stream sync. */
+static int adaptive_batch_to_host(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, bool poses_given,
+                                  uint32_t n_frames, const c2rt_render_opts *opts, float threshold, float *out_rgb, uint8_t *needs_aa,
+                                  const volatile uint8_t *stop_flag)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (n_frames == 0) return C2RT_OK;
+    if (const int st = check_adaptive_batch_args(ctx, cams, poses, poses_given, n_frames, opts, threshold, out_rgb, true)) return st;
+    if (stop_flag && *stop_flag) return fail(ctx, C2RT_ERR_CANCELLED, "stop requested before the batch");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)n_frames * opts->width * opts->height;
+    const size_t off_mask = align256(px * 3 * sizeof(float));
+    if (const int st = ensure_staging(ctx, off_mask + px)) return st;
+    uint8_t *mask_dev = reinterpret_cast<uint8_t *>(ctx->frame) + off_mask;
+    if (const int st = adaptive_batch_enqueue(ctx, cams, poses, poses_given, n_frames, opts, threshold, ctx->frame, mask_dev, ctx->stream)) return st;
+    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->frame, px * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (needs_aa) HIP_TRY(ctx, hipMemcpyAsync(needs_aa, mask_dev, px, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return C2RT_OK;
+}
+
+static int adaptive_batch_to_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, bool poses_given,
+                                    uint32_t n_frames, const c2rt_render_opts *opts, float threshold, float *out_rgb_dev,
+                                    uint8_t *needs_aa_dev, void *hip_stream)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (n_frames == 0) return C2RT_OK;
+    if (const int st = check_adaptive_batch_args(ctx, cams, poses, poses_given, n_frames, opts, threshold, out_rgb_dev, needs_aa_dev != nullptr)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return adaptive_batch_enqueue(ctx, cams, poses, poses_given, n_frames, opts, threshold, out_rgb_dev, needs_aa_dev, static_cast<hipStream_t>(hip_stream));
+}
+
+int c2rt_render_frames_adaptive_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
+                                       float threshold, float *out_rgb_dev, uint8_t *needs_aa_dev, void *hip_stream)
+{
+    return adaptive_batch_to_device(ctx, cams, nullptr, false, n_frames, opts, threshold, out_rgb_dev, needs_aa_dev, hip_stream);
+}
+
+int c2rt_render_frames_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
+                                float threshold, float *out_rgb, uint8_t *needs_aa, const volatile uint8_t *stop_flag)
+{
+    return adaptive_batch_to_host(ctx, cams, nullptr, false, n_frames, opts, threshold, out_rgb, needs_aa, stop_flag);
+}
+
+int c2rt_render_frames_posed_adaptive_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, uint32_t n_frames,
+                                             const c2rt_render_opts *opts, float threshold, float *out_rgb_dev, uint8_t *needs_aa_dev,
+                                             void *hip_stream)
+{
+    return adaptive_batch_to_device(ctx, cams, poses, true, n_frames, opts, threshold, out_rgb_dev, needs_aa_dev, hip_stream);
+}
+
+int c2rt_render_frames_posed_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, uint32_t n_frames,
+                                      const c2rt_render_opts *opts, float threshold, float *out_rgb, uint8_t *needs_aa,
+                                      const volatile uint8_t *stop_flag)
+{
+    return adaptive_batch_to_host(ctx, cams, poses, true, n_frames, opts, threshold, out_rgb, needs_aa, stop_flag);
 }
 
 static int deinterleave_words(c2rt_ctx *ctx, const float *gathered_dev, float *frame_dev, uint32_t width, uint32_t height,

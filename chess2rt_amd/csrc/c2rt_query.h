@@ -20,10 +20,14 @@ int launch_test_visibility(const RenderParams &p, int csg_levels, const c2rt_seg
 /* Hit planes (c2rt_render_hits*): rows [row0, row0 + rows) of the local rows of the frame `p` describes, into planes
  * whose first row is row0; at least one plane non-null, rows > 0 */
 int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream);
-/* Adaptive anti-aliasing (c2rt_render_frame_adaptive*): the flag image needs_aa[y][x] of a whole one-tap frame, then
- * the flagged pixels of the whole frame `p` describes (no strips) from their one-tap to their five-tap value, in place */
-int launch_aa_detect(const float *frame, uint8_t *needs_aa, uint32_t width, uint32_t height, float threshold, void *stream);
+/* Adaptive anti-aliasing (c2rt_render_frame[s]_adaptive*): the flag images needs_aa[i][y][x] of n_frames whole one-tap
+ * frames side by side, then the flagged pixels of the whole frame `p` describes (no strips) from their one-tap to their
+ * five-tap value, in place; launch_aa_refine_batch: the same for the n_frames frames whose blocks are at table_dev (p0:
+ * the host copy of one of them), block i naming frame i as its RenderParams::out, flags side by side at needs_aa */
+int launch_aa_detect(const float *frames, uint8_t *needs_aa, uint32_t width, uint32_t height, uint32_t n_frames, float threshold, void *stream);
 int launch_aa_refine(const RenderParams &p, int csg_levels, float *frame, const uint8_t *needs_aa, void *stream);
+int launch_aa_refine_batch(const RenderParams &p0, int csg_levels, const RenderParams *table_dev, uint32_t n_frames, const uint8_t *needs_aa,
+                           void *stream);
 
 } // namespace c2rt
 #endif

@@ -2,9 +2,12 @@
 """lecture5's three balls moving along a path while the camera stands still, rendered twice and saved as BMPs: once
 frame by frame (Context.updateScene moves the balls in the uploaded scene, no re-upload, then one frame) and once with
 ONE call for the whole animation (Context.renderFramesPosed: a pose per frame, one mask pre-pass launch and one frame
-launch).  Both routes give the same frames, bit for bit.
+launch).  Both routes give the same frames, bit for bit.  With --adaptive both routes are the adaptive ones
+(Context.renderFrameAdaptive frame by frame, Context.renderFramesPosedAdaptive for the animation: one detection and one
+refinement launch for all frames), and the flags are compared as well.
 
   python examples/render_pieces.py /tmp/pieces --frames 16 --size 640 360
+  python examples/render_pieces.py /tmp/pieces --frames 16 --size 640 360 --adaptive
 """
 import argparse
 import ctypes as C
@@ -38,12 +41,17 @@ def main():
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--size", type=int, nargs=2, metavar=("W", "H"))
     ap.add_argument("--no-aa", action="store_true")
+    ap.add_argument("--adaptive", action="store_true", help="five taps only where the edge test flags (implies anti-aliasing)")
     args = ap.parse_args()
     scene = c2.parseSceneFromFile(SCENE)
     if args.size:
         scene.setFrameSize(*args.size)
+    if args.no_aa and args.adaptive:
+        ap.error("--adaptive refines to five taps: not with --no-aa")
     if args.no_aa:
         scene.setAA(False)
+    if args.adaptive:
+        scene.setAA(True)
     cam, opts = scene.beginFrame(), scene.renderOpts()
     balls = [scene.nodeIndex(name) for name in BALLS]
     start = [scene.nodeTransform(name)[27:30] for name in BALLS]
@@ -62,18 +70,24 @@ def main():
     singles = []
     for nodes, lights in poses:
         ctx.updateScene(nodes, lights)          # 464 bytes per moved node, stream-ordered: no sync, no re-upload
-        singles.append(ctx.renderFrame(cam, opts))
+        singles.append(ctx.renderFrameAdaptive(cam, opts) if args.adaptive else ctx.renderFrame(cam, opts))
     dt_singles = time.perf_counter() - t
     ctx.updateScene({n: translated(*p) for n, p in zip(balls, start)})   # back where they were
     t = time.perf_counter()
-    batch = ctx.renderFramesPosed([cam] * len(poses), poses, opts)       # the scene itself stays as it is
+    if args.adaptive:
+        batch, flags = ctx.renderFramesPosedAdaptive([cam] * len(poses), poses, opts)
+        assert all(m.tobytes() == f.tobytes() for (_, m), f in zip(singles, flags))
+        singles = [frame for frame, _ in singles]
+    else:
+        batch = ctx.renderFramesPosed([cam] * len(poses), poses, opts)   # the scene itself stays as it is
     dt_batch = time.perf_counter() - t
     for i, (a, b) in enumerate(zip(singles, batch)):
         assert a.tobytes() == b.tobytes(), i
         with open("%s_%03d.bmp" % (args.out_prefix, i), "wb") as f:
             f.write(c2.saveBmp(b))
-    print("lecture5: %d frames of %dx%d; update + frame: %.2f ms, one posed batch: %.2f ms (both incl. the copies back)"
-          % (len(batch), batch.shape[2], batch.shape[1], dt_singles * 1e3, dt_batch * 1e3))
+    print("lecture5: %d frames of %dx%d%s; update + frame: %.2f ms, one posed batch: %.2f ms (both incl. the copies back)"
+          % (len(batch), batch.shape[2], batch.shape[1], ", adaptive (%.2f %% of the pixels took five rays)" % (100.0 * float(flags.mean())) if args.adaptive else "",
+             dt_singles * 1e3, dt_batch * 1e3))
 
 
 if __name__ == "__main__":

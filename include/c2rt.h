@@ -610,6 +610,52 @@ int c2rt_render_frame_adaptive_device(c2rt_ctx *ctx, const c2rt_camera_frame *ca
 int c2rt_render_frame_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
                                float threshold, float *out_rgb, uint8_t *needs_aa, const volatile uint8_t *stop_flag);
 
+/* Adaptive anti-aliasing for a batch: c2rt_render_frames_device and c2rt_render_frame_adaptive_device in one call.  Frame i
+ * occupies out_rgb_dev + i * W * H * 3 floats and its flags needs_aa_dev + i * W * H bytes; both hold exactly the bits
+ * c2rt_render_frame_adaptive_device(ctx, &cams[i], opts, threshold, ...) writes: every mask byte 0 or 1, the neighbours
+ * of the edge test clamped at the frame's own edges, nothing written beyond frame n_frames - 1.
+ *
+ * Enqueued on `hip_stream`, in order: the one-tap batch exactly as c2rt_render_frames_device enqueues it with taps =
+ * C2RT_TAPS_1 (table copy, mask pre-pass, frame launch or launches), ONE detection launch for all frames, ONE
+ * refinement launch for all frames — the flagged tiles of every frame in one grid, reading their parameter blocks from
+ * the batch's table, which carries one more block per frame in the same copy.  No host sync, no event left in the
+ * queue, no reference kept to the stream.  Blocking, streams and scratch are c2rt_render_frames_device's: the table
+ * goes to the device with a stream-ordered copy from pageable memory, so the call may wait, on the host, until work
+ * enqueued EARLIER on `hip_stream` has drained (never for later work, never for other streams); it also blocks when the
+ * stream's scratch has to grow (first call, more frames, a larger frame) or a 17th stream recycles a slot.  Batches
+ * and single frames on one stream stay ordered and may follow each other without a sync.
+ *
+ * Statuses, all decided before anything is enqueued or written, in this order: those of c2rt_render_frames_device
+ * (n_frames == 0 is C2RT_OK and writes nothing; n_frames > C2RT_MAX_BATCH_FRAMES: C2RT_ERR_LIMIT; depth of field,
+ * stereo, count_rays, prepass_bucket and a multi-device context: C2RT_ERR_UNSUPPORTED); C2RT_ERR_INVALID_ARG for taps
+ * != C2RT_TAPS_REF5, a threshold that is negative or NaN, a null output (needs_aa_dev included);
+ * C2RT_ERR_UNSUPPORTED naming "strip_world" for opts->strip_world > 1. */
+int c2rt_render_frames_adaptive_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames,
+                                       const c2rt_render_opts *opts, float threshold, float *out_rgb_dev,
+                                       uint8_t *needs_aa_dev, void *hip_stream);
+/* The same into HOST memory: frames and flags are staged in the context's staging buffer on the context's own stream
+ * and copied back once each (`needs_aa` is nullable here); blocks until they are there.  `stop_flag` is polled once,
+ * before the launches; C2RT_ERR_CANCELLED leaves the outputs untouched. */
+int c2rt_render_frames_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames,
+                                const c2rt_render_opts *opts, float threshold, float *out_rgb, uint8_t *needs_aa,
+                                const volatile uint8_t *stop_flag);
+
+/* An anti-aliased animation in one call: c2rt_render_frames_adaptive_device with a pose per frame, as
+ * c2rt_render_frames_posed_device is to c2rt_render_frames_device.  Frame i and its flags hold exactly the bits
+ * c2rt_update_scene(&poses[i]) followed by c2rt_render_frame_adaptive_device(&cams[i]) writes, each pose relative to the
+ * context's scene as it is; the context's scene is unchanged by the call.  Frame i's refinement traces frame i's node
+ * and light tables, the copies that travel behind the batch's table.  Enqueue order, blocking, streams and scratch: as
+ * c2rt_render_frames_adaptive_device, the one-tap batch being c2rt_render_frames_posed_device's (plane-instance groups
+ * included).  Statuses: those of c2rt_render_frames_adaptive_device in its order, then null `poses`:
+ * C2RT_ERR_INVALID_ARG, then those of c2rt_update_scene for every poses[i], with "frame i: " in front of the message. */
+int c2rt_render_frames_posed_adaptive_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses,
+                                             uint32_t n_frames, const c2rt_render_opts *opts, float threshold,
+                                             float *out_rgb_dev, uint8_t *needs_aa_dev, void *hip_stream);
+/* The same into HOST memory, as c2rt_render_frames_adaptive is to c2rt_render_frames_adaptive_device. */
+int c2rt_render_frames_posed_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses,
+                                      uint32_t n_frames, const c2rt_render_opts *opts, float threshold, float *out_rgb,
+                                      uint8_t *needs_aa, const volatile uint8_t *stop_flag);
+
 /* Rank-0 side of the multi-GPU gather: `gathered_dev` holds `world`
  * consecutive compact strip buffers (rank-major, as ncclGather leaves them);
  * writes the de-interleaved full frame to `frame_dev`.  Both device

@@ -139,6 +139,19 @@ extern (C) nothrow @nogc
                                           float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
     int c2rt_render_frame_adaptive(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
                                    float* out_rgb, ubyte* needs_aa, const(ubyte)* stop_flag);
+    /// the same for a batch, with or without a pose per frame: frame i at out + i * W * H * 3 floats, its flags at
+    /// needs_aa + i * W * H bytes, the bits of the single-frame adaptive calls; one detection and one refinement
+    /// launch for all frames; what a batch and what an adaptive frame refuse, these refuse
+    int c2rt_render_frames_adaptive_device(c2rt_ctx*, const c2rt_camera_frame* cams, uint nFrames, const c2rt_render_opts*,
+                                           float threshold, float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
+    int c2rt_render_frames_adaptive(c2rt_ctx*, const c2rt_camera_frame* cams, uint nFrames, const c2rt_render_opts*,
+                                    float threshold, float* out_rgb, ubyte* needs_aa, const shared(ubyte)* stop_flag);
+    int c2rt_render_frames_posed_adaptive_device(c2rt_ctx*, const c2rt_camera_frame* cams, const c2rt_scene_pose* poses,
+                                                 uint nFrames, const c2rt_render_opts*, float threshold, float* out_rgb_dev,
+                                                 ubyte* needs_aa_dev, void* hip_stream);
+    int c2rt_render_frames_posed_adaptive(c2rt_ctx*, const c2rt_camera_frame* cams, const c2rt_scene_pose* poses, uint nFrames,
+                                          const c2rt_render_opts*, float threshold, float* out_rgb, ubyte* needs_aa,
+                                          const shared(ubyte)* stop_flag);
 }
 
 /// Owns the flat tables for one uploaded scene (GC memory; c2rt_upload_scene copies them).
