@@ -61,13 +61,13 @@ HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/
 # over the SAME kernel objects; tests and scripts that need a hook load it with C2RT_LIB_VARIANT=diag
 DIAGNAME   := chess2rt_amd/libc2rt_diag.so
 
-all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so
+all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so
 
 $(BUILD):
 	mkdir -p $(BUILD)
 
 # (the Makefile is a prerequisite: the arithmetic and code-generation flags are part of what a kernel object is)
-TRACE_DEPS := $(CSRC)/c2rt_trace_common.inc $(CSRC)/c2rt_trace.inc $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/x87.h $(CSRC)/fp64_lean.h include/c2rt.h Makefile
+TRACE_DEPS := $(CSRC)/c2rt_trace_common.inc $(CSRC)/c2rt_trace.inc $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/x87.h $(CSRC)/fp64_lean.h $(CSRC)/f32_certain.h include/c2rt.h Makefile
 $(BUILD)/c2rt_kernels_u%.o: $(CSRC)/c2rt_kernels.hip $(TRACE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_u$*) $(EXTRA_KERNEL_FLAGS) -DC2RT_UNIT=$* -c $< -o $@
 
@@ -96,6 +96,11 @@ $(DIAGNAME): $(KOBJS) $(BUILD)/c2rt_api_diag.o $(filter-out $(BUILD)/c2rt_api.o,
 # device check of fp64_lean.h against the compiler's own divide / sqrt expansions (tests/test_gpu_parity.py runs it)
 tests/fp64_lean_check: tests/fp64_lean_check.hip $(CSRC)/fp64_lean.h
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 $(FPFLAGS) -fhip-fp32-correctly-rounded-divide-sqrt $< -o $@
+
+# device check of f32_certain.h and its two wrappers against the device's own atan2 / asin / pow and the x87 emulation
+# (tests/test_gpu_f32_certain.py runs it)
+tests/certain_f32_check: tests/certain_f32_check.hip $(TRACE_DEPS)
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 $(FPFLAGS) -fhip-fp32-correctly-rounded-divide-sqrt $< -o $@
 
 # host build of the CsgDiff void-tile test of the mask pre-pass (tests/test_csg_void_tiles.py, scripts/csg_void_tiles.py)
 tests/libcsg_void_check.so: tests/csg_void_check.cpp $(CSRC)/csg_void.h
@@ -141,6 +146,6 @@ resource-usage: | $(BUILD)
 	    -c $(CSRC)/$(q).hip -o $(BUILD)/ru_$(q).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
 
 clean:
-	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so
+	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so
 
 .PHONY: all clean resource-usage

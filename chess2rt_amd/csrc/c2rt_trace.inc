@@ -222,7 +222,7 @@ enum { kCodeAxis = 3, kCodeSide = 4, kCodeFlip = 8 };
 /* the closest hit as the shaders read it (world space) */
 struct Surf {
     D3 p, n;
-    double u, v;
+    double u, v; /* a sphere's under kUVBitmap: good for bitmap_color's float conversion only, not the reference's doubles (UVWant) */
 };
 
 /* what a caller needs back from an intersect call */
@@ -985,10 +985,24 @@ DEV bool node_intersect(const Ctx &cx, NodeP N, const RayW &ray, Hit &best, bool
 /* finish_uv: Sphere.intersect's u,v — rt/geometry.d:118-120.  `PI` is an 80-bit real there: the two expressions
  * are evaluated with the x87's 64-bit significand and rounded to double on assignment; x87.h
  * reproduces that with integer arithmetic (a NaN / infinite operand takes the plain double
- * expression, whose result is the same NaN). */
-DEV void sphere_uv(double dx, double dz, double w, double &u, double &v)
+ * expression, whose result is the same NaN).
+ *
+ * UVWant (wave-uniform): which u,v the caller of hit_surface reads.  kUVExact: those doubles — the probe, the hit
+ * planes and ray queries (which report them), Checker and Procedure2 textures.  kUVBitmap: the only reader is
+ * BitmapTexture.getTexColor with scaling `s`, which converts (u*s - floor(u*s)) to float at once; u,v are then
+ * doubles that give THAT float bit for bit (c2_sphere_uv_bitmap, f32_certain.h) and may differ from the exact ones
+ * by 2^-51.  Planes and cubes return the same u,v in both modes. */
+enum { kUVNone = 0, kUVExact = 1, kUVBitmap = 2 };
+struct UVWant {
+    int kind;
+    double s;
+};
+DEV UVWant uv_want(bool exact) { return UVWant{exact ? kUVExact : kUVNone, 0.0}; }
+
+DEV void sphere_uv(double dx, double dz, double w, UVWant want, double &u, double &v)
 {
-    const UV r = c2_sphere_uv(dx, dz, w); /* c2rt_kernels.hip: a real call */
+    /* c2rt_trace_common.inc: real calls */
+    const UV r = want.kind == kUVBitmap ? c2_sphere_uv_bitmap(dx, dz, w, want.s) : c2_sphere_uv(dx, dz, w);
     u = r.u;
     v = r.v;
 }
@@ -1000,7 +1014,7 @@ DEV void sphere_uv(double dx, double dz, double w, double &u, double &v)
  * or the sphere of a CsgDiff), so its record is read per lane. */
 /* (the leaf's part: G is the node's own record — scalar loads — when the node's geometry is a primitive, and a
  * per-lane record when it is a CsgOp, whose leaf differs from lane to lane) */
-DEV void leaf_surface(const Ctx &cx, GeomP G, int type, const Hit &h, bool want_uv, Surf &s, D3 &n, bool &axis_n)
+DEV void leaf_surface(const Ctx &cx, GeomP G, int type, const Hit &h, UVWant want_uv, Surf &s, D3 &n, bool &axis_n)
 {
     axis_n = true; /* n is an exact signed unit axis: normalize(n) == n */
     s.u = s.v = 0;
@@ -1022,16 +1036,16 @@ DEV void leaf_surface(const Ctx &cx, GeomP G, int type, const Hit &h, bool want_
         n = normalized(cx.bad, pc);
         axis_n = false;
         /* u,v cost an atan2 and an asin and are read by textured shaders (and the probe) only */
-        if (want_uv) {
+        if (want_uv.kind != kUVNone) {
             C2RT_REGION_BEGIN(cx, kRegSphereUV)
-            sphere_uv(pc.x, pc.z, pc.y / G->p[3], s.u, s.v);
+            sphere_uv(pc.x, pc.z, pc.y / G->p[3], want_uv, s.u, s.v);
             C2RT_REGION_END(cx, kRegSphereUV)
         }
     }
 }
 
 template <int PO>
-DEV void hit_surface(const Ctx &cx, NodeP N, const Hit &h, bool want_uv, Surf &s)
+DEV void hit_surface(const Ctx &cx, NodeP N, const Hit &h, UVWant want_uv, Surf &s)
 {
     D3 n;
     bool axis_n;
@@ -1467,7 +1481,7 @@ DEV F3 shade(const RenderParams &P, const Ctx &cx, const Mat &mat, D3 rd, const 
                     C2RT_REGION_BEGIN(cx, kRegLight)
                     if (cosTheta > 0) avgColor = avgColor + baseLight * (float)cosTheta;
                     if (phong & (cosGamma > 0))
-                        avgSpecular = avgSpecular + baseLight * (float)c2_pow(cosGamma, mat.exponent) * mat.strength;
+                        avgSpecular = avgSpecular + baseLight * c2_pow_f32(cosGamma, mat.exponent) * mat.strength;
                     C2RT_REGION_END(cx, kRegLight)
                 }
             }
@@ -1505,7 +1519,7 @@ DEV F3 shade(const RenderParams &P, const Ctx &cx, const Mat &mat, D3 rd, const 
                     light_terms(cx, L, ld3(L->pos), p, N, rd, phong, cosTheta, baseLight, cosGamma);
                     if (cosTheta > 0) avgColor = avgColor + baseLight * (float)cosTheta;
                     if (phong & (cosGamma > 0))
-                        avgSpecular = avgSpecular + baseLight * (float)c2_pow(cosGamma, exponent) * strength;
+                        avgSpecular = avgSpecular + baseLight * c2_pow_f32(cosGamma, exponent) * strength;
                 }
                 lightContrib = lightContrib + avgColor;
                 specular = specular + avgSpecular;
@@ -1716,7 +1730,10 @@ DEV F3 raytrace(const RenderParams &P, const Ctx &cx, D3 o, D3 raw, Counters &cn
             if (closest == cn) {
                 NodeP N = cx.nodes + cn;
                 load_mat(N, mat);
-                hit_surface<PO>(cx, N, best, probe || mat.tex_type >= 0, surf);
+                /* (a bitmap texture reads u,v as floats only: the certain-float route, unless the probe reports them) */
+                const UVWant want = (!probe && mat.tex_type == C2RT_TEX_BITMAP) ? UVWant{kUVBitmap, (double)__uint_as_float(mat.td[2])}
+                                                                                : uv_want(probe || mat.tex_type >= 0);
+                hit_surface<PO>(cx, N, best, want, surf);
                 todo = false;
             }
         }
@@ -1777,7 +1794,7 @@ DEV int trace_closest(const Ctx &cx, D3 o, D3 d, bool record, Hit &best, Surf &s
         if (closest == cn) {
             NodeP N = cx.nodes + cn;
             load_mat(N, mat);
-            hit_surface<0>(cx, N, best, record || mat.tex_type >= 0, surf);
+            hit_surface<0>(cx, N, best, uv_want(record || mat.tex_type >= 0), surf);
             todo = false;
         }
     }

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "c2rt_device.h"
+#include "f32_certain.h"
 #include "fp64_lean.h"
 #include "x87.h"
 
@@ -23,7 +24,6 @@ namespace {
 /* fp64 libm is only reached by a few lanes (sphere u,v, the Phong lobe,
  * Procedure2) but, inlined, its ~70 live registers set the whole kernel's
  * budget; as real calls the trace stays under 168 VGPRs without spills. */
-__device__ __noinline__ double c2_pow(double a, double b) { return pow(a, b); }
 __device__ __noinline__ double c2_sin(double a) { return sin(a); }
 /* Sphere.intersect's u,v (rt/geometry.d:118-120) out of line as well: the x87 emulation (x87.h) is ~500 integer
  * instructions with ~40 live registers, reached by textured sphere hits only; inlined (twice: lean:: and exact::)
@@ -37,6 +37,39 @@ __device__ __noinline__ UV c2_sphere_uv(double dx, double dz, double w)
     UV r;
     r.u = fabs(angle) <= 4.0 ? x87_sphere_u(angle) : (PI + angle) / (2 * PI);
     r.v = fabs(as) <= 2.0 ? x87_sphere_v(as) : 1.0 - (PI / 2 + as) / PI;
+    return r;
+}
+/* The two of them that are converted to float at once by their readers in a frame (f32_certain.h): the cheap expression wherever the float that
+ * comes out of it is certain to be the one above gives, the routine above for the other lanes (a divergent branch
+ * the wave skips when no lane needs it: one lane in a few million does).
+ * c2_pow_f32: (float)pow(a, b), the Phong lobe of shade() — its only reader, so there is no double-valued twin. */
+__device__ __noinline__ float c2_pow_f32(double a, double b)
+{
+    float f;
+    if (pow_f32_certain(a, b, &f)) return f;
+    return (float)pow(a, b);
+}
+/* c2_sphere_uv_bitmap: u, v for BitmapTexture.getTexColor with scaling s, which reads (float)(u*s - floor(u*s)) and
+ * nothing else: doubles from which bitmap_color computes the floats it computes from c2_sphere_uv's — NOT those
+ * doubles themselves (they differ by up to 2^-51), so nothing that reports u, v may call it. */
+__device__ __noinline__ UV c2_sphere_uv_bitmap(double dx, double dz, double w, double s_uniform)
+{
+    /* The scaling must be WAVE-UNIFORM (it is: one texture per call, hit_surface runs per distinct closest node).  Held
+     * in scalar registers it is not live in a vector pair across atan2 and asin; with that and the sequential tests
+     * below the function needs the 22 VGPRs of c2_sphere_uv, not 25 — a count every calling kernel's budget includes. */
+    const double s = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(s_uniform)), __builtin_amdgcn_readfirstlane(__double2loint(s_uniform)));
+    const double angle = atan2(dz, dx);
+    const double as = asin(w);
+    UV r;
+    /* (one coordinate after the other, each behind a branch: tested side by side they add three VGPRs to this function) */
+    bool certain = sphere_uv_fast(angle, as, &r.u, &r.v) != 0;
+    if (certain) certain = uv_float_certain(r.u, F32C_UV_DELTA, s) != 0;
+    if (certain) certain = uv_float_certain(r.v, F32C_UV_DELTA, s) != 0;
+    if (!certain) {
+        constexpr double PI = 3.14159265358979323846;
+        r.u = fabs(angle) <= 4.0 ? x87_sphere_u(angle) : (PI + angle) / (2 * PI);
+        r.v = fabs(as) <= 2.0 ? x87_sphere_v(as) : 1.0 - (PI / 2 + as) / PI;
+    }
     return r;
 }
 /* Register budget per kernel instance, as waves per SIMD (512 VGPRs per lane and SIMD: 128 at 4 waves,
