@@ -67,7 +67,7 @@ $(BUILD):
 	mkdir -p $(BUILD)
 
 # (the Makefile is a prerequisite: the arithmetic and code-generation flags are part of what a kernel object is)
-TRACE_DEPS := $(CSRC)/c2rt_trace_common.inc $(CSRC)/c2rt_trace.inc $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/x87.h $(CSRC)/fp64_lean.h $(CSRC)/f32_certain.h include/c2rt.h Makefile
+TRACE_DEPS := $(CSRC)/c2rt_trace_common.inc $(CSRC)/c2rt_trace_shared.inc $(CSRC)/c2rt_tile_mask.inc $(CSRC)/c2rt_trace.inc $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/x87.h $(CSRC)/fp64_lean.h $(CSRC)/f32_certain.h include/c2rt.h Makefile
 $(BUILD)/c2rt_kernels_u%.o: $(CSRC)/c2rt_kernels.hip $(TRACE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_u$*) $(EXTRA_KERNEL_FLAGS) -DC2RT_UNIT=$* -c $< -o $@
 

@@ -83,7 +83,7 @@ constexpr size_t kAaColourBytes = (size_t)kWave * 4 * 3 * sizeof(float), kAaList
 /* The packed wave over tile blockIdx.x of the frame `P` describes: one body for both entry points below, which only
  * produce (P, K, frame, needs_aa). */
 template <int LEVELS, bool MLC>
-DEV void aa_refine_body(const RenderParams &P, exact::KArgs K, float *__restrict__ frame, const uint8_t *__restrict__ needs_aa,
+DEV void aa_refine_body(const RenderParams &P, KArgs K, float *__restrict__ frame, const uint8_t *__restrict__ needs_aa,
                         const uint32_t tiles_x)
 {
     using namespace exact;
@@ -144,7 +144,7 @@ template <int LEVELS, bool MLC>
 __global__ void __launch_bounds__(kWave) C2RT_WAVES_QUERY(LEVELS, MLC)
 aa_refine_kernel(const RenderParams P, float *__restrict__ frame, const uint8_t *__restrict__ needs_aa, const uint32_t tiles_x)
 {
-    aa_refine_body<LEVELS, MLC>(P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), frame, needs_aa, tiles_x);
+    aa_refine_body<LEVELS, MLC>(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), frame, needs_aa, tiles_x);
 }
 
 /* batch_block of c2rt_kernels.hip, restated (that file's objects stay as they are): block blockIdx.y of the table
@@ -164,7 +164,7 @@ aa_refine_batch_kernel(const RenderParams *table, const uint8_t *__restrict__ ma
 {
     const KArgs K = batch_block(table);
     const RenderParams &P = *(const RenderParams *)K;
-    aa_refine_body<LEVELS, MLC>(P, (exact::KArgs)K, P.out, masks + (size_t)blockIdx.y * frame_px, tiles_x);
+    aa_refine_body<LEVELS, MLC>(P, K, P.out, masks + (size_t)blockIdx.y * frame_px, tiles_x);
 }
 
 /* table_dev null: the single-frame kernel with `p` as its argument, into `frame`; otherwise the n_frames blocks at

@@ -196,7 +196,7 @@ struct RenderParams {
      * decides plane misses from the un-normalised ray direction (plane_points_away) */
     uint32_t planes_only;
     /* every node's matrix is the identity (translations allowed): the launcher picks the kSpecIdentity instances
-     * (c2rt_trace.inc) for uncounted frames with at most one light and no stereo */
+     * (c2rt_trace_shared.inc) for uncounted frames with at most one light and no stereo */
     uint32_t all_identity;
     /* "Ground plane" shadow culling (scene_plan.cpp: plan_ground_rects).  ground_node >= 0: node
      * ground_node is a Plane under an identity matrix with zero offset, at height ground_y.  In a
@@ -219,8 +219,8 @@ struct RenderParams {
     uint32_t *retry_list;
     /* per tile, 4 words: {primary mask, shadow mask of light 0, ground bits, 0}; frames with several culled lights
      * carry a second table of the same layout behind it, mask_entries entries further on: {shadow masks of lights
-     * 1..3, 0} (c2rt_trace.inc: light_shadow_mask) — written by the pre-pass kernel
-     * (launch_tile_masks, c2rt_trace.inc: tile_mask_entry) once per frame with n_cull != 0, read by the frame
+     * 1..3, 0} (c2rt_tile_mask.inc: light_shadow_mask) — written by the pre-pass kernel
+     * (launch_tile_masks, c2rt_tile_mask.inc: tile_mask_entry) once per frame with n_cull != 0, read by the frame
      * kernel with one scalar load per tile.  The table covers the local rows [mask_row0, mask_row0 + mask_rows)
      * (mask_row0 a multiple of the tile height): the launches of a chunked host-output frame share one table */
     const uint32_t *tile_masks;

@@ -46,7 +46,7 @@ hit_planes_kernel(const RenderParams P, const c2rt_hit_planes out, const uint32_
     const bool live = x < P.width && r < rows;
     const bool record = out.dist || out.uv || out.p || out.normal; /* wave-uniform: best.dist and the surface are read */
     Ctx cx;
-    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
+    query_ctx(cx, P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
     D3 d = mk(0, 0, 0);
     Hit best;
     Surf surf;

@@ -23,6 +23,7 @@
  * This file holds the entry points and launchers of the FRAME kernels, the pixel probe, the tile-mask pre-pass,
  * de-interleave and encode; the query kernels (caller's rays, hit planes, adaptive anti-aliasing) have files of their
  * own: c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_adaptive.hip.  The trace itself is
+ * c2rt_trace_shared.inc and c2rt_tile_mask.inc (what does not depend on the arithmetic mode, defined once) and
  * c2rt_trace.inc, included twice by c2rt_trace_common.inc: lean:: (divide / sqrt / normalise through
  * the shortened correctly rounded sequences of fp64_lean.h, optimistically) and
  * exact:: (the compiler's IEEE expansions); render_one() runs a tile through
@@ -55,20 +56,20 @@ template <int LEVELS, int DOF, bool MLC, int PO, bool CNT>
 DEV void render_one(const RenderParams &P, KArgs K, const uint32_t b)
 {
     if constexpr (CNT || LEVELS > kLeanMaxLevels) {
-        exact::render_tile<LEVELS, DOF, MLC, PO, CNT>(P, (exact::KArgs)K, b);
+        exact::render_tile<LEVELS, DOF, MLC, PO, CNT>(P, K, b);
     } else {
         if (!P.force_exact) { /* wave-uniform */
-            const bool redo = lean::render_tile<LEVELS, DOF, MLC, PO, false>(P, (lean::KArgs)K, b);
+            const bool redo = lean::render_tile<LEVELS, DOF, MLC, PO, false>(P, K, b);
             if (!__ballot(redo)) return;
             if (threadIdx.x % kWave == 0) atomicAdd(P.redo_counter, 1ull); /* c2rt_get_exact_redos */
         }
-        if constexpr (LEVELS <= 1 && !DOF && PO != lean::kSpecPlanes) {
+        if constexpr (LEVELS <= 1 && !DOF && PO != kSpecPlanes) {
             KArgs K2 = K;
             uint32_t b2 = b;
             asm volatile("" : "+s"(K2), "+s"(b2));
-            exact::render_tile<LEVELS, DOF, MLC, PO, false>(*(const RenderParams *)K2, (exact::KArgs)K2, b2);
+            exact::render_tile<LEVELS, DOF, MLC, PO, false>(*(const RenderParams *)K2, K2, b2);
         } else {
-            exact::render_tile<LEVELS, DOF, MLC, PO, false>(P, (exact::KArgs)K, b);
+            exact::render_tile<LEVELS, DOF, MLC, PO, false>(P, K, b);
         }
     }
 }
@@ -103,12 +104,12 @@ __global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(LEVELS, DOF, MLC)
 }
 
 /* The same for scenes in which every node's matrix is the identity (RenderParams::all_identity: every scene the
- * reference ships) with at most one light and no depth of field: lean::kSpecIdentity (c2rt_trace.inc) — production
+ * reference ships) with at most one light and no depth of field: kSpecIdentity (c2rt_trace_shared.inc) — production
  * instances only; counted frames run the general instance, and the tests compare the two. */
 template <int LEVELS>
 __global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(LEVELS, 0, false) render_kernel_idn(const RenderParams P)
 {
-    render_body<LEVELS, 0, false, lean::kSpecIdentity, false>(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr());
+    render_body<LEVELS, 0, false, kSpecIdentity, false>(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr());
 }
 
 /* The depth-of-field / stereo instance carries the lens sampling state on top of
@@ -124,7 +125,7 @@ __global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(LEVELS, MODE, MLC
 template <int DOF, bool CNT>
 __global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(0, DOF, false) render_kernel_planes(const RenderParams P)
 {
-    render_body<0, DOF, false, lean::kSpecPlanes, CNT>(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr()); /* at most one light (launch_render_level); planes have no boxes, hence no culling masks */
+    render_body<0, DOF, false, kSpecPlanes, CNT>(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr()); /* at most one light (launch_render_level); planes have no boxes, hence no culling masks */
 }
 /* (no identity-matrix variant of these: single-plane scenes take the straight-line ground trace, which has no matrix
  * code to lose — measured: zaphod x4 0.601 vs 0.606 ms, DOF 4.583 vs 4.582) */
@@ -155,14 +156,14 @@ template <int LEVELS>
 __global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(LEVELS, 0, false) render_kernel_idn_batch(const RenderParams *table)
 {
     const KArgs K = batch_block(table);
-    render_body<LEVELS, 0, false, lean::kSpecIdentity, false>(*(const RenderParams *)K, K);
+    render_body<LEVELS, 0, false, kSpecIdentity, false>(*(const RenderParams *)K, K);
 }
 
 #if C2RT_UNIT == 0 /* (not a template: it would be compiled into every unit) */
 __global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(0, 0, false) render_kernel_planes_batch(const RenderParams *table)
 {
     const KArgs K = batch_block(table);
-    render_body<0, 0, false, lean::kSpecPlanes, false>(*(const RenderParams *)K, K);
+    render_body<0, 0, false, kSpecPlanes, false>(*(const RenderParams *)K, K);
 }
 #endif
 
@@ -220,7 +221,7 @@ __global__ void encode_rgb32_kernel(const float *__restrict__ frame, uint32_t *_
     }
 }
 
-/* The culling masks of every tile of a frame's local rows, one lane per tile (c2rt_trace.inc: tile_mask_entry,
+/* The culling masks of every tile of a frame's local rows, one lane per tile (c2rt_tile_mask.inc: tile_mask_entry,
  * tile_mask_slot).  Runs once per frame whose camera leaves culling rectangles, in front of the frame kernel's
  * launch(es), on the same stream.  One body for both entry points below, which only produce (P, K, V, S, table,
  * tile_rows). */
@@ -231,12 +232,12 @@ DEV void tile_masks_body(const RenderParams &P, KArgs K, const VoidCull &V, cons
     const uint32_t trow = i / cols, tcol = i % cols;
     if (trow >= tile_rows) return;
     uint32_t m[8];
-    exact::tile_mask_entry(P, (exact::KArgs)K, V, S, D, trow, tcol, m);
+    tile_mask_entry(P, K, V, S, D, trow, tcol, m);
     typedef uint32_t __attribute__((ext_vector_type(4))) u4_t;
     u4_t v, w;
     v.x = m[0]; v.y = m[1]; v.z = m[2]; v.w = m[3];
     w.x = m[4]; w.y = m[5]; w.z = m[6]; w.w = m[7];
-    const size_t slot = exact::tile_mask_slot(P, trow, tcol);
+    const size_t slot = tile_mask_slot(P, trow, tcol);
     reinterpret_cast<u4_t *>(table)[slot] = v;
     if (P.n_cull_lights > 1u) reinterpret_cast<u4_t *>(table)[(size_t)P.mask_entries + slot] = w; /* lights 1..3 */
 }

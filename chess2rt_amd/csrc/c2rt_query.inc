@@ -1,8 +1,8 @@
 /*
  * c2rt_query.inc — what the query kernels share (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_adaptive.hip): a lane traces
  * ONE ray that is not a frame tile's — the caller's, or the camera's through a pixel — with exact:: arithmetic (the
- * probe's choice; bit-equal to what the frames compute), every culling mask all ones (exact::query_ctx,
- * c2rt_trace.inc), no ground-tile shortcut, and a full-capacity CSG hit stack: kCsgFullCap(LEVELS) entries in one
+ * probe's choice; bit-equal to what the frames compute), every culling mask all ones (query_ctx,
+ * c2rt_trace_shared.inc), no ground-tile shortcut, and a full-capacity CSG hit stack: kCsgFullCap(LEVELS) entries in one
  * launch, which cannot overflow, so there is no retry list and no per-stream scratch.  That is 10 / 20 / 30 / 40 KiB
  * of LDS per wave at depth 1 / 2 / 3 / 4: the LDS, not the registers, bounds the occupancy of the nested instances
  * (8 / 5 / 4 workgroups per CU), hence two waves per SIMD as their register budget (DESIGN.md, "Ray queries").
@@ -23,17 +23,17 @@ constexpr int occ_query() { return LEVELS >= 2 ? 2 : occ_of<LEVELS, 0, MLC>(); }
 /* The ray through the screen point (x, y) — a pixel's integer corner, plus its tap offset where there is one — of the
  * camera of `P`: Camera.getScreenRay, then raytrace()'s normalisation (rt/camera.d:144-147) — the operations the
  * frame kernels and the probe apply to (x, y). */
-DEV void pixel_ray(const exact::Ctx &cx, const RenderParams &P, double x, double y, exact::D3 &o, exact::D3 &d)
+DEV void pixel_ray(const Ctx &cx, const RenderParams &P, double x, double y, D3 &o, D3 &d)
 {
-    exact::Rng rng = {0u, 0, 0};
-    exact::D3 raw;
+    Rng rng = {0u, 0, 0};
+    D3 raw;
     exact::screen_ray<false>(cx.bad, P, x, y, 0, rng, o, raw);
     d = exact::normalized(cx.bad, raw);
 }
 
 /* one 12-byte store per lane, as the frame kernels store pixels */
 typedef float __attribute__((ext_vector_type(3), aligned(4))) f3_t;
-DEV void store_colour(float *rgb, exact::F3 c)
+DEV void store_colour(float *rgb, F3 c)
 {
     f3_t v3;
     v3.x = c.r;

@@ -35,12 +35,12 @@ static_assert(__builtin_offsetof(c2rt_ray_hit, leaf_geom) == 4 && __builtin_offs
 /* six doubles of an array-of-structures input record (c2rt_ray, c2rt_segment): three 16-byte loads where the
  * hardware takes them at 8-byte alignment */
 typedef double __attribute__((ext_vector_type(2), aligned(8))) d2_t;
-DEV void load6(const void *rec, exact::D3 &a, exact::D3 &b)
+DEV void load6(const void *rec, D3 &a, D3 &b)
 {
     const d2_t *q = static_cast<const d2_t *>(rec);
     const d2_t q0 = q[0], q1 = q[1], q2 = q[2];
-    a = exact::mk(q0.x, q0.y, q1.x);
-    b = exact::mk(q1.y, q2.x, q2.y);
+    a = mk(q0.x, q0.y, q1.x);
+    b = mk(q1.y, q2.x, q2.y);
 }
 
 /* Ray i = trace(ray, TraceType.Ray), rt/renderer.d:325-376, depth 0.  hits / rgb: nullable, not both (wave-uniform). */
@@ -55,7 +55,7 @@ trace_rays_kernel(const RenderParams P, const c2rt_ray *__restrict__ rays, const
     const uint64_t i = first + (uint64_t)lane;
     const bool live = i < n;
     Ctx cx;
-    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
+    query_ctx(cx, P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
     D3 o = mk(0, 0, 0), d = mk(0, 0, 0);
     Hit best;
     Surf surf;
@@ -113,7 +113,7 @@ test_visibility_kernel(const RenderParams P, const c2rt_segment *__restrict__ se
     const uint64_t i = (uint64_t)blockIdx.x * kWave + (uint64_t)lane;
     if (i >= n) return; /* nothing after the trace needs the whole wave */
     Ctx cx;
-    query_ctx(cx, P, (exact::KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
+    query_ctx(cx, P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
     D3 from, to;
     load6(seg + i, from, to);
     const bool vis = test_visibility<LEVELS, 0>(cx, from, to, 0xFFFFFFFFu, false);

@@ -1,11 +1,18 @@
 /*
  * c2rt_trace_common.inc — what a device translation unit needs before it can write a kernel: the HIP runtime header and
  * the device tables, the out-of-line libm wrappers, the register budget per instance (occ_of), the diagnostics knobs,
- * the trace itself (c2rt_trace.inc) and the host helper that picks an instance by CSG depth.  Included once, at file
+ * the trace itself and the host helper that picks an instance by CSG depth.  Included once, at file
  * scope, by the frame file (c2rt_kernels.hip: lean:: and exact::) and by the query files (c2rt_rays.hip,
  * c2rt_hit_planes.hip, c2rt_adaptive.hip), which define C2RT_TRACE_EXACT_ONLY first: they run exact:: arithmetic only
  * and need no lean:: copy of the trace (the emitted code is the same either way, and so is the compile time, about
  * 25 s per query object: the unused copy is only parsed).
+ *
+ * The trace comes in two halves.  What does not depend on the arithmetic mode is defined once, at c2rt:: scope:
+ * c2rt_trace_shared.inc (types, vectors, records, Ctx, textures, RNG, pixel store) and c2rt_tile_mask.inc (the
+ * pre-pass classifier).  What does is c2rt_trace.inc, included into namespace lean (kLean = true) and again into
+ * namespace exact (kLean = false).  The rule: a definition is in c2rt_trace.inc if and only if it reads kLean or
+ * calls or instantiates something that does (the few exceptions are named in that file's header); only such names
+ * are ever written lean:: or exact::.
  */
 #include <hip/hip_runtime.h>
 
@@ -96,6 +103,10 @@ constexpr int occ_of()
 #define C2RT_TILE_STATS 0 /* diagnostics: per-tile wave cycles + class (RenderParams::tile_stats) */
 #endif
 
+/* the arithmetic-independent half, once; then the half that reads kLean, once per namespace */
+#include "c2rt_trace_shared.inc"
+#include "c2rt_tile_mask.inc"
+
 #ifndef C2RT_TRACE_EXACT_ONLY
 namespace lean {
 constexpr bool kLean = true;
@@ -106,8 +117,6 @@ namespace exact {
 constexpr bool kLean = false;
 #include "c2rt_trace.inc"
 } // namespace exact
-
-typedef const RenderParams __attribute__((address_space(4))) *KArgs;
 
 /* The instance of a scene's CSG depth (KernelVariant::csg_levels, chosen at upload): f(std::integral_constant<int, L>)
  * for L = levels, an error for a depth no instance was built for.  Host side. */

@@ -1,6 +1,6 @@
 /*
  * csg_void.h — per-tile "void" test for a CsgDiff(L, Sphere) node, and silhouette test for a Sphere node (further
- * down): the tile's rays provably get no hit on it.  Shared by the mask pre-pass (c2rt_trace.inc: tile_mask_entry),
+ * down): the tile's rays provably get no hit on it.  Shared by the mask pre-pass (c2rt_tile_mask.inc: tile_mask_entry),
  * the host that fills VoidCull and SphereCull (c2rt_api.cpp: prepare_tile_masks) and the host check libraries of the
  * tests (tests/csg_void_check.cpp, tests/sphere_cull_check.cpp).
  *

@@ -227,7 +227,7 @@ def classify(desc, cam, W, H, cand, r_override=None):
 
 def tile_bounds(trow, tcol, mask_row0, mask_rows, strip_height=1, strip_rank=0, strip_world=1):
     """(tx0, ty0, ty1): the first pixel column and the first and last FRAME row of the tile in row `trow` (row 0 =
-    local row mask_row0) and column `tcol` of a mask table, restated from tile_mask_entry (c2rt_trace.inc): the
+    local row mask_row0) and column `tcol` of a mask table, restated from tile_mask_entry (c2rt_tile_mask.inc): the
     last tile row may be ragged; under strips (local rows dealt round-robin in strips of strip_height) the local rows
     map to frame rows and a tile may span two strips, whose frame rows [ty0, ty1] then also hold other ranks' rows."""
     lr_first = trow * TILE + mask_row0

@@ -5,8 +5,8 @@ whole trace is inlined into the kernel, so the line's enclosing function in c2rt
 
 usage: isa_census.py <unit> <mangled-name-substring> [lean|exact]      unit: 0..5 (c2rt_kernels.hip), or rays / hit_planes /
                                                                     adaptive (the query file c2rt_<unit>.hip)
-The production instances hold the trace twice (c2rt_trace.inc: lean:: first, then — after the atomic that counts a
-redo — exact::); `lean` / `exact` restricts the census to that half.
+The production instances hold the trace twice (c2rt_trace.inc and what it inlines of c2rt_trace_shared.inc: lean::
+first, then — after the atomic that counts a redo — exact::); `lean` / `exact` restricts the census to that half.
 Builds build/isa/u<unit>g.s with the Makefile's flags + -gline-tables-only (code generation is unchanged).
 """
 import collections
@@ -17,7 +17,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "chess2rt_amd/csrc/c2rt_kernels.hip")
-TRACE = os.path.join(ROOT, "chess2rt_amd/csrc/c2rt_trace.inc")
+# the trace: what is defined once (shared, tile masks), then the half included into lean:: and exact::
+TRACE = [os.path.join(ROOT, "chess2rt_amd/csrc", f) for f in ("c2rt_trace_shared.inc", "c2rt_tile_mask.inc", "c2rt_trace.inc")]
 
 
 def make_flags():
@@ -106,7 +107,7 @@ def main():
     newest = max(os.path.getmtime(os.path.join(csrc, f)) for f in os.listdir(csrc) if f.endswith(('.hip', '.inc', '.h')))
     if not os.path.exists(out) or os.path.getmtime(out) < newest:
         subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
-    spans = {os.path.basename(p): function_spans(p) for p in (src, TRACE, os.path.join(csrc, "c2rt_query.inc"), os.path.join(csrc, "c2rt_trace_common.inc"))}
+    spans = {os.path.basename(p): function_spans(p) for p in [src] + TRACE + [os.path.join(csrc, "c2rt_query.inc"), os.path.join(csrc, "c2rt_trace_common.inc")]}
 
     files = {}
     for raw in open(out):
@@ -125,8 +126,10 @@ def main():
         for a, b, fn in spans[name]:
             if a <= line <= b:
                 return fn
-        if name == "c2rt_trace.inc":
-            return "vector helpers (D3 / F3 operators, dot, sqmag)" if line < 140 else "(file scope)"
+        if name == "c2rt_trace_shared.inc":
+            return "vector helpers (D3 / F3 operators, dot, sqmag)" if line < 125 else "(file scope)"
+        if name in ("c2rt_trace.inc", "c2rt_tile_mask.inc"):
+            return "(file scope)"
         return "kernel entry (%s)" % name
 
     per_region = collections.defaultdict(collections.Counter)
@@ -167,7 +170,7 @@ def main():
     for name, _ in CLASSES + [("other", None)]:
         if total[name]:
             print("| %s | %d | %.1f %% |" % (name, total[name], 100.0 * total[name] / n))
-    print("\nBy source region (function of c2rt_trace.inc / c2rt_kernels.hip the statement belongs to), largest first; columns: all / fp64 arithmetic / "
+    print("\nBy source region (function of c2rt_trace*.inc / c2rt_tile_mask.inc / c2rt_kernels.hip the statement belongs to), largest first; columns: all / fp64 arithmetic / "
           "fp64 seeds / divide-sqrt scaffolding / compares / selects / moves (32+64) / spill lanes / SALU+branch+wait:\n")
     print("| region | all | fp64 arith | seeds | scaffolding | fp64 cmp | selects | moves | spill lanes | scalar |\n|---|---|---|---|---|---|---|---|---|---|")
     for reg, cnt in sorted(per_region.items(), key=lambda kv: -sum(kv[1].values())):

@@ -15,7 +15,7 @@ radians is `x * (PI / 180)` with std.math's 80-bit PI, mat3d.rotateX / rotateY /
 `v *= 1 / sqrt(squaredMagnitude)`, vector * scalar is component by component.
 
 What the reference leaves irreproducible is BUILD-DEFINED and restated from its specification (DESIGN.md section 2 and
-the comments above hash32 and lens_sincos2pi in chess2rt_amd/csrc/c2rt_trace.inc), not from its code:
+the comments above hash32 and lens_sincos2pi in chess2rt_amd/csrc/c2rt_trace_shared.inc), not from its code:
   - uniform(0, 1) is a counter-based RNG: hash32 is the 32-bit multiply-xorshift finaliser "lowbias32" (shifts 16, 15,
     16; multipliers 0x7feb352d, 0x846ca68b); the key folds the seed's high word (xor 0x243f6a88), its low word (xor),
     the pixel's high word (add), its low word (xor) and the tap (add), one hash each; a draw is

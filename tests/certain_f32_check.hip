@@ -64,7 +64,7 @@ __device__ inline double draw(uint64_t key, int lo, int hi)
     }
     return __longlong_as_double((long long)((b & (1ull << 63)) | ((uint64_t)(e + 1023) << 52) | m));
 }
-/* BitmapTexture.getTexColor's use of a coordinate, as bitmap_color (c2rt_trace.inc) writes it */
+/* BitmapTexture.getTexColor's use of a coordinate, as bitmap_color (c2rt_trace_shared.inc) writes it */
 __device__ inline uint32_t pipeline_bits(double u, double s)
 {
     u *= s;

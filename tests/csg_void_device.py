@@ -37,7 +37,7 @@ def _hook():
 
 
 def tile_mask_slot(trow, tcol, cols, mask_rows):
-    """tile_mask_slot (c2rt_trace.inc), from its documented formula: eight row classes (tile rows r, r + 8, ...),
+    """tile_mask_slot (c2rt_tile_mask.inc), from its documented formula: eight row classes (tile rows r, r + 8, ...),
     each ceil(ceil(mask_rows / 8) / 8) tile rows of `cols` entries"""
     per_class = ((mask_rows + 7) // 8 + 7) // 8
     return ((trow & 7) * per_class + (trow >> 3)) * cols + tcol

@@ -126,7 +126,7 @@ def test_rng_equals_the_oracles():
 
 def test_lens_coefficients_are_the_correctly_rounded_reciprocal_factorials():
     """each +-1/k! computed here (fractions, rounded once) equals the device's hex constant, and so does pi / 2"""
-    text = open(os.path.join(ROOT, "chess2rt_amd", "csrc", "c2rt_trace.inc")).read()
+    text = open(os.path.join(ROOT, "chess2rt_amd", "csrc", "c2rt_trace_shared.inc")).read()
     body = text[text.index("DEV void lens_sincos2pi"):]
     body = body[:body.index("\n}\n")]
     consts = [float.fromhex(h) for h in re.findall(r"-?0x1\.[0-9a-f]+p[+-]\d+", body)]

@@ -43,7 +43,7 @@ def test_window_test_accepts_exactly_the_finite_magnitudes_in_range():
         assert in_window(x), x
     for x in outside:
         assert not in_window(x), x
-    # the running unsigned maximum of t flags a sequence iff one member is outside (Oob in c2rt_trace.inc)
+    # the running unsigned maximum of t flags a sequence iff one member is outside (Oob in c2rt_trace_shared.inc)
     rng = np.random.RandomState(5)
     span = (240 + 240) << 21
     for _ in range(2000):

@@ -1,4 +1,4 @@
-"""The CsgDiff void-tile pre-pass on the device (chess2rt_amd/csrc/csg_void.h, c2rt_trace.inc: tile_mask_entry).
+"""The CsgDiff void-tile pre-pass on the device (chess2rt_amd/csrc/csg_void.h, c2rt_tile_mask.inc: tile_mask_entry).
 
 test_device_drops_equal_host_claims reads the mask table back through the diagnostics build's c2rt_debug_tile_masks
 (tests/csg_void_device.py) at void_flags_mask 0, 1 and 3 and insists that the device dropped a node from exactly

@@ -1,4 +1,4 @@
-"""Dark ground tiles on the device (chess2rt_amd/csrc/csg_void.h: tile_dark_by; c2rt_trace.inc: tile_mask_entry writes
+"""Dark ground tiles on the device (chess2rt_amd/csrc/csg_void.h: tile_dark_by; c2rt_tile_mask.inc: tile_mask_entry writes
 bit 2 of the mask table's third word, lean::ground_tile renders such a tile without shadow rays and light terms).
 
 lecture5 at 640x480 — the smallest size with enough dark tiles to show anything — as a whole frame, as two ranks' 8-row

@@ -600,7 +600,7 @@ def test_occluder_outside_the_left_childs_box(gpu_ctx, tmp_path, scenes_dir):
 
 
 def test_nested_csg_trees_that_only_shadow_the_view(gpu_ctx, tmp_path):
-    """The shadow masks of lights 1.. come from the per-tile table the pre-pass writes (c2rt_trace.inc:
+    """The shadow masks of lights 1.. come from the per-tile table the pre-pass writes (c2rt_tile_mask.inc:
     light_shadow_mask; until round 4 every sample derived them with a ballot).  Here the deep trees (depth 3 and 4)
     are OUT of view and only their shadows — from two lights on opposite sides, and from five lights, one more than
     the table holds masks for — fall into the frame, next to a depth-1 and a depth-2 tree in view: a mask that culled

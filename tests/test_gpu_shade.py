@@ -1,4 +1,4 @@
-"""GPU: shade(), light_terms(), tex_color() and bitmap_filtered() of c2rt_trace.inc in isolation, against
+"""GPU: shade() and light_terms() of c2rt_trace.inc, tex_color() and bitmap_filtered() of c2rt_trace_shared.inc in isolation, against
 tests/shade_reference.py (a typed numpy restatement of the reference's shading stage written from the D source, which
 tests/test_shade_reference.py holds against the oracle on the CPU).
 

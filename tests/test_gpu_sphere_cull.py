@@ -1,5 +1,5 @@
 """The sphere-silhouette test of the mask pre-pass on the device (chess2rt_amd/csrc/csg_void.h: cone_misses_ball,
-c2rt_trace.inc: tile_mask_entry).
+c2rt_tile_mask.inc: tile_mask_entry).
 
 Through the diagnostics hooks (tests/sphere_cull_device.py) the device's drops equal the host classifier's claims
 tile for tile — the classifier tests/test_sphere_cull_tiles.py checks ray by ray in the oracle —, the table with the
