@@ -61,24 +61,24 @@ HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/
 # over the SAME kernel objects; tests and scripts that need a hook load it with C2RT_LIB_VARIANT=diag
 DIAGNAME   := chess2rt_amd/libc2rt_diag.so
 
-all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so
+all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so
 
 $(BUILD):
 	mkdir -p $(BUILD)
 
 # (the Makefile is a prerequisite: the arithmetic and code-generation flags are part of what a kernel object is)
-TRACE_DEPS := $(CSRC)/c2rt_trace_common.inc $(CSRC)/c2rt_trace_shared.inc $(CSRC)/c2rt_tile_mask.inc $(CSRC)/c2rt_trace.inc $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/x87.h $(CSRC)/fp64_lean.h $(CSRC)/f32_certain.h include/c2rt.h Makefile
+TRACE_DEPS := $(CSRC)/c2rt_trace_common.inc $(CSRC)/c2rt_trace_shared.inc $(CSRC)/c2rt_tile_mask.inc $(CSRC)/c2rt_trace.inc $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/x87.h $(CSRC)/fp64_lean.h $(CSRC)/f32_certain.h $(CSRC)/ground_certain.h include/c2rt.h Makefile
 $(BUILD)/c2rt_kernels_u%.o: $(CSRC)/c2rt_kernels.hip $(TRACE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_u$*) $(EXTRA_KERNEL_FLAGS) -DC2RT_UNIT=$* -c $< -o $@
 
 $(foreach q,$(QUERIES),$(BUILD)/$(q).o): $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/c2rt_query.inc $(CSRC)/c2rt_query.h $(TRACE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_QUERY) $(EXTRA_KERNEL_FLAGS) -c $< -o $@
 
-$(BUILD)/c2rt_api.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
+$(BUILD)/c2rt_api.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -c $< -o $@
 
 # the HIP-free planner (scene validation and packing, per-frame culling decisions)
-$(BUILD)/scene_plan.o: $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
+$(BUILD)/scene_plan.o: $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) -c $< -o $@
 
 $(BUILD)/%.o: $(CSRC)/host/%.cpp $(CSRC)/host/scene.hpp $(CSRC)/host/dsc.hpp include/c2rt.h include/c2rt_host.h | $(BUILD)
@@ -87,7 +87,7 @@ $(BUILD)/%.o: $(CSRC)/host/%.cpp $(CSRC)/host/scene.hpp $(CSRC)/host/dsc.hpp inc
 $(LIBNAME): $(KOBJS) $(HOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
-$(BUILD)/c2rt_api_diag.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h | $(BUILD)
+$(BUILD)/c2rt_api_diag.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -DC2RT_DIAG=1 -c $< -o $@
 
 $(DIAGNAME): $(KOBJS) $(BUILD)/c2rt_api_diag.o $(filter-out $(BUILD)/c2rt_api.o,$(HOBJS))
@@ -112,22 +112,31 @@ tests/libsphere_cull_check.so: tests/sphere_cull_check.cpp $(CSRC)/csg_void.h
 
 # host build of the planner, without ROCm on the include path: the build itself enforces that scene_plan.cpp is HIP-free
 # (tests/test_scene_plan.py holds it to the restatements in scripts/csg_void_tiles.py and scripts/sphere_cull_tiles.py)
-tests/libscene_plan_check.so: tests/scene_plan_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h
+tests/libscene_plan_check.so: tests/scene_plan_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/scene_plan_check.cpp $(CSRC)/scene_plan.cpp
 
 # host build of the pose-and-replan step behind c2rt_update_scene and c2rt_render_frames_posed (tests/test_scene_update_plan.py),
 # without ROCm like the planner's: what it drives is scene_plan.cpp's own update_scene_plan, not a copy of it
-tests/libscene_update_check.so: tests/scene_update_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h
+tests/libscene_update_check.so: tests/scene_update_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/scene_update_check.cpp $(CSRC)/scene_plan.cpp
 
 # host build of the planner's decision which frames take the ground-tile path (tests/test_ground_fast_plan.py), without ROCm
-tests/libground_fast_check.so: tests/ground_fast_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h
+tests/libground_fast_check.so: tests/ground_fast_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/ground_fast_check.cpp $(CSRC)/scene_plan.cpp
 
 # host build of the dark-tile test of the mask pre-pass and of the planner's part of it (tests/test_ground_dark_tiles.py,
 # scripts/ground_dark_tiles.py), without ROCm
-tests/libground_dark_check.so: tests/ground_dark_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h include/c2rt.h
+tests/libground_dark_check.so: tests/ground_dark_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/ground_dark_check.cpp $(CSRC)/scene_plan.cpp
+
+# host build of the planner's decision which frames take the short chain for ground tiles (tests/test_ground_certain_plan.py), without ROCm
+tests/libground_certain_check.so: tests/ground_certain_plan_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
+	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/ground_certain_plan_check.cpp $(CSRC)/scene_plan.cpp
+
+# host check of ground_certain.h against the reference's chain in IEEE doubles (tests/test_ground_certain_host.py builds
+# its own copy; `make tests/ground_certain_check SAN=-fsanitize=address,undefined` for a sanitizer run of the same program)
+tests/ground_certain_check: tests/ground_certain_check.c $(CSRC)/ground_certain.h
+	$(CC) -O2 -std=gnu11 $(FPFLAGS) -fopenmp -Wall $(SAN) -o $@ $< -lm
 
 # CPU oracle: plain C restatement of the reference algorithm (tests only)
 oracle/libc2rt_oracle.so: oracle/c2rt_oracle.c oracle/c2rt_oracle.h include/c2rt.h
@@ -146,6 +155,6 @@ resource-usage: | $(BUILD)
 	    -c $(CSRC)/$(q).hip -o $(BUILD)/ru_$(q).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
 
 clean:
-	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so
+	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/ground_certain_check
 
 .PHONY: all clean resource-usage

@@ -459,6 +459,12 @@ class Context:
         self._check(self._lib.c2rt_get_exact_redos(self._h, C.byref(n)))
         return int(n.value)
 
+    def groundBails(self):
+        """Ground-only tiles that left the short fp64 chain for the full one (cumulative; ground_certain.h)."""
+        n = C.c_uint64()
+        self._check(self._lib.c2rt_get_ground_bails(self._h, C.byref(n)))
+        return int(n.value)
+
     def renderPixel(self, cam, opts, x, y):
         r = TraceResult()
         self._check(self._lib.c2rt_render_pixel(self._h, C.byref(cam), C.byref(opts), int(x), int(y), C.byref(r)))

@@ -104,7 +104,7 @@ struct c2rt_ctx {
 
     float *frame = nullptr;        /* staging frame for host-output renders */
     size_t frame_floats = 0;
-    unsigned long long *counters = nullptr; /* [0..2]: RenderParams::ray_counters (reset per counted frame); [3]: RenderParams::redo_counter (cumulative) */
+    unsigned long long *counters = nullptr; /* [0..2]: RenderParams::ray_counters (reset per counted frame); [3]: RenderParams::redo_counter (cumulative); [4]: redo_counter[1], ground tiles that left the short chain (cumulative) */
     c2rt_trace_result *probe = nullptr;
     uint8_t *srgb_lut = nullptr;   /* [4097] */
     FrameScratch scratch[kScratchSlots];
@@ -625,8 +625,8 @@ int c2rt_init(int device, c2rt_ctx **out)
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_ready, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_inflight, hipEventDisableTiming));
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->counters), 4 * sizeof(unsigned long long)));
-    HIP_TRY(ctx, hipMemset(ctx->counters, 0, 4 * sizeof(unsigned long long)));
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->counters), 5 * sizeof(unsigned long long)));
+    HIP_TRY(ctx, hipMemset(ctx->counters, 0, 5 * sizeof(unsigned long long)));
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->probe), sizeof(c2rt_trace_result)));
     uint8_t lut[4097];
     build_srgb_lut(lut);
@@ -1291,6 +1291,24 @@ int c2rt_get_exact_redos(c2rt_ctx *ctx, uint64_t *out)
     return C2RT_OK;
 }
 
+int c2rt_get_ground_bails(c2rt_ctx *ctx, uint64_t *out)
+{
+    if (!ctx || !out) return C2RT_ERR_INVALID_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    unsigned long long h = 0;
+    HIP_TRY(ctx, hipMemcpy(&h, ctx->counters + 4, sizeof h, hipMemcpyDeviceToHost));
+    *out = h;
+    for (c2rt_ctx *c : ctx->peers) {
+        HIP_TRY(ctx, hipSetDevice(c->device));
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        HIP_TRY(ctx, hipMemcpy(&h, c->counters + 4, sizeof h, hipMemcpyDeviceToHost));
+        *out += h;
+    }
+    if (!ctx->peers.empty()) HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return C2RT_OK;
+}
+
 int c2rt_render_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, int x, int y,
                       c2rt_trace_result *out)
 {
@@ -1302,6 +1320,7 @@ int c2rt_render_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_re
     frame_params(ctx, cam, opts, p);
     p.n_cull = 0; /* the probe launch has no tile: never cull */
     p.ground_fast = 0;
+    p.ground_certain_cq = 0;
     p.n_cull_lights = 0;
     p.csg_cap = (uint32_t)kCsgFullCap(C2RT_MAX_CSG_DEPTH); /* the probe instance handles every depth */
     p.probe_x = x;

@@ -216,6 +216,11 @@ struct RenderParams {
      * renders the listed tiles (at full capacity) instead of the whole grid */
     uint32_t csg_cap;
     uint32_t retry_mode, retry_max;
+    /* > 0: a ground_fast frame inside the domain of ground_certain.h (scene_plan.cpp, fill_params: gc_plan) — its
+     * ground-only and dark tiles go through lean::ground_tile_certain first, which either writes the tile's pixels or
+     * bails (one count in redo_counter[1], c2rt_get_ground_bails) and leaves the tile to ground_tile.  The value is
+     * that header's one per-frame constant, cq, rounded up.  (Sits in what was padding: no other member moves.) */
+    float ground_certain_cq;
     uint32_t *retry_list;
     /* per tile, 4 words: {primary mask, shadow mask of light 0, ground bits, 0}; frames with several culled lights
      * carry a second table of the same layout behind it, mask_entries entries further on: {shadow masks of lights
@@ -241,7 +246,8 @@ struct RenderParams {
     const uint8_t *srgb_lut;
     unsigned long long *ray_counters; /* [3] primary rays, shadow rays, CSG hit lists that reached the cap (nullable) */
     /* tiles that the production instances rendered a second time through the compiler's divide / sqrt
-     * because a lane met an operand outside a lean window (c2rt_trace.inc); cumulative, never null */
+     * because a lane met an operand outside a lean window (c2rt_trace.inc); cumulative, never null.  [1]: ground tiles
+     * that left the short chain (ground_tile_certain) */
     unsigned long long *redo_counter;
     /* pixel probe */
     int32_t probe_x, probe_y;

@@ -1298,6 +1298,94 @@ DEV int ground_tile(const RenderParams &P, KArgs K, const uint32_t trow, const u
 }
 
 /*
+ * The same tile through the short chain of ground_certain.h, in a frame the host found inside that header's domain
+ * (RenderParams::ground_certain_cq: eye and light above the floor, a bitmap or a plain colour, magnitudes in range — so
+ * the shadow pre-check holds for the whole frame and d.y < 0 on every lane that hits).  Per sample: the parent's
+ * screen ray and its subtraction o.y - gy, bit for bit; one reciprocal, one product and two fma for the hit point; then
+ * every float and decision the pixel reads — hit / away / beyond limit, the two texture coordinates, (float)r2,
+ * (float)cosTheta — taken from a proven interval around the reference's double, and `unsure` raised where the
+ * interval does not decide it.  From those floats on it is ground_tile's code: bitmap_filtered, base_light, the fp32
+ * shade and the tap sum in the parent's order.  One ballot at the end: a tile with an unsure lane (or one outside a
+ * lean window) writes nothing, counts itself (c2rt_get_ground_bails) and returns kGroundBail — the same wave then
+ * runs ground_tile as if this function did not exist.
+ */
+template <int PO>
+DEV int ground_tile_certain(const RenderParams &P, KArgs K, const uint32_t trow, const uint32_t bcol, const bool dark)
+{
+    static_assert(!(PO & kSpecPlanes), "the planes-only instances have no mask table");
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const uint32_t tcol = bcol * kWavesPerBlock + wave;
+    const uint32_t x = tcol * kTileW + (lane % kTileW);
+    const uint32_t lr0 = trow * kTileH + (lane / kTileW);
+    if (x >= P.width || lr0 >= P.local_rows) return kGroundDone;
+    const uint32_t lr = lr0 + P.row_offset;
+    const uint32_t y = frame_row(P, lr);
+    const uint32_t ntaps = P.taps;
+
+    Oob bad;
+    oob_init(bad);
+    bool unsure = false;
+    F3 accum = mkf(0, 0, 0);
+#pragma unroll 1
+    for (uint32_t s = 0; s < ntaps; ++s) {
+        KArgs Kt = K;
+        asm volatile("" : "+s"(Kt));
+        const RenderParams &Pt = *(const RenderParams *)Kt;
+        Rng rng = {0u, 0, 0};
+        D3 o, raw;
+        screen_ray<0>(bad, Pt, (double)x + k_aa_x[s], (double)y + k_aa_y[s], 0, rng, o, raw);
+        NodeP N = (NodeP)Pt.nodes + Pt.ground_node;
+        const double gy = N->g.p[0], limit = N->g.p[1];
+        double px, pz, bx, bz, q;
+        const int state = gc_hit(o.x, o.z, o.y - gy, raw.x, raw.y, raw.z, (double)Pt.ground_certain_cq, limit, &px, &pz, &bx, &bz, &q);
+        bool u = state == GC_UNSURE;
+        F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
+        if (state == GC_HIT) {
+            Mat mat;
+            load_mat(N, mat);
+            F3 diffuse = mat.color;
+            if (mat.tex_type >= 0) { /* wave-uniform: a bitmap (the host leaves checker floors to ground_tile) */
+                const double sc = (double)__uint_as_float(mat.td[2]);
+                float fu, fv;
+                u |= !gc_tex_float(px, bx, sc, &fu);
+                u |= !gc_tex_float(pz, bz, sc, &fv);
+                /* bitmap_color from its two floats on */
+                const uint32_t w = mat.td[0], hgt = mat.td[1];
+                const uint64_t offset = (uint64_t)mat.td[4] | ((uint64_t)mat.td[5] << 32);
+                diffuse = bitmap_filtered(reinterpret_cast<const float4 *>(Pt.texels) + offset, w, hgt, fu * (float)w, fv * (float)hgt);
+            }
+            F3 lightContrib = mkf(Pt.ambient[0], Pt.ambient[1], Pt.ambient[2]);
+            if (dark) { /* wave-uniform */
+                lightContrib = lightContrib + mkf(0, 0, 0);
+            } else if (Pt.n_lights) {
+                LightP L = (LightP)Pt.lights;
+                F3 avgColor = mkf(0, 0, 0);
+                if (L->lit & 1u) {
+                    const gc_frame f = gc_frame_of(0.0, 1, L->pos[1], gy);
+                    float r2f, cosf;
+                    double unread[4];
+                    u |= !gc_light(px, pz, q, L->pos[0], L->pos[2], &f, &r2f, &cosf, unread);
+                    const F3 baseLight = base_light(bad, L, (double)r2f);
+                    avgColor = avgColor + baseLight * cosf; /* cosTheta > 0 on every lane: the light is above the floor */
+                }
+                lightContrib = lightContrib + avgColor;
+            }
+            c = diffuse * lightContrib;
+        }
+        unsure |= u;
+        accum = s == 0 ? c : accum + c;
+    }
+    if (ntaps > 1) accum = accum / (float)ntaps;
+    if (__ballot(unsure | oob_any(bad))) {
+        if (lane == (int)__builtin_ctzll(__ballot(true))) atomicAdd(P.redo_counter + 1, 1ull); /* c2rt_get_ground_bails */
+        return kGroundBail;
+    }
+    store_pixel(P, (size_t)(P.frame_rows ? y : lr) * P.width + x, accum);
+    return kGroundDone;
+}
+
+/*
  * Frame kernel: Renderer.renderRT passes 2 and 3b (rt/renderer.d:133-142,
  * 183-186) fused — all taps of a pixel are accumulated in registers in the
  * reference's order and the pixel is written once (12 B of HBM traffic per
@@ -1360,6 +1448,13 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
             KArgs Kg = K;
             uint32_t trow_g = trow, bcol_g = bcol, dark_g = (uint32_t)__builtin_amdgcn_readfirstlane(dark && !ground_only ? 1 : 0);
             asm volatile("" : "+s"(Kg), "+s"(trow_g), "+s"(bcol_g), "+s"(dark_g));
+            /* first the short chain, where the host found the frame inside its domain: it renders the tile, or writes
+             * nothing and hands it on (kGroundBail) */
+            if (((const RenderParams *)Kg)->ground_certain_cq > 0) { /* wave-uniform */
+                const int gc = ground_tile_certain<PO>(*(const RenderParams *)Kg, Kg, trow_g, bcol_g, dark_g != 0);
+                if (!__ballot(gc == kGroundBail)) return false;
+                asm volatile("" : "+s"(Kg), "+s"(trow_g), "+s"(bcol_g), "+s"(dark_g));
+            }
             const int g = ground_tile<PO>(*(const RenderParams *)Kg, Kg, trow_g, bcol_g, dark_g != 0);
             if (!__ballot(g == kGroundBail)) return g == kGroundRedo;
         }

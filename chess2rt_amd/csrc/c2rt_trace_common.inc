@@ -21,6 +21,7 @@
 #include "c2rt_device.h"
 #include "f32_certain.h"
 #include "fp64_lean.h"
+#include "ground_certain.h"
 #include "x87.h"
 
 namespace c2rt {

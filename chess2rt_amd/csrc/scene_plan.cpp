@@ -4,6 +4,7 @@
  * the reference's arithmetic.
  */
 #include "scene_plan.h"
+#include "ground_certain.h"
 
 #include <algorithm>
 #include <climits>
@@ -990,6 +991,22 @@ void fill_params(const ScenePlan &plan, const DeviceTables &dev, const DiagKnobs
         const DevMat &m = plan.nodes[(size_t)p.ground_node].mat;
         const bool tex_ok = m.tex_type < 0 || m.tex_type == C2RT_TEX_CHECKER || m.tex_type == C2RT_TEX_BITMAP;
         p.ground_fast = (m.shader_type == C2RT_SHADER_LAMBERT && tex_ok) ? 1u : 0u;
+    }
+    /* Of those frames, the ones inside the domain of ground_certain.h take lean::ground_tile_certain first: a bitmap or
+     * a plain colour (a checker floor stays on ground_tile: its parity test has no certainty form yet), the eye above the
+     * floor, the light — if it shines — above it too, magnitudes in that header's windows (gc_plan).  The light and the
+     * plane are read from the tables the kernel reads, so a posed frame is judged by its own pose.  Diagnostics build:
+     * C2RT_DEBUG_CULL bit 6 leaves every tile to ground_tile. */
+    p.ground_certain_cq = 0;
+    if (p.ground_fast && !(debug_cull & 64)) {
+        const DevNode &g = plan.nodes[(size_t)p.ground_node];
+        const bool bitmap = g.mat.tex_type == C2RT_TEX_BITMAP;
+        float scaling;
+        std::memcpy(&scaling, &g.mat.texdata[2], sizeof scaling);
+        const bool lit = plan.n_lights == 1 && !plan.lights.empty() && (plan.lights[0].lit & 1u);
+        const double none[3] = {0, 0, 0};
+        if ((g.mat.tex_type < 0 || bitmap) && g.g.p[0] == p.ground_y)
+            p.ground_certain_cq = gc_plan(cam->pos, g.g.p[0], g.g.p[1], lit, lit ? plan.lights[0].pos : none, bitmap, (double)scaling);
     }
 }
 

@@ -463,6 +463,14 @@ int c2rt_get_csg_truncations(c2rt_ctx *ctx, uint64_t *out);
  * only and do not count here. */
 int c2rt_get_exact_redos(c2rt_ctx *ctx, uint64_t *out);
 
+/* How many ground-only 8x8 tiles this context has handed from the short fp64 chain back to the full one since it
+ * was created (synchronises the device).  Frames that look down on a floor from above, lit from above, compute a
+ * floor hit through a short chain with a proven error bound (chess2rt_amd/csrc/ground_certain.h) and keep the
+ * result only where every float and decision of the pixel is certain to be the full chain's; a tile with one
+ * uncertain lane writes nothing and is rendered by the full chain at once.  A cost indicator like
+ * c2rt_get_exact_redos, never a matter of correctness; about 1 tile in 3000 on the shipped scenes. */
+int c2rt_get_ground_bails(c2rt_ctx *ctx, uint64_t *out);
+
 /* Pixel probe: mirrors `renderPixel` (rt/renderer.d:46-57): one sample at
  * integer (x, y), no AA, returns the colour and the trace result. */
 int c2rt_render_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam,
