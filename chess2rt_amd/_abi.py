@@ -24,6 +24,7 @@ MAX_CSG_DEPTH = 4
 MAX_CSG_HITS = 8
 MAX_BATCH_FRAMES = 256
 MAX_RAYS = 1 << 28
+MAX_HIT_LAYERS = 16
 AA_THRESHOLD_REF = 0.1     # C2RT_AA_THRESHOLD_REF (0.1f: passed as a C float)
 
 _i32p = C.POINTER(C.c_int32)
@@ -241,6 +242,10 @@ C2RT_SYMBOLS = {
     "c2rt_render_frames_hits": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.POINTER(HitPlanes)]),
     "c2rt_render_frames_posed_hits_device": (C.c_int, [_VP, _CAM_P, _POSE_P, C.c_uint32, _OPTS_P, C.POINTER(HitPlanes), _VP]),
     "c2rt_render_frames_posed_hits": (C.c_int, [_VP, _CAM_P, _POSE_P, C.c_uint32, _OPTS_P, C.POINTER(HitPlanes)]),
+    "c2rt_trace_rays_layers_device": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, _VP, _VP, _VP, _VP]),
+    "c2rt_trace_rays_layers": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, _VP, _VP, _VP]),
+    "c2rt_render_hit_layers_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_uint32, C.POINTER(HitPlanes), _VP, _VP]),
+    "c2rt_render_hit_layers": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_uint32, C.POINTER(HitPlanes), _VP]),
     "c2rt_render_frame_adaptive_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frame_adaptive": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frames_adaptive_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
@@ -273,6 +278,7 @@ C2RT_HOST_SYMBOLS = {
     "c2rt_host_render_wait": (C.c_int, [_VP]),
     "c2rt_host_render_pixel": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.POINTER(TraceResult)]),
     "c2rt_host_render_hits": (C.c_int, [_VP, _VP, C.POINTER(HitPlanes)]),
+    "c2rt_host_render_hit_layers": (C.c_int, [_VP, _VP, C.c_uint32, C.POINTER(HitPlanes), _VP]),
     "c2rt_host_render_rt_adaptive": (C.c_int, [_VP, _VP, _VP, _VP]),
     "c2rt_host_bmp_decode": (C.c_int, [_VP, C.c_size_t, _u32p, _u32p, C.POINTER(_f32p)]),
     "c2rt_host_texture_gamma": (None, [_VP, C.c_size_t, C.c_float]),

@@ -491,6 +491,52 @@ class Context:
         self._check(self._lib.c2rt_trace_rays_device(self._h, C.c_void_p(rays_ptr), int(n), C.c_void_p(hits_ptr or None),
                                                      C.c_void_p(rgb_ptr or None), C.c_void_p(stream)))
 
+    def traceRayLayers(self, rays, max_layers, hits=True, colors=True):
+        """Every surface along caller-supplied rays, in order (c2rt_trace_rays_layers): `rays` as for traceRays.  Returns
+        (records, rgb, count): records (max_layers, n) of RAY_HIT_DTYPE and rgb (max_layers, n, 3) float32, layer k of ray
+        i at [k, i] — the one switched off is None — and count (n,) uint8, the number of hits stored.  Slot [k, i] means
+        something for k <= count[i] only (the miss that ended the walk is stored; what lies behind it is unspecified)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays: expected shape (n, 6), got %r" % (rays.shape,))
+        n, K = rays.shape[0], int(max_layers)
+        rec = np.zeros((max(K, 0), n), dtype=RAY_HIT_DTYPE) if hits else None
+        rgb = np.zeros((max(K, 0), n, 3), dtype=np.float32) if colors else None
+        count = np.zeros(n, dtype=np.uint8)
+        self._check(self._lib.c2rt_trace_rays_layers(self._h, rays.ctypes.data_as(C.c_void_p), n, K,
+                                                     rec.ctypes.data_as(C.c_void_p) if hits else None,
+                                                     rgb.ctypes.data_as(C.c_void_p) if colors else None,
+                                                     count.ctypes.data_as(C.c_void_p)))
+        return rec, rgb, count
+
+    def traceRayLayersDevice(self, rays_ptr, n, max_layers, hits_ptr, rgb_ptr, count_ptr, stream=0):
+        """Enqueue the layer query on `stream` over device memory: n c2rt_ray at rays_ptr, max_layers * n c2rt_ray_hit at
+        hits_ptr, max_layers * n * 3 floats at rgb_ptr (layer-major), n bytes at count_ptr; any output may be 0 / None,
+        not all three.  Slots behind a ray's final miss are not touched."""
+        self._check(self._lib.c2rt_trace_rays_layers_device(self._h, C.c_void_p(rays_ptr), int(n), int(max_layers), C.c_void_p(hits_ptr or None),
+                                                            C.c_void_p(rgb_ptr or None), C.c_void_p(count_ptr or None), C.c_void_p(stream)))
+
+    def renderHitLayers(self, cam, opts, max_layers, planes=("node", "leaf", "dist", "uv", "p", "normal", "rgb")):
+        """Every surface behind every pixel of the frame (c2rt_render_hit_layers): a dict of numpy arrays for the planes
+        named, shaped (max_layers, local_rows, W) or (max_layers, local_rows, W, components) — layer k is the k-th surface
+        along the pixel's ray, layer 0 what renderHits returns — plus "count" (local_rows, W) uint8.  A pixel's layer k
+        means something for k <= count only.  Refuses what renderHits refuses."""
+        K, rows = int(max_layers), self.localRows(opts)
+        pl, out = _new_hit_planes(planes, max(K, 0) * rows, opts.width)
+        count = np.zeros((rows, opts.width), dtype=np.uint8)
+        self._check(self._lib.c2rt_render_hit_layers(self._h, C.byref(cam), C.byref(opts), K, C.byref(pl), count.ctypes.data_as(C.c_void_p)))
+        out = {k: v.reshape((K, rows) + v.shape[1:]) for k, v in out.items()}
+        out["count"] = count
+        return out
+
+    def renderHitLayersDevice(self, cam, opts, max_layers, ptrs, count_ptr=0, stream=0):
+        """Enqueue the hit layers on `stream` into device memory: `ptrs` maps plane names (HIT_PLANES) to device pointers
+        of max_layers * local_rows * W * components elements, layer after layer without padding; count_ptr: local_rows * W
+        bytes.  Planes left out (or 0 / None) are not written; slots behind a pixel's final miss are not touched."""
+        pl = self._device_hit_planes(ptrs)
+        self._check(self._lib.c2rt_render_hit_layers_device(self._h, C.byref(cam), C.byref(opts), int(max_layers), C.byref(pl),
+                                                            C.c_void_p(count_ptr or None), C.c_void_p(stream)))
+
     def renderHits(self, cam, opts, planes=("node", "leaf", "dist", "uv", "p", "normal", "rgb")):
         """What every pixel of the frame hit (c2rt_render_hits): a dict of numpy arrays for the planes named — node,
         leaf (int32) and dist (float64) of shape (local_rows, W), uv (local_rows, W, 2), p and normal (local_rows, W, 3)
@@ -645,6 +691,16 @@ class Renderer:
         s = self.scene.settings
         pl, out = _new_hit_planes(planes, s.frame_height, s.frame_width)
         self.ctx._check(self._lib.c2rt_host_render_hits(self.ctx.handle, self.scene._h, C.byref(pl)))
+        return out
+
+    def renderHitLayers(self, max_layers, planes=("node", "leaf", "dist", "uv", "p", "normal", "rgb")):
+        """Context.renderHitLayers for the scene's own camera and frame size (c2rt_host_render_hit_layers)."""
+        s, K = self.scene.settings, int(max_layers)
+        pl, out = _new_hit_planes(planes, max(K, 0) * s.frame_height, s.frame_width)
+        count = np.zeros((s.frame_height, s.frame_width), dtype=np.uint8)
+        self.ctx._check(self._lib.c2rt_host_render_hit_layers(self.ctx.handle, self.scene._h, K, C.byref(pl), count.ctypes.data_as(C.c_void_p)))
+        out = {k: v.reshape((K, s.frame_height) + v.shape[1:]) for k, v in out.items()}
+        out["count"] = count
         return out
 
 

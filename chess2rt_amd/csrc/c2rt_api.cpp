@@ -1539,6 +1539,150 @@ int c2rt_render_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_ren
     return C2RT_OK;
 }
 
+/* ---- hit layers: every surface along a ray or pixel (c2rt_layers.hip) --------------------------------------------- */
+
+/* the refusals the two faces share, behind the single-hit call's own; out_ok: some output is there */
+static int check_layer_args(c2rt_ctx *ctx, uint32_t max_layers, bool out_ok)
+{
+    if (max_layers == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "max_layers is 0: at least one layer");
+    if (max_layers > (uint32_t)C2RT_MAX_HIT_LAYERS)
+        return fail(ctx, C2RT_ERR_LIMIT, "%u layers in one call (at most %u)", (unsigned)max_layers, (unsigned)C2RT_MAX_HIT_LAYERS);
+    if (!out_ok) return fail(ctx, C2RT_ERR_INVALID_ARG, "no output asked for: every output pointer is null");
+    return C2RT_OK;
+}
+
+int c2rt_trace_rays_layers_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, uint32_t max_layers, c2rt_ray_hit *hits_dev,
+                                  float *rgb_dev, uint8_t *count_dev, void *hip_stream)
+{
+    if (const int st = check_query_args(ctx, rays_dev, n, true)) return st < 0 ? C2RT_OK : st;
+    if (const int st = check_layer_args(ctx, max_layers, hits_dev || rgb_dev || count_dev)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    query_params(ctx, p);
+    const int e = launch_trace_ray_layers(p, ctx->plan.csg_levels, rays_dev, n, max_layers, n, hits_dev, rgb_dev, count_dev, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "hit layer kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+/* Host variant: c2rt_trace_rays' staging with kQueryChunk / max_layers rays per chunk, the chunk's layers side by side
+ * (layer stride = chunk size), so [inputs | hits | colours | counts] is never larger than that call's buffer plus the
+ * counts.  Each layer's slice of a chunk goes to its place in the caller's layer-major arrays. */
+int c2rt_trace_rays_layers(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, uint32_t max_layers, c2rt_ray_hit *hits, float *rgb, uint8_t *count)
+{
+    if (const int st = check_query_args(ctx, rays, n, true)) return st < 0 ? C2RT_OK : st;
+    if (const int st = check_layer_args(ctx, max_layers, hits || rgb || count)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t cap = kQueryChunk / max_layers, chunk = n < cap ? n : cap;
+    const size_t off_hits = align256(chunk * sizeof(c2rt_ray));
+    const size_t off_rgb = off_hits + (hits ? align256(chunk * max_layers * sizeof(c2rt_ray_hit)) : 0);
+    const size_t off_count = off_rgb + (rgb ? align256(chunk * max_layers * 3 * sizeof(float)) : 0);
+    const size_t bytes = off_count + (count ? chunk : 0);
+    if (const int st = ensure_staging(ctx, bytes)) return st;
+    char *base = reinterpret_cast<char *>(ctx->frame);
+    c2rt_ray *rays_dev = reinterpret_cast<c2rt_ray *>(base);
+    c2rt_ray_hit *hits_dev = hits ? reinterpret_cast<c2rt_ray_hit *>(base + off_hits) : nullptr;
+    float *rgb_dev = rgb ? reinterpret_cast<float *>(base + off_rgb) : nullptr;
+    uint8_t *count_dev = count ? reinterpret_cast<uint8_t *>(base + off_count) : nullptr;
+    RenderParams p;
+    query_params(ctx, p);
+    for (uint64_t i = 0; i < n; i += chunk) {
+        const uint64_t m = n - i < chunk ? n - i : chunk;
+        HIP_TRY(ctx, hipMemcpyAsync(rays_dev, rays + i, m * sizeof(c2rt_ray), hipMemcpyHostToDevice, ctx->stream));
+        const int e = launch_trace_ray_layers(p, ctx->plan.csg_levels, rays_dev, m, max_layers, chunk, hits_dev, rgb_dev, count_dev, ctx->stream);
+        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "hit layer kernel launch: %s", hipGetErrorString((hipError_t)e));
+        for (uint32_t k = 0; k < max_layers; ++k) {
+            if (hits) HIP_TRY(ctx, hipMemcpyAsync(hits + k * n + i, hits_dev + k * chunk, m * sizeof(c2rt_ray_hit), hipMemcpyDeviceToHost, ctx->stream));
+            if (rgb) HIP_TRY(ctx, hipMemcpyAsync(rgb + 3 * (k * n + i), rgb_dev + 3 * (k * chunk), m * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (count) HIP_TRY(ctx, hipMemcpyAsync(count + i, count_dev, m, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return C2RT_OK;
+}
+
+/* the refusals of the frame face, in the documented order: a frame call's, null planes, the layers', then the modes in
+ * which a pixel is not one ray, worded as check_hit_args words them */
+static int check_hit_layer_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, uint32_t max_layers,
+                                const c2rt_hit_planes *planes, const uint8_t *count)
+{
+    if (const int st = check_frame_args(ctx, cam, opts)) return st;
+    if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
+    if (const int st = check_layer_args(ctx, max_layers, any_plane(planes) || count)) return st;
+    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: a pixel's record is one ray's, a lens has many per pixel");
+    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: a pixel's record is one ray's, a stereo camera has two per pixel");
+    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the hit planes do not count rays");
+    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
+    return C2RT_OK;
+}
+
+int c2rt_render_hit_layers_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, uint32_t max_layers,
+                                  const c2rt_hit_planes *planes_dev, uint8_t *count_dev, void *hip_stream)
+{
+    if (const int st = check_hit_layer_args(ctx, cam, opts, max_layers, planes_dev, count_dev)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    if (p.local_rows == 0) return C2RT_OK;
+    const int e = launch_hit_layers(p, ctx->plan.csg_levels, *planes_dev, count_dev, max_layers, (size_t)p.local_rows * p.width, 0, p.local_rows, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "hit layer kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+/* Host variant: c2rt_render_hits' staging with chunks of whole rows of at most kQueryChunk / max_layers pixels (one row
+ * at least), the chunk's layers side by side in every plane (layer stride = chunk pixels), then the counts. */
+int c2rt_render_hit_layers(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, uint32_t max_layers,
+                           const c2rt_hit_planes *planes_host, uint8_t *count_host)
+{
+    if (const int st = check_hit_layer_args(ctx, cam, opts, max_layers, planes_host, count_host)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    const uint32_t rows = p.local_rows, width = p.width;
+    if (rows == 0) return C2RT_OK;
+    uint32_t chunk_rows = (uint32_t)(kQueryChunk / max_layers / width);
+    if (chunk_rows == 0) chunk_rows = 1;
+    if (chunk_rows > rows) chunk_rows = rows;
+    const size_t chunk_px = (size_t)chunk_rows * width, frame_px = (size_t)rows * width;
+    char *const host[7] = {reinterpret_cast<char *>(planes_host->node), reinterpret_cast<char *>(planes_host->leaf),
+                           reinterpret_cast<char *>(planes_host->dist), reinterpret_cast<char *>(planes_host->uv),
+                           reinterpret_cast<char *>(planes_host->p), reinterpret_cast<char *>(planes_host->normal),
+                           reinterpret_cast<char *>(planes_host->rgb)};
+    const size_t px_bytes[7] = {4, 4, 8, 16, 24, 24, 12};
+    size_t off[7], bytes = 0;
+    for (int k = 0; k < 7; ++k) {
+        off[k] = bytes;
+        if (host[k]) bytes += align256(chunk_px * max_layers * px_bytes[k]);
+    }
+    const size_t off_count = bytes;
+    if (count_host) bytes += chunk_px;
+    if (const int st = ensure_staging(ctx, bytes)) return st;
+    char *base = reinterpret_cast<char *>(ctx->frame);
+    const auto dev = [&](int k) { return host[k] ? base + off[k] : nullptr; };
+    c2rt_hit_planes d;
+    d.node = reinterpret_cast<int32_t *>(dev(0));
+    d.leaf = reinterpret_cast<int32_t *>(dev(1));
+    d.dist = reinterpret_cast<double *>(dev(2));
+    d.uv = reinterpret_cast<double *>(dev(3));
+    d.p = reinterpret_cast<double *>(dev(4));
+    d.normal = reinterpret_cast<double *>(dev(5));
+    d.rgb = reinterpret_cast<float *>(dev(6));
+    uint8_t *count_dev = count_host ? reinterpret_cast<uint8_t *>(base + off_count) : nullptr;
+    for (uint32_t r0 = 0; r0 < rows; r0 += chunk_rows) {
+        const uint32_t m = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
+        const int e = launch_hit_layers(p, ctx->plan.csg_levels, d, count_dev, max_layers, chunk_px, r0, m, ctx->stream);
+        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "hit layer kernel launch: %s", hipGetErrorString((hipError_t)e));
+        const size_t first = (size_t)r0 * width, px = (size_t)m * width;
+        for (uint32_t l = 0; l < max_layers; ++l)
+            for (int k = 0; k < 7; ++k)
+                if (host[k])
+                    HIP_TRY(ctx, hipMemcpyAsync(host[k] + (l * frame_px + first) * px_bytes[k], base + off[k] + l * chunk_px * px_bytes[k], px * px_bytes[k],
+                                                hipMemcpyDeviceToHost, ctx->stream));
+        if (count_host) HIP_TRY(ctx, hipMemcpyAsync(count_host + first, count_dev, px, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return C2RT_OK;
+}
+
 /* ---- hit planes of a batch of frames (c2rt_hit_planes.hip: hit_planes_batch_kernel) ------------------------------- */
 
 /* The refusals of the four batch entry points, in the documented order: a batch call's (depth of field, stereo,

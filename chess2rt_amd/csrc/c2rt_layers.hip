@@ -1,0 +1,281 @@
+/*
+ * c2rt_layers.hip — hit layers (c2rt_trace_rays_layers*, c2rt_render_hit_layers*): every surface along a ray, in order,
+ * in one launch.  The reference's CsgOp.findAllIntersections (rt/geometry.d:271-290) with the scene's `trace`
+ * (rt/renderer.d:325-338) in the place of geom.intersect: layer k of a ray is the closest hit of the ray that starts
+ * 1e-6 directions behind layer k - 1's point, its `dist` accumulated without the steps; the walk ends with the first
+ * miss, which is stored, or at max_layers (include/c2rt.h, "hit layers", is the contract).
+ *
+ * Two kernels, the two single-hit query kernels with a loop around the trace:
+ *   trace_ray_layers_kernel — c2rt_rays.hip's trace_rays_kernel: 64 consecutive rays of the caller's array per wave;
+ *   hit_layers_kernel       — c2rt_hit_planes.hip's hit_planes_kernel: one 8x8 tile of a camera frame per wave, the ray
+ *                             from pixel_ray, strips as there.
+ * What they share with the other query kernels (exact:: arithmetic, no culling, the full-capacity hit stack, its
+ * occupancy): c2rt_query.inc.  Outputs are layer-major — layer k's slice of every output is the output of the single-hit
+ * kernel, `layer_stride` records or pixels behind layer k - 1's —, so each layer's stores are those kernels' stores.
+ *
+ * The loop is wave-synchronous.  A lane WALKS while it has a ray to trace: it starts walking when it is inside the
+ * array / the frame, and stops when it misses.  Everything between two loop heads is inside `if (walking)`: a lane that
+ * is past the end or that has missed is out by control flow before the next trace_closest, so the __all / __ballot /
+ * readfirstlane of the trace only ever see lanes with a ray, as in the single-hit kernels.  The loop ends when the
+ * ballot of the walking lanes is zero or at max_layers; both are wave-uniform, the loop branch is scalar.
+ * trace_closest's `record` is set whenever the caller reads a record field OR another layer may follow (k + 1 <
+ * max_layers): surf.p seeds the next origin and best.dist the total.  With max_layers == 1 it is the single-hit
+ * kernel's flag.  (The bits of a record do not depend on it.)
+ *
+ * A lane of NaNs, zeros or 1e300 walks like any other through the bounded loops of the trace; a step that does not move
+ * it (p + d * 1e-6 == p) finds the same surface again until max_layers ends it.  What it computes stays in its own
+ * registers and slots.
+ *
+ * Record stores of the ray kernel: each walking lane stores its own ten words, 8-byte stores at an 80-byte stride.  No
+ * LDS, no barrier, and a lane that does not walk stores nothing, so a slot behind a ray's final miss is not touched.
+ * trace_rays_kernel's way — the walking lanes stage their records in the hit stack while it is dead and the whole wave
+ * writes them as rows, word w belonging to lane w / kHitWords and the layer's ballot saying whether that lane stored —
+ * was built and measured against it (profiles/hit_layers.md): 240.0 against 231.8 us for hits + colour at 4 layers
+ * (151.5 against 148.0 at one), 168.3 against 171.9 us for hits alone.  The rows win what they win in trace_rays_kernel
+ * only while nothing else is stored; with colours the LDS round trip and the two barriers per layer cost more, and
+ * the ten rows in flight needed eight more VGPRs.  The plain store is kept.
+ * The frame kernel stores as hit_planes_kernel does, each lane its own values: measured faster there.
+ * All stores are plain vector stores.
+ */
+#define C2RT_TRACE_EXACT_ONLY
+#include "c2rt_trace_common.inc"
+#include "c2rt_query.inc"
+
+namespace c2rt {
+namespace {
+
+constexpr int kHitWords = (int)(sizeof(c2rt_ray_hit) / 8);
+constexpr int kHitTileW = 8, kHitTileH = kWave / kHitTileW;
+static_assert(sizeof(c2rt_ray) == 48 && sizeof(c2rt_ray_hit) == 80 && kHitWords * 8 == sizeof(c2rt_ray_hit), "ABI layout of the query records");
+static_assert(__builtin_offsetof(c2rt_ray_hit, leaf_geom) == 4 && __builtin_offsetof(c2rt_ray_hit, dist) == 8 &&
+              __builtin_offsetof(c2rt_ray_hit, p) == 32 && __builtin_offsetof(c2rt_ray_hit, normal) == 56, "ABI layout of c2rt_ray_hit");
+static_assert(sizeof(c2rt_hit_planes) == 56, "ABI layout of c2rt_hit_planes");
+static_assert(sizeof(RenderParams) + sizeof(c2rt_hit_planes) + 40 <= 4096, "the kernel-argument segment holds at most 4 KiB");
+static_assert(C2RT_MAX_HIT_LAYERS <= 255, "a ray's count is one byte");
+
+/* The register budget: the query kernels' (C2RT_WAVES_QUERY), but for the depth-1 instance with one light.  That one
+ * has four waves per SIMD there, 128 VGPRs, of which trace_rays_kernel uses 109; with the origin, the total, the count
+ * and the loop on top the compiler spilled 22 to 24 VGPRs to scratch at that budget.  Three waves per SIMD, the budget
+ * of its several-lights twin: no scratch — and one wave in four less, which one layer of a depth-1, one-light scene
+ * pays with 20 % over the single-hit call (profiles/hit_layers.md). */
+template <int LEVELS, bool MLC>
+constexpr int occ_layers() { return LEVELS == 1 ? 3 : occ_query<LEVELS, MLC>(); }
+#define C2RT_WAVES_LAYERS(L, M) __attribute__((amdgpu_waves_per_eu(occ_layers<L, M>(), occ_layers<L, M>())))
+
+/* load6 of c2rt_rays.hip, restated (that file's object stays as it is): the six doubles of a c2rt_ray as three 16-byte
+ * loads where the hardware takes them at 8-byte alignment */
+typedef double __attribute__((ext_vector_type(2), aligned(8))) d2_t;
+DEV void load6(const void *rec, D3 &a, D3 &b)
+{
+    const d2_t *q = static_cast<const d2_t *>(rec);
+    const d2_t q0 = q[0], q1 = q[1], q2 = q[2];
+    a = mk(q0.x, q0.y, q1.x);
+    b = mk(q1.y, q2.x, q2.y);
+}
+
+/* One layer's bookkeeping behind trace_closest, for a walking lane: temp.dist += currentLength; currentLength =
+ * temp.dist (rt/geometry.d:283-284) for a hit — one addition, the steps not counted — and the count. */
+DEV void layer_account(const int closest, Hit &best, double &total, uint32_t &cnt)
+{
+    if (closest >= 0) {
+        best.dist = best.dist + total;
+        total = best.dist;
+        ++cnt;
+    }
+}
+
+/* The direction never changes, and the optimiser knows: it would compute everything of a layer that depends on `d`
+ * alone (make_ray's magnitude and reciprocals, the shaders' terms) once ahead of the loop and keep it in registers
+ * across every layer — registers the single-hit kernels do not hold and the budget does not have: 24 VGPRs spilled in
+ * the depth-0 frame kernel, 48 at depth 1.  The empty asm makes each layer's `d` a value of its own: the layer is the single-hit kernel's code on the
+ * single-hit kernel's registers, plus the origin, the total and the count. */
+DEV void layer_dir(D3 &d)
+{
+    asm volatile("" : "+v"(d.x), "+v"(d.y), "+v"(d.z));
+}
+
+/* the next layer's origin: p + dir * 1e-6, componentwise, product then sum (the build does not contract) */
+DEV D3 layer_step(const D3 &p, const D3 &d)
+{
+    return mk(p.x + d.x * 1e-6, p.y + d.y * 1e-6, p.z + d.z * 1e-6);
+}
+
+/* Ray i, layers 0 .. max_layers - 1.  hits / rgb / count: nullable, not all three (wave-uniform); layer k's record of ray
+ * i at hits[k * layer_stride + i], its colour at rgb[(k * layer_stride + i) * 3]; 1 <= max_layers. */
+template <int LEVELS, bool MLC>
+__global__ void __launch_bounds__(kWave) C2RT_WAVES_LAYERS(LEVELS, MLC)
+trace_ray_layers_kernel(const RenderParams P, const c2rt_ray *__restrict__ rays, const uint64_t n, const uint32_t max_layers,
+                        const uint64_t layer_stride, c2rt_ray_hit *__restrict__ hits, float *__restrict__ rgb, uint8_t *__restrict__ count)
+{
+    using namespace exact;
+    extern __shared__ __align__(16) char lds[];
+    const int lane = (int)threadIdx.x;
+    const uint64_t first = (uint64_t)blockIdx.x * kWave; /* < n: the grid is ceil(n / 64) */
+    const uint64_t i = first + (uint64_t)lane;
+    Ctx cx;
+    query_ctx(cx, P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
+    D3 o = mk(0, 0, 0), d = mk(0, 0, 0);
+    bool walking = i < n;
+    if (walking) load6(rays + i, o, d);
+    double total = 0.0;
+    uint32_t cnt = 0;
+#pragma unroll 1
+    for (uint32_t k = 0; k < max_layers; ++k) {
+        if (!__ballot(walking)) break;
+        const bool record = hits != nullptr || k + 1 < max_layers; /* wave-uniform */
+        const uint64_t slot = (uint64_t)k * layer_stride;
+        if (walking) {
+            Hit best;
+            Surf surf;
+            Mat mat;
+            layer_dir(d);
+            const int closest = trace_closest<LEVELS>(cx, o, d, record, best, surf, mat);
+            layer_account(closest, best, total, cnt);
+            if (hits) {
+                unsigned long long *rec = reinterpret_cast<unsigned long long *>(hits + slot + i);
+                const int leaf = closest >= 0 ? best.g : -1;
+                rec[0] = (unsigned long long)(uint32_t)closest | ((unsigned long long)(uint32_t)leaf << 32);
+                rec[1] = (unsigned long long)__double_as_longlong(best.dist);
+                rec[2] = (unsigned long long)__double_as_longlong(surf.u);
+                rec[3] = (unsigned long long)__double_as_longlong(surf.v);
+                rec[4] = (unsigned long long)__double_as_longlong(surf.p.x);
+                rec[5] = (unsigned long long)__double_as_longlong(surf.p.y);
+                rec[6] = (unsigned long long)__double_as_longlong(surf.p.z);
+                rec[7] = (unsigned long long)__double_as_longlong(surf.n.x);
+                rec[8] = (unsigned long long)__double_as_longlong(surf.n.y);
+                rec[9] = (unsigned long long)__double_as_longlong(surf.n.z);
+            }
+            if (rgb) {
+                F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
+                uint32_t shadow_rays = 0;
+                if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
+                store_colour(rgb + (slot + i) * 3, c);
+            }
+            if (closest < 0) walking = false;
+            else o = layer_step(surf.p, d);
+        }
+    }
+    if (i < n && count) count[i] = (uint8_t)cnt;
+}
+
+/* Pixel (x, r) of rows [row0, row0 + rows) of the frame `P` describes, layers 0 .. max_layers - 1: hit_planes_body with
+ * the loop around the trace.  Layer k's slice of a plane starts k * layer_px * components elements behind its pointer;
+ * `out` and `count` point at row row0. */
+template <int LEVELS, bool MLC>
+__global__ void __launch_bounds__(kWave) C2RT_WAVES_LAYERS(LEVELS, MLC)
+hit_layers_kernel(const RenderParams P, const c2rt_hit_planes out, uint8_t *__restrict__ count, const uint32_t max_layers,
+                  const size_t layer_px, const uint32_t row0, const uint32_t rows, const uint32_t tiles_x)
+{
+    using namespace exact;
+    extern __shared__ __align__(16) char lds[];
+    const int lane = (int)threadIdx.x;
+    const uint32_t trow = blockIdx.x / tiles_x, tcol = blockIdx.x % tiles_x; /* the grid is tiles_x * ceil(rows / kHitTileH) */
+    const uint32_t x = tcol * kHitTileW + (uint32_t)(lane % kHitTileW);
+    const uint32_t r = trow * kHitTileH + (uint32_t)(lane / kHitTileW); /* row within this launch */
+    const bool live = x < P.width && r < rows;
+    const bool fields = out.dist || out.uv || out.p || out.normal; /* wave-uniform */
+    Ctx cx;
+    query_ctx(cx, P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
+    D3 o = mk(0, 0, 0), d = mk(0, 0, 0);
+    const size_t px = (size_t)r * P.width + x;
+    bool walking = live;
+    if (walking) {
+        /* local row -> frame row under interleaved strips, as hit_planes_body maps it */
+        const uint32_t lr = r + row0;
+        uint32_t y = lr;
+        if (P.strip_world > 1) {
+            const uint32_t sh = P.strip_height;
+            y = ((lr / sh) * P.strip_world + P.strip_rank) * sh + lr % sh;
+        }
+        pixel_ray(cx, P, (double)x, (double)y, o, d);
+    }
+    double total = 0.0;
+    uint32_t cnt = 0;
+#pragma unroll 1
+    for (uint32_t k = 0; k < max_layers; ++k) {
+        if (!__ballot(walking)) break;
+        const bool record = fields || k + 1 < max_layers; /* wave-uniform */
+        const size_t idx = (size_t)k * layer_px + px;
+        if (walking) {
+            Hit best;
+            Surf surf;
+            Mat mat;
+            layer_dir(d);
+            const int closest = trace_closest<LEVELS>(cx, o, d, record, best, surf, mat);
+            layer_account(closest, best, total, cnt);
+            if (out.node) out.node[idx] = closest;
+            if (out.leaf) out.leaf[idx] = closest >= 0 ? best.g : -1;
+            if (out.dist) out.dist[idx] = best.dist;
+            if (out.uv) {
+                d2_t uv;
+                uv.x = surf.u;
+                uv.y = surf.v;
+                *reinterpret_cast<d2_t *>(out.uv + idx * 2) = uv;
+            }
+            if (out.p) {
+                out.p[idx * 3 + 0] = surf.p.x;
+                out.p[idx * 3 + 1] = surf.p.y;
+                out.p[idx * 3 + 2] = surf.p.z;
+            }
+            if (out.normal) {
+                out.normal[idx * 3 + 0] = surf.n.x;
+                out.normal[idx * 3 + 1] = surf.n.y;
+                out.normal[idx * 3 + 2] = surf.n.z;
+            }
+            if (out.rgb) {
+                F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
+                uint32_t shadow_rays = 0;
+                if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
+                store_colour(out.rgb + idx * 3, c);
+            }
+            if (closest < 0) walking = false;
+            else o = layer_step(surf.p, d);
+        }
+    }
+    if (live && count) count[px] = (uint8_t)cnt;
+}
+
+template <int LEVELS>
+int launch_ray_layers_level(const RenderParams &p, const c2rt_ray *rays, uint64_t n, uint32_t max_layers, uint64_t layer_stride,
+                            c2rt_ray_hit *hits, float *rgb, uint8_t *count, hipStream_t s)
+{
+    const dim3 grid((uint32_t)((n + kWave - 1) / kWave)), block(kWave);
+    const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry;
+    if (p.n_lights > 1) hipLaunchKernelGGL((trace_ray_layers_kernel<LEVELS, true>), grid, block, lds, s, p, rays, n, max_layers, layer_stride, hits, rgb, count);
+    else hipLaunchKernelGGL((trace_ray_layers_kernel<LEVELS, false>), grid, block, lds, s, p, rays, n, max_layers, layer_stride, hits, rgb, count);
+    return (int)hipGetLastError();
+}
+
+template <int LEVELS>
+int launch_hit_layers_level(const RenderParams &p, const c2rt_hit_planes &out, uint8_t *count, uint32_t max_layers, size_t layer_px,
+                            uint32_t row0, uint32_t rows, hipStream_t s)
+{
+    const uint32_t tiles_x = (p.width + kHitTileW - 1) / kHitTileW, tiles_y = (rows + kHitTileH - 1) / kHitTileH;
+    const dim3 grid(tiles_x * tiles_y), block(kWave); /* at most 2^16 x 2^16 pixels / 64 */
+    const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry;
+    if (p.n_lights > 1) hipLaunchKernelGGL((hit_layers_kernel<LEVELS, true>), grid, block, lds, s, p, out, count, max_layers, layer_px, row0, rows, tiles_x);
+    else hipLaunchKernelGGL((hit_layers_kernel<LEVELS, false>), grid, block, lds, s, p, out, count, max_layers, layer_px, row0, rows, tiles_x);
+    return (int)hipGetLastError();
+}
+
+} // namespace
+
+int launch_trace_ray_layers(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint32_t max_layers, uint64_t layer_stride,
+                            c2rt_ray_hit *hits, float *rgb, uint8_t *count, void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!n || n > C2RT_MAX_RAYS || !max_layers || max_layers > C2RT_MAX_HIT_LAYERS || layer_stride < n || (!hits && !rgb && !count))
+        return (int)hipErrorInvalidValue;
+    return for_csg_levels(csg_levels, [&](auto L) { return launch_ray_layers_level<decltype(L)::value>(p, rays, n, max_layers, layer_stride, hits, rgb, count, s); });
+}
+
+int launch_hit_layers(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint8_t *count, uint32_t max_layers, size_t layer_px,
+                      uint32_t row0, uint32_t rows, void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool any = out.node || out.leaf || out.dist || out.uv || out.p || out.normal || out.rgb || count;
+    if (!rows || !p.width || !max_layers || max_layers > C2RT_MAX_HIT_LAYERS || layer_px < (size_t)rows * p.width || !any) return (int)hipErrorInvalidValue;
+    return for_csg_levels(csg_levels, [&](auto L) { return launch_hit_layers_level<decltype(L)::value>(p, out, count, max_layers, layer_px, row0, rows, s); });
+}
+
+} // namespace c2rt

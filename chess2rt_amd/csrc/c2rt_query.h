@@ -1,5 +1,5 @@
 /*
- * c2rt_query.h — launch interface of the query kernels (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_adaptive.hip), shared
+ * c2rt_query.h — launch interface of the query kernels (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip, c2rt_adaptive.hip), shared
  * by those files and c2rt_api.cpp.  A header of its own: c2rt_device.h is a prerequisite of every frame-kernel object,
  * and query work should not rebuild them.  All return hipError_t as int; every pointer is a device pointer.
  *
@@ -25,6 +25,14 @@ int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_plan
  * i * frame_px * components elements behind the plane's pointer, at row row0 */
 int launch_hit_planes_batch(const RenderParams &p0, int csg_levels, const RenderParams *table_dev, uint32_t n_frames, size_t frame_px,
                             const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream);
+/* Hit layers (c2rt_trace_rays_layers*, c2rt_render_hit_layers*; c2rt_layers.hip): the single-hit queries with the walk
+ * along the ray around the trace, 1 <= max_layers <= C2RT_MAX_HIT_LAYERS.  Layer k's slice of an output starts
+ * k * layer_stride records (k * layer_px pixels) behind its pointer: n (the frame's local_rows * width) for a caller's
+ * arrays, the chunk size for a host chunk.  hits / rgb / count (the planes / count): nullable, not all of them. */
+int launch_trace_ray_layers(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint32_t max_layers, uint64_t layer_stride,
+                            c2rt_ray_hit *hits, float *rgb, uint8_t *count, void *stream);
+int launch_hit_layers(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint8_t *count, uint32_t max_layers, size_t layer_px,
+                      uint32_t row0, uint32_t rows, void *stream);
 /* Adaptive anti-aliasing (c2rt_render_frame[s]_adaptive*): the flag images needs_aa[i][y][x] of n_frames whole one-tap
  * frames side by side, then the flagged pixels of the whole frame `p` describes (no strips) from their one-tap to their
  * five-tap value, in place; launch_aa_refine_batch: the same for the n_frames frames whose blocks are at table_dev (p0:

@@ -627,6 +627,80 @@ int c2rt_render_frames_posed_hits_device(c2rt_ctx *ctx, const c2rt_camera_frame 
 int c2rt_render_frames_posed_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses,
                                   uint32_t n_frames, const c2rt_render_opts *opts, const c2rt_hit_planes *planes_host);
 
+/* ---- hit layers: every surface along a ray or pixel, in order --------------- */
+
+/* Most layers one call walks; C2RT_ERR_LIMIT beyond. */
+#define C2RT_MAX_HIT_LAYERS 16
+
+/* All intersections along a ray, in order, in one launch: the reference's CsgOp.findAllIntersections
+ * (rt/geometry.d:271-290) with the scene's `trace` (rt/renderer.d:325-338) in the place of geom.intersect.  For ray i:
+ *
+ *     o = ray.orig; d = ray.dir (never changed); total = 0.0
+ *     for k in 0 .. max_layers-1:
+ *         rec, colour = exactly what c2rt_trace_rays computes for the ray (o, d)
+ *         if rec is a hit: rec.dist = rec.dist + total; total = rec.dist
+ *         slot k := rec (a miss is c2rt_ray_hit's miss record: -1, -1, 1e99, zeros), colour slot k := colour (black for a miss)
+ *         if rec is a miss: break
+ *         o = rec.p + d * 1e-6          (componentwise, the product then the sum, not contracted)
+ *     count = number of HIT records stored (0 .. max_layers)
+ *
+ *   - Layout, layer-major: layer k of ray i is hits[k * n + i], rgb[(k * n + i) * 3 ...]; count[i] is one byte per ray.
+ *     hits + k * n is the array c2rt_trace_rays would fill for the rays of layer k.
+ *   - Slot 0 of every output holds the bits of c2rt_trace_rays for that ray, hit or miss; with max_layers == 1 the call
+ *     is c2rt_trace_rays plus `count`.
+ *   - Slot k is written if and only if k <= count and k < max_layers: the miss that ended the walk is stored, nothing
+ *     behind it is.  The _device variant does not touch the later slots; the host variant leaves them unspecified.
+ *     READ `count`: it says how many slots of a ray mean something.
+ *   - p, normal, u, v, closest_node and leaf_geom are the records of the stepped rays as they are.  Only `dist` is
+ *     accumulated — rec.dist + total, one addition — WITHOUT the 1e-6 steps, as the reference does (temp.dist +=
+ *     currentLength; currentLength = temp.dist): it counts lengths of `dir` from the first origin, short by the steps.
+ *   - `dir` is used exactly as given, as for c2rt_trace_rays.
+ *   - The walk is bounded by max_layers.  A ray of NaNs, zeros or 1e300, or one whose step does not move it (p + d *
+ *     1e-6 == p finds the same surface again), ends there and changes no other ray's result.
+ *   - Every output is nullable, not all three: a null `rgb` casts no shadow ray, a null `hits` stores no record, and
+ *     `count` alone is a valid query ("how many surfaces").  What is written does not depend on which outputs are asked for.
+ *   - No CSG hit list can overflow and there is no scratch: the same full-capacity hit stack as the other queries.
+ *
+ * Statuses, all decided before anything is enqueued or any caller pointer is read (the outputs are untouched), each
+ * with its own message, in this order: those of c2rt_trace_rays (null context; n == 0 is C2RT_OK whatever else is
+ * passed; null `rays`: C2RT_ERR_INVALID_ARG; n > C2RT_MAX_RAYS: C2RT_ERR_LIMIT; no scene: C2RT_ERR_NO_SCENE);
+ * max_layers == 0: C2RT_ERR_INVALID_ARG; max_layers > C2RT_MAX_HIT_LAYERS: C2RT_ERR_LIMIT; all three outputs null:
+ * C2RT_ERR_INVALID_ARG.
+ *
+ * The _device variant takes device pointers and enqueues ONE kernel on `hip_stream` under the rules of
+ * c2rt_trace_rays_device: no host sync, no event, no scratch slot, nothing kept of the stream; on a multi-device
+ * context, the lead device. */
+int c2rt_trace_rays_layers_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, uint32_t max_layers,
+                                  c2rt_ray_hit *hits_dev, float *rgb_dev, uint8_t *count_dev, void *hip_stream);
+/* The same from and into HOST memory: staged through the context's staging buffer in chunks of 2^18 / max_layers rays,
+ * so the buffer never grows beyond what c2rt_trace_rays uses; each layer's slice of a chunk is copied to its place
+ * (slots behind a ray's final miss hold unspecified bytes).  Blocks until the results are there. */
+int c2rt_trace_rays_layers(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, uint32_t max_layers,
+                           c2rt_ray_hit *hits, float *rgb, uint8_t *count);
+
+/* The same for the pixels of a camera frame ("depth peeling"): plane k of a pixel is the k-th surface along the ray
+ * c2rt_render_hits traces for it, by the definition above with c2rt_render_hits in the place of c2rt_trace_rays.
+ * c2rt_hit_planes is unchanged; layer k's slice of a plane starts k * local_rows * W * components elements behind the
+ * plane's pointer (the convention c2rt_render_frames_hits uses for frame i); count is [local_rows][W], one byte per
+ * pixel.  Layer 0 of every plane holds the bits of c2rt_render_hits; all layers and `count` hold the bits of
+ * c2rt_trace_rays_layers for the pixels' rays.  A pixel's slot k of a plane is written if and only if k <= count and
+ * k < max_layers (read `count`).  Every plane and `count` are nullable, not all eight: a null plane is neither
+ * computed nor stored, no rgb casts no shadow ray, `count` alone is valid.  Strips as in c2rt_render_hits.
+ *
+ * Statuses, in this order: those of a frame call; null `planes`: C2RT_ERR_INVALID_ARG; max_layers == 0:
+ * C2RT_ERR_INVALID_ARG; max_layers > C2RT_MAX_HIT_LAYERS: C2RT_ERR_LIMIT; all seven planes and `count` null:
+ * C2RT_ERR_INVALID_ARG; C2RT_ERR_UNSUPPORTED with the cause named for depth of field, stereo, count_rays and
+ * prepass_bucket, worded as c2rt_render_hits words them.
+ *
+ * The _device variant: ONE kernel on `hip_stream`, no sync, no event, no scratch slot, nothing kept of the stream; on a
+ * multi-device context, the lead device. */
+int c2rt_render_hit_layers_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, uint32_t max_layers,
+                                  const c2rt_hit_planes *planes_dev, uint8_t *count_dev, void *hip_stream);
+/* The same into HOST memory: chunks of whole rows of at most 2^18 / max_layers pixels (at least one row) through the
+ * context's staging buffer, each layer's slice of a chunk copied to its place; blocks until the planes are there. */
+int c2rt_render_hit_layers(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, uint32_t max_layers,
+                           const c2rt_hit_planes *planes_host, uint8_t *count_host);
+
 /* ---- adaptive anti-aliasing: refine only the pixels the edge test flags ----- */
 
 /* tooDifferent's default threshold — rt/color.d:18 */

@@ -103,6 +103,12 @@ int c2rt_host_render_pixel(c2rt_ctx *ctx, c2rt_host_scene *scene, int x, int y,
  * C2RT_ERR_UNSUPPORTED (c2rt_last_error names the cause); the AA setting does not matter (one sample per pixel). */
 int c2rt_host_render_hits(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt_hit_planes *planes);
 
+/* The hit layers of the scene's own camera at its frame size (c2rt_render_hit_layers: layer k's slice of a plane
+ * k * frame_height * frame_width * components elements behind its pointer, `count` frame_height x frame_width bytes,
+ * host pointers, every one nullable): to c2rt_host_render_hits what that call is to c2rt_render_hits. */
+int c2rt_host_render_hit_layers(c2rt_ctx *ctx, c2rt_host_scene *scene, uint32_t max_layers,
+                                const c2rt_hit_planes *planes, uint8_t *count);
+
 /* Renderer.renderRT with adaptive anti-aliasing (c2rt_render_frame_adaptive) for the scene's own camera at its frame
  * size, with the reference's threshold (C2RT_AA_THRESHOLD_REF) and C2RT_TAPS_REF5 whatever the AA setting: uploads the
  * scene if needed and calls beginFrame.  `out_rgb`: frameWidth * frameHeight * 3 floats; `needs_aa` (nullable):

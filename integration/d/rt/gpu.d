@@ -148,6 +148,19 @@ extern (C) nothrow @nogc
                                              void* hip_stream);
     int c2rt_render_frames_posed_hits(c2rt_ctx*, const c2rt_camera_frame* cams, const c2rt_scene_pose* poses, uint nFrames,
                                       const c2rt_render_opts*, const c2rt_hit_planes* planes_host);
+    /// hit layers: every surface along a ray / behind a pixel, in order, in one launch (findAllIntersections,
+    /// rt/geometry.d:271-290, over the scene's trace); layer-major outputs (layer k of ray i at k * n + i, layer k's slice
+    /// of a plane k * local_rows * W * components elements behind its pointer), count = hits stored per ray / pixel;
+    /// slot k means something for k <= count only; every output nullable, not all
+    enum C2RT_MAX_HIT_LAYERS = 16;
+    int c2rt_trace_rays_layers_device(c2rt_ctx*, const c2rt_ray* rays_dev, ulong n, uint max_layers, c2rt_ray_hit* hits_dev,
+                                      float* rgb_dev, ubyte* count_dev, void* hip_stream);
+    int c2rt_trace_rays_layers(c2rt_ctx*, const c2rt_ray* rays, ulong n, uint max_layers, c2rt_ray_hit* hits, float* rgb,
+                               ubyte* count);
+    int c2rt_render_hit_layers_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, uint max_layers,
+                                      const c2rt_hit_planes* planes_dev, ubyte* count_dev, void* hip_stream);
+    int c2rt_render_hit_layers(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, uint max_layers,
+                               const c2rt_hit_planes* planes_host, ubyte* count_host);
     enum float C2RT_AA_THRESHOLD_REF = 0.1f; /// tooDifferent's default
     int c2rt_render_frame_adaptive_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
                                           float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
