@@ -62,7 +62,7 @@ HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/
 # over the SAME kernel objects; tests and scripts that need a hook load it with C2RT_LIB_VARIANT=diag
 DIAGNAME   := chess2rt_amd/libc2rt_diag.so
 
-all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so
+all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/libground_texel_check.so tests/tap_average_check
 
 $(BUILD):
 	mkdir -p $(BUILD)
@@ -134,6 +134,15 @@ tests/libground_dark_check.so: tests/ground_dark_check.cpp $(CSRC)/scene_plan.cp
 tests/libground_certain_check.so: tests/ground_certain_plan_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/ground_certain_plan_check.cpp $(CSRC)/scene_plan.cpp
 
+# host build of the planner's two decisions behind the short chain's texel fetch and light term (tests/test_ground_texel_plan.py), without ROCm
+tests/libground_texel_check.so: tests/ground_texel_plan_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
+	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/ground_texel_plan_check.cpp $(CSRC)/scene_plan.cpp
+
+# device check of the short chain's tap average and texel blend against the compiler's division and bitmap_filtered
+# (tests/test_gpu_tap_average.py runs it)
+tests/tap_average_check: tests/tap_average_check.hip $(TRACE_DEPS)
+	$(HIPCC) --offload-arch=$(ARCH) -O3 -std=c++17 $(FPFLAGS) -fhip-fp32-correctly-rounded-divide-sqrt $< -o $@
+
 # host check of ground_certain.h against the reference's chain in IEEE doubles (tests/test_ground_certain_host.py builds
 # its own copy; `make tests/ground_certain_check SAN=-fsanitize=address,undefined` for a sanitizer run of the same program)
 tests/ground_certain_check: tests/ground_certain_check.c $(CSRC)/ground_certain.h
@@ -156,6 +165,6 @@ resource-usage: | $(BUILD)
 	    -c $(CSRC)/$(q).hip -o $(BUILD)/ru_$(q).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
 
 clean:
-	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/ground_certain_check
+	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/ground_certain_check tests/libground_texel_check.so tests/tap_average_check
 
 .PHONY: all clean resource-usage

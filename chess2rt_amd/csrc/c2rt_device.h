@@ -140,7 +140,9 @@ struct alignas(16) DevLight {      /* 48 B */
     double pos[3];
     float color[3];                /* lightColor * lightPower (rt/light.d:11-14) */
     uint32_t lit;                  /* bit 0: intensity(color) != 0; bit 1: every channel +0 or within 2^+-60 (lean fp32 division) */
-    uint32_t pad[2];
+    uint32_t equal;                /* 1: bit 1 of `lit` holds and the three channels are the same bits (ground_tile_certain: one
+                                    * quotient for all three).  A word of its own, in what was padding: `lit` keeps its values */
+    uint32_t pad;
 };
 
 /* Kernel argument block (passed by value: lives in the kernarg segment and is

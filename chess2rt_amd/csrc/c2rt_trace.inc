@@ -1304,8 +1304,11 @@ DEV int ground_tile(const RenderParams &P, KArgs K, const uint32_t trow, const u
  * screen ray and its subtraction o.y - gy, bit for bit; one reciprocal, one product and two fma for the hit point; then
  * every float and decision the pixel reads — hit / away / beyond limit, the two texture coordinates, (float)r2,
  * (float)cosTheta — taken from a proven interval around the reference's double, and `unsure` raised where the
- * interval does not decide it.  From those floats on it is ground_tile's code: bitmap_filtered, base_light, the fp32
- * shade and the tap sum in the parent's order.  One ballot at the end: a tile with an unsure lane (or one outside a
+ * interval does not decide it.  From those floats on it is ground_tile's arithmetic — the same IEEE operations on the
+ * same operands, in the parent's order — in forms of its own where the route knows more: bitmap_filtered_uniform for
+ * bitmap_filtered (a wave-uniform bitmap within 32-bit addressing), one light quotient for base_light's three where the
+ * channels are the same bits (DevLight::equal), tap_average for the division by the tap count (c2rt_trace_shared.inc).
+ * One ballot at the end: a tile with an unsure lane (or one outside a
  * lean window) writes nothing, counts itself (c2rt_get_ground_bails) and returns kGroundBail — the same wave then
  * runs ground_tile as if this function did not exist.
  */
@@ -1352,8 +1355,8 @@ DEV int ground_tile_certain(const RenderParams &P, KArgs K, const uint32_t trow,
                 u |= !gc_tex_float(pz, bz, sc, &fv);
                 /* bitmap_color from its two floats on */
                 const uint32_t w = mat.td[0], hgt = mat.td[1];
-                const uint64_t offset = (uint64_t)mat.td[4] | ((uint64_t)mat.td[5] << 32);
-                diffuse = bitmap_filtered(reinterpret_cast<const float4 *>(Pt.texels) + offset, w, hgt, fu * (float)w, fv * (float)hgt);
+                /* (the host keeps a bitmap beyond 2^28 texels of the pool on ground_tile: td[5] is 0 here) */
+                diffuse = bitmap_filtered_uniform(Pt.texels, mat.td[4], w, hgt, fu * (float)w, fv * (float)hgt);
             }
             F3 lightContrib = mkf(Pt.ambient[0], Pt.ambient[1], Pt.ambient[2]);
             if (dark) { /* wave-uniform */
@@ -1366,8 +1369,16 @@ DEV int ground_tile_certain(const RenderParams &P, KArgs K, const uint32_t trow,
                     float r2f, cosf;
                     double unread[4];
                     u |= !gc_light(px, pz, q, L->pos[0], L->pos[2], &f, &r2f, &cosf, unread);
-                    const F3 baseLight = base_light(bad, L, (double)r2f);
-                    avgColor = avgColor + baseLight * cosf; /* cosTheta > 0 on every lane: the light is above the floor */
+                    /* (cosTheta > 0 on every lane: the light is above the floor) */
+                    if (L->equal) { /* wave-uniform: three equal channels — base_light's quotient, bit for bit, its
+                                        * product with cosTheta and its sum with avgColor's +0 once for all three */
+                        oob_note_f32(bad, r2f);
+                        const float b = div_with_f32(L->color[0], r2f, rcp_refined_f32(r2f));
+                        const float a = 0.0f + b * cosf;
+                        avgColor = mkf(a, a, a);
+                    } else {
+                        avgColor = avgColor + base_light(bad, L, (double)r2f) * cosf;
+                    }
                 }
                 lightContrib = lightContrib + avgColor;
             }
@@ -1376,7 +1387,7 @@ DEV int ground_tile_certain(const RenderParams &P, KArgs K, const uint32_t trow,
         unsure |= u;
         accum = s == 0 ? c : accum + c;
     }
-    if (ntaps > 1) accum = accum / (float)ntaps;
+    if (ntaps > 1) tap_average(bad, accum, (float)ntaps);
     if (__ballot(unsure | oob_any(bad))) {
         if (lane == (int)__builtin_ctzll(__ballot(true))) atomicAdd(P.redo_counter + 1, 1ull); /* c2rt_get_ground_bails */
         return kGroundBail;

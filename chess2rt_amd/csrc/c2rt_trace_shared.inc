@@ -352,6 +352,46 @@ DEV F3 bitmap_filtered(const float4 *texels, uint32_t width, uint32_t height, fl
            mkf(c11.x, c11.y, c11.z) * w11;
 }
 
+/* The same function for lean::ground_tile_certain (c2rt_trace.inc), where the bitmap is wave-uniform: `pool` is the
+ * texel pool (RenderParams::texels), `offset` the bitmap's first texel in it.  Same test, floors, wraps, weights and
+ * sum order — the same IEEE operations on the same operands, hence the same bits (tests/tap_average_check.hip holds it
+ * to bitmap_filtered) —, with the instructions around them cut down:
+ *   addresses are 32-bit byte offsets from the scalar pool pointer (global_load_dwordx3 v, v_off, s[base:base+1]).
+ *     The caller guarantees offset + width * height <= 2^28 texels and width, height < 2^24 (scene_plan.cpp,
+ *     fill_params, leaves a frame outside that on ground_tile): ty * width + offset is then one 24-bit multiply-add,
+ *     the row below is that plus width, or `offset` itself where ty + 1 wraps, and a texel index times 16 fits 32 bits;
+ *   the blend is written on (r, g) pairs as they were loaded, the weights broadcast (op_sel), and on b and the weights
+ *     as single floats: a packed instruction costs 1.67 single ones on this chip, so a pair pays only without the
+ *     moves that gather it (scripts/ubench/pk_f32_issue.hip, profiles/r11_variants.md). */
+/* an empty asm on a product: the SLP vectoriser cannot gather it into a register pair, which it does with moves */
+DEV float alone(float v)
+{
+    asm("" : "+v"(v));
+    return v;
+}
+DEV F3 bitmap_filtered_uniform(const float *pool, uint32_t offset, uint32_t width, uint32_t height, float x, float y)
+{
+    if (!(x < (float)width) | !(y < (float)height) | (width == 0) | (height == 0))
+        return mkf(1.0f, 0.0f, 0.0f); /* NamedColors.red */
+    typedef float __attribute__((ext_vector_type(2))) f2_t;
+    typedef float __attribute__((ext_vector_type(3))) f3_t;
+    const float fx = floorf(x), fy = floorf(y);
+    const uint32_t tx = (uint32_t)fx, ty = (uint32_t)fy;
+    const uint32_t txn = tx + 1 == width ? 0 : tx + 1;
+    const float p = x - fx, q = y - fy;
+    const uint32_t row0 = __umul24(ty, width) + offset;
+    const uint32_t row1 = ty + 1 == height ? offset : row0 + width;
+    const char __attribute__((address_space(1))) *base = (const char __attribute__((address_space(1))) *)pool;
+#define C2RT_TEXEL(i) (*(const f3_t __attribute__((address_space(1))) *)(base + (uint64_t)(uint32_t)((i) << 4)))
+    const f3_t c00 = C2RT_TEXEL(row0 + tx), c10 = C2RT_TEXEL(row0 + txn);
+    const f3_t c01 = C2RT_TEXEL(row1 + tx), c11 = C2RT_TEXEL(row1 + txn);
+#undef C2RT_TEXEL
+    const float w00 = alone((1.0f - p) * (1.0f - q)), w10 = alone(p * (1.0f - q)), w01 = alone((1.0f - p) * q), w11 = alone(p * q);
+    const float b = ((alone(c00.z * w00) + alone(c10.z * w10)) + alone(c01.z * w01)) + alone(c11.z * w11);
+    const f2_t rg = ((c00.xy * w00 + c10.xy * w10) + c01.xy * w01) + c11.xy * w11;
+    return mkf(rg.x, rg.y, b);
+}
+
 /* A node's shading inputs in registers (DevMat, c2rt_device.h). */
 struct Mat {
     int shader_type, tex_type, tex;
@@ -539,6 +579,28 @@ DEV void store_pixel(const RenderParams &P, const size_t pixel_index, const F3 a
         v3.z = accum.b;
         *reinterpret_cast<f3_t *>(P.out + pixel_index * 3) = v3;
     }
+}
+
+/* accum / n for ground_tile_certain: `Color / float` (rt/color.d:128-132) through the lean fp32 quotient of fp64_lean.h,
+ * the refined reciprocal of the wave-uniform tap count taken once.  Every channel must be +0 — a sky pixel, a black
+ * texel: +0 * r, the two remainders and the two sums are all +0, as +0 / n is — or a positive float in [2^-60, 2^60),
+ * where the sequence is the compiler's division bit for bit (tests/tap_average_check.hip); any other channel is noted in
+ * `bad` like an operand outside a lean window, and the tile is rendered by ground_tile, which divides the long way.  That
+ * includes every negative channel, -0 among them (the sequence would return +0 for it): no floor the reference can
+ * describe has one.
+ * v = bits - bits(2^-60) is below bits(2^60) - bits(2^-60) exactly for those positive floats, +0 is let through as
+ * v = 0, and half the largest v of the three is on the accumulator's scale. */
+DEV void tap_average(Oob &bad, F3 &accum, const float n)
+{
+    constexpr uint32_t kLo = (uint32_t)(127 - 60) << 23, kSpan = (uint32_t)120 << 23;
+    static_assert((kSpan >> 1) == ((uint32_t)(kWinHi - kWinLo) << kOobShift), "oob_any's threshold");
+    const uint32_t br = __float_as_uint(accum.r), bg = __float_as_uint(accum.g), bb = __float_as_uint(accum.b);
+    const uint32_t vr = br == 0u ? 0u : br - kLo, vg = bg == 0u ? 0u : bg - kLo, vb = bb == 0u ? 0u : bb - kLo;
+    const uint32_t vrg = vr > vg ? vr : vg, v = vrg > vb ? vrg : vb;
+    const uint32_t t = v >> 1;
+    bad.t = bad.t > t ? bad.t : t;
+    const float rn = rcp_refined_f32(n);
+    accum = mkf(div_with_f32(accum.r, n, rn), div_with_f32(accum.g, n, rn), div_with_f32(accum.b, n, rn));
 }
 
 /* what ground_tile (c2rt_trace.inc) returns */

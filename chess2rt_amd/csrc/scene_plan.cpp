@@ -267,6 +267,9 @@ int plan_lights(const c2rt_scene_desc *s, ScenePlan &p, std::string &err)
             chan_ok = chan_ok && (bits == 0u || (a >= 0x1p-60f && a < 0x1p60f));
         }
         if (chan_ok) d.lit |= 2u;
+        /* equal: bit 1 holds and the three channels are the same bits (`color 1 1 1`: every scene the reference ships) —
+         * lean::ground_tile_certain then takes one quotient by the squared distance for all three */
+        d.equal = (chan_ok && !std::memcmp(&d.color[0], &d.color[1], 4) && !std::memcmp(&d.color[0], &d.color[2], 4)) ? 1u : 0u;
     }
     p.light_pos.assign(s->light_pos, s->light_pos + 3 * (size_t)s->n_lights);
     return C2RT_OK;
@@ -1005,7 +1008,15 @@ void fill_params(const ScenePlan &plan, const DeviceTables &dev, const DiagKnobs
         std::memcpy(&scaling, &g.mat.texdata[2], sizeof scaling);
         const bool lit = plan.n_lights == 1 && !plan.lights.empty() && (plan.lights[0].lit & 1u);
         const double none[3] = {0, 0, 0};
-        if ((g.mat.tex_type < 0 || bitmap) && g.g.p[0] == p.ground_y)
+        /* bitmap_filtered_uniform (c2rt_trace_shared.inc) addresses the floor's texels with 32-bit byte offsets and a
+         * 24-bit row product: the bitmap ends within the pool's first 2^28 texels and neither side reaches 2^24 */
+        bool tex_fits = true;
+        if (bitmap) {
+            const uint64_t w = g.mat.texdata[0], h = g.mat.texdata[1];
+            const uint64_t offset = (uint64_t)g.mat.texdata[4] | ((uint64_t)g.mat.texdata[5] << 32);
+            tex_fits = w < (1ull << 24) && h < (1ull << 24) && offset <= (1ull << 28) && w * h <= (1ull << 28) - offset;
+        }
+        if ((g.mat.tex_type < 0 || bitmap) && tex_fits && g.g.p[0] == p.ground_y)
             p.ground_certain_cq = gc_plan(cam->pos, g.g.p[0], g.g.p[1], lit, lit ? plan.lights[0].pos : none, bitmap, (double)scaling);
     }
 }
