@@ -154,6 +154,18 @@ class HitPlanes(C.Structure):
     ]
 
 
+class ShadePlanes(C.Structure):
+    """c2rt_shade_planes: one nullable pointer per term of the sample's shade() (host or device memory, by entry point)"""
+    _fields_ = [
+        ("node", C.c_void_p),
+        ("albedo", C.c_void_p),
+        ("light", C.c_void_p),
+        ("specular", C.c_void_p),
+        ("visible", C.c_void_p),
+        ("rgb", C.c_void_p),
+    ]
+
+
 class ScenePose(C.Structure):
     """c2rt_scene_pose: new transforms ([n_nodes][30] doubles) and light values for some nodes / lights of the uploaded scene"""
     _fields_ = [
@@ -246,6 +258,10 @@ C2RT_SYMBOLS = {
     "c2rt_trace_rays_layers": (C.c_int, [_VP, _VP, C.c_uint64, C.c_uint32, _VP, _VP, _VP]),
     "c2rt_render_hit_layers_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_uint32, C.POINTER(HitPlanes), _VP, _VP]),
     "c2rt_render_hit_layers": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_uint32, C.POINTER(HitPlanes), _VP]),
+    "c2rt_render_shading_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(ShadePlanes), _VP]),
+    "c2rt_render_shading": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(ShadePlanes)]),
+    "c2rt_trace_rays_shading_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(ShadePlanes), _VP]),
+    "c2rt_trace_rays_shading": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(ShadePlanes)]),
     "c2rt_render_frame_adaptive_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frame_adaptive": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frames_adaptive_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
@@ -279,6 +295,7 @@ C2RT_HOST_SYMBOLS = {
     "c2rt_host_render_pixel": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.POINTER(TraceResult)]),
     "c2rt_host_render_hits": (C.c_int, [_VP, _VP, C.POINTER(HitPlanes)]),
     "c2rt_host_render_hit_layers": (C.c_int, [_VP, _VP, C.c_uint32, C.POINTER(HitPlanes), _VP]),
+    "c2rt_host_render_shading": (C.c_int, [_VP, _VP, C.POINTER(ShadePlanes)]),
     "c2rt_host_render_rt_adaptive": (C.c_int, [_VP, _VP, _VP, _VP]),
     "c2rt_host_bmp_decode": (C.c_int, [_VP, C.c_size_t, _u32p, _u32p, C.POINTER(_f32p)]),
     "c2rt_host_texture_gamma": (None, [_VP, C.c_size_t, C.c_float]),

@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (CameraFrame, HitPlanes, HostCamera, HostSettings, Ray, RayHit, RayStats, RenderOpts, SceneDesc, ScenePose, Segment,
-                   TraceResult)
+                   ShadePlanes, TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
 RAY_HIT_DTYPE = np.dtype({
@@ -42,6 +42,35 @@ def _new_hit_planes(names, rows, width):
         out[n] = np.empty((rows, width) if comps == 1 else (rows, width, comps), dtype=dtype)
         setattr(pl, n, out[n].ctypes.data)
     return pl, out
+
+
+# c2rt_shade_planes: plane name -> (dtype, components per sample), in the order of the struct's members
+SHADE_PLANES = {"node": (np.int32, 1), "albedo": (np.float32, 3), "light": (np.float32, 3), "specular": (np.float32, 3),
+                "visible": (np.uint32, 1), "rgb": (np.float32, 3)}
+
+
+def _new_shade_planes(names, shape):
+    """(ShadePlanes of fresh host arrays, {name: array}) for the planes named, `shape` samples each; the others stay null"""
+    names = tuple(names)
+    for n in names:
+        if n not in SHADE_PLANES:
+            raise ValueError("unknown shading plane %r (one of %s)" % (n, ", ".join(SHADE_PLANES)))
+    out, pl = {}, ShadePlanes()
+    for n in names:
+        dtype, comps = SHADE_PLANES[n]
+        out[n] = np.empty(tuple(shape) if comps == 1 else tuple(shape) + (comps,), dtype=dtype)
+        setattr(pl, n, out[n].ctypes.data)
+    return pl, out
+
+
+def _device_shade_planes(ptrs):
+    """ShadePlanes of the device pointers in `ptrs` ({plane name: pointer}); planes left out (or 0 / None) stay null"""
+    pl = ShadePlanes()
+    for n, ptr in dict(ptrs).items():
+        if n not in SHADE_PLANES:
+            raise ValueError("unknown shading plane %r (one of %s)" % (n, ", ".join(SHADE_PLANES)))
+        setattr(pl, n, ptr or None)
+    return pl
 
 
 def makePose(nodes=None, lights=None):
@@ -606,6 +635,38 @@ class Context:
         pl = self._device_hit_planes(ptrs)
         self._check(self._lib.c2rt_render_frames_posed_hits_device(self._h, arr, parr, n, C.byref(opts), C.byref(pl), C.c_void_p(stream)))
 
+    def renderShading(self, cam, opts, planes=tuple(SHADE_PLANES)):
+        """The terms of every pixel's colour (c2rt_render_shading): a dict of numpy arrays for the planes named — node
+        (int32) and visible (uint32, bit l: light l < 32 passed the shadow test) of shape (local_rows, W); albedo, light,
+        specular and rgb (local_rows, W, 3) float32.  On a hit rgb == albedo * light (+ specular for a Phong node) bit for
+        bit, and rgb and node are renderHits'.  Planes not named are neither computed nor stored; node and albedo alone
+        cast no shadow ray.  Refuses what renderHits refuses."""
+        pl, out = _new_shade_planes(planes, (self.localRows(opts), opts.width))
+        self._check(self._lib.c2rt_render_shading(self._h, C.byref(cam), C.byref(opts), C.byref(pl)))
+        return out
+
+    def renderShadingDevice(self, cam, opts, ptrs, stream=0):
+        """Enqueue the shading planes on `stream` into device memory: `ptrs` maps plane names (SHADE_PLANES) to device
+        pointers of local_rows * W * components elements; planes left out (or 0 / None) are not written."""
+        pl = _device_shade_planes(ptrs)
+        self._check(self._lib.c2rt_render_shading_device(self._h, C.byref(cam), C.byref(opts), C.byref(pl), C.c_void_p(stream)))
+
+    def traceRaysShading(self, rays, planes=tuple(SHADE_PLANES)):
+        """The same terms for caller-supplied rays (c2rt_trace_rays_shading): `rays` as for traceRays; a dict of arrays of
+        shape (n,) or (n, 3).  rgb and node are traceRays'."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays: expected shape (n, 6), got %r" % (rays.shape,))
+        pl, out = _new_shade_planes(planes, (rays.shape[0],))
+        self._check(self._lib.c2rt_trace_rays_shading(self._h, rays.ctypes.data_as(C.c_void_p), rays.shape[0], C.byref(pl)))
+        return out
+
+    def traceRaysShadingDevice(self, rays_ptr, n, ptrs, stream=0):
+        """Enqueue the query on `stream` over device memory: n c2rt_ray at rays_ptr, `ptrs` as for renderShadingDevice
+        with n samples per plane."""
+        pl = _device_shade_planes(ptrs)
+        self._check(self._lib.c2rt_trace_rays_shading_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(pl), C.c_void_p(stream)))
+
     def testVisibility(self, segments):
         """Scene.testVisibility for (n, 6) float64 segments (from, to): (n,) uint8, 1 = nothing in between."""
         seg = np.ascontiguousarray(segments, dtype=np.float64)
@@ -701,6 +762,13 @@ class Renderer:
         self.ctx._check(self._lib.c2rt_host_render_hit_layers(self.ctx.handle, self.scene._h, K, C.byref(pl), count.ctypes.data_as(C.c_void_p)))
         out = {k: v.reshape((K, s.frame_height) + v.shape[1:]) for k, v in out.items()}
         out["count"] = count
+        return out
+
+    def renderShading(self, planes=tuple(SHADE_PLANES)):
+        """Context.renderShading for the scene's own camera and frame size (c2rt_host_render_shading)."""
+        s = self.scene.settings
+        pl, out = _new_shade_planes(planes, (s.frame_height, s.frame_width))
+        self.ctx._check(self._lib.c2rt_host_render_shading(self.ctx.handle, self.scene._h, C.byref(pl)))
         return out
 
 

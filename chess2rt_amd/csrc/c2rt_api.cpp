@@ -1539,6 +1539,148 @@ int c2rt_render_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_ren
     return C2RT_OK;
 }
 
+/* ---- shading planes: the terms of a sample's colour (c2rt_shade_planes.hip) ---------------------------------------- */
+
+static bool any_shade_plane(const c2rt_shade_planes *pl) { return pl->node || pl->albedo || pl->light || pl->specular || pl->visible || pl->rgb; }
+
+/* the planes' own refusals, behind the frame call's or the ray call's */
+static int check_shade_planes(c2rt_ctx *ctx, const c2rt_shade_planes *planes)
+{
+    if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
+    if (!any_shade_plane(planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all six pointers of c2rt_shade_planes are null");
+    return C2RT_OK;
+}
+
+/* c2rt_render_hits' refusals in its order and wording, with these planes in the place of the hit planes */
+static int check_shading_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_shade_planes *planes)
+{
+    if (const int st = check_frame_args(ctx, cam, opts)) return st;
+    if (const int st = check_shade_planes(ctx, planes)) return st;
+    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: a pixel's terms are one ray's, a lens has many per pixel");
+    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: a pixel's terms are one ray's, a stereo camera has two per pixel");
+    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the shading planes do not count rays");
+    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
+    return C2RT_OK;
+}
+
+/* The six planes in the order of the struct's members, as bytes: what the host variants stage and copy */
+constexpr int kShadePlanes = 6;
+constexpr size_t kShadeBytes[kShadePlanes] = {4, 12, 12, 12, 4, 12}; /* 56 B per sample */
+static void shade_plane_ptrs(const c2rt_shade_planes *pl, char *out[kShadePlanes])
+{
+    out[0] = reinterpret_cast<char *>(pl->node);
+    out[1] = reinterpret_cast<char *>(pl->albedo);
+    out[2] = reinterpret_cast<char *>(pl->light);
+    out[3] = reinterpret_cast<char *>(pl->specular);
+    out[4] = reinterpret_cast<char *>(pl->visible);
+    out[5] = reinterpret_cast<char *>(pl->rgb);
+}
+/* the device planes of one chunk of chunk_n samples at `base`, only those asked for; returns the bytes they take */
+static size_t shade_staging(char *const host[kShadePlanes], size_t chunk_n, char *base, size_t off[kShadePlanes], c2rt_shade_planes *d)
+{
+    size_t bytes = 0;
+    for (int k = 0; k < kShadePlanes; ++k) {
+        off[k] = bytes;
+        if (host[k]) bytes += align256(chunk_n * kShadeBytes[k]);
+    }
+    if (d) {
+        const auto dev = [&](int k) { return host[k] ? base + off[k] : nullptr; };
+        d->node = reinterpret_cast<int32_t *>(dev(0));
+        d->albedo = reinterpret_cast<float *>(dev(1));
+        d->light = reinterpret_cast<float *>(dev(2));
+        d->specular = reinterpret_cast<float *>(dev(3));
+        d->visible = reinterpret_cast<uint32_t *>(dev(4));
+        d->rgb = reinterpret_cast<float *>(dev(5));
+    }
+    return bytes;
+}
+
+int c2rt_render_shading_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                               const c2rt_shade_planes *planes_dev, void *hip_stream)
+{
+    if (const int st = check_shading_args(ctx, cam, opts, planes_dev)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    if (p.local_rows == 0) return C2RT_OK;
+    const int e = launch_shade_planes(p, ctx->plan.csg_levels, *planes_dev, 0, p.local_rows, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "shading plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+/* Host variant: c2rt_render_hits' chunks of whole rows, at most kQueryChunk pixels each, plane after plane for the
+ * chunk size and only for the planes asked for — 56 B per pixel, 14 MiB at most.  Each chunk ends with a stream sync. */
+int c2rt_render_shading(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_shade_planes *planes_host)
+{
+    if (const int st = check_shading_args(ctx, cam, opts, planes_host)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    const uint32_t rows = p.local_rows, width = p.width;
+    if (rows == 0) return C2RT_OK;
+    uint32_t chunk_rows = (uint32_t)(kQueryChunk / width); /* width <= 2^16: at least four rows */
+    if (chunk_rows > rows) chunk_rows = rows;
+    char *host[kShadePlanes];
+    shade_plane_ptrs(planes_host, host);
+    size_t off[kShadePlanes];
+    if (const int st = ensure_staging(ctx, shade_staging(host, (size_t)chunk_rows * width, nullptr, off, nullptr))) return st;
+    char *base = reinterpret_cast<char *>(ctx->frame);
+    c2rt_shade_planes d;
+    shade_staging(host, (size_t)chunk_rows * width, base, off, &d);
+    for (uint32_t r0 = 0; r0 < rows; r0 += chunk_rows) {
+        const uint32_t m = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
+        const int e = launch_shade_planes(p, ctx->plan.csg_levels, d, r0, m, ctx->stream);
+        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "shading plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+        const size_t first = (size_t)r0 * width, px = (size_t)m * width;
+        for (int k = 0; k < kShadePlanes; ++k)
+            if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k] + first * kShadeBytes[k], base + off[k], px * kShadeBytes[k], hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return C2RT_OK;
+}
+
+int c2rt_trace_rays_shading_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, const c2rt_shade_planes *planes_dev, void *hip_stream)
+{
+    if (const int st = check_query_args(ctx, rays_dev, n, true)) return st < 0 ? C2RT_OK : st;
+    if (const int st = check_shade_planes(ctx, planes_dev)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    query_params(ctx, p);
+    const int e = launch_trace_rays_shade(p, ctx->plan.csg_levels, rays_dev, n, *planes_dev, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "shading plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+/* Host variant: c2rt_trace_rays' staging, [rays | planes asked for] for chunks of at most kQueryChunk rays */
+int c2rt_trace_rays_shading(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const c2rt_shade_planes *planes_host)
+{
+    if (const int st = check_query_args(ctx, rays, n, true)) return st < 0 ? C2RT_OK : st;
+    if (const int st = check_shade_planes(ctx, planes_host)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const uint64_t chunk = n < kQueryChunk ? n : kQueryChunk;
+    const size_t off_planes = align256(chunk * sizeof(c2rt_ray));
+    char *host[kShadePlanes];
+    shade_plane_ptrs(planes_host, host);
+    size_t off[kShadePlanes];
+    if (const int st = ensure_staging(ctx, off_planes + shade_staging(host, chunk, nullptr, off, nullptr))) return st;
+    char *base = reinterpret_cast<char *>(ctx->frame);
+    c2rt_ray *rays_dev = reinterpret_cast<c2rt_ray *>(base);
+    c2rt_shade_planes d;
+    shade_staging(host, chunk, base + off_planes, off, &d);
+    RenderParams p;
+    query_params(ctx, p);
+    for (uint64_t i = 0; i < n; i += chunk) {
+        const uint64_t m = n - i < chunk ? n - i : chunk;
+        HIP_TRY(ctx, hipMemcpyAsync(rays_dev, rays + i, m * sizeof(c2rt_ray), hipMemcpyHostToDevice, ctx->stream));
+        const int e = launch_trace_rays_shade(p, ctx->plan.csg_levels, rays_dev, m, d, ctx->stream);
+        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "shading plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+        for (int k = 0; k < kShadePlanes; ++k)
+            if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k] + i * kShadeBytes[k], base + off_planes + off[k], m * kShadeBytes[k], hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return C2RT_OK;
+}
+
 /* ---- hit layers: every surface along a ray or pixel (c2rt_layers.hip) --------------------------------------------- */
 
 /* the refusals the two faces share, behind the single-hit call's own; out_ok: some output is there */

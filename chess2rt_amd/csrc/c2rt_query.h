@@ -1,5 +1,5 @@
 /*
- * c2rt_query.h — launch interface of the query kernels (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip, c2rt_adaptive.hip), shared
+ * c2rt_query.h — launch interface of the query kernels (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip, c2rt_shade_planes.hip, c2rt_adaptive.hip), shared
  * by those files and c2rt_api.cpp.  A header of its own: c2rt_device.h is a prerequisite of every frame-kernel object,
  * and query work should not rebuild them.  All return hipError_t as int; every pointer is a device pointer.
  *
@@ -33,6 +33,10 @@ int launch_trace_ray_layers(const RenderParams &p, int csg_levels, const c2rt_ra
                             c2rt_ray_hit *hits, float *rgb, uint8_t *count, void *stream);
 int launch_hit_layers(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint8_t *count, uint32_t max_layers, size_t layer_px,
                       uint32_t row0, uint32_t rows, void *stream);
+/* Shading planes (c2rt_render_shading*, c2rt_trace_rays_shading*; c2rt_shade_planes.hip): the hit planes' rows, or the
+ * ray query's rays, with the terms of the closest node's shade() one plane each; at least one plane non-null */
+int launch_shade_planes(const RenderParams &p, int csg_levels, const c2rt_shade_planes &out, uint32_t row0, uint32_t rows, void *stream);
+int launch_trace_rays_shade(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, const c2rt_shade_planes &out, void *stream);
 /* Adaptive anti-aliasing (c2rt_render_frame[s]_adaptive*): the flag images needs_aa[i][y][x] of n_frames whole one-tap
  * frames side by side, then the flagged pixels of the whole frame `p` describes (no strips) from their one-tap to their
  * five-tap value, in place; launch_aa_refine_batch: the same for the n_frames frames whose blocks are at table_dev (p0:

@@ -701,6 +701,53 @@ int c2rt_render_hit_layers_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, c
 int c2rt_render_hit_layers(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, uint32_t max_layers,
                            const c2rt_hit_planes *planes_host, uint8_t *count_host);
 
+/* ---- shading planes: the terms of a sample's colour, one plane each --------- */
+
+/* One plane per term of Lambert.shade / Phong.shade (rt/shader.d:67-105, 197-250) of ONE sample.  Every pointer is
+ * nullable; at least one must be given.  A plane that is null is neither computed nor stored. */
+typedef struct c2rt_shade_planes {      /* 48 bytes */
+    int32_t  *node;      /* [..]     closest node, -1: no hit (the hit planes' `node`)                                   */
+    float    *albedo;    /* [..][3]  diffuseColor: texture.getTexColor(u, v) or shader.color        shader.d:74-76,202-203 */
+    float    *light;     /* [..][3]  lightContrib when shade returns: ambient + every light's avgColor  shader.d:78-103,205-243 */
+    float    *specular;  /* [..][3]  Phong's `specular` when shade returns (shader.d:207,244); +0,+0,+0 for a Lambert node */
+    uint32_t *visible;   /* [..]     bit l (l < 32): light l passed `intensity() != 0 && testVisibility(p + N*1e-6, lightPos)` */
+    float    *rgb;       /* [..][3]  shade's return value = the hit planes' `rgb` = the C2RT_TAPS_1 frame                  */
+} c2rt_shade_planes;
+
+/* What lies between the hit planes and the colour: the three locals of the reference's `shade` of the closest node at
+ * its `return`, in fp32, computed by the statements the frames execute, and the lights that passed the shadow test.
+ *   - Camera calls: the sample is the one c2rt_render_hits traces for pixel (x, y); planes are row-major
+ *     [local_rows][W], strips as there.  Ray calls: the sample is ray i of c2rt_trace_rays, `dir` exactly as given;
+ *     planes are [n].
+ *   - rgb is albedo * light for a Lambert node and (albedo * light) + specular for a Phong node — the reference's own
+ *     last statement — and has the bits of the hit planes' `rgb`, hence of the one-tap frame: on every hit the four
+ *     colour planes satisfy that identity BIT FOR BIT in IEEE fp32 without contraction.
+ *   - visible: bit l is set when light l < 32 passed the condition above.  A dark light's bit is clear and no shadow
+ *     ray is cast for it, as in the reference; a visible light with cosTheta <= 0 has its bit set and adds zero.
+ *     Lights 32 and beyond still add to `light` and `specular`; they have no bit.
+ *   - A miss holds node -1, visible 0 and +0 in every float (rgb: the environment's black, rt/environment.d:7-10).
+ *   - `node` and `albedo` alone cast no shadow ray and evaluate no light; the texture is read only when `albedo` or
+ *     `rgb` is asked for.  What is written to one plane never depends on which others are asked for.
+ *
+ * Statuses, all decided before anything is enqueued or written.  Camera calls, in c2rt_render_hits' order and wording:
+ * those of a frame call; null `planes`, or all six pointers null: C2RT_ERR_INVALID_ARG, each with its own message;
+ * C2RT_ERR_UNSUPPORTED naming "depth of field", "stereo", "count_rays", "prepass_bucket".  Ray calls, in
+ * c2rt_trace_rays' order: null context; n == 0 is C2RT_OK whatever else is passed; null `rays`: C2RT_ERR_INVALID_ARG;
+ * n > C2RT_MAX_RAYS: C2RT_ERR_LIMIT; no scene: C2RT_ERR_NO_SCENE; then null `planes`, or all six pointers null:
+ * C2RT_ERR_INVALID_ARG.
+ *
+ * The _device variants take device pointers and enqueue ONE kernel on `hip_stream`: no host sync, no event, no scratch
+ * slot, nothing kept of the stream; on a multi-device context, the lead device.  The host variants go through the
+ * context's staging buffer on the context's own stream in chunks of whole rows (or rays) of at most 2^18 samples —
+ * at most 56 B per sample of planes — and block until the planes are there. */
+int c2rt_render_shading_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                               const c2rt_shade_planes *planes_dev, void *hip_stream);
+int c2rt_render_shading(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                        const c2rt_shade_planes *planes_host);
+int c2rt_trace_rays_shading_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n,
+                                   const c2rt_shade_planes *planes_dev, void *hip_stream);
+int c2rt_trace_rays_shading(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const c2rt_shade_planes *planes_host);
+
 /* ---- adaptive anti-aliasing: refine only the pixels the edge test flags ----- */
 
 /* tooDifferent's default threshold — rt/color.d:18 */

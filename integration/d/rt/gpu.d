@@ -161,6 +161,22 @@ extern (C) nothrow @nogc
                                       const c2rt_hit_planes* planes_dev, ubyte* count_dev, void* hip_stream);
     int c2rt_render_hit_layers(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, uint max_layers,
                                const c2rt_hit_planes* planes_host, ubyte* count_host);
+    /// shading planes: the terms of the closest node's shade() of one sample, one nullable plane each; on a hit
+    /// rgb == albedo * light (+ specular for Phong) bit for bit, and rgb / node are the hit planes'
+    struct c2rt_shade_planes
+    {
+        int* node;                  /// closest node, -1: no hit
+        float* albedo, light;       /// [3] per sample: diffuseColor, lightContrib
+        float* specular;            /// [3] per sample: Phong's specular; +0 for a Lambert node
+        uint* visible;              /// bit l: light l < 32 passed intensity() != 0 && testVisibility
+        float* rgb;                 /// [3] per sample: shade's return value
+    }
+    int c2rt_render_shading_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*,
+                                   const c2rt_shade_planes* planes_dev, void* hip_stream);
+    int c2rt_render_shading(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_shade_planes* planes_host);
+    int c2rt_trace_rays_shading_device(c2rt_ctx*, const c2rt_ray* rays_dev, ulong n, const c2rt_shade_planes* planes_dev,
+                                       void* hip_stream);
+    int c2rt_trace_rays_shading(c2rt_ctx*, const c2rt_ray* rays, ulong n, const c2rt_shade_planes* planes_host);
     enum float C2RT_AA_THRESHOLD_REF = 0.1f; /// tooDifferent's default
     int c2rt_render_frame_adaptive_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
                                           float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
