@@ -115,9 +115,7 @@ DEV void aa_refine_body(const RenderParams &P, KArgs K, float *__restrict__ fram
             Surf surf;
             Mat mat;
             const int closest = trace_closest<LEVELS>(cx, o, d, false, best, surf, mat);
-            F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
-            uint32_t shadow_rays = 0;
-            if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
+            const F3 c = sample_colour<LEVELS, MLC>(P, cx, closest, mat, d, surf);
             float *slot = colour + (pl * 4 + (t - 1)) * 3;
             slot[0] = c.r;
             slot[1] = c.g;
@@ -147,16 +145,6 @@ aa_refine_kernel(const RenderParams P, float *__restrict__ frame, const uint8_t 
     aa_refine_body<LEVELS, MLC>(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), frame, needs_aa, tiles_x);
 }
 
-/* batch_block of c2rt_kernels.hip, restated (that file's objects stay as they are): block blockIdx.y of the table
- * through a constant-address-space pointer; the empty asm keeps the optimiser from folding the casts back to the global
- * pointer, loads through which would be vector loads. */
-DEV KArgs batch_block(const RenderParams *table)
-{
-    KArgs K = (KArgs)table + blockIdx.y;
-    asm volatile("" : "+s"(K));
-    return K;
-}
-
 /* The same over a batch: blockIdx.y = frame, blockIdx.x = tile.  frame_px = the pixels of one frame. */
 template <int LEVELS, bool MLC>
 __global__ void __launch_bounds__(kWave) C2RT_WAVES_QUERY(LEVELS, MLC)
@@ -169,20 +157,19 @@ aa_refine_batch_kernel(const RenderParams *table, const uint8_t *__restrict__ ma
 
 /* table_dev null: the single-frame kernel with `p` as its argument, into `frame`; otherwise the n_frames blocks at
  * table_dev, of which `p` is any one's host copy (the grid, the stack and the instance are the same for all of them) */
-template <int LEVELS>
-int launch_aa_refine_level(const RenderParams &p, const RenderParams *table_dev, uint32_t n_frames, float *frame, const uint8_t *needs_aa,
-                           hipStream_t s)
+int launch_refine(const RenderParams &p, int csg_levels, const RenderParams *table_dev, uint32_t n_frames, float *frame, const uint8_t *needs_aa,
+                  hipStream_t s)
 {
-    const uint32_t tiles_x = (p.width + kTileW - 1) / kTileW, tiles_y = (p.height + kTileH - 1) / kTileH;
-    const dim3 grid(tiles_x * tiles_y, n_frames), block(kWave); /* at most 2^16 x 2^16 pixels / 64 */
-    const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry + kAaColourBytes + kAaListBytes;
-    const size_t frame_px = (size_t)p.width * p.height;
-    if (table_dev) {
-        if (p.n_lights > 1) hipLaunchKernelGGL((aa_refine_batch_kernel<LEVELS, true>), grid, block, lds, s, table_dev, needs_aa, frame_px, tiles_x);
-        else hipLaunchKernelGGL((aa_refine_batch_kernel<LEVELS, false>), grid, block, lds, s, table_dev, needs_aa, frame_px, tiles_x);
-    } else if (p.n_lights > 1) hipLaunchKernelGGL((aa_refine_kernel<LEVELS, true>), grid, block, lds, s, p, frame, needs_aa, tiles_x);
-    else hipLaunchKernelGGL((aa_refine_kernel<LEVELS, false>), grid, block, lds, s, p, frame, needs_aa, tiles_x);
-    return (int)hipGetLastError();
+    static_assert(kTileW == kQueryTileW && kTileH == kQueryTileH, "the refinement walks the frames' tiles");
+    uint32_t tiles_x;
+    const dim3 grid = tile_grid(p, p.height, tiles_x, n_frames);
+    const size_t lds = stack_lds(p) + kAaColourBytes + kAaListBytes, frame_px = (size_t)p.width * p.height;
+    return for_csg_levels(csg_levels, [&](auto L) {
+        constexpr int LEVELS = decltype(L)::value;
+        if (table_dev)
+            return launch_query(p, aa_refine_batch_kernel<LEVELS, true>, aa_refine_batch_kernel<LEVELS, false>, grid, lds, s, table_dev, needs_aa, frame_px, tiles_x);
+        return launch_query(p, aa_refine_kernel<LEVELS, true>, aa_refine_kernel<LEVELS, false>, grid, lds, s, p, frame, needs_aa, tiles_x);
+    });
 }
 
 } // namespace
@@ -203,9 +190,8 @@ int launch_aa_detect(const float *frames, uint8_t *needs_aa, uint32_t width, uin
  * no culling, no ground node; no strips) from their one-tap to their five-tap value, in place. */
 int launch_aa_refine(const RenderParams &p, int csg_levels, float *frame, const uint8_t *needs_aa, void *stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (!p.width || !p.height || !frame || !needs_aa) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) { return launch_aa_refine_level<decltype(L)::value>(p, nullptr, 1, frame, needs_aa, s); });
+    return launch_refine(p, csg_levels, nullptr, 1, frame, needs_aa, static_cast<hipStream_t>(stream));
 }
 
 /* The same for the n_frames frames of a batch in one launch: table_dev holds their blocks (p0: any one's host copy),
@@ -213,9 +199,8 @@ int launch_aa_refine(const RenderParams &p, int csg_levels, float *frame, const 
 int launch_aa_refine_batch(const RenderParams &p0, int csg_levels, const RenderParams *table_dev, uint32_t n_frames, const uint8_t *needs_aa,
                            void *stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
     if (!p0.width || !p0.height || !table_dev || !n_frames || n_frames > C2RT_MAX_BATCH_FRAMES || !needs_aa) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) { return launch_aa_refine_level<decltype(L)::value>(p0, table_dev, n_frames, nullptr, needs_aa, s); });
+    return launch_refine(p0, csg_levels, table_dev, n_frames, nullptr, needs_aa, static_cast<hipStream_t>(stream));
 }
 
 } // namespace c2rt

@@ -1395,66 +1395,165 @@ int c2rt_test_visibility_device(c2rt_ctx *ctx, const c2rt_segment *seg_dev, uint
     return C2RT_OK;
 }
 
-/* Host variants: chunks of at most kQueryChunk records through ONE staging allocation (the context's, shared with the
- * host-output frames: calls on a context are serialised) laid out [inputs | hits | colours] for the chunk size and
- * only for the outputs asked for — 12 MiB + 20 MiB + 3 MiB at most, whatever n is.  Copies from and to pageable
- * memory are staged by the runtime; each chunk ends with a stream sync, so the call blocks as documented. */
+/* Host variants: chunks of at most kQueryChunk samples through ONE staging allocation (the context's, shared with the
+ * host-output frames: calls on a context are serialised) laid out [inputs | output after output] for the chunk size and
+ * only for the outputs asked for, 256-byte aligned — for c2rt_trace_rays 12 MiB + 20 MiB + 3 MiB at most, whatever n
+ * is.  Copies from and to pageable memory are staged by the runtime; each chunk ends with a stream sync, so the call
+ * blocks as documented. */
 constexpr uint64_t kQueryChunk = 1u << 18;
 static size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
 
-int c2rt_trace_rays(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb)
+extern "C++" { /* templates */
+
+/* A plane struct as the host code sees it: nothing but pointers, member k to samples of v[k] bytes */
+template <class S> struct PlaneBytes;
+template <> struct PlaneBytes<c2rt_hit_planes> { static constexpr size_t v[] = {4, 4, 8, 16, 24, 24, 12}; };  /* 92 B per sample */
+template <> struct PlaneBytes<c2rt_shade_planes> { static constexpr size_t v[] = {4, 12, 12, 12, 4, 12}; };   /* 56 B per sample */
+template <class S> constexpr int kPlanes = (int)(sizeof PlaneBytes<S>::v / sizeof(size_t));
+static_assert(sizeof(c2rt_hit_planes) == kPlanes<c2rt_hit_planes> * sizeof(void *) &&
+              sizeof(c2rt_shade_planes) == kPlanes<c2rt_shade_planes> * sizeof(void *), "the plane structs are arrays of pointers");
+
+/* What a host variant stages: its outputs in staging order.  An output is `layers` slices (layer-major on both sides)
+ * of samples of `bytes` bytes each; `host` null: not asked for, takes no room.  lay_out places them. */
+struct Staging {
+    struct Output {
+        char *host;
+        size_t bytes;
+        uint32_t layers;
+        char *dev;
+    };
+    Output out[8];
+    int n = 0;
+
+    void add(void *host, size_t bytes, uint32_t layers = 1) { out[n++] = {static_cast<char *>(host), bytes, layers, nullptr}; }
+    template <class S>
+    void add_planes(const S &planes_host, uint32_t layers = 1)
+    {
+        char *host[kPlanes<S>];
+        std::memcpy(host, &planes_host, sizeof host);
+        for (int k = 0; k < kPlanes<S>; ++k) add(host[k], PlaneBytes<S>::v[k], layers);
+    }
+    /* the device-side struct of the planes added as outputs first, first + 1, ... */
+    template <class S>
+    S planes(int first = 0) const
+    {
+        char *dev[kPlanes<S>];
+        for (int k = 0; k < kPlanes<S>; ++k) dev[k] = out[first + k].dev;
+        S d;
+        std::memcpy(&d, dev, sizeof d);
+        return d;
+    }
+    template <class T>
+    T *dev(int k) const { return reinterpret_cast<T *>(out[k].dev); }
+};
+
+/* The staging allocation for `in_bytes` of inputs and one chunk of `chunk` samples of every output asked for */
+static int lay_out(c2rt_ctx *ctx, Staging &outs, size_t in_bytes, size_t chunk)
 {
-    if (const int st = check_query_args(ctx, rays, n, hits || rgb)) return st < 0 ? C2RT_OK : st;
+    size_t off[8], at = align256(in_bytes), end = in_bytes;
+    for (int k = 0; k < outs.n; ++k) {
+        off[k] = at;
+        if (!outs.out[k].host) continue;
+        end = at + chunk * outs.out[k].layers * outs.out[k].bytes;
+        at = align256(end);
+    }
+    if (const int e = ensure_staging(ctx, end)) return e;
+    for (int k = 0; k < outs.n; ++k) outs.out[k].dev = outs.out[k].host ? reinterpret_cast<char *>(ctx->frame) + off[k] : nullptr;
+    return C2RT_OK;
+}
+
+/* Samples [first, first + m) of every layer of every output from the chunk's staging to their place in the caller's
+ * arrays: layers host_stride samples apart there, `chunk` samples apart in the staging */
+static int copy_back(c2rt_ctx *ctx, const Staging &outs, size_t first, size_t m, size_t host_stride, size_t chunk)
+{
+    for (int k = 0; k < outs.n; ++k) {
+        const Staging::Output &o = outs.out[k];
+        for (uint32_t l = 0; o.host && l < o.layers; ++l)
+            HIP_TRY(ctx, hipMemcpyAsync(o.host + (l * host_stride + first) * o.bytes, o.dev + l * chunk * o.bytes, m * o.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return C2RT_OK;
+}
+
+/* The ray faces: n input records (c2rt_ray, c2rt_segment) in chunks of at most `cap`.  launch(p, records_dev, m, chunk)
+ * enqueues the `what` kernel over m staged records, the layer stride of its outputs being `chunk`. */
+template <class Launch>
+static int ray_chunks(c2rt_ctx *ctx, const void *in, uint64_t n, uint64_t cap, Staging &outs, const char *what, Launch launch)
+{
+    static_assert(sizeof(c2rt_ray) == sizeof(c2rt_segment), "one input record size");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t chunk = n < kQueryChunk ? n : kQueryChunk;
-    const size_t off_hits = align256(chunk * sizeof(c2rt_ray));
-    const size_t off_rgb = off_hits + (hits ? align256(chunk * sizeof(c2rt_ray_hit)) : 0);
-    const size_t bytes = off_rgb + (rgb ? chunk * 3 * sizeof(float) : 0);
-    if (const int st = ensure_staging(ctx, bytes)) return st;
-    char *base = reinterpret_cast<char *>(ctx->frame);
-    c2rt_ray *rays_dev = reinterpret_cast<c2rt_ray *>(base);
-    c2rt_ray_hit *hits_dev = hits ? reinterpret_cast<c2rt_ray_hit *>(base + off_hits) : nullptr;
-    float *rgb_dev = rgb ? reinterpret_cast<float *>(base + off_rgb) : nullptr;
+    const uint64_t chunk = n < cap ? n : cap;
+    if (const int e = lay_out(ctx, outs, chunk * sizeof(c2rt_ray), chunk)) return e;
+    c2rt_ray *in_dev = reinterpret_cast<c2rt_ray *>(ctx->frame);
     RenderParams p;
     query_params(ctx, p);
     for (uint64_t i = 0; i < n; i += chunk) {
         const uint64_t m = n - i < chunk ? n - i : chunk;
-        HIP_TRY(ctx, hipMemcpyAsync(rays_dev, rays + i, m * sizeof(c2rt_ray), hipMemcpyHostToDevice, ctx->stream));
-        const int e = launch_trace_rays(p, ctx->plan.csg_levels, rays_dev, m, hits_dev, rgb_dev, ctx->stream);
-        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "ray query kernel launch: %s", hipGetErrorString((hipError_t)e));
-        if (hits) HIP_TRY(ctx, hipMemcpyAsync(hits + i, hits_dev, m * sizeof(c2rt_ray_hit), hipMemcpyDeviceToHost, ctx->stream));
-        if (rgb) HIP_TRY(ctx, hipMemcpyAsync(rgb + 3 * i, rgb_dev, m * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(in_dev, static_cast<const c2rt_ray *>(in) + i, m * sizeof(c2rt_ray), hipMemcpyHostToDevice, ctx->stream));
+        const int e = launch(p, in_dev, m, chunk);
+        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "%s kernel launch: %s", what, hipGetErrorString((hipError_t)e));
+        if (const int st = copy_back(ctx, outs, i, m, n, chunk)) return st;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     return C2RT_OK;
+}
+
+/* The frame faces: the local rows of the frame `p` describes in chunks of whole rows, at most kQueryChunk / layers
+ * pixels each but one row at least (width <= 2^16: with one layer that is four rows or more).  launch(r0, m, chunk_px)
+ * enqueues the `what` kernel over rows [r0, r0 + m) into the staging, whose layers are chunk_px pixels apart. */
+template <class Launch>
+static int row_chunks(c2rt_ctx *ctx, const RenderParams &p, uint32_t layers, Staging &outs, const char *what, Launch launch)
+{
+    const uint32_t rows = p.local_rows, width = p.width;
+    uint32_t chunk_rows = (uint32_t)(kQueryChunk / layers / width);
+    if (chunk_rows == 0) chunk_rows = 1;
+    if (chunk_rows > rows) chunk_rows = rows;
+    const size_t chunk_px = (size_t)chunk_rows * width;
+    if (const int e = lay_out(ctx, outs, 0, chunk_px)) return e;
+    for (uint32_t r0 = 0; r0 < rows; r0 += chunk_rows) {
+        const uint32_t m = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
+        const int e = launch(r0, m, chunk_px);
+        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "%s kernel launch: %s", what, hipGetErrorString((hipError_t)e));
+        if (const int st = copy_back(ctx, outs, (size_t)r0 * width, (size_t)m * width, (size_t)rows * width, chunk_px)) return st;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return C2RT_OK;
+}
+
+} /* extern "C++" */
+
+int c2rt_trace_rays(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb)
+{
+    if (const int st = check_query_args(ctx, rays, n, hits || rgb)) return st < 0 ? C2RT_OK : st;
+    Staging outs;
+    outs.add(hits, sizeof(c2rt_ray_hit));
+    outs.add(rgb, 3 * sizeof(float));
+    return ray_chunks(ctx, rays, n, kQueryChunk, outs, "ray query", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t m, uint64_t) {
+        return launch_trace_rays(p, ctx->plan.csg_levels, rays_dev, m, outs.dev<c2rt_ray_hit>(0), outs.dev<float>(1), ctx->stream);
+    });
 }
 
 int c2rt_test_visibility(c2rt_ctx *ctx, const c2rt_segment *seg, uint64_t n, uint8_t *visible)
 {
     if (const int st = check_query_args(ctx, seg, n, visible != nullptr)) return st < 0 ? C2RT_OK : st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t chunk = n < kQueryChunk ? n : kQueryChunk;
-    const size_t off_vis = align256(chunk * sizeof(c2rt_segment));
-    if (const int st = ensure_staging(ctx, off_vis + chunk)) return st;
-    char *base = reinterpret_cast<char *>(ctx->frame);
-    c2rt_segment *seg_dev = reinterpret_cast<c2rt_segment *>(base);
-    uint8_t *vis_dev = reinterpret_cast<uint8_t *>(base + off_vis);
-    RenderParams p;
-    query_params(ctx, p);
-    for (uint64_t i = 0; i < n; i += chunk) {
-        const uint64_t m = n - i < chunk ? n - i : chunk;
-        HIP_TRY(ctx, hipMemcpyAsync(seg_dev, seg + i, m * sizeof(c2rt_segment), hipMemcpyHostToDevice, ctx->stream));
-        const int e = launch_test_visibility(p, ctx->plan.csg_levels, seg_dev, m, vis_dev, ctx->stream);
-        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "visibility query kernel launch: %s", hipGetErrorString((hipError_t)e));
-        HIP_TRY(ctx, hipMemcpyAsync(visible + i, vis_dev, m, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return C2RT_OK;
+    Staging outs;
+    outs.add(visible, 1);
+    return ray_chunks(ctx, seg, n, kQueryChunk, outs, "visibility query", [&](const RenderParams &p, const c2rt_ray *seg_dev, uint64_t m, uint64_t) {
+        return launch_test_visibility(p, ctx->plan.csg_levels, reinterpret_cast<const c2rt_segment *>(seg_dev), m, outs.dev<uint8_t>(0), ctx->stream);
+    });
 }
 
 /* ---- hit planes of a camera frame (c2rt_hit_planes.hip) ---------------------------------------------------------- */
 
-static bool any_plane(const c2rt_hit_planes *pl) { return pl->node || pl->leaf || pl->dist || pl->uv || pl->p || pl->normal || pl->rgb; }
+/* The refusals of the modes in which a pixel is not one ray, in the documented order; `holds`: what a pixel holds in the
+ * call ("record is", "terms are"), `planes`: which planes it fills ("hit", "shading") */
+static int check_one_ray_per_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const char *holds, const char *planes)
+{
+    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: a pixel's %s one ray's, a lens has many per pixel", holds);
+    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: a pixel's %s one ray's, a stereo camera has two per pixel", holds);
+    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the %s planes do not count rays", planes);
+    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
+    return C2RT_OK;
+}
 
 /* the refusals of both entry points, in the documented order: a frame call's, then the planes', then the modes in which
  * a pixel is not one ray */
@@ -1462,12 +1561,8 @@ static int check_hit_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2r
 {
     if (const int st = check_frame_args(ctx, cam, opts)) return st;
     if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
-    if (!any_plane(planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all seven pointers of c2rt_hit_planes are null");
-    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: a pixel's record is one ray's, a lens has many per pixel");
-    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: a pixel's record is one ray's, a stereo camera has two per pixel");
-    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the hit planes do not count rays");
-    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
-    return C2RT_OK;
+    if (!any_plane(*planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all seven pointers of c2rt_hit_planes are null");
+    return check_one_ray_per_pixel(ctx, cam, opts, "record is", "hit");
 }
 
 /* The frame's parameter block for its camera, strips and size, with the query settings on top (query_params): exact::
@@ -1491,63 +1586,29 @@ int c2rt_render_hits_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c
     return C2RT_OK;
 }
 
-/* Host variant: chunks of whole rows, at most kQueryChunk pixels each, through the context's staging allocation laid
- * out plane after plane for the chunk size and only for the planes asked for — 92 B per pixel, 23 MiB at most,
- * whatever the frame size.  Each chunk ends with a stream sync, so the call blocks as documented. */
+/* Host variant: chunks of whole rows, at most kQueryChunk pixels each (row_chunks), plane after plane for the chunk size
+ * and only for the planes asked for — 92 B per pixel, 23 MiB at most, whatever the frame size. */
 int c2rt_render_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_hit_planes *planes_host)
 {
     if (const int st = check_hit_args(ctx, cam, opts, planes_host)) return st;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     hit_params(ctx, cam, opts, p);
-    const uint32_t rows = p.local_rows, width = p.width;
-    if (rows == 0) return C2RT_OK;
-    uint32_t chunk_rows = (uint32_t)(kQueryChunk / width); /* width <= 2^16: at least four rows */
-    if (chunk_rows > rows) chunk_rows = rows;
-    const size_t chunk_px = (size_t)chunk_rows * width;
-    /* bytes per pixel of the seven planes, in the order of the struct's members */
-    char *const host[7] = {reinterpret_cast<char *>(planes_host->node), reinterpret_cast<char *>(planes_host->leaf),
-                           reinterpret_cast<char *>(planes_host->dist), reinterpret_cast<char *>(planes_host->uv),
-                           reinterpret_cast<char *>(planes_host->p), reinterpret_cast<char *>(planes_host->normal),
-                           reinterpret_cast<char *>(planes_host->rgb)};
-    const size_t px_bytes[7] = {4, 4, 8, 16, 24, 24, 12};
-    size_t off[7], bytes = 0;
-    for (int k = 0; k < 7; ++k) {
-        off[k] = bytes;
-        if (host[k]) bytes += align256(chunk_px * px_bytes[k]);
-    }
-    if (const int st = ensure_staging(ctx, bytes)) return st;
-    char *base = reinterpret_cast<char *>(ctx->frame);
-    const auto dev = [&](int k) { return host[k] ? base + off[k] : nullptr; };
-    c2rt_hit_planes d;
-    d.node = reinterpret_cast<int32_t *>(dev(0));
-    d.leaf = reinterpret_cast<int32_t *>(dev(1));
-    d.dist = reinterpret_cast<double *>(dev(2));
-    d.uv = reinterpret_cast<double *>(dev(3));
-    d.p = reinterpret_cast<double *>(dev(4));
-    d.normal = reinterpret_cast<double *>(dev(5));
-    d.rgb = reinterpret_cast<float *>(dev(6));
-    for (uint32_t r0 = 0; r0 < rows; r0 += chunk_rows) {
-        const uint32_t m = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
-        const int e = launch_hit_planes(p, ctx->plan.csg_levels, d, r0, m, ctx->stream);
-        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "hit plane kernel launch: %s", hipGetErrorString((hipError_t)e));
-        const size_t first = (size_t)r0 * width, px = (size_t)m * width;
-        for (int k = 0; k < 7; ++k)
-            if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k] + first * px_bytes[k], base + off[k], px * px_bytes[k], hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return C2RT_OK;
+    if (p.local_rows == 0) return C2RT_OK;
+    Staging outs;
+    outs.add_planes(*planes_host);
+    return row_chunks(ctx, p, 1, outs, "hit plane", [&](uint32_t r0, uint32_t m, size_t) {
+        return launch_hit_planes(p, ctx->plan.csg_levels, outs.planes<c2rt_hit_planes>(), r0, m, ctx->stream);
+    });
 }
 
 /* ---- shading planes: the terms of a sample's colour (c2rt_shade_planes.hip) ---------------------------------------- */
-
-static bool any_shade_plane(const c2rt_shade_planes *pl) { return pl->node || pl->albedo || pl->light || pl->specular || pl->visible || pl->rgb; }
 
 /* the planes' own refusals, behind the frame call's or the ray call's */
 static int check_shade_planes(c2rt_ctx *ctx, const c2rt_shade_planes *planes)
 {
     if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
-    if (!any_shade_plane(planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all six pointers of c2rt_shade_planes are null");
+    if (!any_plane(*planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all six pointers of c2rt_shade_planes are null");
     return C2RT_OK;
 }
 
@@ -1556,43 +1617,7 @@ static int check_shading_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const
 {
     if (const int st = check_frame_args(ctx, cam, opts)) return st;
     if (const int st = check_shade_planes(ctx, planes)) return st;
-    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: a pixel's terms are one ray's, a lens has many per pixel");
-    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: a pixel's terms are one ray's, a stereo camera has two per pixel");
-    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the shading planes do not count rays");
-    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
-    return C2RT_OK;
-}
-
-/* The six planes in the order of the struct's members, as bytes: what the host variants stage and copy */
-constexpr int kShadePlanes = 6;
-constexpr size_t kShadeBytes[kShadePlanes] = {4, 12, 12, 12, 4, 12}; /* 56 B per sample */
-static void shade_plane_ptrs(const c2rt_shade_planes *pl, char *out[kShadePlanes])
-{
-    out[0] = reinterpret_cast<char *>(pl->node);
-    out[1] = reinterpret_cast<char *>(pl->albedo);
-    out[2] = reinterpret_cast<char *>(pl->light);
-    out[3] = reinterpret_cast<char *>(pl->specular);
-    out[4] = reinterpret_cast<char *>(pl->visible);
-    out[5] = reinterpret_cast<char *>(pl->rgb);
-}
-/* the device planes of one chunk of chunk_n samples at `base`, only those asked for; returns the bytes they take */
-static size_t shade_staging(char *const host[kShadePlanes], size_t chunk_n, char *base, size_t off[kShadePlanes], c2rt_shade_planes *d)
-{
-    size_t bytes = 0;
-    for (int k = 0; k < kShadePlanes; ++k) {
-        off[k] = bytes;
-        if (host[k]) bytes += align256(chunk_n * kShadeBytes[k]);
-    }
-    if (d) {
-        const auto dev = [&](int k) { return host[k] ? base + off[k] : nullptr; };
-        d->node = reinterpret_cast<int32_t *>(dev(0));
-        d->albedo = reinterpret_cast<float *>(dev(1));
-        d->light = reinterpret_cast<float *>(dev(2));
-        d->specular = reinterpret_cast<float *>(dev(3));
-        d->visible = reinterpret_cast<uint32_t *>(dev(4));
-        d->rgb = reinterpret_cast<float *>(dev(5));
-    }
-    return bytes;
+    return check_one_ray_per_pixel(ctx, cam, opts, "terms are", "shading");
 }
 
 int c2rt_render_shading_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
@@ -1608,35 +1633,20 @@ int c2rt_render_shading_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, cons
     return C2RT_OK;
 }
 
-/* Host variant: c2rt_render_hits' chunks of whole rows, at most kQueryChunk pixels each, plane after plane for the
- * chunk size and only for the planes asked for — 56 B per pixel, 14 MiB at most.  Each chunk ends with a stream sync. */
+/* Host variant: c2rt_render_hits' chunks of whole rows, plane after plane for the chunk size and only for the planes
+ * asked for — 56 B per pixel, 14 MiB at most. */
 int c2rt_render_shading(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_shade_planes *planes_host)
 {
     if (const int st = check_shading_args(ctx, cam, opts, planes_host)) return st;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     hit_params(ctx, cam, opts, p);
-    const uint32_t rows = p.local_rows, width = p.width;
-    if (rows == 0) return C2RT_OK;
-    uint32_t chunk_rows = (uint32_t)(kQueryChunk / width); /* width <= 2^16: at least four rows */
-    if (chunk_rows > rows) chunk_rows = rows;
-    char *host[kShadePlanes];
-    shade_plane_ptrs(planes_host, host);
-    size_t off[kShadePlanes];
-    if (const int st = ensure_staging(ctx, shade_staging(host, (size_t)chunk_rows * width, nullptr, off, nullptr))) return st;
-    char *base = reinterpret_cast<char *>(ctx->frame);
-    c2rt_shade_planes d;
-    shade_staging(host, (size_t)chunk_rows * width, base, off, &d);
-    for (uint32_t r0 = 0; r0 < rows; r0 += chunk_rows) {
-        const uint32_t m = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
-        const int e = launch_shade_planes(p, ctx->plan.csg_levels, d, r0, m, ctx->stream);
-        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "shading plane kernel launch: %s", hipGetErrorString((hipError_t)e));
-        const size_t first = (size_t)r0 * width, px = (size_t)m * width;
-        for (int k = 0; k < kShadePlanes; ++k)
-            if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k] + first * kShadeBytes[k], base + off[k], px * kShadeBytes[k], hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return C2RT_OK;
+    if (p.local_rows == 0) return C2RT_OK;
+    Staging outs;
+    outs.add_planes(*planes_host);
+    return row_chunks(ctx, p, 1, outs, "shading plane", [&](uint32_t r0, uint32_t m, size_t) {
+        return launch_shade_planes(p, ctx->plan.csg_levels, outs.planes<c2rt_shade_planes>(), r0, m, ctx->stream);
+    });
 }
 
 int c2rt_trace_rays_shading_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, const c2rt_shade_planes *planes_dev, void *hip_stream)
@@ -1656,29 +1666,11 @@ int c2rt_trace_rays_shading(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, con
 {
     if (const int st = check_query_args(ctx, rays, n, true)) return st < 0 ? C2RT_OK : st;
     if (const int st = check_shade_planes(ctx, planes_host)) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t chunk = n < kQueryChunk ? n : kQueryChunk;
-    const size_t off_planes = align256(chunk * sizeof(c2rt_ray));
-    char *host[kShadePlanes];
-    shade_plane_ptrs(planes_host, host);
-    size_t off[kShadePlanes];
-    if (const int st = ensure_staging(ctx, off_planes + shade_staging(host, chunk, nullptr, off, nullptr))) return st;
-    char *base = reinterpret_cast<char *>(ctx->frame);
-    c2rt_ray *rays_dev = reinterpret_cast<c2rt_ray *>(base);
-    c2rt_shade_planes d;
-    shade_staging(host, chunk, base + off_planes, off, &d);
-    RenderParams p;
-    query_params(ctx, p);
-    for (uint64_t i = 0; i < n; i += chunk) {
-        const uint64_t m = n - i < chunk ? n - i : chunk;
-        HIP_TRY(ctx, hipMemcpyAsync(rays_dev, rays + i, m * sizeof(c2rt_ray), hipMemcpyHostToDevice, ctx->stream));
-        const int e = launch_trace_rays_shade(p, ctx->plan.csg_levels, rays_dev, m, d, ctx->stream);
-        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "shading plane kernel launch: %s", hipGetErrorString((hipError_t)e));
-        for (int k = 0; k < kShadePlanes; ++k)
-            if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k] + i * kShadeBytes[k], base + off_planes + off[k], m * kShadeBytes[k], hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return C2RT_OK;
+    Staging outs;
+    outs.add_planes(*planes_host);
+    return ray_chunks(ctx, rays, n, kQueryChunk, outs, "shading plane", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t m, uint64_t) {
+        return launch_trace_rays_shade(p, ctx->plan.csg_levels, rays_dev, m, outs.planes<c2rt_shade_planes>(), ctx->stream);
+    });
 }
 
 /* ---- hit layers: every surface along a ray or pixel (c2rt_layers.hip) --------------------------------------------- */
@@ -1713,33 +1705,14 @@ int c2rt_trace_rays_layers(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, uint
 {
     if (const int st = check_query_args(ctx, rays, n, true)) return st < 0 ? C2RT_OK : st;
     if (const int st = check_layer_args(ctx, max_layers, hits || rgb || count)) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const uint64_t cap = kQueryChunk / max_layers, chunk = n < cap ? n : cap;
-    const size_t off_hits = align256(chunk * sizeof(c2rt_ray));
-    const size_t off_rgb = off_hits + (hits ? align256(chunk * max_layers * sizeof(c2rt_ray_hit)) : 0);
-    const size_t off_count = off_rgb + (rgb ? align256(chunk * max_layers * 3 * sizeof(float)) : 0);
-    const size_t bytes = off_count + (count ? chunk : 0);
-    if (const int st = ensure_staging(ctx, bytes)) return st;
-    char *base = reinterpret_cast<char *>(ctx->frame);
-    c2rt_ray *rays_dev = reinterpret_cast<c2rt_ray *>(base);
-    c2rt_ray_hit *hits_dev = hits ? reinterpret_cast<c2rt_ray_hit *>(base + off_hits) : nullptr;
-    float *rgb_dev = rgb ? reinterpret_cast<float *>(base + off_rgb) : nullptr;
-    uint8_t *count_dev = count ? reinterpret_cast<uint8_t *>(base + off_count) : nullptr;
-    RenderParams p;
-    query_params(ctx, p);
-    for (uint64_t i = 0; i < n; i += chunk) {
-        const uint64_t m = n - i < chunk ? n - i : chunk;
-        HIP_TRY(ctx, hipMemcpyAsync(rays_dev, rays + i, m * sizeof(c2rt_ray), hipMemcpyHostToDevice, ctx->stream));
-        const int e = launch_trace_ray_layers(p, ctx->plan.csg_levels, rays_dev, m, max_layers, chunk, hits_dev, rgb_dev, count_dev, ctx->stream);
-        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "hit layer kernel launch: %s", hipGetErrorString((hipError_t)e));
-        for (uint32_t k = 0; k < max_layers; ++k) {
-            if (hits) HIP_TRY(ctx, hipMemcpyAsync(hits + k * n + i, hits_dev + k * chunk, m * sizeof(c2rt_ray_hit), hipMemcpyDeviceToHost, ctx->stream));
-            if (rgb) HIP_TRY(ctx, hipMemcpyAsync(rgb + 3 * (k * n + i), rgb_dev + 3 * (k * chunk), m * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        if (count) HIP_TRY(ctx, hipMemcpyAsync(count + i, count_dev, m, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return C2RT_OK;
+    Staging outs;
+    outs.add(hits, sizeof(c2rt_ray_hit), max_layers);
+    outs.add(rgb, 3 * sizeof(float), max_layers);
+    outs.add(count, 1);
+    return ray_chunks(ctx, rays, n, kQueryChunk / max_layers, outs, "hit layer", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t m, uint64_t chunk) {
+        return launch_trace_ray_layers(p, ctx->plan.csg_levels, rays_dev, m, max_layers, chunk, outs.dev<c2rt_ray_hit>(0), outs.dev<float>(1), outs.dev<uint8_t>(2),
+                                       ctx->stream);
+    });
 }
 
 /* the refusals of the frame face, in the documented order: a frame call's, null planes, the layers', then the modes in
@@ -1749,12 +1722,8 @@ static int check_hit_layer_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, con
 {
     if (const int st = check_frame_args(ctx, cam, opts)) return st;
     if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
-    if (const int st = check_layer_args(ctx, max_layers, any_plane(planes) || count)) return st;
-    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: a pixel's record is one ray's, a lens has many per pixel");
-    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: a pixel's record is one ray's, a stereo camera has two per pixel");
-    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the hit planes do not count rays");
-    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
-    return C2RT_OK;
+    if (const int st = check_layer_args(ctx, max_layers, any_plane(*planes) || count)) return st;
+    return check_one_ray_per_pixel(ctx, cam, opts, "record is", "hit");
 }
 
 int c2rt_render_hit_layers_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, uint32_t max_layers,
@@ -1779,50 +1748,14 @@ int c2rt_render_hit_layers(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     hit_params(ctx, cam, opts, p);
-    const uint32_t rows = p.local_rows, width = p.width;
-    if (rows == 0) return C2RT_OK;
-    uint32_t chunk_rows = (uint32_t)(kQueryChunk / max_layers / width);
-    if (chunk_rows == 0) chunk_rows = 1;
-    if (chunk_rows > rows) chunk_rows = rows;
-    const size_t chunk_px = (size_t)chunk_rows * width, frame_px = (size_t)rows * width;
-    char *const host[7] = {reinterpret_cast<char *>(planes_host->node), reinterpret_cast<char *>(planes_host->leaf),
-                           reinterpret_cast<char *>(planes_host->dist), reinterpret_cast<char *>(planes_host->uv),
-                           reinterpret_cast<char *>(planes_host->p), reinterpret_cast<char *>(planes_host->normal),
-                           reinterpret_cast<char *>(planes_host->rgb)};
-    const size_t px_bytes[7] = {4, 4, 8, 16, 24, 24, 12};
-    size_t off[7], bytes = 0;
-    for (int k = 0; k < 7; ++k) {
-        off[k] = bytes;
-        if (host[k]) bytes += align256(chunk_px * max_layers * px_bytes[k]);
-    }
-    const size_t off_count = bytes;
-    if (count_host) bytes += chunk_px;
-    if (const int st = ensure_staging(ctx, bytes)) return st;
-    char *base = reinterpret_cast<char *>(ctx->frame);
-    const auto dev = [&](int k) { return host[k] ? base + off[k] : nullptr; };
-    c2rt_hit_planes d;
-    d.node = reinterpret_cast<int32_t *>(dev(0));
-    d.leaf = reinterpret_cast<int32_t *>(dev(1));
-    d.dist = reinterpret_cast<double *>(dev(2));
-    d.uv = reinterpret_cast<double *>(dev(3));
-    d.p = reinterpret_cast<double *>(dev(4));
-    d.normal = reinterpret_cast<double *>(dev(5));
-    d.rgb = reinterpret_cast<float *>(dev(6));
-    uint8_t *count_dev = count_host ? reinterpret_cast<uint8_t *>(base + off_count) : nullptr;
-    for (uint32_t r0 = 0; r0 < rows; r0 += chunk_rows) {
-        const uint32_t m = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
-        const int e = launch_hit_layers(p, ctx->plan.csg_levels, d, count_dev, max_layers, chunk_px, r0, m, ctx->stream);
-        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "hit layer kernel launch: %s", hipGetErrorString((hipError_t)e));
-        const size_t first = (size_t)r0 * width, px = (size_t)m * width;
-        for (uint32_t l = 0; l < max_layers; ++l)
-            for (int k = 0; k < 7; ++k)
-                if (host[k])
-                    HIP_TRY(ctx, hipMemcpyAsync(host[k] + (l * frame_px + first) * px_bytes[k], base + off[k] + l * chunk_px * px_bytes[k], px * px_bytes[k],
-                                                hipMemcpyDeviceToHost, ctx->stream));
-        if (count_host) HIP_TRY(ctx, hipMemcpyAsync(count_host + first, count_dev, px, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
-    return C2RT_OK;
+    if (p.local_rows == 0) return C2RT_OK;
+    Staging outs;
+    outs.add_planes(*planes_host, max_layers);
+    outs.add(count_host, 1);
+    return row_chunks(ctx, p, max_layers, outs, "hit layer", [&](uint32_t r0, uint32_t m, size_t chunk_px) {
+        return launch_hit_layers(p, ctx->plan.csg_levels, outs.planes<c2rt_hit_planes>(), outs.dev<uint8_t>(kPlanes<c2rt_hit_planes>), max_layers, chunk_px, r0, m,
+                                 ctx->stream);
+    });
 }
 
 /* ---- hit planes of a batch of frames (c2rt_hit_planes.hip: hit_planes_batch_kernel) ------------------------------- */
@@ -1835,7 +1768,7 @@ static int check_hit_batch_args(c2rt_ctx *ctx, const c2rt_camera_frame *cams, co
 {
     if (const int st = check_batch_args(ctx, cams, n_frames, opts)) return st;
     if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
-    if (!any_plane(planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all seven pointers of c2rt_hit_planes are null");
+    if (!any_plane(*planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all seven pointers of c2rt_hit_planes are null");
     if (poses_given)
         if (const int st = check_posed_args(ctx, poses, n_frames)) return st;
     return C2RT_OK;
@@ -1936,27 +1869,10 @@ static int hit_batch_to_host(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const
     uint32_t chunk_rows = whole ? rows : (uint32_t)(kQueryChunk / width);
     if (chunk_rows > rows) chunk_rows = rows;
     const size_t chunk_px = (size_t)chunk_frames * chunk_rows * width;
-    char *const host[7] = {reinterpret_cast<char *>(planes_host->node), reinterpret_cast<char *>(planes_host->leaf),
-                           reinterpret_cast<char *>(planes_host->dist), reinterpret_cast<char *>(planes_host->uv),
-                           reinterpret_cast<char *>(planes_host->p), reinterpret_cast<char *>(planes_host->normal),
-                           reinterpret_cast<char *>(planes_host->rgb)};
-    const size_t px_bytes[7] = {4, 4, 8, 16, 24, 24, 12};
-    size_t off[7], bytes = 0;
-    for (int k = 0; k < 7; ++k) {
-        off[k] = bytes;
-        if (host[k]) bytes += align256(chunk_px * px_bytes[k]);
-    }
-    if (const int st = ensure_staging(ctx, bytes)) return st;
-    char *base = reinterpret_cast<char *>(ctx->frame);
-    const auto dev = [&](int k) { return host[k] ? base + off[k] : nullptr; };
-    c2rt_hit_planes d;
-    d.node = reinterpret_cast<int32_t *>(dev(0));
-    d.leaf = reinterpret_cast<int32_t *>(dev(1));
-    d.dist = reinterpret_cast<double *>(dev(2));
-    d.uv = reinterpret_cast<double *>(dev(3));
-    d.p = reinterpret_cast<double *>(dev(4));
-    d.normal = reinterpret_cast<double *>(dev(5));
-    d.rgb = reinterpret_cast<float *>(dev(6));
+    Staging outs;
+    outs.add_planes(*planes_host);
+    if (const int e = lay_out(ctx, outs, 0, chunk_px)) return e;
+    const c2rt_hit_planes d = outs.planes<c2rt_hit_planes>();
     const RenderParams *table_dev = nullptr;
     RenderParams p0;
     if (const int st = hit_batch_table(ctx, cams, poses_given ? &posed : nullptr, n_frames, opts, ctx->stream, &table_dev, p0)) return st;
@@ -1968,8 +1884,7 @@ static int hit_batch_to_host(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const
             const int e = launch_hit_planes_batch(p0, ctx->plan.csg_levels, table_dev + f0, nf, frame_px, d, r0, m, ctx->stream);
             if (e != 0) return fail(ctx, C2RT_ERR_HIP, "hit plane batch kernel launch: %s", hipGetErrorString((hipError_t)e));
             const size_t first = (size_t)f0 * frame_px + (size_t)r0 * width, px = (size_t)(nf - 1) * frame_px + (size_t)m * width;
-            for (int k = 0; k < 7; ++k)
-                if (host[k]) HIP_TRY(ctx, hipMemcpyAsync(host[k] + first * px_bytes[k], base + off[k], px * px_bytes[k], hipMemcpyDeviceToHost, ctx->stream));
+            if (const int st = copy_back(ctx, outs, first, px, 0, 0)) return st;
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         }
     }

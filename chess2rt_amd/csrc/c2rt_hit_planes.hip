@@ -1,17 +1,13 @@
 /*
  * c2rt_hit_planes.hip — hit planes (c2rt_render_hits*): the closest-hit record of the ray through the integer corner of
  * every pixel of a camera frame, one plane per field.  The ray query kernel (c2rt_rays.hip) with the caller's ray array
- * replaced by the camera: the lane builds its own screen ray (screen_ray<false>, normalized), so nothing is read but the
+ * replaced by the camera: the lane builds its own screen ray (pixel_ray), so nothing is read but the
  * scene, and only the planes asked for are written.  What it shares with the other query kernels: c2rt_query.inc.
  *
- * Pixel -> lane (the output does not depend on it): the frames' 8x8 tile.  Measured against a run of 64 pixels of one
- * row — every store instruction of a scalar plane covers 256 / 512 contiguous bytes — and against 16x4: lecture5.sdl
- * 1080p, all seven planes / node + dist / all but rgb: 117.9 / 62.6 / 65.3 us for the run, 112.8 / 60.1 / 62.0 for the
- * 8x8 tile, 112.5 / 59.9 / 62.1 for 16x4 (profiles/hit_planes.md): coherent rays and fewer distinct closest nodes per
- * wave are worth more than the wider stores.  Lanes past the right or bottom edge are masked out by control flow before
- * the trace, as the ray query kernel masks its tail.
+ * Pixel -> lane: the 8x8 tile of c2rt_query.inc (tile_pixel, where the measurement that chose it is told).
  *
- * Stores: each lane stores its own values, the three-component planes as three 8-byte stores at a 24-byte stride.
+ * Stores (store_hit_planes, c2rt_query.inc): each lane stores its own values, the three-component planes as three 8-byte
+ * stores at a 24-byte stride.
  * Staging uv / p / normal in the dead hit stack and writing them as rows, lane l storing words l, l + 64, ... of each
  * tile row's contiguous run (the ray query kernel's record store), was SLOWER here — 67.2 against 62.0 us for all but
  * rgb (8x8), 70.1 against 65.3 (run of 64): a plane's values of a tile row are already adjacent lanes' and the L2 merges
@@ -36,10 +32,6 @@
 namespace c2rt {
 namespace {
 
-constexpr int kHitTileW = 8, kHitTileH = kWave / kHitTileW;
-static_assert(sizeof(RenderParams) + sizeof(c2rt_hit_planes) + 16 <= 4096, "the kernel-argument segment holds at most 4 KiB");
-static_assert(sizeof(c2rt_hit_planes) == 56, "ABI layout of c2rt_hit_planes");
-
 /* The wave over tile blockIdx.x of rows [row0, row0 + rows) of the frame `P` describes: one body for both entry points
  * below, which only produce (P, K, out). */
 template <int LEVELS, bool MLC>
@@ -49,59 +41,18 @@ DEV void hit_planes_body(const RenderParams &P, KArgs K, const c2rt_hit_planes &
     using namespace exact;
     extern __shared__ __align__(16) char lds[];
     const int lane = (int)threadIdx.x;
-    const uint32_t trow = blockIdx.x / tiles_x, tcol = blockIdx.x % tiles_x; /* the grid is tiles_x * ceil(rows / kHitTileH) */
-    const uint32_t x0 = tcol * kHitTileW, r0 = trow * kHitTileH;
-    const uint32_t x = x0 + (uint32_t)(lane % kHitTileW);
-    const uint32_t r = r0 + (uint32_t)(lane / kHitTileW); /* row within this launch */
-    const bool live = x < P.width && r < rows;
+    const TilePixel px = tile_pixel(P, lane, rows, tiles_x);
     const bool record = out.dist || out.uv || out.p || out.normal; /* wave-uniform: best.dist and the surface are read */
     Ctx cx;
     query_ctx(cx, P, K, lds, lane);
-    D3 d = mk(0, 0, 0);
-    Hit best;
-    Surf surf;
-    Mat mat;
-    int closest = -1;
-    const size_t idx = (size_t)r * P.width + x;
-    if (live) {
-        /* local row -> frame row under interleaved strips, as render_tile maps it */
-        const uint32_t lr = r + row0;
-        uint32_t y = lr;
-        if (P.strip_world > 1) {
-            const uint32_t sh = P.strip_height;
-            y = ((lr / sh) * P.strip_world + P.strip_rank) * sh + lr % sh;
-        }
-        Rng rng = {0u, 0, 0};
-        D3 o, raw;
-        screen_ray<false>(cx.bad, P, (double)x, (double)y, 0, rng, o, raw);
-        d = normalized(cx.bad, raw); /* raytrace(): rt/camera.d:144-147 */
-        closest = trace_closest<LEVELS>(cx, o, d, record, best, surf, mat);
-        if (out.node) out.node[idx] = closest;
-        if (out.leaf) out.leaf[idx] = closest >= 0 ? best.g : -1;
-        if (out.dist) out.dist[idx] = best.dist;
-        if (out.uv) {
-            typedef double __attribute__((ext_vector_type(2), aligned(8))) d2_t;
-            d2_t uv;
-            uv.x = surf.u;
-            uv.y = surf.v;
-            *reinterpret_cast<d2_t *>(out.uv + idx * 2) = uv;
-        }
-        if (out.p) {
-            out.p[idx * 3 + 0] = surf.p.x;
-            out.p[idx * 3 + 1] = surf.p.y;
-            out.p[idx * 3 + 2] = surf.p.z;
-        }
-        if (out.normal) {
-            out.normal[idx * 3 + 0] = surf.n.x;
-            out.normal[idx * 3 + 1] = surf.n.y;
-            out.normal[idx * 3 + 2] = surf.n.z;
-        }
-    }
-    if (live && out.rgb) {
-        F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
-        uint32_t shadow_rays = 0;
-        if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
-        store_colour(out.rgb + idx * 3, c);
+    if (px.live) {
+        D3 o, d;
+        pixel_ray(cx, P, (double)px.x, (double)px.y(P, row0), o, d);
+        Hit best;
+        Surf surf;
+        Mat mat;
+        const int closest = trace_closest<LEVELS>(cx, o, d, record, best, surf, mat);
+        store_hit_planes<LEVELS, MLC>(P, cx, out, px.idx, closest, best, surf, mat, d);
     }
 }
 
@@ -110,16 +61,6 @@ __global__ void __launch_bounds__(kWave) C2RT_WAVES_QUERY(LEVELS, MLC)
 hit_planes_kernel(const RenderParams P, const c2rt_hit_planes out, const uint32_t row0, const uint32_t rows, const uint32_t tiles_x)
 {
     hit_planes_body<LEVELS, MLC>(P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), out, row0, rows, tiles_x);
-}
-
-/* batch_block of c2rt_adaptive.hip, restated (that file's object stays as it is): block blockIdx.y of the table through
- * a constant-address-space pointer; the empty asm keeps the optimiser from folding the casts back to the global
- * pointer, loads through which would be vector loads. */
-DEV KArgs batch_block(const RenderParams *table)
-{
-    KArgs K = (KArgs)table + blockIdx.y;
-    asm volatile("" : "+s"(K));
-    return K;
 }
 
 /* The same over a batch: blockIdx.y = frame, blockIdx.x = tile of the row window.  `planes` are the batch's: frame
@@ -147,19 +88,18 @@ hit_planes_batch_kernel(const RenderParams *table, const c2rt_hit_planes planes,
 /* table_dev null: the single-frame kernel with `p` as its argument; otherwise the n_frames blocks at table_dev, of which
  * `p` is any one's host copy (the grid, the stack and the instance are the same for all of them), frame_px pixels from
  * one frame's slice of a plane to the next's */
-template <int LEVELS>
-int launch_hit_planes_level(const RenderParams &p, const RenderParams *table_dev, uint32_t n_frames, size_t frame_px,
-                            const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, hipStream_t s)
+int launch_planes(const RenderParams &p, int csg_levels, const RenderParams *table_dev, uint32_t n_frames, size_t frame_px,
+                  const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, hipStream_t s)
 {
-    const uint32_t tiles_x = (p.width + kHitTileW - 1) / kHitTileW, tiles_y = (rows + kHitTileH - 1) / kHitTileH;
-    const dim3 grid(tiles_x * tiles_y, n_frames), block(kWave); /* at most 2^16 x 2^16 pixels / 64; n_frames <= 256 */
-    const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry;
-    if (table_dev) {
-        if (p.n_lights > 1) hipLaunchKernelGGL((hit_planes_batch_kernel<LEVELS, true>), grid, block, lds, s, table_dev, out, frame_px, row0, rows, tiles_x);
-        else hipLaunchKernelGGL((hit_planes_batch_kernel<LEVELS, false>), grid, block, lds, s, table_dev, out, frame_px, row0, rows, tiles_x);
-    } else if (p.n_lights > 1) hipLaunchKernelGGL((hit_planes_kernel<LEVELS, true>), grid, block, lds, s, p, out, row0, rows, tiles_x);
-    else hipLaunchKernelGGL((hit_planes_kernel<LEVELS, false>), grid, block, lds, s, p, out, row0, rows, tiles_x);
-    return (int)hipGetLastError();
+    uint32_t tiles_x;
+    const dim3 grid = tile_grid(p, rows, tiles_x, n_frames);
+    return for_csg_levels(csg_levels, [&](auto L) {
+        constexpr int LEVELS = decltype(L)::value;
+        if (table_dev)
+            return launch_query(p, hit_planes_batch_kernel<LEVELS, true>, hit_planes_batch_kernel<LEVELS, false>, grid, stack_lds(p), s, table_dev, out,
+                                frame_px, row0, rows, tiles_x);
+        return launch_query(p, hit_planes_kernel<LEVELS, true>, hit_planes_kernel<LEVELS, false>, grid, stack_lds(p), s, p, out, row0, rows, tiles_x);
+    });
 }
 
 } // namespace
@@ -169,9 +109,8 @@ int launch_hit_planes_level(const RenderParams &p, const RenderParams *table_dev
  * device pointers, at least one of them non-null, rows > 0. */
 int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!rows || !p.width || !(out.node || out.leaf || out.dist || out.uv || out.p || out.normal || out.rgb)) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) { return launch_hit_planes_level<decltype(L)::value>(p, nullptr, 1, 0, out, row0, rows, s); });
+    if (!rows || !p.width || !any_plane(out)) return (int)hipErrorInvalidValue;
+    return launch_planes(p, csg_levels, nullptr, 1, 0, out, row0, rows, static_cast<hipStream_t>(stream));
 }
 
 /* The same rows of the n_frames frames of a batch in one launch: table_dev holds their blocks (p0: any one's host copy;
@@ -180,11 +119,8 @@ int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_plan
 int launch_hit_planes_batch(const RenderParams &p0, int csg_levels, const RenderParams *table_dev, uint32_t n_frames, size_t frame_px,
                             const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream)
 {
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!rows || !p0.width || !table_dev || !n_frames || n_frames > C2RT_MAX_BATCH_FRAMES ||
-        !(out.node || out.leaf || out.dist || out.uv || out.p || out.normal || out.rgb))
-        return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) { return launch_hit_planes_level<decltype(L)::value>(p0, table_dev, n_frames, frame_px, out, row0, rows, s); });
+    if (!rows || !p0.width || !table_dev || !n_frames || n_frames > C2RT_MAX_BATCH_FRAMES || !any_plane(out)) return (int)hipErrorInvalidValue;
+    return launch_planes(p0, csg_levels, table_dev, n_frames, frame_px, out, row0, rows, static_cast<hipStream_t>(stream));
 }
 
 } // namespace c2rt

@@ -134,16 +134,8 @@ __global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(0, DOF, false) re
  * blockIdx.y = frame.  A tile's whole identity is (parameter block, block index): blockIdx.x is what it is in the
  * single-frame launch of that frame (so the tile lands on the same XCD class), and the block is read through a
  * constant-address-space pointer exactly as the single-frame kernels re-read their kernel-argument segment — scalar
- * loads, no VGPR.  The pointer goes through an empty asm so that the optimiser cannot fold the address-space casts
- * back to the global pointer it was made from (loads through that one would be vector loads: the kernel stores to
- * global memory, so nothing proves them invariant).  Only the instances a batch can reach: no counting, no depth of
+ * loads, no VGPR (batch_block, c2rt_trace_shared.inc).  Only the instances a batch can reach: no counting, no depth of
  * field.  Register budget, scratch and occupancy equal the single-frame twins' (profiles/frame_batch.md). */
-DEV KArgs batch_block(const RenderParams *table)
-{
-    KArgs K = (KArgs)table + blockIdx.y;
-    asm volatile("" : "+s"(K));
-    return K;
-}
 
 template <int LEVELS, bool MLC>
 __global__ void __launch_bounds__(kBlockThreads) C2RT_WAVES_OF(LEVELS, 0, MLC) render_kernel_batch(const RenderParams *table)

@@ -34,7 +34,7 @@
  * (151.5 against 148.0 at one), 168.3 against 171.9 us for hits alone.  The rows win what they win in trace_rays_kernel
  * only while nothing else is stored; with colours the LDS round trip and the two barriers per layer cost more, and
  * the ten rows in flight needed eight more VGPRs.  The plain store is kept.
- * The frame kernel stores as hit_planes_kernel does, each lane its own values: measured faster there.
+ * The frame kernel stores as hit_planes_kernel does (store_hit_planes), each lane its own values: measured faster there.
  * All stores are plain vector stores.
  */
 #define C2RT_TRACE_EXACT_ONLY
@@ -44,13 +44,6 @@
 namespace c2rt {
 namespace {
 
-constexpr int kHitWords = (int)(sizeof(c2rt_ray_hit) / 8);
-constexpr int kHitTileW = 8, kHitTileH = kWave / kHitTileW;
-static_assert(sizeof(c2rt_ray) == 48 && sizeof(c2rt_ray_hit) == 80 && kHitWords * 8 == sizeof(c2rt_ray_hit), "ABI layout of the query records");
-static_assert(__builtin_offsetof(c2rt_ray_hit, leaf_geom) == 4 && __builtin_offsetof(c2rt_ray_hit, dist) == 8 &&
-              __builtin_offsetof(c2rt_ray_hit, p) == 32 && __builtin_offsetof(c2rt_ray_hit, normal) == 56, "ABI layout of c2rt_ray_hit");
-static_assert(sizeof(c2rt_hit_planes) == 56, "ABI layout of c2rt_hit_planes");
-static_assert(sizeof(RenderParams) + sizeof(c2rt_hit_planes) + 40 <= 4096, "the kernel-argument segment holds at most 4 KiB");
 static_assert(C2RT_MAX_HIT_LAYERS <= 255, "a ray's count is one byte");
 
 /* The register budget: the query kernels' (C2RT_WAVES_QUERY), but for the depth-1 instance with one light.  That one
@@ -61,17 +54,6 @@ static_assert(C2RT_MAX_HIT_LAYERS <= 255, "a ray's count is one byte");
 template <int LEVELS, bool MLC>
 constexpr int occ_layers() { return LEVELS == 1 ? 3 : occ_query<LEVELS, MLC>(); }
 #define C2RT_WAVES_LAYERS(L, M) __attribute__((amdgpu_waves_per_eu(occ_layers<L, M>(), occ_layers<L, M>())))
-
-/* load6 of c2rt_rays.hip, restated (that file's object stays as it is): the six doubles of a c2rt_ray as three 16-byte
- * loads where the hardware takes them at 8-byte alignment */
-typedef double __attribute__((ext_vector_type(2), aligned(8))) d2_t;
-DEV void load6(const void *rec, D3 &a, D3 &b)
-{
-    const d2_t *q = static_cast<const d2_t *>(rec);
-    const d2_t q0 = q[0], q1 = q[1], q2 = q[2];
-    a = mk(q0.x, q0.y, q1.x);
-    b = mk(q1.y, q2.x, q2.y);
-}
 
 /* One layer's bookkeeping behind trace_closest, for a walking lane: temp.dist += currentLength; currentLength =
  * temp.dist (rt/geometry.d:283-284) for a hit — one addition, the steps not counted — and the count. */
@@ -131,26 +113,8 @@ trace_ray_layers_kernel(const RenderParams P, const c2rt_ray *__restrict__ rays,
             layer_dir(d);
             const int closest = trace_closest<LEVELS>(cx, o, d, record, best, surf, mat);
             layer_account(closest, best, total, cnt);
-            if (hits) {
-                unsigned long long *rec = reinterpret_cast<unsigned long long *>(hits + slot + i);
-                const int leaf = closest >= 0 ? best.g : -1;
-                rec[0] = (unsigned long long)(uint32_t)closest | ((unsigned long long)(uint32_t)leaf << 32);
-                rec[1] = (unsigned long long)__double_as_longlong(best.dist);
-                rec[2] = (unsigned long long)__double_as_longlong(surf.u);
-                rec[3] = (unsigned long long)__double_as_longlong(surf.v);
-                rec[4] = (unsigned long long)__double_as_longlong(surf.p.x);
-                rec[5] = (unsigned long long)__double_as_longlong(surf.p.y);
-                rec[6] = (unsigned long long)__double_as_longlong(surf.p.z);
-                rec[7] = (unsigned long long)__double_as_longlong(surf.n.x);
-                rec[8] = (unsigned long long)__double_as_longlong(surf.n.y);
-                rec[9] = (unsigned long long)__double_as_longlong(surf.n.z);
-            }
-            if (rgb) {
-                F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
-                uint32_t shadow_rays = 0;
-                if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
-                store_colour(rgb + (slot + i) * 3, c);
-            }
+            if (hits) store_record(reinterpret_cast<unsigned long long *>(hits + slot + i), closest, best, surf);
+            if (rgb) store_colour(rgb + (slot + i) * 3, sample_colour<LEVELS, MLC>(P, cx, closest, mat, d, surf));
             if (closest < 0) walking = false;
             else o = layer_step(surf.p, d);
         }
@@ -169,33 +133,20 @@ hit_layers_kernel(const RenderParams P, const c2rt_hit_planes out, uint8_t *__re
     using namespace exact;
     extern __shared__ __align__(16) char lds[];
     const int lane = (int)threadIdx.x;
-    const uint32_t trow = blockIdx.x / tiles_x, tcol = blockIdx.x % tiles_x; /* the grid is tiles_x * ceil(rows / kHitTileH) */
-    const uint32_t x = tcol * kHitTileW + (uint32_t)(lane % kHitTileW);
-    const uint32_t r = trow * kHitTileH + (uint32_t)(lane / kHitTileW); /* row within this launch */
-    const bool live = x < P.width && r < rows;
+    const TilePixel px = tile_pixel(P, lane, rows, tiles_x);
     const bool fields = out.dist || out.uv || out.p || out.normal; /* wave-uniform */
     Ctx cx;
     query_ctx(cx, P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
     D3 o = mk(0, 0, 0), d = mk(0, 0, 0);
-    const size_t px = (size_t)r * P.width + x;
-    bool walking = live;
-    if (walking) {
-        /* local row -> frame row under interleaved strips, as hit_planes_body maps it */
-        const uint32_t lr = r + row0;
-        uint32_t y = lr;
-        if (P.strip_world > 1) {
-            const uint32_t sh = P.strip_height;
-            y = ((lr / sh) * P.strip_world + P.strip_rank) * sh + lr % sh;
-        }
-        pixel_ray(cx, P, (double)x, (double)y, o, d);
-    }
+    bool walking = px.live;
+    if (walking) pixel_ray(cx, P, (double)px.x, (double)px.y(P, row0), o, d);
     double total = 0.0;
     uint32_t cnt = 0;
 #pragma unroll 1
     for (uint32_t k = 0; k < max_layers; ++k) {
         if (!__ballot(walking)) break;
         const bool record = fields || k + 1 < max_layers; /* wave-uniform */
-        const size_t idx = (size_t)k * layer_px + px;
+        const size_t idx = (size_t)k * layer_px + px.idx;
         if (walking) {
             Hit best;
             Surf surf;
@@ -203,59 +154,12 @@ hit_layers_kernel(const RenderParams P, const c2rt_hit_planes out, uint8_t *__re
             layer_dir(d);
             const int closest = trace_closest<LEVELS>(cx, o, d, record, best, surf, mat);
             layer_account(closest, best, total, cnt);
-            if (out.node) out.node[idx] = closest;
-            if (out.leaf) out.leaf[idx] = closest >= 0 ? best.g : -1;
-            if (out.dist) out.dist[idx] = best.dist;
-            if (out.uv) {
-                d2_t uv;
-                uv.x = surf.u;
-                uv.y = surf.v;
-                *reinterpret_cast<d2_t *>(out.uv + idx * 2) = uv;
-            }
-            if (out.p) {
-                out.p[idx * 3 + 0] = surf.p.x;
-                out.p[idx * 3 + 1] = surf.p.y;
-                out.p[idx * 3 + 2] = surf.p.z;
-            }
-            if (out.normal) {
-                out.normal[idx * 3 + 0] = surf.n.x;
-                out.normal[idx * 3 + 1] = surf.n.y;
-                out.normal[idx * 3 + 2] = surf.n.z;
-            }
-            if (out.rgb) {
-                F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
-                uint32_t shadow_rays = 0;
-                if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
-                store_colour(out.rgb + idx * 3, c);
-            }
+            store_hit_planes<LEVELS, MLC>(P, cx, out, idx, closest, best, surf, mat, d);
             if (closest < 0) walking = false;
             else o = layer_step(surf.p, d);
         }
     }
-    if (live && count) count[px] = (uint8_t)cnt;
-}
-
-template <int LEVELS>
-int launch_ray_layers_level(const RenderParams &p, const c2rt_ray *rays, uint64_t n, uint32_t max_layers, uint64_t layer_stride,
-                            c2rt_ray_hit *hits, float *rgb, uint8_t *count, hipStream_t s)
-{
-    const dim3 grid((uint32_t)((n + kWave - 1) / kWave)), block(kWave);
-    const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry;
-    if (p.n_lights > 1) hipLaunchKernelGGL((trace_ray_layers_kernel<LEVELS, true>), grid, block, lds, s, p, rays, n, max_layers, layer_stride, hits, rgb, count);
-    else hipLaunchKernelGGL((trace_ray_layers_kernel<LEVELS, false>), grid, block, lds, s, p, rays, n, max_layers, layer_stride, hits, rgb, count);
-    return (int)hipGetLastError();
-}
-
-template <int LEVELS>
-int launch_hit_layers_level(const RenderParams &p, const c2rt_hit_planes &out, uint8_t *count, uint32_t max_layers, size_t layer_px,
-                            uint32_t row0, uint32_t rows, hipStream_t s)
-{
-    const uint32_t tiles_x = (p.width + kHitTileW - 1) / kHitTileW, tiles_y = (rows + kHitTileH - 1) / kHitTileH;
-    const dim3 grid(tiles_x * tiles_y), block(kWave); /* at most 2^16 x 2^16 pixels / 64 */
-    const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry;
-    if (p.n_lights > 1) hipLaunchKernelGGL((hit_layers_kernel<LEVELS, true>), grid, block, lds, s, p, out, count, max_layers, layer_px, row0, rows, tiles_x);
-    else hipLaunchKernelGGL((hit_layers_kernel<LEVELS, false>), grid, block, lds, s, p, out, count, max_layers, layer_px, row0, rows, tiles_x);
-    return (int)hipGetLastError();
+    if (px.live && count) count[px.idx] = (uint8_t)cnt;
 }
 
 } // namespace
@@ -266,16 +170,26 @@ int launch_trace_ray_layers(const RenderParams &p, int csg_levels, const c2rt_ra
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!n || n > C2RT_MAX_RAYS || !max_layers || max_layers > C2RT_MAX_HIT_LAYERS || layer_stride < n || (!hits && !rgb && !count))
         return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) { return launch_ray_layers_level<decltype(L)::value>(p, rays, n, max_layers, layer_stride, hits, rgb, count, s); });
+    return for_csg_levels(csg_levels, [&](auto L) {
+        constexpr int LEVELS = decltype(L)::value;
+        return launch_query(p, trace_ray_layers_kernel<LEVELS, true>, trace_ray_layers_kernel<LEVELS, false>, ray_grid(n), stack_lds(p), s, p, rays, n,
+                            max_layers, layer_stride, hits, rgb, count);
+    });
 }
 
 int launch_hit_layers(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint8_t *count, uint32_t max_layers, size_t layer_px,
                       uint32_t row0, uint32_t rows, void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool any = out.node || out.leaf || out.dist || out.uv || out.p || out.normal || out.rgb || count;
-    if (!rows || !p.width || !max_layers || max_layers > C2RT_MAX_HIT_LAYERS || layer_px < (size_t)rows * p.width || !any) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) { return launch_hit_layers_level<decltype(L)::value>(p, out, count, max_layers, layer_px, row0, rows, s); });
+    if (!rows || !p.width || !max_layers || max_layers > C2RT_MAX_HIT_LAYERS || layer_px < (size_t)rows * p.width || !(any_plane(out) || count))
+        return (int)hipErrorInvalidValue;
+    uint32_t tiles_x;
+    const dim3 grid = tile_grid(p, rows, tiles_x);
+    return for_csg_levels(csg_levels, [&](auto L) {
+        constexpr int LEVELS = decltype(L)::value;
+        return launch_query(p, hit_layers_kernel<LEVELS, true>, hit_layers_kernel<LEVELS, false>, grid, stack_lds(p), s, p, out, count, max_layers, layer_px,
+                            row0, rows, tiles_x);
+    });
 }
 
 } // namespace c2rt

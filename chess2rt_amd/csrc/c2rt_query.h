@@ -13,6 +13,10 @@
 
 namespace c2rt {
 
+/* "at least one plane asked for": what the launches below and the entry points of c2rt_api.cpp both refuse without */
+inline bool any_plane(const c2rt_hit_planes &o) { return o.node || o.leaf || o.dist || o.uv || o.p || o.normal || o.rgb; }
+inline bool any_plane(const c2rt_shade_planes &o) { return o.node || o.albedo || o.light || o.specular || o.visible || o.rgb; }
+
 /* Ray and visibility queries (c2rt_trace_rays*, c2rt_test_visibility*): no camera; 0 < n <= C2RT_MAX_RAYS; hits / rgb
  * nullable, not both */
 int launch_trace_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb, void *stream);

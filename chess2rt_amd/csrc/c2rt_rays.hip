@@ -27,22 +27,6 @@
 namespace c2rt {
 namespace {
 
-constexpr int kHitWords = (int)(sizeof(c2rt_ray_hit) / 8);
-static_assert(sizeof(c2rt_ray) == 48 && sizeof(c2rt_segment) == 48 && sizeof(c2rt_ray_hit) == 80 && kHitWords * 8 == sizeof(c2rt_ray_hit), "ABI layout of the query records");
-static_assert(__builtin_offsetof(c2rt_ray_hit, leaf_geom) == 4 && __builtin_offsetof(c2rt_ray_hit, dist) == 8 &&
-              __builtin_offsetof(c2rt_ray_hit, p) == 32 && __builtin_offsetof(c2rt_ray_hit, normal) == 56, "ABI layout of c2rt_ray_hit");
-
-/* six doubles of an array-of-structures input record (c2rt_ray, c2rt_segment): three 16-byte loads where the
- * hardware takes them at 8-byte alignment */
-typedef double __attribute__((ext_vector_type(2), aligned(8))) d2_t;
-DEV void load6(const void *rec, D3 &a, D3 &b)
-{
-    const d2_t *q = static_cast<const d2_t *>(rec);
-    const d2_t q0 = q[0], q1 = q[1], q2 = q[2];
-    a = mk(q0.x, q0.y, q1.x);
-    b = mk(q1.y, q2.x, q2.y);
-}
-
 /* Ray i = trace(ray, TraceType.Ray), rt/renderer.d:325-376, depth 0.  hits / rgb: nullable, not both (wave-uniform). */
 template <int LEVELS, bool MLC>
 __global__ void __launch_bounds__(kWave) C2RT_WAVES_QUERY(LEVELS, MLC)
@@ -65,20 +49,7 @@ trace_rays_kernel(const RenderParams P, const c2rt_ray *__restrict__ rays, const
     if (live) {
         load6(rays + i, o, d);
         closest = trace_closest<LEVELS>(cx, o, d, hits != nullptr, best, surf, mat);
-        if (hits) {
-            unsigned long long *rec = stage + lane * kHitWords;
-            const int leaf = closest >= 0 ? best.g : -1;
-            rec[0] = (unsigned long long)(uint32_t)closest | ((unsigned long long)(uint32_t)leaf << 32);
-            rec[1] = (unsigned long long)__double_as_longlong(best.dist);
-            rec[2] = (unsigned long long)__double_as_longlong(surf.u);
-            rec[3] = (unsigned long long)__double_as_longlong(surf.v);
-            rec[4] = (unsigned long long)__double_as_longlong(surf.p.x);
-            rec[5] = (unsigned long long)__double_as_longlong(surf.p.y);
-            rec[6] = (unsigned long long)__double_as_longlong(surf.p.z);
-            rec[7] = (unsigned long long)__double_as_longlong(surf.n.x);
-            rec[8] = (unsigned long long)__double_as_longlong(surf.n.y);
-            rec[9] = (unsigned long long)__double_as_longlong(surf.n.z);
-        }
+        if (hits) store_record(stage + lane * kHitWords, closest, best, surf);
     }
     if (hits) {
         /* every lane of the wave, live or not: the rows of the records of the live lanes (LDS operations of one
@@ -95,6 +66,8 @@ trace_rays_kernel(const RenderParams P, const c2rt_ray *__restrict__ rays, const
         __builtin_amdgcn_wave_barrier(); /* the shadow rays below reuse the stack */
     }
     if (live && rgb) {
+        /* sample_colour's statements, written out: through the function the depth 1 - 4 instances come out with two
+         * register pairs exchanged; like this the unit's code is the measured one (profiles/query_shared.md) */
         F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
         uint32_t shadow_rays = 0;
         if (closest >= 0) c = shade<LEVELS, MLC, 0>(P, cx, mat, d, surf, shadow_rays);
@@ -120,25 +93,6 @@ test_visibility_kernel(const RenderParams P, const c2rt_segment *__restrict__ se
     visible[i] = vis ? (uint8_t)1 : (uint8_t)0;
 }
 
-template <int LEVELS>
-int launch_trace_rays_level(const RenderParams &p, const c2rt_ray *rays, uint64_t n, c2rt_ray_hit *hits, float *rgb, hipStream_t s)
-{
-    const dim3 grid((uint32_t)((n + kWave - 1) / kWave)), block(kWave);
-    const size_t stack = (size_t)p.csg_cap * kCsgLdsPerEntry, stage = hits ? (size_t)kWave * sizeof(c2rt_ray_hit) : 0;
-    const size_t lds = stack > stage ? stack : stage;
-    if (p.n_lights > 1) hipLaunchKernelGGL((trace_rays_kernel<LEVELS, true>), grid, block, lds, s, p, rays, n, hits, rgb);
-    else hipLaunchKernelGGL((trace_rays_kernel<LEVELS, false>), grid, block, lds, s, p, rays, n, hits, rgb);
-    return (int)hipGetLastError();
-}
-
-template <int LEVELS>
-int launch_test_visibility_level(const RenderParams &p, const c2rt_segment *seg, uint64_t n, uint8_t *visible, hipStream_t s)
-{
-    const dim3 grid((uint32_t)((n + kWave - 1) / kWave)), block(kWave);
-    hipLaunchKernelGGL((test_visibility_kernel<LEVELS>), grid, block, (size_t)p.csg_cap * kCsgLdsPerEntry, s, p, seg, n, visible);
-    return (int)hipGetLastError();
-}
-
 } // namespace
 
 /* the instance of the scene's CSG depth, as the frame kernels are chosen at upload; p.csg_cap = kCsgFullCap(levels) */
@@ -146,14 +100,22 @@ int launch_trace_rays(const RenderParams &p, int csg_levels, const c2rt_ray *ray
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!n || n > C2RT_MAX_RAYS || (!hits && !rgb)) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) { return launch_trace_rays_level<decltype(L)::value>(p, rays, n, hits, rgb, s); });
+    /* the staged records share the LDS with the hit stack, which a scene without CSG does not have */
+    const size_t stage = hits ? (size_t)kWave * sizeof(c2rt_ray_hit) : 0, lds = stack_lds(p) > stage ? stack_lds(p) : stage;
+    return for_csg_levels(csg_levels, [&](auto L) {
+        constexpr int LEVELS = decltype(L)::value;
+        return launch_query(p, trace_rays_kernel<LEVELS, true>, trace_rays_kernel<LEVELS, false>, ray_grid(n), lds, s, p, rays, n, hits, rgb);
+    });
 }
 
 int launch_test_visibility(const RenderParams &p, int csg_levels, const c2rt_segment *seg, uint64_t n, uint8_t *visible, void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!n || n > C2RT_MAX_RAYS) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) { return launch_test_visibility_level<decltype(L)::value>(p, seg, n, visible, s); });
+    return for_csg_levels(csg_levels, [&](auto L) {
+        hipLaunchKernelGGL((test_visibility_kernel<decltype(L)::value>), ray_grid(n), dim3(kWave), stack_lds(p), s, p, seg, n, visible);
+        return (int)hipGetLastError();
+    });
 }
 
 } // namespace c2rt

@@ -24,11 +24,6 @@
 namespace c2rt {
 namespace {
 
-constexpr int kShadeTileW = 8, kShadeTileH = kWave / kShadeTileW; /* the hit planes' tile */
-static_assert(sizeof(RenderParams) + sizeof(c2rt_shade_planes) + 16 <= 4096, "the kernel-argument segment holds at most 4 KiB");
-static_assert(sizeof(c2rt_shade_planes) == 48, "ABI layout of c2rt_shade_planes");
-static_assert(sizeof(c2rt_ray) == 48, "ABI layout of c2rt_ray");
-
 /* the three locals of the reference's shade() at its return, and bit l: light l < 32 passed
  * `lightColor.intensity() != 0 && scene.testVisibility(p + N * 1e-6, lightPos)` */
 struct ShadeParts {
@@ -151,36 +146,14 @@ shade_planes_kernel(const RenderParams P, const c2rt_shade_planes out, const uin
     using namespace exact;
     extern __shared__ __align__(16) char lds[];
     const int lane = (int)threadIdx.x;
-    const uint32_t trow = blockIdx.x / tiles_x, tcol = blockIdx.x % tiles_x; /* the grid is tiles_x * ceil(rows / kShadeTileH) */
-    const uint32_t x = tcol * kShadeTileW + (uint32_t)(lane % kShadeTileW);
-    const uint32_t r = trow * kShadeTileH + (uint32_t)(lane / kShadeTileW); /* row within this launch */
+    const TilePixel px = tile_pixel(P, lane, rows, tiles_x);
     Ctx cx;
     query_ctx(cx, P, (KArgs)__builtin_amdgcn_kernarg_segment_ptr(), lds, lane);
-    if (x < P.width && r < rows) { /* lanes past the edge: masked out before the trace */
-        /* local row -> frame row under interleaved strips, as render_tile maps it */
-        const uint32_t lr = r + row0;
-        uint32_t y = lr;
-        if (P.strip_world > 1) {
-            const uint32_t sh = P.strip_height;
-            y = ((lr / sh) * P.strip_world + P.strip_rank) * sh + lr % sh;
-        }
-        Rng rng = {0u, 0, 0};
-        D3 o, raw;
-        screen_ray<false>(cx.bad, P, (double)x, (double)y, 0, rng, o, raw);
-        const D3 d = normalized(cx.bad, raw); /* raytrace(): rt/camera.d:144-147 */
-        shade_sample<LEVELS, MLC>(P, cx, out, (size_t)r * P.width + x, o, d);
+    if (px.live) { /* lanes past the edge: masked out before the trace */
+        D3 o, d;
+        pixel_ray(cx, P, (double)px.x, (double)px.y(P, row0), o, d);
+        shade_sample<LEVELS, MLC>(P, cx, out, px.idx, o, d);
     }
-}
-
-/* six doubles of a c2rt_ray: three 16-byte loads at 8-byte alignment (load6 of c2rt_rays.hip, restated: that file's
- * object stays as it is) */
-typedef double __attribute__((ext_vector_type(2), aligned(8))) d2_t;
-DEV void load6(const void *rec, D3 &a, D3 &b)
-{
-    const d2_t *q = static_cast<const d2_t *>(rec);
-    const d2_t q0 = q[0], q1 = q[1], q2 = q[2];
-    a = mk(q0.x, q0.y, q1.x);
-    b = mk(q1.y, q2.x, q2.y);
 }
 
 /* Ray i of c2rt_trace_rays, `dir` as given: 64 consecutive rays per wave, the tail masked out before the trace */
@@ -200,29 +173,6 @@ trace_rays_shade_kernel(const RenderParams P, const c2rt_shade_planes out, const
     }
 }
 
-bool any_plane(const c2rt_shade_planes &o) { return o.node || o.albedo || o.light || o.specular || o.visible || o.rgb; }
-
-template <int LEVELS>
-int launch_shade_planes_level(const RenderParams &p, const c2rt_shade_planes &out, uint32_t row0, uint32_t rows, hipStream_t s)
-{
-    const uint32_t tiles_x = (p.width + kShadeTileW - 1) / kShadeTileW, tiles_y = (rows + kShadeTileH - 1) / kShadeTileH;
-    const dim3 grid(tiles_x * tiles_y), block(kWave); /* at most 2^16 x 2^16 pixels / 64 */
-    const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry;
-    if (p.n_lights > 1) hipLaunchKernelGGL((shade_planes_kernel<LEVELS, true>), grid, block, lds, s, p, out, row0, rows, tiles_x);
-    else hipLaunchKernelGGL((shade_planes_kernel<LEVELS, false>), grid, block, lds, s, p, out, row0, rows, tiles_x);
-    return (int)hipGetLastError();
-}
-
-template <int LEVELS>
-int launch_trace_rays_shade_level(const RenderParams &p, const c2rt_ray *rays, uint64_t n, const c2rt_shade_planes &out, hipStream_t s)
-{
-    const dim3 grid((uint32_t)((n + kWave - 1) / kWave)), block(kWave);
-    const size_t lds = (size_t)p.csg_cap * kCsgLdsPerEntry;
-    if (p.n_lights > 1) hipLaunchKernelGGL((trace_rays_shade_kernel<LEVELS, true>), grid, block, lds, s, p, out, rays, n);
-    else hipLaunchKernelGGL((trace_rays_shade_kernel<LEVELS, false>), grid, block, lds, s, p, out, rays, n);
-    return (int)hipGetLastError();
-}
-
 } // namespace
 
 /* Rows [row0, row0 + rows) of the local rows of the frame `p` describes (hit_params, c2rt_api.cpp) into planes whose
@@ -231,7 +181,12 @@ int launch_shade_planes(const RenderParams &p, int csg_levels, const c2rt_shade_
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!rows || !p.width || !any_plane(out)) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) { return launch_shade_planes_level<decltype(L)::value>(p, out, row0, rows, s); });
+    uint32_t tiles_x;
+    const dim3 grid = tile_grid(p, rows, tiles_x);
+    return for_csg_levels(csg_levels, [&](auto L) {
+        constexpr int LEVELS = decltype(L)::value;
+        return launch_query(p, shade_planes_kernel<LEVELS, true>, shade_planes_kernel<LEVELS, false>, grid, stack_lds(p), s, p, out, row0, rows, tiles_x);
+    });
 }
 
 /* The planes [n] of the caller's rays; p: query_params (c2rt_api.cpp), 0 < n <= C2RT_MAX_RAYS */
@@ -239,7 +194,10 @@ int launch_trace_rays_shade(const RenderParams &p, int csg_levels, const c2rt_ra
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!n || n > C2RT_MAX_RAYS || !rays || !any_plane(out)) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) { return launch_trace_rays_shade_level<decltype(L)::value>(p, rays, n, out, s); });
+    return for_csg_levels(csg_levels, [&](auto L) {
+        constexpr int LEVELS = decltype(L)::value;
+        return launch_query(p, trace_rays_shade_kernel<LEVELS, true>, trace_rays_shade_kernel<LEVELS, false>, ray_grid(n), stack_lds(p), s, p, out, rays, n);
+    });
 }
 
 } // namespace c2rt

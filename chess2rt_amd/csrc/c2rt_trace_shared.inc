@@ -170,6 +170,18 @@ enum Need {
  * meaningful in the kernel function; an out-of-line callee would read garbage). */
 typedef const RenderParams __attribute__((address_space(4))) *KArgs;
 
+/* The same for a batch kernel (frames, hit planes, adaptive refinement), whose parameter blocks are a table in HBM with
+ * blockIdx.y = frame: block blockIdx.y of the table through a constant-address-space pointer — scalar loads, no VGPR,
+ * exactly as a single-frame kernel re-reads its kernel-argument segment.  The pointer goes through an empty asm so
+ * that the optimiser cannot fold the address-space casts back to the global pointer it was made from (loads through
+ * that one would be vector loads: the kernel stores to global memory, so nothing proves them invariant). */
+DEV KArgs batch_block(const RenderParams *table)
+{
+    KArgs K = (KArgs)table + blockIdx.y;
+    asm volatile("" : "+s"(K));
+    return K;
+}
+
 struct Ctx {
     KArgs kargs;
     GeomP geoms;

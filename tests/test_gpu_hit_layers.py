@@ -428,3 +428,74 @@ def test_layers_see_an_updated_scene_on_the_same_stream(gpu_ctx):
     m = written(count, K)
     assert np.array_equal(rec_t.cpu().numpy().reshape(K, n, 80)[m], bits(want[0]).reshape(K, n, 80)[m])
     assert np.array_equal(bits(rgb_t.cpu().numpy()).reshape(K, n, 12)[m], bits(want[1]).reshape(K, n, 12)[m])
+
+
+# ---- 10: host chunking -----------------------------------------------------------------------------------------------------------
+
+
+# 2^18 / max_layers rays per host chunk: a second chunk of one partial wave; 3 does not divide 2^18
+@pytest.mark.parametrize("K,n", ((16, 16384 + 5), (3, 87381 + 5)))
+def test_host_chunks_of_rays_equal_the_device_call(gpu_ctx, K, n):
+    import torch
+    from test_gpu_ray_queries import eyeless_case
+
+    scene, base, _ = eyeless_case("csg_stress")
+    gpu_ctx.uploadScene(scene.desc)
+    rays = np.ascontiguousarray(np.tile(base, (n // len(base) + 1, 1))[:n])
+    rec, rgb, count = gpu_ctx.traceRayLayers(rays, K)
+    base_count = gpu_ctx.traceRayLayers(base, K, hits=False, colors=False)[2]
+    assert np.array_equal(count, base_count[np.arange(n) % len(base)])
+    s1 = torch.cuda.Stream(torch.device("cuda:0"))
+    rays_t = torch.from_numpy(rays).to("cuda:0")
+    sizes = {"hits": K * n * 80, "rgb": K * n * 12, "count": n}
+    t = {k: torch.full((v + GUARD,), SENTINEL, dtype=torch.uint8, device="cuda:0") for k, v in sizes.items()}
+    torch.cuda.synchronize()
+    gpu_ctx.traceRayLayersDevice(rays_t.data_ptr(), n, K, t["hits"].data_ptr(), t["rgb"].data_ptr(), t["count"].data_ptr(), s1.cuda_stream)
+    s1.synchronize()
+    raw = {k: t[k].cpu().numpy() for k in t}
+    for k, size in sizes.items():
+        assert (raw[k][size:] == SENTINEL).all(), "guard behind %s" % k
+    assert np.array_equal(raw["count"][:n], count)
+    m = written(count, K)
+    tail = n - (1 << 18) // K                  # the rays of the host's second chunk
+    assert m[:, -tail:].any() and (~m[:, -tail:]).any() and (~m[:, :-tail]).any()
+    hits = raw["hits"][:sizes["hits"]].reshape(K, n, 80)
+    cols = raw["rgb"][:sizes["rgb"]].reshape(K, n, 12)
+    # the caller's bytes behind a ray's final miss stay, on both sides of the host's chunk boundary (the device variant's
+    # contract; the host variant's slots there are unspecified, include/c2rt.h)
+    assert (hits[~m] == SENTINEL).all() and (cols[~m] == SENTINEL).all()
+    assert np.array_equal(hits[m], bits(rec).reshape(K, n, 80)[m]) and np.array_equal(cols[m], bits(rgb).reshape(K, n, 12)[m])
+
+
+# 640 x 30: chunks of 25 and 5 rows at 16 layers; 16400 x 2: 2^18 / 16 / width is 0, one row per chunk
+@pytest.mark.parametrize("w,h,names", ((640, 30, ALL_PLANES), (16400, 2, ("node", "dist"))), ids=("640x30", "16400x2"))
+def test_host_chunks_of_a_frame_equal_the_device_call(gpu_ctx, w, h, names):
+    import torch
+
+    K = 16
+    scene = c2.parseSceneFromFile(os.path.join(SCENES, "csg_stress.sdl"))
+    scene.setFrameSize(w, h)
+    scene.setAA(False)
+    scene.setDof(False)
+    cam, opts = scene.beginFrame(), scene.renderOpts(taps=_abi.TAPS_1)
+    gpu_ctx.uploadScene(scene.desc)
+    host = gpu_ctx.renderHitLayers(cam, opts, K, planes=names)
+    count = host["count"]
+    px = w * h
+    s1 = torch.cuda.Stream(torch.device("cuda:0"))
+    size = {name: HIT_PLANES[name][1] * np.dtype(HIT_PLANES[name][0]).itemsize for name in names}
+    t = {name: torch.full((K * px * size[name] + GUARD,), SENTINEL, dtype=torch.uint8, device="cuda:0") for name in names}
+    tc = torch.full((px + GUARD,), SENTINEL, dtype=torch.uint8, device="cuda:0")
+    torch.cuda.synchronize()
+    gpu_ctx.renderHitLayersDevice(cam, opts, K, {k: v.data_ptr() for k, v in t.items()}, tc.data_ptr(), s1.cuda_stream)
+    s1.synchronize()
+    raw_count = tc.cpu().numpy()
+    assert np.array_equal(raw_count[:px].reshape(h, w), count) and (raw_count[px:] == SENTINEL).all()
+    m = written(count.ravel(), K)
+    assert int(count[-1].max()) >= 1 and (~m[:, -w:]).any()             # layers to copy and slots to leave in the last chunk
+    for name in names:
+        raw = t[name].cpu().numpy()
+        assert (raw[K * px * size[name]:] == SENTINEL).all(), name
+        raw = raw[:K * px * size[name]].reshape(K, px, size[name])
+        assert (raw[~m] == SENTINEL).all(), name
+        assert np.array_equal(raw[m], bits(host[name]).reshape(K, px, size[name])[m]), name

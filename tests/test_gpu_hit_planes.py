@@ -342,3 +342,27 @@ def test_host_mirror_and_python_face(gpu_ctx):
     with pytest.raises(c2.C2rtError) as e:
         c2.Renderer(dof, gpu_ctx).renderHits()
     assert e.value.status == _abi.ERR_UNSUPPORTED and "depth of field" in str(e.value)
+
+
+# ---- 9: host chunking ---------------------------------------------------------------------------------------------------
+
+
+def test_host_chunks_of_a_frame_equal_the_device_call(gpu_ctx):
+    import torch
+
+    w, h = 640, 480                          # 307 200 pixels: chunks of 409 and 71 whole rows
+    scene, cam, opts = make_scene("lecture5.sdl", w, h)
+    gpu_ctx.uploadScene(scene.desc)
+    host = gpu_ctx.renderHits(cam, opts)
+    dev = torch.device("cuda:0")
+    s1 = torch.cuda.Stream(dev)
+    t = device_planes(torch, dev, w * h)
+    torch.cuda.synchronize()
+    gpu_ctx.renderHitsDevice(cam, opts, {k: v.data_ptr() for k, v in t.items()}, s1.cuda_stream)
+    s1.synchronize()
+    for name in PLANES:
+        got = t[name].cpu().numpy()
+        nb = plane_bytes(name, w * h)
+        assert got[:nb].tobytes() == bits(host[name]).tobytes(), name
+        assert (got[nb:] == SENTINEL).all(), name
+    assert 0 < int((host["node"][409:] >= 0).sum())                    # hits behind the chunk boundary

@@ -368,3 +368,71 @@ def test_python_face(gpu_ctx):
         gpu_ctx.traceRays(np.zeros((3, 5)))
     with pytest.raises(c2.C2rtError):
         gpu_ctx.traceRays(rays, hits=False, colors=False)
+
+
+# ---- 11: host chunking ------------------------------------------------------------------------------------------------
+
+CHUNKED = (1 << 18) + 5          # the host variants stage 2^18 records per chunk: a second chunk of one partial wave
+GUARD = 256                      # sentinel bytes behind each device output
+
+
+def tiled(a, n):
+    return np.ascontiguousarray(np.tile(a, (n // len(a) + 1, 1))[:n])
+
+
+def guarded_bytes(torch, size):
+    return torch.full((size + GUARD,), SENTINEL, dtype=torch.uint8, device="cuda:0")
+
+
+def payload(t, size, what):
+    raw = t.cpu().numpy()
+    assert (raw[size:] == SENTINEL).all(), "guard behind %s" % what
+    return raw[:size]
+
+
+@pytest.mark.parametrize("colours", (True, False), ids=("hits+rgb", "hits"))
+def test_host_chunks_of_rays_equal_the_device_call(gpu_ctx, colours):
+    import torch
+
+    scene, base, _ = eyeless_case("lecture5")
+    gpu_ctx.uploadScene(scene.desc)
+    n = CHUNKED
+    rays = tiled(base, n)
+    base_rec, base_rgb = gpu_ctx.traceRays(base, colors=colours)
+    rec, rgb = gpu_ctx.traceRays(rays, colors=colours)
+    reps = np.arange(n) % len(base)
+    assert np.array_equal(bits(rec), bits(base_rec[reps])), "records of the tiled rays"
+    assert 0 < int((rec["closest_node"] >= 0).sum()) < n
+    s1 = torch.cuda.Stream(torch.device("cuda:0"))
+    rays_t = torch.from_numpy(rays).to("cuda:0")
+    rec_t = guarded_bytes(torch, n * 80)
+    rgb_t = guarded_bytes(torch, n * 12) if colours else None
+    torch.cuda.synchronize()
+    gpu_ctx.traceRaysDevice(rays_t.data_ptr(), n, rec_t.data_ptr(), rgb_t.data_ptr() if colours else 0, s1.cuda_stream)
+    s1.synchronize()
+    assert payload(rec_t, n * 80, "hits").tobytes() == bits(rec).tobytes()
+    if colours:
+        assert np.array_equal(bits(rgb), bits(base_rgb[reps]))
+        assert payload(rgb_t, n * 12, "rgb").tobytes() == bits(rgb).tobytes()
+    else:
+        assert rgb is None
+
+
+def test_host_chunks_of_segments_equal_the_device_call(gpu_ctx):
+    import torch
+
+    scene, _, want = eyeless_case("lecture5")
+    gpu_ctx.uploadScene(scene.desc)
+    base = visibility_segments(scene.desc, want, 21)
+    n = CHUNKED
+    segs = tiled(base, n)
+    vis = gpu_ctx.testVisibility(segs)
+    assert np.array_equal(vis, gpu_ctx.testVisibility(base)[np.arange(n) % len(base)])
+    assert 0 < int(vis.sum()) < n
+    s1 = torch.cuda.Stream(torch.device("cuda:0"))
+    segs_t = torch.from_numpy(segs).to("cuda:0")
+    vis_t = guarded_bytes(torch, n)
+    torch.cuda.synchronize()
+    gpu_ctx.testVisibilityDevice(segs_t.data_ptr(), n, vis_t.data_ptr(), s1.cuda_stream)
+    s1.synchronize()
+    assert np.array_equal(payload(vis_t, n, "visible"), vis)
