@@ -63,7 +63,7 @@ HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/
 # over the SAME kernel objects; tests and scripts that need a hook load it with C2RT_LIB_VARIANT=diag
 DIAGNAME   := chess2rt_amd/libc2rt_diag.so
 
-all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/libground_texel_check.so tests/tap_average_check
+all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/libground_texel_check.so tests/libsphere_interior_check.so tests/tap_average_check
 
 $(BUILD):
 	mkdir -p $(BUILD)
@@ -131,6 +131,11 @@ tests/libground_fast_check.so: tests/ground_fast_check.cpp $(CSRC)/scene_plan.cp
 tests/libground_dark_check.so: tests/ground_dark_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/ground_dark_check.cpp $(CSRC)/scene_plan.cpp
 
+# host build of the sphere-interior test of the mask pre-pass and of the planner's part of it (tests/test_sphere_interior_tiles.py,
+# tests/test_gpu_sphere_tiles.py, scripts/sphere_interior_tiles.py), without ROCm
+tests/libsphere_interior_check.so: tests/sphere_interior_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
+	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/sphere_interior_check.cpp $(CSRC)/scene_plan.cpp
+
 # host build of the planner's decision which frames take the short chain for ground tiles (tests/test_ground_certain_plan.py), without ROCm
 tests/libground_certain_check.so: tests/ground_certain_plan_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/ground_certain_plan_check.cpp $(CSRC)/scene_plan.cpp
@@ -166,6 +171,6 @@ resource-usage: | $(BUILD)
 	    -c $(CSRC)/$(q).hip -o $(BUILD)/ru_$(q).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
 
 clean:
-	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/ground_certain_check tests/libground_texel_check.so tests/tap_average_check
+	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/ground_certain_check tests/libground_texel_check.so tests/libsphere_interior_check.so tests/tap_average_check
 
 .PHONY: all clean resource-usage

@@ -494,6 +494,12 @@ class Context:
         self._check(self._lib.c2rt_get_ground_bails(self._h, C.byref(n)))
         return int(n.value)
 
+    def sphereBails(self):
+        """Sphere-interior tiles handed back to the general path (cumulative; csg_void.h: the proof says 0)."""
+        n = C.c_uint64()
+        self._check(self._lib.c2rt_get_sphere_bails(self._h, C.byref(n)))
+        return int(n.value)
+
     def renderPixel(self, cam, opts, x, y):
         r = TraceResult()
         self._check(self._lib.c2rt_render_pixel(self._h, C.byref(cam), C.byref(opts), int(x), int(y), C.byref(r)))

@@ -105,7 +105,7 @@ struct c2rt_ctx {
 
     float *frame = nullptr;        /* staging frame for host-output renders */
     size_t frame_floats = 0;
-    unsigned long long *counters = nullptr; /* [0..2]: RenderParams::ray_counters (reset per counted frame); [3]: RenderParams::redo_counter (cumulative); [4]: redo_counter[1], ground tiles that left the short chain (cumulative) */
+    unsigned long long *counters = nullptr; /* [0..2]: RenderParams::ray_counters (reset per counted frame); [3]: RenderParams::redo_counter (cumulative); [4]: redo_counter[1], ground tiles that left the short chain (cumulative); [5]: redo_counter[2], sphere-interior tiles handed back to the general path (cumulative) */
     c2rt_trace_result *probe = nullptr;
     uint8_t *srgb_lut = nullptr;   /* [4097] */
     FrameScratch scratch[kScratchSlots];
@@ -626,8 +626,8 @@ int c2rt_init(int device, c2rt_ctx **out)
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_ready, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_inflight, hipEventDisableTiming));
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->counters), 5 * sizeof(unsigned long long)));
-    HIP_TRY(ctx, hipMemset(ctx->counters, 0, 5 * sizeof(unsigned long long)));
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->counters), 6 * sizeof(unsigned long long)));
+    HIP_TRY(ctx, hipMemset(ctx->counters, 0, 6 * sizeof(unsigned long long)));
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->probe), sizeof(c2rt_trace_result)));
     uint8_t lut[4097];
     build_srgb_lut(lut);
@@ -1304,6 +1304,24 @@ int c2rt_get_ground_bails(c2rt_ctx *ctx, uint64_t *out)
         HIP_TRY(ctx, hipSetDevice(c->device));
         HIP_TRY(ctx, hipDeviceSynchronize());
         HIP_TRY(ctx, hipMemcpy(&h, c->counters + 4, sizeof h, hipMemcpyDeviceToHost));
+        *out += h;
+    }
+    if (!ctx->peers.empty()) HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return C2RT_OK;
+}
+
+int c2rt_get_sphere_bails(c2rt_ctx *ctx, uint64_t *out)
+{
+    if (!ctx || !out) return C2RT_ERR_INVALID_ARG;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    unsigned long long h = 0;
+    HIP_TRY(ctx, hipMemcpy(&h, ctx->counters + 5, sizeof h, hipMemcpyDeviceToHost));
+    *out = h;
+    for (c2rt_ctx *c : ctx->peers) {
+        HIP_TRY(ctx, hipSetDevice(c->device));
+        HIP_TRY(ctx, hipDeviceSynchronize());
+        HIP_TRY(ctx, hipMemcpy(&h, c->counters + 5, sizeof h, hipMemcpyDeviceToHost));
         *out += h;
     }
     if (!ctx->peers.empty()) HIP_TRY(ctx, hipSetDevice(ctx->device));

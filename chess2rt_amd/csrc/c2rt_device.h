@@ -249,7 +249,8 @@ struct RenderParams {
     unsigned long long *ray_counters; /* [3] primary rays, shadow rays, CSG hit lists that reached the cap (nullable) */
     /* tiles that the production instances rendered a second time through the compiler's divide / sqrt
      * because a lane met an operand outside a lean window (c2rt_trace.inc); cumulative, never null.  [1]: ground tiles
-     * that left the short chain (ground_tile_certain) */
+     * that left the short chain (ground_tile_certain); [2]: sphere-interior tiles handed back to the general path
+     * (sphere_tile) */
     unsigned long long *redo_counter;
     /* pixel probe */
     int32_t probe_x, probe_y;

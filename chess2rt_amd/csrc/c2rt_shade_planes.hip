@@ -55,7 +55,7 @@ DEV ShadeParts shade_parts(const RenderParams &P, const Ctx &cx, const Mat &mat,
                     const D3 from = h.p + N * 1e-6;
                     double cosTheta, cosGamma;
                     F3 baseLight;
-                    light_terms(cx, L, lightPos, h.p, N, rd, phong, cosTheta, baseLight, cosGamma);
+                    light_terms(cx.bad, L, lightPos, h.p, N, rd, phong, cosTheta, baseLight, cosGamma);
                     const bool visible = test_visibility<LEVELS, 0>(cx, from, lightPos, cx.shadow_mask0, cx.shadow_ground_only);
                     if (visible) {
                         word = 1u;
@@ -90,7 +90,7 @@ DEV ShadeParts shade_parts(const RenderParams &P, const Ctx &cx, const Mat &mat,
                     if ((L->lit & 1u) && ((vis >> (l - l0)) & 1u)) {
                         double cosTheta, cosGamma;
                         F3 baseLight;
-                        light_terms(cx, L, ld3(L->pos), p, N, rd, phong, cosTheta, baseLight, cosGamma);
+                        light_terms(cx.bad, L, ld3(L->pos), p, N, rd, phong, cosTheta, baseLight, cosGamma);
                         if (cosTheta > 0) avgColor = avgColor + baseLight * (float)cosTheta;
                         if (phong & (cosGamma > 0))
                             avgSpecular = avgSpecular + baseLight * c2_pow_f32(cosGamma, exponent) * strength;

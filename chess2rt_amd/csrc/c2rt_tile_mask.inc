@@ -14,7 +14,8 @@
  * a tile and loops over the nodes (their rectangles and hulls are scalar loads), 64 tiles per wave; the frame
  * kernel reads the four words with one scalar load.  out: {primary mask, shadow mask for light 0,
  * bit 0 = primary rays reach the ground plane only | bit 1 = and so do the shadow rays | bit 2 = primary-ground and every
- * shadow ray occluded (dark), 0}. */
+ * shadow ray occluded (dark) | bit 3 = every primary ray's closest hit is on the one Sphere node left in the primary mask
+ * beside the ground and no other node can occlude its shadow rays (sphere-interior), 0}. */
 /* Where the tile in tile row `trow` of the table (row 0 = local row RenderParams::mask_row0), tile column `tcol`
  * keeps its four words: tile rows r, r + 8, r + 16, ... of a launch run on the same XCD (round-robin dispatch,
  * render_tile), so the table is laid out in eight row classes — each L2 fetches its own eighth once instead of
@@ -187,9 +188,29 @@ DEV void tile_mask_entry(const RenderParams &P, KArgs K, const VoidCull &V, cons
         }
         ground_only = (smask0 & (0xFFFFFFFFu >> (32u - nn))) == (1u << gnode);
     }
+    /* Sphere-interior tile (csg_void.h, "Sphere-interior tiles"): after every test above the primary mask holds ONE Sphere
+     * node the host marked (SphereCull::interior), the ground plane and nothing else, every primary ray hits that sphere in
+     * front of the ground, and nothing else can occlude the shadow rays.  Only tiles that keep such a sphere get here; its
+     * radius comes from the node's own record (a scalar load). */
+    bool interior = false;
+    if (__builtin_expect(S.interior != 0u, 0) && nn >= 1u && nn <= 32u) { /* (unlikely: laid out behind the rest, which a frame
+                                                                          * without the claim then runs as it did before) */
+        const uint32_t live = pmask & (0xFFFFFFFFu >> (32u - nn));
+        const uint32_t gbit = gnode >= 0 ? 1u << gnode : 0u;
+        const uint32_t rest = live & ~gbit;
+        if ((live & gbit) == gbit && rest && !(rest & (rest - 1u)) && (rest & S.interior)) {
+            for (uint32_t j = 0; j < S.n; ++j) {
+                const SphereNode &sn = S.s[j];
+                if ((1u << sn.node) != rest) continue;
+                if (!have_pcone) { pcone = primary_cone(); have_pcone = true; }
+                const double R = ((NodeP)P.nodes)[sn.node].g.p[3];
+                interior = sphere_interior_tile(P.cam.pos, pcone, S, j, R, V, smask0, nn, gnode, P.ground_y, P.n_lights != 0u);
+            }
+        }
+    }
     out[0] = pmask;
     out[1] = smask0;
-    out[2] = (primary_ground ? 1u : 0u) | (ground_only ? 2u : 0u) | (dark ? 4u : 0u);
+    out[2] = (primary_ground ? 1u : 0u) | (ground_only ? 2u : 0u) | (dark ? 4u : 0u) | (interior ? 8u : 0u);
     /* shadow masks of the further culled lights (second table): the same predicate as light 0's view-pyramid part */
     out[3] = 0;
     out[4] = out[5] = out[6] = 0xFFFFFFFFu;

@@ -814,7 +814,7 @@ DEV F3 base_light(Oob &bad, LightP L, double r2)
     }
     return ldf3(L->color) / r2f;
 }
-DEV void light_terms(const Ctx &cx, LightP L, D3 lightPos, D3 p, D3 N, D3 rd, bool phong, double &cosTheta, F3 &baseLight, double &cosGamma)
+DEV void light_terms(Oob &bad, LightP L, D3 lightPos, D3 p, D3 N, D3 rd, bool phong, double &cosTheta, F3 &baseLight, double &cosGamma)
 {
     /* squaredMagnitude(p - lightPos) == squaredMagnitude(lightPos - p) bit for bit (IEEE a - b is
      * exactly -(b - a), and the squares drop the sign): one vector, one sum of squares for both
@@ -822,10 +822,10 @@ DEV void light_terms(const Ctx &cx, LightP L, D3 lightPos, D3 p, D3 N, D3 rd, bo
     const D3 lv = lightPos - p;
     const double r2 = sqmag(lv);
     double rlen, rinv;
-    len_inv(cx.bad, r2, rlen, rinv);
+    len_inv(bad, r2, rlen, rinv);
     const D3 lightDir = mk(lv.x * rinv, lv.y * rinv, lv.z * rinv);
     cosTheta = dot(lightDir, N);
-    baseLight = base_light(cx.bad, L, r2);
+    baseLight = base_light(bad, L, r2);
     cosGamma = 0;
     if (phong) {
         /* reflect(-lightDir, N) — rt/imported_types.d:62-67 */
@@ -833,7 +833,7 @@ DEV void light_terms(const Ctx &cx, LightP L, D3 lightPos, D3 p, D3 N, D3 rd, bo
         /* (the mirror image of a unit vector in a unit normal is unit up to rounding: the integer form) */
         const D3 rv = ml - N * (2 * dot(ml, N));
         double rl, ri;
-        len_inv_unit(cx.bad, sqmag(rv), rl, ri);
+        len_inv_unit(bad, sqmag(rv), rl, ri);
         const D3 R = rv * ri;
         cosGamma = dot(R, -rd);
     }
@@ -864,7 +864,7 @@ DEV F3 shade(const RenderParams &P, const Ctx &cx, const Mat &mat, D3 rd, const 
                 const D3 from = h.p + N * 1e-6;
                 double cosTheta, cosGamma;
                 F3 baseLight;
-                light_terms(cx, L, lightPos, h.p, N, rd, phong, cosTheta, baseLight, cosGamma);
+                light_terms(cx.bad, L, lightPos, h.p, N, rd, phong, cosTheta, baseLight, cosGamma);
                 C2RT_REGION_BEGIN(cx, kRegShadow)
                 const bool visible = test_visibility<LEVELS, PO>(cx, from, lightPos, cx.shadow_mask0, cx.shadow_ground_only);
                 C2RT_REGION_END(cx, kRegShadow)
@@ -907,7 +907,7 @@ DEV F3 shade(const RenderParams &P, const Ctx &cx, const Mat &mat, D3 rd, const 
                 if ((L->lit & 1u) && ((vis >> (l - l0)) & 1u)) {
                     double cosTheta, cosGamma;
                     F3 baseLight;
-                    light_terms(cx, L, ld3(L->pos), p, N, rd, phong, cosTheta, baseLight, cosGamma);
+                    light_terms(cx.bad, L, ld3(L->pos), p, N, rd, phong, cosTheta, baseLight, cosGamma);
                     if (cosTheta > 0) avgColor = avgColor + baseLight * (float)cosTheta;
                     if (phong & (cosGamma > 0))
                         avgSpecular = avgSpecular + baseLight * c2_pow_f32(cosGamma, exponent) * strength;
@@ -1396,6 +1396,152 @@ DEV int ground_tile_certain(const RenderParams &P, KArgs K, const uint32_t trow,
     return kGroundDone;
 }
 
+/* ------------------------------------------------------------------ */
+/* sphere-interior tiles: a straight-line path of their own (lean:: only) */
+/* ------------------------------------------------------------------ */
+/*
+ * A tile of which the mask pre-pass has proven (bit 3 of the mask table's third word; csg_void.h, "Sphere-interior
+ * tiles") that every primary ray gets its closest hit on ONE Sphere node under the identity matrix — `node`, the one bit
+ * of the primary mask beside the ground's — and that no other node can occlude its shadow rays towards the one light,
+ * in a frame and on a node the host found eligible (SphereCull::interior: Lambert or Phong over a plain colour or a
+ * bitmap).  Rendered whole — tap loop, samples, store — by code that knows all of that.  It performs the IEEE operations
+ * of the general path for such a tile, on the same operands, in the same order: screen_ray, normalized, make_ray,
+ * node_intersect's offset subtraction and sphere_intersect<kFull> (against the limit of a ray that has hit nothing: the
+ * proof says the ground is farther), the sphere branch of leaf_surface and hit_surface, faceforward, the bitmap's
+ * u,v (c2_sphere_uv_bitmap) and texel blend (bitmap_color's arithmetic in front of bitmap_filtered_uniform, which is
+ * bitmap_filtered bit for bit), light_terms, test_visibility's arithmetic for that ONE node (len_inv, make_ray, the
+ * offset, sphere_intersect<kBool> against the light's distance), the Lambert and Phong terms of shade(), the tap sum,
+ * its division by the tap count and the store; and the oob_notes of all of
+ * it, so that a lane outside a lean window sends the tile to exact:: as before.  What it does not carry: the node loop
+ * with its per-lane best-hit merge, `closest`, the pass over distinct closest nodes, a Mat in vector registers, the
+ * ground plane's test, CSG, LDS.  Material, texture descriptor, sphere record and light are wave-uniform: read per
+ * sample through the re-read kernel-argument pointer into scalar registers; shader and texture kind are scalar branches.
+ *
+ * If any lane's sphere test misses, the proof was wrong: the wave writes nothing, counts the tile (redo_counter[2],
+ * c2rt_get_sphere_bails) and returns kGroundBail; the general path below then renders it as if this function did not
+ * exist.  Returns per lane, like ground_tile. */
+template <int PO>
+DEV int sphere_tile(const RenderParams &P, KArgs K, const uint32_t trow, const uint32_t bcol, const uint32_t node)
+{
+    static_assert(!(PO & kSpecPlanes), "the planes-only instances have no mask table");
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const uint32_t tcol = bcol * kWavesPerBlock + wave;
+    const uint32_t x = tcol * kTileW + (lane % kTileW);
+    const uint32_t lr0 = trow * kTileH + (lane / kTileW);
+    if (x >= P.width || lr0 >= P.local_rows) return kGroundDone;
+    const uint32_t lr = lr0 + P.row_offset;
+    const uint32_t y = frame_row(P, lr);
+    const uint32_t ntaps = P.taps;
+
+    Oob bad;
+    oob_init(bad);
+    bool missed = false;
+    F3 accum = mkf(0, 0, 0);
+#pragma unroll 1
+    for (uint32_t s = 0; s < ntaps; ++s) {
+        KArgs Kt = K;
+        asm volatile("" : "+s"(Kt));
+        const RenderParams &Pt = *(const RenderParams *)Kt;
+        Rng rng = {0u, 0, 0};
+        D3 o, raw;
+        screen_ray<0>(bad, Pt, (double)x + k_aa_x[s], (double)y + k_aa_y[s], 0, rng, o, raw);
+        const D3 d = normalized(bad, raw);
+        NodeP N = (NodeP)Pt.nodes + node;
+        GeomP G = &N->g;
+        const bool has_off = !(N->flags & kNodeZeroOffset); /* wave-uniform */
+        /* raytrace(): make_ray, then Node.intersect + Sphere.intersect on the one node */
+        const RayW ray = make_ray(bad, o, d);
+        Hit h;
+        {
+            ORay rc;
+            rc.o = ray.o;
+            if (has_off) rc.o = rc.o - ld3(N->off);
+            rc.d = ray.dn;
+            rc.A = ray.A;
+            prep_dir(rc, kPrepA);
+            h.dist = 1e99 * ray.len;
+            h.p = ray.o; /* (a lane that misses — never, by the proof — reads a defined point below) */
+            missed |= !sphere_intersect<kFull>(bad, G, N->geom, rc, h, false);
+        }
+        /* hit_surface: the sphere branch of leaf_surface, the identity-matrix normal, the offset */
+        Mat mat;
+        load_mat(N, mat);
+        const D3 pc = h.p - ld3(G->p);
+        D3 n = normalized(bad, pc);
+        F3 diffuse = mat.color;
+        if (mat.tex_type >= 0) { /* wave-uniform: a bitmap (the host leaves every other texture to the general path) */
+            double u, v;
+            const double sc = (double)__uint_as_float(mat.td[2]);
+            sphere_uv(pc.x, pc.z, pc.y / G->p[3], UVWant{kUVBitmap, sc}, u, v);
+            /* bitmap_color, its texels through the uniform fetch (td[5] is 0 here: the host's limit) */
+            u *= sc;
+            v *= sc;
+            u = u - floor(u);
+            v = v - floor(v);
+            const uint32_t w = mat.td[0], hgt = mat.td[1];
+            diffuse = bitmap_filtered_uniform(Pt.texels, mat.td[4], w, hgt, (float)u * (float)w, (float)v * (float)hgt);
+        }
+        {
+            double len, inv;
+            len_inv_unit(bad, sqmag(n), len, inv);
+            n = n * inv;
+        }
+        D3 p = h.p;
+        if (has_off) p = p + ld3(N->off);
+        /* shade() */
+        const bool phong = mat.shader_type == C2RT_SHADER_PHONG; /* wave-uniform */
+        const D3 Nf = dot(d, n) < 0 ? n : -n; /* faceforward */
+        F3 lightContrib = mkf(Pt.ambient[0], Pt.ambient[1], Pt.ambient[2]);
+        F3 specular = mkf(0, 0, 0);
+        if (Pt.n_lights) {
+            LightP L = (LightP)Pt.lights;
+            F3 avgColor = mkf(0, 0, 0), avgSpecular = mkf(0, 0, 0);
+            if (L->lit & 1u) {
+                const D3 lightPos = ld3(L->pos);
+                const D3 from = p + Nf * 1e-6;
+                double cosTheta, cosGamma;
+                F3 baseLight;
+                light_terms(bad, L, lightPos, p, Nf, d, phong, cosTheta, baseLight, cosGamma);
+                /* test_visibility for the one node that can occlude: the sphere itself */
+                const D3 sraw = lightPos - from;
+                double rlen, rinv;
+                len_inv(bad, sqmag(sraw), rlen, rinv);
+                const RayW sray = make_ray(bad, from, mk(sraw.x * rinv, sraw.y * rinv, sraw.z * rinv));
+                ORay rc;
+                rc.o = sray.o;
+                if (has_off) rc.o = rc.o - ld3(N->off);
+                rc.d = sray.dn;
+                rc.A = sray.A;
+                prep_dir(rc, kPrepA);
+                Hit t;
+                t.dist = rlen * sray.len;
+                const bool visible = !sphere_intersect<kBool>(bad, G, N->geom, rc, t, false);
+                if (visible) {
+                    if (cosTheta > 0) avgColor = avgColor + baseLight * (float)cosTheta;
+                    if (phong & (cosGamma > 0))
+                        avgSpecular = avgSpecular + baseLight * c2_pow_f32(cosGamma, mat.exponent) * mat.strength;
+                }
+            }
+            lightContrib = lightContrib + avgColor;
+            specular = specular + avgSpecular;
+        }
+        const F3 res = diffuse * lightContrib;
+        const F3 c = phong ? res + specular : res;
+        accum = s == 0 ? c : accum + c;
+    }
+    /* `accum / 5` as render_tile has it, not tap_average: a Phong lobe's far tail (cos^80) leaves channels far below that
+     * routine's window, and every such tile would be rendered again */
+    if (ntaps > 1) accum = accum / (float)ntaps;
+    if (__ballot(missed)) {
+        if (lane == (int)__builtin_ctzll(__ballot(true))) atomicAdd(P.redo_counter + 2, 1ull); /* c2rt_get_sphere_bails */
+        return kGroundBail;
+    }
+    if (__ballot(oob_any(bad))) return kGroundRedo;
+    store_pixel(P, (size_t)(P.frame_rows ? y : lr) * P.width + x, accum);
+    return kGroundDone;
+}
+
 /*
  * Frame kernel: Renderer.renderRT passes 2 and 3b (rt/renderer.d:133-142,
  * 183-186) fused — all taps of a pixel are accumulated in registers in the
@@ -1433,7 +1579,7 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
      * light, and is the ground plane all that is left?  One scalar load from the table the pre-pass kernel
      * wrote for this frame (tile_mask_entry). */
     uint32_t pmask = 0xFFFFFFFFu, smask0 = 0xFFFFFFFFu, mask_slot = 0;
-    bool ground_only = false, primary_ground = false, dark = false;
+    bool ground_only = false, primary_ground = false, dark = false, interior = false;
     Oob tile_bad;
     oob_init(tile_bad);
     if constexpr (!DOF) {
@@ -1446,6 +1592,7 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
             primary_ground = (m.z & 1u) != 0;
             ground_only = (m.z & 2u) != 0;
             dark = (m.z & 4u) != 0;
+            interior = (m.z & 8u) != 0;
         }
     }
 
@@ -1467,6 +1614,19 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
                 asm volatile("" : "+s"(Kg), "+s"(trow_g), "+s"(bcol_g), "+s"(dark_g));
             }
             const int g = ground_tile<PO>(*(const RenderParams *)Kg, Kg, trow_g, bcol_g, dark_g != 0);
+            if (!__ballot(g == kGroundBail)) return g == kGroundRedo;
+        }
+        /* Sphere-interior tile (bit 3: every primary ray's closest hit is on the one Sphere node the primary mask keeps
+         * beside the ground, and nothing else can occlude its shadow rays): sphere_tile renders it, or — a lane's sphere
+         * test missed, which the proof rules out — writes nothing and the tile goes on below.  The same kind of call. */
+        if (__builtin_expect(interior, 0)) { /* wave-uniform; unlikely: the block is laid out behind the general code, where a
+                                              * frame that never takes it does not fetch past it */
+            uint32_t rest = pmask & (0xFFFFFFFFu >> (32u - P.n_nodes));
+            if (P.ground_node >= 0) rest &= ~(1u << P.ground_node);
+            KArgs Ks = K;
+            uint32_t trow_s = trow, bcol_s = bcol, node_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)__builtin_ctz(rest | 0x80000000u));
+            asm volatile("" : "+s"(Ks), "+s"(trow_s), "+s"(bcol_s), "+s"(node_s));
+            const int g = sphere_tile<PO>(*(const RenderParams *)Ks, Ks, trow_s, bcol_s, node_s);
             if (!__ballot(g == kGroundBail)) return g == kGroundRedo;
         }
     }

@@ -199,7 +199,11 @@ struct SphereNode {
 
 /* the per-frame sphere argument of the mask pre-pass (tile_masks_kernel), next to VoidCull (whose light0 it uses) */
 struct SphereCull {
-    uint32_t n, pad;
+    uint32_t n;
+    /* bit k: node k (an entry of s[]) may be claimed as the one sphere of a sphere-interior tile ("Sphere-interior tiles",
+     * below): the frame can take lean::sphere_tile and the node's material is one that path carries (host:
+     * sphere_cull_of).  Sits in what was padding. */
+    uint32_t interior;
     double reach;                  /* the scale the margins were derived for: the shadow test's footprint limit */
     SphereNode s[kMaxSphereNodes];
 };
@@ -415,6 +419,186 @@ C2RT_VOID_FN bool tile_dark_by(const double light[3], const double sdir[4][3], b
         dark = dark || ok;
     }
     return dark;
+}
+
+/* ---- Sphere-interior tiles -----------------------------------------------------------------------------------
+ * The third claim about a Sphere node (c, R) under an identity matrix: EVERY primary ray of the tile gets its closest
+ * hit on it, and no other node can occlude the tile's shadow rays towards light 0 — bit 3 of the mask table's third
+ * word; lean::sphere_tile (c2rt_trace.inc) renders such a tile with that one sphere and nothing else.  m = sphere_margin
+ * = rp - R, rp = SphereNode::rp, R from the node's own record.
+ *
+ * (a) Every ray hits, in front of the eye (cone_inside_ball).  The tile's pyramid lies in its cone (pyramid_cone): axis
+ * u, half angle theta.  With d = |c - eye| and phi the angle between u and c - eye, a ray of the cone makes an angle psi
+ * in [max(0, phi - theta), phi + theta] with c - eye and passes the centre at d sin(psi).  phi + theta < 90 degrees and
+ * d sin(phi + theta) <= R - m put every ray within R - m of c: the exact discriminant of Sphere.intersect is
+ * 4 (R^2 - d'^2) >= 4 (2 R m - m^2) > 4 R m for a unit direction, against a rounding below 1e-14 |o - c|^2 (the
+ * silhouette test's bound, sign reversed; |o - c| <= scale for a primary ray, and m >= 1e-9 scale^2 / R).  d >= R + m
+ * keeps the eye outside: C > 0, both roots positive, the reference reports the near one, t(psi) = d cos(psi) -
+ * sqrt(R^2 - d^2 sin^2(psi)), which grows with psi — the hit points lie at ray parameters [t_lo, t_hi] = [t(psi_min),
+ * t(psi_max)].  Sines and cosines come from the addition theorems: no inverse trigonometry.
+ *
+ * (b) Nothing is nearer.  The caller (tile_mask_entry) grants the claim only where the primary mask, after every other
+ * test, holds this node, the ground plane and nothing else; unboxed nodes never leave the mask.  Ground: the eye above
+ * the plane and the padded ball strictly above it (c.y - rp > ground_y + tol): a ray that reaches the plane at all
+ * enters the ball at least rp - R = m earlier, so whichever of the two Node.intersect sees first, `mult > dist`
+ * (Plane) resp. `sol > dist` (Sphere) keeps the sphere's hit.
+ *
+ * (c) Shadow rays towards light 0.  They start at p + N 1e-6, p a hit point: eye + t w, t in [t_lo, t_hi], w within theta
+ * of u.  |t w - tm u| <= t |w - u| + |t - tm| <= t_hi tan(theta) + (t_hi - t_lo) / 2 for tm the interval's middle, so the
+ * origins lie in the ball (q, rho), q = eye + tm u, rho = that + 2 m (the 1e-6 step, the rounding of p and of this
+ * bound, with orders of magnitude to spare).  The segments from that ball to the light lie in the cone with apex L
+ * around q - L of half angle asin(rho / |q - L|) (patch_shadow_cone); another node cannot occlude when the cone misses
+ * its padded ball (Sphere: shadow_cone_misses_ball with its rp; a CsgDiff candidate: the ball around its padded box, grown by
+ * m, which is at least void_margin).  Beyond the light a ray leaves that cone, so — as for the ground tiles' shadow tests — the other node must
+ * lie strictly on the ground's side of the light's height (its flags bit 1) and so must the patch (q.y + rho < L.y -
+ * tol): every ray climbs to the light and none continues into the node.  The ground: patch and light strictly above the
+ * plane, so Plane.intersect either sees the ray leave (dir.y > -1e-9) or finds the crossing beyond the light.  The sphere
+ * itself is not part of the claim: the path tests it per sample.
+ * Only the arrangement "eye, ball and light above the ground" is claimed; the mirrored one stays on the general path. */
+
+/* (a): true if every ray of the cone k around `apex` passes within R - m of c and starts outside the ball (c, R + m);
+ * [t_lo, t_hi] then bound the near root along every such ray.  1e-9 relative and 1e-9 d absolute to spare, as in
+ * cone_misses_ball.  Refuses a cone of 90 degrees or more and any non-finite operand. */
+C2RT_VOID_FN bool cone_inside_ball(const double apex[3], const PyramidCone &k, const double c[3], double R, double m, double &t_lo,
+                                   double &t_hi)
+{
+    t_lo = t_hi = 0;
+    if (!k.ok) return false;
+    const double w0 = c[0] - apex[0], w1 = c[1] - apex[1], w2 = c[2] - apex[2];
+    const double a = w0 * k.u[0] + w1 * k.u[1] + w2 * k.u[2];
+    const double e0 = w0 - a * k.u[0], e1 = w1 - a * k.u[1], e2 = w2 - a * k.u[2];
+    const double lat = sqrt(e0 * e0 + e1 * e1 + e2 * e2);
+    const double d = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+    const double sec = sqrt(1.0 + k.tan_t * k.tan_t);
+    if (!(d < 1e150) || !(R < 1e150) || !(R > 0) || !(m > 0) || !(m < R) || !(sec < 1e150) || !(a > 0)) return false;
+    if (!(d >= (R + m) * (1 + 1e-9))) return false; /* the eye in (or at) the padded ball */
+    const double inv_d = 1.0 / d, ct = 1.0 / sec; /* (two divisions for four quotients: the pre-pass is a latency chain) */
+    const double sp = lat * inv_d, cp = a * inv_d, st = k.tan_t * ct;
+    const double s_hi = sp * ct + cp * st, c_hi = cp * ct - sp * st; /* phi + theta */
+    if (!(c_hi > 1e-9)) return false;
+    if (!(d * s_hi * (1 + 1e-9) + 1e-9 * d <= R - m)) return false;
+    double s_lo = sp * ct - cp * st, c_lo = cp * ct + sp * st; /* phi - theta, or 0 where the axis' own ray is inside */
+    if (!(s_lo > 0)) { s_lo = 0; c_lo = 1; }
+    t_lo = d * c_lo - sqrt(R * R - d * d * s_lo * s_lo);
+    t_hi = d * c_hi - sqrt(R * R - d * d * s_hi * s_hi);
+    return t_lo > 0 && t_hi >= t_lo && t_hi < 1e150;
+}
+
+/* (c): the ball (q, rho) that holds every shadow origin of the tile, and the cone from `light` that holds the segments
+ * from it to the light.  false: the light in (or near) that ball, or non-finite. */
+struct ShadowCone {
+    double u[3];
+    double tan_t, sec; /* of the half angle: rho / sqrt(D^2 - rho^2) and D / sqrt(D^2 - rho^2), rounded up by 1e-9 */
+    bool ok;
+};
+
+C2RT_VOID_FN bool patch_shadow_cone(const double apex[3], const PyramidCone &k, double t_lo, double t_hi, double m, const double light[3],
+                                    double q[3], double &rho, ShadowCone &sc)
+{
+    const double tm = 0.5 * (t_lo + t_hi);
+    rho = (0.5 * (t_hi - t_lo) + t_hi * k.tan_t) * (1 + 1e-9) + 2 * m + 1e-9 * t_hi;
+    double v[3], D2 = 0;
+    for (int i = 0; i < 3; ++i) {
+        q[i] = apex[i] + tm * k.u[i];
+        v[i] = q[i] - light[i];
+        D2 += v[i] * v[i];
+    }
+    const double D = sqrt(D2);
+    sc.ok = false;
+    if (!(D < 1e150) || !(rho < 1e150) || !(D > 2 * rho)) return false;
+    const double inv_D = 1.0 / D, inv_h = 1.0 / sqrt(D2 - rho * rho);
+    for (int i = 0; i < 3; ++i) sc.u[i] = v[i] * inv_D;
+    sc.tan_t = rho * inv_h * (1 + 1e-9);
+    sc.sec = D * inv_h * (1 + 1e-9);
+    sc.ok = sc.tan_t < 1e150 && sc.sec < 1e150;
+    return sc.ok;
+}
+
+/* cone_misses_ball for the shadow cone, without a square root: the pre-pass evaluates it in one lane per tile, once per
+ * node left in the shadow mask, behind everything else the tile's wave has to do.  The same geometry — the distance
+ * from c to the solid cone exceeds rp — with the two lengths compared by their squares: d is bounded from above by the
+ * 1-norm in the padding term (a larger `need`: never a wrong miss), the apex-in-ball test is d^2 > need^2, "c projects
+ * onto the rim ray" is a >= 0 or lat^2 tan^2 >= a^2, and lat > x is lat^2 > x^2 for x > 0 and true for x <= 0. */
+C2RT_VOID_FN bool shadow_cone_misses_ball(const double apex[3], const ShadowCone &k, const double c[3], double rp)
+{
+    if (!k.ok) return false;
+    const double w0 = c[0] - apex[0], w1 = c[1] - apex[1], w2 = c[2] - apex[2];
+    const double a = w0 * k.u[0] + w1 * k.u[1] + w2 * k.u[2];
+    const double e0 = w0 - a * k.u[0], e1 = w1 - a * k.u[1], e2 = w2 - a * k.u[2];
+    const double lat2 = e0 * e0 + e1 * e1 + e2 * e2, d2 = w0 * w0 + w1 * w1 + w2 * w2;
+    const double d1 = void_abs(w0) + void_abs(w1) + void_abs(w2);
+    if (!(d1 < 1e150) || !(rp < 1e150) || !(rp > 0)) return false; /* non-finite or absurd */
+    const double need = rp * (1 + 1e-9) + 1e-9 * d1;
+    if (!(d2 > need * need * (1 + 1e-9))) return false; /* the apex in (or at) the padded ball */
+    if (a >= 0 || lat2 * k.tan_t * k.tan_t >= a * a) {
+        const double x = (a * k.tan_t + need * k.sec) * (1 + 1e-9);
+        return !(x > 0) || lat2 > x * x * (1 + 1e-9);
+    }
+    return true; /* behind the apex, and farther from it than rp */
+}
+
+/* the ball around a CsgDiff candidate's padded box (VoidNode: lo, hi), grown by m */
+C2RT_VOID_FN void box_ball(const VoidNode &v, double m, double c[3], double &rp)
+{
+    double r2 = 0;
+    for (int i = 0; i < 3; ++i) {
+        c[i] = 0.5 * (v.lo[i] + v.hi[i]);
+        const double h = 0.5 * (v.hi[i] - v.lo[i]);
+        r2 += h * h;
+    }
+    rp = sqrt(r2) * (1 + 1e-9) + m;
+}
+
+/* (b) and (c) for a tile whose cone has passed (a) with the entry depths [t_lo, t_hi] (m = the sphere's margin): the ground
+ * below the padded ball and the eye, and every other node of the shadow mask missed by the cone from the light. */
+C2RT_VOID_FN bool sphere_interior_rest(const double eye[3], const PyramidCone &k, const SphereCull &S, uint32_t self, double m, double t_lo,
+                                       double t_hi, const VoidCull &V, uint32_t smask0, uint32_t n_nodes, int ground_node,
+                                       double ground_y, bool has_light)
+{
+    const SphereNode &sn = S.s[self];
+    const double tol = 1e-6 + 1e-9 * (void_abs(ground_y) + void_abs(sn.c[1]) + sn.rp + void_abs(eye[1]));
+    if (ground_node >= 0 && !(eye[1] > ground_y + tol && sn.c[1] - sn.rp > ground_y + tol)) return false;
+    if (!has_light) return true;
+    const double *L = V.light0;
+    double q[3], rho;
+    ShadowCone sc;
+    if (!patch_shadow_cone(eye, k, t_lo, t_hi, m, L, q, rho, sc)) return false;
+    const double ltol = 1e-6 + 1e-9 * (void_abs(L[1]) + void_abs(q[1]) + rho + void_abs(ground_y));
+    if (ground_node >= 0 && !(L[1] > ground_y + ltol)) return false;
+    uint32_t others = smask0 & (n_nodes >= 32u ? 0xFFFFFFFFu : ((1u << n_nodes) - 1u)) & ~(1u << sn.node);
+    if (ground_node >= 0) others &= ~(1u << ground_node);
+    if (!others) return true;
+    if (!(q[1] + rho < L[1] - ltol)) return false; /* the patch strictly below the light's height */
+    for (uint32_t j = 0; j < S.n; ++j) {
+        const SphereNode &o = S.s[j];
+        if (j == self || !((others >> o.node) & 1u)) continue;
+        if (!(o.flags & 2u) || !shadow_cone_misses_ball(L, sc, o.c, o.rp)) return false;
+        others &= ~(1u << o.node);
+    }
+    for (uint32_t j = 0; j < V.n; ++j) {
+        const VoidNode &o = V.v[j];
+        if (!((others >> o.node) & 1u)) continue;
+        double bc[3], brp;
+        box_ball(o, m, bc, brp);
+        if (!(o.flags & 2u) || !shadow_cone_misses_ball(L, sc, bc, brp)) return false;
+        others &= ~(1u << o.node);
+    }
+    return others == 0u; /* a node neither table knows: no claim */
+}
+
+/* One tile, cone k of its primary pyramid around `eye`: the claim above for entry `self` of S (radius R from the node's
+ * record), given the shadow mask smask0 the other tests left (bits at and above n_nodes ignored), the ground node (-1:
+ * none; then the scene must have no unboxed node at all, which the caller's primary-mask condition implies) and light 0
+ * (has_light = false: no shadow ray is cast).  The primary-mask condition (b) is the caller's. */
+C2RT_VOID_FN bool sphere_interior_tile(const double eye[3], const PyramidCone &k, const SphereCull &S, uint32_t self, double R,
+                                       const VoidCull &V, uint32_t smask0, uint32_t n_nodes, int ground_node, double ground_y,
+                                       bool has_light)
+{
+    const SphereNode &sn = S.s[self];
+    const double m = sn.rp - R;
+    double t_lo, t_hi;
+    if (!cone_inside_ball(eye, k, sn.c, R, m, t_lo, t_hi)) return false;
+    return sphere_interior_rest(eye, k, S, self, m, t_lo, t_hi, V, smask0, n_nodes, ground_node, ground_y, has_light);
 }
 
 } // namespace c2rt

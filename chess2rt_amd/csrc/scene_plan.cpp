@@ -1184,6 +1184,36 @@ SphereCull sphere_cull_of(const ScenePlan &plan, const DiagKnobs &knobs, const R
         s.flags &= flags_mask;
         if (s.flags) sc.s[sc.n++] = s;
     }
+    /* Sphere-interior tiles through lean::sphere_tile (c2rt_trace.inc; csg_void.h): the frame conditions of the ground-tile
+     * path — a mask table, at most one light, no depth of field, no stereo, no nested CsgOp (the instances that carry the
+     * path), not a counted frame (RenderParams::ray_counters is set by then: those run exact:: throughout) — and per node a material the path carries:
+     * Lambert or Phong over a plain colour or a bitmap that bitmap_filtered_uniform can address (within the pool's first
+     * 2^28 texels, sides below 2^24).  Checker and Procedure2 spheres stay on the general path.
+     * And only a frame large enough to pay for the test: in the pre-pass — one lane per tile, a chain of latencies in
+     * front of the frame kernel — the claim costs about 3 us per frame whatever the frame's size, and a claimed tile
+     * saves about 0.7 ns per tap (profiles/r12_variants.md: lecture5 at 1080p with one tap lost 1.9 us with the path, at
+     * 4K with five it gains 21 us).  With some 6 % of the tiles claimed the two meet near five million samples per launch;
+     * kSphereTileMinSamples is a little above.  Diagnostics build: C2RT_DEBUG_CULL bit 7 leaves every tile to the general
+     * path, bit 8 drops the size condition (the tests' small frames). */
+    constexpr uint64_t kSphereTileMinSamples = 6000000;
+    const uint64_t samples = (uint64_t)p.width * p.height * p.taps / (p.strip_world > 1 ? p.strip_world : 1u);
+    if (p.n_cull && plan.n_lights <= 1 && plan.csg_levels <= 1 && !p.cam.dof && p.cam.stereo_separation == 0 && !p.ray_counters &&
+        !(knobs.debug_cull & 128) &&
+        (samples >= kSphereTileMinSamples || (knobs.debug_cull & 256))) {
+        for (uint32_t j = 0; j < sc.n; ++j) {
+            const uint32_t n = sc.s[j].node;
+            if (n >= plan.nodes.size() || n >= 32u) continue;
+            const DevMat &m = plan.nodes[n].mat;
+            if (m.shader_type != C2RT_SHADER_LAMBERT && m.shader_type != C2RT_SHADER_PHONG) continue;
+            bool tex_ok = m.tex_type < 0;
+            if (m.tex_type == C2RT_TEX_BITMAP) {
+                const uint64_t w = m.texdata[0], h = m.texdata[1];
+                const uint64_t offset = (uint64_t)m.texdata[4] | ((uint64_t)m.texdata[5] << 32);
+                tex_ok = w < (1ull << 24) && h < (1ull << 24) && offset <= (1ull << 28) && w * h <= (1ull << 28) - offset;
+            }
+            if (tex_ok) sc.interior |= 1u << n;
+        }
+    }
     return sc;
 }
 

@@ -125,7 +125,8 @@ struct DiagKnobs {
      * ground-plane refinement of the shadow mask; bit 2: no view-pyramid culling of shadow rays; bit 3: no
      * sphere-silhouette test in the mask pre-pass; bit 4: no ground-tile path (RenderParams::ground_fast stays 0); bit 5: no
      * dark-tile test in the mask pre-pass (dark_cull_of); bit 6: no short-chain ground tiles (RenderParams::ground_certain_cq
-     * stays 0) */
+     * stays 0); bit 7: no sphere-interior tiles (SphereCull::interior stays 0); bit 8: sphere-interior
+     * tiles whatever the frame's size (sphere_cull_of: kSphereTileMinSamples) */
     int debug_cull = 0;
     int csg_first_cap = 0;             /* C2RT_CSG_FIRST_CAP=<entries>: the first pass's hit-stack capacity */
 };

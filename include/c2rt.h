@@ -471,6 +471,14 @@ int c2rt_get_exact_redos(c2rt_ctx *ctx, uint64_t *out);
  * c2rt_get_exact_redos, never a matter of correctness; about 1 tile in 3000 on the shipped scenes. */
 int c2rt_get_ground_bails(c2rt_ctx *ctx, uint64_t *out);
 
+/* How many sphere-interior 8x8 tiles this context has handed back to the general path since it was created
+ * (synchronises the device).  A tile in which the mask pre-pass has proven that every primary ray's closest hit lies on
+ * one sphere, and that nothing else can shadow it, is rendered by code that tests that sphere only
+ * (chess2rt_amd/csrc/csg_void.h, "Sphere-interior tiles"); should a ray of such a tile miss the sphere after all, the
+ * tile writes nothing and is rendered by the general path at once.  The proof says this stays 0; a cost indicator like
+ * c2rt_get_exact_redos, never a matter of correctness. */
+int c2rt_get_sphere_bails(c2rt_ctx *ctx, uint64_t *out);
+
 /* Pixel probe: mirrors `renderPixel` (rt/renderer.d:46-57): one sample at
  * integer (x, y), no AA, returns the colour and the trace result. */
 int c2rt_render_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam,

@@ -91,6 +91,7 @@ extern (C) nothrow @nogc
     int c2rt_get_exact_redos(c2rt_ctx*, ulong* outCount);
     /// ground-only tiles handed from the short fp64 chain back to the full one (a cost indicator)
     int c2rt_get_ground_bails(c2rt_ctx*, ulong* outCount);
+    int c2rt_get_sphere_bails(c2rt_ctx*, ulong* outCount);
     /// many cameras, one scene, one call: frame i at out + i * local_rows * width * 3 floats, the bits of the
     /// single-frame calls; no depth of field / stereo / counted / preview frames (C2RT_ERR_UNSUPPORTED)
     enum C2RT_MAX_BATCH_FRAMES = 256;
