@@ -5,15 +5,16 @@ the reference's Scene / Camera / Renderer API mirrored in C++
 (include/c2rt_host.h) and exposed here through ctypes.  No CPU fallback.
 """
 from . import _abi
-from ._abi import (CameraFrame, HostCamera, HostSettings, Ray, RayHit, RayStats, RenderOpts, SceneDesc, ScenePose, Segment, ShadePlanes, TraceResult,
-                   TAPS_1, TAPS_4, TAPS_REF5)
-from .api import (RAY_HIT_DTYPE, SHADE_PLANES, C2rtError, Context, Renderer, Scene, loadBmpImage, makePose, parseSceneFromFile, renderPixel, saveBmp)
+from ._abi import (CameraFrame, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc, ScenePose, Segment,
+                   ShadePlanes, TraceResult, TAPS_1, TAPS_4, TAPS_REF5)
+from .api import (OCCLUSION_PLANES, RAY_HIT_DTYPE, SHADE_PLANES, C2rtError, Context, Renderer, Scene, loadBmpImage, makePose, parseSceneFromFile, renderPixel, saveBmp)
 from .sharding import (StripPlan, deinterleave_strips_torch, exchange_strips_p2p, local_rows, plan_strips, render_frame_sharded)
 
 __all__ = [
     "C2rtError", "Context", "Renderer", "Scene", "parseSceneFromFile", "renderPixel", "loadBmpImage", "saveBmp",
     "CameraFrame", "HostCamera", "HostSettings", "RayStats", "RenderOpts", "SceneDesc", "ScenePose", "makePose", "TraceResult",
     "Ray", "Segment", "RayHit", "RAY_HIT_DTYPE", "ShadePlanes", "SHADE_PLANES",
+    "OcclusionOpts", "OcclusionPlanes", "OCCLUSION_PLANES",
     "TAPS_1", "TAPS_4", "TAPS_REF5",
     "StripPlan", "plan_strips", "local_rows", "render_frame_sharded", "deinterleave_strips_torch", "exchange_strips_p2p",
 ]

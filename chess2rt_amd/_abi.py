@@ -166,6 +166,26 @@ class ShadePlanes(C.Structure):
     ]
 
 
+class OcclusionOpts(C.Structure):
+    """c2rt_occlusion_opts: the segments' length, the counter RNG's seed and the sample count K (1 .. 64)"""
+    _fields_ = [
+        ("radius", C.c_double),
+        ("seed", C.c_uint64),
+        ("samples", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class OcclusionPlanes(C.Structure):
+    """c2rt_occlusion_planes: one nullable pointer per plane (host or device memory, by entry point)"""
+    _fields_ = [
+        ("node", C.c_void_p),
+        ("open", C.c_void_p),
+        ("ao", C.c_void_p),
+        ("bent", C.c_void_p),
+    ]
+
+
 class ScenePose(C.Structure):
     """c2rt_scene_pose: new transforms ([n_nodes][30] doubles) and light values for some nodes / lights of the uploaded scene"""
     _fields_ = [
@@ -263,6 +283,10 @@ C2RT_SYMBOLS = {
     "c2rt_render_shading": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(ShadePlanes)]),
     "c2rt_trace_rays_shading_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(ShadePlanes), _VP]),
     "c2rt_trace_rays_shading": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(ShadePlanes)]),
+    "c2rt_render_occlusion_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes), _VP]),
+    "c2rt_render_occlusion": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes)]),
+    "c2rt_trace_rays_occlusion_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes), _VP]),
+    "c2rt_trace_rays_occlusion": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes)]),
     "c2rt_render_frame_adaptive_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frame_adaptive": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frames_adaptive_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
@@ -297,6 +321,7 @@ C2RT_HOST_SYMBOLS = {
     "c2rt_host_render_hits": (C.c_int, [_VP, _VP, C.POINTER(HitPlanes)]),
     "c2rt_host_render_hit_layers": (C.c_int, [_VP, _VP, C.c_uint32, C.POINTER(HitPlanes), _VP]),
     "c2rt_host_render_shading": (C.c_int, [_VP, _VP, C.POINTER(ShadePlanes)]),
+    "c2rt_host_render_occlusion": (C.c_int, [_VP, _VP, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes)]),
     "c2rt_host_render_rt_adaptive": (C.c_int, [_VP, _VP, _VP, _VP]),
     "c2rt_host_bmp_decode": (C.c_int, [_VP, C.c_size_t, _u32p, _u32p, C.POINTER(_f32p)]),
     "c2rt_host_texture_gamma": (None, [_VP, C.c_size_t, C.c_float]),

@@ -12,8 +12,8 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (CameraFrame, HitPlanes, HostCamera, HostSettings, Ray, RayHit, RayStats, RenderOpts, SceneDesc, ScenePose, Segment,
-                   ShadePlanes, TraceResult)
+from ._abi import (CameraFrame, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
+                   ScenePose, Segment, ShadePlanes, TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
 RAY_HIT_DTYPE = np.dtype({
@@ -71,6 +71,38 @@ def _device_shade_planes(ptrs):
             raise ValueError("unknown shading plane %r (one of %s)" % (n, ", ".join(SHADE_PLANES)))
         setattr(pl, n, ptr or None)
     return pl
+
+
+# c2rt_occlusion_planes: plane name -> (dtype, components per sample), in the order of the struct's members
+OCCLUSION_PLANES = {"node": (np.int32, 1), "open": (np.uint64, 1), "ao": (np.float32, 1), "bent": (np.float64, 3)}
+
+
+def _new_occlusion_planes(names, shape):
+    """(OcclusionPlanes of fresh host arrays, {name: array}) for the planes named, `shape` samples each; the others stay null"""
+    names = tuple(names)
+    for n in names:
+        if n not in OCCLUSION_PLANES:
+            raise ValueError("unknown occlusion plane %r (one of %s)" % (n, ", ".join(OCCLUSION_PLANES)))
+    out, pl = {}, OcclusionPlanes()
+    for n in names:
+        dtype, comps = OCCLUSION_PLANES[n]
+        out[n] = np.empty(tuple(shape) if comps == 1 else tuple(shape) + (comps,), dtype=dtype)
+        setattr(pl, n, out[n].ctypes.data)
+    return pl, out
+
+
+def _device_occlusion_planes(ptrs):
+    """OcclusionPlanes of the device pointers in `ptrs` ({plane name: pointer}); planes left out (or 0 / None) stay null"""
+    pl = OcclusionPlanes()
+    for n, ptr in dict(ptrs).items():
+        if n not in OCCLUSION_PLANES:
+            raise ValueError("unknown occlusion plane %r (one of %s)" % (n, ", ".join(OCCLUSION_PLANES)))
+        setattr(pl, n, ptr or None)
+    return pl
+
+
+def _occlusion_opts(samples, radius, seed):
+    return OcclusionOpts(radius=float(radius), seed=int(seed), samples=int(samples), reserved=0)
 
 
 def makePose(nodes=None, lights=None):
@@ -673,6 +705,44 @@ class Context:
         pl = _device_shade_planes(ptrs)
         self._check(self._lib.c2rt_trace_rays_shading_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(pl), C.c_void_p(stream)))
 
+    def renderOcclusion(self, cam, opts, samples, radius, seed=0, planes=tuple(OCCLUSION_PLANES)):
+        """Ambient occlusion of every pixel's closest hit (c2rt_render_occlusion): `samples` (1 .. 64) segments of length
+        `radius` over the hemisphere around the hit's normal, each answered by the library's visibility test.  A dict of
+        numpy arrays for the planes named — node (int32), open (uint64, bit s: sample s is unoccluded) and ao (float32,
+        the open fraction) of shape (local_rows, W); bent (local_rows, W, 3) float64, the sum of the open directions.  A
+        miss holds -1, the low `samples` bits, 1.0 and zeros.  node alone traces no sample.  Refuses what renderHits
+        refuses."""
+        occ = _occlusion_opts(samples, radius, seed)
+        pl, out = _new_occlusion_planes(planes, (self.localRows(opts), opts.width))
+        self._check(self._lib.c2rt_render_occlusion(self._h, C.byref(cam), C.byref(opts), C.byref(occ), C.byref(pl)))
+        return out
+
+    def renderOcclusionDevice(self, cam, opts, samples, radius, ptrs, seed=0, stream=0):
+        """Enqueue the occlusion planes on `stream` into device memory: `ptrs` maps plane names (OCCLUSION_PLANES) to
+        device pointers of local_rows * W * components elements; planes left out (or 0 / None) are not written."""
+        occ = _occlusion_opts(samples, radius, seed)
+        pl = _device_occlusion_planes(ptrs)
+        self._check(self._lib.c2rt_render_occlusion_device(self._h, C.byref(cam), C.byref(opts), C.byref(occ), C.byref(pl), C.c_void_p(stream)))
+
+    def traceRaysOcclusion(self, rays, samples, radius, seed=0, planes=tuple(OCCLUSION_PLANES)):
+        """The same planes for caller-supplied rays (c2rt_trace_rays_occlusion): `rays` as for traceRays; a dict of arrays
+        of shape (n,) or (n, 3).  Ray i draws the samples of index i; node is traceRays'."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays: expected shape (n, 6), got %r" % (rays.shape,))
+        occ = _occlusion_opts(samples, radius, seed)
+        pl, out = _new_occlusion_planes(planes, (rays.shape[0],))
+        self._check(self._lib.c2rt_trace_rays_occlusion(self._h, rays.ctypes.data_as(C.c_void_p), rays.shape[0], C.byref(occ), C.byref(pl)))
+        return out
+
+    def traceRaysOcclusionDevice(self, rays_ptr, n, samples, radius, ptrs, seed=0, stream=0):
+        """Enqueue the query on `stream` over device memory: n c2rt_ray at rays_ptr, `ptrs` as for renderOcclusionDevice
+        with n samples per plane."""
+        occ = _occlusion_opts(samples, radius, seed)
+        pl = _device_occlusion_planes(ptrs)
+        self._check(self._lib.c2rt_trace_rays_occlusion_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(occ), C.byref(pl),
+                                                               C.c_void_p(stream)))
+
     def testVisibility(self, segments):
         """Scene.testVisibility for (n, 6) float64 segments (from, to): (n,) uint8, 1 = nothing in between."""
         seg = np.ascontiguousarray(segments, dtype=np.float64)
@@ -775,6 +845,14 @@ class Renderer:
         s = self.scene.settings
         pl, out = _new_shade_planes(planes, (s.frame_height, s.frame_width))
         self.ctx._check(self._lib.c2rt_host_render_shading(self.ctx.handle, self.scene._h, C.byref(pl)))
+        return out
+
+    def renderOcclusion(self, samples, radius, seed=0, planes=tuple(OCCLUSION_PLANES)):
+        """Context.renderOcclusion for the scene's own camera and frame size (c2rt_host_render_occlusion)."""
+        s = self.scene.settings
+        occ = _occlusion_opts(samples, radius, seed)
+        pl, out = _new_occlusion_planes(planes, (s.frame_height, s.frame_width))
+        self.ctx._check(self._lib.c2rt_host_render_occlusion(self.ctx.handle, self.scene._h, C.byref(occ), C.byref(pl)))
         return out
 
 

@@ -756,6 +756,79 @@ int c2rt_trace_rays_shading_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint
                                    const c2rt_shade_planes *planes_dev, void *hip_stream);
 int c2rt_trace_rays_shading(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const c2rt_shade_planes *planes_host);
 
+/* ---- occlusion planes: hemisphere visibility of every hit ------------------- */
+
+/* Most visibility tests per sample; C2RT_ERR_LIMIT beyond (the mask is one 64-bit word). */
+#define C2RT_MAX_OCCLUSION_SAMPLES 64
+
+typedef struct c2rt_occlusion_opts {    /* 24 bytes */
+    double   radius;     /* length of every sample's segment; finite and > 0 */
+    uint64_t seed;       /* counter-RNG seed (opts->seed of a camera call is ignored, as the hit planes ignore it) */
+    uint32_t samples;    /* K: 1 .. C2RT_MAX_OCCLUSION_SAMPLES */
+    uint32_t reserved;   /* must be 0 */
+} c2rt_occlusion_opts;
+
+typedef struct c2rt_occlusion_planes {  /* 32 bytes; every pointer nullable, at least one given */
+    int32_t  *node;      /* [..]     closest node, -1: no hit (the hit planes' `node`) */
+    uint64_t *open;      /* [..]     bit s (s < K): sample s's segment is unoccluded; bits >= K are 0 */
+    float    *ao;        /* [..]     (float)popcount(open) / (float)K */
+    double   *bent;      /* [..][3]  sum, in sample order from +0, of the OPEN samples' directions; not normalised */
+} c2rt_occlusion_planes;
+
+/* Ambient occlusion of the closest hit of ONE sample: K segments of length `radius` from Lambert.spawnRay's origin
+ * (p + N * 1e-6, rt/shader.d:118-135) along directions of hemisphereSample(N) (rt/shader.d:156-174), each answered by
+ * Scene.testVisibility (rt/scene.d:62-78).  For sample index idx and ray (o, d) —
+ *   camera calls: idx = FRAME row * W + column (strips and host chunks do not change it), (o, d) the ray
+ *     c2rt_render_hits traces for the pixel; planes are row-major [local_rows][W], strips as there;
+ *   ray calls: idx = the ray's index i in the caller's array (whatever chunk it travels in), `dir` exactly as given;
+ *     planes are [n] —
+ *
+ *     rec = what c2rt_trace_rays computes for the ray (o, d)              -- node := rec.closest_node
+ *     miss:  open = low K bits set, ao = 1.0f, bent = +0,+0,+0           -- nothing occludes the sky; no sample is drawn
+ *     hit:   N    = dot(d, rec.normal) < 0 ? rec.normal : -rec.normal    -- faceforward, as shade() does
+ *            from = rec.p + N * 1e-6
+ *            key  = rng_key(occ.seed, idx, 0)
+ *            for s in 0 .. K-1:
+ *                u = rng_uniform(key, s, 0);  v = rng_uniform(key, s, 1)
+ *                (sn, cs) = lens_sincos2pi(u)                             -- theta = 2 pi u
+ *                w = 2.0 * v - 1.0;  c = sqrt(1.0 - w * w)                -- phi = acos(w) - pi/2: sin(phi) = -w, cos(phi) = c
+ *                res = (cs * c, -w, sn * c)
+ *                if ((res.x*N.x + res.y*N.y) + res.z*N.z) < 0: res = -res
+ *                to = from + res * occ.radius                             -- product, then sum, not contracted
+ *                if testVisibility(from, to): open |= 1 << s; bent += res -- c2rt_test_visibility's answer for (from, to)
+ *            ao = (float)popcount(open) / (float)K
+ *
+ *   - Every operation is an IEEE fp64 +, * or sqrt without contraction, or one of the three routines of the lens samples
+ *     (rng_key, rng_uniform, lens_sincos2pi: the counter RNG and the libm-free sine and cosine of 2 pi u); no libm call,
+ *     so a CPU restatement produces the same bits.  Composition is the contract: the planes are what a caller gets who
+ *     takes the records from c2rt_trace_rays, builds the segments as above and asks c2rt_test_visibility, BIT FOR BIT.
+ *   - Build-defined, like the lens sample: the reference draws from rand() and goes through acos, cos and sin; the
+ *     directions above are within 3.4e-15 per component of that formula evaluated by libm for the same (u, v), and of
+ *     unit length within 1 ulp.
+ *   - What is written to a plane never depends on which others are asked for; `node` alone traces no sample.
+ *   - A lane of NaNs, zeros or 1e300 terminates (K bounded tests) and changes no other sample's result.
+ *
+ * Statuses, all decided before anything is enqueued or written, each with its own message.  Camera calls: those of a
+ * frame call, in c2rt_render_hits' order; ray calls: those of c2rt_trace_rays, in its order (null context; n == 0 is
+ * C2RT_OK whatever else is passed; null `rays`: C2RT_ERR_INVALID_ARG; n > C2RT_MAX_RAYS: C2RT_ERR_LIMIT; no scene:
+ * C2RT_ERR_NO_SCENE).  Then, for both: null `occ`: C2RT_ERR_INVALID_ARG; radius NaN, infinite or <= 0:
+ * C2RT_ERR_INVALID_ARG; samples == 0 or reserved != 0: C2RT_ERR_INVALID_ARG; samples > C2RT_MAX_OCCLUSION_SAMPLES:
+ * C2RT_ERR_LIMIT; null `planes`, or all four pointers null: C2RT_ERR_INVALID_ARG.  Camera calls then:
+ * C2RT_ERR_UNSUPPORTED naming "depth of field", "stereo", "count_rays", "prepass_bucket".
+ *
+ * The _device variants take device pointers and enqueue ONE kernel on `hip_stream`: no host sync, no event, no scratch
+ * slot, nothing kept of the stream; on a multi-device context, the lead device; after c2rt_update_scene they see the
+ * posed scene.  The host variants go through the context's staging buffer on the context's own stream in chunks of whole
+ * rows (or rays) of at most 2^18 samples — at most 40 B per sample of planes — and block until the planes are there. */
+int c2rt_render_occlusion_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                                 const c2rt_occlusion_opts *occ, const c2rt_occlusion_planes *planes_dev, void *hip_stream);
+int c2rt_render_occlusion(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                          const c2rt_occlusion_opts *occ, const c2rt_occlusion_planes *planes_host);
+int c2rt_trace_rays_occlusion_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n,
+                                     const c2rt_occlusion_opts *occ, const c2rt_occlusion_planes *planes_dev, void *hip_stream);
+int c2rt_trace_rays_occlusion(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n,
+                              const c2rt_occlusion_opts *occ, const c2rt_occlusion_planes *planes_host);
+
 /* ---- adaptive anti-aliasing: refine only the pixels the edge test flags ----- */
 
 /* tooDifferent's default threshold — rt/color.d:18 */

@@ -178,6 +178,31 @@ extern (C) nothrow @nogc
     int c2rt_trace_rays_shading_device(c2rt_ctx*, const c2rt_ray* rays_dev, ulong n, const c2rt_shade_planes* planes_dev,
                                        void* hip_stream);
     int c2rt_trace_rays_shading(c2rt_ctx*, const c2rt_ray* rays, ulong n, const c2rt_shade_planes* planes_host);
+    /// occlusion planes: `samples` segments of length `radius` from p + N * 1e-6 over hemisphereSample(N) of the closest
+    /// hit, each answered by testVisibility; sample index: frame row * W + column, or the ray's index (include/c2rt.h)
+    enum uint C2RT_MAX_OCCLUSION_SAMPLES = 64;
+    struct c2rt_occlusion_opts
+    {
+        double radius;              /// length of every segment; finite, > 0
+        ulong seed;                 /// counter-RNG seed
+        uint samples;               /// K: 1 .. C2RT_MAX_OCCLUSION_SAMPLES
+        uint reserved;              /// must be 0
+    }
+    struct c2rt_occlusion_planes
+    {
+        int* node;                  /// closest node, -1: no hit
+        ulong* open;                /// bit s < K: sample s's segment is unoccluded
+        float* ao;                  /// popcount(open) / K
+        double* bent;               /// [3] per sample: sum of the open samples' directions, not normalised
+    }
+    int c2rt_render_occlusion_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_occlusion_opts*,
+                                     const c2rt_occlusion_planes* planes_dev, void* hip_stream);
+    int c2rt_render_occlusion(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_occlusion_opts*,
+                              const c2rt_occlusion_planes* planes_host);
+    int c2rt_trace_rays_occlusion_device(c2rt_ctx*, const c2rt_ray* rays_dev, ulong n, const c2rt_occlusion_opts*,
+                                         const c2rt_occlusion_planes* planes_dev, void* hip_stream);
+    int c2rt_trace_rays_occlusion(c2rt_ctx*, const c2rt_ray* rays, ulong n, const c2rt_occlusion_opts*,
+                                  const c2rt_occlusion_planes* planes_host);
     enum float C2RT_AA_THRESHOLD_REF = 0.1f; /// tooDifferent's default
     int c2rt_render_frame_adaptive_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
                                           float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
