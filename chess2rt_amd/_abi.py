@@ -25,6 +25,7 @@ MAX_CSG_HITS = 8
 MAX_BATCH_FRAMES = 256
 MAX_RAYS = 1 << 28
 MAX_HIT_LAYERS = 16
+MAX_SAMPLE_TAPS = 16
 AA_THRESHOLD_REF = 0.1     # C2RT_AA_THRESHOLD_REF (0.1f: passed as a C float)
 
 _i32p = C.POINTER(C.c_int32)
@@ -186,6 +187,15 @@ class OcclusionPlanes(C.Structure):
     ]
 
 
+class TapTable(C.Structure):
+    """c2rt_tap_table: n (1 .. 16) sample offsets within the pixel; tap s samples the screen point (x + offset[s][0], y + offset[s][1])"""
+    _fields_ = [
+        ("n", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("offset", (C.c_double * 2) * MAX_SAMPLE_TAPS),
+    ]
+
+
 class ScenePose(C.Structure):
     """c2rt_scene_pose: new transforms ([n_nodes][30] doubles) and light values for some nodes / lights of the uploaded scene"""
     _fields_ = [
@@ -236,6 +246,7 @@ _SCENE_P = C.POINTER(SceneDesc)
 _CAM_P = C.POINTER(CameraFrame)
 _OPTS_P = C.POINTER(RenderOpts)
 _POSE_P = C.POINTER(ScenePose)
+_TAPS_P = C.POINTER(TapTable)
 _VP = C.c_void_p
 
 # every symbol include/c2rt.h declares: name -> (restype, argtypes)
@@ -293,6 +304,10 @@ C2RT_SYMBOLS = {
     "c2rt_render_frames_adaptive": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frames_posed_adaptive_device": (C.c_int, [_VP, _CAM_P, _POSE_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frames_posed_adaptive": (C.c_int, [_VP, _CAM_P, _POSE_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
+    "c2rt_render_frame_taps_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, _TAPS_P, _VP, _VP]),
+    "c2rt_render_frame_taps": (C.c_int, [_VP, _CAM_P, _OPTS_P, _TAPS_P, _VP]),
+    "c2rt_render_frame_adaptive_taps_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, _TAPS_P, C.c_float, _VP, _VP, _VP]),
+    "c2rt_render_frame_adaptive_taps": (C.c_int, [_VP, _CAM_P, _OPTS_P, _TAPS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_deinterleave_strips": (C.c_int, [_VP, _VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _VP]),
     "c2rt_encode_rgb32": (C.c_int, [_VP, _VP, _VP, C.c_uint64, _VP]),
     "c2rt_render_frame_rgb32": (C.c_int, [_VP, _CAM_P, _OPTS_P, _VP, _VP]),
@@ -323,6 +338,8 @@ C2RT_HOST_SYMBOLS = {
     "c2rt_host_render_shading": (C.c_int, [_VP, _VP, C.POINTER(ShadePlanes)]),
     "c2rt_host_render_occlusion": (C.c_int, [_VP, _VP, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes)]),
     "c2rt_host_render_rt_adaptive": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "c2rt_host_render_rt_taps": (C.c_int, [_VP, _VP, _TAPS_P, _VP]),
+    "c2rt_host_render_rt_adaptive_taps": (C.c_int, [_VP, _VP, _TAPS_P, _VP, _VP]),
     "c2rt_host_bmp_decode": (C.c_int, [_VP, C.c_size_t, _u32p, _u32p, C.POINTER(_f32p)]),
     "c2rt_host_texture_gamma": (None, [_VP, C.c_size_t, C.c_float]),
     "c2rt_host_bmp_encode": (C.c_int, [_VP, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_size_t)]),

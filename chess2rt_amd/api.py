@@ -13,7 +13,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (CameraFrame, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
-                   ScenePose, Segment, ShadePlanes, TraceResult)
+                   ScenePose, Segment, ShadePlanes, TapTable, TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
 RAY_HIT_DTYPE = np.dtype({
@@ -103,6 +103,32 @@ def _device_occlusion_planes(ptrs):
 
 def _occlusion_opts(samples, radius, seed):
     return OcclusionOpts(radius=float(radius), seed=int(seed), samples=int(samples), reserved=0)
+
+
+# the reference's five taps (rt/renderer.d:235-242): the table behind C2RT_TAPS_REF5, its first four behind C2RT_TAPS_4
+TAPS_REF5_TABLE = ((0.0, 0.0), (0.3, 0.3), (0.6, 0.0), (0.0, 0.6), (0.6, 0.6))
+
+
+def tap_grid(k):
+    """The k x k regular grid (1 <= k <= 4) as a tuple of (dx, dy): tap s at ((s % k) / k, (s // k) / k), so tap 0 is
+    the pixel's corner (0, 0) and the table also serves the adaptive calls."""
+    if not 1 <= k <= 4:
+        raise ValueError("tap_grid: k is %r (1 .. 4: at most %d taps)" % (k, _abi.MAX_SAMPLE_TAPS))
+    return tuple((float(s % k) / float(k), float(s // k) / float(k)) for s in range(k * k))
+
+
+def _tap_table(taps):
+    """c2rt_tap_table of a TapTable (as it is) or of a sequence of (dx, dy); a sequence longer than the struct holds
+    keeps its count, which the library refuses"""
+    if isinstance(taps, TapTable):
+        return taps
+    taps = list(taps)
+    t = TapTable()
+    t.n = len(taps)
+    for s, (dx, dy) in enumerate(taps[:_abi.MAX_SAMPLE_TAPS]):
+        t.offset[s][0] = dx
+        t.offset[s][1] = dy
+    return t
 
 
 def makePose(nodes=None, lights=None):
@@ -459,6 +485,36 @@ class Context:
         self._check(self._lib.c2rt_render_frame_adaptive_device(self._h, C.byref(cam), C.byref(opts), float(threshold),
                                                                 C.c_void_p(out_ptr or None), C.c_void_p(mask_ptr or None), C.c_void_p(stream)))
 
+    def renderFrameTaps(self, cam, opts, taps):
+        """A frame sampled through the caller's tap table (c2rt_render_frame_taps): a new host array of shape
+        (local_rows, W, 3), every pixel the sum of its taps' colours in tap order divided by their count.  `taps`: a
+        TapTable or a sequence of up to 16 (dx, dy) — TAPS_REF5_TABLE gives the bits of the TAPS_REF5 frame, tap_grid(4)
+        a 4x4 grid.  opts.taps is ignored.  No depth of field, stereo, count_rays or prepass_bucket (ERR_UNSUPPORTED)."""
+        out = np.empty((self.localRows(opts), opts.width, 3), dtype=np.float32)
+        self._check(self._lib.c2rt_render_frame_taps(self._h, C.byref(cam), C.byref(opts), C.byref(_tap_table(taps)), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def renderFrameTapsDevice(self, cam, opts, taps, out_ptr, stream=0):
+        """Enqueue the same frame into device memory (local_rows * W * 3 floats at out_ptr) on `stream`: one kernel."""
+        self._check(self._lib.c2rt_render_frame_taps_device(self._h, C.byref(cam), C.byref(opts), C.byref(_tap_table(taps)), C.c_void_p(out_ptr or None),
+                                                            C.c_void_p(stream)))
+
+    def renderFrameAdaptiveTaps(self, cam, opts, taps, threshold=_abi.AA_THRESHOLD_REF, stop_flag=None):
+        """renderFrameAdaptive with taps 1 .. n-1 of the caller's table on the flagged pixels
+        (c2rt_render_frame_adaptive_taps; n >= 2, tap 0 at (0, 0)): (frame, mask).  A flagged pixel holds the bits of
+        renderFrameTaps for the same table, an unflagged one the bits of the one-tap frame."""
+        frame = np.empty((opts.height, opts.width, 3), dtype=np.float32)
+        mask = np.empty((opts.height, opts.width), dtype=np.uint8)
+        stop = stop_flag.ctypes.data_as(C.c_void_p) if stop_flag is not None else None
+        self._check(self._lib.c2rt_render_frame_adaptive_taps(self._h, C.byref(cam), C.byref(opts), C.byref(_tap_table(taps)), float(threshold),
+                                                              frame.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p), stop))
+        return frame, mask
+
+    def renderFrameAdaptiveTapsDevice(self, cam, opts, taps, out_ptr, mask_ptr, threshold=_abi.AA_THRESHOLD_REF, stream=0):
+        """Enqueue the same on `stream` into device memory: H * W * 3 floats at out_ptr, H * W bytes at mask_ptr (required)."""
+        self._check(self._lib.c2rt_render_frame_adaptive_taps_device(self._h, C.byref(cam), C.byref(opts), C.byref(_tap_table(taps)), float(threshold),
+                                                                     C.c_void_p(out_ptr or None), C.c_void_p(mask_ptr or None), C.c_void_p(stream)))
+
     def renderFramesAdaptive(self, cams, opts, threshold=_abi.AA_THRESHOLD_REF, stop_flag=None):
         """Adaptive anti-aliasing for a batch of cameras (c2rt_render_frames_adaptive; opts.taps must be TAPS_REF5):
         (frames, masks) of shapes (len(cams), H, W, 3) float32 and (len(cams), H, W) uint8; frame i and mask i hold
@@ -805,6 +861,23 @@ class Renderer:
         mask = np.empty((s.frame_height, s.frame_width), dtype=np.uint8)
         self.ctx._check(self._lib.c2rt_host_render_rt_adaptive(self.ctx.handle, self.scene._h, frame.ctypes.data_as(C.c_void_p),
                                                                mask.ctypes.data_as(C.c_void_p)))
+        return frame, mask
+
+    def renderRTTaps(self, taps):
+        """Context.renderFrameTaps for the scene's own camera and frame size (c2rt_host_render_rt_taps)."""
+        s = self.scene.settings
+        out = np.empty((s.frame_height, s.frame_width, 3), dtype=np.float32)
+        self.ctx._check(self._lib.c2rt_host_render_rt_taps(self.ctx.handle, self.scene._h, C.byref(_tap_table(taps)), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def renderRTAdaptiveTaps(self, taps):
+        """Context.renderFrameAdaptiveTaps for the scene's own camera and frame size at the reference's threshold
+        (c2rt_host_render_rt_adaptive_taps): (frame, mask)."""
+        s = self.scene.settings
+        frame = np.empty((s.frame_height, s.frame_width, 3), dtype=np.float32)
+        mask = np.empty((s.frame_height, s.frame_width), dtype=np.uint8)
+        self.ctx._check(self._lib.c2rt_host_render_rt_adaptive_taps(self.ctx.handle, self.scene._h, C.byref(_tap_table(taps)),
+                                                                    frame.ctypes.data_as(C.c_void_p), mask.ctypes.data_as(C.c_void_p)))
         return frame, mask
 
     def renderSceneAsync(self, out, is_rendering, needs_rendering=None):

@@ -2044,8 +2044,9 @@ static int check_adaptive_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, cons
 
 /* The three steps on `stream`, device pointers: the one-tap frame through the frame path as it is (pre-pass, lean / exact
  * redo, nested-CSG retry, the stream's scratch slot), the flags, the refinement of the flagged pixels in place.  The
- * caller's mask is the only buffer between detection and refinement: no scratch of this call's own. */
-static int adaptive_enqueue(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, float threshold,
+ * caller's mask is the only buffer between detection and refinement: no scratch of this call's own.  `taps` null: the
+ * reference's four extra taps (c2rt_adaptive.hip); otherwise taps 1 .. n-1 of the caller's table (c2rt_sample_taps.hip). */
+static int adaptive_enqueue(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_tap_table *taps, float threshold,
                             float *out_dev, uint8_t *mask_dev, hipStream_t stream)
 {
     c2rt_render_opts one = *opts;
@@ -2055,7 +2056,7 @@ static int adaptive_enqueue(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c
     if (e != 0) return fail(ctx, C2RT_ERR_HIP, "adaptive AA detection kernel launch: %s", hipGetErrorString((hipError_t)e));
     RenderParams p;
     hit_params(ctx, cam, &one, p);
-    e = launch_aa_refine(p, ctx->plan.csg_levels, out_dev, mask_dev, stream);
+    e = taps ? launch_aa_refine_taps(p, ctx->plan.csg_levels, *taps, out_dev, mask_dev, stream) : launch_aa_refine(p, ctx->plan.csg_levels, out_dev, mask_dev, stream);
     if (e != 0) return fail(ctx, C2RT_ERR_HIP, "adaptive AA refinement kernel launch: %s", hipGetErrorString((hipError_t)e));
     return C2RT_OK;
 }
@@ -2065,15 +2066,14 @@ int c2rt_render_frame_adaptive_device(c2rt_ctx *ctx, const c2rt_camera_frame *ca
 {
     if (const int st = check_adaptive_args(ctx, cam, opts, threshold, out_rgb_dev, needs_aa_dev != nullptr)) return st;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return adaptive_enqueue(ctx, cam, opts, threshold, out_rgb_dev, needs_aa_dev, static_cast<hipStream_t>(hip_stream));
+    return adaptive_enqueue(ctx, cam, opts, nullptr, threshold, out_rgb_dev, needs_aa_dev, static_cast<hipStream_t>(hip_stream));
 }
 
-/* Host variant: frame and mask side by side in the context's staging allocation, on the context's stream; one copy
- * back per output, then a stream sync. */
-int c2rt_render_frame_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, float threshold,
-                               float *out_rgb, uint8_t *needs_aa, const volatile uint8_t *stop_flag)
+/* Both host variants, the arguments checked: frame and mask side by side in the context's staging allocation, on the
+ * context's stream; one copy back per output, then a stream sync. */
+static int adaptive_to_host(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_tap_table *taps, float threshold,
+                            float *out_rgb, uint8_t *needs_aa, const volatile uint8_t *stop_flag)
 {
-    if (const int st = check_adaptive_args(ctx, cam, opts, threshold, out_rgb, true)) return st;
     /* isStopReq() before the pass — rt/renderer.d:129 */
     if (stop_flag && *stop_flag) return fail(ctx, C2RT_ERR_CANCELLED, "stop requested before the frame");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2081,11 +2081,112 @@ int c2rt_render_frame_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cam, cons
     const size_t off_mask = align256(px * 3 * sizeof(float));
     if (const int st = ensure_staging(ctx, off_mask + px)) return st;
     uint8_t *mask_dev = reinterpret_cast<uint8_t *>(ctx->frame) + off_mask;
-    if (const int st = adaptive_enqueue(ctx, cam, opts, threshold, ctx->frame, mask_dev, ctx->stream)) return st;
+    if (const int st = adaptive_enqueue(ctx, cam, opts, taps, threshold, ctx->frame, mask_dev, ctx->stream)) return st;
     HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->frame, px * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     if (needs_aa) HIP_TRY(ctx, hipMemcpyAsync(needs_aa, mask_dev, px, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return C2RT_OK;
+}
+
+int c2rt_render_frame_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, float threshold,
+                               float *out_rgb, uint8_t *needs_aa, const volatile uint8_t *stop_flag)
+{
+    if (const int st = check_adaptive_args(ctx, cam, opts, threshold, out_rgb, true)) return st;
+    return adaptive_to_host(ctx, cam, opts, nullptr, threshold, out_rgb, needs_aa, stop_flag);
+}
+
+/* ---- sample tables: N-tap frames, whole and adaptive (c2rt_sample_taps.hip) ---------------------------------------- */
+
+/* the table's own refusals, behind the frame call's, in the documented order */
+static int check_tap_table(c2rt_ctx *ctx, const c2rt_tap_table *taps)
+{
+    if (!taps) return fail(ctx, C2RT_ERR_INVALID_ARG, "null taps");
+    if (taps->n == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "taps: n is 0 (1 .. %u)", (unsigned)C2RT_MAX_SAMPLE_TAPS);
+    if (taps->n > C2RT_MAX_SAMPLE_TAPS) return fail(ctx, C2RT_ERR_LIMIT, "taps: n is %u (at most %u)", (unsigned)taps->n, (unsigned)C2RT_MAX_SAMPLE_TAPS);
+    if (taps->reserved != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "taps: reserved is %u, not 0", (unsigned)taps->reserved);
+    for (uint32_t s = 0; s < taps->n; ++s)
+        if (!std::isfinite(taps->offset[s][0]) || !std::isfinite(taps->offset[s][1]))
+            return fail(ctx, C2RT_ERR_INVALID_ARG, "taps: the offset of tap %u is not finite", (unsigned)s);
+    return C2RT_OK;
+}
+
+/* the refusals of both whole-frame entry points, in the documented order */
+static int check_frame_taps_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_tap_table *taps,
+                                 const void *out_rgb)
+{
+    if (const int st = check_frame_args(ctx, cam, opts)) return st;
+    if (const int st = check_tap_table(ctx, taps)) return st;
+    if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: a tap is one ray, a lens has many per tap");
+    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: a tap is one ray, a stereo camera has two per tap");
+    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the sample-table frames do not count rays");
+    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
+    return C2RT_OK;
+}
+
+int c2rt_render_frame_taps_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_tap_table *taps,
+                                  float *out_rgb_dev, void *hip_stream)
+{
+    if (const int st = check_frame_taps_args(ctx, cam, opts, taps, out_rgb_dev)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    if (p.local_rows == 0) return C2RT_OK;
+    const int e = launch_frame_taps(p, ctx->plan.csg_levels, *taps, out_rgb_dev, 0, p.local_rows, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "sample-table frame kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+/* Host variant: c2rt_render_hits' chunks of whole rows, 12 B per pixel — 3 MiB at most. */
+int c2rt_render_frame_taps(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_tap_table *taps, float *out_rgb)
+{
+    if (const int st = check_frame_taps_args(ctx, cam, opts, taps, out_rgb)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    if (p.local_rows == 0) return C2RT_OK;
+    Staging outs;
+    outs.add(out_rgb, 3 * sizeof(float));
+    return row_chunks(ctx, p, 1, outs, "sample-table frame", [&](uint32_t r0, uint32_t m, size_t) {
+        return launch_frame_taps(p, ctx->plan.csg_levels, *taps, outs.dev<float>(0), r0, m, ctx->stream);
+    });
+}
+
+/* the refusals of both adaptive entry points, in the documented order: a frame call's, then the table's and the other
+ * arguments of this call, then c2rt_render_frame_adaptive's unsupported modes in its wording */
+static int check_adaptive_taps_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_tap_table *taps,
+                                    float threshold, const void *out_rgb, bool mask_ok)
+{
+    if (const int st = check_frame_args(ctx, cam, opts)) return st;
+    if (const int st = check_tap_table(ctx, taps)) return st;
+    if (taps->n < 2) return fail(ctx, C2RT_ERR_INVALID_ARG, "taps: n is %u, adaptive refinement needs at least 2", (unsigned)taps->n);
+    if (taps->offset[0][0] != 0.0 || taps->offset[0][1] != 0.0)
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "taps: tap 0 is (%g, %g), the one-tap frame samples (0, 0)", taps->offset[0][0], taps->offset[0][1]);
+    if (!(threshold >= 0.0f)) return fail(ctx, C2RT_ERR_INVALID_ARG, "threshold %g: neither negative nor NaN", (double)threshold);
+    if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    if (!mask_ok) return fail(ctx, C2RT_ERR_INVALID_ARG, "null needs_aa: the device variant keeps the flags in the caller's buffer");
+    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: the flags compare one ray per pixel, a lens has many");
+    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: the flags compare one ray per pixel, a stereo camera has two");
+    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the refinement does not count rays");
+    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
+    if (opts->strip_world > 1) return fail(ctx, C2RT_ERR_UNSUPPORTED, "strip_world > 1: the rows above and below a strip belong to other ranks");
+    if (!ctx->peers.empty()) return fail(ctx, C2RT_ERR_UNSUPPORTED, "multi-device context: the rows above and below a strip are on other devices");
+    return C2RT_OK;
+}
+
+int c2rt_render_frame_adaptive_taps_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_tap_table *taps,
+                                           float threshold, float *out_rgb_dev, uint8_t *needs_aa_dev, void *hip_stream)
+{
+    if (const int st = check_adaptive_taps_args(ctx, cam, opts, taps, threshold, out_rgb_dev, needs_aa_dev != nullptr)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return adaptive_enqueue(ctx, cam, opts, taps, threshold, out_rgb_dev, needs_aa_dev, static_cast<hipStream_t>(hip_stream));
+}
+
+int c2rt_render_frame_adaptive_taps(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_tap_table *taps,
+                                    float threshold, float *out_rgb, uint8_t *needs_aa, const volatile uint8_t *stop_flag)
+{
+    if (const int st = check_adaptive_taps_args(ctx, cam, opts, taps, threshold, out_rgb, true)) return st;
+    return adaptive_to_host(ctx, cam, opts, taps, threshold, out_rgb, needs_aa, stop_flag);
 }
 
 /* The refusals of the four batch entry points, in the documented order: a batch call's, then the arguments of this

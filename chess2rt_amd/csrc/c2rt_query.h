@@ -1,5 +1,5 @@
 /*
- * c2rt_query.h — launch interface of the query kernels (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip, c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_adaptive.hip), shared
+ * c2rt_query.h — launch interface of the query kernels (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip, c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_adaptive.hip, c2rt_sample_taps.hip), shared
  * by those files and c2rt_api.cpp.  A header of its own: c2rt_device.h is a prerequisite of every frame-kernel object,
  * and query work should not rebuild them.  All return hipError_t as int; every pointer is a device pointer.
  *
@@ -57,6 +57,11 @@ int launch_aa_detect(const float *frames, uint8_t *needs_aa, uint32_t width, uin
 int launch_aa_refine(const RenderParams &p, int csg_levels, float *frame, const uint8_t *needs_aa, void *stream);
 int launch_aa_refine_batch(const RenderParams &p0, int csg_levels, const RenderParams *table_dev, uint32_t n_frames, const uint8_t *needs_aa,
                            void *stream);
+/* Sample tables (c2rt_render_frame_taps*, c2rt_render_frame_adaptive_taps*; c2rt_sample_taps.hip): the hit planes' rows
+ * with every pixel the average of the table's taps (1 <= taps.n <= C2RT_MAX_SAMPLE_TAPS) into `out`, whose first row is
+ * row0; and launch_aa_refine with taps 1 .. taps.n - 1 of the table in the place of the reference's four (taps.n >= 2) */
+int launch_frame_taps(const RenderParams &p, int csg_levels, const c2rt_tap_table &taps, float *out, uint32_t row0, uint32_t rows, void *stream);
+int launch_aa_refine_taps(const RenderParams &p, int csg_levels, const c2rt_tap_table &taps, float *frame, const uint8_t *needs_aa, void *stream);
 
 } // namespace c2rt
 #endif

@@ -315,6 +315,32 @@ int c2rt_host_render_rt_adaptive(c2rt_ctx *ctx, c2rt_host_scene *s, float *out_r
     return c2rt_render_frame_adaptive(ctx, &cam, &o, C2RT_AA_THRESHOLD_REF, out_rgb, needs_aa, nullptr);
 }
 
+int c2rt_host_render_rt_taps(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_tap_table *taps, float *out_rgb)
+{
+    if (!ctx || !s) return C2RT_ERR_INVALID_ARG;
+    // c2rt_host_render_hits' set-up; the table, the output and the camera are judged by c2rt_render_frame_taps
+    c2rt_camera_frame cam;
+    c2rt_host_scene_begin_frame(s, &cam);
+    Renderer r{ctx, s, nullptr, nullptr, nullptr};
+    const int st = r.ensureUploaded();
+    if (st != C2RT_OK) return st;
+    const c2rt_render_opts o = opts_of(*s->scene);
+    return c2rt_render_frame_taps(ctx, &cam, &o, taps, out_rgb);
+}
+
+int c2rt_host_render_rt_adaptive_taps(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_tap_table *taps, float *out_rgb, uint8_t *needs_aa)
+{
+    if (!ctx || !s) return C2RT_ERR_INVALID_ARG;
+    // c2rt_host_render_rt_adaptive with the caller's table behind the flags
+    c2rt_camera_frame cam;
+    c2rt_host_scene_begin_frame(s, &cam);
+    Renderer r{ctx, s, nullptr, nullptr, nullptr};
+    const int st = r.ensureUploaded();
+    if (st != C2RT_OK) return st;
+    const c2rt_render_opts o = opts_of(*s->scene);
+    return c2rt_render_frame_adaptive_taps(ctx, &cam, &o, taps, C2RT_AA_THRESHOLD_REF, out_rgb, needs_aa, nullptr);
+}
+
 int c2rt_host_bmp_decode(const uint8_t *bytes, size_t len, uint32_t *width, uint32_t *height, float **out_rgb)
 {
     if (!bytes || !width || !height || !out_rgb) return C2RT_ERR_INVALID_ARG;

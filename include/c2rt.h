@@ -915,6 +915,72 @@ int c2rt_render_frames_posed_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *ca
                                       uint32_t n_frames, const c2rt_render_opts *opts, float threshold, float *out_rgb,
                                       uint8_t *needs_aa, const volatile uint8_t *stop_flag);
 
+/* ---- sample tables: N-tap supersampled frames, whole and adaptive ------------ */
+
+/* The table travels as a kernel argument behind the frame's parameter block (no copy, no scratch slot), which is what
+ * bounds it; a 4x4 grid is the largest regular pattern under the cap. */
+#define C2RT_MAX_SAMPLE_TAPS 16          /* C2RT_ERR_LIMIT beyond */
+
+typedef struct c2rt_tap_table {          /* 264 bytes */
+    uint32_t n;                          /* 1 .. C2RT_MAX_SAMPLE_TAPS */
+    uint32_t reserved;                   /* must be 0 */
+    double   offset[C2RT_MAX_SAMPLE_TAPS][2];   /* tap s samples the screen point (x + offset[s][0], y + offset[s][1]);
+                                                    entries s >= n are not read */
+} c2rt_tap_table;
+
+/* A frame whose pixels average the caller's taps, for a pinhole, mono camera.  A composition of existing calls: for the
+ * pixel (x, y) (frame row and column; strips as in c2rt_render_hits),
+ *   for s in 0 .. n-1: c_s = the colour c2rt_trace_rays computes for the ray through the screen point
+ *                            ((double)x + offset[s][0], (double)y + offset[s][1]) — Camera.getScreenRay and raytrace()'s
+ *                            normalisation, the frames' own operations;
+ *   accum = c_0; accum = accum + c_s for s = 1 .. n-1 (fp32, per channel, in tap order, no contraction);
+ *   out = n > 1 ? accum / (float)n : accum  (Color / float: a division, not a reciprocal).
+ * These are the frame kernels' statements, so bit for bit: the reference's five taps ({0,0}, {.3,.3}, {.6,0}, {0,.6},
+ * {.6,.6}) give the C2RT_TAPS_REF5 frame of c2rt_render_frame_device, their first four the C2RT_TAPS_4 frame, and
+ * {(0,0)} the C2RT_TAPS_1 frame and the hit planes' rgb.  Offsets may be negative or exceed 1 (the tap then samples a
+ * neighbour's area).  opts->taps must be a valid mode and is otherwise ignored; opts->seed is ignored.  Strips give
+ * compact rows, c2rt_local_rows(opts) of them; on a multi-device context the call runs on the lead device; after
+ * c2rt_update_scene it sees the posed scene.
+ *
+ * The _device variant is ONE kernel on `hip_stream` (a hipStream_t, NULL = default stream): no host sync, no event left
+ * in the queue, no scratch slot, no reference kept to the stream.
+ *
+ * Statuses, all decided before anything is enqueued or written, in this order: those of a frame call, in
+ * c2rt_render_hits' order (null context, camera or options: C2RT_ERR_INVALID_ARG; no scene: C2RT_ERR_NO_SCENE; bad size
+ * / tap mode / strip rank); null `taps`: C2RT_ERR_INVALID_ARG; n == 0: C2RT_ERR_INVALID_ARG; n > C2RT_MAX_SAMPLE_TAPS:
+ * C2RT_ERR_LIMIT; reserved != 0: C2RT_ERR_INVALID_ARG; a NaN or infinite offset among the first n:
+ * C2RT_ERR_INVALID_ARG, the message naming the tap; null output: C2RT_ERR_INVALID_ARG; C2RT_ERR_UNSUPPORTED with the
+ * cause named in c2rt_last_error for cam->dof ("depth of field"), cam->stereo_separation != 0 ("stereo"),
+ * opts->count_rays ("count_rays") and opts->prepass_bucket ("prepass_bucket"). */
+int c2rt_render_frame_taps_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                                  const c2rt_tap_table *taps, float *out_rgb_dev, void *hip_stream);
+/* The same into HOST memory: through the context's staging buffer on the context's own stream, in chunks of whole rows of
+ * at most 2^18 pixels (12 B per pixel); blocks until the frame is there. */
+int c2rt_render_frame_taps(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                           const c2rt_tap_table *taps, float *out_rgb);
+
+/* c2rt_render_frame_adaptive_device with step 3 generalised to the caller's table.  Steps 1 and 2 are that call's: the
+ * one-tap frame from the frame path with taps = 1, the detection kernel and its mask.  Step 3, for the flagged pixels
+ * only: accum = out[y][x]; accum += c_s for s = 1 .. n-1 in that order (c_s as above); out[y][x] = accum / (float)n.
+ * The call requires n >= 2 and offset[0] == (0, 0), so a flagged pixel holds the bits of c2rt_render_frame_taps for the
+ * same table and an unflagged pixel the bits of the C2RT_TAPS_1 frame; with the reference's five taps, frame and mask
+ * are the bits of c2rt_render_frame_adaptive_device.  opts->taps must be a valid mode and is otherwise ignored.
+ * Enqueue order, streams, the required needs_aa_dev: as c2rt_render_frame_adaptive_device, with this refinement kernel
+ * in the place of its own.
+ *
+ * Statuses, all decided before anything is enqueued or written, in this order: those of a frame call;
+ * C2RT_ERR_INVALID_ARG (C2RT_ERR_LIMIT for n > C2RT_MAX_SAMPLE_TAPS) for a bad table as above, then for n < 2, for
+ * offset[0] != (0, 0), for a threshold that is negative or NaN, for a null output (needs_aa_dev included); then the
+ * C2RT_ERR_UNSUPPORTED causes of c2rt_render_frame_adaptive_device, "strip_world" and "multi-device" among them. */
+int c2rt_render_frame_adaptive_taps_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                                           const c2rt_tap_table *taps, float threshold,
+                                           float *out_rgb_dev, uint8_t *needs_aa_dev, void *hip_stream);
+/* The same into HOST memory, as c2rt_render_frame_adaptive is to c2rt_render_frame_adaptive_device: `needs_aa` is
+ * nullable here; `stop_flag` is polled once, before the launches; C2RT_ERR_CANCELLED leaves the outputs untouched. */
+int c2rt_render_frame_adaptive_taps(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                                    const c2rt_tap_table *taps, float threshold,
+                                    float *out_rgb, uint8_t *needs_aa, const volatile uint8_t *stop_flag);
+
 /* Rank-0 side of the multi-GPU gather: `gathered_dev` holds `world`
  * consecutive compact strip buffers (rank-major, as ncclGather leaves them);
  * writes the de-interleaved full frame to `frame_dev`.  Both device

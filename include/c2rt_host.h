@@ -124,6 +124,14 @@ int c2rt_host_render_occlusion(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt
  * frameWidth * frameHeight bytes.  Depth of field and stereo are refused with C2RT_ERR_UNSUPPORTED. */
 int c2rt_host_render_rt_adaptive(c2rt_ctx *ctx, c2rt_host_scene *scene, float *out_rgb, uint8_t *needs_aa);
 
+/* The scene's own camera at its frame size through a caller's tap table: c2rt_render_frame_taps (every pixel the average
+ * of the table's taps) and c2rt_render_frame_adaptive_taps at the reference's threshold (taps 1 .. n-1 on the flagged
+ * pixels only; `needs_aa` nullable).  Both upload the scene if needed and call beginFrame; the table, the outputs and the
+ * camera are judged by those calls. */
+int c2rt_host_render_rt_taps(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt_tap_table *taps, float *out_rgb);
+int c2rt_host_render_rt_adaptive_taps(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt_tap_table *taps, float *out_rgb,
+                                      uint8_t *needs_aa);
+
 /* ---- moving a node or a light of a loaded scene ----------------------------- */
 
 /* Index of the named node / light in the flat tables (and in a c2rt_scene_pose); -1: no such name. */

@@ -221,6 +221,25 @@ extern (C) nothrow @nogc
     int c2rt_render_frames_posed_adaptive(c2rt_ctx*, const c2rt_camera_frame* cams, const c2rt_scene_pose* poses, uint nFrames,
                                           const c2rt_render_opts*, float threshold, float* out_rgb, ubyte* needs_aa,
                                           const shared(ubyte)* stop_flag);
+    /// sample tables: every pixel the average of the caller's n taps (accum = c_0, += c_s in tap order, / cast(float) n),
+    /// or, adaptive, taps 1 .. n-1 on the flagged pixels only (n >= 2, offset[0] == (0, 0)); the reference's five taps
+    /// give the bits of the C2RT_TAPS_REF5 frame and of c2rt_render_frame_adaptive (include/c2rt.h)
+    enum uint C2RT_MAX_SAMPLE_TAPS = 16;
+    struct c2rt_tap_table
+    {
+        uint n;                     /// 1 .. C2RT_MAX_SAMPLE_TAPS
+        uint reserved;              /// must be 0
+        double[2][C2RT_MAX_SAMPLE_TAPS] offset; /// tap s samples the screen point (x + offset[s][0], y + offset[s][1])
+    }
+    int c2rt_render_frame_taps_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_tap_table*,
+                                      float* out_rgb_dev, void* hip_stream);
+    int c2rt_render_frame_taps(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_tap_table*,
+                               float* out_rgb);
+    int c2rt_render_frame_adaptive_taps_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*,
+                                               const c2rt_tap_table*, float threshold, float* out_rgb_dev,
+                                               ubyte* needs_aa_dev, void* hip_stream);
+    int c2rt_render_frame_adaptive_taps(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_tap_table*,
+                                        float threshold, float* out_rgb, ubyte* needs_aa, const shared(ubyte)* stop_flag);
 }
 
 /// Owns the flat tables for one uploaded scene (GC memory; c2rt_upload_scene copies them).
