@@ -64,14 +64,16 @@ HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/
 # diagnostics build of the same library: c2rt_api.cpp with the environment hooks compiled in (-DC2RT_DIAG=1), linked
 # over the SAME kernel objects; tests and scripts that need a hook load it with C2RT_LIB_VARIANT=diag
 DIAGNAME   := chess2rt_amd/libc2rt_diag.so
+# the same with the depth-1 frame unit's lane statistics compiled in (its rules are below, behind the diagnostics library's)
+STATSNAME  := chess2rt_amd/libc2rt_lanestats.so
 
-all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/libground_texel_check.so tests/libsphere_interior_check.so tests/tap_average_check
+all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME) $(STATSNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/libground_texel_check.so tests/libsphere_interior_check.so tests/libcsg_certain_check.so tests/tap_average_check
 
 $(BUILD):
 	mkdir -p $(BUILD)
 
 # (the Makefile is a prerequisite: the arithmetic and code-generation flags are part of what a kernel object is)
-TRACE_DEPS := $(CSRC)/c2rt_trace_common.inc $(CSRC)/c2rt_trace_shared.inc $(CSRC)/c2rt_tile_mask.inc $(CSRC)/c2rt_trace.inc $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/x87.h $(CSRC)/fp64_lean.h $(CSRC)/f32_certain.h $(CSRC)/ground_certain.h include/c2rt.h Makefile
+TRACE_DEPS := $(CSRC)/c2rt_trace_common.inc $(CSRC)/c2rt_trace_shared.inc $(CSRC)/c2rt_tile_mask.inc $(CSRC)/c2rt_trace.inc $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/csg_certain.h $(CSRC)/x87.h $(CSRC)/fp64_lean.h $(CSRC)/f32_certain.h $(CSRC)/ground_certain.h include/c2rt.h Makefile
 $(BUILD)/c2rt_kernels_u%.o: $(CSRC)/c2rt_kernels.hip $(TRACE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_u$*) $(EXTRA_KERNEL_FLAGS) -DC2RT_UNIT=$* -c $< -o $@
 
@@ -97,6 +99,19 @@ $(BUILD)/c2rt_api_diag.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_query.h $(CSRC)/scen
 $(DIAGNAME): $(KOBJS) $(BUILD)/c2rt_api_diag.o $(filter-out $(BUILD)/c2rt_api.o,$(HOBJS))
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
+# lane-statistics build of the diagnostics library: the depth-1 frame unit and c2rt_api.cpp compiled with -DC2RT_TILE_STATS=1
+# (the region and lane counters of c2rt_trace_shared.inc, c2rt_debug_set_tile_stats), linked over the SAME objects for
+# everything else — one more compile of one unit.  tests/test_gpu_csg_certain.py reads the certain / unsure lane counts
+# of csg_certain.h from it (C2RT_LIB_VARIANT=lanestats); frames of other CSG depths run the plain units and count nothing.
+$(BUILD)/c2rt_kernels_u1_stats.o: $(CSRC)/c2rt_kernels.hip $(TRACE_DEPS) | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_u1) $(EXTRA_KERNEL_FLAGS) -DC2RT_TILE_STATS=1 -DC2RT_UNIT=1 -c $< -o $@
+
+$(BUILD)/c2rt_api_stats.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
+	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -DC2RT_DIAG=1 -DC2RT_TILE_STATS=1 -c $< -o $@
+
+$(STATSNAME): $(filter-out $(BUILD)/c2rt_kernels_u1.o,$(KOBJS)) $(BUILD)/c2rt_kernels_u1_stats.o $(BUILD)/c2rt_api_stats.o $(filter-out $(BUILD)/c2rt_api.o,$(HOBJS))
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
+
 # device check of fp64_lean.h against the compiler's own divide / sqrt expansions (tests/test_gpu_parity.py runs it)
 tests/fp64_lean_check: tests/fp64_lean_check.hip $(CSRC)/fp64_lean.h
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -std=c++17 $(FPFLAGS) -fhip-fp32-correctly-rounded-divide-sqrt $< -o $@
@@ -109,6 +124,11 @@ tests/certain_f32_check: tests/certain_f32_check.hip $(TRACE_DEPS)
 # host build of the CsgDiff void-tile test of the mask pre-pass (tests/test_csg_void_tiles.py, scripts/csg_void_tiles.py)
 tests/libcsg_void_check.so: tests/csg_void_check.cpp $(CSRC)/csg_void.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ $<
+
+# host build of csg_certain.h, the per-lane decision of a leaf CsgOp's winning hit (tests/test_csg_certain_host.py,
+# scripts/csg_certain_census.py) and of the planner's kCsgCertain flag (tests/test_csg_certain_plan.py), without ROCm
+tests/libcsg_certain_check.so: tests/csg_certain_check.cpp $(CSRC)/csg_certain.h $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
+	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/csg_certain_check.cpp $(CSRC)/scene_plan.cpp
 
 # host build of the sphere-silhouette test of the mask pre-pass (tests/test_sphere_cull_tiles.py, scripts/sphere_cull_tiles.py)
 tests/libsphere_cull_check.so: tests/sphere_cull_check.cpp $(CSRC)/csg_void.h
@@ -173,6 +193,6 @@ resource-usage: | $(BUILD)
 	    -c $(CSRC)/$(q).hip -o $(BUILD)/ru_$(q).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
 
 clean:
-	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/ground_certain_check tests/libground_texel_check.so tests/libsphere_interior_check.so tests/tap_average_check
+	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/ground_certain_check tests/libground_texel_check.so tests/libsphere_interior_check.so tests/libcsg_certain_check.so tests/tap_average_check
 
 .PHONY: all clean resource-usage

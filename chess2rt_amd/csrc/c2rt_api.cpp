@@ -83,6 +83,13 @@ static const DiagKnobs &diag_knobs()
     return k;
 }
 
+/* C2RT_DEBUG_CULL bit 9 (diagnostics build): no CsgOp is decided by csg_certain.h — every plan this library makes loses
+ * its kCsgCertain flags (frames are unchanged, slower).  Called on every fresh plan, so that plans stay comparable. */
+static void apply_plan_knobs(ScenePlan &plan)
+{
+    if (diag_knobs().debug_cull & 512) drop_csg_certain(plan);
+}
+
 struct c2rt_ctx {
     int device = 0;
     /* c2rt_init_multi: the further device slots of this (lead) context, each a complete
@@ -400,6 +407,7 @@ int plan_posed_frames(c2rt_ctx *ctx, const c2rt_scene_pose *poses, uint32_t n_fr
         std::string err;
         pose_scene(ctx->scene, &poses[i], undo);
         const int st = replan_scene(ctx->scene, f->plan, err);
+        if (st == C2RT_OK) apply_plan_knobs(f->plan);
         unpose_scene(ctx->scene, &poses[i], undo);
         if (st != C2RT_OK) return fail(ctx, st, "frame %u: %s", i, err.c_str());
         f->own_nodes = !same_bytes(f->plan.nodes, ctx->plan.nodes);
@@ -565,6 +573,7 @@ int update_one(c2rt_ctx *c, const c2rt_scene_pose *pose, hipStream_t stream)
     const std::vector<double> rects = c->plan.shadow_rects;
     const DarkCull dark = c->plan.dark;
     if (const int st = update_scene_plan(c->scene, c->plan, pose, c->err)) return st;
+    apply_plan_knobs(c->plan);
     HIP_TRY(c, hipSetDevice(c->device));
     const std::vector<DevNode> &now = c->plan.nodes;
     for (size_t a = 0; a < now.size();) { /* runs of changed records */
@@ -747,6 +756,7 @@ static int upload_one(c2rt_ctx *ctx, const c2rt_scene_desc *s)
     ctx->has_scene = false;
     ScenePlan plan;
     if ((st = plan_scene(s, plan, ctx->err)) != C2RT_OK) return st;
+    apply_plan_knobs(plan);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     /* frames enqueued on callers' streams may still be reading the tables about to be replaced */
     HIP_TRY(ctx, hipDeviceSynchronize());

@@ -57,6 +57,10 @@ enum GeomFlags : int32_t {
     /* every parameter and table entry (p[], q[]) of a primitive is finite: the premise of the exact early-outs that
      * reason about ordered comparisons (c2rt_trace.inc: cube_away) */
     kGeomFinite = 8,
+    /* a CsgOp over two distinct primitives, each a Sphere or a finite Cube, inside the domain of csg_certain.h
+     * (scene_plan.cpp: csg_certain_ok): the frame kernels decide its winning hit from the children's closed-form
+     * intervals for every lane where that decision is certain (c2rt_trace.inc: csg_intersect_leaf) */
+    kCsgCertain = 16,
 };
 
 struct alignas(16) DevGeom {       /* 128 B */

@@ -419,7 +419,9 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
     uint16_t *ltag = reinterpret_cast<uint16_t *>(cx.lds + cx.csg_cap * (kWave * 8)) + cx.lane + base * kWave;
     const int room = cx.csg_cap - base;
     const int type = G->type, left = G->left, right = G->right, flags = G->flags;
+#if !C2RT_CSG_CERTAIN
     const D3 d = ray.d;
+#endif
 #if C2RT_TILE_STATS
     if (cx.lane_stats) {
         const unsigned long long act = __ballot(true);
@@ -427,6 +429,64 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
     }
 #endif
 
+#if C2RT_CSG_CERTAIN /* the frame units only (c2rt_trace_common.inc): the query units compile the parent's text */
+    int wside = 0, wk = 0;
+    uint32_t wcode = 0;
+    (void)wcode; /* (read by the instances that need the hit record) */
+    double wdist = 0;
+    /* The winner decided from the children's closed-form intervals (csg_certain.h), per lane, where that is certain:
+     * such a lane skips both collect loops, the lists and the sort, and takes its record from the literal stepping
+     * loop below (for hit 0 that is one literal call on the unmoved ray).  An unsure lane runs the literal evaluation,
+     * under divergence.  Not for kRt: the innermost level of a nested tree starts from restarted origins, 1e-6 off a
+     * surface, where nothing is certain. */
+    bool certain = false;
+    if constexpr (NEED != kRt) {
+        /* (kBool: `full` is node_intersect's `own` — a wave whose shadow rays all start on this very node asks nothing) */
+        if (cx.csg_certain && (flags & kCsgCertain) && !(NEED == kBool && __all(full))) { /* wave-uniform */
+            auto child = [&](int c) {
+                const double co[3] = {ray.o.x, ray.o.y, ray.o.z}, cd[3] = {ray.d.x, ray.d.y, ray.d.z};
+                GeomP C = cx.geoms + c;
+                if (C->type == C2RT_GEOM_SPHERE) {
+                    const double cc[3] = {C->p[0], C->p[1], C->p[2]};
+                    return cc_sphere(co, cd, cc, C->p[3], 1.0);
+                }
+                const double lo[3] = {C->q[0], C->q[1], C->q[2]}, hi[3] = {C->q[3], C->q[4], C->q[5]};
+                if constexpr (kLean) { /* the direction's reciprocals are there (prep_dir): 1 / d.x = -rx */
+                    const double ri[3] = {-ray.rx, -ray.ry, -ray.rz};
+                    return cc_cube(co, cd, lo, hi, 1.0, ri);
+                }
+                return cc_cube(co, cd, lo, hi, 1.0);
+            };
+            const CcResult w = cc_decide_with(type - C2RT_GEOM_CSG_UNION, (flags & kCsgShortA) != 0, (flags & kCsgShortB) != 0,
+                                              [&] { return child(left); }, [&] { return child(right); });
+#if C2RT_TILE_STATS
+            if (cx.lane_stats) {
+                const unsigned long long act = __ballot(true), sure = __ballot(w.kind != CC_R_UNSURE);
+                if (cx.lane == (int)__builtin_ctzll(act)) {
+                    atomicAdd(cx.lane_stats + 4 + 3 * kRegions + 0, (unsigned long long)__builtin_popcountll(sure));
+                    atomicAdd(cx.lane_stats + 4 + 3 * kRegions + 1, (unsigned long long)__builtin_popcountll(act & ~sure));
+                }
+            }
+#endif
+            if (w.kind == CC_R_NOHIT) return false;
+            if (w.kind == CC_R_HIT) {
+                if (w.dist - w.del > h.dist) return false; /* the literal `wdist > h.dist`, for every wdist within del */
+                if (NEED == kBool) {
+                    /* (the callers of kBool — test_visibility — read no distance: h.dist stays) */
+                    if (w.dist + w.del < h.dist) return true;
+                } else {
+                    certain = true;
+                    wside = w.side;
+                    wk = w.k;
+                }
+            }
+        }
+    }
+
+    const D3 d = ray.d;
+
+    if (!certain) {
+#endif
     int nL = 0, nR = 0;
     int n = 0;
 #pragma unroll 1
@@ -476,10 +536,12 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
      * is regular; one lane with a tie, a NaN distance, one or three hits on a child (origin inside it, a grazing
      * step) sends the wave through the literal sort and walk below.  `left != right`: the walk tells the lists
      * apart by leaf identity (`current.g is left`), so Op(a, a) is not regular either. */
+#if !C2RT_CSG_CERTAIN
     int wside = 0, wk = 0;
     uint32_t wcode = 0;
     (void)wcode; /* (read by the instances that need the hit record) */
     double wdist = 0;
+#endif
     bool have = false, regular = false;
     if (left != right) {
         const bool hasL = nL == 2, hasR = nR == 2;
@@ -547,6 +609,9 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
     if (!have) return false;
     if (wdist > h.dist) return false;
     if (NEED == kBool) { h.dist = wdist; return true; }
+#if C2RT_CSG_CERTAIN
+    } /* (!certain) */
+#endif
 
     /* re-derive the winning IntersectionData (data = current, rt/geometry.d:326) */
     C2RT_REGION_BEGIN(cx, kRegReplay)
@@ -557,12 +622,18 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
      * with the unmoved ray and cur = 0, so its distance is the primitive's own `mult` (mult + 0.0 == mult), its
      * point is that primitive's `o + d * mult` — Plane rt/geometry.d:40, Sphere :107, Cube :213 — its leaf is
      * the child and its face code sits in the tag: the same operands, the same bits. */
+#if C2RT_CSG_CERTAIN
+    if (wk == 0 && !certain) {
+#else
     if (wk == 0) {
+#endif
         t.dist = wdist;
         t.p = ray.o + d * wdist;
         t.g = child;
         t.code = (int)wcode;
     } else {
+        /* (a certain lane has no list: its record comes from here whatever its k, and for k = 0 the loop below is empty
+         * and this is one literal call on the unmoved ray, the very call the collect loop would have begun with) */
         ORay rr = ray;
         double cur = 0;
         for (int i = 0; i < wk; ++i) {
@@ -576,6 +647,9 @@ __device__ __forceinline__ bool csg_intersect_leaf(const Ctx &cx, GeomP G, const
         t.dist = 1e99;
         geom_intersect<0, NEED>(cx, child, rr, t, full, 0);
         t.dist += cur;
+#if C2RT_CSG_CERTAIN
+        if (certain && t.dist > h.dist) return false; /* the literal rejection, on the literal distance */
+#endif
     }
     h = t;
 
@@ -640,8 +714,14 @@ DEV RayW make_ray(Oob &bad, D3 o, D3 d)
 /* Node.intersect; `best.dist` is data.dist (world units) in and out.  `last` (wave-uniform): no
  * further node will be tested against this ray, so nobody reads the updated best.dist again (it only
  * serves as the next node's limit) and its division is skipped. */
+/* `own` (kBool only, per lane): the ray is a shadow ray that starts ON this node — 1e-6 off its surface, where
+ * csg_certain.h decides nothing; a wave of such lanes does not ask it (csg_intersect_leaf). */
 template <int LEVELS, int NEED, int PO>
+#if C2RT_CSG_CERTAIN
+DEV bool node_intersect(const Ctx &cx, NodeP N, const RayW &ray, Hit &best, bool last = false, bool own = false)
+#else
 DEV bool node_intersect(const Ctx &cx, NodeP N, const RayW &ray, Hit &best, bool last = false)
+#endif
 {
     const uint32_t flags = N->flags;
     ORay rc;
@@ -676,12 +756,12 @@ DEV bool node_intersect(const Ctx &cx, NodeP N, const RayW &ray, Hit &best, bool
 #if C2RT_TILE_STATS
         if (G->type > C2RT_GEOM_CUBE) { /* (scalar) a CsgOp node: the whole evaluation, all lanes back at END */
             C2RT_REGION_BEGIN(cx, kRegCsg)
-            const bool hit_ = geom_intersect_rec<LEVELS, NEED>(cx, G, gid, rc, h, false, 0);
+            const bool hit_ = geom_intersect_rec<LEVELS, NEED>(cx, G, gid, rc, h, C2RT_OWN(NEED), 0);
             C2RT_REGION_END(cx, kRegCsg)
             if (!hit_) return false;
         } else
 #endif
-        if (!geom_intersect_rec<LEVELS, NEED>(cx, G, gid, rc, h, false, 0)) return false;
+        if (!geom_intersect_rec<LEVELS, NEED>(cx, G, gid, rc, h, C2RT_OWN(NEED), 0)) return false;
     }
     if (NEED == kBool) return true;
     if (!last) best.dist = div_r(cx.bad, h.dist, len, linv);
@@ -764,8 +844,13 @@ DEV void hit_surface(const Ctx &cx, NodeP N, const Hit &h, UVWant want_uv, Surf 
 }
 
 /* Scene.testVisibility — rt/scene.d:62-78 */
+/* `self`: the node the segment starts on (a shadow ray of its closest hit), -1 when the caller does not know */
 template <int LEVELS, int PO>
+#if C2RT_CSG_CERTAIN
+DEV bool test_visibility(const Ctx &cx, D3 from, D3 to, uint32_t node_mask, bool ground_only, int self = -1)
+#else
 DEV bool test_visibility(const Ctx &cx, D3 from, D3 to, uint32_t node_mask, bool ground_only)
+#endif
 {
     const D3 raw = to - from;
     if (!(PO & kSpecPlanes) && ground_only) { /* wave-uniform */
@@ -787,7 +872,11 @@ DEV bool test_visibility(const Ctx &cx, D3 from, D3 to, uint32_t node_mask, bool
     Hit temp;
     temp.dist = rlen;                                             /* magnitude(raw) */
     for (; n < nn; n = next_node(node_mask, n + 1)) /* scalar loop, file order */
+#if C2RT_CSG_CERTAIN
+        if (node_intersect<LEVELS, kBool, PO>(cx, cx.nodes + n, ray, temp, false, self == (int)n)) return false;
+#else
         if (node_intersect<LEVELS, kBool, PO>(cx, cx.nodes + n, ray, temp)) return false;
+#endif
     return true;
 }
 
@@ -840,7 +929,11 @@ DEV void light_terms(Oob &bad, LightP L, D3 lightPos, D3 p, D3 N, D3 rd, bool ph
 }
 
 template <int LEVELS, bool MLC, int PO>
+#if C2RT_CSG_CERTAIN
+DEV F3 shade(const RenderParams &P, const Ctx &cx, const Mat &mat, D3 rd, const Surf &h, uint32_t &shadow_rays, int self = -1)
+#else
 DEV F3 shade(const RenderParams &P, const Ctx &cx, const Mat &mat, D3 rd, const Surf &h, uint32_t &shadow_rays)
+#endif
 {
     const bool phong = mat.shader_type == C2RT_SHADER_PHONG;
     const D3 N = dot(rd, h.n) < 0 ? h.n : -h.n; /* faceforward — rt/imported_types.d:69-73 */
@@ -866,7 +959,7 @@ DEV F3 shade(const RenderParams &P, const Ctx &cx, const Mat &mat, D3 rd, const 
                 F3 baseLight;
                 light_terms(cx.bad, L, lightPos, h.p, N, rd, phong, cosTheta, baseLight, cosGamma);
                 C2RT_REGION_BEGIN(cx, kRegShadow)
-                const bool visible = test_visibility<LEVELS, PO>(cx, from, lightPos, cx.shadow_mask0, cx.shadow_ground_only);
+                const bool visible = test_visibility<LEVELS, PO>(cx, from, lightPos, cx.shadow_mask0, cx.shadow_ground_only C2RT_SELF);
                 C2RT_REGION_END(cx, kRegShadow)
                 if (visible) {
                     C2RT_REGION_BEGIN(cx, kRegLight)
@@ -897,7 +990,7 @@ DEV F3 shade(const RenderParams &P, const Ctx &cx, const Mat &mat, D3 rd, const 
                 if (L->lit & 1u) {
                     shadow_rays += 1;
                     const D3 from = p + N * 1e-6;
-                    if (test_visibility<LEVELS, PO>(cx, from, ld3(L->pos), l == 0 ? cx.shadow_mask0 : light_shadow_mask(P, cx.mask_slot, l), l == 0 && cx.shadow_ground_only))
+                    if (test_visibility<LEVELS, PO>(cx, from, ld3(L->pos), l == 0 ? cx.shadow_mask0 : light_shadow_mask(P, cx.mask_slot, l), l == 0 && cx.shadow_ground_only C2RT_SELF))
                         vis |= 1u << (l - l0);
                 }
             }
@@ -1070,13 +1163,21 @@ DEV F3 raytrace(const RenderParams &P, const Ctx &cx, D3 o, D3 raw, Counters &cn
     {
         C2RT_REGION_BEGIN(cx, kRegShade)
         F3 col_ = mkf(0, 0, 0);
+#if C2RT_CSG_CERTAIN
+        if (closest >= 0) col_ = shade<LEVELS, MLC, PO>(P, cx, mat, d, surf, cnt.shadow, closest);
+#else
         if (closest >= 0) col_ = shade<LEVELS, MLC, PO>(P, cx, mat, d, surf, cnt.shadow);
+#endif
         C2RT_REGION_END(cx, kRegShade)
         return col_;
     }
 #endif
     if (closest < 0) return mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
+#if C2RT_CSG_CERTAIN
+    return shade<LEVELS, MLC, PO>(P, cx, mat, d, surf, cnt.shadow, closest);
+#else
     return shade<LEVELS, MLC, PO>(P, cx, mat, d, surf, cnt.shadow);
+#endif
 }
 
 /* The first half of `trace` (rt/renderer.d:325-338) for a CALLER's ray (c2rt_trace_rays; c2rt_rays.hip,
@@ -1658,6 +1759,9 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
     cx.overflow = false;
     cx.bad = tile_bad;
     cx.trunc_counter = CNT ? P.ray_counters + 2 : nullptr;
+#if C2RT_CSG_CERTAIN
+    cx.csg_certain = !CNT;
+#endif
 #if C2RT_TILE_STATS
     cx.lane_stats = P.tile_stats ? reinterpret_cast<unsigned long long *>(P.tile_stats + 2 * (size_t)P.tiles_x * P.tiles_y) : nullptr;
 #endif

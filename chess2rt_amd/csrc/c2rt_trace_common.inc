@@ -19,10 +19,26 @@
 #include <type_traits>
 
 #include "c2rt_device.h"
+#include "csg_certain.h"
 #include "f32_certain.h"
 #include "fp64_lean.h"
 #include "ground_certain.h"
 #include "x87.h"
+
+/* Leaf CsgOps decided by csg_certain.h (c2rt_trace.inc: csg_intersect_leaf) exist in the FRAME units only.  A query unit
+ * (C2RT_TRACE_EXACT_ONLY) compiles the text it compiled before that route existed, token for token — the route's
+ * declarations, the `own` / `self` arguments that carry a shadow ray's source node down, Ctx::csg_certain — so that its
+ * kernels stay the instructions they were (scripts/isa_equal.py): an argument that is never read still moved their
+ * scalar registers. */
+#ifdef C2RT_TRACE_EXACT_ONLY
+#define C2RT_CSG_CERTAIN 0
+#define C2RT_OWN(NEED) false
+#define C2RT_SELF
+#else
+#define C2RT_CSG_CERTAIN 1
+#define C2RT_OWN(NEED) ((NEED) == kBool && own)
+#define C2RT_SELF , self
+#endif
 
 namespace c2rt {
 namespace {

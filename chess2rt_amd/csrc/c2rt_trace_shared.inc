@@ -205,6 +205,12 @@ struct Ctx {
      * headline kernel, which sits exactly at its 128-VGPR budget, a flag carried to the end of the tile
      * cost 3 % and an atomic on the spot 8 %. */
     unsigned long long *trunc_counter;
+    /* a kCsgCertain CsgOp may be decided by csg_certain.h (csg_intersect_leaf).  A compile-time constant wherever it is
+     * set: true in the uncounted frame instances, false in the counted ones — which therefore compare the two routes
+     * bit for bit in every counted frame — and in the query kernels. */
+#if C2RT_CSG_CERTAIN
+    bool csg_certain;
+#endif
 #if C2RT_TILE_STATS
     unsigned long long *lane_stats; /* diagnostics: {active, slots} pairs — [0..1] CSG evaluations entered, [2..3] child stepping calls */
 #endif
@@ -235,6 +241,9 @@ DEV void query_ctx(Ctx &cx, const RenderParams &P, KArgs K, char *lds, int lane)
     cx.overflow = false;
     oob_init(cx.bad);
     cx.trunc_counter = nullptr;
+#if C2RT_CSG_CERTAIN
+    cx.csg_certain = false;
+#endif
 #if C2RT_TILE_STATS
     cx.lane_stats = nullptr;
 #endif

@@ -71,6 +71,24 @@ BoundInfo enclose(const BoundInfo &a, const BoundInfo &b)
     return o;
 }
 
+/* kCsgCertain: the CsgOp over children l and r lies in the domain csg_certain.h's bounds were derived for — two DISTINCT
+ * primitives (the walk tells the lists apart by leaf identity: Op(a, a) is another walk), each a Sphere or a Cube with
+ * finite parameters, every centre coordinate within 2^20 and the radius / side in [2^-10, 2^20].  A Plane child, a
+ * nested child, a non-finite or degenerate primitive or geometry beyond that scale leave the flag off. */
+bool csg_certain_ok(const c2rt_scene_desc *s, int32_t l, int32_t r)
+{
+    if (l == r) return false;
+    for (const int32_t c : {l, r}) {
+        const int t = s->geom_type[c];
+        if (t != C2RT_GEOM_SPHERE && t != C2RT_GEOM_CUBE) return false;
+        const double *p = s->geom_param + 4 * (size_t)c;
+        for (int i = 0; i < 3; ++i)
+            if (!(std::fabs(p[i]) <= 0x1p20)) return false;
+        if (!(p[3] >= 0x1p-10 && p[3] <= 0x1p20)) return false;
+    }
+    return true;
+}
+
 /* geometries must already be validated acyclic (csg_depth) */
 BoundInfo bound_of(const c2rt_scene_desc *s, int32_t g, std::vector<BoundInfo> &memo, std::vector<DevGeom> &geoms)
 {
@@ -94,6 +112,7 @@ BoundInfo bound_of(const c2rt_scene_desc *s, int32_t g, std::vector<BoundInfo> &
         const bool shortB = t == C2RT_GEOM_CSG_INTER && !is_csg(s->geom_type[l]);
         if (shortA) geoms[g].flags |= kCsgShortA;
         if (shortB) geoms[g].flags |= kCsgShortB;
+        if (csg_certain_ok(s, l, r)) geoms[g].flags |= kCsgCertain;
         if (shortA && bl.bounded) b = bl;       /* nothing on the left => false */
         else b = enclose(bl, br);               /* nothing on either side => false */
         b.done = true;
@@ -767,6 +786,12 @@ int check_scene_pose(const SceneCopy &scene, const c2rt_scene_pose *pose, std::s
         }
     }
     return C2RT_OK;
+}
+
+void drop_csg_certain(ScenePlan &plan)
+{
+    for (DevGeom &g : plan.geoms) g.flags &= ~kCsgCertain;
+    for (DevNode &n : plan.nodes) n.g.flags &= ~kCsgCertain;
 }
 
 int replan_scene(const SceneCopy &scene, ScenePlan &plan, std::string &err)

@@ -61,6 +61,10 @@ int check_scene_desc(const c2rt_scene_desc *s, std::string &err);
  * reason in `err`, and `plan` untouched. */
 int plan_scene(const c2rt_scene_desc *s, ScenePlan &plan, std::string &err);
 
+/* clears kCsgCertain (c2rt_device.h) in every record of `plan`: the diagnostics switch that leaves every CsgOp to the
+ * literal evaluation */
+void drop_csg_certain(ScenePlan &plan);
+
 /* ---- posing an uploaded scene (c2rt_update_scene, c2rt_render_frames_posed) ---- */
 
 /* A deep copy of a planned description without its texels: `desc` points into the vectors (texels null, n_texels
@@ -126,7 +130,8 @@ struct DiagKnobs {
      * sphere-silhouette test in the mask pre-pass; bit 4: no ground-tile path (RenderParams::ground_fast stays 0); bit 5: no
      * dark-tile test in the mask pre-pass (dark_cull_of); bit 6: no short-chain ground tiles (RenderParams::ground_certain_cq
      * stays 0); bit 7: no sphere-interior tiles (SphereCull::interior stays 0); bit 8: sphere-interior
-     * tiles whatever the frame's size (sphere_cull_of: kSphereTileMinSamples) */
+     * tiles whatever the frame's size (sphere_cull_of: kSphereTileMinSamples); bit 9: no CsgOp decided by csg_certain.h
+     * (drop_csg_certain on every plan: a switch of the scene's tables, not of a frame) */
     int debug_cull = 0;
     int csg_first_cap = 0;             /* C2RT_CSG_FIRST_CAP=<entries>: the first pass's hit-stack capacity */
 };
