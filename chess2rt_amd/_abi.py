@@ -196,6 +196,25 @@ class TapTable(C.Structure):
     ]
 
 
+class GatherOpts(C.Structure):
+    """c2rt_gather_opts: the counter RNG's seed and the sample count K (1 .. 64)"""
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("samples", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class GatherPlanes(C.Structure):
+    """c2rt_gather_planes: one nullable pointer per plane (host or device memory, by entry point)"""
+    _fields_ = [
+        ("node", C.c_void_p),
+        ("hits", C.c_void_p),
+        ("indirect", C.c_void_p),
+        ("bounce", C.c_void_p),
+    ]
+
+
 class ScenePose(C.Structure):
     """c2rt_scene_pose: new transforms ([n_nodes][30] doubles) and light values for some nodes / lights of the uploaded scene"""
     _fields_ = [
@@ -298,6 +317,10 @@ C2RT_SYMBOLS = {
     "c2rt_render_occlusion": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes)]),
     "c2rt_trace_rays_occlusion_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes), _VP]),
     "c2rt_trace_rays_occlusion": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes)]),
+    "c2rt_render_gather_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(GatherOpts), C.POINTER(GatherPlanes), _VP]),
+    "c2rt_render_gather": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(GatherOpts), C.POINTER(GatherPlanes)]),
+    "c2rt_trace_rays_gather_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(GatherOpts), C.POINTER(GatherPlanes), _VP]),
+    "c2rt_trace_rays_gather": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(GatherOpts), C.POINTER(GatherPlanes)]),
     "c2rt_render_frame_adaptive_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frame_adaptive": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frames_adaptive_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
@@ -337,6 +360,7 @@ C2RT_HOST_SYMBOLS = {
     "c2rt_host_render_hit_layers": (C.c_int, [_VP, _VP, C.c_uint32, C.POINTER(HitPlanes), _VP]),
     "c2rt_host_render_shading": (C.c_int, [_VP, _VP, C.POINTER(ShadePlanes)]),
     "c2rt_host_render_occlusion": (C.c_int, [_VP, _VP, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes)]),
+    "c2rt_host_render_gather": (C.c_int, [_VP, _VP, C.POINTER(GatherOpts), C.POINTER(GatherPlanes)]),
     "c2rt_host_render_rt_adaptive": (C.c_int, [_VP, _VP, _VP, _VP]),
     "c2rt_host_render_rt_taps": (C.c_int, [_VP, _VP, _TAPS_P, _VP]),
     "c2rt_host_render_rt_adaptive_taps": (C.c_int, [_VP, _VP, _TAPS_P, _VP, _VP]),

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (CameraFrame, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
+from ._abi import (CameraFrame, GatherOpts, GatherPlanes, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
                    ScenePose, Segment, ShadePlanes, TapTable, TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
@@ -129,6 +129,38 @@ def _tap_table(taps):
         t.offset[s][0] = dx
         t.offset[s][1] = dy
     return t
+
+
+# c2rt_gather_planes: plane name -> (dtype, components per sample), in the order of the struct's members
+GATHER_PLANES = {"node": (np.int32, 1), "hits": (np.uint64, 1), "indirect": (np.float32, 3), "bounce": (np.float32, 3)}
+
+
+def _new_gather_planes(names, shape):
+    """(GatherPlanes of fresh host arrays, {name: array}) for the planes named, `shape` samples each; the others stay null"""
+    names = tuple(names)
+    for n in names:
+        if n not in GATHER_PLANES:
+            raise ValueError("unknown gather plane %r (one of %s)" % (n, ", ".join(GATHER_PLANES)))
+    out, pl = {}, GatherPlanes()
+    for n in names:
+        dtype, comps = GATHER_PLANES[n]
+        out[n] = np.empty(tuple(shape) if comps == 1 else tuple(shape) + (comps,), dtype=dtype)
+        setattr(pl, n, out[n].ctypes.data)
+    return pl, out
+
+
+def _device_gather_planes(ptrs):
+    """GatherPlanes of the device pointers in `ptrs` ({plane name: pointer}); planes left out (or 0 / None) stay null"""
+    pl = GatherPlanes()
+    for n, ptr in dict(ptrs).items():
+        if n not in GATHER_PLANES:
+            raise ValueError("unknown gather plane %r (one of %s)" % (n, ", ".join(GATHER_PLANES)))
+        setattr(pl, n, ptr or None)
+    return pl
+
+
+def _gather_opts(samples, seed):
+    return GatherOpts(seed=int(seed), samples=int(samples), reserved=0)
 
 
 def makePose(nodes=None, lights=None):
@@ -799,6 +831,43 @@ class Context:
         self._check(self._lib.c2rt_trace_rays_occlusion_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(occ), C.byref(pl),
                                                                C.c_void_p(stream)))
 
+    def renderGather(self, cam, opts, samples, seed=0, planes=tuple(GATHER_PLANES)):
+        """One-bounce indirect diffuse light of every pixel's closest hit (c2rt_render_gather): `samples` (1 .. 64) rays
+        over the hemisphere around the hit's normal, each traced and shaded as traceRays does.  A dict of numpy arrays
+        for the planes named — node (int32) and hits (uint64, bit s: sample s's ray hit a node) of shape (local_rows,
+        W); indirect and bounce (local_rows, W, 3) float32: the mean weighted colour arriving, and that times the hit's
+        albedo — what to add to the frame's colour.  A miss holds -1, 0 and zeros.  node alone traces no sample.
+        Refuses what renderHits refuses."""
+        g = _gather_opts(samples, seed)
+        pl, out = _new_gather_planes(planes, (self.localRows(opts), opts.width))
+        self._check(self._lib.c2rt_render_gather(self._h, C.byref(cam), C.byref(opts), C.byref(g), C.byref(pl)))
+        return out
+
+    def renderGatherDevice(self, cam, opts, samples, ptrs, seed=0, stream=0):
+        """Enqueue the gather planes on `stream` into device memory: `ptrs` maps plane names (GATHER_PLANES) to device
+        pointers of local_rows * W * components elements; planes left out (or 0 / None) are not written."""
+        g = _gather_opts(samples, seed)
+        pl = _device_gather_planes(ptrs)
+        self._check(self._lib.c2rt_render_gather_device(self._h, C.byref(cam), C.byref(opts), C.byref(g), C.byref(pl), C.c_void_p(stream)))
+
+    def traceRaysGather(self, rays, samples, seed=0, planes=tuple(GATHER_PLANES)):
+        """The same planes for caller-supplied rays (c2rt_trace_rays_gather): `rays` as for traceRays; a dict of arrays of
+        shape (n,) or (n, 3).  Ray i draws the samples of index i; node is traceRays'."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays: expected shape (n, 6), got %r" % (rays.shape,))
+        g = _gather_opts(samples, seed)
+        pl, out = _new_gather_planes(planes, (rays.shape[0],))
+        self._check(self._lib.c2rt_trace_rays_gather(self._h, rays.ctypes.data_as(C.c_void_p), rays.shape[0], C.byref(g), C.byref(pl)))
+        return out
+
+    def traceRaysGatherDevice(self, rays_ptr, n, samples, ptrs, seed=0, stream=0):
+        """Enqueue the query on `stream` over device memory: n c2rt_ray at rays_ptr, `ptrs` as for renderGatherDevice with
+        n samples per plane."""
+        g = _gather_opts(samples, seed)
+        pl = _device_gather_planes(ptrs)
+        self._check(self._lib.c2rt_trace_rays_gather_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(g), C.byref(pl), C.c_void_p(stream)))
+
     def testVisibility(self, segments):
         """Scene.testVisibility for (n, 6) float64 segments (from, to): (n,) uint8, 1 = nothing in between."""
         seg = np.ascontiguousarray(segments, dtype=np.float64)
@@ -926,6 +995,14 @@ class Renderer:
         occ = _occlusion_opts(samples, radius, seed)
         pl, out = _new_occlusion_planes(planes, (s.frame_height, s.frame_width))
         self.ctx._check(self._lib.c2rt_host_render_occlusion(self.ctx.handle, self.scene._h, C.byref(occ), C.byref(pl)))
+        return out
+
+    def renderGather(self, samples, seed=0, planes=tuple(GATHER_PLANES)):
+        """Context.renderGather for the scene's own camera and frame size (c2rt_host_render_gather)."""
+        s = self.scene.settings
+        g = _gather_opts(samples, seed)
+        pl, out = _new_gather_planes(planes, (s.frame_height, s.frame_width))
+        self.ctx._check(self._lib.c2rt_host_render_gather(self.ctx.handle, self.scene._h, C.byref(g), C.byref(pl)))
         return out
 
 

@@ -1438,10 +1438,12 @@ template <class S> struct PlaneBytes;
 template <> struct PlaneBytes<c2rt_hit_planes> { static constexpr size_t v[] = {4, 4, 8, 16, 24, 24, 12}; };  /* 92 B per sample */
 template <> struct PlaneBytes<c2rt_shade_planes> { static constexpr size_t v[] = {4, 12, 12, 12, 4, 12}; };   /* 56 B per sample */
 template <> struct PlaneBytes<c2rt_occlusion_planes> { static constexpr size_t v[] = {4, 8, 4, 24}; };        /* 40 B per sample */
+template <> struct PlaneBytes<c2rt_gather_planes> { static constexpr size_t v[] = {4, 8, 12, 12}; };          /* 36 B per sample */
 template <class S> constexpr int kPlanes = (int)(sizeof PlaneBytes<S>::v / sizeof(size_t));
 static_assert(sizeof(c2rt_hit_planes) == kPlanes<c2rt_hit_planes> * sizeof(void *) &&
               sizeof(c2rt_shade_planes) == kPlanes<c2rt_shade_planes> * sizeof(void *) &&
-              sizeof(c2rt_occlusion_planes) == kPlanes<c2rt_occlusion_planes> * sizeof(void *), "the plane structs are arrays of pointers");
+              sizeof(c2rt_occlusion_planes) == kPlanes<c2rt_occlusion_planes> * sizeof(void *) &&
+              sizeof(c2rt_gather_planes) == kPlanes<c2rt_gather_planes> * sizeof(void *), "the plane structs are arrays of pointers");
 
 /* What a host variant stages: its outputs in staging order.  An output is `layers` slices (layer-major on both sides)
  * of samples of `bytes` bytes each; `host` null: not asked for, takes no room.  lay_out places them. */
@@ -1786,6 +1788,89 @@ int c2rt_trace_rays_occlusion(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, c
         const uint64_t base = first;
         first += m;
         return launch_trace_rays_occlusion(p, ctx->plan.csg_levels, rays_dev, m, base, *occ, outs.planes<c2rt_occlusion_planes>(), ctx->stream);
+    });
+}
+
+/* ---- gather planes: one-bounce indirect light of every hit (c2rt_gather.hip) ---------------------------------------- */
+
+/* the call's own refusals, behind the frame call's or the ray call's, in the documented order */
+static int check_gather_args(c2rt_ctx *ctx, const c2rt_gather_opts *g, const c2rt_gather_planes *planes)
+{
+    if (!g) return fail(ctx, C2RT_ERR_INVALID_ARG, "null gather options");
+    if (g->samples == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "gather samples is 0: at least one sample");
+    if (g->reserved != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "c2rt_gather_opts.reserved is %u: must be 0", (unsigned)g->reserved);
+    if (g->samples > C2RT_MAX_GATHER_SAMPLES)
+        return fail(ctx, C2RT_ERR_LIMIT, "%u gather samples (at most %u)", (unsigned)g->samples, (unsigned)C2RT_MAX_GATHER_SAMPLES);
+    if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
+    if (!any_plane(*planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all four pointers of c2rt_gather_planes are null");
+    return C2RT_OK;
+}
+
+/* c2rt_render_hits' refusals in its order and wording, with the options and these planes in the place of the hit planes */
+static int check_gather_frame(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_gather_opts *g,
+                              const c2rt_gather_planes *planes)
+{
+    if (const int st = check_frame_args(ctx, cam, opts)) return st;
+    if (const int st = check_gather_args(ctx, g, planes)) return st;
+    return check_one_ray_per_pixel(ctx, cam, opts, "gather is", "gather");
+}
+
+int c2rt_render_gather_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_gather_opts *g,
+                              const c2rt_gather_planes *planes_dev, void *hip_stream)
+{
+    if (const int st = check_gather_frame(ctx, cam, opts, g, planes_dev)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    if (p.local_rows == 0) return C2RT_OK;
+    const int e = launch_gather_planes(p, ctx->plan.csg_levels, *g, *planes_dev, 0, p.local_rows, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "gather plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+/* Host variant: c2rt_render_hits' chunks of whole rows, plane after plane for the chunk size and only for the planes
+ * asked for — 36 B per pixel, 9 MiB at most.  A chunk's pixels draw the samples of their place in the frame. */
+int c2rt_render_gather(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_gather_opts *g,
+                       const c2rt_gather_planes *planes_host)
+{
+    if (const int st = check_gather_frame(ctx, cam, opts, g, planes_host)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    if (p.local_rows == 0) return C2RT_OK;
+    Staging outs;
+    outs.add_planes(*planes_host);
+    return row_chunks(ctx, p, 1, outs, "gather plane", [&](uint32_t r0, uint32_t m, size_t) {
+        return launch_gather_planes(p, ctx->plan.csg_levels, *g, outs.planes<c2rt_gather_planes>(), r0, m, ctx->stream);
+    });
+}
+
+int c2rt_trace_rays_gather_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, const c2rt_gather_opts *g, const c2rt_gather_planes *planes_dev,
+                                  void *hip_stream)
+{
+    if (const int st = check_query_args(ctx, rays_dev, n, true)) return st < 0 ? C2RT_OK : st;
+    if (const int st = check_gather_args(ctx, g, planes_dev)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    query_params(ctx, p);
+    const int e = launch_trace_rays_gather(p, ctx->plan.csg_levels, rays_dev, n, 0, *g, *planes_dev, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "gather plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+/* Host variant: c2rt_trace_rays' staging, [rays | planes asked for] for chunks of at most kQueryChunk rays; ray_chunks
+ * launches the chunks in order, so `first` is the index in the caller's array of the chunk's first ray */
+int c2rt_trace_rays_gather(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const c2rt_gather_opts *g, const c2rt_gather_planes *planes_host)
+{
+    if (const int st = check_query_args(ctx, rays, n, true)) return st < 0 ? C2RT_OK : st;
+    if (const int st = check_gather_args(ctx, g, planes_host)) return st;
+    Staging outs;
+    outs.add_planes(*planes_host);
+    uint64_t first = 0;
+    return ray_chunks(ctx, rays, n, kQueryChunk, outs, "gather plane", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t m, uint64_t) {
+        const uint64_t base = first;
+        first += m;
+        return launch_trace_rays_gather(p, ctx->plan.csg_levels, rays_dev, m, base, *g, outs.planes<c2rt_gather_planes>(), ctx->stream);
     });
 }
 

@@ -33,20 +33,6 @@ struct OccArgs {
     uint32_t samples;
 };
 
-/* hemisphereSample(N), rt/shader.d:156-174, draw s of the sample whose key is `key`: theta = 2 pi u, phi = acos(w) -
- * pi / 2 with w = 2 v - 1, so sin(phi) = -w and cos(phi) = sqrt(1 - w^2) — IEEE +, *, sqrt and lens_sincos2pi only, no
- * libm (include/c2rt.h, "Definition of a sample") */
-DEV D3 hemisphere_sample(const uint32_t key, const uint32_t s, const D3 N)
-{
-    const double u = rng_uniform(key, s, 0), v = rng_uniform(key, s, 1);
-    double sn, cs;
-    lens_sincos2pi(u, sn, cs);
-    const double w = 2.0 * v - 1.0;
-    const double c = sqrt(1.0 - w * w);
-    const D3 res = mk(cs * c, -w, sn * c);
-    return dot(res, N) < 0 ? -res : res;
-}
-
 /* The planes of sample `idx` — the ray (o, d) of a live lane — stored at element `at` of each plane */
 template <int LEVELS>
 DEV void occlusion_sample(const Ctx &cx, const c2rt_occlusion_planes &out, const OccArgs &occ, const size_t at, const uint64_t idx, D3 o, D3 d)

@@ -1,5 +1,5 @@
 /*
- * c2rt_query.h — launch interface of the query kernels (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip, c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_adaptive.hip, c2rt_sample_taps.hip), shared
+ * c2rt_query.h — launch interface of the query kernels (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip, c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_gather.hip, c2rt_adaptive.hip, c2rt_sample_taps.hip), shared
  * by those files and c2rt_api.cpp.  A header of its own: c2rt_device.h is a prerequisite of every frame-kernel object,
  * and query work should not rebuild them.  All return hipError_t as int; every pointer is a device pointer.
  *
@@ -17,6 +17,7 @@ namespace c2rt {
 inline bool any_plane(const c2rt_hit_planes &o) { return o.node || o.leaf || o.dist || o.uv || o.p || o.normal || o.rgb; }
 inline bool any_plane(const c2rt_shade_planes &o) { return o.node || o.albedo || o.light || o.specular || o.visible || o.rgb; }
 inline bool any_plane(const c2rt_occlusion_planes &o) { return o.node || o.open || o.ao || o.bent; }
+inline bool any_plane(const c2rt_gather_planes &o) { return o.node || o.hits || o.indirect || o.bounce; }
 
 /* Ray and visibility queries (c2rt_trace_rays*, c2rt_test_visibility*): no camera; 0 < n <= C2RT_MAX_RAYS; hits / rgb
  * nullable, not both */
@@ -49,6 +50,13 @@ int launch_occlusion_planes(const RenderParams &p, int csg_levels, const c2rt_oc
                             uint32_t rows, void *stream);
 int launch_trace_rays_occlusion(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_occlusion_opts &occ,
                                 const c2rt_occlusion_planes &out, void *stream);
+/* Gather planes (c2rt_render_gather*, c2rt_trace_rays_gather*; c2rt_gather.hip): the hit planes' rows, or the ray query's
+ * rays, with g.samples rays spawned over the hemisphere behind every hit, traced and shaded as c2rt_trace_rays' are; at
+ * least one plane non-null, 1 <= g.samples <= C2RT_MAX_GATHER_SAMPLES.  Ray i draws the samples of index base + i */
+int launch_gather_planes(const RenderParams &p, int csg_levels, const c2rt_gather_opts &g, const c2rt_gather_planes &out, uint32_t row0, uint32_t rows,
+                         void *stream);
+int launch_trace_rays_gather(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_gather_opts &g,
+                             const c2rt_gather_planes &out, void *stream);
 /* Adaptive anti-aliasing (c2rt_render_frame[s]_adaptive*): the flag images needs_aa[i][y][x] of n_frames whole one-tap
  * frames side by side, then the flagged pixels of the whole frame `p` describes (no strips) from their one-tap to their
  * five-tap value, in place; launch_aa_refine_batch: the same for the n_frames frames whose blocks are at table_dev (p0:

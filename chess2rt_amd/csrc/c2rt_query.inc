@@ -1,7 +1,7 @@
 /*
  * c2rt_query.inc — what the query kernels share (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip,
- * c2rt_shade_planes.hip, c2rt_adaptive.hip): a lane traces ONE ray that is not a frame tile's — the caller's, or the
- * camera's through a pixel — with exact:: arithmetic (the probe's choice; bit-equal to what the frames compute), every
+ * c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_gather.hip, c2rt_adaptive.hip, c2rt_sample_taps.hip): a lane traces
+ * ONE ray that is not a frame tile's — the caller's, or the camera's through a pixel — with exact:: arithmetic (the probe's choice; bit-equal to what the frames compute), every
  * culling mask all ones (query_ctx, c2rt_trace_shared.inc), no ground-tile shortcut, and a full-capacity CSG hit stack:
  * kCsgFullCap(LEVELS) entries in one launch, which cannot overflow, so there is no retry list and no per-stream scratch.
  * That is 10 / 20 / 30 / 40 KiB of LDS per wave at depth 1 / 2 / 3 / 4: the LDS, not the registers, bounds the
@@ -10,7 +10,8 @@
  * C2RT_TRACE_EXACT_ONLY.
  *
  * Each piece once, in this order: the ABI layout the lane code relies on; the register budget; where a lane's sample
- * comes from (load6 for a caller's record, tile_pixel and pixel_ray for a camera's pixel); where its result goes
+ * comes from (load6 for a caller's record, tile_pixel and pixel_ray for a camera's pixel; hemisphere_sample for the
+ * directions the occlusion and gather planes draw behind a hit); where its result goes
  * (store_colour, store_record, sample_colour, store_hit_planes); the host side of a launch (ray_grid, tile_grid,
  * launch_query).
  */
@@ -87,6 +88,20 @@ DEV void pixel_ray(const Ctx &cx, const RenderParams &P, double x, double y, D3 
     D3 raw;
     exact::screen_ray<false>(cx.bad, P, x, y, 0, rng, o, raw);
     d = exact::normalized(cx.bad, raw);
+}
+
+/* hemisphereSample(N), rt/shader.d:156-174, draw s of the sample whose key is `key` (the occlusion and gather planes):
+ * theta = 2 pi u, phi = acos(w) - pi / 2 with w = 2 v - 1, so sin(phi) = -w and cos(phi) = sqrt(1 - w^2) — IEEE +, *,
+ * sqrt and lens_sincos2pi only, no libm (include/c2rt.h, the definition of a sample under "occlusion planes") */
+DEV D3 hemisphere_sample(const uint32_t key, const uint32_t s, const D3 N)
+{
+    const double u = rng_uniform(key, s, 0), v = rng_uniform(key, s, 1);
+    double sn, cs;
+    lens_sincos2pi(u, sn, cs);
+    const double w = 2.0 * v - 1.0;
+    const double c = sqrt(1.0 - w * w);
+    const D3 res = mk(cs * c, -w, sn * c);
+    return dot(res, N) < 0 ? -res : res;
 }
 
 /* one 12-byte store per lane, as the frame kernels store pixels */

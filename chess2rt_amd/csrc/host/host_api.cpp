@@ -301,6 +301,19 @@ int c2rt_host_render_occlusion(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_occ
     return c2rt_render_occlusion(ctx, &cam, &o, occ, planes);
 }
 
+int c2rt_host_render_gather(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_gather_opts *g, const c2rt_gather_planes *planes)
+{
+    if (!ctx || !s) return C2RT_ERR_INVALID_ARG;
+    // c2rt_host_render_hits' set-up; the options, the planes and the camera are judged by c2rt_render_gather
+    c2rt_camera_frame cam;
+    c2rt_host_scene_begin_frame(s, &cam);
+    Renderer r{ctx, s, nullptr, nullptr, nullptr};
+    const int st = r.ensureUploaded();
+    if (st != C2RT_OK) return st;
+    const c2rt_render_opts o = opts_of(*s->scene);
+    return c2rt_render_gather(ctx, &cam, &o, g, planes);
+}
+
 int c2rt_host_render_rt_adaptive(c2rt_ctx *ctx, c2rt_host_scene *s, float *out_rgb, uint8_t *needs_aa)
 {
     if (!ctx || !s || !out_rgb) return C2RT_ERR_INVALID_ARG;

@@ -829,6 +829,90 @@ int c2rt_trace_rays_occlusion_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, ui
 int c2rt_trace_rays_occlusion(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n,
                               const c2rt_occlusion_opts *occ, const c2rt_occlusion_planes *planes_host);
 
+/* ---- gather planes: one-bounce indirect diffuse light of every hit ----------- */
+
+/* Most spawned rays per sample; C2RT_ERR_LIMIT beyond (the mask is one 64-bit word). */
+#define C2RT_MAX_GATHER_SAMPLES 64
+
+typedef struct c2rt_gather_opts {      /* 16 bytes */
+    uint64_t seed;       /* counter-RNG seed (opts->seed of a camera call is ignored) */
+    uint32_t samples;    /* K: 1 .. C2RT_MAX_GATHER_SAMPLES */
+    uint32_t reserved;   /* must be 0 */
+} c2rt_gather_opts;
+
+typedef struct c2rt_gather_planes {    /* 32 bytes; every pointer nullable, at least one given */
+    int32_t  *node;      /* [..]    closest node, -1: no hit (the hit planes' `node`) */
+    uint64_t *hits;      /* [..]    bit s (s < K): sample s's ray hit a node; bits >= K are 0 */
+    float    *indirect;  /* [..][3] mean weighted colour arriving over the hemisphere */
+    float    *bounce;    /* [..][3] albedo * indirect: what to ADD to the frame's colour */
+} c2rt_gather_planes;
+
+/* One-bounce indirect diffuse light of the closest hit of ONE sample: K rays from Lambert.spawnRay's origin (p + N *
+ * 1e-6, rt/shader.d:118-135) along directions of hemisphereSample(N) (rt/shader.d:156-174), each given the colour of
+ * Renderer.raytrace — what c2rt_trace_rays returns as `rgb` — and the weight brdfEval / pdf of pathtrace_impl
+ * (rt/renderer.d:451-460) without the albedo.  `frame + bounce` is a one-bounce global-illumination frame.  Sample index
+ * idx and ray (o, d) are exactly the occlusion planes' —
+ *   camera calls: idx = FRAME row * W + column (strips and host chunks do not change it), (o, d) the ray
+ *     c2rt_render_hits traces for the pixel; planes are row-major [local_rows][W], strips as there;
+ *   ray calls: idx = the ray's index i in the caller's array (whatever chunk it travels in), `dir` exactly as given;
+ *     planes are [n] —
+ *
+ *     rec = what c2rt_trace_rays computes for (o, d)                      -- node := rec.closest_node
+ *     miss, or the scene's max_trace_depth == 0:
+ *            hits = 0, indirect = bounce = +0,+0,+0                       -- no sample is drawn
+ *            (max_trace_depth == 0: the spawned ray has depth 1 and trace() returns black before
+ *             intersecting anything, rt/renderer.d:330; node is still the record's)
+ *     hit:   N    = dot(d, rec.normal) < 0 ? rec.normal : -rec.normal     -- faceforward
+ *            from = rec.p + N * 1e-6
+ *            key  = rng_key(seed, idx, 0)
+ *            sum  = (+0f, +0f, +0f);  hits = 0
+ *            for s in 0 .. K-1:
+ *                res  = the occlusion planes' direction for (key, s, N)   -- same draws, same flip, same bits
+ *                cosw = (res.x*N.x + res.y*N.y) + res.z*N.z               -- fp64
+ *                w    = (float)(2.0 * cosw)                               -- brdfEval/pdf without the albedo:
+ *                                                                            ((1/PI) * cos) / (1/(2 PI))
+ *                (hit_s, L) = what c2rt_trace_rays reports for the ray (from, res), `dir` exactly as given:
+ *                             closest_node >= 0, and its rgb
+ *                if hit_s: hits |= 1 << s
+ *                sum.c = sum.c + L.c * w        for c in r, g, b           -- fp32 multiply, then fp32 add, not contracted
+ *            indirect.c = sum.c / (float)K
+ *            bounce.c   = albedo.c * indirect.c                            -- albedo: the shading planes' `albedo` for (o, d)
+ *
+ *   - Composition is the contract: the planes are, BIT FOR BIT, what a caller gets who takes the records from
+ *     c2rt_trace_rays, builds the K rays per hit as above, asks c2rt_trace_rays (records and rgb) for them, takes
+ *     `albedo` from c2rt_trace_rays_shading and does the fp32 sums.  The definition uses no libm call of its own.
+ *   - With the same seed the directions are those of the occlusion planes.  `res` is passed on un-normalised (it is of
+ *     unit length within 1 ulp), because that is what the composed call sees.
+ *   - The spawned rays are shaded with the full node mask and no ground shortcut, as every caller's ray is.
+ *   - What is written to a plane never depends on which others are asked for.  `node` alone traces no sample; `node` +
+ *     `hits` alone cast no shadow ray (the spawned rays' closest-hit search only); `indirect` without `bounce` fetches no
+ *     primary albedo.
+ *   - A lane of NaNs, zeros or 1e300 terminates (K bounded traces) and changes no other sample's result.
+ *   - Build-defined, where the reference is not reproducible: the draws, as for the lens and occlusion samples; the
+ *     rounding of `w` to fp32; that the path multiplier is applied at all (the reference's pathtrace(ray, multiplier)
+ *     drops its second argument); that the spawned ray's colour is raytrace's — direct light by shadow rays — rather
+ *     than a further bounce (with PointLight.solidAngle == 0, a black environment and lights that cannot be hit, every
+ *     further bounce of the reference is black).  gi_enabled stays refused.
+ *
+ * Statuses, all decided before anything is enqueued or written, each with its own message.  Camera calls: those of a
+ * frame call, in c2rt_render_hits' order; ray calls: those of c2rt_trace_rays, in its order (n == 0 is C2RT_OK whatever
+ * else is passed).  Then, for both: null `g`, samples == 0 or reserved != 0: C2RT_ERR_INVALID_ARG; samples >
+ * C2RT_MAX_GATHER_SAMPLES: C2RT_ERR_LIMIT; null `planes`, or all four pointers null: C2RT_ERR_INVALID_ARG.  Camera calls
+ * then: C2RT_ERR_UNSUPPORTED naming "depth of field", "stereo", "count_rays", "prepass_bucket".
+ *
+ * The _device variants take device pointers and enqueue ONE kernel on `hip_stream`: no host sync, no event, no scratch
+ * slot, nothing kept of the stream; on a multi-device context, the lead device; after c2rt_update_scene they see the
+ * posed scene.  The host variants go through the context's staging buffer on the context's own stream in chunks of whole
+ * rows (or rays) of at most 2^18 samples — at most 36 B per sample of planes — and block until the planes are there. */
+int c2rt_render_gather_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                              const c2rt_gather_opts *g, const c2rt_gather_planes *planes_dev, void *hip_stream);
+int c2rt_render_gather(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                       const c2rt_gather_opts *g, const c2rt_gather_planes *planes_host);
+int c2rt_trace_rays_gather_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n,
+                                  const c2rt_gather_opts *g, const c2rt_gather_planes *planes_dev, void *hip_stream);
+int c2rt_trace_rays_gather(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n,
+                           const c2rt_gather_opts *g, const c2rt_gather_planes *planes_host);
+
 /* ---- adaptive anti-aliasing: refine only the pixels the edge test flags ----- */
 
 /* tooDifferent's default threshold — rt/color.d:18 */

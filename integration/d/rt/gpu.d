@@ -203,6 +203,30 @@ extern (C) nothrow @nogc
                                          const c2rt_occlusion_planes* planes_dev, void* hip_stream);
     int c2rt_trace_rays_occlusion(c2rt_ctx*, const c2rt_ray* rays, ulong n, const c2rt_occlusion_opts*,
                                   const c2rt_occlusion_planes* planes_host);
+    /// gather planes: `samples` rays from p + N * 1e-6 over hemisphereSample(N) of the closest hit (the occlusion planes'
+    /// directions), each traced and shaded as c2rt_trace_rays does, weighted 2 cos and averaged (include/c2rt.h)
+    enum uint C2RT_MAX_GATHER_SAMPLES = 64;
+    struct c2rt_gather_opts
+    {
+        ulong seed;                 /// counter-RNG seed
+        uint samples;               /// K: 1 .. C2RT_MAX_GATHER_SAMPLES
+        uint reserved;              /// must be 0
+    }
+    struct c2rt_gather_planes
+    {
+        int* node;                  /// closest node, -1: no hit
+        ulong* hits;                /// bit s < K: sample s's ray hit a node
+        float* indirect;            /// [3] per sample: mean weighted colour arriving over the hemisphere
+        float* bounce;              /// [3] per sample: albedo * indirect, what to add to the frame's colour
+    }
+    int c2rt_render_gather_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_gather_opts*,
+                                  const c2rt_gather_planes* planes_dev, void* hip_stream);
+    int c2rt_render_gather(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_gather_opts*,
+                           const c2rt_gather_planes* planes_host);
+    int c2rt_trace_rays_gather_device(c2rt_ctx*, const c2rt_ray* rays_dev, ulong n, const c2rt_gather_opts*,
+                                      const c2rt_gather_planes* planes_dev, void* hip_stream);
+    int c2rt_trace_rays_gather(c2rt_ctx*, const c2rt_ray* rays, ulong n, const c2rt_gather_opts*,
+                               const c2rt_gather_planes* planes_host);
     enum float C2RT_AA_THRESHOLD_REF = 0.1f; /// tooDifferent's default
     int c2rt_render_frame_adaptive_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
                                           float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
