@@ -5,7 +5,8 @@ Thin wrappers over the C ABI (include/c2rt.h) and the C++ host mirror
 (rt/scene_loader.d:20-41), ``Scene.beginFrame`` (rt/scene.d:55-58),
 ``Renderer.renderRT`` / ``renderPixelNoAA`` (rt/renderer.d:83,223),
 ``renderPixel`` (rt/renderer.d:46-57).  Python holds no algorithm: all
-rendering happens in libc2rt.so on the GPU.
+rendering happens in libc2rt.so on the GPU.  The hit, shading, occlusion and
+gather planes are each described once (``_PlaneFamily``: struct, table, noun).
 """
 import ctypes as C
 
@@ -25,80 +26,61 @@ RAY_HIT_DTYPE = np.dtype({
 })
 
 
+class _PlaneFamily:
+    """One plane family, described once: the ctypes struct of its pointers, its table {plane name: (dtype, components
+    per sample)} in the order of the struct's members, and the noun its ValueError names it by."""
+
+    def __init__(self, struct, table, noun):
+        self.struct, self.table, self.noun = struct, table, noun
+
+    def _known(self, n):
+        if n not in self.table:
+            raise ValueError("unknown %s plane %r (one of %s)" % (self.noun, n, ", ".join(self.table)))
+
+    def new(self, names, shape):
+        """(struct of fresh host arrays, {name: array}) for the planes named, `shape` samples each; the others stay null"""
+        names = tuple(names)
+        for n in names:
+            self._known(n)
+        out, pl = {}, self.struct()
+        for n in names:
+            dtype, comps = self.table[n]
+            out[n] = np.empty(tuple(shape) if comps == 1 else tuple(shape) + (comps,), dtype=dtype)
+            setattr(pl, n, out[n].ctypes.data)
+        return pl, out
+
+    def device(self, ptrs):
+        """struct of the device pointers in `ptrs` ({plane name: pointer}); planes left out (or 0 / None) stay null"""
+        pl = self.struct()
+        for n, ptr in dict(ptrs).items():
+            self._known(n)
+            setattr(pl, n, ptr or None)
+        return pl
+
+
 # c2rt_hit_planes: plane name -> (dtype, components per pixel), in the order of the struct's members
 HIT_PLANES = {"node": (np.int32, 1), "leaf": (np.int32, 1), "dist": (np.float64, 1), "uv": (np.float64, 2),
               "p": (np.float64, 3), "normal": (np.float64, 3), "rgb": (np.float32, 3)}
-
-
-def _new_hit_planes(names, rows, width):
-    """(HitPlanes of fresh host arrays, {name: array}) for the planes named; the others stay null"""
-    names = tuple(names)
-    for n in names:
-        if n not in HIT_PLANES:
-            raise ValueError("unknown hit plane %r (one of %s)" % (n, ", ".join(HIT_PLANES)))
-    out, pl = {}, HitPlanes()
-    for n in names:
-        dtype, comps = HIT_PLANES[n]
-        out[n] = np.empty((rows, width) if comps == 1 else (rows, width, comps), dtype=dtype)
-        setattr(pl, n, out[n].ctypes.data)
-    return pl, out
-
-
 # c2rt_shade_planes: plane name -> (dtype, components per sample), in the order of the struct's members
 SHADE_PLANES = {"node": (np.int32, 1), "albedo": (np.float32, 3), "light": (np.float32, 3), "specular": (np.float32, 3),
                 "visible": (np.uint32, 1), "rgb": (np.float32, 3)}
-
-
-def _new_shade_planes(names, shape):
-    """(ShadePlanes of fresh host arrays, {name: array}) for the planes named, `shape` samples each; the others stay null"""
-    names = tuple(names)
-    for n in names:
-        if n not in SHADE_PLANES:
-            raise ValueError("unknown shading plane %r (one of %s)" % (n, ", ".join(SHADE_PLANES)))
-    out, pl = {}, ShadePlanes()
-    for n in names:
-        dtype, comps = SHADE_PLANES[n]
-        out[n] = np.empty(tuple(shape) if comps == 1 else tuple(shape) + (comps,), dtype=dtype)
-        setattr(pl, n, out[n].ctypes.data)
-    return pl, out
-
-
-def _device_shade_planes(ptrs):
-    """ShadePlanes of the device pointers in `ptrs` ({plane name: pointer}); planes left out (or 0 / None) stay null"""
-    pl = ShadePlanes()
-    for n, ptr in dict(ptrs).items():
-        if n not in SHADE_PLANES:
-            raise ValueError("unknown shading plane %r (one of %s)" % (n, ", ".join(SHADE_PLANES)))
-        setattr(pl, n, ptr or None)
-    return pl
-
-
 # c2rt_occlusion_planes: plane name -> (dtype, components per sample), in the order of the struct's members
 OCCLUSION_PLANES = {"node": (np.int32, 1), "open": (np.uint64, 1), "ao": (np.float32, 1), "bent": (np.float64, 3)}
+# c2rt_gather_planes: plane name -> (dtype, components per sample), in the order of the struct's members
+GATHER_PLANES = {"node": (np.int32, 1), "hits": (np.uint64, 1), "indirect": (np.float32, 3), "bounce": (np.float32, 3)}
+
+_HIT = _PlaneFamily(HitPlanes, HIT_PLANES, "hit")
+_SHADE = _PlaneFamily(ShadePlanes, SHADE_PLANES, "shading")
+_OCCLUSION = _PlaneFamily(OcclusionPlanes, OCCLUSION_PLANES, "occlusion")
+_GATHER = _PlaneFamily(GatherPlanes, GATHER_PLANES, "gather")
 
 
-def _new_occlusion_planes(names, shape):
-    """(OcclusionPlanes of fresh host arrays, {name: array}) for the planes named, `shape` samples each; the others stay null"""
-    names = tuple(names)
-    for n in names:
-        if n not in OCCLUSION_PLANES:
-            raise ValueError("unknown occlusion plane %r (one of %s)" % (n, ", ".join(OCCLUSION_PLANES)))
-    out, pl = {}, OcclusionPlanes()
-    for n in names:
-        dtype, comps = OCCLUSION_PLANES[n]
-        out[n] = np.empty(tuple(shape) if comps == 1 else tuple(shape) + (comps,), dtype=dtype)
-        setattr(pl, n, out[n].ctypes.data)
-    return pl, out
-
-
-def _device_occlusion_planes(ptrs):
-    """OcclusionPlanes of the device pointers in `ptrs` ({plane name: pointer}); planes left out (or 0 / None) stay null"""
-    pl = OcclusionPlanes()
-    for n, ptr in dict(ptrs).items():
-        if n not in OCCLUSION_PLANES:
-            raise ValueError("unknown occlusion plane %r (one of %s)" % (n, ", ".join(OCCLUSION_PLANES)))
-        setattr(pl, n, ptr or None)
-    return pl
+def _rays_array(rays, what="rays"):
+    """`rays` (c2rt_ray: origin, direction; c2rt_segment: from, to) as a contiguous (n, 6) float64 array"""
+    rays = np.ascontiguousarray(rays, dtype=np.float64)
+    if rays.ndim != 2 or rays.shape[1] != 6:
+        raise ValueError("%s: expected shape (n, 6), got %r" % (what, rays.shape))
+    return rays
 
 
 def _occlusion_opts(samples, radius, seed):
@@ -129,34 +111,6 @@ def _tap_table(taps):
         t.offset[s][0] = dx
         t.offset[s][1] = dy
     return t
-
-
-# c2rt_gather_planes: plane name -> (dtype, components per sample), in the order of the struct's members
-GATHER_PLANES = {"node": (np.int32, 1), "hits": (np.uint64, 1), "indirect": (np.float32, 3), "bounce": (np.float32, 3)}
-
-
-def _new_gather_planes(names, shape):
-    """(GatherPlanes of fresh host arrays, {name: array}) for the planes named, `shape` samples each; the others stay null"""
-    names = tuple(names)
-    for n in names:
-        if n not in GATHER_PLANES:
-            raise ValueError("unknown gather plane %r (one of %s)" % (n, ", ".join(GATHER_PLANES)))
-    out, pl = {}, GatherPlanes()
-    for n in names:
-        dtype, comps = GATHER_PLANES[n]
-        out[n] = np.empty(tuple(shape) if comps == 1 else tuple(shape) + (comps,), dtype=dtype)
-        setattr(pl, n, out[n].ctypes.data)
-    return pl, out
-
-
-def _device_gather_planes(ptrs):
-    """GatherPlanes of the device pointers in `ptrs` ({plane name: pointer}); planes left out (or 0 / None) stay null"""
-    pl = GatherPlanes()
-    for n, ptr in dict(ptrs).items():
-        if n not in GATHER_PLANES:
-            raise ValueError("unknown gather plane %r (one of %s)" % (n, ", ".join(GATHER_PLANES)))
-        setattr(pl, n, ptr or None)
-    return pl
 
 
 def _gather_opts(samples, seed):
@@ -426,15 +380,20 @@ class Context:
         poses = [p if isinstance(p, ScenePose) else makePose(*p) for p in poses]
         return (ScenePose * max(len(poses), 1))(*poses), len(poses), poses
 
+    def _posed_arrays(self, cams, poses):
+        """(camera array, pose array, count, what keeps the poses' arrays alive) of a posed batch: n cameras, n poses"""
+        arr, n = self._camera_array(cams)
+        parr, np_, keep = self._pose_array(poses)
+        if np_ != n:
+            raise ValueError("%d cameras, %d poses" % (n, np_))
+        return arr, parr, n, keep
+
     def renderFramesPosed(self, cams, poses, opts, stop_flag=None):
         """An animation in one call (c2rt_render_frames_posed): frame i is the current scene with poses[i] applied — a
         ScenePose or a (nodes, lights) pair as for updateScene, each relative to the current scene — seen through
         cams[i]: the bits of updateScene(poses[i]) + renderFrame(cams[i]).  The context's scene is unchanged.  A new
         host array of shape (len(cams), local_rows, W, 3)."""
-        arr, n = self._camera_array(cams)
-        parr, np_, keep = self._pose_array(poses)
-        if np_ != n:
-            raise ValueError("%d cameras, %d poses" % (n, np_))
+        arr, parr, n, keep = self._posed_arrays(cams, poses)
         out = np.empty((n, self.localRows(opts), opts.width, 3), dtype=np.float32)
         stop = stop_flag.ctypes.data_as(C.c_void_p) if stop_flag is not None else None
         self._check(self._lib.c2rt_render_frames_posed(self._h, arr, parr, n, C.byref(opts), out.ctypes.data_as(C.c_void_p), stop))
@@ -442,10 +401,7 @@ class Context:
 
     def renderFramesPosedDevice(self, cams, poses, opts, out_ptr, stream=0):
         """Enqueue the posed batch into device memory (len(cams) * local_rows * W * 3 floats at out_ptr) on `stream`."""
-        arr, n = self._camera_array(cams)
-        parr, np_, keep = self._pose_array(poses)
-        if np_ != n:
-            raise ValueError("%d cameras, %d poses" % (n, np_))
+        arr, parr, n, keep = self._posed_arrays(cams, poses)
         self._check(self._lib.c2rt_render_frames_posed_device(self._h, arr, parr, n, C.byref(opts), C.c_void_p(out_ptr), C.c_void_p(stream)))
 
     def localRows(self, opts):
@@ -571,10 +527,7 @@ class Context:
         """An anti-aliased animation in one call (c2rt_render_frames_posed_adaptive): renderFramesAdaptive with poses[i]
         — given as renderFramesPosed takes them, each relative to the current scene — applied to frame i.  The
         context's scene is unchanged."""
-        arr, n = self._camera_array(cams)
-        parr, np_, keep = self._pose_array(poses)
-        if np_ != n:
-            raise ValueError("%d cameras, %d poses" % (n, np_))
+        arr, parr, n, keep = self._posed_arrays(cams, poses)
         frames = np.empty((n, opts.height, opts.width, 3), dtype=np.float32)
         masks = np.empty((n, opts.height, opts.width), dtype=np.uint8)
         stop = stop_flag.ctypes.data_as(C.c_void_p) if stop_flag is not None else None
@@ -584,10 +537,7 @@ class Context:
 
     def renderFramesPosedAdaptiveDevice(self, cams, poses, opts, out_ptr, mask_ptr, threshold=_abi.AA_THRESHOLD_REF, stream=0):
         """Enqueue the posed adaptive batch on `stream` into device memory, laid out as for renderFramesAdaptiveDevice."""
-        arr, n = self._camera_array(cams)
-        parr, np_, keep = self._pose_array(poses)
-        if np_ != n:
-            raise ValueError("%d cameras, %d poses" % (n, np_))
+        arr, parr, n, keep = self._posed_arrays(cams, poses)
         self._check(self._lib.c2rt_render_frames_posed_adaptive_device(self._h, arr, parr, n, C.byref(opts), float(threshold),
                                                                        C.c_void_p(out_ptr or None), C.c_void_p(mask_ptr or None), C.c_void_p(stream)))
 
@@ -629,9 +579,7 @@ class Context:
         """Closest hit and colour of caller-supplied rays (c2rt_trace_rays): `rays` is (n, 6) float64 — origin, then the
         direction, used exactly as given.  Returns (records, rgb): a structured array of RAY_HIT_DTYPE (c2rt_ray_hit)
         and an (n, 3) float32 array; the one switched off is None (colors=False casts no shadow ray)."""
-        rays = np.ascontiguousarray(rays, dtype=np.float64)
-        if rays.ndim != 2 or rays.shape[1] != 6:
-            raise ValueError("rays: expected shape (n, 6), got %r" % (rays.shape,))
+        rays = _rays_array(rays)
         n = rays.shape[0]
         rec = np.empty(n, dtype=RAY_HIT_DTYPE) if hits else None
         rgb = np.empty((n, 3), dtype=np.float32) if colors else None
@@ -651,9 +599,7 @@ class Context:
         (records, rgb, count): records (max_layers, n) of RAY_HIT_DTYPE and rgb (max_layers, n, 3) float32, layer k of ray
         i at [k, i] — the one switched off is None — and count (n,) uint8, the number of hits stored.  Slot [k, i] means
         something for k <= count[i] only (the miss that ended the walk is stored; what lies behind it is unspecified)."""
-        rays = np.ascontiguousarray(rays, dtype=np.float64)
-        if rays.ndim != 2 or rays.shape[1] != 6:
-            raise ValueError("rays: expected shape (n, 6), got %r" % (rays.shape,))
+        rays = _rays_array(rays)
         n, K = rays.shape[0], int(max_layers)
         rec = np.zeros((max(K, 0), n), dtype=RAY_HIT_DTYPE) if hits else None
         rgb = np.zeros((max(K, 0), n, 3), dtype=np.float32) if colors else None
@@ -677,7 +623,7 @@ class Context:
         along the pixel's ray, layer 0 what renderHits returns — plus "count" (local_rows, W) uint8.  A pixel's layer k
         means something for k <= count only.  Refuses what renderHits refuses."""
         K, rows = int(max_layers), self.localRows(opts)
-        pl, out = _new_hit_planes(planes, max(K, 0) * rows, opts.width)
+        pl, out = _HIT.new(planes, (max(K, 0) * rows, opts.width))
         count = np.zeros((rows, opts.width), dtype=np.uint8)
         self._check(self._lib.c2rt_render_hit_layers(self._h, C.byref(cam), C.byref(opts), K, C.byref(pl), count.ctypes.data_as(C.c_void_p)))
         out = {k: v.reshape((K, rows) + v.shape[1:]) for k, v in out.items()}
@@ -688,7 +634,7 @@ class Context:
         """Enqueue the hit layers on `stream` into device memory: `ptrs` maps plane names (HIT_PLANES) to device pointers
         of max_layers * local_rows * W * components elements, layer after layer without padding; count_ptr: local_rows * W
         bytes.  Planes left out (or 0 / None) are not written; slots behind a pixel's final miss are not touched."""
-        pl = self._device_hit_planes(ptrs)
+        pl = _HIT.device(ptrs)
         self._check(self._lib.c2rt_render_hit_layers_device(self._h, C.byref(cam), C.byref(opts), int(max_layers), C.byref(pl),
                                                             C.c_void_p(count_ptr or None), C.c_void_p(stream)))
 
@@ -697,29 +643,15 @@ class Context:
         leaf (int32) and dist (float64) of shape (local_rows, W), uv (local_rows, W, 2), p and normal (local_rows, W, 3)
         float64, rgb (local_rows, W, 3) float32: renderPixel(x, y)'s record at [y, x].  Planes not named are neither
         computed nor stored.  No depth of field, stereo, count_rays or prepass_bucket (C2rtError, ERR_UNSUPPORTED)."""
-        pl, out = _new_hit_planes(planes, self.localRows(opts), opts.width)
+        pl, out = _HIT.new(planes, (self.localRows(opts), opts.width))
         self._check(self._lib.c2rt_render_hits(self._h, C.byref(cam), C.byref(opts), C.byref(pl)))
         return out
 
     def renderHitsDevice(self, cam, opts, ptrs, stream=0):
         """Enqueue the hit planes on `stream` into device memory: `ptrs` maps plane names (HIT_PLANES) to device
         pointers of local_rows * W * components elements; planes left out (or 0 / None) are not written."""
-        pl = HitPlanes()
-        for n, ptr in dict(ptrs).items():
-            if n not in HIT_PLANES:
-                raise ValueError("unknown hit plane %r (one of %s)" % (n, ", ".join(HIT_PLANES)))
-            setattr(pl, n, ptr or None)
+        pl = _HIT.device(ptrs)
         self._check(self._lib.c2rt_render_hits_device(self._h, C.byref(cam), C.byref(opts), C.byref(pl), C.c_void_p(stream)))
-
-    @staticmethod
-    def _device_hit_planes(ptrs):
-        """HitPlanes of the device pointers in `ptrs` ({plane name: pointer}); planes left out (or 0 / None) stay null"""
-        pl = HitPlanes()
-        for n, ptr in dict(ptrs).items():
-            if n not in HIT_PLANES:
-                raise ValueError("unknown hit plane %r (one of %s)" % (n, ", ".join(HIT_PLANES)))
-            setattr(pl, n, ptr or None)
-        return pl
 
     def renderFramesHits(self, cams, opts, planes=("node", "leaf", "dist", "uv", "p", "normal", "rgb")):
         """The hit planes of a batch of cameras in one call (c2rt_render_frames_hits): a dict of numpy arrays for the
@@ -727,7 +659,7 @@ class Context:
         bits renderHits(cams[i], opts, planes) returns.  What a batch refuses, this refuses (C2rtError)."""
         arr, n = self._camera_array(cams)
         rows = self.localRows(opts)
-        pl, out = _new_hit_planes(planes, n * rows, opts.width)
+        pl, out = _HIT.new(planes, (n * rows, opts.width))
         self._check(self._lib.c2rt_render_frames_hits(self._h, arr, n, C.byref(opts), C.byref(pl)))
         return {k: v.reshape((n, rows) + v.shape[1:]) for k, v in out.items()}
 
@@ -736,29 +668,23 @@ class Context:
         names (HIT_PLANES) to device pointers of len(cams) * local_rows * W * components elements, frame after frame
         without padding; planes left out (or 0 / None) are not written."""
         arr, n = self._camera_array(cams)
-        pl = self._device_hit_planes(ptrs)
+        pl = _HIT.device(ptrs)
         self._check(self._lib.c2rt_render_frames_hits_device(self._h, arr, n, C.byref(opts), C.byref(pl), C.c_void_p(stream)))
 
     def renderFramesPosedHits(self, cams, poses, opts, planes=("node", "leaf", "dist", "uv", "p", "normal", "rgb")):
         """The hit planes of a posed animation in one call (c2rt_render_frames_posed_hits): renderFramesHits with
         poses[i] — given as renderFramesPosed takes them, each relative to the current scene — applied to frame i: the
         bits of updateScene(poses[i]) + renderHits(cams[i]).  The context's scene is unchanged."""
-        arr, n = self._camera_array(cams)
-        parr, np_, keep = self._pose_array(poses)
-        if np_ != n:
-            raise ValueError("%d cameras, %d poses" % (n, np_))
+        arr, parr, n, keep = self._posed_arrays(cams, poses)
         rows = self.localRows(opts)
-        pl, out = _new_hit_planes(planes, n * rows, opts.width)
+        pl, out = _HIT.new(planes, (n * rows, opts.width))
         self._check(self._lib.c2rt_render_frames_posed_hits(self._h, arr, parr, n, C.byref(opts), C.byref(pl)))
         return {k: v.reshape((n, rows) + v.shape[1:]) for k, v in out.items()}
 
     def renderFramesPosedHitsDevice(self, cams, poses, opts, ptrs, stream=0):
         """Enqueue the posed batch's hit planes on `stream` into device memory, laid out as for renderFramesHitsDevice."""
-        arr, n = self._camera_array(cams)
-        parr, np_, keep = self._pose_array(poses)
-        if np_ != n:
-            raise ValueError("%d cameras, %d poses" % (n, np_))
-        pl = self._device_hit_planes(ptrs)
+        arr, parr, n, keep = self._posed_arrays(cams, poses)
+        pl = _HIT.device(ptrs)
         self._check(self._lib.c2rt_render_frames_posed_hits_device(self._h, arr, parr, n, C.byref(opts), C.byref(pl), C.c_void_p(stream)))
 
     def renderShading(self, cam, opts, planes=tuple(SHADE_PLANES)):
@@ -767,30 +693,28 @@ class Context:
         specular and rgb (local_rows, W, 3) float32.  On a hit rgb == albedo * light (+ specular for a Phong node) bit for
         bit, and rgb and node are renderHits'.  Planes not named are neither computed nor stored; node and albedo alone
         cast no shadow ray.  Refuses what renderHits refuses."""
-        pl, out = _new_shade_planes(planes, (self.localRows(opts), opts.width))
+        pl, out = _SHADE.new(planes, (self.localRows(opts), opts.width))
         self._check(self._lib.c2rt_render_shading(self._h, C.byref(cam), C.byref(opts), C.byref(pl)))
         return out
 
     def renderShadingDevice(self, cam, opts, ptrs, stream=0):
         """Enqueue the shading planes on `stream` into device memory: `ptrs` maps plane names (SHADE_PLANES) to device
         pointers of local_rows * W * components elements; planes left out (or 0 / None) are not written."""
-        pl = _device_shade_planes(ptrs)
+        pl = _SHADE.device(ptrs)
         self._check(self._lib.c2rt_render_shading_device(self._h, C.byref(cam), C.byref(opts), C.byref(pl), C.c_void_p(stream)))
 
     def traceRaysShading(self, rays, planes=tuple(SHADE_PLANES)):
         """The same terms for caller-supplied rays (c2rt_trace_rays_shading): `rays` as for traceRays; a dict of arrays of
         shape (n,) or (n, 3).  rgb and node are traceRays'."""
-        rays = np.ascontiguousarray(rays, dtype=np.float64)
-        if rays.ndim != 2 or rays.shape[1] != 6:
-            raise ValueError("rays: expected shape (n, 6), got %r" % (rays.shape,))
-        pl, out = _new_shade_planes(planes, (rays.shape[0],))
+        rays = _rays_array(rays)
+        pl, out = _SHADE.new(planes, (rays.shape[0],))
         self._check(self._lib.c2rt_trace_rays_shading(self._h, rays.ctypes.data_as(C.c_void_p), rays.shape[0], C.byref(pl)))
         return out
 
     def traceRaysShadingDevice(self, rays_ptr, n, ptrs, stream=0):
         """Enqueue the query on `stream` over device memory: n c2rt_ray at rays_ptr, `ptrs` as for renderShadingDevice
         with n samples per plane."""
-        pl = _device_shade_planes(ptrs)
+        pl = _SHADE.device(ptrs)
         self._check(self._lib.c2rt_trace_rays_shading_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(pl), C.c_void_p(stream)))
 
     def renderOcclusion(self, cam, opts, samples, radius, seed=0, planes=tuple(OCCLUSION_PLANES)):
@@ -801,7 +725,7 @@ class Context:
         miss holds -1, the low `samples` bits, 1.0 and zeros.  node alone traces no sample.  Refuses what renderHits
         refuses."""
         occ = _occlusion_opts(samples, radius, seed)
-        pl, out = _new_occlusion_planes(planes, (self.localRows(opts), opts.width))
+        pl, out = _OCCLUSION.new(planes, (self.localRows(opts), opts.width))
         self._check(self._lib.c2rt_render_occlusion(self._h, C.byref(cam), C.byref(opts), C.byref(occ), C.byref(pl)))
         return out
 
@@ -809,17 +733,15 @@ class Context:
         """Enqueue the occlusion planes on `stream` into device memory: `ptrs` maps plane names (OCCLUSION_PLANES) to
         device pointers of local_rows * W * components elements; planes left out (or 0 / None) are not written."""
         occ = _occlusion_opts(samples, radius, seed)
-        pl = _device_occlusion_planes(ptrs)
+        pl = _OCCLUSION.device(ptrs)
         self._check(self._lib.c2rt_render_occlusion_device(self._h, C.byref(cam), C.byref(opts), C.byref(occ), C.byref(pl), C.c_void_p(stream)))
 
     def traceRaysOcclusion(self, rays, samples, radius, seed=0, planes=tuple(OCCLUSION_PLANES)):
         """The same planes for caller-supplied rays (c2rt_trace_rays_occlusion): `rays` as for traceRays; a dict of arrays
         of shape (n,) or (n, 3).  Ray i draws the samples of index i; node is traceRays'."""
-        rays = np.ascontiguousarray(rays, dtype=np.float64)
-        if rays.ndim != 2 or rays.shape[1] != 6:
-            raise ValueError("rays: expected shape (n, 6), got %r" % (rays.shape,))
+        rays = _rays_array(rays)
         occ = _occlusion_opts(samples, radius, seed)
-        pl, out = _new_occlusion_planes(planes, (rays.shape[0],))
+        pl, out = _OCCLUSION.new(planes, (rays.shape[0],))
         self._check(self._lib.c2rt_trace_rays_occlusion(self._h, rays.ctypes.data_as(C.c_void_p), rays.shape[0], C.byref(occ), C.byref(pl)))
         return out
 
@@ -827,7 +749,7 @@ class Context:
         """Enqueue the query on `stream` over device memory: n c2rt_ray at rays_ptr, `ptrs` as for renderOcclusionDevice
         with n samples per plane."""
         occ = _occlusion_opts(samples, radius, seed)
-        pl = _device_occlusion_planes(ptrs)
+        pl = _OCCLUSION.device(ptrs)
         self._check(self._lib.c2rt_trace_rays_occlusion_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(occ), C.byref(pl),
                                                                C.c_void_p(stream)))
 
@@ -839,7 +761,7 @@ class Context:
         albedo — what to add to the frame's colour.  A miss holds -1, 0 and zeros.  node alone traces no sample.
         Refuses what renderHits refuses."""
         g = _gather_opts(samples, seed)
-        pl, out = _new_gather_planes(planes, (self.localRows(opts), opts.width))
+        pl, out = _GATHER.new(planes, (self.localRows(opts), opts.width))
         self._check(self._lib.c2rt_render_gather(self._h, C.byref(cam), C.byref(opts), C.byref(g), C.byref(pl)))
         return out
 
@@ -847,17 +769,15 @@ class Context:
         """Enqueue the gather planes on `stream` into device memory: `ptrs` maps plane names (GATHER_PLANES) to device
         pointers of local_rows * W * components elements; planes left out (or 0 / None) are not written."""
         g = _gather_opts(samples, seed)
-        pl = _device_gather_planes(ptrs)
+        pl = _GATHER.device(ptrs)
         self._check(self._lib.c2rt_render_gather_device(self._h, C.byref(cam), C.byref(opts), C.byref(g), C.byref(pl), C.c_void_p(stream)))
 
     def traceRaysGather(self, rays, samples, seed=0, planes=tuple(GATHER_PLANES)):
         """The same planes for caller-supplied rays (c2rt_trace_rays_gather): `rays` as for traceRays; a dict of arrays of
         shape (n,) or (n, 3).  Ray i draws the samples of index i; node is traceRays'."""
-        rays = np.ascontiguousarray(rays, dtype=np.float64)
-        if rays.ndim != 2 or rays.shape[1] != 6:
-            raise ValueError("rays: expected shape (n, 6), got %r" % (rays.shape,))
+        rays = _rays_array(rays)
         g = _gather_opts(samples, seed)
-        pl, out = _new_gather_planes(planes, (rays.shape[0],))
+        pl, out = _GATHER.new(planes, (rays.shape[0],))
         self._check(self._lib.c2rt_trace_rays_gather(self._h, rays.ctypes.data_as(C.c_void_p), rays.shape[0], C.byref(g), C.byref(pl)))
         return out
 
@@ -865,14 +785,12 @@ class Context:
         """Enqueue the query on `stream` over device memory: n c2rt_ray at rays_ptr, `ptrs` as for renderGatherDevice with
         n samples per plane."""
         g = _gather_opts(samples, seed)
-        pl = _device_gather_planes(ptrs)
+        pl = _GATHER.device(ptrs)
         self._check(self._lib.c2rt_trace_rays_gather_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(g), C.byref(pl), C.c_void_p(stream)))
 
     def testVisibility(self, segments):
         """Scene.testVisibility for (n, 6) float64 segments (from, to): (n,) uint8, 1 = nothing in between."""
-        seg = np.ascontiguousarray(segments, dtype=np.float64)
-        if seg.ndim != 2 or seg.shape[1] != 6:
-            raise ValueError("segments: expected shape (n, 6), got %r" % (seg.shape,))
+        seg = _rays_array(segments, "segments")
         vis = np.empty(seg.shape[0], dtype=np.uint8)
         self._check(self._lib.c2rt_test_visibility(self._h, seg.ctypes.data_as(C.c_void_p), seg.shape[0], vis.ctypes.data_as(C.c_void_p)))
         return vis
@@ -968,14 +886,14 @@ class Renderer:
         """Context.renderHits for the scene's own camera and frame size (c2rt_host_render_hits); a camera with depth
         of field or stereo is refused (C2rtError, ERR_UNSUPPORTED)."""
         s = self.scene.settings
-        pl, out = _new_hit_planes(planes, s.frame_height, s.frame_width)
+        pl, out = _HIT.new(planes, (s.frame_height, s.frame_width))
         self.ctx._check(self._lib.c2rt_host_render_hits(self.ctx.handle, self.scene._h, C.byref(pl)))
         return out
 
     def renderHitLayers(self, max_layers, planes=("node", "leaf", "dist", "uv", "p", "normal", "rgb")):
         """Context.renderHitLayers for the scene's own camera and frame size (c2rt_host_render_hit_layers)."""
         s, K = self.scene.settings, int(max_layers)
-        pl, out = _new_hit_planes(planes, max(K, 0) * s.frame_height, s.frame_width)
+        pl, out = _HIT.new(planes, (max(K, 0) * s.frame_height, s.frame_width))
         count = np.zeros((s.frame_height, s.frame_width), dtype=np.uint8)
         self.ctx._check(self._lib.c2rt_host_render_hit_layers(self.ctx.handle, self.scene._h, K, C.byref(pl), count.ctypes.data_as(C.c_void_p)))
         out = {k: v.reshape((K, s.frame_height) + v.shape[1:]) for k, v in out.items()}
@@ -985,7 +903,7 @@ class Renderer:
     def renderShading(self, planes=tuple(SHADE_PLANES)):
         """Context.renderShading for the scene's own camera and frame size (c2rt_host_render_shading)."""
         s = self.scene.settings
-        pl, out = _new_shade_planes(planes, (s.frame_height, s.frame_width))
+        pl, out = _SHADE.new(planes, (s.frame_height, s.frame_width))
         self.ctx._check(self._lib.c2rt_host_render_shading(self.ctx.handle, self.scene._h, C.byref(pl)))
         return out
 
@@ -993,7 +911,7 @@ class Renderer:
         """Context.renderOcclusion for the scene's own camera and frame size (c2rt_host_render_occlusion)."""
         s = self.scene.settings
         occ = _occlusion_opts(samples, radius, seed)
-        pl, out = _new_occlusion_planes(planes, (s.frame_height, s.frame_width))
+        pl, out = _OCCLUSION.new(planes, (s.frame_height, s.frame_width))
         self.ctx._check(self._lib.c2rt_host_render_occlusion(self.ctx.handle, self.scene._h, C.byref(occ), C.byref(pl)))
         return out
 
@@ -1001,7 +919,7 @@ class Renderer:
         """Context.renderGather for the scene's own camera and frame size (c2rt_host_render_gather)."""
         s = self.scene.settings
         g = _gather_opts(samples, seed)
-        pl, out = _new_gather_planes(planes, (s.frame_height, s.frame_width))
+        pl, out = _GATHER.new(planes, (s.frame_height, s.frame_width))
         self.ctx._check(self._lib.c2rt_host_render_gather(self.ctx.handle, self.scene._h, C.byref(g), C.byref(pl)))
         return out
 

@@ -1,7 +1,11 @@
 /*
  * c2rt_api.cpp — implementation of the C ABI in include/c2rt.h: context,
  * upload of a planned scene (scene_plan.h: SoA tables -> scalar-loadable records in HBM),
- * frame / pixel-probe launches, strip de-interleave and display encode.
+ * frame / pixel-probe launches, the ray and plane queries, strip de-interleave and display encode.
+ *
+ * The hit, shading, occlusion and gather planes are one code path: each family is described once (Family<S>: sample
+ * sizes, the words of its messages, its options and their refusals) and its entry points are one-line calls of the
+ * four faces frame_planes_device / frame_planes_host / ray_planes_device / ray_planes_host.
  *
  * There is no CPU fallback anywhere in this file: without a usable HIP
  * device every entry point fails with C2RT_ERR_NO_DEVICE / C2RT_ERR_HIP.
@@ -1265,78 +1269,38 @@ int c2rt_get_ray_stats(c2rt_ctx *ctx, c2rt_ray_stats *out)
     return C2RT_OK;
 }
 
-int c2rt_get_csg_truncations(c2rt_ctx *ctx, uint64_t *out)
+/* One counter of the context, summed over its device slots.  counted: the counter is the ray counts' (only a counting
+ * render leaves it valid, and a counted device-output frame may still be running: drain it, then each peer's stream);
+ * otherwise every render writes it, on whatever stream: wait for the devices. */
+static int get_counter(c2rt_ctx *ctx, int index, bool counted, uint64_t *out)
 {
     if (!ctx || !out) return C2RT_ERR_INVALID_ARG;
-    if (!ctx->counters_valid) return fail(ctx, C2RT_ERR_INVALID_ARG, "last render did not count rays");
+    if (counted && !ctx->counters_valid) return fail(ctx, C2RT_ERR_INVALID_ARG, "last render did not count rays");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (const int st = drain_inflight(ctx)) return st;
+    if (counted) {
+        if (const int st = drain_inflight(ctx)) return st;
+    } else
+        HIP_TRY(ctx, hipDeviceSynchronize());
     unsigned long long h = 0;
-    HIP_TRY(ctx, hipMemcpy(&h, ctx->counters + 2, sizeof h, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(&h, ctx->counters + index, sizeof h, hipMemcpyDeviceToHost));
     *out = h;
     for (c2rt_ctx *c : ctx->peers) {
         HIP_TRY(ctx, hipSetDevice(c->device));
-        HIP_TRY(ctx, hipStreamSynchronize(c->stream));
-        HIP_TRY(ctx, hipMemcpy(&h, c->counters + 2, sizeof h, hipMemcpyDeviceToHost));
+        if (counted)
+            HIP_TRY(ctx, hipStreamSynchronize(c->stream));
+        else
+            HIP_TRY(ctx, hipDeviceSynchronize());
+        HIP_TRY(ctx, hipMemcpy(&h, c->counters + index, sizeof h, hipMemcpyDeviceToHost));
         *out += h;
     }
     if (!ctx->peers.empty()) HIP_TRY(ctx, hipSetDevice(ctx->device));
     return C2RT_OK;
 }
 
-int c2rt_get_exact_redos(c2rt_ctx *ctx, uint64_t *out)
-{
-    if (!ctx || !out) return C2RT_ERR_INVALID_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    unsigned long long h = 0;
-    HIP_TRY(ctx, hipMemcpy(&h, ctx->counters + 3, sizeof h, hipMemcpyDeviceToHost));
-    *out = h;
-    for (c2rt_ctx *c : ctx->peers) {
-        HIP_TRY(ctx, hipSetDevice(c->device));
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        HIP_TRY(ctx, hipMemcpy(&h, c->counters + 3, sizeof h, hipMemcpyDeviceToHost));
-        *out += h;
-    }
-    if (!ctx->peers.empty()) HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return C2RT_OK;
-}
-
-int c2rt_get_ground_bails(c2rt_ctx *ctx, uint64_t *out)
-{
-    if (!ctx || !out) return C2RT_ERR_INVALID_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    unsigned long long h = 0;
-    HIP_TRY(ctx, hipMemcpy(&h, ctx->counters + 4, sizeof h, hipMemcpyDeviceToHost));
-    *out = h;
-    for (c2rt_ctx *c : ctx->peers) {
-        HIP_TRY(ctx, hipSetDevice(c->device));
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        HIP_TRY(ctx, hipMemcpy(&h, c->counters + 4, sizeof h, hipMemcpyDeviceToHost));
-        *out += h;
-    }
-    if (!ctx->peers.empty()) HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return C2RT_OK;
-}
-
-int c2rt_get_sphere_bails(c2rt_ctx *ctx, uint64_t *out)
-{
-    if (!ctx || !out) return C2RT_ERR_INVALID_ARG;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    unsigned long long h = 0;
-    HIP_TRY(ctx, hipMemcpy(&h, ctx->counters + 5, sizeof h, hipMemcpyDeviceToHost));
-    *out = h;
-    for (c2rt_ctx *c : ctx->peers) {
-        HIP_TRY(ctx, hipSetDevice(c->device));
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        HIP_TRY(ctx, hipMemcpy(&h, c->counters + 5, sizeof h, hipMemcpyDeviceToHost));
-        *out += h;
-    }
-    if (!ctx->peers.empty()) HIP_TRY(ctx, hipSetDevice(ctx->device));
-    return C2RT_OK;
-}
+int c2rt_get_csg_truncations(c2rt_ctx *ctx, uint64_t *out) { return get_counter(ctx, 2, true, out); }
+int c2rt_get_exact_redos(c2rt_ctx *ctx, uint64_t *out) { return get_counter(ctx, 3, false, out); }
+int c2rt_get_ground_bails(c2rt_ctx *ctx, uint64_t *out) { return get_counter(ctx, 4, false, out); }
+int c2rt_get_sphere_bails(c2rt_ctx *ctx, uint64_t *out) { return get_counter(ctx, 5, false, out); }
 
 int c2rt_render_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, int x, int y,
                       c2rt_trace_result *out)
@@ -1433,17 +1397,60 @@ static size_t align256(size_t b) { return (b + 255u) & ~(size_t)255u; }
 
 extern "C++" { /* templates */
 
-/* A plane struct as the host code sees it: nothing but pointers, member k to samples of v[k] bytes */
-template <class S> struct PlaneBytes;
-template <> struct PlaneBytes<c2rt_hit_planes> { static constexpr size_t v[] = {4, 4, 8, 16, 24, 24, 12}; };  /* 92 B per sample */
-template <> struct PlaneBytes<c2rt_shade_planes> { static constexpr size_t v[] = {4, 12, 12, 12, 4, 12}; };   /* 56 B per sample */
-template <> struct PlaneBytes<c2rt_occlusion_planes> { static constexpr size_t v[] = {4, 8, 4, 24}; };        /* 40 B per sample */
-template <> struct PlaneBytes<c2rt_gather_planes> { static constexpr size_t v[] = {4, 8, 12, 12}; };          /* 36 B per sample */
-template <class S> constexpr int kPlanes = (int)(sizeof PlaneBytes<S>::v / sizeof(size_t));
-static_assert(sizeof(c2rt_hit_planes) == kPlanes<c2rt_hit_planes> * sizeof(void *) &&
-              sizeof(c2rt_shade_planes) == kPlanes<c2rt_shade_planes> * sizeof(void *) &&
-              sizeof(c2rt_occlusion_planes) == kPlanes<c2rt_occlusion_planes> * sizeof(void *) &&
-              sizeof(c2rt_gather_planes) == kPlanes<c2rt_gather_planes> * sizeof(void *), "the plane structs are arrays of pointers");
+/* A plane family, described once; the generic faces under "plane families" below are written against it.  bytes: the
+ * struct as the host code sees it, member k a pointer to samples of bytes[k] bytes (kPlanes<S> of them, c2rt_query.h).
+ * The words its messages are built from: which planes ("the %s planes"), what a pixel holds ("a pixel's %s one
+ * ray's"), how many pointers of which struct, the kernel of the launch error.  Opts and check_opts: the options in front
+ * of the planes and their refusals, in the documented order (NoOpts: none).  The launches are the overloads
+ * launch_plane_rows / launch_plane_rays of c2rt_query.h on S. */
+template <class S> struct Family;
+template <> struct Family<c2rt_hit_planes> {
+    static constexpr size_t bytes[] = {4, 4, 8, 16, 24, 24, 12}; /* 92 B per sample */
+    static constexpr const char *planes = "hit", *holds = "record is", *count = "seven", *name = "c2rt_hit_planes", *what = "hit plane";
+    using Opts = NoOpts;
+    static int check_opts(c2rt_ctx *, const Opts *) { return C2RT_OK; }
+};
+template <> struct Family<c2rt_shade_planes> {
+    static constexpr size_t bytes[] = {4, 12, 12, 12, 4, 12}; /* 56 B per sample */
+    static constexpr const char *planes = "shading", *holds = "terms are", *count = "six", *name = "c2rt_shade_planes", *what = "shading plane";
+    using Opts = NoOpts;
+    static int check_opts(c2rt_ctx *, const Opts *) { return C2RT_OK; }
+};
+template <> struct Family<c2rt_occlusion_planes> {
+    static constexpr size_t bytes[] = {4, 8, 4, 24}; /* 40 B per sample */
+    static constexpr const char *planes = "occlusion", *holds = "occlusion is", *count = "four", *name = "c2rt_occlusion_planes", *what = "occlusion plane";
+    using Opts = c2rt_occlusion_opts;
+    static int check_opts(c2rt_ctx *ctx, const Opts *occ)
+    {
+        if (!occ) return fail(ctx, C2RT_ERR_INVALID_ARG, "null occlusion options");
+        if (!(occ->radius > 0) || !std::isfinite(occ->radius))
+            return fail(ctx, C2RT_ERR_INVALID_ARG, "occlusion radius %g: a finite length above 0", occ->radius);
+        if (occ->samples == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "occlusion samples is 0: at least one sample");
+        if (occ->reserved != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "c2rt_occlusion_opts.reserved is %u: must be 0", (unsigned)occ->reserved);
+        if (occ->samples > C2RT_MAX_OCCLUSION_SAMPLES)
+            return fail(ctx, C2RT_ERR_LIMIT, "%u occlusion samples (at most %u)", (unsigned)occ->samples, (unsigned)C2RT_MAX_OCCLUSION_SAMPLES);
+        return C2RT_OK;
+    }
+};
+template <> struct Family<c2rt_gather_planes> {
+    static constexpr size_t bytes[] = {4, 8, 12, 12}; /* 36 B per sample */
+    static constexpr const char *planes = "gather", *holds = "gather is", *count = "four", *name = "c2rt_gather_planes", *what = "gather plane";
+    using Opts = c2rt_gather_opts;
+    static int check_opts(c2rt_ctx *ctx, const Opts *g)
+    {
+        if (!g) return fail(ctx, C2RT_ERR_INVALID_ARG, "null gather options");
+        if (g->samples == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "gather samples is 0: at least one sample");
+        if (g->reserved != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "c2rt_gather_opts.reserved is %u: must be 0", (unsigned)g->reserved);
+        if (g->samples > C2RT_MAX_GATHER_SAMPLES)
+            return fail(ctx, C2RT_ERR_LIMIT, "%u gather samples (at most %u)", (unsigned)g->samples, (unsigned)C2RT_MAX_GATHER_SAMPLES);
+        return C2RT_OK;
+    }
+};
+static_assert(sizeof Family<c2rt_hit_planes>::bytes == kPlanes<c2rt_hit_planes> * sizeof(size_t) &&
+              sizeof Family<c2rt_shade_planes>::bytes == kPlanes<c2rt_shade_planes> * sizeof(size_t) &&
+              sizeof Family<c2rt_occlusion_planes>::bytes == kPlanes<c2rt_occlusion_planes> * sizeof(size_t) &&
+              sizeof Family<c2rt_gather_planes>::bytes == kPlanes<c2rt_gather_planes> * sizeof(size_t), "a sample size for every plane");
+static constexpr NoOpts kNoOpts = {};
 
 /* What a host variant stages: its outputs in staging order.  An output is `layers` slices (layer-major on both sides)
  * of samples of `bytes` bytes each; `host` null: not asked for, takes no room.  lay_out places them. */
@@ -1463,7 +1470,7 @@ struct Staging {
     {
         char *host[kPlanes<S>];
         std::memcpy(host, &planes_host, sizeof host);
-        for (int k = 0; k < kPlanes<S>; ++k) add(host[k], PlaneBytes<S>::v[k], layers);
+        for (int k = 0; k < kPlanes<S>; ++k) add(host[k], Family<S>::bytes[k], layers);
     }
     /* the device-side struct of the planes added as outputs first, first + 1, ... */
     template <class S>
@@ -1506,8 +1513,9 @@ static int copy_back(c2rt_ctx *ctx, const Staging &outs, size_t first, size_t m,
     return C2RT_OK;
 }
 
-/* The ray faces: n input records (c2rt_ray, c2rt_segment) in chunks of at most `cap`.  launch(p, records_dev, m, chunk)
- * enqueues the `what` kernel over m staged records, the layer stride of its outputs being `chunk`. */
+/* The ray faces: n input records (c2rt_ray, c2rt_segment) in chunks of at most `cap`.  launch(p, records_dev, first, m,
+ * chunk) enqueues the `what` kernel over m staged records, `first` the index in the caller's array of the first of them,
+ * the layer stride of its outputs being `chunk`. */
 template <class Launch>
 static int ray_chunks(c2rt_ctx *ctx, const void *in, uint64_t n, uint64_t cap, Staging &outs, const char *what, Launch launch)
 {
@@ -1521,7 +1529,7 @@ static int ray_chunks(c2rt_ctx *ctx, const void *in, uint64_t n, uint64_t cap, S
     for (uint64_t i = 0; i < n; i += chunk) {
         const uint64_t m = n - i < chunk ? n - i : chunk;
         HIP_TRY(ctx, hipMemcpyAsync(in_dev, static_cast<const c2rt_ray *>(in) + i, m * sizeof(c2rt_ray), hipMemcpyHostToDevice, ctx->stream));
-        const int e = launch(p, in_dev, m, chunk);
+        const int e = launch(p, in_dev, i, m, chunk);
         if (e != 0) return fail(ctx, C2RT_ERR_HIP, "%s kernel launch: %s", what, hipGetErrorString((hipError_t)e));
         if (const int st = copy_back(ctx, outs, i, m, n, chunk)) return st;
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1559,7 +1567,7 @@ int c2rt_trace_rays(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, c2rt_ray_hi
     Staging outs;
     outs.add(hits, sizeof(c2rt_ray_hit));
     outs.add(rgb, 3 * sizeof(float));
-    return ray_chunks(ctx, rays, n, kQueryChunk, outs, "ray query", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t m, uint64_t) {
+    return ray_chunks(ctx, rays, n, kQueryChunk, outs, "ray query", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t, uint64_t m, uint64_t) {
         return launch_trace_rays(p, ctx->plan.csg_levels, rays_dev, m, outs.dev<c2rt_ray_hit>(0), outs.dev<float>(1), ctx->stream);
     });
 }
@@ -1569,12 +1577,13 @@ int c2rt_test_visibility(c2rt_ctx *ctx, const c2rt_segment *seg, uint64_t n, uin
     if (const int st = check_query_args(ctx, seg, n, visible != nullptr)) return st < 0 ? C2RT_OK : st;
     Staging outs;
     outs.add(visible, 1);
-    return ray_chunks(ctx, seg, n, kQueryChunk, outs, "visibility query", [&](const RenderParams &p, const c2rt_ray *seg_dev, uint64_t m, uint64_t) {
+    return ray_chunks(ctx, seg, n, kQueryChunk, outs, "visibility query", [&](const RenderParams &p, const c2rt_ray *seg_dev, uint64_t, uint64_t m, uint64_t) {
         return launch_test_visibility(p, ctx->plan.csg_levels, reinterpret_cast<const c2rt_segment *>(seg_dev), m, outs.dev<uint8_t>(0), ctx->stream);
     });
 }
 
-/* ---- hit planes of a camera frame (c2rt_hit_planes.hip) ---------------------------------------------------------- */
+/* ---- plane families: hit, shading, occlusion and gather planes of a camera frame or of a caller's rays --------------- */
+/* (c2rt_hit_planes.hip, c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_gather.hip; each described by its Family above) */
 
 /* The refusals of the modes in which a pixel is not one ray, in the documented order; `holds`: what a pixel holds in the
  * call ("record is", "terms are"), `planes`: which planes it fills ("hit", "shading") */
@@ -1587,16 +1596,6 @@ static int check_one_ray_per_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam, 
     return C2RT_OK;
 }
 
-/* the refusals of both entry points, in the documented order: a frame call's, then the planes', then the modes in which
- * a pixel is not one ray */
-static int check_hit_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_hit_planes *planes)
-{
-    if (const int st = check_frame_args(ctx, cam, opts)) return st;
-    if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
-    if (!any_plane(*planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all seven pointers of c2rt_hit_planes are null");
-    return check_one_ray_per_pixel(ctx, cam, opts, "record is", "hit");
-}
-
 /* The frame's parameter block for its camera, strips and size, with the query settings on top (query_params): exact::
  * arithmetic, full-capacity hit stack, no culling rectangles (every mask all ones), no ground node, one tap. */
 static void hit_params(const c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, RenderParams &p)
@@ -1605,273 +1604,169 @@ static void hit_params(const c2rt_ctx *ctx, const c2rt_camera_frame *cam, const 
     hit_settings(ctx, p);
 }
 
-int c2rt_render_hits_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
-                            const c2rt_hit_planes *planes_dev, void *hip_stream)
+extern "C++" { /* templates: the four faces of a family S, `o` its options (&kNoOpts where it has none) */
+
+/* the family's own refusals, behind the frame call's or the ray call's, in the documented order: the options', then the
+ * planes' */
+template <class S>
+static int check_planes(c2rt_ctx *ctx, const typename Family<S>::Opts *o, const S *planes)
 {
-    if (const int st = check_hit_args(ctx, cam, opts, planes_dev)) return st;
+    if (const int st = Family<S>::check_opts(ctx, o)) return st;
+    if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
+    if (!any_plane(*planes))
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all %s pointers of %s are null", Family<S>::count, Family<S>::name);
+    return C2RT_OK;
+}
+
+/* the refusals of both frame faces, in the documented order: a frame call's, then the family's, then the modes in which
+ * a pixel is not one ray */
+template <class S>
+static int check_frame_planes(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const typename Family<S>::Opts *o, const S *planes)
+{
+    if (const int st = check_frame_args(ctx, cam, opts)) return st;
+    if (const int st = check_planes(ctx, o, planes)) return st;
+    return check_one_ray_per_pixel(ctx, cam, opts, Family<S>::holds, Family<S>::planes);
+}
+
+template <class S>
+static int frame_planes_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const typename Family<S>::Opts *o,
+                               const S *planes_dev, void *hip_stream)
+{
+    if (const int st = check_frame_planes(ctx, cam, opts, o, planes_dev)) return st;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     hit_params(ctx, cam, opts, p);
     if (p.local_rows == 0) return C2RT_OK;
-    const int e = launch_hit_planes(p, ctx->plan.csg_levels, *planes_dev, 0, p.local_rows, hip_stream);
-    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "hit plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+    const int e = launch_plane_rows(p, ctx->plan.csg_levels, *o, *planes_dev, 0, p.local_rows, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "%s kernel launch: %s", Family<S>::what, hipGetErrorString((hipError_t)e));
     return C2RT_OK;
 }
 
 /* Host variant: chunks of whole rows, at most kQueryChunk pixels each (row_chunks), plane after plane for the chunk size
- * and only for the planes asked for — 92 B per pixel, 23 MiB at most, whatever the frame size. */
-int c2rt_render_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_hit_planes *planes_host)
+ * and only for the planes asked for — 92 / 56 / 40 / 36 B per pixel, 23 / 14 / 10 / 9 MiB at most, whatever the frame
+ * size.  A chunk's pixels draw the samples of their place in the frame. */
+template <class S>
+static int frame_planes_host(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const typename Family<S>::Opts *o,
+                             const S *planes_host)
 {
-    if (const int st = check_hit_args(ctx, cam, opts, planes_host)) return st;
+    if (const int st = check_frame_planes(ctx, cam, opts, o, planes_host)) return st;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     hit_params(ctx, cam, opts, p);
     if (p.local_rows == 0) return C2RT_OK;
     Staging outs;
     outs.add_planes(*planes_host);
-    return row_chunks(ctx, p, 1, outs, "hit plane", [&](uint32_t r0, uint32_t m, size_t) {
-        return launch_hit_planes(p, ctx->plan.csg_levels, outs.planes<c2rt_hit_planes>(), r0, m, ctx->stream);
+    return row_chunks(ctx, p, 1, outs, Family<S>::what, [&](uint32_t r0, uint32_t m, size_t) {
+        return launch_plane_rows(p, ctx->plan.csg_levels, *o, outs.planes<S>(), r0, m, ctx->stream);
     });
 }
 
-/* ---- shading planes: the terms of a sample's colour (c2rt_shade_planes.hip) ---------------------------------------- */
-
-/* the planes' own refusals, behind the frame call's or the ray call's */
-static int check_shade_planes(c2rt_ctx *ctx, const c2rt_shade_planes *planes)
+template <class S>
+static int ray_planes_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, const typename Family<S>::Opts *o, const S *planes_dev, void *hip_stream)
 {
-    if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
-    if (!any_plane(*planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all six pointers of c2rt_shade_planes are null");
+    if (const int st = check_query_args(ctx, rays_dev, n, true)) return st < 0 ? C2RT_OK : st;
+    if (const int st = check_planes(ctx, o, planes_dev)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    query_params(ctx, p);
+    const int e = launch_plane_rays(p, ctx->plan.csg_levels, rays_dev, n, 0, *o, *planes_dev, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "%s kernel launch: %s", Family<S>::what, hipGetErrorString((hipError_t)e));
     return C2RT_OK;
 }
 
-/* c2rt_render_hits' refusals in its order and wording, with these planes in the place of the hit planes */
-static int check_shading_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_shade_planes *planes)
+/* Host variant: c2rt_trace_rays' staging, [rays | planes asked for] for chunks of at most kQueryChunk rays; a chunk's rays
+ * draw the samples of their place in the caller's array (ray_chunks' `first`) */
+template <class S>
+static int ray_planes_host(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const typename Family<S>::Opts *o, const S *planes_host)
 {
-    if (const int st = check_frame_args(ctx, cam, opts)) return st;
-    if (const int st = check_shade_planes(ctx, planes)) return st;
-    return check_one_ray_per_pixel(ctx, cam, opts, "terms are", "shading");
+    if (const int st = check_query_args(ctx, rays, n, true)) return st < 0 ? C2RT_OK : st;
+    if (const int st = check_planes(ctx, o, planes_host)) return st;
+    Staging outs;
+    outs.add_planes(*planes_host);
+    return ray_chunks(ctx, rays, n, kQueryChunk, outs, Family<S>::what, [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t first, uint64_t m, uint64_t) {
+        return launch_plane_rays(p, ctx->plan.csg_levels, rays_dev, m, first, *o, outs.planes<S>(), ctx->stream);
+    });
+}
+
+} /* extern "C++" */
+
+int c2rt_render_hits_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                            const c2rt_hit_planes *planes_dev, void *hip_stream)
+{
+    return frame_planes_device(ctx, cam, opts, &kNoOpts, planes_dev, hip_stream);
+}
+
+int c2rt_render_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_hit_planes *planes_host)
+{
+    return frame_planes_host(ctx, cam, opts, &kNoOpts, planes_host);
 }
 
 int c2rt_render_shading_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
                                const c2rt_shade_planes *planes_dev, void *hip_stream)
 {
-    if (const int st = check_shading_args(ctx, cam, opts, planes_dev)) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    RenderParams p;
-    hit_params(ctx, cam, opts, p);
-    if (p.local_rows == 0) return C2RT_OK;
-    const int e = launch_shade_planes(p, ctx->plan.csg_levels, *planes_dev, 0, p.local_rows, hip_stream);
-    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "shading plane kernel launch: %s", hipGetErrorString((hipError_t)e));
-    return C2RT_OK;
+    return frame_planes_device(ctx, cam, opts, &kNoOpts, planes_dev, hip_stream);
 }
 
-/* Host variant: c2rt_render_hits' chunks of whole rows, plane after plane for the chunk size and only for the planes
- * asked for — 56 B per pixel, 14 MiB at most. */
 int c2rt_render_shading(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_shade_planes *planes_host)
 {
-    if (const int st = check_shading_args(ctx, cam, opts, planes_host)) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    RenderParams p;
-    hit_params(ctx, cam, opts, p);
-    if (p.local_rows == 0) return C2RT_OK;
-    Staging outs;
-    outs.add_planes(*planes_host);
-    return row_chunks(ctx, p, 1, outs, "shading plane", [&](uint32_t r0, uint32_t m, size_t) {
-        return launch_shade_planes(p, ctx->plan.csg_levels, outs.planes<c2rt_shade_planes>(), r0, m, ctx->stream);
-    });
+    return frame_planes_host(ctx, cam, opts, &kNoOpts, planes_host);
 }
 
 int c2rt_trace_rays_shading_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, const c2rt_shade_planes *planes_dev, void *hip_stream)
 {
-    if (const int st = check_query_args(ctx, rays_dev, n, true)) return st < 0 ? C2RT_OK : st;
-    if (const int st = check_shade_planes(ctx, planes_dev)) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    RenderParams p;
-    query_params(ctx, p);
-    const int e = launch_trace_rays_shade(p, ctx->plan.csg_levels, rays_dev, n, *planes_dev, hip_stream);
-    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "shading plane kernel launch: %s", hipGetErrorString((hipError_t)e));
-    return C2RT_OK;
+    return ray_planes_device(ctx, rays_dev, n, &kNoOpts, planes_dev, hip_stream);
 }
 
-/* Host variant: c2rt_trace_rays' staging, [rays | planes asked for] for chunks of at most kQueryChunk rays */
 int c2rt_trace_rays_shading(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const c2rt_shade_planes *planes_host)
 {
-    if (const int st = check_query_args(ctx, rays, n, true)) return st < 0 ? C2RT_OK : st;
-    if (const int st = check_shade_planes(ctx, planes_host)) return st;
-    Staging outs;
-    outs.add_planes(*planes_host);
-    return ray_chunks(ctx, rays, n, kQueryChunk, outs, "shading plane", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t m, uint64_t) {
-        return launch_trace_rays_shade(p, ctx->plan.csg_levels, rays_dev, m, outs.planes<c2rt_shade_planes>(), ctx->stream);
-    });
-}
-
-/* ---- occlusion planes: hemisphere visibility of every hit (c2rt_occlusion.hip) ------------------------------------- */
-
-/* the call's own refusals, behind the frame call's or the ray call's, in the documented order */
-static int check_occlusion_args(c2rt_ctx *ctx, const c2rt_occlusion_opts *occ, const c2rt_occlusion_planes *planes)
-{
-    if (!occ) return fail(ctx, C2RT_ERR_INVALID_ARG, "null occlusion options");
-    if (!(occ->radius > 0) || !std::isfinite(occ->radius))
-        return fail(ctx, C2RT_ERR_INVALID_ARG, "occlusion radius %g: a finite length above 0", occ->radius);
-    if (occ->samples == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "occlusion samples is 0: at least one sample");
-    if (occ->reserved != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "c2rt_occlusion_opts.reserved is %u: must be 0", (unsigned)occ->reserved);
-    if (occ->samples > C2RT_MAX_OCCLUSION_SAMPLES)
-        return fail(ctx, C2RT_ERR_LIMIT, "%u occlusion samples (at most %u)", (unsigned)occ->samples, (unsigned)C2RT_MAX_OCCLUSION_SAMPLES);
-    if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
-    if (!any_plane(*planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all four pointers of c2rt_occlusion_planes are null");
-    return C2RT_OK;
-}
-
-/* c2rt_render_hits' refusals in its order and wording, with the options and these planes in the place of the hit planes */
-static int check_occlusion_frame(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_occlusion_opts *occ,
-                                 const c2rt_occlusion_planes *planes)
-{
-    if (const int st = check_frame_args(ctx, cam, opts)) return st;
-    if (const int st = check_occlusion_args(ctx, occ, planes)) return st;
-    return check_one_ray_per_pixel(ctx, cam, opts, "occlusion is", "occlusion");
+    return ray_planes_host(ctx, rays, n, &kNoOpts, planes_host);
 }
 
 int c2rt_render_occlusion_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_occlusion_opts *occ,
                                  const c2rt_occlusion_planes *planes_dev, void *hip_stream)
 {
-    if (const int st = check_occlusion_frame(ctx, cam, opts, occ, planes_dev)) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    RenderParams p;
-    hit_params(ctx, cam, opts, p);
-    if (p.local_rows == 0) return C2RT_OK;
-    const int e = launch_occlusion_planes(p, ctx->plan.csg_levels, *occ, *planes_dev, 0, p.local_rows, hip_stream);
-    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "occlusion plane kernel launch: %s", hipGetErrorString((hipError_t)e));
-    return C2RT_OK;
+    return frame_planes_device(ctx, cam, opts, occ, planes_dev, hip_stream);
 }
 
-/* Host variant: c2rt_render_hits' chunks of whole rows, plane after plane for the chunk size and only for the planes
- * asked for — 40 B per pixel, 10 MiB at most.  A chunk's pixels draw the samples of their place in the frame. */
 int c2rt_render_occlusion(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_occlusion_opts *occ,
                           const c2rt_occlusion_planes *planes_host)
 {
-    if (const int st = check_occlusion_frame(ctx, cam, opts, occ, planes_host)) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    RenderParams p;
-    hit_params(ctx, cam, opts, p);
-    if (p.local_rows == 0) return C2RT_OK;
-    Staging outs;
-    outs.add_planes(*planes_host);
-    return row_chunks(ctx, p, 1, outs, "occlusion plane", [&](uint32_t r0, uint32_t m, size_t) {
-        return launch_occlusion_planes(p, ctx->plan.csg_levels, *occ, outs.planes<c2rt_occlusion_planes>(), r0, m, ctx->stream);
-    });
+    return frame_planes_host(ctx, cam, opts, occ, planes_host);
 }
 
 int c2rt_trace_rays_occlusion_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, const c2rt_occlusion_opts *occ,
                                      const c2rt_occlusion_planes *planes_dev, void *hip_stream)
 {
-    if (const int st = check_query_args(ctx, rays_dev, n, true)) return st < 0 ? C2RT_OK : st;
-    if (const int st = check_occlusion_args(ctx, occ, planes_dev)) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    RenderParams p;
-    query_params(ctx, p);
-    const int e = launch_trace_rays_occlusion(p, ctx->plan.csg_levels, rays_dev, n, 0, *occ, *planes_dev, hip_stream);
-    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "occlusion plane kernel launch: %s", hipGetErrorString((hipError_t)e));
-    return C2RT_OK;
+    return ray_planes_device(ctx, rays_dev, n, occ, planes_dev, hip_stream);
 }
 
-/* Host variant: c2rt_trace_rays' staging, [rays | planes asked for] for chunks of at most kQueryChunk rays; ray_chunks
- * launches the chunks in order, so `first` is the index in the caller's array of the chunk's first ray */
 int c2rt_trace_rays_occlusion(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const c2rt_occlusion_opts *occ,
                               const c2rt_occlusion_planes *planes_host)
 {
-    if (const int st = check_query_args(ctx, rays, n, true)) return st < 0 ? C2RT_OK : st;
-    if (const int st = check_occlusion_args(ctx, occ, planes_host)) return st;
-    Staging outs;
-    outs.add_planes(*planes_host);
-    uint64_t first = 0;
-    return ray_chunks(ctx, rays, n, kQueryChunk, outs, "occlusion plane", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t m, uint64_t) {
-        const uint64_t base = first;
-        first += m;
-        return launch_trace_rays_occlusion(p, ctx->plan.csg_levels, rays_dev, m, base, *occ, outs.planes<c2rt_occlusion_planes>(), ctx->stream);
-    });
-}
-
-/* ---- gather planes: one-bounce indirect light of every hit (c2rt_gather.hip) ---------------------------------------- */
-
-/* the call's own refusals, behind the frame call's or the ray call's, in the documented order */
-static int check_gather_args(c2rt_ctx *ctx, const c2rt_gather_opts *g, const c2rt_gather_planes *planes)
-{
-    if (!g) return fail(ctx, C2RT_ERR_INVALID_ARG, "null gather options");
-    if (g->samples == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "gather samples is 0: at least one sample");
-    if (g->reserved != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "c2rt_gather_opts.reserved is %u: must be 0", (unsigned)g->reserved);
-    if (g->samples > C2RT_MAX_GATHER_SAMPLES)
-        return fail(ctx, C2RT_ERR_LIMIT, "%u gather samples (at most %u)", (unsigned)g->samples, (unsigned)C2RT_MAX_GATHER_SAMPLES);
-    if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
-    if (!any_plane(*planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all four pointers of c2rt_gather_planes are null");
-    return C2RT_OK;
-}
-
-/* c2rt_render_hits' refusals in its order and wording, with the options and these planes in the place of the hit planes */
-static int check_gather_frame(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_gather_opts *g,
-                              const c2rt_gather_planes *planes)
-{
-    if (const int st = check_frame_args(ctx, cam, opts)) return st;
-    if (const int st = check_gather_args(ctx, g, planes)) return st;
-    return check_one_ray_per_pixel(ctx, cam, opts, "gather is", "gather");
+    return ray_planes_host(ctx, rays, n, occ, planes_host);
 }
 
 int c2rt_render_gather_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_gather_opts *g,
                               const c2rt_gather_planes *planes_dev, void *hip_stream)
 {
-    if (const int st = check_gather_frame(ctx, cam, opts, g, planes_dev)) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    RenderParams p;
-    hit_params(ctx, cam, opts, p);
-    if (p.local_rows == 0) return C2RT_OK;
-    const int e = launch_gather_planes(p, ctx->plan.csg_levels, *g, *planes_dev, 0, p.local_rows, hip_stream);
-    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "gather plane kernel launch: %s", hipGetErrorString((hipError_t)e));
-    return C2RT_OK;
+    return frame_planes_device(ctx, cam, opts, g, planes_dev, hip_stream);
 }
 
-/* Host variant: c2rt_render_hits' chunks of whole rows, plane after plane for the chunk size and only for the planes
- * asked for — 36 B per pixel, 9 MiB at most.  A chunk's pixels draw the samples of their place in the frame. */
 int c2rt_render_gather(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_gather_opts *g,
                        const c2rt_gather_planes *planes_host)
 {
-    if (const int st = check_gather_frame(ctx, cam, opts, g, planes_host)) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    RenderParams p;
-    hit_params(ctx, cam, opts, p);
-    if (p.local_rows == 0) return C2RT_OK;
-    Staging outs;
-    outs.add_planes(*planes_host);
-    return row_chunks(ctx, p, 1, outs, "gather plane", [&](uint32_t r0, uint32_t m, size_t) {
-        return launch_gather_planes(p, ctx->plan.csg_levels, *g, outs.planes<c2rt_gather_planes>(), r0, m, ctx->stream);
-    });
+    return frame_planes_host(ctx, cam, opts, g, planes_host);
 }
 
 int c2rt_trace_rays_gather_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, const c2rt_gather_opts *g, const c2rt_gather_planes *planes_dev,
                                   void *hip_stream)
 {
-    if (const int st = check_query_args(ctx, rays_dev, n, true)) return st < 0 ? C2RT_OK : st;
-    if (const int st = check_gather_args(ctx, g, planes_dev)) return st;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    RenderParams p;
-    query_params(ctx, p);
-    const int e = launch_trace_rays_gather(p, ctx->plan.csg_levels, rays_dev, n, 0, *g, *planes_dev, hip_stream);
-    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "gather plane kernel launch: %s", hipGetErrorString((hipError_t)e));
-    return C2RT_OK;
+    return ray_planes_device(ctx, rays_dev, n, g, planes_dev, hip_stream);
 }
 
-/* Host variant: c2rt_trace_rays' staging, [rays | planes asked for] for chunks of at most kQueryChunk rays; ray_chunks
- * launches the chunks in order, so `first` is the index in the caller's array of the chunk's first ray */
 int c2rt_trace_rays_gather(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const c2rt_gather_opts *g, const c2rt_gather_planes *planes_host)
 {
-    if (const int st = check_query_args(ctx, rays, n, true)) return st < 0 ? C2RT_OK : st;
-    if (const int st = check_gather_args(ctx, g, planes_host)) return st;
-    Staging outs;
-    outs.add_planes(*planes_host);
-    uint64_t first = 0;
-    return ray_chunks(ctx, rays, n, kQueryChunk, outs, "gather plane", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t m, uint64_t) {
-        const uint64_t base = first;
-        first += m;
-        return launch_trace_rays_gather(p, ctx->plan.csg_levels, rays_dev, m, base, *g, outs.planes<c2rt_gather_planes>(), ctx->stream);
-    });
+    return ray_planes_host(ctx, rays, n, g, planes_host);
 }
 
 /* ---- hit layers: every surface along a ray or pixel (c2rt_layers.hip) --------------------------------------------- */
@@ -1910,21 +1805,21 @@ int c2rt_trace_rays_layers(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, uint
     outs.add(hits, sizeof(c2rt_ray_hit), max_layers);
     outs.add(rgb, 3 * sizeof(float), max_layers);
     outs.add(count, 1);
-    return ray_chunks(ctx, rays, n, kQueryChunk / max_layers, outs, "hit layer", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t m, uint64_t chunk) {
+    return ray_chunks(ctx, rays, n, kQueryChunk / max_layers, outs, "hit layer", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t, uint64_t m, uint64_t chunk) {
         return launch_trace_ray_layers(p, ctx->plan.csg_levels, rays_dev, m, max_layers, chunk, outs.dev<c2rt_ray_hit>(0), outs.dev<float>(1), outs.dev<uint8_t>(2),
                                        ctx->stream);
     });
 }
 
 /* the refusals of the frame face, in the documented order: a frame call's, null planes, the layers', then the modes in
- * which a pixel is not one ray, worded as check_hit_args words them */
+ * which a pixel is not one ray, worded as check_frame_planes words them for the hit planes */
 static int check_hit_layer_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, uint32_t max_layers,
                                 const c2rt_hit_planes *planes, const uint8_t *count)
 {
     if (const int st = check_frame_args(ctx, cam, opts)) return st;
     if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
     if (const int st = check_layer_args(ctx, max_layers, any_plane(*planes) || count)) return st;
-    return check_one_ray_per_pixel(ctx, cam, opts, "record is", "hit");
+    return check_one_ray_per_pixel(ctx, cam, opts, Family<c2rt_hit_planes>::holds, Family<c2rt_hit_planes>::planes);
 }
 
 int c2rt_render_hit_layers_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, uint32_t max_layers,
@@ -1968,8 +1863,7 @@ static int check_hit_batch_args(c2rt_ctx *ctx, const c2rt_camera_frame *cams, co
                                 uint32_t n_frames, const c2rt_render_opts *opts, const c2rt_hit_planes *planes)
 {
     if (const int st = check_batch_args(ctx, cams, n_frames, opts)) return st;
-    if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null planes");
-    if (!any_plane(*planes)) return fail(ctx, C2RT_ERR_INVALID_ARG, "no plane asked for: all seven pointers of c2rt_hit_planes are null");
+    if (const int st = check_planes(ctx, &kNoOpts, planes)) return st;
     if (poses_given)
         if (const int st = check_posed_args(ctx, poses, n_frames)) return st;
     return C2RT_OK;
@@ -2118,6 +2012,26 @@ int c2rt_render_frames_posed_hits(c2rt_ctx *ctx, const c2rt_camera_frame *cams, 
 
 /* ---- adaptive anti-aliasing (c2rt_adaptive.hip) ------------------------------------------------------------------- */
 
+/* What every adaptive call refuses behind its own first checks, in the documented order: the threshold and the outputs,
+ * then the modes in which a pixel is not five rays of its own or its neighbours are not in this frame.  cam null: a
+ * batch call, whose own refusals (check_batch_args) have covered all of those modes but the strips. */
+static int check_adaptive_tail(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, float threshold, const void *out_rgb,
+                               bool mask_ok)
+{
+    if (!(threshold >= 0.0f)) return fail(ctx, C2RT_ERR_INVALID_ARG, "threshold %g: neither negative nor NaN", (double)threshold);
+    if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    if (!mask_ok) return fail(ctx, C2RT_ERR_INVALID_ARG, "null needs_aa: the device variant keeps the flags in the caller's buffer");
+    if (cam) {
+        if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: the flags compare one ray per pixel, a lens has many");
+        if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: the flags compare one ray per pixel, a stereo camera has two");
+        if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the refinement does not count rays");
+        if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
+    }
+    if (opts->strip_world > 1) return fail(ctx, C2RT_ERR_UNSUPPORTED, "strip_world > 1: the rows above and below a strip belong to other ranks");
+    if (cam && !ctx->peers.empty()) return fail(ctx, C2RT_ERR_UNSUPPORTED, "multi-device context: the rows above and below a strip are on other devices");
+    return C2RT_OK;
+}
+
 /* the refusals of both entry points, in the documented order: a frame call's, then the arguments of this call, then the
  * modes in which a pixel is not five rays of its own or its neighbours are not in this frame */
 static int check_adaptive_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, float threshold,
@@ -2125,16 +2039,7 @@ static int check_adaptive_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam, cons
 {
     if (const int st = check_frame_args(ctx, cam, opts)) return st;
     if (opts->taps != C2RT_TAPS_REF5) return fail(ctx, C2RT_ERR_INVALID_ARG, "adaptive anti-aliasing refines to C2RT_TAPS_REF5: taps is %u", (unsigned)opts->taps);
-    if (!(threshold >= 0.0f)) return fail(ctx, C2RT_ERR_INVALID_ARG, "threshold %g: neither negative nor NaN", (double)threshold);
-    if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
-    if (!mask_ok) return fail(ctx, C2RT_ERR_INVALID_ARG, "null needs_aa: the device variant keeps the flags in the caller's buffer");
-    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: the flags compare one ray per pixel, a lens has many");
-    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: the flags compare one ray per pixel, a stereo camera has two");
-    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the refinement does not count rays");
-    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
-    if (opts->strip_world > 1) return fail(ctx, C2RT_ERR_UNSUPPORTED, "strip_world > 1: the rows above and below a strip belong to other ranks");
-    if (!ctx->peers.empty()) return fail(ctx, C2RT_ERR_UNSUPPORTED, "multi-device context: the rows above and below a strip are on other devices");
-    return C2RT_OK;
+    return check_adaptive_tail(ctx, cam, opts, threshold, out_rgb, mask_ok);
 }
 
 /* The three steps on `stream`, device pointers: the one-tap frame through the frame path as it is (pre-pass, lean / exact
@@ -2164,6 +2069,16 @@ int c2rt_render_frame_adaptive_device(c2rt_ctx *ctx, const c2rt_camera_frame *ca
     return adaptive_enqueue(ctx, cam, opts, nullptr, threshold, out_rgb_dev, needs_aa_dev, static_cast<hipStream_t>(hip_stream));
 }
 
+/* The tail of every adaptive host variant: the px pixels of the frame(s) at the head of the staging allocation and, where
+ * asked for, their flags at mask_dev back to the caller, one copy per output, then a stream sync */
+static int adaptive_copy_back(c2rt_ctx *ctx, size_t px, const uint8_t *mask_dev, float *out_rgb, uint8_t *needs_aa)
+{
+    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->frame, px * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (needs_aa) HIP_TRY(ctx, hipMemcpyAsync(needs_aa, mask_dev, px, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return C2RT_OK;
+}
+
 /* Both host variants, the arguments checked: frame and mask side by side in the context's staging allocation, on the
  * context's stream; one copy back per output, then a stream sync. */
 static int adaptive_to_host(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_tap_table *taps, float threshold,
@@ -2177,10 +2092,7 @@ static int adaptive_to_host(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c
     if (const int st = ensure_staging(ctx, off_mask + px)) return st;
     uint8_t *mask_dev = reinterpret_cast<uint8_t *>(ctx->frame) + off_mask;
     if (const int st = adaptive_enqueue(ctx, cam, opts, taps, threshold, ctx->frame, mask_dev, ctx->stream)) return st;
-    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->frame, px * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (needs_aa) HIP_TRY(ctx, hipMemcpyAsync(needs_aa, mask_dev, px, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return C2RT_OK;
+    return adaptive_copy_back(ctx, px, mask_dev, out_rgb, needs_aa);
 }
 
 int c2rt_render_frame_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, float threshold,
@@ -2257,16 +2169,7 @@ static int check_adaptive_taps_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam,
     if (taps->n < 2) return fail(ctx, C2RT_ERR_INVALID_ARG, "taps: n is %u, adaptive refinement needs at least 2", (unsigned)taps->n);
     if (taps->offset[0][0] != 0.0 || taps->offset[0][1] != 0.0)
         return fail(ctx, C2RT_ERR_INVALID_ARG, "taps: tap 0 is (%g, %g), the one-tap frame samples (0, 0)", taps->offset[0][0], taps->offset[0][1]);
-    if (!(threshold >= 0.0f)) return fail(ctx, C2RT_ERR_INVALID_ARG, "threshold %g: neither negative nor NaN", (double)threshold);
-    if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
-    if (!mask_ok) return fail(ctx, C2RT_ERR_INVALID_ARG, "null needs_aa: the device variant keeps the flags in the caller's buffer");
-    if (cam->dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "depth of field: the flags compare one ray per pixel, a lens has many");
-    if (cam->stereo_separation != 0) return fail(ctx, C2RT_ERR_UNSUPPORTED, "stereo: the flags compare one ray per pixel, a stereo camera has two");
-    if (opts->count_rays) return fail(ctx, C2RT_ERR_UNSUPPORTED, "count_rays: the refinement does not count rays");
-    if (opts->prepass_bucket) return fail(ctx, C2RT_ERR_UNSUPPORTED, "prepass_bucket: a preview's pixels share the sample of their block");
-    if (opts->strip_world > 1) return fail(ctx, C2RT_ERR_UNSUPPORTED, "strip_world > 1: the rows above and below a strip belong to other ranks");
-    if (!ctx->peers.empty()) return fail(ctx, C2RT_ERR_UNSUPPORTED, "multi-device context: the rows above and below a strip are on other devices");
-    return C2RT_OK;
+    return check_adaptive_tail(ctx, cam, opts, threshold, out_rgb, mask_ok);
 }
 
 int c2rt_render_frame_adaptive_taps_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_tap_table *taps,
@@ -2292,10 +2195,7 @@ static int check_adaptive_batch_args(c2rt_ctx *ctx, const c2rt_camera_frame *cam
 {
     if (const int st = check_batch_args(ctx, cams, n_frames, opts)) return st;
     if (opts->taps != C2RT_TAPS_REF5) return fail(ctx, C2RT_ERR_INVALID_ARG, "adaptive anti-aliasing refines to C2RT_TAPS_REF5: taps is %u", (unsigned)opts->taps);
-    if (!(threshold >= 0.0f)) return fail(ctx, C2RT_ERR_INVALID_ARG, "threshold %g: neither negative nor NaN", (double)threshold);
-    if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
-    if (!mask_ok) return fail(ctx, C2RT_ERR_INVALID_ARG, "null needs_aa: the device variant keeps the flags in the caller's buffer");
-    if (opts->strip_world > 1) return fail(ctx, C2RT_ERR_UNSUPPORTED, "strip_world > 1: the rows above and below a strip belong to other ranks");
+    if (const int st = check_adaptive_tail(ctx, nullptr, opts, threshold, out_rgb, mask_ok)) return st;
     if (poses_given)
         if (const int st = check_posed_args(ctx, poses, n_frames)) return st;
     return C2RT_OK;
@@ -2332,10 +2232,7 @@ static int adaptive_batch_to_host(c2rt_ctx *ctx, const c2rt_camera_frame *cams, 
     if (const int st = ensure_staging(ctx, off_mask + px)) return st;
     uint8_t *mask_dev = reinterpret_cast<uint8_t *>(ctx->frame) + off_mask;
     if (const int st = adaptive_batch_enqueue(ctx, cams, poses, poses_given, n_frames, opts, threshold, ctx->frame, mask_dev, ctx->stream)) return st;
-    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->frame, px * 3 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    if (needs_aa) HIP_TRY(ctx, hipMemcpyAsync(needs_aa, mask_dev, px, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return C2RT_OK;
+    return adaptive_copy_back(ctx, px, mask_dev, out_rgb, needs_aa);
 }
 
 static int adaptive_batch_to_device(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, bool poses_given,

@@ -141,15 +141,12 @@ inline bool gather_args(const c2rt_gather_opts &g, GatherArgs &a)
 
 /* Rows [row0, row0 + rows) of the local rows of the frame `p` describes (hit_params, c2rt_api.cpp) into planes whose
  * first row is row0; device pointers, at least one of them non-null, rows > 0, 1 <= g.samples <= 64. */
-int launch_gather_planes(const RenderParams &p, int csg_levels, const c2rt_gather_opts &g, const c2rt_gather_planes &out, uint32_t row0, uint32_t rows,
-                         void *stream)
+int launch_plane_rows(const RenderParams &p, int csg_levels, const c2rt_gather_opts &g, const c2rt_gather_planes &out, uint32_t row0, uint32_t rows,
+                      void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     GatherArgs a;
-    if (!rows || !p.width || !any_plane(out) || !gather_args(g, a)) return (int)hipErrorInvalidValue;
-    uint32_t tiles_x;
-    const dim3 grid = tile_grid(p, rows, tiles_x);
-    return for_csg_levels(csg_levels, [&](auto L) {
+    return launch_rows_of(p, csg_levels, out, gather_args(g, a), rows, [&](auto L, dim3 grid, uint32_t tiles_x) {
         constexpr int LEVELS = decltype(L)::value;
         return launch_query(p, gather_planes_kernel<LEVELS, true>, gather_planes_kernel<LEVELS, false>, grid, stack_lds(p), s, p, out, a, row0, rows, tiles_x);
     });
@@ -157,16 +154,14 @@ int launch_gather_planes(const RenderParams &p, int csg_levels, const c2rt_gathe
 
 /* The planes [n] of the caller's rays, ray i drawing the samples of index base + i; p: query_params (c2rt_api.cpp),
  * 0 < n <= C2RT_MAX_RAYS */
-int launch_trace_rays_gather(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_gather_opts &g,
-                             const c2rt_gather_planes &out, void *stream)
+int launch_plane_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_gather_opts &g,
+                      const c2rt_gather_planes &out, void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     GatherArgs a;
-    if (!n || n > C2RT_MAX_RAYS || !rays || !any_plane(out) || !gather_args(g, a)) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) {
+    return launch_rays_of(csg_levels, rays, n, out, gather_args(g, a), [&](auto L, dim3 grid) {
         constexpr int LEVELS = decltype(L)::value;
-        return launch_query(p, trace_rays_gather_kernel<LEVELS, true>, trace_rays_gather_kernel<LEVELS, false>, ray_grid(n), stack_lds(p), s, p, out, a, rays,
-                            n, base);
+        return launch_query(p, trace_rays_gather_kernel<LEVELS, true>, trace_rays_gather_kernel<LEVELS, false>, grid, stack_lds(p), s, p, out, a, rays, n, base);
     });
 }
 

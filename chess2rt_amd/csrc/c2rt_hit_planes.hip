@@ -107,7 +107,7 @@ int launch_planes(const RenderParams &p, int csg_levels, const RenderParams *tab
 /* Rows [row0, row0 + rows) of the local rows of the frame `p` describes (frame_params with the query settings on top:
  * force_exact, csg_cap = kCsgFullCap(csg_levels), no culling, no ground node) into planes whose first row is row0;
  * device pointers, at least one of them non-null, rows > 0. */
-int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream)
+int launch_plane_rows(const RenderParams &p, int csg_levels, const NoOpts &, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream)
 {
     if (!rows || !p.width || !any_plane(out)) return (int)hipErrorInvalidValue;
     return launch_planes(p, csg_levels, nullptr, 1, 0, out, row0, rows, static_cast<hipStream_t>(stream));

@@ -127,15 +127,12 @@ inline bool occ_args(const c2rt_occlusion_opts &occ, OccArgs &a)
 
 /* Rows [row0, row0 + rows) of the local rows of the frame `p` describes (hit_params, c2rt_api.cpp) into planes whose
  * first row is row0; device pointers, at least one of them non-null, rows > 0, 1 <= occ.samples <= 64. */
-int launch_occlusion_planes(const RenderParams &p, int csg_levels, const c2rt_occlusion_opts &occ, const c2rt_occlusion_planes &out, uint32_t row0,
-                            uint32_t rows, void *stream)
+int launch_plane_rows(const RenderParams &p, int csg_levels, const c2rt_occlusion_opts &occ, const c2rt_occlusion_planes &out, uint32_t row0,
+                      uint32_t rows, void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     OccArgs a;
-    if (!rows || !p.width || !any_plane(out) || !occ_args(occ, a)) return (int)hipErrorInvalidValue;
-    uint32_t tiles_x;
-    const dim3 grid = tile_grid(p, rows, tiles_x);
-    return for_csg_levels(csg_levels, [&](auto L) {
+    return launch_rows_of(p, csg_levels, out, occ_args(occ, a), rows, [&](auto L, dim3 grid, uint32_t tiles_x) {
         hipLaunchKernelGGL((occlusion_planes_kernel<decltype(L)::value>), grid, dim3(kWave), stack_lds(p), s, p, out, a, row0, rows, tiles_x);
         return (int)hipGetLastError();
     });
@@ -143,14 +140,13 @@ int launch_occlusion_planes(const RenderParams &p, int csg_levels, const c2rt_oc
 
 /* The planes [n] of the caller's rays, ray i drawing the samples of index base + i; p: query_params (c2rt_api.cpp),
  * 0 < n <= C2RT_MAX_RAYS */
-int launch_trace_rays_occlusion(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_occlusion_opts &occ,
-                                const c2rt_occlusion_planes &out, void *stream)
+int launch_plane_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_occlusion_opts &occ,
+                      const c2rt_occlusion_planes &out, void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
     OccArgs a;
-    if (!n || n > C2RT_MAX_RAYS || !rays || !any_plane(out) || !occ_args(occ, a)) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) {
-        hipLaunchKernelGGL((trace_rays_occlusion_kernel<decltype(L)::value>), ray_grid(n), dim3(kWave), stack_lds(p), s, p, out, a, rays, n, base);
+    return launch_rays_of(csg_levels, rays, n, out, occ_args(occ, a), [&](auto L, dim3 grid) {
+        hipLaunchKernelGGL((trace_rays_occlusion_kernel<decltype(L)::value>), grid, dim3(kWave), stack_lds(p), s, p, out, a, rays, n, base);
         return (int)hipGetLastError();
     });
 }

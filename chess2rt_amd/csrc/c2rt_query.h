@@ -10,14 +10,37 @@
 #define C2RT_QUERY_H
 
 #include "c2rt_device.h"
+#include <cstring>
 
 namespace c2rt {
 
+/* A plane struct (c2rt_hit_planes, c2rt_shade_planes, c2rt_occlusion_planes, c2rt_gather_planes) as the host code sees
+ * it: nothing but pointers, kPlanes<S> of them (c2rt_api.cpp keeps the sample size of each next to the family's words) */
+template <class S> constexpr int kPlanes = 0;
+template <> inline constexpr int kPlanes<c2rt_hit_planes> = 7;
+template <> inline constexpr int kPlanes<c2rt_shade_planes> = 6;
+template <> inline constexpr int kPlanes<c2rt_occlusion_planes> = 4;
+template <> inline constexpr int kPlanes<c2rt_gather_planes> = 4;
+static_assert(sizeof(c2rt_hit_planes) == kPlanes<c2rt_hit_planes> * sizeof(void *) &&
+              sizeof(c2rt_shade_planes) == kPlanes<c2rt_shade_planes> * sizeof(void *) &&
+              sizeof(c2rt_occlusion_planes) == kPlanes<c2rt_occlusion_planes> * sizeof(void *) &&
+              sizeof(c2rt_gather_planes) == kPlanes<c2rt_gather_planes> * sizeof(void *), "the plane structs are arrays of pointers");
+
 /* "at least one plane asked for": what the launches below and the entry points of c2rt_api.cpp both refuse without */
-inline bool any_plane(const c2rt_hit_planes &o) { return o.node || o.leaf || o.dist || o.uv || o.p || o.normal || o.rgb; }
-inline bool any_plane(const c2rt_shade_planes &o) { return o.node || o.albedo || o.light || o.specular || o.visible || o.rgb; }
-inline bool any_plane(const c2rt_occlusion_planes &o) { return o.node || o.open || o.ao || o.bent; }
-inline bool any_plane(const c2rt_gather_planes &o) { return o.node || o.hits || o.indirect || o.bounce; }
+template <class S>
+inline bool any_plane(const S &o)
+{
+    const void *plane[kPlanes<S>];
+    std::memcpy(plane, &o, sizeof plane);
+    for (const void *q : plane)
+        if (q) return true;
+    return false;
+}
+
+/* The plane families launch alike: launch_plane_rows (rows of a camera frame) and launch_plane_rays (a caller's rays,
+ * ray i drawing the samples of index base + i) are overloaded on the planes type, the family's options in front of the
+ * planes.  NoOpts: the options of a family that has none (the hit and shading planes, which ignore `base` too). */
+struct NoOpts {};
 
 /* Ray and visibility queries (c2rt_trace_rays*, c2rt_test_visibility*): no camera; 0 < n <= C2RT_MAX_RAYS; hits / rgb
  * nullable, not both */
@@ -25,7 +48,7 @@ int launch_trace_rays(const RenderParams &p, int csg_levels, const c2rt_ray *ray
 int launch_test_visibility(const RenderParams &p, int csg_levels, const c2rt_segment *seg, uint64_t n, uint8_t *visible, void *stream);
 /* Hit planes (c2rt_render_hits*): rows [row0, row0 + rows) of the local rows of the frame `p` describes, into planes
  * whose first row is row0; at least one plane non-null, rows > 0 */
-int launch_hit_planes(const RenderParams &p, int csg_levels, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream);
+int launch_plane_rows(const RenderParams &p, int csg_levels, const NoOpts &, const c2rt_hit_planes &out, uint32_t row0, uint32_t rows, void *stream);
 /* Hit planes of a batch (c2rt_render_frames_hits*, c2rt_render_frames_posed_hits*): the same rows of the n_frames frames
  * whose blocks are at table_dev (p0: the host copy of one of them), in one launch; frame i's slice of a plane starts
  * i * frame_px * components elements behind the plane's pointer, at row row0 */
@@ -41,22 +64,23 @@ int launch_hit_layers(const RenderParams &p, int csg_levels, const c2rt_hit_plan
                       uint32_t row0, uint32_t rows, void *stream);
 /* Shading planes (c2rt_render_shading*, c2rt_trace_rays_shading*; c2rt_shade_planes.hip): the hit planes' rows, or the
  * ray query's rays, with the terms of the closest node's shade() one plane each; at least one plane non-null */
-int launch_shade_planes(const RenderParams &p, int csg_levels, const c2rt_shade_planes &out, uint32_t row0, uint32_t rows, void *stream);
-int launch_trace_rays_shade(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, const c2rt_shade_planes &out, void *stream);
+int launch_plane_rows(const RenderParams &p, int csg_levels, const NoOpts &, const c2rt_shade_planes &out, uint32_t row0, uint32_t rows, void *stream);
+int launch_plane_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const NoOpts &, const c2rt_shade_planes &out,
+                      void *stream);
 /* Occlusion planes (c2rt_render_occlusion*, c2rt_trace_rays_occlusion*; c2rt_occlusion.hip): the hit planes' rows, or the
  * ray query's rays, with occ.samples hemisphere visibility tests behind every hit; at least one plane non-null,
  * 1 <= occ.samples <= C2RT_MAX_OCCLUSION_SAMPLES.  Ray i draws the samples of index base + i (a host chunk's first ray) */
-int launch_occlusion_planes(const RenderParams &p, int csg_levels, const c2rt_occlusion_opts &occ, const c2rt_occlusion_planes &out, uint32_t row0,
-                            uint32_t rows, void *stream);
-int launch_trace_rays_occlusion(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_occlusion_opts &occ,
-                                const c2rt_occlusion_planes &out, void *stream);
+int launch_plane_rows(const RenderParams &p, int csg_levels, const c2rt_occlusion_opts &occ, const c2rt_occlusion_planes &out, uint32_t row0,
+                      uint32_t rows, void *stream);
+int launch_plane_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_occlusion_opts &occ,
+                      const c2rt_occlusion_planes &out, void *stream);
 /* Gather planes (c2rt_render_gather*, c2rt_trace_rays_gather*; c2rt_gather.hip): the hit planes' rows, or the ray query's
  * rays, with g.samples rays spawned over the hemisphere behind every hit, traced and shaded as c2rt_trace_rays' are; at
  * least one plane non-null, 1 <= g.samples <= C2RT_MAX_GATHER_SAMPLES.  Ray i draws the samples of index base + i */
-int launch_gather_planes(const RenderParams &p, int csg_levels, const c2rt_gather_opts &g, const c2rt_gather_planes &out, uint32_t row0, uint32_t rows,
-                         void *stream);
-int launch_trace_rays_gather(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_gather_opts &g,
-                             const c2rt_gather_planes &out, void *stream);
+int launch_plane_rows(const RenderParams &p, int csg_levels, const c2rt_gather_opts &g, const c2rt_gather_planes &out, uint32_t row0, uint32_t rows,
+                      void *stream);
+int launch_plane_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_gather_opts &g,
+                      const c2rt_gather_planes &out, void *stream);
 /* Adaptive anti-aliasing (c2rt_render_frame[s]_adaptive*): the flag images needs_aa[i][y][x] of n_frames whole one-tap
  * frames side by side, then the flagged pixels of the whole frame `p` describes (no strips) from their one-tap to their
  * five-tap value, in place; launch_aa_refine_batch: the same for the n_frames frames whose blocks are at table_dev (p0:

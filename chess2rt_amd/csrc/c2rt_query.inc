@@ -13,7 +13,7 @@
  * comes from (load6 for a caller's record, tile_pixel and pixel_ray for a camera's pixel; hemisphere_sample for the
  * directions the occlusion and gather planes draw behind a hit); where its result goes
  * (store_colour, store_record, sample_colour, store_hit_planes); the host side of a launch (ray_grid, tile_grid,
- * launch_query).
+ * launch_query; launch_rows_of and launch_rays_of, the two launch shapes of the plane families).
  */
 #include "c2rt_query.h"
 
@@ -196,6 +196,25 @@ int launch_query(const RenderParams &p, K *several, K *one, dim3 grid, size_t ld
 {
     hipLaunchKernelGGL(p.n_lights > 1 ? several : one, grid, dim3(kWave), lds, s, args...);
     return (int)hipGetLastError();
+}
+
+/* The two launch shapes of the plane families (launch_plane_rows / launch_plane_rays of each unit): refuse, size the grid,
+ * pick the CSG depth.  opts_ok: the unit's option struct converted (OccArgs, GatherArgs; true where there is none).
+ * launch(L, grid, tiles_x) / launch(L, grid) enqueues the unit's kernel of depth decltype(L)::value, so a unit names
+ * only the instances it had before, whether its kernels template on LEVELS alone or on LEVELS and MLC. */
+template <class S, class Launch>
+int launch_rows_of(const RenderParams &p, int csg_levels, const S &out, bool opts_ok, uint32_t rows, Launch launch)
+{
+    if (!rows || !p.width || !any_plane(out) || !opts_ok) return (int)hipErrorInvalidValue;
+    uint32_t tiles_x;
+    const dim3 grid = tile_grid(p, rows, tiles_x);
+    return for_csg_levels(csg_levels, [&](auto L) { return launch(L, grid, tiles_x); });
+}
+template <class S, class Launch>
+int launch_rays_of(int csg_levels, const c2rt_ray *rays, uint64_t n, const S &out, bool opts_ok, Launch launch)
+{
+    if (!n || n > C2RT_MAX_RAYS || !rays || !any_plane(out) || !opts_ok) return (int)hipErrorInvalidValue;
+    return for_csg_levels(csg_levels, [&](auto L) { return launch(L, ray_grid(n)); });
 }
 
 } // namespace

@@ -177,26 +177,24 @@ trace_rays_shade_kernel(const RenderParams P, const c2rt_shade_planes out, const
 
 /* Rows [row0, row0 + rows) of the local rows of the frame `p` describes (hit_params, c2rt_api.cpp) into planes whose
  * first row is row0; device pointers, at least one of them non-null, rows > 0. */
-int launch_shade_planes(const RenderParams &p, int csg_levels, const c2rt_shade_planes &out, uint32_t row0, uint32_t rows, void *stream)
+int launch_plane_rows(const RenderParams &p, int csg_levels, const NoOpts &, const c2rt_shade_planes &out, uint32_t row0, uint32_t rows, void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!rows || !p.width || !any_plane(out)) return (int)hipErrorInvalidValue;
-    uint32_t tiles_x;
-    const dim3 grid = tile_grid(p, rows, tiles_x);
-    return for_csg_levels(csg_levels, [&](auto L) {
+    return launch_rows_of(p, csg_levels, out, true, rows, [&](auto L, dim3 grid, uint32_t tiles_x) {
         constexpr int LEVELS = decltype(L)::value;
         return launch_query(p, shade_planes_kernel<LEVELS, true>, shade_planes_kernel<LEVELS, false>, grid, stack_lds(p), s, p, out, row0, rows, tiles_x);
     });
 }
 
-/* The planes [n] of the caller's rays; p: query_params (c2rt_api.cpp), 0 < n <= C2RT_MAX_RAYS */
-int launch_trace_rays_shade(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, const c2rt_shade_planes &out, void *stream)
+/* The planes [n] of the caller's rays (no samples are drawn: `base` is not read); p: query_params (c2rt_api.cpp),
+ * 0 < n <= C2RT_MAX_RAYS */
+int launch_plane_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t, const NoOpts &, const c2rt_shade_planes &out,
+                      void *stream)
 {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!n || n > C2RT_MAX_RAYS || !rays || !any_plane(out)) return (int)hipErrorInvalidValue;
-    return for_csg_levels(csg_levels, [&](auto L) {
+    return launch_rays_of(csg_levels, rays, n, out, true, [&](auto L, dim3 grid) {
         constexpr int LEVELS = decltype(L)::value;
-        return launch_query(p, trace_rays_shade_kernel<LEVELS, true>, trace_rays_shade_kernel<LEVELS, false>, ray_grid(n), stack_lds(p), s, p, out, rays, n);
+        return launch_query(p, trace_rays_shade_kernel<LEVELS, true>, trace_rays_shade_kernel<LEVELS, false>, grid, stack_lds(p), s, p, out, rays, n);
     });
 }
 

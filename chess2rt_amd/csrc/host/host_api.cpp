@@ -1,5 +1,6 @@
 // host_api.cpp — Renderer (the GPU drop-in for rt/renderer.d's Renderer /
 // renderSceneAsync / renderPixel) and the C wrappers of include/c2rt_host.h.
+// The probe, plane, layer, tap and adaptive renders share one set-up (frame_setup).
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -235,122 +236,100 @@ int c2rt_host_render_wait(c2rt_host_scene *s)
     return s->async_status;
 }
 
-int c2rt_host_render_pixel(c2rt_ctx *ctx, c2rt_host_scene *s, int x, int y, c2rt_trace_result *out)
+// The set-up of the calls that render one frame of the scene as it stands, without renderRT's passes: refuse null
+// arguments (args_ok: the call's own required pointers), beginFrame, the scene uploaded if it has changed, the options
+// of its settings.  C2RT_OK: cam and o are the frame's.
+static int frame_setup(c2rt_ctx *ctx, c2rt_host_scene *s, bool args_ok, c2rt_camera_frame &cam, c2rt_render_opts &o)
 {
-    if (!ctx || !s || !out) return C2RT_ERR_INVALID_ARG;
-    // renderPixel — rt/renderer.d:46-57
-    c2rt_camera_frame cam;
+    if (!ctx || !s || !args_ok) return C2RT_ERR_INVALID_ARG;
     c2rt_host_scene_begin_frame(s, &cam);
     Renderer r{ctx, s, nullptr, nullptr, nullptr};
     const int st = r.ensureUploaded();
     if (st != C2RT_OK) return st;
-    const c2rt_render_opts o = opts_of(*s->scene);
+    o = opts_of(*s->scene);
+    return C2RT_OK;
+}
+
+int c2rt_host_render_pixel(c2rt_ctx *ctx, c2rt_host_scene *s, int x, int y, c2rt_trace_result *out)
+{
+    // renderPixel — rt/renderer.d:46-57
+    c2rt_camera_frame cam;
+    c2rt_render_opts o;
+    if (const int st = frame_setup(ctx, s, out != nullptr, cam, o)) return st;
     return c2rt_render_pixel(ctx, &cam, &o, x, y, out);
 }
 
 int c2rt_host_render_hits(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_hit_planes *planes)
 {
-    if (!ctx || !s) return C2RT_ERR_INVALID_ARG;
     // the probe's set-up (c2rt_host_render_pixel) for every pixel at once; a camera with depth of field or
     // stereo, and null planes, are refused by c2rt_render_hits with the ABI's statuses
     c2rt_camera_frame cam;
-    c2rt_host_scene_begin_frame(s, &cam);
-    Renderer r{ctx, s, nullptr, nullptr, nullptr};
-    const int st = r.ensureUploaded();
-    if (st != C2RT_OK) return st;
-    const c2rt_render_opts o = opts_of(*s->scene);
+    c2rt_render_opts o;
+    if (const int st = frame_setup(ctx, s, true, cam, o)) return st;
     return c2rt_render_hits(ctx, &cam, &o, planes);
 }
 
 int c2rt_host_render_hit_layers(c2rt_ctx *ctx, c2rt_host_scene *s, uint32_t max_layers, const c2rt_hit_planes *planes, uint8_t *count)
 {
-    if (!ctx || !s) return C2RT_ERR_INVALID_ARG;
     // c2rt_host_render_hits' set-up; the layers, the planes and the camera are judged by c2rt_render_hit_layers
     c2rt_camera_frame cam;
-    c2rt_host_scene_begin_frame(s, &cam);
-    Renderer r{ctx, s, nullptr, nullptr, nullptr};
-    const int st = r.ensureUploaded();
-    if (st != C2RT_OK) return st;
-    const c2rt_render_opts o = opts_of(*s->scene);
+    c2rt_render_opts o;
+    if (const int st = frame_setup(ctx, s, true, cam, o)) return st;
     return c2rt_render_hit_layers(ctx, &cam, &o, max_layers, planes, count);
 }
 
 int c2rt_host_render_shading(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_shade_planes *planes)
 {
-    if (!ctx || !s) return C2RT_ERR_INVALID_ARG;
     // c2rt_host_render_hits' set-up; the planes and the camera are judged by c2rt_render_shading
     c2rt_camera_frame cam;
-    c2rt_host_scene_begin_frame(s, &cam);
-    Renderer r{ctx, s, nullptr, nullptr, nullptr};
-    const int st = r.ensureUploaded();
-    if (st != C2RT_OK) return st;
-    const c2rt_render_opts o = opts_of(*s->scene);
+    c2rt_render_opts o;
+    if (const int st = frame_setup(ctx, s, true, cam, o)) return st;
     return c2rt_render_shading(ctx, &cam, &o, planes);
 }
 
 int c2rt_host_render_occlusion(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_occlusion_opts *occ, const c2rt_occlusion_planes *planes)
 {
-    if (!ctx || !s) return C2RT_ERR_INVALID_ARG;
     // c2rt_host_render_hits' set-up; the options, the planes and the camera are judged by c2rt_render_occlusion
     c2rt_camera_frame cam;
-    c2rt_host_scene_begin_frame(s, &cam);
-    Renderer r{ctx, s, nullptr, nullptr, nullptr};
-    const int st = r.ensureUploaded();
-    if (st != C2RT_OK) return st;
-    const c2rt_render_opts o = opts_of(*s->scene);
+    c2rt_render_opts o;
+    if (const int st = frame_setup(ctx, s, true, cam, o)) return st;
     return c2rt_render_occlusion(ctx, &cam, &o, occ, planes);
 }
 
 int c2rt_host_render_gather(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_gather_opts *g, const c2rt_gather_planes *planes)
 {
-    if (!ctx || !s) return C2RT_ERR_INVALID_ARG;
     // c2rt_host_render_hits' set-up; the options, the planes and the camera are judged by c2rt_render_gather
     c2rt_camera_frame cam;
-    c2rt_host_scene_begin_frame(s, &cam);
-    Renderer r{ctx, s, nullptr, nullptr, nullptr};
-    const int st = r.ensureUploaded();
-    if (st != C2RT_OK) return st;
-    const c2rt_render_opts o = opts_of(*s->scene);
+    c2rt_render_opts o;
+    if (const int st = frame_setup(ctx, s, true, cam, o)) return st;
     return c2rt_render_gather(ctx, &cam, &o, g, planes);
 }
 
 int c2rt_host_render_rt_adaptive(c2rt_ctx *ctx, c2rt_host_scene *s, float *out_rgb, uint8_t *needs_aa)
 {
-    if (!ctx || !s || !out_rgb) return C2RT_ERR_INVALID_ARG;
     // renderRT's passes 2, 3a and 3b (rt/renderer.d:132-188) with 3b on the flagged pixels only
     c2rt_camera_frame cam;
-    c2rt_host_scene_begin_frame(s, &cam);
-    Renderer r{ctx, s, nullptr, nullptr, nullptr};
-    const int st = r.ensureUploaded();
-    if (st != C2RT_OK) return st;
-    c2rt_render_opts o = opts_of(*s->scene);
+    c2rt_render_opts o;
+    if (const int st = frame_setup(ctx, s, out_rgb != nullptr, cam, o)) return st;
     o.taps = C2RT_TAPS_REF5;
     return c2rt_render_frame_adaptive(ctx, &cam, &o, C2RT_AA_THRESHOLD_REF, out_rgb, needs_aa, nullptr);
 }
 
 int c2rt_host_render_rt_taps(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_tap_table *taps, float *out_rgb)
 {
-    if (!ctx || !s) return C2RT_ERR_INVALID_ARG;
     // c2rt_host_render_hits' set-up; the table, the output and the camera are judged by c2rt_render_frame_taps
     c2rt_camera_frame cam;
-    c2rt_host_scene_begin_frame(s, &cam);
-    Renderer r{ctx, s, nullptr, nullptr, nullptr};
-    const int st = r.ensureUploaded();
-    if (st != C2RT_OK) return st;
-    const c2rt_render_opts o = opts_of(*s->scene);
+    c2rt_render_opts o;
+    if (const int st = frame_setup(ctx, s, true, cam, o)) return st;
     return c2rt_render_frame_taps(ctx, &cam, &o, taps, out_rgb);
 }
 
 int c2rt_host_render_rt_adaptive_taps(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_tap_table *taps, float *out_rgb, uint8_t *needs_aa)
 {
-    if (!ctx || !s) return C2RT_ERR_INVALID_ARG;
     // c2rt_host_render_rt_adaptive with the caller's table behind the flags
     c2rt_camera_frame cam;
-    c2rt_host_scene_begin_frame(s, &cam);
-    Renderer r{ctx, s, nullptr, nullptr, nullptr};
-    const int st = r.ensureUploaded();
-    if (st != C2RT_OK) return st;
-    const c2rt_render_opts o = opts_of(*s->scene);
+    c2rt_render_opts o;
+    if (const int st = frame_setup(ctx, s, true, cam, o)) return st;
     return c2rt_render_frame_adaptive_taps(ctx, &cam, &o, taps, C2RT_AA_THRESHOLD_REF, out_rgb, needs_aa, nullptr);
 }
 

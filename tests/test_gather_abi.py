@@ -98,14 +98,14 @@ def test_header_layout_and_null_context(tmp_path):
 def test_python_layer_checks_its_arguments_before_the_library():
     """an unknown plane name and a wrong ray shape are refused by the Python layer: no context is touched"""
     with pytest.raises(ValueError):
-        api._new_gather_planes(("node", "depth"), (4,))
+        api._GATHER.new(("node", "depth"), (4,))
     with pytest.raises(ValueError):
-        api._device_gather_planes({"open": 1})
-    pl, out = api._new_gather_planes(("hits", "bounce"), (3, 5))
+        api._GATHER.device({"open": 1})
+    pl, out = api._GATHER.new(("hits", "bounce"), (3, 5))
     assert list(out) == ["hits", "bounce"] and out["hits"].shape == (3, 5) and out["bounce"].shape == (3, 5, 3)
     assert out["hits"].dtype == np.uint64 and out["bounce"].dtype == np.float32
     assert pl.node is None and pl.indirect is None and pl.hits == out["hits"].ctypes.data and pl.bounce == out["bounce"].ctypes.data
-    dev = api._device_gather_planes({"node": 64, "indirect": 0})
+    dev = api._GATHER.device({"node": 64, "indirect": 0})
     assert dev.node == 64 and dev.indirect is None and dev.hits is None and dev.bounce is None
     g = api._gather_opts(16, (1 << 40) + 5)
     assert (g.samples, g.seed, g.reserved) == (16, (1 << 40) + 5, 0)

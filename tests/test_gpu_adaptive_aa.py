@@ -123,6 +123,22 @@ def untouched(*bufs):
     return all((b == SENTINEL).all() for b in bufs)
 
 
+# The messages every adaptive call shares (the library builds them in one place), whole: a cause listed here is compared
+# with the whole message, any other cause as a part of it
+WHOLE = {
+    "threshold -1": "threshold -1: neither negative nor NaN",
+    "threshold nan": "threshold nan: neither negative nor NaN",
+    "null output": "null output",
+    "null needs_aa": "null needs_aa: the device variant keeps the flags in the caller's buffer",
+    "depth of field": "depth of field: the flags compare one ray per pixel, a lens has many",
+    "stereo": "stereo: the flags compare one ray per pixel, a stereo camera has two",
+    "count_rays": "count_rays: the refinement does not count rays",
+    "prepass_bucket": "prepass_bucket: a preview's pixels share the sample of their block",
+    "strip_world": "strip_world > 1: the rows above and below a strip belong to other ranks",
+    "multi-device": "multi-device context: the rows above and below a strip are on other devices",
+}
+
+
 def last_error(ctx):
     return _abi.load_library().c2rt_last_error(ctx.handle).decode(errors="replace")
 
@@ -243,9 +259,9 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
     def refused(ctx, c, o, t, status, cause, host_frame=fbuf, dev_frame=fdev.ptr, dev_mask=mdev.ptr, host=True):
         if host:
             assert raw_call(ctx, c, o, t, host_frame, mbuf) == status, cause
-            assert cause in last_error(ctx), (cause, last_error(ctx))
+            assert last_error(ctx) == WHOLE[cause] if cause in WHOLE else cause in last_error(ctx), (cause, last_error(ctx))
         assert raw_device_call(ctx, c, o, t, dev_frame, dev_mask) == status, cause
-        assert cause in last_error(ctx), (cause, last_error(ctx))
+        assert last_error(ctx) == WHOLE[cause] if cause in WHOLE else cause in last_error(ctx), (cause, last_error(ctx))
         assert hip_runtime().hipDeviceSynchronize() == 0
         assert untouched(fbuf, mbuf, fdev.get(), mdev.get()), cause
 
@@ -253,13 +269,13 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
     refused(gpu_ctx, cam, copy_opts(width=0, taps=_abi.TAPS_1), thr, _abi.ERR_INVALID_ARG, "")
     for taps in (_abi.TAPS_1, _abi.TAPS_4):
         refused(gpu_ctx, cam, copy_opts(taps=taps), thr, _abi.ERR_INVALID_ARG, "C2RT_TAPS_REF5")
-    refused(gpu_ctx, cam, opts, -1.0, _abi.ERR_INVALID_ARG, "threshold")
-    refused(gpu_ctx, cam, opts, float("nan"), _abi.ERR_INVALID_ARG, "threshold")
+    refused(gpu_ctx, cam, opts, -1.0, _abi.ERR_INVALID_ARG, "threshold -1")
+    refused(gpu_ctx, cam, opts, float("nan"), _abi.ERR_INVALID_ARG, "threshold nan")
     refused(gpu_ctx, cam, opts, thr, _abi.ERR_INVALID_ARG, "null output", host_frame=None, dev_frame=None)
     # the mask is required in the device variant only
     refused(gpu_ctx, cam, opts, thr, _abi.ERR_INVALID_ARG, "null needs_aa", dev_mask=None, host=False)
     # an invalid argument is reported before an unsupported mode
-    refused(gpu_ctx, copy_cam(dof=1, num_samples=4), opts, -1.0, _abi.ERR_INVALID_ARG, "threshold")
+    refused(gpu_ctx, copy_cam(dof=1, num_samples=4), opts, -1.0, _abi.ERR_INVALID_ARG, "threshold -1")
     for c, o, cause in [(copy_cam(dof=1, num_samples=4), opts, "depth of field"),
                         (copy_cam(stereo_separation=0.5), opts, "stereo"),
                         (cam, copy_opts(count_rays=1), "count_rays"),

@@ -383,10 +383,10 @@ def test_posed_scene_and_mirrors(gpu_ctx):
 # ---- refusals ------------------------------------------------------------------------------------------------------------------
 
 
-BAD_G = [  # (options, status, message), in the documented order
-    (dict(samples=0), _abi.ERR_INVALID_ARG, "samples is 0"),
-    (dict(reserved=1), _abi.ERR_INVALID_ARG, "reserved"),
-    (dict(samples=65), _abi.ERR_LIMIT, "at most 64"),
+BAD_G = [  # (options, status, the whole message), in the documented order
+    (dict(samples=0), _abi.ERR_INVALID_ARG, "gather samples is 0: at least one sample"),
+    (dict(reserved=1), _abi.ERR_INVALID_ARG, "c2rt_gather_opts.reserved is 1: must be 0"),
+    (dict(samples=65), _abi.ERR_LIMIT, "65 gather samples (at most 64)"),
 ]
 
 
@@ -429,30 +429,32 @@ def test_frame_refusals_leave_the_outputs_untouched(gpu_ctx):
     assert st == L.c2rt_render_hits(gpu_ctx.handle, C.byref(cam), C.byref(copy_opts(width=0)), C.byref(hp)) != _abi.OK and msg == last_error(gpu_ctx)
     # then the options, each with its own message
     st, msg = both(cam, opts, None, pl)
-    assert st == _abi.ERR_INVALID_ARG and "null gather options" in msg
+    assert st == _abi.ERR_INVALID_ARG and msg == "null gather options"
     for kw, status, text in BAD_G:
         st, msg = both(cam, opts, g_opts(**{**dict(samples=K), **kw}), pl)
-        assert st == status and text in msg, (kw, st, msg)
+        assert st == status and msg == text, (kw, st, msg)
     # two rules at once: samples == 0 and reserved before the limit, the options before the planes, the planes before
     # the modes
     st, msg = both(cam, opts, g_opts(samples=0, reserved=3), pl)
-    assert st == _abi.ERR_INVALID_ARG and "samples is 0" in msg
+    assert st == _abi.ERR_INVALID_ARG and msg == "gather samples is 0: at least one sample"
     st, msg = both(cam, opts, g_opts(samples=65, reserved=3), pl)
-    assert st == _abi.ERR_INVALID_ARG and "reserved" in msg
+    assert st == _abi.ERR_INVALID_ARG and msg == "c2rt_gather_opts.reserved is 3: must be 0"
     assert both(cam, opts, g_opts(samples=65), None)[0] == _abi.ERR_LIMIT
-    assert "null gather options" in both(cam, opts, None, None)[1]
+    assert both(cam, opts, None, None)[1] == "null gather options"
     st, msg = both(cam, opts, good, None)
-    assert st == _abi.ERR_INVALID_ARG and "null planes" in msg
+    assert st == _abi.ERR_INVALID_ARG and msg == "null planes"
     st, msg = both(cam, opts, good, none)
-    assert st == _abi.ERR_INVALID_ARG and "all four" in msg
+    assert st == _abi.ERR_INVALID_ARG and msg == "no plane asked for: all four pointers of c2rt_gather_planes are null"
     assert both(dof, opts, good, none)[0] == _abi.ERR_INVALID_ARG
     assert both(dof, opts, g_opts(samples=65), pl)[0] == _abi.ERR_LIMIT
     # then the modes in which a pixel is not one ray
-    for c, o, cause in [(dof, opts, "depth of field"), (copy_cam(stereo_separation=0.5), opts, "stereo"),
-                        (cam, copy_opts(count_rays=1), "count_rays"), (cam, copy_opts(prepass_bucket=48), "prepass_bucket")]:
+    for c, o, cause in [(dof, opts, "depth of field: a pixel's gather is one ray's, a lens has many per pixel"),
+                        (copy_cam(stereo_separation=0.5), opts, "stereo: a pixel's gather is one ray's, a stereo camera has two per pixel"),
+                        (cam, copy_opts(count_rays=1), "count_rays: the gather planes do not count rays"),
+                        (cam, copy_opts(prepass_bucket=48), "prepass_bucket: a preview's pixels share the sample of their block")]:
         st, msg = both(c, o, good, pl)
-        assert st == _abi.ERR_UNSUPPORTED and cause in msg, (cause, st, msg)
-    assert "depth of field" in both(copy_cam(dof=1, num_samples=4, stereo_separation=0.5), copy_opts(count_rays=1), good, pl)[1]
+        assert st == _abi.ERR_UNSUPPORTED and msg == cause, (cause, st, msg)
+    assert both(copy_cam(dof=1, num_samples=4, stereo_separation=0.5), copy_opts(count_rays=1), good, pl)[1] == "depth of field: a pixel's gather is one ray's, a lens has many per pixel"
     fresh = c2.Context(0)
     try:
         a = (C.byref(cam), C.byref(opts))
@@ -485,16 +487,16 @@ def test_ray_refusals_leave_the_outputs_untouched(gpu_ctx):
         assert fn(gpu_ctx.handle, rp, _abi.MAX_RAYS + 1, None, None, *tail) == _abi.ERR_LIMIT      # the limit before the options
         assert "rays in one call" in last_error(gpu_ctx)
         assert fn(gpu_ctx.handle, rp, n, None, C.byref(pl), *tail) == _abi.ERR_INVALID_ARG
-        assert "null gather options" in last_error(gpu_ctx)
+        assert last_error(gpu_ctx) == "null gather options"
         for kw, status, text in BAD_G:
             g = g_opts(**{**dict(samples=K), **kw})
-            assert fn(gpu_ctx.handle, rp, n, C.byref(g), C.byref(pl), *tail) == status and text in last_error(gpu_ctx), (kw, last_error(gpu_ctx))
-        assert fn(gpu_ctx.handle, rp, n, C.byref(bad), None, *tail) == _abi.ERR_INVALID_ARG and "samples is 0" in last_error(gpu_ctx)
+            assert fn(gpu_ctx.handle, rp, n, C.byref(g), C.byref(pl), *tail) == status and last_error(gpu_ctx) == text, (kw, last_error(gpu_ctx))
+        assert fn(gpu_ctx.handle, rp, n, C.byref(bad), None, *tail) == _abi.ERR_INVALID_ARG and last_error(gpu_ctx) == "gather samples is 0: at least one sample"
         assert fn(gpu_ctx.handle, rp, n, C.byref(g_opts(samples=65)), None, *tail) == _abi.ERR_LIMIT   # the options before the planes
         assert fn(gpu_ctx.handle, rp, n, C.byref(good), None, *tail) == _abi.ERR_INVALID_ARG
-        assert "null planes" in last_error(gpu_ctx)
+        assert last_error(gpu_ctx) == "null planes"
         assert fn(gpu_ctx.handle, rp, n, C.byref(good), C.byref(none), *tail) == _abi.ERR_INVALID_ARG
-        assert "all four" in last_error(gpu_ctx)
+        assert last_error(gpu_ctx) == "no plane asked for: all four pointers of c2rt_gather_planes are null"
     fresh = c2.Context(0)
     try:
         fn = L.c2rt_trace_rays_gather

@@ -337,14 +337,14 @@ def test_posed_scene_and_mirrors(gpu_ctx):
 # ---- 11: refusals ------------------------------------------------------------------------------------------------------------
 
 
-BAD_OCC = [  # (options, status, message), in the documented order
-    (dict(radius=float("nan")), _abi.ERR_INVALID_ARG, "radius"),
-    (dict(radius=float("inf")), _abi.ERR_INVALID_ARG, "radius"),
-    (dict(radius=0.0), _abi.ERR_INVALID_ARG, "radius"),
-    (dict(radius=-1.0), _abi.ERR_INVALID_ARG, "radius"),
-    (dict(samples=0), _abi.ERR_INVALID_ARG, "samples is 0"),
-    (dict(reserved=1), _abi.ERR_INVALID_ARG, "reserved"),
-    (dict(samples=65), _abi.ERR_LIMIT, "at most 64"),
+BAD_OCC = [  # (options, status, the whole message), in the documented order
+    (dict(radius=float("nan")), _abi.ERR_INVALID_ARG, "occlusion radius nan: a finite length above 0"),
+    (dict(radius=float("inf")), _abi.ERR_INVALID_ARG, "occlusion radius inf: a finite length above 0"),
+    (dict(radius=0.0), _abi.ERR_INVALID_ARG, "occlusion radius 0: a finite length above 0"),
+    (dict(radius=-1.0), _abi.ERR_INVALID_ARG, "occlusion radius -1: a finite length above 0"),
+    (dict(samples=0), _abi.ERR_INVALID_ARG, "occlusion samples is 0: at least one sample"),
+    (dict(reserved=1), _abi.ERR_INVALID_ARG, "c2rt_occlusion_opts.reserved is 1: must be 0"),
+    (dict(samples=65), _abi.ERR_LIMIT, "65 occlusion samples (at most 64)"),
 ]
 
 
@@ -387,30 +387,32 @@ def test_frame_refusals_leave_the_outputs_untouched(gpu_ctx):
     assert st == L.c2rt_render_hits(gpu_ctx.handle, C.byref(cam), C.byref(copy_opts(width=0)), C.byref(hp)) != _abi.OK and msg == last_error(gpu_ctx)
     # then the options, each with its own message
     st, msg = both(cam, opts, None, pl)
-    assert st == _abi.ERR_INVALID_ARG and "null occlusion options" in msg
+    assert st == _abi.ERR_INVALID_ARG and msg == "null occlusion options"
     for kw, status, text in BAD_OCC:
         st, msg = both(cam, opts, occ_opts(**{**dict(samples=K, radius=oc.RADIUS[name]), **kw}), pl)
-        assert st == status and text in msg, (kw, st, msg)
+        assert st == status and msg == text, (kw, st, msg)
     # two rules at once: the radius before the samples, samples == 0 and reserved before the limit, the options before
     # the planes, the planes before the modes
-    assert "radius" in both(cam, opts, occ_opts(samples=0, radius=-1.0), pl)[1]
+    assert both(cam, opts, occ_opts(samples=0, radius=-1.0), pl)[1] == "occlusion radius -1: a finite length above 0"
     assert both(cam, opts, occ_opts(samples=65, radius=0.0), pl)[0] == _abi.ERR_INVALID_ARG
     st, msg = both(cam, opts, occ_opts(samples=65, reserved=3), pl)
-    assert st == _abi.ERR_INVALID_ARG and "reserved" in msg
+    assert st == _abi.ERR_INVALID_ARG and msg == "c2rt_occlusion_opts.reserved is 3: must be 0"
     assert both(cam, opts, occ_opts(samples=65), None)[0] == _abi.ERR_LIMIT
-    assert "null occlusion options" in both(cam, opts, None, None)[1]
+    assert both(cam, opts, None, None)[1] == "null occlusion options"
     st, msg = both(cam, opts, good, None)
-    assert st == _abi.ERR_INVALID_ARG and "null planes" in msg
+    assert st == _abi.ERR_INVALID_ARG and msg == "null planes"
     st, msg = both(cam, opts, good, none)
-    assert st == _abi.ERR_INVALID_ARG and "all four" in msg
+    assert st == _abi.ERR_INVALID_ARG and msg == "no plane asked for: all four pointers of c2rt_occlusion_planes are null"
     assert both(dof, opts, good, none)[0] == _abi.ERR_INVALID_ARG
     assert both(dof, opts, occ_opts(samples=65), pl)[0] == _abi.ERR_LIMIT
     # then the modes in which a pixel is not one ray
-    for c, o, cause in [(dof, opts, "depth of field"), (copy_cam(stereo_separation=0.5), opts, "stereo"),
-                        (cam, copy_opts(count_rays=1), "count_rays"), (cam, copy_opts(prepass_bucket=48), "prepass_bucket")]:
+    for c, o, cause in [(dof, opts, "depth of field: a pixel's occlusion is one ray's, a lens has many per pixel"),
+                        (copy_cam(stereo_separation=0.5), opts, "stereo: a pixel's occlusion is one ray's, a stereo camera has two per pixel"),
+                        (cam, copy_opts(count_rays=1), "count_rays: the occlusion planes do not count rays"),
+                        (cam, copy_opts(prepass_bucket=48), "prepass_bucket: a preview's pixels share the sample of their block")]:
         st, msg = both(c, o, good, pl)
-        assert st == _abi.ERR_UNSUPPORTED and cause in msg, (cause, st, msg)
-    assert "depth of field" in both(copy_cam(dof=1, num_samples=4, stereo_separation=0.5), copy_opts(count_rays=1), good, pl)[1]
+        assert st == _abi.ERR_UNSUPPORTED and msg == cause, (cause, st, msg)
+    assert both(copy_cam(dof=1, num_samples=4, stereo_separation=0.5), copy_opts(count_rays=1), good, pl)[1] == "depth of field: a pixel's occlusion is one ray's, a lens has many per pixel"
     fresh = c2.Context(0)
     try:
         a = (C.byref(cam), C.byref(opts))
@@ -443,16 +445,16 @@ def test_ray_refusals_leave_the_outputs_untouched(gpu_ctx):
         assert fn(gpu_ctx.handle, rp, _abi.MAX_RAYS + 1, None, None, *tail) == _abi.ERR_LIMIT      # the limit before the options
         assert "rays in one call" in last_error(gpu_ctx)
         assert fn(gpu_ctx.handle, rp, n, None, C.byref(pl), *tail) == _abi.ERR_INVALID_ARG
-        assert "null occlusion options" in last_error(gpu_ctx)
+        assert last_error(gpu_ctx) == "null occlusion options"
         for kw, status, text in BAD_OCC:
             occ = occ_opts(**{**dict(samples=K, radius=oc.RADIUS[name]), **kw})
-            assert fn(gpu_ctx.handle, rp, n, C.byref(occ), C.byref(pl), *tail) == status and text in last_error(gpu_ctx), (kw, last_error(gpu_ctx))
-        assert fn(gpu_ctx.handle, rp, n, C.byref(bad), None, *tail) == _abi.ERR_INVALID_ARG and "radius" in last_error(gpu_ctx)
+            assert fn(gpu_ctx.handle, rp, n, C.byref(occ), C.byref(pl), *tail) == status and last_error(gpu_ctx) == text, (kw, last_error(gpu_ctx))
+        assert fn(gpu_ctx.handle, rp, n, C.byref(bad), None, *tail) == _abi.ERR_INVALID_ARG and last_error(gpu_ctx) == "occlusion radius -1: a finite length above 0"
         assert fn(gpu_ctx.handle, rp, n, C.byref(occ_opts(samples=65)), None, *tail) == _abi.ERR_LIMIT   # the options before the planes
         assert fn(gpu_ctx.handle, rp, n, C.byref(good), None, *tail) == _abi.ERR_INVALID_ARG
-        assert "null planes" in last_error(gpu_ctx)
+        assert last_error(gpu_ctx) == "null planes"
         assert fn(gpu_ctx.handle, rp, n, C.byref(good), C.byref(none), *tail) == _abi.ERR_INVALID_ARG
-        assert "all four" in last_error(gpu_ctx)
+        assert last_error(gpu_ctx) == "no plane asked for: all four pointers of c2rt_occlusion_planes are null"
     fresh = c2.Context(0)
     try:
         fn = L.c2rt_trace_rays_occlusion
