@@ -19,19 +19,16 @@ import chess2rt_amd as c2
 from aa_reference import needs_aa, tile_counts
 from chess2rt_amd import _abi
 from golden_configs import SCENES
+from query_test_util import DeviceBytes, frame_and_mask, hip_runtime, holds, last_error, lib, untouched, with_fields
+from query_test_util import float_bits as bits
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
-GUARD = 64               # extra elements behind both outputs
+GUARD = 64               # extra bytes behind the device outputs, extra elements behind the host outputs
 COMPOSITION = [("lecture5.sdl", 67, 45), ("csg_corner.sdl", 96, 72), ("csg_stress.sdl", 96, 72), ("lecture4.sdl", 160, 120),
                ("lecture4-proc-texture.sdl", 61, 47)]
 _cases = {}
 _tile_classes = {}
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint8)
 
 
 def make_scene(scene_file, width, height):
@@ -67,60 +64,15 @@ def assert_composition(frame, mask, one, five, want_mask, what):
     assert bits(frame)[~m].tobytes() == bits(one)[~m].tobytes(), "%s: unflagged pixels differ from the one-tap frame" % (what,)
 
 
-def guarded(width, height):
-    n = width * height
-    return (np.full(n * 3 * 4 + GUARD * 4, SENTINEL, dtype=np.uint8), np.full(n + GUARD, SENTINEL, dtype=np.uint8))
-
-
 def raw_call(ctx, cam, opts, threshold, frame_buf, mask_buf, stop=None):
-    lib = _abi.load_library()
-    return lib.c2rt_render_frame_adaptive(ctx.handle, C.byref(cam) if cam is not None else None, C.byref(opts) if opts is not None else None,
+    return lib().c2rt_render_frame_adaptive(ctx.handle, C.byref(cam) if cam is not None else None, C.byref(opts) if opts is not None else None,
                                           threshold, frame_buf.ctypes.data if frame_buf is not None else None,
                                           mask_buf.ctypes.data if mask_buf is not None else None,
                                           stop.ctypes.data if stop is not None else None)
 
 
 def raw_device_call(ctx, cam, opts, threshold, out_ptr, mask_ptr, stream=None):
-    lib = _abi.load_library()
-    return lib.c2rt_render_frame_adaptive_device(ctx.handle, C.byref(cam), C.byref(opts), threshold, out_ptr, mask_ptr, stream)
-
-
-def hip_runtime():
-    """the HIP runtime the library is linked against, reached through the library's own handle (a second copy of the
-    runtime, as C.CDLL("libamdhip64.so") can map, must not be handed the first one's streams or pointers)"""
-    hip = _abi.load_library()
-    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    hip.hipStreamDestroy.argtypes = [C.c_void_p]
-    hip.hipStreamSynchronize.argtypes = [C.c_void_p]
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipFree.argtypes = [C.c_void_p]
-    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return hip
-
-
-class DeviceBytes:
-    """`nbytes` of device memory filled with SENTINEL"""
-
-    def __init__(self, nbytes):
-        self.hip, self.nbytes, self.ptr = hip_runtime(), nbytes, C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(self.ptr), nbytes) == 0
-        assert self.hip.hipMemset(self.ptr, SENTINEL, nbytes) == 0
-        assert self.hip.hipDeviceSynchronize() == 0
-
-    def get(self):
-        out = np.empty(self.nbytes, dtype=np.uint8)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, 2) == 0     # hipMemcpyDeviceToHost
-        return out
-
-    def free(self):
-        if self.ptr:
-            assert self.hip.hipFree(self.ptr) == 0
-            self.ptr = C.c_void_p()
-
-
-def untouched(*bufs):
-    return all((b == SENTINEL).all() for b in bufs)
+    return lib().c2rt_render_frame_adaptive_device(ctx.handle, C.byref(cam), C.byref(opts), threshold, out_ptr, mask_ptr, stream)
 
 
 # The messages every adaptive call shares (the library builds them in one place), whole: a cause listed here is compared
@@ -137,10 +89,6 @@ WHOLE = {
     "strip_world": "strip_world > 1: the rows above and below a strip belong to other ranks",
     "multi-device": "multi-device context: the rows above and below a strip are on other devices",
 }
-
-
-def last_error(ctx):
-    return _abi.load_library().c2rt_last_error(ctx.handle).decode(errors="replace")
 
 
 # ---- 1: composition ------------------------------------------------------------------------------------------------------
@@ -204,11 +152,11 @@ def test_threshold(gpu_ctx):
     assert (masks[0.02] <= masks[0.0]).all() and (none <= masks[0.02]).all()
     assert (masks[_abi.AA_THRESHOLD_REF] <= masks[0.02]).all()
     assert 0 < int(masks[0.02].sum()) < int(masks[0.0].sum())
-    fbuf, mbuf = guarded(67, 45)
+    fbuf, mbuf = frame_and_mask(67 * 45, guard_elems=GUARD)
     for bad in (-1.0, float("nan")):
         assert raw_call(gpu_ctx, cam, opts, bad, fbuf, mbuf) == _abi.ERR_INVALID_ARG, bad
         assert "threshold" in last_error(gpu_ctx)
-        assert untouched(fbuf, mbuf), bad
+        assert untouched((fbuf, mbuf)), bad
 
 
 # ---- 4: edges ---------------------------------------------------------------------------------------------------------------
@@ -221,13 +169,13 @@ def test_edges(gpu_ctx, width, height):
     # the reference's threshold, and two at which the small frames have flags as well (9x1 and 1x9 have none at 0.1)
     for thr in (_abi.AA_THRESHOLD_REF, 0.02, 0.0):
         want_mask = needs_aa(one, thr)
-        fbuf, mbuf = guarded(width, height)
+        fbuf, mbuf = frame_and_mask(width * height, guard_elems=GUARD)
         assert raw_call(gpu_ctx, cam, opts, thr, fbuf, mbuf) == _abi.OK, last_error(gpu_ctx)
         mask = mbuf[:n].reshape(height, width)
         assert ((mask == 0) | (mask == 1)).all(), (width, height, thr)
         frame = fbuf[:n * 12].view(np.float32).reshape(height, width, 3)
         assert_composition(frame, mask, one, five, want_mask, "%dx%d at %g" % (width, height, thr))
-        assert (fbuf[n * 12:] == SENTINEL).all() and (mbuf[n:] == SENTINEL).all(), (width, height, thr)
+        assert untouched((fbuf[n * 12:], mbuf[n:])), (width, height, thr)
     if (width, height) != (1, 1):
         assert needs_aa(one, 0.0).any(), (width, height)
 
@@ -241,19 +189,13 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
     n = width * height
 
     def copy_cam(**kw):
-        c = _abi.CameraFrame.from_buffer_copy(cam)
-        for k, v in kw.items():
-            setattr(c, k, v)
-        return c
+        return with_fields(cam, **kw)
 
     def copy_opts(**kw):
-        o = _abi.RenderOpts.from_buffer_copy(opts)
-        for k, v in kw.items():
-            setattr(o, k, v)
-        return o
+        return with_fields(opts, **kw)
 
     fdev, mdev = DeviceBytes(n * 12 + GUARD), DeviceBytes(n + GUARD)
-    fbuf, mbuf = guarded(width, height)
+    fbuf, mbuf = frame_and_mask(width * height, guard_elems=GUARD)
     thr = _abi.AA_THRESHOLD_REF
 
     def refused(ctx, c, o, t, status, cause, host_frame=fbuf, dev_frame=fdev.ptr, dev_mask=mdev.ptr, host=True):
@@ -263,7 +205,7 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
         assert raw_device_call(ctx, c, o, t, dev_frame, dev_mask) == status, cause
         assert last_error(ctx) == WHOLE[cause] if cause in WHOLE else cause in last_error(ctx), (cause, last_error(ctx))
         assert hip_runtime().hipDeviceSynchronize() == 0
-        assert untouched(fbuf, mbuf, fdev.get(), mdev.get()), cause
+        assert untouched((fbuf, mbuf, fdev.get(), mdev.get())), cause
 
     # a frame call's own statuses come first: a bad size wins over a bad tap mode for this call
     refused(gpu_ctx, cam, copy_opts(width=0, taps=_abi.TAPS_1), thr, _abi.ERR_INVALID_ARG, "")
@@ -296,16 +238,16 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
     # a stop request before the launches
     stop = np.ones(1, dtype=np.uint8)
     assert raw_call(gpu_ctx, cam, opts, thr, fbuf, mbuf, stop) == _abi.ERR_CANCELLED
-    assert untouched(fbuf, mbuf)
+    assert untouched((fbuf, mbuf))
     # afterwards the same context renders a correct adaptive frame, with and without the (nullable) host mask
     stop[0] = 0
     assert raw_call(gpu_ctx, cam, opts, thr, fbuf, mbuf, stop) == _abi.OK, last_error(gpu_ctx)
     want_mask = needs_aa(one, thr)
     frame = fbuf[:n * 12].view(np.float32).reshape(height, width, 3)
     assert_composition(frame, mbuf[:n].reshape(height, width), one, five, want_mask, "after the refusals")
-    fbuf2, mbuf2 = guarded(width, height)
+    fbuf2, mbuf2 = frame_and_mask(width * height, guard_elems=GUARD)
     assert raw_call(gpu_ctx, cam, opts, thr, fbuf2, None) == _abi.OK, last_error(gpu_ctx)
-    assert fbuf2.tobytes() == fbuf.tobytes() and untouched(mbuf2)
+    assert fbuf2.tobytes() == fbuf.tobytes() and untouched((mbuf2,))
     fdev.free()
     mdev.free()
 
@@ -333,12 +275,8 @@ def test_streams(gpu_ctx):
     assert hip.hipStreamSynchronize(stream) == 0
     assert hip.hipStreamDestroy(stream) == 0          # the library keeps no reference to it
     for f, m, wf, wm in ((f1, m1, want_frame, want_mask), (f2, m2, want_frame2, want_mask2)):
-        got_f, got_m = f.get(), m.get()
-        assert got_m[:n].tobytes() == wm.tobytes()
-        assert got_f[:n * 12].tobytes() == bits(wf).tobytes()
-        assert (got_f[n * 12:] == SENTINEL).all() and (got_m[n:] == SENTINEL).all()
-    got = plain.get()
-    assert got[:n * 12].tobytes() == bits(five).tobytes() and (got[n * 12:] == SENTINEL).all()
+        assert holds(m.get(), wm) and holds(f.get(), wf)
+    assert holds(plain.get(), five)
     for b in (f1, m1, f2, m2, plain):
         b.free()
     frame, mask = gpu_ctx.renderFrameAdaptive(cam, opts)

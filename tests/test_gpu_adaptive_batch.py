@@ -19,27 +19,13 @@ import chess2rt_amd as c2
 import scene_update_util as U
 from aa_reference import needs_aa, tile_counts
 from chess2rt_amd import _abi
+from query_test_util import DeviceBytes, frame_and_mask, hip_runtime, holds, last_error, lib, same, scratch_ctx, untouched, with_fields
+from query_test_util import float_bits as bits
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 0xA5
 GUARD = 64               # extra bytes behind both outputs
 THR = _abi.AA_THRESHOLD_REF
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint8)
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-@pytest.fixture(scope="module")
-def scratch_ctx():
-    ctx = c2.Context(0)
-    yield ctx
-    ctx.close()
 
 
 def file_scene(name, size):
@@ -254,45 +240,8 @@ def test_a_threshold_nothing_reaches(gpu_ctx):
 # ---- the raw entry points ---------------------------------------------------------------------------------------------------
 
 
-def hip_runtime():
-    """the HIP runtime the library is linked against, reached through the library's own handle"""
-    hip = _abi.load_library()
-    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    hip.hipStreamDestroy.argtypes = [C.c_void_p]
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipFree.argtypes = [C.c_void_p]
-    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return hip
-
-
-class DeviceBytes:
-    """`nbytes` of device memory filled with SENTINEL, allocated by the library's own runtime"""
-
-    def __init__(self, nbytes):
-        self.hip, self.nbytes, self.ptr = hip_runtime(), nbytes, C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(self.ptr), nbytes) == 0
-        assert self.hip.hipMemset(self.ptr, SENTINEL, nbytes) == 0
-        assert self.hip.hipDeviceSynchronize() == 0
-
-    def get(self):
-        out = np.empty(self.nbytes, dtype=np.uint8)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, 2) == 0     # hipMemcpyDeviceToHost
-        return out
-
-    def free(self):
-        if self.ptr:
-            assert self.hip.hipFree(self.ptr) == 0
-            self.ptr = C.c_void_p()
-
-
 def host_bufs(n, width, height):
-    px = n * width * height
-    return np.full(px * 12 + GUARD, SENTINEL, dtype=np.uint8), np.full(px + GUARD, SENTINEL, dtype=np.uint8)
-
-
-def untouched(*bufs):
-    return all((b == SENTINEL).all() for b in bufs)
+    return frame_and_mask(n * width * height, guard_bytes=GUARD)
 
 
 # The messages every adaptive call shares (the library builds them in one place), whole: a cause listed here is compared
@@ -306,10 +255,6 @@ WHOLE = {
 }
 
 
-def last_error(ctx):
-    return _abi.load_library().c2rt_last_error(ctx.handle).decode(errors="replace")
-
-
 def addr(buf):
     if buf is None:
         return None
@@ -319,10 +264,9 @@ def addr(buf):
 def raw(ctx, cams, n, opts, thr, out, mask, poses=None, posed=False, device=False, tail=None):
     """one of the four entry points: cams / poses ctypes arrays or None, out / mask numpy arrays, device pointers or None;
     tail: the stop flag (host) or the stream (device)"""
-    lib = _abi.load_library()
     name = "c2rt_render_frames%s_adaptive%s" % ("_posed" if posed else "", "_device" if device else "")
     args = [ctx.handle, cams] + ([poses] if posed else []) + [n, C.byref(opts) if opts is not None else None, thr, addr(out), addr(mask), addr(tail)]
-    return getattr(lib, name)(*args)
+    return getattr(lib(), name)(*args)
 
 
 def unpack(fbuf, mbuf, n, width, height):
@@ -360,7 +304,7 @@ def test_no_frame_and_one_frame_too_many(gpu_ctx):
             assert raw(gpu_ctx, arr, 257, o5, THR, out, mask, parr, posed, device) == _abi.ERR_LIMIT
             assert "257 frames" in last_error(gpu_ctx)
     assert hip_runtime().hipDeviceSynchronize() == 0
-    assert untouched(fbuf, mbuf, fdev.get(), mdev.get())
+    assert untouched((fbuf, mbuf, fdev.get(), mdev.get()))
     fdev.free()
     mdev.free()
     frames, masks = gpu_ctx.renderFramesAdaptive([], o5)
@@ -383,7 +327,7 @@ def test_256_frames(gpu_ctx):
     assert raw(gpu_ctx, arr, 256, o5, THR, fbuf, mbuf) == _abi.OK, last_error(gpu_ctx)
     frames, masks = unpack(fbuf, mbuf, 256, 24, 16)
     assert_composition(frames, masks, one, five, want, "256 frames")
-    assert untouched(fbuf[256 * 384 * 12:], mbuf[256 * 384:])
+    assert untouched((fbuf[256 * 384 * 12:], mbuf[256 * 384:]))
     assert_single_frames(gpu_ctx, cams, o5, frames, masks, "256 frames")
 
 
@@ -405,7 +349,7 @@ def test_frame_sizes(gpu_ctx, width, height):
         frames, masks = unpack(fbuf, mbuf, 2, width, height)
         assert ((masks == 0) | (masks == 1)).all(), (width, height, thr)
         assert_composition(frames, masks, one, five, want, "%dx%d at %g" % (width, height, thr))
-        assert untouched(fbuf[px * 12:], mbuf[px:]), (width, height, thr)
+        assert untouched((fbuf[px * 12:], mbuf[px:])), (width, height, thr)
         assert_single_frames(gpu_ctx, cams, o5, frames, masks, "%dx%d at %g" % (width, height, thr), thr)
     if (width, height) != (1, 1):
         assert needs_aa(one[0], 0.0).any(), (width, height)
@@ -430,16 +374,10 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
     fdev, mdev = DeviceBytes(fbuf.nbytes), DeviceBytes(mbuf.nbytes)
 
     def cams_with(**kw):
-        c = _abi.CameraFrame.from_buffer_copy(cams[1])
-        for k, v in kw.items():
-            setattr(c, k, v)
-        return (_abi.CameraFrame * n)(cams[0], c, cams[2])
+        return (_abi.CameraFrame * n)(cams[0], with_fields(cams[1], **kw), cams[2])
 
     def opts_with(**kw):
-        o = _abi.RenderOpts.from_buffer_copy(o5)
-        for k, v in kw.items():
-            setattr(o, k, v)
-        return o
+        return with_fields(o5, **kw)
 
     def refused(status, cause, cc=arr, oo=o5, thr=THR, poses=good, null_out=False, null_mask=False, host=True, plain=True):
         for posed in ((False, True) if plain else (True,)):
@@ -449,7 +387,7 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
                 assert got == status, (cause, posed, device, got, last_error(gpu_ctx))
                 assert last_error(gpu_ctx) == WHOLE[cause] if cause in WHOLE else cause in last_error(gpu_ctx), (cause, posed, device, last_error(gpu_ctx))
         assert hip_runtime().hipDeviceSynchronize() == 0
-        assert untouched(fbuf, mbuf, fdev.get(), mdev.get()), cause
+        assert untouched((fbuf, mbuf, fdev.get(), mdev.get())), cause
 
     refused(_abi.ERR_INVALID_ARG, "null cameras", cc=None)
     refused(_abi.ERR_INVALID_ARG, "null cameras", oo=None)
@@ -475,7 +413,7 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
     stop = np.ones(1, dtype=np.uint8)
     for posed in (False, True):
         assert raw(gpu_ctx, arr, n, o5, THR, fbuf, mbuf, good, posed, False, stop) == _abi.ERR_CANCELLED
-        assert "stop requested" in last_error(gpu_ctx) and untouched(fbuf, mbuf)
+        assert "stop requested" in last_error(gpu_ctx) and untouched((fbuf, mbuf))
     stop[0] = 0
     # afterwards the same context renders the batch, and nothing lands behind frame n - 1 or mask n - 1
     px = n * width * height
@@ -484,7 +422,7 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
     assert raw(gpu_ctx, arr, n, o5, THR, fbuf, mbuf, tail=stop) == _abi.OK, last_error(gpu_ctx)
     frames, masks = unpack(fbuf, mbuf, n, width, height)
     assert_composition(frames, masks, one, five, want, "after the refusals")
-    assert untouched(fbuf[px * 12:], mbuf[px:])
+    assert untouched((fbuf[px * 12:], mbuf[px:]))
     assert raw(gpu_ctx, arr, n, o5, THR, fdev.ptr, mdev.ptr, device=True) == _abi.OK, last_error(gpu_ctx)
     assert hip_runtime().hipDeviceSynchronize() == 0
     assert fdev.get().tobytes() == fbuf.tobytes() and mdev.get().tobytes() == mbuf.tobytes()
@@ -493,7 +431,7 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
         fbuf2, mbuf2 = host_bufs(n, width, height)
         none = (_abi.ScenePose * n)()        # both counts 0: frames of the scene as it is
         assert raw(gpu_ctx, arr, n, o5, THR, fbuf2, None, none, posed) == _abi.OK, last_error(gpu_ctx)
-        assert fbuf2.tobytes() == fbuf.tobytes() and untouched(mbuf2)
+        assert fbuf2.tobytes() == fbuf.tobytes() and untouched((mbuf2,))
     # the posed variants into guarded buffers
     posed_one, posed_five = gpu_ctx.renderFramesPosed(cams, good, o1), gpu_ctx.renderFramesPosed(cams, good, o5)
     posed_want = [needs_aa(f, THR) for f in posed_one]
@@ -502,7 +440,7 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
     assert raw(gpu_ctx, arr, n, o5, THR, fbuf3, mbuf3, good, True) == _abi.OK, last_error(gpu_ctx)
     frames, masks = unpack(fbuf3, mbuf3, n, width, height)
     assert_composition(frames, masks, posed_one, posed_five, posed_want, "posed, after the refusals")
-    assert untouched(fbuf3[px * 12:], mbuf3[px:])
+    assert untouched((fbuf3[px * 12:], mbuf3[px:]))
     assert raw(gpu_ctx, arr, n, o5, THR, fdev3.ptr, mdev3.ptr, good, True, True) == _abi.OK, last_error(gpu_ctx)
     assert hip_runtime().hipDeviceSynchronize() == 0
     assert fdev3.get().tobytes() == fbuf3.tobytes() and mdev3.get().tobytes() == mbuf3.tobytes()
@@ -537,10 +475,7 @@ def test_streams(gpu_ctx):
     assert hip.hipDeviceSynchronize() == 0
     assert hip.hipStreamDestroy(s1) == 0 and hip.hipStreamDestroy(s2) == 0      # the library keeps no reference to them
     for (f, m), (wf, wm) in zip(bufs, (want_a, want_b, want_c)):
-        got_f, got_m = f.get(), m.get()
-        assert got_m[:px].tobytes() == wm.tobytes()
-        assert got_f[:px * 12].tobytes() == bits(wf).tobytes()
-        assert untouched(got_f[px * 12:], got_m[px:])
+        assert holds(m.get(), wm) and holds(f.get(), wf)
         f.free()
         m.free()
     again = gpu_ctx.renderFramesAdaptive(cams, o5)

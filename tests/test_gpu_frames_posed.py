@@ -12,21 +12,11 @@ import pytest
 import chess2rt_amd as c2
 import scene_update_util as U
 from chess2rt_amd import _abi
+from query_test_util import same, scratch_ctx
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def same(a, b):
-    return a.shape == b.shape and a.tobytes() == b.tobytes()
-
-
-@pytest.fixture(scope="module")
-def scratch_ctx():
-    ctx = c2.Context(0)
-    yield ctx
-    ctx.close()
 
 
 def _lecture5(size=(100, 52)):

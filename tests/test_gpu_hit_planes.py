@@ -13,13 +13,12 @@ import chess2rt_amd as c2
 from chess2rt_amd import _abi
 from chess2rt_amd.api import HIT_PLANES, RAY_HIT_DTYPE
 from golden_configs import SCENES
+from query_test_util import HITS, check_device_against_host, check_filled, check_strips, device_planes, guarded, last_error, raw_call, untouched, with_fields
 from ray_query_util import assert_records_match_oracle, bits, oracle_trace, record_from_trace_result, screen_rays
 
 pytestmark = pytest.mark.gpu
 
 W, H = 61, 47
-SENTINEL = 0xA5
-GUARD = 64               # extra elements behind every plane
 PLANES = tuple(HIT_PLANES)
 # the set-up of test_gpu_ray_queries.test_a_frames_own_rays_reproduce_the_frame: the file's camera with its pitch raised
 # so that at least a tenth of the rays leave the scene while every node is still some ray's closest
@@ -74,34 +73,6 @@ def records_of(pl):
     return rec
 
 
-def plane_bytes(name, pixels):
-    dtype, comps = HIT_PLANES[name]
-    return pixels * comps * np.dtype(dtype).itemsize
-
-
-def guarded(names, pixels):
-    """{name: byte buffer of the plane plus GUARD elements, all SENTINEL}"""
-    return {n: np.full(plane_bytes(n, pixels) + GUARD * np.dtype(HIT_PLANES[n][0]).itemsize, SENTINEL, dtype=np.uint8) for n in names}
-
-
-def raw_call(ctx, cam, opts, bufs, null_struct=False):
-    """c2rt_render_hits through the raw entry point: planes not in `bufs` are passed as null"""
-    lib = _abi.load_library()
-    pl = _abi.HitPlanes()
-    for n, b in bufs.items():
-        setattr(pl, n, b.ctypes.data)
-    return lib.c2rt_render_hits(ctx.handle, C.byref(cam) if cam is not None else None, C.byref(opts) if opts is not None else None,
-                                None if null_struct else C.byref(pl))
-
-
-def untouched(bufs):
-    return all((b == SENTINEL).all() for b in bufs.values())
-
-
-def last_error(ctx):
-    return _abi.load_library().c2rt_last_error(ctx.handle).decode(errors="replace")
-
-
 # ---- 1: the planes are the frame's own rays ------------------------------------------------------------------------
 
 
@@ -140,12 +111,9 @@ def test_edges(gpu_ctx, height):
         gpu_ctx.uploadScene(scene.desc)
         rec, rgb = gpu_ctx.traceRays(screen_rays(cam, width, height))
         n = width * height
-        bufs = guarded(PLANES, n)
-        assert raw_call(gpu_ctx, cam, opts, bufs) == _abi.OK, last_error(gpu_ctx)
-        for name in PLANES:
-            nb = plane_bytes(name, n)
-            assert bufs[name][:nb].tobytes() == bits(field_of(name, rec, rgb)).tobytes(), (width, height, name)
-            assert (bufs[name][nb:] == SENTINEL).all(), (width, height, name)
+        bufs = guarded(HIT_PLANES, PLANES, n)
+        assert raw_call(HITS, gpu_ctx, bufs, cam, opts) == _abi.OK, last_error(gpu_ctx)
+        check_filled(HIT_PLANES, bufs, {name: field_of(name, rec, rgb) for name in PLANES}, n, (width, height))
 
 
 # ---- 3: plane subsets --------------------------------------------------------------------------------------------------
@@ -157,13 +125,10 @@ def test_plane_subsets(gpu_ctx, subset):
     gpu_ctx.uploadScene(scene.desc)
     full = gpu_ctx.renderHits(cam, opts)
     n = W * H
-    bufs = guarded(subset, n)
+    bufs = guarded(HIT_PLANES, subset, n)
     # what is not asked for is null in the struct; the buffers passed sit in one allocation each with their guards
-    assert raw_call(gpu_ctx, cam, opts, bufs) == _abi.OK, last_error(gpu_ctx)
-    for name in subset:
-        nb = plane_bytes(name, n)
-        assert bufs[name][:nb].tobytes() == bits(full[name]).tobytes(), (subset, name)
-        assert (bufs[name][nb:] == SENTINEL).all(), (subset, name)
+    assert raw_call(HITS, gpu_ctx, bufs, cam, opts) == _abi.OK, last_error(gpu_ctx)
+    check_filled(HIT_PLANES, bufs, full, n, subset, subset)
     got = gpu_ctx.renderHits(cam, opts, planes=subset)
     assert set(got) == set(subset)
     for name in subset:
@@ -181,17 +146,7 @@ def test_strips(gpu_ctx, world):
     names = ("node", "dist", "normal", "rgb")
     full = gpu_ctx.renderHits(cam, opts, planes=names)
     assert 0 < int((full["node"] >= 0).sum()) < sw * sh
-    seen = np.zeros(sh, dtype=int)
-    for rank in range(world):
-        o = scene.renderOpts(taps=_abi.TAPS_1, strip_height=strip, strip_rank=rank, strip_world=world)
-        rows = [y for y in range(sh) if (y // strip) % world == rank]
-        assert gpu_ctx.localRows(o) == len(rows)
-        got = gpu_ctx.renderHits(cam, o, planes=names)
-        for name in names:
-            assert got[name].shape[0] == len(rows)
-            assert bits(got[name]).tobytes() == bits(full[name][rows]).tobytes(), (world, rank, name)
-        seen[rows] += 1
-    assert (seen == 1).all()
+    check_strips(gpu_ctx, scene, lambda o: gpu_ctx.renderHits(cam, o, planes=names), full, sh, world, strip, names, world)
 
 
 # ---- 5: no hit -------------------------------------------------------------------------------------------------------
@@ -222,21 +177,15 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
     n = W * H
 
     def copy_cam(**kw):
-        c = _abi.CameraFrame.from_buffer_copy(cam)
-        for k, v in kw.items():
-            setattr(c, k, v)
-        return c
+        return with_fields(cam, **kw)
 
     def copy_opts(**kw):
-        o = _abi.RenderOpts.from_buffer_copy(opts)
-        for k, v in kw.items():
-            setattr(o, k, v)
-        return o
+        return with_fields(opts, **kw)
 
-    bufs = guarded(PLANES, n)
-    assert raw_call(gpu_ctx, cam, opts, bufs, null_struct=True) == _abi.ERR_INVALID_ARG
+    bufs = guarded(HIT_PLANES, PLANES, n)
+    assert raw_call(HITS, gpu_ctx, bufs, cam, opts, null_struct=True) == _abi.ERR_INVALID_ARG
     assert last_error(gpu_ctx) == "null planes"
-    assert raw_call(gpu_ctx, cam, opts, {}) == _abi.ERR_INVALID_ARG
+    assert raw_call(HITS, gpu_ctx, {}, cam, opts) == _abi.ERR_INVALID_ARG
     assert last_error(gpu_ctx) == "no plane asked for: all seven pointers of c2rt_hit_planes are null"
     cases = [(copy_cam(dof=1, num_samples=4), opts, "depth of field: a pixel's record is one ray's, a lens has many per pixel"),
              (copy_cam(stereo_separation=0.5), opts, "stereo: a pixel's record is one ray's, a stereo camera has two per pixel"),
@@ -244,7 +193,7 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
              (cam, copy_opts(prepass_bucket=48), "prepass_bucket: a preview's pixels share the sample of their block")]
     lib = _abi.load_library()
     for c, o, cause in cases:
-        assert raw_call(gpu_ctx, c, o, bufs) == _abi.ERR_UNSUPPORTED, cause
+        assert raw_call(HITS, gpu_ctx, bufs, c, o) == _abi.ERR_UNSUPPORTED, cause
         assert last_error(gpu_ctx) == cause, (cause, last_error(gpu_ctx))
         assert untouched(bufs), cause
         # the device variant decides the same before it enqueues anything (the pointers are never used)
@@ -254,28 +203,18 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
         assert last_error(gpu_ctx) == cause
     fresh = c2.Context(0)
     try:
-        assert raw_call(fresh, cam, opts, bufs) == _abi.ERR_NO_SCENE
+        assert raw_call(HITS, fresh, bufs, cam, opts) == _abi.ERR_NO_SCENE
         assert "no scene" in last_error(fresh)
     finally:
         fresh.close()
     assert untouched(bufs)
     # afterwards the same context renders a correct plane set
     rec, rgb = gpu_ctx.traceRays(rays)
-    assert raw_call(gpu_ctx, cam, opts, bufs) == _abi.OK
-    for name in PLANES:
-        nb = plane_bytes(name, n)
-        assert bufs[name][:nb].tobytes() == bits(field_of(name, rec, rgb)).tobytes(), name
-        assert (bufs[name][nb:] == SENTINEL).all(), name
+    assert raw_call(HITS, gpu_ctx, bufs, cam, opts) == _abi.OK
+    check_filled(HIT_PLANES, bufs, {name: field_of(name, rec, rgb) for name in PLANES}, n, "after the refusals")
 
 
 # ---- 7: streams and slots -------------------------------------------------------------------------------------------
-
-
-def device_planes(torch, dev, n):
-    t = {}
-    for name in PLANES:
-        t[name] = torch.full((plane_bytes(name, n) + GUARD,), SENTINEL, dtype=torch.uint8, device=dev)
-    return t
 
 
 def test_streams_and_slots(gpu_ctx):
@@ -288,22 +227,18 @@ def test_streams_and_slots(gpu_ctx):
     want_frame = gpu_ctx.renderFrame(cam, opts)
     dev = torch.device("cuda:0")
     s1 = torch.cuda.Stream(dev)
-    t = device_planes(torch, dev, n)
+    t = device_planes(HIT_PLANES, n, dev, guard_bytes=64)
     frame_t = torch.full((H, W, 3), -1.0, dtype=torch.float32, device=dev)
     torch.cuda.synchronize()
     gpu_ctx.renderHitsDevice(cam, opts, {k: v.data_ptr() for k, v in t.items()}, s1.cuda_stream)
     gpu_ctx.renderFrameDevice(cam, opts, frame_t.data_ptr(), s1.cuda_stream)
     s1.synchronize()
-    for name in PLANES:
-        got = t[name].cpu().numpy()
-        nb = plane_bytes(name, n)
-        assert got[:nb].tobytes() == bits(want[name]).tobytes(), name
-        assert (got[nb:] == SENTINEL).all(), name
+    check_device_against_host(HIT_PLANES, t, want, n, "own stream")
     assert bits(frame_t.cpu().numpy()).tobytes() == bits(want_frame).tobytes()
     two = c2.Context(devices=[0, 0])
     try:
         two.uploadScene(scene.desc)
-        t2 = device_planes(torch, dev, n)
+        t2 = device_planes(HIT_PLANES, n, dev, guard_bytes=64)
         torch.cuda.synchronize()
         two.renderHitsDevice(cam, opts, {k: v.data_ptr() for k, v in t2.items()}, s1.cuda_stream)
         s1.synchronize()
@@ -356,13 +291,9 @@ def test_host_chunks_of_a_frame_equal_the_device_call(gpu_ctx):
     host = gpu_ctx.renderHits(cam, opts)
     dev = torch.device("cuda:0")
     s1 = torch.cuda.Stream(dev)
-    t = device_planes(torch, dev, w * h)
+    t = device_planes(HIT_PLANES, w * h, dev, guard_bytes=64)
     torch.cuda.synchronize()
     gpu_ctx.renderHitsDevice(cam, opts, {k: v.data_ptr() for k, v in t.items()}, s1.cuda_stream)
     s1.synchronize()
-    for name in PLANES:
-        got = t[name].cpu().numpy()
-        nb = plane_bytes(name, w * h)
-        assert got[:nb].tobytes() == bits(host[name]).tobytes(), name
-        assert (got[nb:] == SENTINEL).all(), name
+    check_device_against_host(HIT_PLANES, t, host, w * h, "640x480")
     assert 0 < int((host["node"][409:] >= 0).sum())                    # hits behind the chunk boundary

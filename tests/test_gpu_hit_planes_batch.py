@@ -15,34 +15,20 @@ import numpy as np
 import pytest
 
 import chess2rt_amd as c2
+import query_test_util as Q
 import scene_update_util as U
 from chess2rt_amd import _abi
 from chess2rt_amd.api import HIT_PLANES
+from query_test_util import SENTINEL, device_planes, fetch, free_all, last_error, lib, plane_bytes, same, scratch_ctx, struct_of, untouched, with_fields
+from ray_query_util import bits
 
 pytestmark = pytest.mark.gpu
 
 W, H = 61, 47
-SENTINEL = 0xA5
-GUARD = 64               # extra elements behind every plane
 PLANES = tuple(HIT_PLANES)
 # the cameras of tests/test_gpu_hit_planes.py: the file's camera with its pitch raised so that part of the rays leave
 # the scene while every node is still some ray's closest
 PITCH_UP = {"lecture5.sdl": 5.0, "csg_stress.sdl": 5.0, "zaphod.sdl": 40.0, "lecture4-proc-texture.sdl": 5.0}
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint8)
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
-
-
-@pytest.fixture(scope="module")
-def scratch_ctx():
-    ctx = c2.Context(0)
-    yield ctx
-    ctx.close()
 
 
 def make_scene(scene_file, width=W, height=H):
@@ -83,87 +69,15 @@ def singles(ctx, scene_file):
     return _SINGLES[scene_file]
 
 
-def plane_bytes(name, pixels):
-    dtype, comps = HIT_PLANES[name]
-    return pixels * comps * np.dtype(dtype).itemsize
-
-
-def guard_bytes(name):
-    return GUARD * np.dtype(HIT_PLANES[name][0]).itemsize
-
-
-def guarded(names, pixels):
-    """{name: host byte buffer of the plane plus GUARD elements, all SENTINEL}"""
-    return {n: np.full(plane_bytes(n, pixels) + guard_bytes(n), SENTINEL, dtype=np.uint8) for n in names}
-
-
-def hip_runtime():
-    """the HIP runtime the library is linked against, reached through the library's own handle"""
-    hip = _abi.load_library()
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipFree.argtypes = [C.c_void_p]
-    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return hip
-
-
-class DeviceBytes:
-    """`nbytes` of device memory filled with SENTINEL, allocated by the library's own runtime"""
-
-    def __init__(self, nbytes):
-        self.hip, self.nbytes, self.ptr = hip_runtime(), nbytes, C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(self.ptr), nbytes) == 0
-        assert self.hip.hipMemset(self.ptr, SENTINEL, nbytes) == 0
-        assert self.hip.hipDeviceSynchronize() == 0
-
-    def get(self):
-        out = np.empty(self.nbytes, dtype=np.uint8)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, 2) == 0     # hipMemcpyDeviceToHost
-        return out
-
-    def free(self):
-        if self.ptr:
-            assert self.hip.hipFree(self.ptr) == 0
-            self.ptr = C.c_void_p()
-
-
-def guarded_dev(names, pixels):
-    return {n: DeviceBytes(plane_bytes(n, pixels) + guard_bytes(n)) for n in names}
-
-
-def fetch(dev):
-    """the device buffers of guarded_dev copied back (after a device sync)"""
-    assert hip_runtime().hipDeviceSynchronize() == 0
-    return {n: d.get() for n, d in dev.items()}
-
-
-def free_all(dev):
-    for d in dev.values():
-        d.free()
-
-
-def untouched(bufs):
-    return all((b == SENTINEL).all() for b in bufs.values())
-
-
-def last_error(ctx):
-    return _abi.load_library().c2rt_last_error(ctx.handle).decode(errors="replace")
-
-
-def addr(b):
-    if isinstance(b, np.ndarray):
-        return b.ctypes.data
-    return b.ptr.value if isinstance(b, DeviceBytes) else b
+guarded = functools.partial(Q.guarded, HIT_PLANES)                  # 64 elements behind every plane, host and device
+guarded_dev = functools.partial(Q.guarded_device, HIT_PLANES)
 
 
 def raw(ctx, cams, n, opts, bufs, poses=None, posed=False, device=False, stream=None, null_struct=False, handle=True):
     """one of the four entry points: cams / poses ctypes arrays or None; the planes not in `bufs` ({name: host buffer,
     DeviceBytes or address}) are passed as null"""
-    lib = _abi.load_library()
-    pl = _abi.HitPlanes()
-    for name, b in bufs.items():
-        setattr(pl, name, addr(b))
-    fn = getattr(lib, "c2rt_render_frames%s_hits%s" % ("_posed" if posed else "", "_device" if device else ""))
+    pl = struct_of(_abi.HitPlanes, bufs)
+    fn = getattr(lib(), "c2rt_render_frames%s_hits%s" % ("_posed" if posed else "", "_device" if device else ""))
     args = [ctx.handle if handle else None, cams] + ([poses] if posed else []) + [n, C.byref(opts) if opts is not None else None,
                                                                                  None if null_struct else C.byref(pl)]
     return fn(*(args + ([stream] if device else [])))
@@ -172,7 +86,7 @@ def raw(ctx, cams, n, opts, bufs, poses=None, posed=False, device=False, stream=
 def assert_slices(bufs, names, n, pixels, want, what):
     """bufs[name] holds want[i][name] at slice i for i < n, then sentinel"""
     for name in names:
-        nb = plane_bytes(name, pixels)
+        nb = plane_bytes(HIT_PLANES, name, pixels)
         for i in range(n):
             assert bufs[name][i * nb:(i + 1) * nb].tobytes() == bits(want[i][name]).tobytes(), "%s: frame %d, plane %s" % (what, i, name)
         assert (bufs[name][n * nb:] == SENTINEL).all(), "%s: plane %s: written behind frame %d" % (what, name, n - 1)
@@ -355,7 +269,7 @@ def test_stream_order(gpu_ctx):
     dev = torch.device("cuda:0")
 
     def planes(n):
-        return {name: torch.full((plane_bytes(name, n * px) + guard_bytes(name),), SENTINEL, dtype=torch.uint8, device=dev) for name in PLANES}
+        return device_planes(HIT_PLANES, n * px, dev, guard_elems=64)
 
     def check(t, n, wanted, what):
         assert_slices({k: v.cpu().numpy() for k, v in t.items()}, PLANES, n, px, wanted, what)
@@ -402,12 +316,12 @@ def test_host_chunking(gpu_ctx, scene_file, width, height, n, names):
     back = fetch(dev)
     for name in names:
         assert host[name].tobytes() == back[name].tobytes(), (scene_file, name)
-        assert (host[name][plane_bytes(name, n * px):] == SENTINEL).all(), (scene_file, name)
+        assert (host[name][plane_bytes(HIT_PLANES, name, n * px):] == SENTINEL).all(), (scene_file, name)
     free_all(dev)
     # and both are the single-frame call's: the last frame, which the last chunk holds
     last = gpu_ctx.renderHits(cams[-1], opts, planes=names)
     for name in names:
-        nb = plane_bytes(name, px)
+        nb = plane_bytes(HIT_PLANES, name, px)
         assert host[name][(n - 1) * nb:n * nb].tobytes() == bits(last[name]).tobytes(), (scene_file, name)
     assert len({host["dist"][i * px * 8:(i + 1) * px * 8].tobytes() for i in range(n)}) == n
 
@@ -426,10 +340,10 @@ def test_256_frames_and_one_too_many(gpu_ctx):
     for i in (0, 127, 255):
         single = gpu_ctx.renderHits(cams[i], opts)
         for name in PLANES:
-            nb = plane_bytes(name, 64)
+            nb = plane_bytes(HIT_PLANES, name, 64)
             assert host[name][i * nb:(i + 1) * nb].tobytes() == bits(single[name]).tobytes(), (i, name)
     for name in PLANES:
-        assert (host[name][plane_bytes(name, 256 * 64):] == SENTINEL).all(), name
+        assert (host[name][plane_bytes(HIT_PLANES, name, 256 * 64):] == SENTINEL).all(), name
     assert len({host["rgb"][i * 768:(i + 1) * 768].tobytes() for i in range(256)}) > 128
     arr = (_abi.CameraFrame * 257)(*(cams + cams[:1]))
     parr = (_abi.ScenePose * 257)()          # both counts 0: frames of the scene as it is
@@ -461,16 +375,10 @@ def test_statuses_in_order_leave_the_outputs_untouched(gpu_ctx):
     host, dev = guarded(PLANES, px), guarded_dev(PLANES, px)
 
     def cams_with(**kw):
-        c = _abi.CameraFrame.from_buffer_copy(cams[1])
-        for k, v in kw.items():
-            setattr(c, k, v)
-        return (_abi.CameraFrame * n)(cams[0], c, cams[2])
+        return (_abi.CameraFrame * n)(cams[0], with_fields(cams[1], **kw), cams[2])
 
     def opts_with(**kw):
-        o = _abi.RenderOpts.from_buffer_copy(opts)
-        for k, v in kw.items():
-            setattr(o, k, v)
-        return o
+        return with_fields(opts, **kw)
 
     def refused(status, cause, ctx=gpu_ctx, cc=arr, count=n, oo=opts, poses=good, null_struct=False, no_plane=False, plain=True):
         for posed in ((False, True) if plain else (True,)):

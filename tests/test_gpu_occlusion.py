@@ -4,6 +4,7 @@ planes are, BIT FOR BIT and with no sample excused, what tests/occlusion_referen
 answers also equal the oracle's.  Then the camera call against the ray call, strips, sample counts, plane subsets,
 seeds, misses and garbage, the host variants' chunks, a posed scene, the mirrors, and every refusal."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -11,32 +12,20 @@ import pytest
 import chess2rt_amd as c2
 import occlusion_cases as oc
 import occlusion_reference as ocr
+import query_test_util as Q
 import scene_update_util as U
 from chess2rt_amd import _abi
 from chess2rt_amd.api import OCCLUSION_PLANES
+from query_test_util import OCCLUSION, check_device_against_host, check_filled, device_planes, guarded, last_error, lib, raw_call, struct_of, untouched
+from query_test_util import occlusion_options as occ_opts
 from ray_query_util import bits, oracle_visibility
 
 pytestmark = pytest.mark.gpu
 
 W, H, K, SEED = oc.W, oc.H, oc.K, oc.SEED
 PLANES = tuple(OCCLUSION_PLANES)
-SENTINEL = 0xA5
-GUARD = 64               # extra elements behind every plane
 _cases = {}
-
-
-def lib():
-    return _abi.load_library()
-
-
-def last_error(ctx):
-    return lib().c2rt_last_error(ctx.handle).decode(errors="replace")
-
-
-def same_planes(got, want, what, names=PLANES):
-    for name in names:
-        assert got[name].dtype == want[name].dtype and got[name].size == want[name].size, (what, name)
-        assert bits(got[name]).tobytes() == bits(want[name]).tobytes(), "%s: plane %s differs" % (what, name)
+same_planes = functools.partial(Q.same_planes, names=PLANES)
 
 
 def composed(ctx, rays, samples, radius, seed, idx=None):
@@ -103,18 +92,7 @@ def test_camera_call_equals_ray_call_and_strips(gpu_ctx, name):
     other = _abi.RenderOpts.from_buffer_copy(opts)
     other.seed = 99
     same_planes(gpu_ctx.renderOcclusion(cam, other, K, oc.RADIUS[name], SEED), full, "%s opts.seed" % name)
-    world, strip = 3, 8
-    seen = np.zeros(H, dtype=int)
-    for rank in range(world):
-        o = scene.renderOpts(taps=_abi.TAPS_1, strip_height=strip, strip_rank=rank, strip_world=world)
-        rows = [y for y in range(H) if (y // strip) % world == rank]
-        assert gpu_ctx.localRows(o) == len(rows)
-        got = gpu_ctx.renderOcclusion(cam, o, K, oc.RADIUS[name], SEED)
-        for p in PLANES:
-            assert got[p].shape[0] == len(rows)
-            assert bits(got[p]).tobytes() == bits(full[p][rows]).tobytes(), (name, rank, p)
-        seen[rows] += 1
-    assert (seen == 1).all()
+    Q.check_strips(gpu_ctx, scene, lambda o: gpu_ctx.renderOcclusion(cam, o, K, oc.RADIUS[name], SEED), full, H, 3, 8, PLANES, name)
 
 
 # ---- 6: sample counts --------------------------------------------------------------------------------------------------
@@ -148,42 +126,6 @@ def test_sample_counts(gpu_ctx):
 # ---- 7: plane independence and seeds ---------------------------------------------------------------------------------------
 
 
-def plane_bytes(name, samples):
-    dtype, comps = OCCLUSION_PLANES[name]
-    return samples * comps * np.dtype(dtype).itemsize
-
-
-def guarded(names, samples):
-    """{name: 8-byte aligned byte buffer of the plane plus GUARD elements, all SENTINEL}"""
-    out = {}
-    for n in names:
-        words = (plane_bytes(n, samples) + GUARD * np.dtype(OCCLUSION_PLANES[n][0]).itemsize + 7) // 8
-        out[n] = np.full(words, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64).view(np.uint8)
-    return out
-
-
-def untouched(bufs):
-    return all((b == SENTINEL).all() for b in bufs.values())
-
-
-def struct_of(bufs):
-    pl = _abi.OcclusionPlanes()
-    for n, b in bufs.items():
-        setattr(pl, n, b.ctypes.data)
-    return pl
-
-
-def occ_opts(samples=K, radius=50.0, seed=SEED, reserved=0):
-    return _abi.OcclusionOpts(radius=radius, seed=seed, samples=samples, reserved=reserved)
-
-
-def check_filled(bufs, want, n, what, names=PLANES):
-    for name in names:
-        nb = plane_bytes(name, n)
-        assert bufs[name][:nb].tobytes() == bits(want[name]).tobytes(), (what, name)
-        assert (bufs[name][nb:] == SENTINEL).all(), (what, name)
-
-
 def test_plane_independence_and_seeds(gpu_ctx):
     name = "csg_stress"
     scene, cam, opts = oc.load(name)
@@ -191,18 +133,8 @@ def test_plane_independence_and_seeds(gpu_ctx):
     rays, full_rays = c["eyeless"][0], c["eyeless"][1]
     radius = oc.RADIUS[name]
     full = gpu_ctx.renderOcclusion(cam, opts, K, radius, SEED)
-    L = lib()
-    occ = occ_opts(K, radius, SEED)
-    for subset in [(p,) for p in PLANES] + [("open", "bent"), ("node", "ao")]:
-        # what is not asked for is null in the struct; its buffer keeps the pattern
-        bufs, rbufs = guarded(PLANES, W * H), guarded(PLANES, len(rays))
-        pl, rpl = struct_of({k: bufs[k] for k in subset}), struct_of({k: rbufs[k] for k in subset})
-        assert L.c2rt_render_occlusion(gpu_ctx.handle, C.byref(cam), C.byref(opts), C.byref(occ), C.byref(pl)) == _abi.OK, last_error(gpu_ctx)
-        assert L.c2rt_trace_rays_occlusion(gpu_ctx.handle, rays.ctypes.data_as(C.c_void_p), len(rays), C.byref(occ), C.byref(rpl)) == _abi.OK, last_error(gpu_ctx)
-        for b in (bufs, rbufs):
-            assert untouched({k: v for k, v in b.items() if k not in subset}), subset
-        check_filled(bufs, full, W * H, subset, subset)
-        check_filled(rbufs, full_rays, len(rays), subset, subset)
+    subsets = [(p,) for p in PLANES] + [("open", "bent"), ("node", "ao")]
+    Q.check_plane_subsets(OCCLUSION, gpu_ctx, cam, opts, rays, occ_opts(K, radius, SEED), subsets, full, full_rays, W * H, name, align=8)
     hits = gpu_ctx.renderHits(cam, opts, planes=("node",))
     alone = gpu_ctx.renderOcclusion(cam, opts, K, radius, SEED, planes=("node",))
     assert list(alone) == ["node"] and bits(alone["node"]).tobytes() == bits(hits["node"]).tobytes()
@@ -231,37 +163,10 @@ def test_misses_and_garbage_rays(gpu_ctx):
     assert (want["node"][miss] == -1).all() and (want["open"][miss] == np.uint64((1 << K) - 1)).all()
     assert want["ao"][miss].tobytes() == np.ones(int(miss.sum()), dtype=np.float32).tobytes()
     assert not want["bent"][miss].view(np.uint64).any()                   # +0, +0, +0
-    rays = rays0.copy()
-    wave = 5
-    lanes = np.arange(64 * wave, 64 * wave + 64)
-    assert hit[lanes].sum() >= 16
-    where = {64 * wave + 21: np.nan, 64 * wave + 40: 0.0}                 # in the middle of one wave
-    for i, v in where.items():
-        rays[i] = v
-    rays[64 * 9 + 3] = 1e300                                             # and one of 1e300 in another wave
-    got = gpu_ctx.traceRaysOcclusion(rays, K, oc.RADIUS[name], SEED)     # the call returns
-    keep = np.ones(len(rays), dtype=bool)
-    keep[list(where) + [64 * 9 + 3]] = False
-    assert keep[lanes].sum() == 62
-    for p in PLANES:
-        assert bits(got[p][keep]).tobytes() == bits(want[p][keep]).tobytes(), p
-    for i in where:
-        assert not (int(got["open"][i]) >> K), i                         # whatever a garbage lane holds, no bit at or above K
+    Q.check_garbage_lanes(lambda rays: gpu_ctx.traceRaysOcclusion(rays, K, oc.RADIUS[name], SEED), rays0, want, hit, PLANES, "open", K)
 
 
 # ---- 9: host variants ------------------------------------------------------------------------------------------------------
-
-
-def device_planes(torch, dev, n):
-    return {name: torch.full((plane_bytes(name, n) + GUARD,), SENTINEL, dtype=torch.uint8, device=dev) for name in PLANES}
-
-
-def check_device_against_host(t, host, n, what):
-    for name in PLANES:
-        got = t[name].cpu().numpy()
-        nb = plane_bytes(name, n)
-        assert got[:nb].tobytes() == bits(host[name]).tobytes(), (what, name)
-        assert (got[nb:] == SENTINEL).all(), (what, name)
 
 
 def test_host_variants_equal_the_device_variants(gpu_ctx):
@@ -275,22 +180,22 @@ def test_host_variants_equal_the_device_variants(gpu_ctx):
     s1 = torch.cuda.Stream(dev)
     # the frame at 61x47
     host = gpu_ctx.renderOcclusion(cam, opts, K, radius, SEED)
-    t = device_planes(torch, dev, W * H)
+    t = device_planes(OCCLUSION_PLANES, W * H, dev, guard_bytes=64)
     torch.cuda.synchronize()
     gpu_ctx.renderOcclusionDevice(cam, opts, K, radius, {k: v.data_ptr() for k, v in t.items()}, seed=SEED, stream=s1.cuda_stream)
     s1.synchronize()
-    check_device_against_host(t, host, W * H, "61x47")
+    check_device_against_host(OCCLUSION_PLANES, t, host, W * H, "61x47")
     # 2^18 + 70 rays, K = 2: the second chunk starts at a non-zero index, and its rays draw the samples of THEIR index
     n = (1 << 18) + 70
     reps = np.arange(n) % len(base[0])
     rays = np.ascontiguousarray(base[0][reps])
     host = gpu_ctx.traceRaysOcclusion(rays, 2, radius, SEED)
-    t = device_planes(torch, dev, n)
+    t = device_planes(OCCLUSION_PLANES, n, dev, guard_bytes=64)
     rays_t = torch.from_numpy(rays).to(dev)
     torch.cuda.synchronize()
     gpu_ctx.traceRaysOcclusionDevice(rays_t.data_ptr(), n, 2, radius, {k: v.data_ptr() for k, v in t.items()}, seed=SEED, stream=s1.cuda_stream)
     s1.synchronize()
-    check_device_against_host(t, host, n, "2^18 + 70 rays")
+    check_device_against_host(OCCLUSION_PLANES, t, host, n, "2^18 + 70 rays")
     assert np.array_equal(host["node"], base[1]["node"][reps])
     # the tail behind the chunk boundary against the composition at its own indices; a copy of a ray elsewhere in the
     # array draws other directions
@@ -317,10 +222,10 @@ def test_posed_scene_and_mirrors(gpu_ctx):
     same_planes(got, frame, "Renderer.renderOcclusion")
     sub = c2.Renderer(scene, gpu_ctx).renderOcclusion(K, radius, SEED, planes=("ao",))
     assert list(sub) == ["ao"] and bits(sub["ao"]).tobytes() == bits(frame["ao"]).tobytes()
-    raw = guarded(PLANES, W * H)
-    pl, occ = struct_of(raw), occ_opts(K, radius, SEED)
+    raw = guarded(OCCLUSION_PLANES, PLANES, W * H, align=8)
+    pl, occ = struct_of(_abi.OcclusionPlanes, raw), occ_opts(K, radius, SEED)
     assert lib().c2rt_host_render_occlusion(gpu_ctx.handle, scene._h, C.byref(occ), C.byref(pl)) == _abi.OK, last_error(gpu_ctx)
-    check_filled(raw, frame, W * H, "c2rt_host_render_occlusion")
+    check_filled(OCCLUSION_PLANES, raw, frame, W * H, "c2rt_host_render_occlusion")
     # a ball moves: the call sees the posed scene
     gpu_ctx.uploadScene(scene.desc)
     gpu_ctx.updateScene({3: U.xf(("translate", 60, 15, 200))})
@@ -356,19 +261,13 @@ def test_frame_refusals_leave_the_outputs_untouched(gpu_ctx):
     L = lib()
 
     def copy_cam(**kw):
-        c = _abi.CameraFrame.from_buffer_copy(cam)
-        for k, v in kw.items():
-            setattr(c, k, v)
-        return c
+        return Q.with_fields(cam, **kw)
 
     def copy_opts(**kw):
-        o = _abi.RenderOpts.from_buffer_copy(opts)
-        for k, v in kw.items():
-            setattr(o, k, v)
-        return o
+        return Q.with_fields(opts, **kw)
 
-    bufs = guarded(PLANES, n)
-    pl, none = struct_of(bufs), _abi.OcclusionPlanes()
+    bufs = guarded(OCCLUSION_PLANES, PLANES, n, align=8)
+    pl, none = struct_of(_abi.OcclusionPlanes, bufs), _abi.OcclusionPlanes()
     good = occ_opts(K, oc.RADIUS[name], SEED)
     dof = copy_cam(dof=1, num_samples=4)
 
@@ -422,17 +321,17 @@ def test_frame_refusals_leave_the_outputs_untouched(gpu_ctx):
         fresh.close()
     assert untouched(bufs)
     # afterwards the same context fills a correct plane set
-    assert L.c2rt_render_occlusion(gpu_ctx.handle, C.byref(cam), C.byref(opts), C.byref(good), C.byref(pl)) == _abi.OK, last_error(gpu_ctx)
-    check_filled(bufs, want, n, "after the refusals")
+    assert raw_call(OCCLUSION, gpu_ctx, bufs, cam, opts, options=good) == _abi.OK, last_error(gpu_ctx)
+    check_filled(OCCLUSION_PLANES, bufs, want, n, "after the refusals")
 
 
 def test_ray_refusals_leave_the_outputs_untouched(gpu_ctx):
     name = "lecture5"
     rays, want, _, _ = case(gpu_ctx, name)["eyeless"]
     n = len(rays)
-    bufs = guarded(PLANES, n)
+    bufs = guarded(OCCLUSION_PLANES, PLANES, n, align=8)
     L = lib()
-    pl, none = struct_of(bufs), _abi.OcclusionPlanes()
+    pl, none = struct_of(_abi.OcclusionPlanes, bufs), _abi.OcclusionPlanes()
     good = occ_opts(K, oc.RADIUS[name], SEED)
     bad = occ_opts(samples=0, radius=-1.0, reserved=9)
     rp = rays.ctypes.data_as(C.c_void_p)
@@ -465,5 +364,5 @@ def test_ray_refusals_leave_the_outputs_untouched(gpu_ctx):
     finally:
         fresh.close()
     assert untouched(bufs)
-    assert L.c2rt_trace_rays_occlusion(gpu_ctx.handle, rp, n, C.byref(good), C.byref(pl)) == _abi.OK, last_error(gpu_ctx)
-    check_filled(bufs, want, n, "after the refusals")
+    assert raw_call(OCCLUSION, gpu_ctx, bufs, rays=rays, n=n, options=good) == _abi.OK, last_error(gpu_ctx)
+    check_filled(OCCLUSION_PLANES, bufs, want, n, "after the refusals")

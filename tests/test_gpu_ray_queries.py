@@ -17,6 +17,7 @@ from chess2rt_amd import _abi
 from chess2rt_amd.api import RAY_HIT_DTYPE
 from golden_configs import SCENES
 from parity_util import TOL, maxdiff
+from query_test_util import SENTINEL
 from ray_query_util import (assert_records_match_oracle, bits, csg_node_mask, eyeless_rays, light_positions, oracle_trace,
                             oracle_visibility, record_from_trace_result, screen_rays, visibility_segments)
 from scene_fuzz import many_nodes_scene_sdl, random_scene_sdl
@@ -24,7 +25,6 @@ from scene_fuzz import many_nodes_scene_sdl, random_scene_sdl
 pytestmark = pytest.mark.gpu
 
 W, H = 61, 47            # 2 867 rays: 44 full waves and a 51-lane tail
-SENTINEL = 0xA5
 
 # test 5's scenes: name -> (how to get the SDL, seed of the ray set).  The fuzz seeds are the first whose tree has
 # exactly that CSG depth and whose ray set meets the preconditions below on the oracle alone (found on the CPU).

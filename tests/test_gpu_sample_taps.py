@@ -20,26 +20,15 @@ from aa_reference import needs_aa, tile_counts
 from chess2rt_amd import _abi
 from chess2rt_amd.api import _tap_table
 from golden_configs import SCENES
+from query_test_util import DeviceBytes, frame_and_mask, hip_runtime, holds, last_error, lib, same, untouched, with_fields
+from query_test_util import float_bits as bits
 
 pytestmark = pytest.mark.gpu
 needs_x87 = pytest.mark.skipif(not cr.x87_available(), reason="np.longdouble is not the x87 80-bit format: radians cannot be restated")
 
-SENTINEL = 0xA5
-GUARD = 64               # extra elements behind every output
+GUARD = 64               # extra bytes behind the device outputs, extra elements behind the host outputs
 F = np.float32
 _cases = {}
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint8)
-
-
-def same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and bits(a).tobytes() == bits(b).tobytes()
-
-
-def lib():
-    return _abi.load_library()
 
 
 # The messages every adaptive call shares, c2rt_render_frame_adaptive_taps* among them (the library builds them in one place), whole: a cause listed here is compared
@@ -58,10 +47,6 @@ WHOLE = {
 }
 
 
-def last_error(ctx):
-    return lib().c2rt_last_error(ctx.handle).decode(errors="replace")
-
-
 def golden_case(ctx, scene_file, width, height):
     """(scene, camera, one-tap options, one-tap frame) of the file's camera, rendered once and shared (read-only); the scene
     is uploaded on return"""
@@ -74,48 +59,6 @@ def golden_case(ctx, scene_file, width, height):
         _cases[key] = (scene, cam, opts, one)
     ctx.uploadScene(_cases[key][0].desc)
     return _cases[key]
-
-
-def hip_runtime():
-    """the HIP runtime the library is linked against, reached through the library's own handle"""
-    hip = lib()
-    hip.hipStreamCreate.argtypes = [C.POINTER(C.c_void_p)]
-    hip.hipStreamDestroy.argtypes = [C.c_void_p]
-    hip.hipStreamSynchronize.argtypes = [C.c_void_p]
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipFree.argtypes = [C.c_void_p]
-    hip.hipMemset.argtypes = [C.c_void_p, C.c_int, C.c_size_t]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    return hip
-
-
-class DeviceBytes:
-    """`nbytes` of device memory filled with SENTINEL"""
-
-    def __init__(self, nbytes):
-        self.hip, self.nbytes, self.ptr = hip_runtime(), nbytes, C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(self.ptr), nbytes) == 0
-        assert self.hip.hipMemset(self.ptr, SENTINEL, nbytes) == 0
-        assert self.hip.hipDeviceSynchronize() == 0
-
-    def get(self):
-        out = np.empty(self.nbytes, dtype=np.uint8)
-        assert self.hip.hipMemcpy(out.ctypes.data, self.ptr, self.nbytes, 2) == 0     # hipMemcpyDeviceToHost
-        return out
-
-    def free(self):
-        if self.ptr:
-            assert self.hip.hipFree(self.ptr) == 0
-            self.ptr = C.c_void_p()
-
-
-def untouched(*bufs):
-    return all((b == SENTINEL).all() for b in bufs)
-
-
-def guarded(n):
-    """host frame and mask buffers for n pixels, GUARD elements behind each, all SENTINEL"""
-    return np.full(n * 12 + GUARD * 4, SENTINEL, dtype=np.uint8), np.full(n + GUARD, SENTINEL, dtype=np.uint8)
 
 
 def composed(ctx, cam, width, height, table, rows=None):
@@ -235,8 +178,7 @@ def test_host_chunks_equal_one_device_launch(gpu_ctx):
         got = dev.get()
     finally:
         dev.free()
-    assert got[:n * 12].tobytes() == bits(host).tobytes()
-    assert (got[n * 12:] == SENTINEL).all()
+    assert holds(got, host)
     # the last rows, which the second chunk holds, are not the first rows again
     assert not same(host[-1], host[0])
 
@@ -260,8 +202,8 @@ def test_device_variant_on_a_stream_of_its_own(gpu_ctx):
     finally:
         plain.free()
         out.free()
-    assert got[:n * 12].tobytes() == bits(want).tobytes() and (got[n * 12:] == SENTINEL).all()
-    assert first[:n * 12].tobytes() == bits(one).tobytes() and (first[n * 12:] == SENTINEL).all()
+    assert holds(got, want)
+    assert holds(first, one)
     assert same(gpu_ctx.renderFrameTaps(cam, opts, tc.GRID16), want)
 
 
@@ -375,22 +317,16 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
     good = table_of(tc.ODD7)
 
     def copy_cam(**kw):
-        c = _abi.CameraFrame.from_buffer_copy(cam)
-        for k, v in kw.items():
-            setattr(c, k, v)
-        return c
+        return with_fields(cam, **kw)
 
     def copy_opts(**kw):
-        o = _abi.RenderOpts.from_buffer_copy(opts)
-        for k, v in kw.items():
-            setattr(o, k, v)
-        return o
+        return with_fields(opts, **kw)
 
     def ref(x):
         return C.byref(x) if x is not None else None
 
     fdev, mdev = DeviceBytes(n * 12 + GUARD), DeviceBytes(n + GUARD)
-    fbuf, mbuf = guarded(n)
+    fbuf, mbuf = frame_and_mask(n, guard_elems=GUARD)
 
     def whole_refused(ctx, c, o, t, status, cause, out=True):
         for st in (L.c2rt_render_frame_taps(ctx.handle, ref(c), ref(o), ref(t), fbuf.ctypes.data if out else None),
@@ -398,7 +334,7 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
             assert st == status, (cause, st, last_error(ctx))
             assert cause in last_error(ctx), (cause, last_error(ctx))
         assert hip_runtime().hipDeviceSynchronize() == 0
-        assert untouched(fbuf, fdev.get()), cause
+        assert untouched((fbuf, fdev.get())), cause
 
     def adaptive_refused(ctx, c, o, t, threshold, status, cause, out=True, dev_mask=True, host=True):
         calls = []
@@ -410,7 +346,7 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
             assert st == status, (cause, st, last_error(ctx))
             assert last_error(ctx) == WHOLE[cause] if cause in WHOLE else cause in last_error(ctx), (cause, last_error(ctx))
         assert hip_runtime().hipDeviceSynchronize() == 0
-        assert untouched(fbuf, mbuf, fdev.get(), mdev.get()), cause
+        assert untouched((fbuf, mbuf, fdev.get(), mdev.get())), cause
 
     def both_refused(ctx, c, o, t, status, cause):
         whole_refused(ctx, c, o, t, status, cause)
@@ -470,27 +406,25 @@ def test_statuses_leave_the_outputs_untouched(gpu_ctx):
         stop = np.ones(1, dtype=np.uint8)
         assert L.c2rt_render_frame_adaptive_taps(gpu_ctx.handle, ref(cam), ref(opts), ref(good), thr, fbuf.ctypes.data, mbuf.ctypes.data,
                                                  stop.ctypes.data) == _abi.ERR_CANCELLED
-        assert untouched(fbuf, mbuf)
+        assert untouched((fbuf, mbuf))
         # an offset the table does not count is not read; afterwards the context renders correct frames, behind sentinels,
         # with and without the (nullable) host mask
         t = with_offset(tc.ODD7, 7, 0, float("nan"))
         assert L.c2rt_render_frame_taps(gpu_ctx.handle, ref(cam), ref(opts), ref(t), fbuf.ctypes.data) == _abi.OK, last_error(gpu_ctx)
-        assert fbuf[:n * 12].tobytes() == bits(want).tobytes() and (fbuf[n * 12:] == SENTINEL).all()
+        assert holds(fbuf, want)
         want_frame, want_mask = gpu_ctx.renderFrameAdaptiveTaps(cam, opts, tc.ODD7)
-        fbuf2, mbuf2 = guarded(n)
+        fbuf2, mbuf2 = frame_and_mask(n, guard_elems=GUARD)
         stop[0] = 0
         assert L.c2rt_render_frame_adaptive_taps(gpu_ctx.handle, ref(cam), ref(opts), ref(t), thr, fbuf2.ctypes.data, mbuf2.ctypes.data,
                                                  stop.ctypes.data) == _abi.OK, last_error(gpu_ctx)
-        assert fbuf2[:n * 12].tobytes() == bits(want_frame).tobytes() and (fbuf2[n * 12:] == SENTINEL).all()
-        assert mbuf2[:n].tobytes() == want_mask.tobytes() and (mbuf2[n:] == SENTINEL).all()
-        fbuf3, mbuf3 = guarded(n)
+        assert holds(fbuf2, want_frame) and holds(mbuf2, want_mask)
+        fbuf3, mbuf3 = frame_and_mask(n, guard_elems=GUARD)
         assert L.c2rt_render_frame_adaptive_taps(gpu_ctx.handle, ref(cam), ref(opts), ref(t), thr, fbuf3.ctypes.data, None, None) == _abi.OK
-        assert fbuf3.tobytes() == fbuf2.tobytes() and untouched(mbuf3)
+        assert fbuf3.tobytes() == fbuf2.tobytes() and untouched((mbuf3,))
         assert L.c2rt_render_frame_adaptive_taps_device(gpu_ctx.handle, ref(cam), ref(opts), ref(t), thr, fdev.ptr, mdev.ptr, None) == _abi.OK
         assert hip_runtime().hipDeviceSynchronize() == 0
         got_f, got_m = fdev.get(), mdev.get()
-        assert got_f[:n * 12].tobytes() == bits(want_frame).tobytes() and (got_f[n * 12:] == SENTINEL).all()
-        assert got_m[:n].tobytes() == want_mask.tobytes() and (got_m[n:] == SENTINEL).all()
+        assert holds(got_f, want_frame) and holds(got_m, want_mask)
     finally:
         fdev.free()
         mdev.free()

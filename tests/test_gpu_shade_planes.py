@@ -13,69 +13,26 @@ import numpy as np
 import pytest
 
 import chess2rt_amd as c2
+import query_test_util as Q
 import shade_parts_reference as sp
 import shade_reference as sr
 import shade_scenes as ss
 from chess2rt_amd import _abi
 from chess2rt_amd.api import SHADE_PLANES
 from golden_configs import SCENES
+from query_test_util import SHADING, check_device_against_host, check_filled, device_planes, guarded, last_error, lib, raw_call, struct_of, untouched
 from ray_query_util import bits, oracle_visibility, screen_rays
 
 pytestmark = pytest.mark.gpu
 
 W, H = ss.W, ss.H
-SENTINEL = 0xA5
-GUARD = 64               # extra elements behind every plane
 PLANES = tuple(SHADE_PLANES)
 FLOATS = ("albedo", "light", "specular", "rgb")
 MIN_REACH = 30
 _gpu_cases = {}
 
 
-def lib():
-    return _abi.load_library()
-
-
-def last_error(ctx):
-    return lib().c2rt_last_error(ctx.handle).decode(errors="replace")
-
-
-def plane_bytes(name, samples):
-    dtype, comps = SHADE_PLANES[name]
-    return samples * comps * np.dtype(dtype).itemsize
-
-
-def guarded(names, samples):
-    """{name: byte buffer of the plane plus GUARD elements, all SENTINEL}"""
-    return {n: np.full(plane_bytes(n, samples) + GUARD * np.dtype(SHADE_PLANES[n][0]).itemsize, SENTINEL, dtype=np.uint8) for n in names}
-
-
-def untouched(bufs):
-    return all((b == SENTINEL).all() for b in bufs.values())
-
-
-def struct_of(bufs):
-    pl = _abi.ShadePlanes()
-    for n, b in bufs.items():
-        setattr(pl, n, b.ctypes.data)
-    return pl
-
-
-def raw_frame(ctx, cam, opts, bufs, null_struct=False):
-    """c2rt_render_shading through the raw entry point: planes not in `bufs` are passed as null"""
-    pl = struct_of(bufs)
-    return lib().c2rt_render_shading(ctx.handle, C.byref(cam), C.byref(opts), None if null_struct else C.byref(pl))
-
-
-def raw_rays(ctx, rays, n, bufs, null_struct=False):
-    pl = struct_of(bufs)
-    return lib().c2rt_trace_rays_shading(ctx.handle if ctx is not None else None, rays.ctypes.data_as(C.c_void_p) if rays is not None else None, n,
-                                         None if null_struct else C.byref(pl))
-
-
-def same_planes(got, want, what, names=PLANES):
-    for name in names:
-        assert bits(got[name]).tobytes() == bits(want[name]).tobytes(), "%s: plane %s differs" % (what, name)
+same_planes = functools.partial(Q.same_planes, names=PLANES)
 
 
 def phong_of(T, node):
@@ -154,7 +111,7 @@ def test_rgb_and_node_are_the_hit_calls_and_the_parts_recombine(gpu_ctx, variant
         assert hit.sum() >= MIN_REACH and phong.sum() >= MIN_REACH and (hit & ~phong).sum() >= MIN_REACH, what
     frame = gpu_ctx.renderShading(cam, opts)
     hits = gpu_ctx.renderHits(cam, opts, planes=("node", "rgb"))
-    same_planes(frame, hits, "%s frame against renderHits" % variant, ("node", "rgb"))
+    same_planes(frame, hits, "%s frame against renderHits" % variant, names=("node", "rgb"))
     check_identity(T, frame, "%s frame" % variant)
     # the frame's planes are the planes of its own screen rays
     screen = gpu_case(gpu_ctx, variant)["screen"][3]
@@ -227,21 +184,10 @@ def test_plane_subsets(gpu_ctx, variant):
     case = gpu_case(gpu_ctx, variant)
     rays, full_rays = case["random"][0], case["random"][3]
     full = gpu_ctx.renderShading(cam, opts)
-    for subset in SUBSETS:
-        # what is not asked for is null in the struct; its buffer keeps the pattern
-        bufs, rbufs = guarded(PLANES, W * H), guarded(PLANES, len(rays))
-        assert raw_frame(gpu_ctx, cam, opts, {k: bufs[k] for k in subset}) == _abi.OK, last_error(gpu_ctx)
-        assert raw_rays(gpu_ctx, rays, len(rays), {k: rbufs[k] for k in subset}) == _abi.OK, last_error(gpu_ctx)
-        for b in (bufs, rbufs):
-            assert untouched({k: v for k, v in b.items() if k not in subset}), (variant, subset)
-        for name in subset:
-            for b, want, n in ((bufs, full, W * H), (rbufs, full_rays, len(rays))):
-                nb = plane_bytes(name, n)
-                assert b[name][:nb].tobytes() == bits(want[name]).tobytes(), (variant, subset, name)
-                assert (b[name][nb:] == SENTINEL).all(), (variant, subset, name)
+    Q.check_plane_subsets(SHADING, gpu_ctx, cam, opts, rays, None, SUBSETS, full, full_rays, W * H, variant)
     got = gpu_ctx.renderShading(cam, opts, planes=("visible", "albedo"))
     assert set(got) == {"visible", "albedo"}
-    same_planes(got, full, variant, ("visible", "albedo"))
+    same_planes(got, full, variant, names=("visible", "albedo"))
     with pytest.raises(ValueError):
         gpu_ctx.renderShading(cam, opts, planes=("depth",))
 
@@ -250,21 +196,10 @@ def test_plane_subsets(gpu_ctx, variant):
 
 
 def test_strips(gpu_ctx):
-    world, strip = 3, 8
     scene, cam, opts = ss.load("L5")
     gpu_ctx.uploadScene(scene.desc)
     full = gpu_ctx.renderShading(cam, opts)
-    seen = np.zeros(H, dtype=int)
-    for rank in range(world):
-        o = scene.renderOpts(taps=_abi.TAPS_1, strip_height=strip, strip_rank=rank, strip_world=world)
-        rows = [y for y in range(H) if (y // strip) % world == rank]
-        assert gpu_ctx.localRows(o) == len(rows)
-        got = gpu_ctx.renderShading(cam, o)
-        for name in PLANES:
-            assert got[name].shape[0] == len(rows)
-            assert bits(got[name]).tobytes() == bits(full[name][rows]).tobytes(), (rank, name)
-        seen[rows] += 1
-    assert (seen == 1).all()
+    Q.check_strips(gpu_ctx, scene, lambda o: gpu_ctx.renderShading(cam, o), full, H, 3, 8, PLANES, "L5")
 
 
 # ---- 7: host chunking ------------------------------------------------------------------------------------------------
@@ -281,18 +216,6 @@ def lecture5(width, height, pitch_up=0.0):
     return scene, scene.beginFrame(), scene.renderOpts(taps=_abi.TAPS_1)
 
 
-def device_planes(torch, dev, n):
-    return {name: torch.full((plane_bytes(name, n) + GUARD,), SENTINEL, dtype=torch.uint8, device=dev) for name in PLANES}
-
-
-def check_device_against_host(t, host, n, what):
-    for name in PLANES:
-        got = t[name].cpu().numpy()
-        nb = plane_bytes(name, n)
-        assert got[:nb].tobytes() == bits(host[name]).tobytes(), (what, name)
-        assert (got[nb:] == SENTINEL).all(), (what, name)
-
-
 def test_host_chunks_of_a_frame_equal_the_device_call(gpu_ctx):
     import torch
 
@@ -302,11 +225,11 @@ def test_host_chunks_of_a_frame_equal_the_device_call(gpu_ctx):
     host = gpu_ctx.renderShading(cam, opts)
     dev = torch.device("cuda:0")
     s1 = torch.cuda.Stream(dev)
-    t = device_planes(torch, dev, w * h)
+    t = device_planes(SHADE_PLANES, w * h, dev, guard_bytes=64)
     torch.cuda.synchronize()
     gpu_ctx.renderShadingDevice(cam, opts, {k: v.data_ptr() for k, v in t.items()}, s1.cuda_stream)
     s1.synchronize()
-    check_device_against_host(t, host, w * h, "640x480")
+    check_device_against_host(SHADE_PLANES, t, host, w * h, "640x480")
     assert 0 < int((host["node"] >= 0).sum()) < w * h
 
 
@@ -322,12 +245,12 @@ def test_host_chunks_of_rays_equal_the_device_call(gpu_ctx):
         assert bits(host[name]).tobytes() == bits(base[3][name][reps]).tobytes(), name
     dev = torch.device("cuda:0")
     s1 = torch.cuda.Stream(dev)
-    t = device_planes(torch, dev, n)
+    t = device_planes(SHADE_PLANES, n, dev, guard_bytes=64)
     rays_t = torch.from_numpy(rays).to(dev)
     torch.cuda.synchronize()
     gpu_ctx.traceRaysShadingDevice(rays_t.data_ptr(), n, {k: v.data_ptr() for k, v in t.items()}, s1.cuda_stream)
     s1.synchronize()
-    check_device_against_host(t, host, n, "2^18 + 5 rays")
+    check_device_against_host(SHADE_PLANES, t, host, n, "2^18 + 5 rays")
 
 
 # ---- 8: rays of garbage ------------------------------------------------------------------------------------------------
@@ -356,62 +279,53 @@ def test_frame_statuses_leave_the_outputs_untouched(gpu_ctx):
     n = W * H
 
     def copy_cam(**kw):
-        c = _abi.CameraFrame.from_buffer_copy(cam)
-        for k, v in kw.items():
-            setattr(c, k, v)
-        return c
+        return Q.with_fields(cam, **kw)
 
     def copy_opts(**kw):
-        o = _abi.RenderOpts.from_buffer_copy(opts)
-        for k, v in kw.items():
-            setattr(o, k, v)
-        return o
+        return Q.with_fields(opts, **kw)
 
-    bufs = guarded(PLANES, n)
+    bufs = guarded(SHADE_PLANES, PLANES, n)
     L = lib()
-    pl = struct_of(bufs)
+    pl = struct_of(_abi.ShadePlanes, bufs)
     assert L.c2rt_render_shading(gpu_ctx.handle, None, C.byref(opts), C.byref(pl)) == _abi.ERR_INVALID_ARG          # a frame call's own
     assert L.c2rt_render_shading(gpu_ctx.handle, C.byref(cam), C.byref(copy_opts(width=0)), C.byref(pl)) == L.c2rt_render_hits(
         gpu_ctx.handle, C.byref(cam), C.byref(copy_opts(width=0)), C.byref(_abi.HitPlanes(node=bufs["node"].ctypes.data)))
-    assert raw_frame(gpu_ctx, cam, opts, bufs, null_struct=True) == _abi.ERR_INVALID_ARG
+    assert raw_call(SHADING, gpu_ctx, bufs, cam, opts, null_struct=True) == _abi.ERR_INVALID_ARG
     assert last_error(gpu_ctx) == "null planes"
-    assert raw_frame(gpu_ctx, cam, opts, {}) == _abi.ERR_INVALID_ARG
+    assert raw_call(SHADING, gpu_ctx, {}, cam, opts) == _abi.ERR_INVALID_ARG
     assert last_error(gpu_ctx) == "no plane asked for: all six pointers of c2rt_shade_planes are null"
     # the planes are judged before the modes: a depth-of-field camera with no plane is an invalid argument
-    assert raw_frame(gpu_ctx, copy_cam(dof=1, num_samples=4), opts, {}) == _abi.ERR_INVALID_ARG
+    assert raw_call(SHADING, gpu_ctx, {}, copy_cam(dof=1, num_samples=4), opts) == _abi.ERR_INVALID_ARG
     cases = [(copy_cam(dof=1, num_samples=4), opts, "depth of field: a pixel's terms are one ray's, a lens has many per pixel"),
              (copy_cam(stereo_separation=0.5), opts, "stereo: a pixel's terms are one ray's, a stereo camera has two per pixel"),
              (cam, copy_opts(count_rays=1), "count_rays: the shading planes do not count rays"),
              (cam, copy_opts(prepass_bucket=48), "prepass_bucket: a preview's pixels share the sample of their block")]
     for c, o, cause in cases:
-        assert raw_frame(gpu_ctx, c, o, bufs) == _abi.ERR_UNSUPPORTED, cause
+        assert raw_call(SHADING, gpu_ctx, bufs, c, o) == _abi.ERR_UNSUPPORTED, cause
         assert last_error(gpu_ctx) == cause, (cause, last_error(gpu_ctx))
         # the device variant decides the same before it enqueues anything (the pointers are never used)
         assert L.c2rt_render_shading_device(gpu_ctx.handle, C.byref(c), C.byref(o), C.byref(pl), None) == _abi.ERR_UNSUPPORTED, cause
         assert last_error(gpu_ctx) == cause
     fresh = c2.Context(0)
     try:
-        assert raw_frame(fresh, cam, opts, bufs) == _abi.ERR_NO_SCENE
+        assert raw_call(SHADING, fresh, bufs, cam, opts) == _abi.ERR_NO_SCENE
         assert "no scene" in last_error(fresh)
-        assert raw_frame(fresh, cam, opts, {}) == _abi.ERR_NO_SCENE                  # the frame checks come first
+        assert raw_call(SHADING, fresh, {}, cam, opts) == _abi.ERR_NO_SCENE                  # the frame checks come first
     finally:
         fresh.close()
     assert untouched(bufs)
     # afterwards the same context renders a correct plane set
     want = gpu_ctx.renderShading(cam, opts)
-    assert raw_frame(gpu_ctx, cam, opts, bufs) == _abi.OK
-    for name in PLANES:
-        nb = plane_bytes(name, n)
-        assert bufs[name][:nb].tobytes() == bits(want[name]).tobytes(), name
-        assert (bufs[name][nb:] == SENTINEL).all(), name
+    assert raw_call(SHADING, gpu_ctx, bufs, cam, opts) == _abi.OK
+    check_filled(SHADE_PLANES, bufs, want, n, "after the refusals")
 
 
 def test_ray_statuses_leave_the_outputs_untouched(gpu_ctx):
     rays, _, _, want, _, _, _ = gpu_case(gpu_ctx, "L2")["random"]
     n = len(rays)
-    bufs = guarded(PLANES, n)
+    bufs = guarded(SHADE_PLANES, PLANES, n)
     L = lib()
-    pl = struct_of(bufs)
+    pl = struct_of(_abi.ShadePlanes, bufs)
     rp = rays.ctypes.data_as(C.c_void_p)
     for fn, tail in ((L.c2rt_trace_rays_shading, ()), (L.c2rt_trace_rays_shading_device, (None,))):
         assert fn(None, rp, n, C.byref(pl), *tail) == _abi.ERR_INVALID_ARG                        # null context
@@ -427,19 +341,16 @@ def test_ray_statuses_leave_the_outputs_untouched(gpu_ctx):
         assert last_error(gpu_ctx) == "no plane asked for: all six pointers of c2rt_shade_planes are null"
     fresh = c2.Context(0)
     try:
-        assert raw_rays(fresh, rays, n, bufs) == _abi.ERR_NO_SCENE
+        assert raw_call(SHADING, fresh, bufs, rays=rays, n=n) == _abi.ERR_NO_SCENE
         assert "no scene" in last_error(fresh)
-        assert raw_rays(fresh, rays, n, bufs, null_struct=True) == _abi.ERR_NO_SCENE   # no scene before the planes
-        assert raw_rays(fresh, rays, _abi.MAX_RAYS + 1, bufs) == _abi.ERR_LIMIT        # the limit before the scene
-        assert raw_rays(fresh, None, 0, {}, null_struct=True) == _abi.OK
+        assert raw_call(SHADING, fresh, bufs, rays=rays, n=n, null_struct=True) == _abi.ERR_NO_SCENE   # no scene before the planes
+        assert raw_call(SHADING, fresh, bufs, rays=rays, n=_abi.MAX_RAYS + 1) == _abi.ERR_LIMIT        # the limit before the scene
+        assert raw_call(SHADING, fresh, {}, n=0, null_struct=True) == _abi.OK
     finally:
         fresh.close()
     assert untouched(bufs)
-    assert raw_rays(gpu_ctx, rays, n, bufs) == _abi.OK
-    for name in PLANES:
-        nb = plane_bytes(name, n)
-        assert bufs[name][:nb].tobytes() == bits(want[name]).tobytes(), name
-        assert (bufs[name][nb:] == SENTINEL).all(), name
+    assert raw_call(SHADING, gpu_ctx, bufs, rays=rays, n=n) == _abi.OK
+    check_filled(SHADE_PLANES, bufs, want, n, "after the refusals")
 
 
 # ---- 10: host mirror ---------------------------------------------------------------------------------------------------
@@ -483,7 +394,7 @@ def test_csg_scenes_hit_calls_and_identity(gpu_ctx, scene_file):
     T = sr.Tables(scene.desc)
     pl = gpu_ctx.renderShading(cam, opts)
     hits = gpu_ctx.renderHits(cam, opts, planes=("node", "rgb"))
-    same_planes(pl, hits, scene_file, ("node", "rgb"))
+    same_planes(pl, hits, scene_file, names=("node", "rgb"))
     hit, _ = check_identity(T, pl, scene_file)
     assert 0 < hit.sum() < W * H
     rays = screen_rays(cam, W, H)
