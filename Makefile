@@ -68,7 +68,7 @@ DIAGNAME   := chess2rt_amd/libc2rt_diag.so
 # the same with the depth-1 frame unit's lane statistics compiled in (its rules are below, behind the diagnostics library's)
 STATSNAME  := chess2rt_amd/libc2rt_lanestats.so
 
-all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME) $(STATSNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/libground_texel_check.so tests/libsphere_interior_check.so tests/libcsg_certain_check.so tests/tap_average_check
+all: $(LIBNAME) $(if $(VARIANT),,$(DIAGNAME) $(STATSNAME)) oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/libground_texel_check.so tests/libsphere_interior_check.so tests/libcsg_certain_check.so tests/libcsg_tile_check.so tests/tap_average_check
 
 $(BUILD):
 	mkdir -p $(BUILD)
@@ -130,6 +130,11 @@ tests/libcsg_void_check.so: tests/csg_void_check.cpp $(CSRC)/csg_void.h
 # scripts/csg_certain_census.py) and of the planner's kCsgCertain flag (tests/test_csg_certain_plan.py), without ROCm
 tests/libcsg_certain_check.so: tests/csg_certain_check.cpp $(CSRC)/csg_certain.h $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
 	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/csg_certain_check.cpp $(CSRC)/scene_plan.cpp
+
+# host build of the planner's decision which nodes a frame may render beside the ground through lean::csg_tile
+# (tests/test_csg_tile_plan.py, tests/test_gpu_csg_tiles.py, scripts/csg_tile_census.py), without ROCm
+tests/libcsg_tile_check.so: tests/csg_tile_check.cpp $(CSRC)/scene_plan.cpp $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h
+	g++ -O2 -std=c++17 -fPIC -shared $(FPFLAGS) -Wall -o $@ tests/csg_tile_check.cpp $(CSRC)/scene_plan.cpp
 
 # host build of the sphere-silhouette test of the mask pre-pass (tests/test_sphere_cull_tiles.py, scripts/sphere_cull_tiles.py)
 tests/libsphere_cull_check.so: tests/sphere_cull_check.cpp $(CSRC)/csg_void.h
@@ -194,6 +199,6 @@ resource-usage: | $(BUILD)
 	    -c $(CSRC)/$(q).hip -o $(BUILD)/ru_$(q).o 2>&1 | grep -E "remark:" | sed -e 's/.*remark: [^ ]* *//' -e 's/ \[-Rpass-analysis=kernel-resource-usage\]//' ;)
 
 clean:
-	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/ground_certain_check tests/libground_texel_check.so tests/libsphere_interior_check.so tests/libcsg_certain_check.so tests/tap_average_check
+	rm -rf build build_* chess2rt_amd/libc2rt*.so oracle/libc2rt_oracle.so oracle/libc2rt_oracle_count.so tests/fp64_lean_check tests/certain_f32_check tests/libcsg_void_check.so tests/libsphere_cull_check.so tests/libscene_plan_check.so tests/libscene_update_check.so tests/libground_fast_check.so tests/libground_dark_check.so tests/libground_certain_check.so tests/ground_certain_check tests/libground_texel_check.so tests/libsphere_interior_check.so tests/libcsg_certain_check.so tests/libcsg_tile_check.so tests/tap_average_check
 
 .PHONY: all clean resource-usage

@@ -570,6 +570,18 @@ class Context:
         self._check(self._lib.c2rt_get_sphere_bails(self._h, C.byref(n)))
         return int(n.value)
 
+    def csgTileBails(self):
+        """Ground-and-CsgOp tiles handed back to the general path (cumulative; c2rt_trace.inc: csg_tile)."""
+        n = C.c_uint64()
+        self._check(self._lib.c2rt_get_csg_tile_bails(self._h, C.byref(n)))
+        return int(n.value)
+
+    def csgTiles(self):
+        """Tiles csg_tile rendered (cumulative; counted by the lane-statistics library only, 0 elsewhere)."""
+        n = C.c_uint64()
+        self._check(self._lib.c2rt_get_csg_tiles(self._h, C.byref(n)))
+        return int(n.value)
+
     def renderPixel(self, cam, opts, x, y):
         r = TraceResult()
         self._check(self._lib.c2rt_render_pixel(self._h, C.byref(cam), C.byref(opts), int(x), int(y), C.byref(r)))

@@ -88,10 +88,12 @@ static const DiagKnobs &diag_knobs()
 }
 
 /* C2RT_DEBUG_CULL bit 9 (diagnostics build): no CsgOp is decided by csg_certain.h — every plan this library makes loses
- * its kCsgCertain flags (frames are unchanged, slower).  Called on every fresh plan, so that plans stay comparable. */
+ * its kCsgCertain flags (frames are unchanged, slower).  Bit 10: no tile goes through lean::csg_tile — every plan loses its
+ * kNodeCsgTile flags.  Called on every fresh plan, so that plans stay comparable. */
 static void apply_plan_knobs(ScenePlan &plan)
 {
     if (diag_knobs().debug_cull & 512) drop_csg_certain(plan);
+    if (diag_knobs().debug_cull & 1024) drop_csg_tile(plan);
 }
 
 struct c2rt_ctx {
@@ -116,7 +118,7 @@ struct c2rt_ctx {
 
     float *frame = nullptr;        /* staging frame for host-output renders */
     size_t frame_floats = 0;
-    unsigned long long *counters = nullptr; /* [0..2]: RenderParams::ray_counters (reset per counted frame); [3]: RenderParams::redo_counter (cumulative); [4]: redo_counter[1], ground tiles that left the short chain (cumulative); [5]: redo_counter[2], sphere-interior tiles handed back to the general path (cumulative) */
+    unsigned long long *counters = nullptr; /* [0..2]: RenderParams::ray_counters (reset per counted frame); [3]: RenderParams::redo_counter (cumulative); [4]: redo_counter[1], ground tiles that left the short chain (cumulative); [5]: redo_counter[2], sphere-interior tiles handed back to the general path (cumulative); [6]: redo_counter[3], ground-and-CsgOp tiles handed back likewise (cumulative); [7]: redo_counter[4], the tiles lean::csg_tile rendered (cumulative; counted by the lane-statistics library only) */
     c2rt_trace_result *probe = nullptr;
     uint8_t *srgb_lut = nullptr;   /* [4097] */
     FrameScratch scratch[kScratchSlots];
@@ -639,8 +641,8 @@ int c2rt_init(int device, c2rt_ctx **out)
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_ready, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming));
     HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_inflight, hipEventDisableTiming));
-    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->counters), 6 * sizeof(unsigned long long)));
-    HIP_TRY(ctx, hipMemset(ctx->counters, 0, 6 * sizeof(unsigned long long)));
+    HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->counters), 8 * sizeof(unsigned long long)));
+    HIP_TRY(ctx, hipMemset(ctx->counters, 0, 8 * sizeof(unsigned long long)));
     HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->probe), sizeof(c2rt_trace_result)));
     uint8_t lut[4097];
     build_srgb_lut(lut);
@@ -1301,6 +1303,8 @@ int c2rt_get_csg_truncations(c2rt_ctx *ctx, uint64_t *out) { return get_counter(
 int c2rt_get_exact_redos(c2rt_ctx *ctx, uint64_t *out) { return get_counter(ctx, 3, false, out); }
 int c2rt_get_ground_bails(c2rt_ctx *ctx, uint64_t *out) { return get_counter(ctx, 4, false, out); }
 int c2rt_get_sphere_bails(c2rt_ctx *ctx, uint64_t *out) { return get_counter(ctx, 5, false, out); }
+int c2rt_get_csg_tile_bails(c2rt_ctx *ctx, uint64_t *out) { return get_counter(ctx, 6, false, out); }
+int c2rt_get_csg_tiles(c2rt_ctx *ctx, uint64_t *out) { return get_counter(ctx, 7, false, out); }
 
 int c2rt_render_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, int x, int y,
                       c2rt_trace_result *out)

@@ -92,6 +92,13 @@ enum NodeFlags : uint32_t {
      * normalize((0,1,0) * transposedInverse) — rt/node.d:41-43 — the same for every hit on the node, evaluated at
      * upload with the reference's IEEE operations (finite results only) instead of per lane and per sample */
     kNodePlaneNormal = 8u,
+    /* a leaf CsgOp node the frame kernels may render, together with the ground, through lean::csg_tile (c2rt_trace.inc):
+     * its geometry carries kCsgCertain (two distinct primitive children, each a Sphere or a Cube), its matrix is the
+     * identity (an offset is fine) like every other node's of the scene (all_identity: the instances that carry the
+     * path), its shader is Lambert or Phong over a plain colour, and the scene has at most one light (scene_plan.cpp:
+     * plan_csg_tile_nodes).  What depends on the frame — no depth of field, no stereo, a mask
+     * table, an eligible floor — is RenderParams::ground_fast, which the kernel reads beside this bit. */
+    kNodeCsgTile = 16u,
 };
 
 /* What shading a hit on a node reads, flattened at upload from
@@ -233,7 +240,11 @@ struct RenderParams {
      * 1..3, 0} (c2rt_tile_mask.inc: light_shadow_mask) — written by the pre-pass kernel
      * (launch_tile_masks, c2rt_tile_mask.inc: tile_mask_entry) once per frame with n_cull != 0, read by the frame
      * kernel with one scalar load per tile.  The table covers the local rows [mask_row0, mask_row0 + mask_rows)
-     * (mask_row0 a multiple of the tile height): the launches of a chunked host-output frame share one table */
+     * (mask_row0 a multiple of the tile height): the launches of a chunked host-output frame share one table.
+     * What the frame kernel derives from the words beyond the masks themselves (render_tile): the ground bits pick
+     * ground_tile / sphere_tile, and a tile whose live primary mask is exactly {ground_node, n} while its live shadow mask
+     * keeps nothing beyond those two goes to csg_tile when node n carries kNodeCsgTile — the pre-pass writes nothing
+     * for that path */
     const uint32_t *tile_masks;
     uint32_t mask_row0, mask_rows;
     uint32_t mask_entries;         /* entries of the (first) table: tile_mask_entries() */
@@ -254,7 +265,8 @@ struct RenderParams {
     /* tiles that the production instances rendered a second time through the compiler's divide / sqrt
      * because a lane met an operand outside a lean window (c2rt_trace.inc); cumulative, never null.  [1]: ground tiles
      * that left the short chain (ground_tile_certain); [2]: sphere-interior tiles handed back to the general path
-     * (sphere_tile) */
+     * (sphere_tile); [3]: ground-and-CsgOp tiles handed back likewise (csg_tile); [4]: the tiles csg_tile rendered, counted
+     * by the lane-statistics build only */
     unsigned long long *redo_counter;
     /* pixel probe */
     int32_t probe_x, probe_y;

@@ -1643,6 +1643,231 @@ DEV int sphere_tile(const RenderParams &P, KArgs K, const uint32_t trow, const u
     return kGroundDone;
 }
 
+#if C2RT_CSG_TILE /* the frame units only (c2rt_trace_common.inc) */
+/* ------------------------------------------------------------------ */
+/* ground + one leaf CsgOp: a straight-line path of their own (lean:: only) */
+/* ------------------------------------------------------------------ */
+/*
+ * A tile whose live primary mask is exactly {ground node, `node`} and whose live shadow mask towards the one light
+ * (`smask`) is a subset of that pair, in a ground_fast frame, where the host marked `node` kNodeCsgTile: a leaf CsgOp
+ * that csg_certain.h accepts, under the identity matrix, Lambert or Phong over a plain colour (scene_plan.cpp:
+ * plan_csg_tile_nodes).  The condition is read from the two mask words render_tile loads anyway; the pre-pass knows
+ * nothing of this path.  Rendered whole — tap loop, samples, store — with the IEEE operations the general path performs
+ * for such a tile, on the same operands: screen_ray, normalized, make_ray; the two nodes in FILE order, the running
+ * best.dist handed from the first to the second (so the later node wins a tie) and its division skipped behind the
+ * second (node_intersect's `last`); the ground through the operations of raytrace()'s ground branch against that limit,
+ * the CsgOp through node_intersect<1, kFull> itself; the cube and sphere branches of leaf_surface and hit_surface for
+ * the lanes on the CsgOp, (0, 1, 0) and u = p.x, v = p.z for the lanes on the ground; faceforward, light_terms once,
+ * with the reflection under the mask of the lanes on a Phong CsgOp; test_visibility's ray, then the nodes `smask`
+ * keeps, in file order, a lane leaving at its first occluder — the ground dropped by the wave-uniform test
+ * test_visibility has for ground-only tiles (every lane's plane test would return at its first comparison), the CsgOp
+ * through node_intersect<1, kBool> with `own` for the lanes that start on it; shade()'s Lambert and Phong terms, the
+ * tap sum in the reference's order, `accum / taps`, the store; and the oob_notes of all of it.  One thing it leaves
+ * unexecuted: the shadow ray of a lane whose light terms are both off (see `lit_lane` below), whose answer nothing reads.
+ *
+ * What it does not carry: the loop over a mask, the flag tests and prep_dir selection of the ground node, the pass over
+ * distinct closest nodes, the leaf's record and the material read per lane — both children's records and both
+ * materials are wave-uniform scalar loads, the lane selects —, a Mat in vector registers (so the floor's texture goes
+ * through the uniform fetch, as in ground_tile), u,v of the CsgOp's leaves (the node has no texture).
+ *
+ * A lane whose CSG hit lists outgrew the wave's stack (Ctx::overflow; never at the capacity a depth-1 launch has) makes
+ * the wave write nothing, count the tile (redo_counter[3], c2rt_get_csg_tile_bails) and return kGroundBail: the general
+ * path renders it as if this function did not exist.  Returns per lane, like ground_tile.  The lane-statistics build
+ * keeps the path and counts the tiles it rendered (redo_counter[4], c2rt_get_csg_tiles).  Not taken for the short
+ * chain of ground_certain.h: its texel chain would have to stay live beside the CsgOp's walk, in a kernel that sits at
+ * its register budget. */
+template <int PO>
+DEV int csg_tile(const RenderParams &P, KArgs K, const uint32_t trow, const uint32_t bcol, const uint32_t node, const uint32_t smask)
+{
+    static_assert(!(PO & kSpecPlanes), "the planes-only instances have no mask table");
+    extern __shared__ __align__(16) char lds_all[];
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x / kWave;
+    const uint32_t tcol = bcol * kWavesPerBlock + wave;
+    const uint32_t x = tcol * kTileW + (lane % kTileW);
+    const uint32_t lr0 = trow * kTileH + (lane / kTileW);
+    if (x >= P.width || lr0 >= P.local_rows) return kGroundDone;
+    const uint32_t lr = lr0 + P.row_offset;
+    const uint32_t y = frame_row(P, lr);
+    const uint32_t ntaps = P.taps;
+#if C2RT_TILE_STATS
+    const unsigned long long stamp0 = __builtin_amdgcn_s_memtime();
+#endif
+
+    Ctx cx;
+    query_ctx(cx, P, K, lds_all + (size_t)wave * P.csg_cap * kCsgLdsPerEntry, lane);
+    cx.csg_certain = true;
+#if C2RT_TILE_STATS
+    cx.lane_stats = P.tile_stats ? reinterpret_cast<unsigned long long *>(P.tile_stats + 2 * (size_t)P.tiles_x * P.tiles_y) : nullptr;
+#endif
+    F3 accum = mkf(0, 0, 0);
+#pragma unroll 1
+    for (uint32_t s = 0; s < ntaps; ++s) {
+        KArgs Kt = K;
+        asm volatile("" : "+s"(Kt));
+        const RenderParams &Pt = *(const RenderParams *)Kt;
+        cx.geoms = (GeomP)Pt.geoms;
+        cx.csg_cap = (int)Pt.csg_cap;
+        Rng rng = {0u, 0, 0};
+        D3 o, raw;
+        screen_ray<0>(cx.bad, Pt, (double)x + k_aa_x[s], (double)y + k_aa_y[s], 0, rng, o, raw);
+        const D3 d = normalized(cx.bad, raw);
+        const uint32_t gnode = (uint32_t)Pt.ground_node;
+        NodeP Ng = (NodeP)Pt.nodes + gnode, Nc = (NodeP)Pt.nodes + node;
+        const bool ground_first = gnode < node; /* wave-uniform: the scene file's order */
+        /* raytrace(): the two nodes in file order */
+        const RayW ray = make_ray(cx.bad, o, d);
+        Hit best;
+        best.dist = 1e99;
+        best.g = -1;
+        best.code = 0;
+        D3 pg = o;
+        bool on_g = false, on_c = false;
+#pragma unroll 1
+        for (int i = 0; i < 2; ++i) {
+            const bool last = i == 1;
+            if ((i == 0) == ground_first) {
+                /* Node.intersect + Plane.intersect on the ground node (identity matrix, zero offset): the operations of
+                 * raytrace()'s ground branch, against the limit the node in front of it left */
+                const double gy = Ng->g.p[0], limit = Ng->g.p[1];
+                const D3 dn = ray.dn;
+                const bool away = ((o.y > gy) & (dn.y > -1e-9)) | ((o.y < gy) & (dn.y < 1e-9));
+                const double rden = rcp_refined(-dn.y);
+                const double mult = div_r(cx.bad, o.y - gy, -dn.y, rden);
+                const D3 p = o + dn * mult;
+                const bool miss = away | (mult > best.dist * ray.len) | (fabs(p.x) > limit) | (fabs(p.z) > limit);
+                if (!miss) {
+                    if (!last) best.dist = div_r(cx.bad, mult, ray.len, ray.inv);
+                    pg = p;
+                    on_g = true;
+                    on_c = false;
+                }
+            } else if (node_intersect<1, kFull, PO>(cx, Nc, ray, best, last)) {
+                on_c = true;
+                on_g = false;
+            }
+        }
+        F3 c = mkf(0, 0, 0); /* Environment.getEnvironment — rt/environment.d:7-10 */
+        if (on_g | on_c) {
+            /* hit_surface, with no pass per node: the lanes on the CsgOp take the normal of the child they hit — both
+             * children's records are scalar loads —, the lanes on the ground (0, 1, 0) */
+            D3 n = mk(0, 1, 0), p = pg;
+            if (on_c) {
+                GeomP G = &Nc->g;
+                const int left = G->left;
+                GeomP GL = cx.geoms + left, GR = cx.geoms + G->right;
+                const bool is_l = best.g == left;
+                const bool sphere = is_l ? GL->type == C2RT_GEOM_SPHERE : GR->type == C2RT_GEOM_SPHERE;
+                if (sphere) {
+                    const D3 ctr = is_l ? ld3(GL->p) : ld3(GR->p);
+                    n = normalized(cx.bad, best.p - ctr);
+                    if (best.code & kCodeFlip) n = -n;
+                    double len, inv;
+                    len_inv_unit(cx.bad, sqmag(n), len, inv);
+                    n = n * inv;
+                } else {
+                    const int axis = best.code & kCodeAxis;
+                    const double side = (best.code & kCodeSide) ? 1.0 : -1.0;
+                    n = mk(axis == 0 ? side : 0.0, axis == 1 ? side : 0.0, axis == 2 ? side : 0.0);
+                    if (best.code & kCodeFlip) n = -n;
+                }
+                p = best.p;
+                if (!(Nc->flags & kNodeZeroOffset)) p = p + ld3(Nc->off);
+            }
+            /* shade(): the CsgOp's material in scalar registers, the floor's inside its branch */
+            MatP Mc = &Nc->mat;
+            const bool phong = on_c & (Mc->shader_type == C2RT_SHADER_PHONG); /* (the floor is Lambert: ground_fast) */
+            const D3 Nf = dot(d, n) < 0 ? n : -n; /* faceforward */
+            F3 diffuse = ldf3(Mc->color);
+            if (on_g) {
+                Mat mg;
+                load_mat(Ng, mg);
+                diffuse = mg.tex_type == C2RT_TEX_CHECKER ? checker_color(mg, p.x, p.z)
+                        : (mg.tex_type >= 0 ? bitmap_color(Pt, mg, p.x, p.z) : mg.color);
+            }
+            F3 lightContrib = mkf(Pt.ambient[0], Pt.ambient[1], Pt.ambient[2]);
+            F3 specular = mkf(0, 0, 0);
+            if (Pt.n_lights) {
+                LightP L = (LightP)Pt.lights;
+                F3 avgColor = mkf(0, 0, 0), avgSpecular = mkf(0, 0, 0);
+                if (L->lit & 1u) {
+                    const D3 lightPos = ld3(L->pos);
+                    const D3 from = p + Nf * 1e-6;
+                    double cosTheta, cosGamma;
+                    F3 baseLight;
+                    light_terms(cx.bad, L, lightPos, p, Nf, d, phong, cosTheta, baseLight, cosGamma);
+                    /* The answer of test_visibility is read by the two additions at the end of this block and by nothing else:
+                     * a lane whose surface faces away from the light (cosTheta <= 0, or a NaN) and has no lobe towards the
+                     * eye casts no shadow ray — its pixel is the same float either way, and what goes unexecuted is the
+                     * most expensive thing such a lane does (a ray that starts on the CsgOp is decided by the literal
+                     * lists).  Its oob_notes go with it: a note only ever sends the tile to exact::, which computes the
+                     * same bits. */
+                    const bool lit_lane = (cosTheta > 0) | (phong & (cosGamma > 0));
+                    if (lit_lane) {
+                        /* test_visibility over the nodes the shadow mask keeps */
+                        const D3 sraw = lightPos - from;
+                        bool test_g = (smask >> gnode) & 1u; /* wave-uniform */
+                        const bool test_c = (smask >> node) & 1u;
+                        if (test_g) {
+                            /* every lane above the plane and heading up (or below and heading down): Plane.intersect
+                             * returns false at its first comparison for all of them */
+                            const double ground_y = Pt.ground_y;
+                            const bool sane = (fabs(sraw.x) < 1e150) & (fabs(sraw.z) < 1e150);
+                            const bool up = (sraw.y > 1e-150) & (sraw.y < 1e150), down = (sraw.y < -1e-150) & (sraw.y > -1e150);
+                            if (__all(sane & (((from.y > ground_y) & up) | ((from.y < ground_y) & down)))) test_g = false;
+                        }
+                        double rlen, rinv;
+                        len_inv(cx.bad, sqmag(sraw), rlen, rinv);
+                        const RayW sray = make_ray(cx.bad, from, mk(sraw.x * rinv, sraw.y * rinv, sraw.z * rinv));
+                        Hit temp;
+                        temp.dist = rlen;
+                        bool visible = true;
+#pragma unroll 1
+                        for (int i = 0; i < 2; ++i) {
+                            if ((i == 0) == ground_first) {
+                                if (test_g && visible) visible = !node_intersect<1, kBool, PO>(cx, Ng, sray, temp, false, false);
+                            } else {
+                                if (test_c && visible) visible = !node_intersect<1, kBool, PO>(cx, Nc, sray, temp, false, on_c);
+                            }
+                        }
+                        if (visible) {
+                            if (cosTheta > 0) avgColor = avgColor + baseLight * (float)cosTheta;
+                            if (phong & (cosGamma > 0))
+                                avgSpecular = avgSpecular + baseLight * c2_pow_f32(cosGamma, Mc->exponent) * Mc->strength;
+                        }
+                    }
+                }
+                lightContrib = lightContrib + avgColor;
+                specular = specular + avgSpecular;
+            }
+            const F3 res = diffuse * lightContrib;
+            c = phong ? res + specular : res;
+        }
+        accum = s == 0 ? c : accum + c;
+    }
+    /* `accum / 5` as render_tile has it (not tap_average: a Phong lobe's far tail leaves its window) */
+    if (ntaps > 1) accum = accum / (float)ntaps;
+    if (__ballot(cx.overflow)) {
+        if (lane == (int)__builtin_ctzll(__ballot(true))) atomicAdd(P.redo_counter + 3, 1ull); /* c2rt_get_csg_tile_bails */
+        return kGroundBail;
+    }
+    if (__ballot(oob_any(cx.bad))) return kGroundRedo;
+    store_pixel(P, (size_t)(P.frame_rows ? y : lr) * P.width + x, accum);
+#if C2RT_TILE_STATS
+    if (lane == (int)__builtin_ctzll(__ballot(true))) {
+        atomicAdd(P.redo_counter + 4, 1ull); /* c2rt_get_csg_tiles */
+        if (P.tile_stats) { /* the stamps render_tile leaves for a tile of the general path */
+            const unsigned long long dt = __builtin_amdgcn_s_memtime() - stamp0;
+            const uint32_t tile = trow * P.tiles_x + tcol;
+            P.tile_stats[2 * tile] = dt > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)dt;
+            P.tile_stats[2 * tile + 1] = ((1u << P.ground_node) | (1u << node)) << 8;
+        }
+    }
+#endif
+    return kGroundDone;
+}
+#endif /* C2RT_CSG_TILE */
+
 /*
  * Frame kernel: Renderer.renderRT passes 2 and 3b (rt/renderer.d:133-142,
  * 183-186) fused — all taps of a pixel are accumulated in registers in the
@@ -1731,6 +1956,30 @@ DEV bool render_tile(const RenderParams &P, KArgs K, const uint32_t b)
             if (!__ballot(g == kGroundBail)) return g == kGroundRedo;
         }
     }
+#if C2RT_CSG_TILE
+    /* Tile with the ground and ONE leaf CsgOp node the host marked (kNodeCsgTile) in its primary mask, and nothing beyond
+     * those two in its shadow mask: csg_tile renders it, or — a lane's hit lists outgrew the stack — writes nothing and
+     * the tile goes on below.  Read from the two words loaded above; the same kind of call as the two before it.  (The
+     * lane-statistics build keeps this path: it counts the tiles taken.)  In the identity-matrix instances only, which
+     * hold it in 126 VGPRs without scratch: the general depth-1 instance, at 128 VGPRs, went from 48 B to 112 B of scratch
+     * with it, so the planner marks no node in a scene that has a matrix (plan_csg_tile_nodes). */
+    if constexpr (kLean && LEVELS == 1 && !DOF && !MLC && !CNT && (PO & kSpecIdentity) && !(PO & kSpecPlanes)) {
+        if (P.ground_fast && !ground_only && P.n_nodes <= 32u) { /* wave-uniform */
+            const uint32_t live = 0xFFFFFFFFu >> (32u - P.n_nodes), gbit = 1u << P.ground_node;
+            const uint32_t pm = pmask & live, sm = smask0 & live, rest = pm & ~gbit;
+            if (__builtin_expect((pm & gbit) && rest && !(rest & (rest - 1u)) && !(sm & ~pm), 0)) {
+                uint32_t node_c = (uint32_t)__builtin_amdgcn_readfirstlane((int)__builtin_ctz(rest));
+                if (((NodeP)P.nodes)[node_c].flags & kNodeCsgTile) {
+                    KArgs Kc = K;
+                    uint32_t trow_c = trow, bcol_c = bcol, smask_c = (uint32_t)__builtin_amdgcn_readfirstlane((int)sm);
+                    asm volatile("" : "+s"(Kc), "+s"(trow_c), "+s"(bcol_c), "+s"(node_c), "+s"(smask_c));
+                    const int g = csg_tile<PO>(*(const RenderParams *)Kc, Kc, trow_c, bcol_c, node_c, smask_c);
+                    if (!__ballot(g == kGroundBail)) return g == kGroundRedo;
+                }
+            }
+        }
+    }
+#endif
 
     /* a scene whose only node is the ground plane (zaphod.sdl, lecture4.sdl): every tile is a ground
      * tile, wherever its rays start (depth of field, stereo) */

@@ -39,6 +39,13 @@
 #define C2RT_OWN(NEED) ((NEED) == kBool && own)
 #define C2RT_SELF , self
 #endif
+/* Likewise the straight-line path for tiles that hold the ground and one leaf CsgOp node (c2rt_trace.inc:
+ * lean::csg_tile, called from render_tile): frame units only, so that a query unit does not even parse it. */
+#ifdef C2RT_TRACE_EXACT_ONLY
+#define C2RT_CSG_TILE 0
+#else
+#define C2RT_CSG_TILE 1
+#endif
 
 namespace c2rt {
 namespace {

@@ -400,6 +400,20 @@ void plan_node_flags(const c2rt_scene_desc *s, ScenePlan &p)
         if (!(nodes[n].flags & kNodeIdentityMatrix)) p.all_identity = 0;
 }
 
+/* kNodeCsgTile (c2rt_device.h): the nodes lean::csg_tile may render beside the ground.  A scene fact: the frame's part of
+ * the condition (a mask table, no depth of field, no stereo, not counted, an eligible floor) is RenderParams::ground_fast. */
+void plan_csg_tile_nodes(const c2rt_scene_desc *s, ScenePlan &p)
+{
+    /* (every node under the identity matrix: the instances that carry the path, launch_render_level's `idn`) */
+    if (s->n_lights > 1 || !p.all_identity) return;
+    for (uint32_t n = 0; n < s->n_nodes && n < (uint32_t)kMaxCullNodes; ++n) {
+        DevNode &d = p.nodes[n];
+        const bool leaf = d.g.type >= C2RT_GEOM_CSG_UNION && (d.g.flags & kCsgCertain);
+        const bool shader = d.mat.shader_type == C2RT_SHADER_LAMBERT || d.mat.shader_type == C2RT_SHADER_PHONG;
+        if (leaf && (d.flags & kNodeIdentityMatrix) && shader && d.mat.tex_type < 0) d.flags |= kNodeCsgTile;
+    }
+}
+
 void plan_world_boxes(const c2rt_scene_desc *s, ScenePlan &p)
 {
     const std::vector<DevGeom> &geoms = p.geoms;
@@ -703,6 +717,7 @@ int plan_checked_scene(const c2rt_scene_desc *s, ScenePlan &plan, std::string &e
     if ((st = plan_lights(s, p, err)) != C2RT_OK) return st;
     if ((st = plan_nodes(s, p, err)) != C2RT_OK) return st;
     plan_node_flags(s, p);
+    plan_csg_tile_nodes(s, p);
     plan_world_boxes(s, p);
     plan_ground_rects(s, p);
     plan_void_nodes(s, p);
@@ -792,6 +807,11 @@ void drop_csg_certain(ScenePlan &plan)
 {
     for (DevGeom &g : plan.geoms) g.flags &= ~kCsgCertain;
     for (DevNode &n : plan.nodes) n.g.flags &= ~kCsgCertain;
+}
+
+void drop_csg_tile(ScenePlan &plan)
+{
+    for (DevNode &n : plan.nodes) n.flags &= ~kNodeCsgTile;
 }
 
 int replan_scene(const SceneCopy &scene, ScenePlan &plan, std::string &err)

@@ -64,6 +64,9 @@ int plan_scene(const c2rt_scene_desc *s, ScenePlan &plan, std::string &err);
 /* clears kCsgCertain (c2rt_device.h) in every record of `plan`: the diagnostics switch that leaves every CsgOp to the
  * literal evaluation */
 void drop_csg_certain(ScenePlan &plan);
+/* clears kNodeCsgTile (c2rt_device.h) in every node of `plan`: the diagnostics switch that leaves every tile with the
+ * ground and a leaf CsgOp node to the general path */
+void drop_csg_tile(ScenePlan &plan);
 
 /* ---- posing an uploaded scene (c2rt_update_scene, c2rt_render_frames_posed) ---- */
 
@@ -131,7 +134,8 @@ struct DiagKnobs {
      * dark-tile test in the mask pre-pass (dark_cull_of); bit 6: no short-chain ground tiles (RenderParams::ground_certain_cq
      * stays 0); bit 7: no sphere-interior tiles (SphereCull::interior stays 0); bit 8: sphere-interior
      * tiles whatever the frame's size (sphere_cull_of: kSphereTileMinSamples); bit 9: no CsgOp decided by csg_certain.h
-     * (drop_csg_certain on every plan: a switch of the scene's tables, not of a frame) */
+     * (drop_csg_certain on every plan: a switch of the scene's tables, not of a frame); bit 10: no ground-and-CsgOp tiles
+     * through lean::csg_tile (drop_csg_tile on every plan, likewise) */
     int debug_cull = 0;
     int csg_first_cap = 0;             /* C2RT_CSG_FIRST_CAP=<entries>: the first pass's hit-stack capacity */
 };

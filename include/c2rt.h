@@ -479,6 +479,17 @@ int c2rt_get_ground_bails(c2rt_ctx *ctx, uint64_t *out);
  * c2rt_get_exact_redos, never a matter of correctness. */
 int c2rt_get_sphere_bails(c2rt_ctx *ctx, uint64_t *out);
 
+/* How many 8x8 tiles that hold the ground and one leaf CsgOp node this context has handed back to the general path since
+ * it was created (synchronises the device).  Such a tile is rendered by straight-line code for exactly those two nodes
+ * (chess2rt_amd/csrc/c2rt_trace.inc: csg_tile); a tile in which a lane's CSG hit lists outgrow the wave's stack writes
+ * nothing and is rendered by the general path at once.  0 on the shipped scenes; a cost indicator like
+ * c2rt_get_exact_redos, never a matter of correctness. */
+int c2rt_get_csg_tile_bails(c2rt_ctx *ctx, uint64_t *out);
+
+/* Diagnostics: how many tiles that path has rendered since the context was created (synchronises the device).  Counted
+ * by the lane-statistics build of the library only (chess2rt_amd/libc2rt_lanestats.so); 0 in every other build. */
+int c2rt_get_csg_tiles(c2rt_ctx *ctx, uint64_t *out);
+
 /* Pixel probe: mirrors `renderPixel` (rt/renderer.d:46-57): one sample at
  * integer (x, y), no AA, returns the colour and the trace result. */
 int c2rt_render_pixel(c2rt_ctx *ctx, const c2rt_camera_frame *cam,
