@@ -45,6 +45,7 @@ KERNELFLAGS_u5 :=
 # c2rt_shade_planes (the terms of a sample's colour, c2rt_render_shading / c2rt_trace_rays_shading),
 # c2rt_occlusion (hemisphere visibility of every hit, c2rt_render_occlusion / c2rt_trace_rays_occlusion),
 # c2rt_gather (one-bounce indirect light of every hit, c2rt_render_gather / c2rt_trace_rays_gather),
+# c2rt_paths (multi-bounce indirect light of every hit, c2rt_render_paths / c2rt_trace_rays_paths),
 # c2rt_adaptive (adaptive anti-aliasing, c2rt_render_frame_adaptive: detection and refinement),
 # c2rt_sample_taps (frames and adaptive refinement over a caller's tap table, c2rt_render_frame_taps); the
 # flags of the frame units were tuned on the frame kernels and have not been measured here
@@ -58,7 +59,7 @@ BUILD      := build$(if $(VARIANT),_$(VARIANT))
 LIBNAME    := chess2rt_amd/libc2rt$(if $(VARIANT),_$(VARIANT)).so
 
 UNITS      := 0 1 2 3 4 5
-QUERIES    := c2rt_rays c2rt_hit_planes c2rt_layers c2rt_shade_planes c2rt_occlusion c2rt_gather c2rt_adaptive c2rt_sample_taps
+QUERIES    := c2rt_rays c2rt_hit_planes c2rt_layers c2rt_shade_planes c2rt_occlusion c2rt_gather c2rt_paths c2rt_adaptive c2rt_sample_taps
 KOBJS      := $(foreach u,$(UNITS),$(BUILD)/c2rt_kernels_u$(u).o) $(foreach q,$(QUERIES),$(BUILD)/$(q).o)
 HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/scene.o $(BUILD)/host_api.o
 

@@ -215,6 +215,26 @@ class GatherPlanes(C.Structure):
     ]
 
 
+class PathOpts(C.Structure):
+    """c2rt_path_opts: the counter RNG's seed, the path count P (1 .. 64) and the bounce count B (1 .. 8)"""
+    _fields_ = [
+        ("seed", C.c_uint64),
+        ("paths", C.c_uint32),
+        ("bounces", C.c_uint32),
+    ]
+
+
+class PathPlanes(C.Structure):
+    """c2rt_path_planes: one nullable pointer per plane (host or device memory, by entry point)"""
+    _fields_ = [
+        ("node", C.c_void_p),
+        ("segments", C.c_void_p),
+        ("indirect", C.c_void_p),
+        ("bounce", C.c_void_p),
+        ("radiance", C.c_void_p),
+    ]
+
+
 class ScenePose(C.Structure):
     """c2rt_scene_pose: new transforms ([n_nodes][30] doubles) and light values for some nodes / lights of the uploaded scene"""
     _fields_ = [
@@ -323,6 +343,10 @@ C2RT_SYMBOLS = {
     "c2rt_render_gather": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(GatherOpts), C.POINTER(GatherPlanes)]),
     "c2rt_trace_rays_gather_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(GatherOpts), C.POINTER(GatherPlanes), _VP]),
     "c2rt_trace_rays_gather": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(GatherOpts), C.POINTER(GatherPlanes)]),
+    "c2rt_render_paths_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(PathOpts), C.POINTER(PathPlanes), _VP]),
+    "c2rt_render_paths": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(PathOpts), C.POINTER(PathPlanes)]),
+    "c2rt_trace_rays_paths_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(PathOpts), C.POINTER(PathPlanes), _VP]),
+    "c2rt_trace_rays_paths": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(PathOpts), C.POINTER(PathPlanes)]),
     "c2rt_render_frame_adaptive_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frame_adaptive": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frames_adaptive_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
@@ -363,7 +387,8 @@ C2RT_HOST_SYMBOLS = {
     "c2rt_host_render_shading": (C.c_int, [_VP, _VP, C.POINTER(ShadePlanes)]),
     "c2rt_host_render_occlusion": (C.c_int, [_VP, _VP, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes)]),
     "c2rt_host_render_gather": (C.c_int, [_VP, _VP, C.POINTER(GatherOpts), C.POINTER(GatherPlanes)]),
-    "c2rt_host_render_rt_adaptive": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "c2rt_host_render_paths": (C.c_int, [_VP, _VP, C.POINTER(PathOpts), C.POINTER(PathPlanes)]),
+    "c2rt_host_render_rt_adaptive":(C.c_int, [_VP, _VP, _VP, _VP]),
     "c2rt_host_render_rt_taps": (C.c_int, [_VP, _VP, _TAPS_P, _VP]),
     "c2rt_host_render_rt_adaptive_taps": (C.c_int, [_VP, _VP, _TAPS_P, _VP, _VP]),
     "c2rt_host_bmp_decode": (C.c_int, [_VP, C.c_size_t, _u32p, _u32p, C.POINTER(_f32p)]),

@@ -5,15 +5,15 @@ Thin wrappers over the C ABI (include/c2rt.h) and the C++ host mirror
 (rt/scene_loader.d:20-41), ``Scene.beginFrame`` (rt/scene.d:55-58),
 ``Renderer.renderRT`` / ``renderPixelNoAA`` (rt/renderer.d:83,223),
 ``renderPixel`` (rt/renderer.d:46-57).  Python holds no algorithm: all
-rendering happens in libc2rt.so on the GPU.  The hit, shading, occlusion and
-gather planes are each described once (``_PlaneFamily``: struct, table, noun).
+rendering happens in libc2rt.so on the GPU.  The hit, shading, occlusion, gather
+and path planes are each described once (``_PlaneFamily``: struct, table, noun).
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _abi
-from ._abi import (CameraFrame, GatherOpts, GatherPlanes, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
+from ._abi import (CameraFrame, GatherOpts, GatherPlanes, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
                    ScenePose, Segment, ShadePlanes, TapTable, TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
@@ -68,11 +68,14 @@ SHADE_PLANES = {"node": (np.int32, 1), "albedo": (np.float32, 3), "light": (np.f
 OCCLUSION_PLANES = {"node": (np.int32, 1), "open": (np.uint64, 1), "ao": (np.float32, 1), "bent": (np.float64, 3)}
 # c2rt_gather_planes: plane name -> (dtype, components per sample), in the order of the struct's members
 GATHER_PLANES = {"node": (np.int32, 1), "hits": (np.uint64, 1), "indirect": (np.float32, 3), "bounce": (np.float32, 3)}
+# c2rt_path_planes: plane name -> (dtype, components per sample), in the order of the struct's members
+PATH_PLANES = {"node": (np.int32, 1), "segments": (np.uint32, 1), "indirect": (np.float32, 3), "bounce": (np.float32, 3), "radiance": (np.float32, 3)}
 
 _HIT = _PlaneFamily(HitPlanes, HIT_PLANES, "hit")
 _SHADE = _PlaneFamily(ShadePlanes, SHADE_PLANES, "shading")
 _OCCLUSION = _PlaneFamily(OcclusionPlanes, OCCLUSION_PLANES, "occlusion")
 _GATHER = _PlaneFamily(GatherPlanes, GATHER_PLANES, "gather")
+_PATHS = _PlaneFamily(PathPlanes, PATH_PLANES, "path")
 
 
 def _rays_array(rays, what="rays"):
@@ -115,6 +118,10 @@ def _tap_table(taps):
 
 def _gather_opts(samples, seed):
     return GatherOpts(seed=int(seed), samples=int(samples), reserved=0)
+
+
+def _path_opts(paths, bounces, seed):
+    return PathOpts(seed=int(seed), paths=int(paths), bounces=int(bounces))
 
 
 def makePose(nodes=None, lights=None):
@@ -800,6 +807,41 @@ class Context:
         pl = _GATHER.device(ptrs)
         self._check(self._lib.c2rt_trace_rays_gather_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(g), C.byref(pl), C.c_void_p(stream)))
 
+    def renderPaths(self, cam, opts, paths, bounces, seed=0, planes=tuple(PATH_PLANES)):
+        """Multi-bounce indirect diffuse light of every pixel's closest hit (c2rt_render_paths): `paths` (1 .. 64) paths
+        of at most min(`bounces` (1 .. 8), the scene's max_trace_depth) segments behind the hit, every segment shaded as
+        traceRays shades a ray.  Planes (PATH_PLANES): node, segments (how many spawned segments hit a node), indirect,
+        bounce (albedo * indirect), radiance (the frame's colour + bounce); a dict of arrays of shape (localRows, width)
+        and (localRows, width, 3).  With bounces == 1: renderGather's indirect and bounce at samples == paths.  Depth of
+        field, stereo, count_rays and prepass_bucket are refused."""
+        g = _path_opts(paths, bounces, seed)
+        pl, out = _PATHS.new(planes, (self.localRows(opts), opts.width))
+        self._check(self._lib.c2rt_render_paths(self._h, C.byref(cam), C.byref(opts), C.byref(g), C.byref(pl)))
+        return out
+
+    def renderPathsDevice(self, cam, opts, paths, bounces, ptrs, seed=0, stream=0):
+        """Enqueue the path planes on `stream` into device memory: `ptrs` maps plane names (PATH_PLANES) to device
+        pointers; planes left out are not computed."""
+        g = _path_opts(paths, bounces, seed)
+        pl = _PATHS.device(ptrs)
+        self._check(self._lib.c2rt_render_paths_device(self._h, C.byref(cam), C.byref(opts), C.byref(g), C.byref(pl), C.c_void_p(stream)))
+
+    def traceRaysPaths(self, rays, paths, bounces, seed=0, planes=tuple(PATH_PLANES)):
+        """The same planes for caller-supplied rays (c2rt_trace_rays_paths): `rays` as for traceRays; a dict of arrays of
+        shape (n,) and (n, 3).  Ray i draws the paths of index i."""
+        rays = _rays_array(rays)
+        g = _path_opts(paths, bounces, seed)
+        pl, out = _PATHS.new(planes, (rays.shape[0],))
+        self._check(self._lib.c2rt_trace_rays_paths(self._h, rays.ctypes.data_as(C.c_void_p), rays.shape[0], C.byref(g), C.byref(pl)))
+        return out
+
+    def traceRaysPathsDevice(self, rays_ptr, n, paths, bounces, ptrs, seed=0, stream=0):
+        """Enqueue the query on `stream` over device memory: n c2rt_ray at rays_ptr, `ptrs` as for renderPathsDevice with
+        n samples per plane."""
+        g = _path_opts(paths, bounces, seed)
+        pl = _PATHS.device(ptrs)
+        self._check(self._lib.c2rt_trace_rays_paths_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(g), C.byref(pl), C.c_void_p(stream)))
+
     def testVisibility(self, segments):
         """Scene.testVisibility for (n, 6) float64 segments (from, to): (n,) uint8, 1 = nothing in between."""
         seg = _rays_array(segments, "segments")
@@ -933,6 +975,16 @@ class Renderer:
         g = _gather_opts(samples, seed)
         pl, out = _GATHER.new(planes, (s.frame_height, s.frame_width))
         self.ctx._check(self._lib.c2rt_host_render_gather(self.ctx.handle, self.scene._h, C.byref(g), C.byref(pl)))
+        return out
+
+    def renderPaths(self, paths=None, bounces=None, seed=0, planes=tuple(PATH_PLANES)):
+        """Context.renderPaths for the scene's own camera and frame size (c2rt_host_render_paths): renderSampleGI's
+        frame (rt/renderer.d:289-301) as the `radiance` plane.  None takes the scene's own pathsPerPixel / maxTraceDepth;
+        a setting beyond the library's limits is refused by the library (C2rtError, ERR_LIMIT)."""
+        s = self.scene.settings
+        g = _path_opts(s.paths_per_pixel if paths is None else paths, s.max_trace_depth if bounces is None else bounces, seed)
+        pl, out = _PATHS.new(planes, (s.frame_height, s.frame_width))
+        self.ctx._check(self._lib.c2rt_host_render_paths(self.ctx.handle, self.scene._h, C.byref(g), C.byref(pl)))
         return out
 
 

@@ -3,7 +3,7 @@
  * upload of a planned scene (scene_plan.h: SoA tables -> scalar-loadable records in HBM),
  * frame / pixel-probe launches, the ray and plane queries, strip de-interleave and display encode.
  *
- * The hit, shading, occlusion and gather planes are one code path: each family is described once (Family<S>: sample
+ * The hit, shading, occlusion, gather and path planes are one code path: each family is described once (Family<S>: sample
  * sizes, the words of its messages, its options and their refusals) and its entry points are one-line calls of the
  * four faces frame_planes_device / frame_planes_host / ray_planes_device / ray_planes_host.
  *
@@ -1450,10 +1450,26 @@ template <> struct Family<c2rt_gather_planes> {
         return C2RT_OK;
     }
 };
+template <> struct Family<c2rt_path_planes> {
+    static constexpr size_t bytes[] = {4, 4, 12, 12, 12}; /* 44 B per sample */
+    static constexpr const char *planes = "path", *holds = "paths are", *count = "five", *name = "c2rt_path_planes", *what = "path plane";
+    using Opts = c2rt_path_opts;
+    static int check_opts(c2rt_ctx *ctx, const Opts *g)
+    {
+        if (!g) return fail(ctx, C2RT_ERR_INVALID_ARG, "null path options");
+        if (g->paths == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "paths is 0: at least one path");
+        if (g->bounces == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "bounces is 0: at least one bounce");
+        if (g->paths > C2RT_MAX_PATHS) return fail(ctx, C2RT_ERR_LIMIT, "%u paths (at most %u)", (unsigned)g->paths, (unsigned)C2RT_MAX_PATHS);
+        if (g->bounces > C2RT_MAX_PATH_BOUNCES)
+            return fail(ctx, C2RT_ERR_LIMIT, "%u bounces (at most %u)", (unsigned)g->bounces, (unsigned)C2RT_MAX_PATH_BOUNCES);
+        return C2RT_OK;
+    }
+};
 static_assert(sizeof Family<c2rt_hit_planes>::bytes == kPlanes<c2rt_hit_planes> * sizeof(size_t) &&
               sizeof Family<c2rt_shade_planes>::bytes == kPlanes<c2rt_shade_planes> * sizeof(size_t) &&
               sizeof Family<c2rt_occlusion_planes>::bytes == kPlanes<c2rt_occlusion_planes> * sizeof(size_t) &&
-              sizeof Family<c2rt_gather_planes>::bytes == kPlanes<c2rt_gather_planes> * sizeof(size_t), "a sample size for every plane");
+              sizeof Family<c2rt_gather_planes>::bytes == kPlanes<c2rt_gather_planes> * sizeof(size_t) &&
+              sizeof Family<c2rt_path_planes>::bytes == kPlanes<c2rt_path_planes> * sizeof(size_t), "a sample size for every plane");
 static constexpr NoOpts kNoOpts = {};
 
 /* What a host variant stages: its outputs in staging order.  An output is `layers` slices (layer-major on both sides)
@@ -1586,8 +1602,8 @@ int c2rt_test_visibility(c2rt_ctx *ctx, const c2rt_segment *seg, uint64_t n, uin
     });
 }
 
-/* ---- plane families: hit, shading, occlusion and gather planes of a camera frame or of a caller's rays --------------- */
-/* (c2rt_hit_planes.hip, c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_gather.hip; each described by its Family above) */
+/* ---- plane families: hit, shading, occlusion, gather and path planes of a camera frame or of a caller's rays --------- */
+/* (c2rt_hit_planes.hip, c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_gather.hip, c2rt_paths.hip; each described by its Family above) */
 
 /* The refusals of the modes in which a pixel is not one ray, in the documented order; `holds`: what a pixel holds in the
  * call ("record is", "terms are"), `planes`: which planes it fills ("hit", "shading") */
@@ -1647,7 +1663,7 @@ static int frame_planes_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, cons
 }
 
 /* Host variant: chunks of whole rows, at most kQueryChunk pixels each (row_chunks), plane after plane for the chunk size
- * and only for the planes asked for — 92 / 56 / 40 / 36 B per pixel, 23 / 14 / 10 / 9 MiB at most, whatever the frame
+ * and only for the planes asked for — 92 / 56 / 40 / 36 / 44 B per pixel, 23 / 14 / 10 / 9 / 11 MiB at most, whatever the frame
  * size.  A chunk's pixels draw the samples of their place in the frame. */
 template <class S>
 static int frame_planes_host(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const typename Family<S>::Opts *o,
@@ -1769,6 +1785,29 @@ int c2rt_trace_rays_gather_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint6
 }
 
 int c2rt_trace_rays_gather(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const c2rt_gather_opts *g, const c2rt_gather_planes *planes_host)
+{
+    return ray_planes_host(ctx, rays, n, g, planes_host);
+}
+
+int c2rt_render_paths_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_path_opts *g,
+                             const c2rt_path_planes *planes_dev, void *hip_stream)
+{
+    return frame_planes_device(ctx, cam, opts, g, planes_dev, hip_stream);
+}
+
+int c2rt_render_paths(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_path_opts *g,
+                      const c2rt_path_planes *planes_host)
+{
+    return frame_planes_host(ctx, cam, opts, g, planes_host);
+}
+
+int c2rt_trace_rays_paths_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, const c2rt_path_opts *g, const c2rt_path_planes *planes_dev,
+                                 void *hip_stream)
+{
+    return ray_planes_device(ctx, rays_dev, n, g, planes_dev, hip_stream);
+}
+
+int c2rt_trace_rays_paths(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const c2rt_path_opts *g, const c2rt_path_planes *planes_host)
 {
     return ray_planes_host(ctx, rays, n, g, planes_host);
 }

@@ -1,5 +1,5 @@
 /*
- * c2rt_query.h — launch interface of the query kernels (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip, c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_gather.hip, c2rt_adaptive.hip, c2rt_sample_taps.hip), shared
+ * c2rt_query.h — launch interface of the query kernels (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip, c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_gather.hip, c2rt_paths.hip, c2rt_adaptive.hip, c2rt_sample_taps.hip), shared
  * by those files and c2rt_api.cpp.  A header of its own: c2rt_device.h is a prerequisite of every frame-kernel object,
  * and query work should not rebuild them.  All return hipError_t as int; every pointer is a device pointer.
  *
@@ -14,17 +14,19 @@
 
 namespace c2rt {
 
-/* A plane struct (c2rt_hit_planes, c2rt_shade_planes, c2rt_occlusion_planes, c2rt_gather_planes) as the host code sees
+/* A plane struct (c2rt_hit_planes, c2rt_shade_planes, c2rt_occlusion_planes, c2rt_gather_planes, c2rt_path_planes) as the host code sees
  * it: nothing but pointers, kPlanes<S> of them (c2rt_api.cpp keeps the sample size of each next to the family's words) */
 template <class S> constexpr int kPlanes = 0;
 template <> inline constexpr int kPlanes<c2rt_hit_planes> = 7;
 template <> inline constexpr int kPlanes<c2rt_shade_planes> = 6;
 template <> inline constexpr int kPlanes<c2rt_occlusion_planes> = 4;
 template <> inline constexpr int kPlanes<c2rt_gather_planes> = 4;
+template <> inline constexpr int kPlanes<c2rt_path_planes> = 5;
 static_assert(sizeof(c2rt_hit_planes) == kPlanes<c2rt_hit_planes> * sizeof(void *) &&
               sizeof(c2rt_shade_planes) == kPlanes<c2rt_shade_planes> * sizeof(void *) &&
               sizeof(c2rt_occlusion_planes) == kPlanes<c2rt_occlusion_planes> * sizeof(void *) &&
-              sizeof(c2rt_gather_planes) == kPlanes<c2rt_gather_planes> * sizeof(void *), "the plane structs are arrays of pointers");
+              sizeof(c2rt_gather_planes) == kPlanes<c2rt_gather_planes> * sizeof(void *) &&
+              sizeof(c2rt_path_planes) == kPlanes<c2rt_path_planes> * sizeof(void *), "the plane structs are arrays of pointers");
 
 /* "at least one plane asked for": what the launches below and the entry points of c2rt_api.cpp both refuse without */
 template <class S>
@@ -81,6 +83,14 @@ int launch_plane_rows(const RenderParams &p, int csg_levels, const c2rt_gather_o
                       void *stream);
 int launch_plane_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_gather_opts &g,
                       const c2rt_gather_planes &out, void *stream);
+/* Path planes (c2rt_render_paths*, c2rt_trace_rays_paths*; c2rt_paths.hip): the hit planes' rows, or the ray query's rays,
+ * with g.paths paths of at most g.bounces segments behind every hit, each segment traced and shaded as c2rt_trace_rays'
+ * rays are; at least one plane non-null, 1 <= g.paths <= C2RT_MAX_PATHS, 1 <= g.bounces <= C2RT_MAX_PATH_BOUNCES.  Ray
+ * i draws the paths of index base + i */
+int launch_plane_rows(const RenderParams &p, int csg_levels, const c2rt_path_opts &g, const c2rt_path_planes &out, uint32_t row0, uint32_t rows,
+                      void *stream);
+int launch_plane_rays(const RenderParams &p, int csg_levels, const c2rt_ray *rays, uint64_t n, uint64_t base, const c2rt_path_opts &g,
+                      const c2rt_path_planes &out, void *stream);
 /* Adaptive anti-aliasing (c2rt_render_frame[s]_adaptive*): the flag images needs_aa[i][y][x] of n_frames whole one-tap
  * frames side by side, then the flagged pixels of the whole frame `p` describes (no strips) from their one-tap to their
  * five-tap value, in place; launch_aa_refine_batch: the same for the n_frames frames whose blocks are at table_dev (p0:

@@ -1,6 +1,6 @@
 /*
  * c2rt_query.inc — what the query kernels share (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip,
- * c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_gather.hip, c2rt_adaptive.hip, c2rt_sample_taps.hip): a lane traces
+ * c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_gather.hip, c2rt_paths.hip, c2rt_adaptive.hip, c2rt_sample_taps.hip): a lane traces
  * ONE ray that is not a frame tile's — the caller's, or the camera's through a pixel — with exact:: arithmetic (the probe's choice; bit-equal to what the frames compute), every
  * culling mask all ones (query_ctx, c2rt_trace_shared.inc), no ground-tile shortcut, and a full-capacity CSG hit stack:
  * kCsgFullCap(LEVELS) entries in one launch, which cannot overflow, so there is no retry list and no per-stream scratch.
@@ -11,7 +11,7 @@
  *
  * Each piece once, in this order: the ABI layout the lane code relies on; the register budget; where a lane's sample
  * comes from (load6 for a caller's record, tile_pixel and pixel_ray for a camera's pixel; hemisphere_sample for the
- * directions the occlusion and gather planes draw behind a hit); where its result goes
+ * directions the occlusion, gather and path planes draw behind a hit); where its result goes
  * (store_colour, store_record, sample_colour, store_hit_planes); the host side of a launch (ray_grid, tile_grid,
  * launch_query; launch_rows_of and launch_rays_of, the two launch shapes of the plane families).
  */
@@ -90,7 +90,7 @@ DEV void pixel_ray(const Ctx &cx, const RenderParams &P, double x, double y, D3 
     d = exact::normalized(cx.bad, raw);
 }
 
-/* hemisphereSample(N), rt/shader.d:156-174, draw s of the sample whose key is `key` (the occlusion and gather planes):
+/* hemisphereSample(N), rt/shader.d:156-174, draw s of the sample whose key is `key` (the occlusion, gather and path planes):
  * theta = 2 pi u, phi = acos(w) - pi / 2 with w = 2 v - 1, so sin(phi) = -w and cos(phi) = sqrt(1 - w^2) — IEEE +, *,
  * sqrt and lens_sincos2pi only, no libm (include/c2rt.h, the definition of a sample under "occlusion planes") */
 DEV D3 hemisphere_sample(const uint32_t key, const uint32_t s, const D3 N)
@@ -199,7 +199,7 @@ int launch_query(const RenderParams &p, K *several, K *one, dim3 grid, size_t ld
 }
 
 /* The two launch shapes of the plane families (launch_plane_rows / launch_plane_rays of each unit): refuse, size the grid,
- * pick the CSG depth.  opts_ok: the unit's option struct converted (OccArgs, GatherArgs; true where there is none).
+ * pick the CSG depth.  opts_ok: the unit's option struct converted (OccArgs, GatherArgs, PathArgs; true where there is none).
  * launch(L, grid, tiles_x) / launch(L, grid) enqueues the unit's kernel of depth decltype(L)::value, so a unit names
  * only the instances it had before, whether its kernels template on LEVELS alone or on LEVELS and MLC. */
 template <class S, class Launch>

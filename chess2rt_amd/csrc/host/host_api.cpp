@@ -305,6 +305,15 @@ int c2rt_host_render_gather(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_gather
     return c2rt_render_gather(ctx, &cam, &o, g, planes);
 }
 
+int c2rt_host_render_paths(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_path_opts *g, const c2rt_path_planes *planes)
+{
+    // c2rt_host_render_hits' set-up; the options, the planes and the camera are judged by c2rt_render_paths
+    c2rt_camera_frame cam;
+    c2rt_render_opts o;
+    if (const int st = frame_setup(ctx, s, true, cam, o)) return st;
+    return c2rt_render_paths(ctx, &cam, &o, g, planes);
+}
+
 int c2rt_host_render_rt_adaptive(c2rt_ctx *ctx, c2rt_host_scene *s, float *out_rgb, uint8_t *needs_aa)
 {
     // renderRT's passes 2, 3a and 3b (rt/renderer.d:132-188) with 3b on the flagged pixels only

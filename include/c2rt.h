@@ -924,6 +924,103 @@ int c2rt_trace_rays_gather_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint6
 int c2rt_trace_rays_gather(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n,
                            const c2rt_gather_opts *g, const c2rt_gather_planes *planes_host);
 
+/* ---- path planes: multi-bounce indirect diffuse light of every hit ----------- */
+
+/* Most paths per sample and most bounces per path; C2RT_ERR_LIMIT beyond. */
+#define C2RT_MAX_PATHS        64
+#define C2RT_MAX_PATH_BOUNCES  8
+
+typedef struct c2rt_path_opts {        /* 16 bytes */
+    uint64_t seed;       /* counter-RNG seed (opts->seed of a camera call is ignored) */
+    uint32_t paths;      /* P: 1 .. C2RT_MAX_PATHS */
+    uint32_t bounces;    /* B: 1 .. C2RT_MAX_PATH_BOUNCES; what is traced is Beff = min(B, scene max_trace_depth) */
+} c2rt_path_opts;
+
+typedef struct c2rt_path_planes {      /* 40 bytes; every pointer nullable, at least one given */
+    int32_t  *node;      /* [..]    closest node, -1: no hit (the hit planes' `node`) */
+    uint32_t *segments;  /* [..]    spawned segments that hit a node, over all paths and depths (<= P * Beff) */
+    float    *indirect;  /* [..][3] mean weighted light arriving at the hit, all depths */
+    float    *bounce;    /* [..][3] albedo * indirect */
+    float    *radiance;  /* [..][3] rgb + bounce: the global-illumination frame itself */
+} c2rt_path_planes;
+
+/* Multi-bounce indirect diffuse light of the closest hit of ONE sample: renderSampleGI's pathsPerPixel paths of up to
+ * maxTraceDepth bounces (rt/renderer.d:289-301, pathtrace_impl 378-463).  P paths leave the hit as the gather planes'
+ * rays do; where a segment hits, the path goes on from Lambert.spawnRay's origin of that hit along another direction of
+ * hemisphereSample, its throughput multiplied by the albedo of the vertex it leaves and by brdfEval / pdf without the
+ * albedo.  Every segment is given the colour of Renderer.raytrace — what c2rt_trace_rays returns as `rgb`.  Sample index
+ * idx and ray (o, d) are exactly the gather planes' —
+ *   camera calls: idx = FRAME row * W + column (strips and host chunks do not change it), (o, d) the ray
+ *     c2rt_render_hits traces for the pixel; planes are row-major [local_rows][W], strips as there;
+ *   ray calls: idx = the ray's index i in the caller's array (whatever chunk it travels in), `dir` exactly as given;
+ *     planes are [n] —
+ *   and with Beff = min(bounces, the scene's max_trace_depth):
+ *
+ *     rec = what c2rt_trace_rays computes for (o, d)                      -- node := rec.closest_node
+ *     miss, or Beff == 0:
+ *            segments = 0, indirect = bounce = +0,+0,+0, radiance = the ray's c2rt_trace_rays rgb; nothing is drawn
+ *     hit:   N0 = dot(d, rec.normal) < 0 ? rec.normal : -rec.normal       -- faceforward
+ *            from0 = rec.p + N0 * 1e-6
+ *            a0  = the shading planes' `albedo` for (o, d)
+ *            sum = (+0f, +0f, +0f);  segments = 0
+ *            for p in 0 .. P-1:                                           -- path-major ...
+ *                from = from0;  N = N0
+ *                for j in 0 .. Beff-1:                                    -- ... bounce-minor: this ORDER of the fp32
+ *                                                                            sum is the contract
+ *                    res  = the occlusion planes' direction for (rng_key(seed, idx, j), p, N)
+ *                                                                         -- tap = depth, sample = path; j == 0: the
+ *                                                                            gather planes' draws
+ *                    w    = (float)(2.0 * ((res.x*N.x + res.y*N.y) + res.z*N.z))
+ *                    T.c  = j == 0 ? w : (T.c * a.c) * w                  -- fp32, two multiplies in this order;
+ *                                                                            a: albedo of the vertex just left
+ *                    (r, L) = c2rt_trace_rays' record and rgb for the ray (from, res), `dir` exactly as given
+ *                                                                         -- a miss: L = +0,+0,+0
+ *                    sum.c = sum.c + L.c * T.c                            -- fp32 multiply, then fp32 add, not
+ *                                                                            contracted; executed for a miss too
+ *                    if r.closest_node < 0: break
+ *                    segments += 1
+ *                    a = the shading planes' `albedo` for (from, res)
+ *                    N = dot(res, r.normal) < 0 ? r.normal : -r.normal;  from = r.p + N * 1e-6
+ *            indirect.c = sum.c / (float)P
+ *            bounce.c   = a0.c * indirect.c
+ *            radiance.c = rgb.c + bounce.c                                -- rgb: c2rt_trace_rays' for (o, d)
+ *
+ *   - Composition is the contract: every plane is, BIT FOR BIT, what a caller gets from c2rt_trace_rays (records and
+ *     rgb), c2rt_trace_rays_shading (`albedo`) and the fp32 arithmetic above.  No libm call of its own.
+ *   - With bounces == 1 `indirect` and `bounce` are the gather planes' bits at samples == P and the same seed, and
+ *     `segments` is the popcount of their `hits`.
+ *   - Why Beff: the spawned ray at vertex j has depth j + 1, and trace() returns black before intersecting once the
+ *     depth exceeds maxTraceDepth (rt/renderer.d:330).  max_trace_depth == 0 draws nothing.
+ *   - What is written to a plane never depends on which others are asked for.  `node` alone traces no path; `node` +
+ *     `segments` cast no shadow ray and fetch no albedo (closest-hit searches only); only `radiance` casts the primary
+ *     hit's shadow rays.
+ *   - A lane of NaNs, zeros or 1e300 ends after at most P * Beff segments and changes no other sample's result.
+ *   - Build-defined: the gather planes' list (the draws, the rounding of `w`, that the multiplier is applied at all,
+ *     that every vertex takes raytrace's direct light from all lights — the reference's one random light has
+ *     solidAngle == 0 and contributes nothing), and two more: every material continues the path as Lambert does (the
+ *     reference's Phong.spawnRay is assert(0)); the primary ray is not jittered (renderSampleGI's x + uniform * dx is
+ *     what the sample tables are for).  gi_enabled stays refused.
+ *
+ * Statuses, all decided before anything is enqueued or written, each with its own message.  Camera calls: those of a
+ * frame call, in c2rt_render_hits' order; ray calls: those of c2rt_trace_rays, in its order (n == 0 is C2RT_OK whatever
+ * else is passed).  Then, for both: null `g`, paths == 0, bounces == 0: C2RT_ERR_INVALID_ARG; paths > C2RT_MAX_PATHS,
+ * bounces > C2RT_MAX_PATH_BOUNCES: C2RT_ERR_LIMIT, in this order; null `planes`, or all five pointers null:
+ * C2RT_ERR_INVALID_ARG.  Camera calls then: C2RT_ERR_UNSUPPORTED naming "depth of field", "stereo", "count_rays",
+ * "prepass_bucket".
+ *
+ * The _device variants take device pointers and enqueue ONE kernel on `hip_stream`: no host sync, no event, no scratch
+ * slot, nothing kept of the stream; on a multi-device context, the lead device; after c2rt_update_scene they see the
+ * posed scene.  The host variants go through the context's staging buffer on the context's own stream in chunks of whole
+ * rows (or rays) of at most 2^18 samples — at most 44 B per sample of planes — and block until the planes are there. */
+int c2rt_render_paths_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                             const c2rt_path_opts *g, const c2rt_path_planes *planes_dev, void *hip_stream);
+int c2rt_render_paths(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                      const c2rt_path_opts *g, const c2rt_path_planes *planes_host);
+int c2rt_trace_rays_paths_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n,
+                                 const c2rt_path_opts *g, const c2rt_path_planes *planes_dev, void *hip_stream);
+int c2rt_trace_rays_paths(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n,
+                          const c2rt_path_opts *g, const c2rt_path_planes *planes_host);
+
 /* ---- adaptive anti-aliasing: refine only the pixels the edge test flags ----- */
 
 /* tooDifferent's default threshold — rt/color.d:18 */

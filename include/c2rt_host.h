@@ -122,6 +122,11 @@ int c2rt_host_render_occlusion(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt
  * per plane, host pointers, every one nullable; `g` as there): as c2rt_host_render_hits is to c2rt_render_hits. */
 int c2rt_host_render_gather(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt_gather_opts *g, const c2rt_gather_planes *planes);
 
+/* The path planes of the scene's own camera at its frame size (c2rt_render_paths: frame_height x frame_width samples
+ * per plane, host pointers, every one nullable; `g` as there — the scene's own pathsPerPixel and maxTraceDepth are in
+ * c2rt_host_settings): as c2rt_host_render_hits is to c2rt_render_hits. */
+int c2rt_host_render_paths(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt_path_opts *g, const c2rt_path_planes *planes);
+
 /* Renderer.renderRT with adaptive anti-aliasing (c2rt_render_frame_adaptive) for the scene's own camera at its frame
  * size, with the reference's threshold (C2RT_AA_THRESHOLD_REF) and C2RT_TAPS_REF5 whatever the AA setting: uploads the
  * scene if needed and calls beginFrame.  `out_rgb`: frameWidth * frameHeight * 3 floats; `needs_aa` (nullable):

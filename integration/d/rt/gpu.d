@@ -227,6 +227,33 @@ extern (C) nothrow @nogc
                                       const c2rt_gather_planes* planes_dev, void* hip_stream);
     int c2rt_trace_rays_gather(c2rt_ctx*, const c2rt_ray* rays, ulong n, const c2rt_gather_opts*,
                                const c2rt_gather_planes* planes_host);
+    /// path planes: `paths` paths of at most min(`bounces`, the scene's max_trace_depth) segments behind the closest hit,
+    /// every vertex continued as Lambert.spawnRay continues it, every segment traced and shaded as c2rt_trace_rays does,
+    /// weighted with the path's throughput and averaged: renderSampleGI's frame as `radiance` (include/c2rt.h)
+    enum uint C2RT_MAX_PATHS = 64;
+    enum uint C2RT_MAX_PATH_BOUNCES = 8;
+    struct c2rt_path_opts
+    {
+        ulong seed;                 /// counter-RNG seed
+        uint paths;                 /// P: 1 .. C2RT_MAX_PATHS
+        uint bounces;               /// B: 1 .. C2RT_MAX_PATH_BOUNCES
+    }
+    struct c2rt_path_planes
+    {
+        int* node;                  /// closest node, -1: no hit
+        uint* segments;             /// spawned segments that hit a node, over all paths and depths
+        float* indirect;            /// [3] per sample: mean weighted light arriving at the hit, all depths
+        float* bounce;              /// [3] per sample: albedo * indirect
+        float* radiance;            /// [3] per sample: rgb + bounce, the global-illumination frame itself
+    }
+    int c2rt_render_paths_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_path_opts*,
+                                 const c2rt_path_planes* planes_dev, void* hip_stream);
+    int c2rt_render_paths(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_path_opts*,
+                          const c2rt_path_planes* planes_host);
+    int c2rt_trace_rays_paths_device(c2rt_ctx*, const c2rt_ray* rays_dev, ulong n, const c2rt_path_opts*,
+                                     const c2rt_path_planes* planes_dev, void* hip_stream);
+    int c2rt_trace_rays_paths(c2rt_ctx*, const c2rt_ray* rays, ulong n, const c2rt_path_opts*,
+                              const c2rt_path_planes* planes_host);
     enum float C2RT_AA_THRESHOLD_REF = 0.1f; /// tooDifferent's default
     int c2rt_render_frame_adaptive_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
                                           float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
