@@ -26,6 +26,7 @@ MAX_BATCH_FRAMES = 256
 MAX_RAYS = 1 << 28
 MAX_HIT_LAYERS = 16
 MAX_SAMPLE_TAPS = 16
+MAX_DENOISE_LEVELS = 8
 AA_THRESHOLD_REF = 0.1     # C2RT_AA_THRESHOLD_REF (0.1f: passed as a C float)
 
 _i32p = C.POINTER(C.c_int32)
@@ -235,6 +236,33 @@ class PathPlanes(C.Structure):
     ]
 
 
+class DenoiseGuides(C.Structure):
+    """c2rt_denoise_guides: node, normal and p of the hit planes (required), albedo and base (nullable); host or device
+    memory, by entry point"""
+    _fields_ = [
+        ("node", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("p", C.c_void_p),
+        ("albedo", C.c_void_p),
+        ("base", C.c_void_p),
+    ]
+
+
+class DenoiseOpts(C.Structure):
+    """c2rt_denoise_opts: the whole frame's size, levels (0 .. 8), channels (1 | 3), the normal term's exponent as
+    log2 (0 .. 7), the plane and colour scales"""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("levels", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("normal_power_log2", C.c_uint32),
+        ("sigma_plane", C.c_float),
+        ("sigma_colour", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class ScenePose(C.Structure):
     """c2rt_scene_pose: new transforms ([n_nodes][30] doubles) and light values for some nodes / lights of the uploaded scene"""
     _fields_ = [
@@ -347,6 +375,10 @@ C2RT_SYMBOLS = {
     "c2rt_render_paths": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(PathOpts), C.POINTER(PathPlanes)]),
     "c2rt_trace_rays_paths_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(PathOpts), C.POINTER(PathPlanes), _VP]),
     "c2rt_trace_rays_paths": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(PathOpts), C.POINTER(PathPlanes)]),
+    "c2rt_denoise_scratch_bytes": (C.c_size_t, [C.POINTER(DenoiseOpts)]),
+    "c2rt_denoise_device": (C.c_int, [_VP, C.POINTER(DenoiseGuides), C.POINTER(DenoiseOpts), _VP, _VP, _VP, _VP]),
+    "c2rt_denoise": (C.c_int, [_VP, C.POINTER(DenoiseGuides), C.POINTER(DenoiseOpts), _VP, _VP]),
+    "c2rt_render_paths_denoised": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(PathOpts), C.POINTER(DenoiseOpts), _VP]),
     "c2rt_render_frame_adaptive_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frame_adaptive": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frames_adaptive_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),
@@ -388,6 +420,7 @@ C2RT_HOST_SYMBOLS = {
     "c2rt_host_render_occlusion": (C.c_int, [_VP, _VP, C.POINTER(OcclusionOpts), C.POINTER(OcclusionPlanes)]),
     "c2rt_host_render_gather": (C.c_int, [_VP, _VP, C.POINTER(GatherOpts), C.POINTER(GatherPlanes)]),
     "c2rt_host_render_paths": (C.c_int, [_VP, _VP, C.POINTER(PathOpts), C.POINTER(PathPlanes)]),
+    "c2rt_host_render_paths_denoised": (C.c_int, [_VP, _VP, C.POINTER(PathOpts), C.POINTER(DenoiseOpts), _VP]),
     "c2rt_host_render_rt_adaptive":(C.c_int, [_VP, _VP, _VP, _VP]),
     "c2rt_host_render_rt_taps": (C.c_int, [_VP, _VP, _TAPS_P, _VP]),
     "c2rt_host_render_rt_adaptive_taps": (C.c_int, [_VP, _VP, _TAPS_P, _VP, _VP]),

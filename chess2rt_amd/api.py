@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (CameraFrame, GatherOpts, GatherPlanes, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
+from ._abi import (CameraFrame, DenoiseGuides, DenoiseOpts, GatherOpts, GatherPlanes, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
                    ScenePose, Segment, ShadePlanes, TapTable, TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
@@ -122,6 +122,22 @@ def _gather_opts(samples, seed):
 
 def _path_opts(paths, bounces, seed):
     return PathOpts(seed=int(seed), paths=int(paths), bounces=int(bounces))
+
+
+# Context.denoise's sigma_plane when none is given: a tap one world unit off the centre's tangent plane weighs half
+DENOISE_SIGMA_PLANE = 1.0
+
+
+def _denoise_opts(width, height, channels, levels, normal_power_log2, sigma_plane, sigma_colour):
+    return DenoiseOpts(width=int(width), height=int(height), levels=int(levels), channels=int(channels), normal_power_log2=int(normal_power_log2),
+                       sigma_plane=float(sigma_plane), sigma_colour=float(sigma_colour), reserved=0)
+
+
+def denoise_scratch_bytes(width, height, channels=3, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE, sigma_colour=0.0):
+    """c2rt_denoise_scratch_bytes: what Context.denoiseDevice needs at `scratch_ptr` for these options (the guides packed
+    to fp32, 32 B per pixel, and for levels > 1 one ping-pong plane); 0 for levels == 0 and for options it would refuse."""
+    o = _denoise_opts(width, height, channels, levels, normal_power_log2, sigma_plane, sigma_colour)
+    return int(_abi.load_library().c2rt_denoise_scratch_bytes(C.byref(o)))
 
 
 def makePose(nodes=None, lights=None):
@@ -842,6 +858,62 @@ class Context:
         pl = _PATHS.device(ptrs)
         self._check(self._lib.c2rt_trace_rays_paths_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(g), C.byref(pl), C.c_void_p(stream)))
 
+    def denoise(self, guides, image, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE, sigma_colour=0.0, albedo=None, base=None):
+        """Edge-aware a-trous filter of a Monte-Carlo plane (c2rt_denoise).  `guides`: a dict with the hit planes' node
+        (H, W), normal and p (H, W, 3), e.g. what renderHits returns for the WHOLE frame; `image`: (H, W, 3) float32, or
+        (H, W) / (H, W, 1) for one channel (renderOcclusion's ao).  `levels` (0 .. 8) 5x5 passes with taps 2^l pixels
+        apart; a tap counts only on the centre's node, by dot(n, n')^(2^normal_power_log2), by its distance from the
+        centre's tangent plane against `sigma_plane` and, with sigma_colour > 0, by its colour difference.  Then, for
+        every pixel, `albedo` (nullable) is multiplied in and `base` (nullable) added: with renderPaths' indirect,
+        renderShading's albedo and renderHits' rgb the result is the denoised global-illumination frame.  Returns an
+        array of `image`'s shape."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim not in (2, 3):
+            raise ValueError("denoise: image of shape %r (expected (H, W), (H, W, 1) or (H, W, 3))" % (image.shape,))
+        h, w = image.shape[:2]
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        keep = [np.ascontiguousarray(guides["node"], dtype=np.int32), np.ascontiguousarray(guides["normal"], dtype=np.float64),
+                np.ascontiguousarray(guides["p"], dtype=np.float64)]
+        for a, shape, name in zip(keep, ((h, w), (h, w, 3), (h, w, 3)), ("node", "normal", "p")):
+            if a.shape != shape:
+                raise ValueError("denoise: guide %s of shape %r (expected %r)" % (name, a.shape, shape))
+        g = DenoiseGuides(node=keep[0].ctypes.data, normal=keep[1].ctypes.data, p=keep[2].ctypes.data)
+        for name, a in (("albedo", albedo), ("base", base)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.size != image.size:
+                    raise ValueError("denoise: %s of shape %r (expected %r)" % (name, a.shape, image.shape))
+                keep.append(a)
+                setattr(g, name, a.ctypes.data)
+        o = _denoise_opts(w, h, ch, levels, normal_power_log2, sigma_plane, sigma_colour)
+        out = np.empty_like(image)
+        self._check(self._lib.c2rt_denoise(self._h, C.byref(g), C.byref(o), image.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def denoiseDevice(self, ptrs, width, height, in_ptr, out_ptr, scratch_ptr, channels=3, levels=5, normal_power_log2=5,
+                      sigma_plane=DENOISE_SIGMA_PLANE, sigma_colour=0.0, stream=0):
+        """Enqueue the filter on `stream` over device memory (c2rt_denoise_device): `ptrs` maps node, normal, p and
+        optionally albedo, base to device pointers of full-frame planes; `scratch_ptr`: denoise_scratch_bytes(...) bytes,
+        16-byte aligned (0 where that is 0).  No sync; writes only out_ptr and scratch_ptr."""
+        g = DenoiseGuides()
+        for n, ptr in dict(ptrs).items():
+            if n not in ("node", "normal", "p", "albedo", "base"):
+                raise ValueError("unknown denoise guide %r (one of node, normal, p, albedo, base)" % (n,))
+            setattr(g, n, ptr or None)
+        o = _denoise_opts(width, height, channels, levels, normal_power_log2, sigma_plane, sigma_colour)
+        self._check(self._lib.c2rt_denoise_device(self._h, C.byref(g), C.byref(o), C.c_void_p(in_ptr or None), C.c_void_p(out_ptr or None),
+                                                  C.c_void_p(scratch_ptr or None), C.c_void_p(stream)))
+
+    def renderPathsDenoised(self, cam, opts, paths, bounces, seed=0, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE, sigma_colour=0.0):
+        """The global-illumination frame in one call, denoised (c2rt_render_paths_denoised): renderHits' node, normal, p
+        and rgb, renderShading's albedo, renderPaths' indirect and denoise(..., albedo=albedo, base=rgb), chained on the
+        device; (height, width, 3) float32, bit for bit that composition.  Strips (strip_world > 1) are refused."""
+        g = _path_opts(paths, bounces, seed)
+        d = _denoise_opts(opts.width, opts.height, 3, levels, normal_power_log2, sigma_plane, sigma_colour)
+        out = np.empty((opts.height, opts.width, 3), dtype=np.float32)
+        self._check(self._lib.c2rt_render_paths_denoised(self._h, C.byref(cam), C.byref(opts), C.byref(g), C.byref(d), out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def testVisibility(self, segments):
         """Scene.testVisibility for (n, 6) float64 segments (from, to): (n,) uint8, 1 = nothing in between."""
         seg = _rays_array(segments, "segments")
@@ -985,6 +1057,16 @@ class Renderer:
         g = _path_opts(s.paths_per_pixel if paths is None else paths, s.max_trace_depth if bounces is None else bounces, seed)
         pl, out = _PATHS.new(planes, (s.frame_height, s.frame_width))
         self.ctx._check(self._lib.c2rt_host_render_paths(self.ctx.handle, self.scene._h, C.byref(g), C.byref(pl)))
+        return out
+
+    def renderPathsDenoised(self, paths=None, bounces=None, seed=0, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE, sigma_colour=0.0):
+        """Context.renderPathsDenoised for the scene's own camera and frame size (c2rt_host_render_paths_denoised); None
+        takes the scene's own pathsPerPixel / maxTraceDepth, as renderPaths does."""
+        s = self.scene.settings
+        g = _path_opts(s.paths_per_pixel if paths is None else paths, s.max_trace_depth if bounces is None else bounces, seed)
+        d = _denoise_opts(s.frame_width, s.frame_height, 3, levels, normal_power_log2, sigma_plane, sigma_colour)
+        out = np.empty((s.frame_height, s.frame_width, 3), dtype=np.float32)
+        self.ctx._check(self._lib.c2rt_host_render_paths_denoised(self.ctx.handle, self.scene._h, C.byref(g), C.byref(d), out.ctypes.data_as(C.c_void_p)))
         return out
 
 

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "c2rt_query.h"
+#include "c2rt_denoise.h"
 #include "scene_plan.h"
 
 using namespace c2rt;
@@ -1810,6 +1811,159 @@ int c2rt_trace_rays_paths_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64
 int c2rt_trace_rays_paths(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const c2rt_path_opts *g, const c2rt_path_planes *planes_host)
 {
     return ray_planes_host(ctx, rays, n, g, planes_host);
+}
+
+/* ---- denoise: the a-trous filter over full-frame planes (c2rt_denoise.hip) ------------------------------------------- */
+
+/* the options' own refusals, in the documented order (`ctx` null: the status alone) */
+static int check_denoise_opts(c2rt_ctx *ctx, const c2rt_denoise_opts *o)
+{
+    if (!o->width || !o->height) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise frame of %u x %u pixels: both must be above 0", (unsigned)o->width, (unsigned)o->height);
+    if (o->channels != 1 && o->channels != 3) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise channels is %u: 1 or 3", (unsigned)o->channels);
+    if (!(o->sigma_plane > 0) || !std::isfinite(o->sigma_plane))
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "sigma_plane %g: a finite length above 0", (double)o->sigma_plane);
+    if (!(o->sigma_colour >= 0) || !std::isfinite(o->sigma_colour))
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "sigma_colour %g: finite and not negative", (double)o->sigma_colour);
+    if (o->reserved != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "c2rt_denoise_opts.reserved is %u: must be 0", (unsigned)o->reserved);
+    if (o->levels > C2RT_MAX_DENOISE_LEVELS)
+        return fail(ctx, C2RT_ERR_LIMIT, "%u denoise levels (at most %u)", (unsigned)o->levels, (unsigned)C2RT_MAX_DENOISE_LEVELS);
+    if (o->normal_power_log2 > 7) return fail(ctx, C2RT_ERR_LIMIT, "normal_power_log2 is %u (at most 7)", (unsigned)o->normal_power_log2);
+    return C2RT_OK;
+}
+
+/* every refusal of c2rt_denoise_device, in the documented order; with_scratch false: the host variant, whose scratch is
+ * the library's own */
+static int check_denoise(c2rt_ctx *ctx, const c2rt_denoise_guides *g, const c2rt_denoise_opts *o, const float *in, const float *out,
+                         const void *scratch, bool with_scratch)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (!o) return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise options");
+    if (!g) return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise guides");
+    if (const int st = check_denoise_opts(ctx, o)) return st;
+    if (!g->node) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: node");
+    if (!g->normal) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: normal");
+    if (!g->p) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: p");
+    if (!in) return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise input");
+    if (!out) return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise output");
+    if (out == in) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise output is the input: the filter does not run in place");
+    if (!with_scratch) return C2RT_OK;
+    if (scratch && out == scratch) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise output is the scratch");
+    if (scratch && in == scratch) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise input is the scratch");
+    if (!scratch && c2rt_denoise_scratch_bytes(o) != 0)
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise scratch: these options need %zu bytes", c2rt_denoise_scratch_bytes(o));
+    if (reinterpret_cast<uintptr_t>(scratch) % 16 != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise scratch is not 16-byte aligned");
+    return C2RT_OK;
+}
+
+/* the contract's per-call and per-level factors, in fp32, and the launches */
+static int denoise_enqueue(c2rt_ctx *ctx, const c2rt_denoise_guides &g, const c2rt_denoise_opts &o, const float *in, float *out, void *scratch,
+                           void *stream)
+{
+    const float inv_plane = 1.0f / o.sigma_plane;
+    float inv_c2[C2RT_MAX_DENOISE_LEVELS] = {};
+    for (uint32_t l = 0; l < o.levels; ++l) {
+        const volatile float sc = o.sigma_colour * std::ldexp(1.0f, -(int)l);
+        const volatile float sc2 = sc * sc;
+        inv_c2[l] = 1.0f / sc2;
+    }
+    const int e = launch_denoise(g, o, inv_plane, inv_c2, in, out, scratch, stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "denoise kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+size_t c2rt_denoise_scratch_bytes(const c2rt_denoise_opts *o)
+{
+    if (!o || check_denoise_opts(nullptr, o) != C2RT_OK) return 0;
+    return denoise_guide_bytes(*o) + denoise_plane_bytes(*o);
+}
+
+int c2rt_denoise_device(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_dev, const c2rt_denoise_opts *o, const float *in_dev, float *out_dev,
+                        void *scratch_dev, void *hip_stream)
+{
+    if (const int st = check_denoise(ctx, guides_dev, o, in_dev, out_dev, scratch_dev, true)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return denoise_enqueue(ctx, *guides_dev, *o, in_dev, out_dev, scratch_dev, hip_stream);
+}
+
+int c2rt_denoise(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_host, const c2rt_denoise_opts *o, const float *in, float *out)
+{
+    if (const int st = check_denoise(ctx, guides_host, o, in, out, nullptr, false)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)o->width * o->height, colour = (size_t)o->channels * sizeof(float);
+    /* [node | normal | p | albedo | base | in | out | scratch], each 256-byte aligned */
+    const void *host[6] = {guides_host->node, guides_host->normal, guides_host->p, guides_host->albedo, guides_host->base, in};
+    const size_t bytes[8] = {px * 4, px * 24, px * 24, guides_host->albedo ? px * colour : 0, guides_host->base ? px * colour : 0, px * colour,
+                             px * colour, c2rt_denoise_scratch_bytes(o)};
+    size_t off[8], at = 0;
+    for (int k = 0; k < 8; ++k) {
+        off[k] = at;
+        at = align256(at + bytes[k]);
+    }
+    if (const int e = ensure_staging(ctx, at)) return e;
+    char *dev = reinterpret_cast<char *>(ctx->frame);
+    for (int k = 0; k < 6; ++k)
+        if (bytes[k]) HIP_TRY(ctx, hipMemcpyAsync(dev + off[k], host[k], bytes[k], hipMemcpyHostToDevice, ctx->stream));
+    c2rt_denoise_guides g;
+    g.node = reinterpret_cast<const int32_t *>(dev + off[0]);
+    g.normal = reinterpret_cast<const double *>(dev + off[1]);
+    g.p = reinterpret_cast<const double *>(dev + off[2]);
+    g.albedo = bytes[3] ? reinterpret_cast<const float *>(dev + off[3]) : nullptr;
+    g.base = bytes[4] ? reinterpret_cast<const float *>(dev + off[4]) : nullptr;
+    if (const int st = denoise_enqueue(ctx, g, *o, reinterpret_cast<const float *>(dev + off[5]), reinterpret_cast<float *>(dev + off[6]),
+                                       bytes[7] ? dev + off[7] : nullptr, ctx->stream))
+        return st;
+    HIP_TRY(ctx, hipMemcpyAsync(out, dev + off[6], bytes[6], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return C2RT_OK;
+}
+
+int c2rt_render_paths_denoised(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
+                               const c2rt_denoise_opts *d, float *out_rgb)
+{
+    if (const int st = check_frame_args(ctx, cam, opts)) return st;
+    if (const int st = Family<c2rt_path_planes>::check_opts(ctx, pg)) return st;
+    if (!d) return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise options");
+    if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
+    if (const int st = check_one_ray_per_pixel(ctx, cam, opts, "paths are", "path")) return st;
+    if (opts->strip_world > 1)
+        return fail(ctx, C2RT_ERR_UNSUPPORTED, "strip_world is %u: the filter reads its neighbours, it needs the whole frame", (unsigned)opts->strip_world);
+    if (d->width != opts->width || d->height != opts->height)
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise options for %u x %u pixels, the frame has %u x %u", (unsigned)d->width, (unsigned)d->height,
+                    (unsigned)opts->width, (unsigned)opts->height);
+    if (d->channels != 3) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise channels is %u: a frame has 3", (unsigned)d->channels);
+    if (const int st = check_denoise_opts(ctx, d)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    const size_t px = (size_t)opts->width * opts->height;
+    /* [node | normal | p | rgb | albedo | indirect | out | scratch], each 256-byte aligned */
+    const size_t bytes[8] = {px * 4, px * 24, px * 24, px * 12, px * 12, px * 12, px * 12, c2rt_denoise_scratch_bytes(d)};
+    size_t off[8], at = 0;
+    for (int k = 0; k < 8; ++k) {
+        off[k] = at;
+        at = align256(at + bytes[k]);
+    }
+    if (const int e = ensure_staging(ctx, at)) return e;
+    char *dev = reinterpret_cast<char *>(ctx->frame);
+    c2rt_hit_planes hits = {};
+    hits.node = reinterpret_cast<int32_t *>(dev + off[0]);
+    hits.normal = reinterpret_cast<double *>(dev + off[1]);
+    hits.p = reinterpret_cast<double *>(dev + off[2]);
+    hits.rgb = reinterpret_cast<float *>(dev + off[3]);
+    c2rt_shade_planes shade = {};
+    shade.albedo = reinterpret_cast<float *>(dev + off[4]);
+    c2rt_path_planes paths = {};
+    paths.indirect = reinterpret_cast<float *>(dev + off[5]);
+    int e = launch_plane_rows(p, ctx->plan.csg_levels, kNoOpts, hits, 0, p.local_rows, ctx->stream);
+    if (e == 0) e = launch_plane_rows(p, ctx->plan.csg_levels, kNoOpts, shade, 0, p.local_rows, ctx->stream);
+    if (e == 0) e = launch_plane_rows(p, ctx->plan.csg_levels, *pg, paths, 0, p.local_rows, ctx->stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "denoised path frame, plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+    c2rt_denoise_guides g = {hits.node, hits.normal, hits.p, shade.albedo, hits.rgb};
+    if (const int st = denoise_enqueue(ctx, g, *d, paths.indirect, reinterpret_cast<float *>(dev + off[6]), bytes[7] ? dev + off[7] : nullptr, ctx->stream))
+        return st;
+    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, dev + off[6], bytes[6], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return C2RT_OK;
 }
 
 /* ---- hit layers: every surface along a ray or pixel (c2rt_layers.hip) --------------------------------------------- */

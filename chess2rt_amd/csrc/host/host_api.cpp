@@ -314,6 +314,15 @@ int c2rt_host_render_paths(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_path_op
     return c2rt_render_paths(ctx, &cam, &o, g, planes);
 }
 
+int c2rt_host_render_paths_denoised(c2rt_ctx *ctx, c2rt_host_scene *s, const c2rt_path_opts *g, const c2rt_denoise_opts *d, float *out_rgb)
+{
+    // c2rt_host_render_hits' set-up; the options, the output and the camera are judged by c2rt_render_paths_denoised
+    c2rt_camera_frame cam;
+    c2rt_render_opts o;
+    if (const int st = frame_setup(ctx, s, true, cam, o)) return st;
+    return c2rt_render_paths_denoised(ctx, &cam, &o, g, d, out_rgb);
+}
+
 int c2rt_host_render_rt_adaptive(c2rt_ctx *ctx, c2rt_host_scene *s, float *out_rgb, uint8_t *needs_aa)
 {
     // renderRT's passes 2, 3a and 3b (rt/renderer.d:132-188) with 3b on the flagged pixels only

@@ -1021,6 +1021,102 @@ int c2rt_trace_rays_paths_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64
 int c2rt_trace_rays_paths(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n,
                           const c2rt_path_opts *g, const c2rt_path_planes *planes_host);
 
+/* ---- denoise: edge-aware a-trous filter of a Monte-Carlo plane, guided by the hit planes ---- */
+
+/* Most levels of one call; C2RT_ERR_LIMIT beyond (level l taps 2^l pixels apart). */
+#define C2RT_MAX_DENOISE_LEVELS 8
+
+typedef struct c2rt_denoise_guides {   /* 40 bytes */
+    const int32_t *node;     /* [H][W]     required: the hit planes' `node`, < 0: no hit */
+    const double  *normal;   /* [H][W][3]  required: the hit planes' `normal`, exactly as c2rt_render_hits writes it */
+    const double  *p;        /* [H][W][3]  required: the hit planes' `p` */
+    const float   *albedo;   /* [H][W][channels]  nullable: multiplied into the result (the shading planes' `albedo`) */
+    const float   *base;     /* [H][W][channels]  nullable: added to the result (the hit planes' `rgb`) */
+} c2rt_denoise_guides;
+
+typedef struct c2rt_denoise_opts {     /* 32 bytes */
+    uint32_t width, height;        /* the WHOLE frame: no strips (a caller who renders in strips de-interleaves first) */
+    uint32_t levels;               /* 0 .. C2RT_MAX_DENOISE_LEVELS; 0: the two closing steps alone */
+    uint32_t channels;             /* 1 | 3 (1: the occlusion planes' `ao`) */
+    uint32_t normal_power_log2;    /* 0 .. 7: the normal term is dot(n, n')^(2^this) */
+    float    sigma_plane;          /* finite, > 0: distance from the centre's tangent plane at which a tap weighs half */
+    float    sigma_colour;         /* finite, >= 0; 0: no colour term */
+    uint32_t reserved;             /* 0 */
+} c2rt_denoise_opts;
+
+/* An edge-avoiding a-trous wavelet filter: a 5x5 B3-spline with dilation 2^l per level, its edge-stopping terms computed
+ * in fp32 from the hit planes, which are on the device anyway.  All planes are full-frame, row-major [H][W], and `in` and
+ * `out` are float[channels] per pixel.  The arithmetic is the contract — fp32, no libm call, no exp, no contraction, IEEE
+ * divide, subnormals kept — and tests/denoise_reference.py restates it in numpy to the bit:
+ *
+ *   per pixel, once:  nf.c = (float)normal.c,  pf.c = (float)p.c
+ *   per call:         K = {1/16, 1/4, 3/8, 1/4, 1/16};  inv_plane = 1f / sigma_plane
+ *   per level l:      sc = sigma_colour * 2^-l;  inv_c2 = 1f / (sc * sc)
+ *
+ *   level l, step s = 1 << l, plane C to plane D, pixel q = (x, y):
+ *     node[q] < 0:  D[q] = C[q] (the bits)
+ *     else: sumw = +0f; sum.c = +0f
+ *       for j in -2..2: for i in -2..2:            -- this ORDER of the fp32 sums is the contract
+ *         t = (x + i*s, y + j*s); outside the frame: skip
+ *         (i, j) == (0, 0): w = K[2]*K[2]          -- the centre always counts, none of the tests below
+ *         else:
+ *           node[t] != node[q]: skip
+ *           dn = (nf[q].x*nf[t].x + nf[q].y*nf[t].y) + nf[q].z*nf[t].z;   !(dn > 0): skip
+ *           wn = dn; normal_power_log2 times: wn = wn * wn
+ *           d.c = pf[t].c - pf[q].c;  dp = (nf[q].x*d.x + nf[q].y*d.y) + nf[q].z*d.z
+ *           e = dp * inv_plane;  wp = 1f / (1f + e*e)
+ *           w = ((K[i+2]*K[j+2]) * wn) * wp        -- K[i+2]*K[j+2] is exact in fp32
+ *           sigma_colour > 0:  dc.c = C[t].c - C[q].c;  d2 = (dc.r*dc.r + dc.g*dc.g) + dc.b*dc.b   (one channel: dc*dc)
+ *                              w = w * (1f / (1f + d2 * inv_c2))
+ *           !(w > 0): skip                          -- NaN, and underflow to zero
+ *         sum.c = sum.c + w * C[t].c;  sumw = sumw + w     -- multiply, then add; not contracted
+ *       D[q].c = sum.c / sumw
+ *
+ *   Levels 0 .. levels-1 run in order, from `in` to `out` through `out` itself and one more plane in the scratch; `in`
+ *   and the guides are never written.  Then, for EVERY pixel (misses included), fused into the last store:
+ *     albedo given:  v.c = albedo.c * v.c
+ *     base given:    v.c = base.c + v.c
+ *   levels == 0 does these two steps alone: with the path planes' `indirect` as `in`, the shading planes' `albedo` and the
+ *   hit planes' `rgb` as `base`, `out` is the path planes' `radiance` bit for bit.
+ *
+ *   - A NaN or infinite colour reaches exactly the pixels this arithmetic says; a NaN normal or a `p` beyond fp32 drops
+ *     the taps it makes NaN and never the centre.
+ *   - The step may exceed the frame: then only the centre is inside, and D[q].c = (w*C[q].c) / w.
+ *
+ * c2rt_denoise_scratch_bytes: pure host arithmetic, no context.  0 for options c2rt_denoise_device would refuse, and
+ * for levels == 0 (then `scratch_dev` may be null).  Otherwise width * height * (32 + (levels > 1 ? 4 * channels : 0)):
+ * the guides packed to fp32 once — per pixel (nf, the bits of node) and (pf, 0), two 16-byte words — and, behind them, the
+ * one ping-pong plane that levels > 1 need beside `out`.  At most 44 B per pixel.  `scratch_dev` must be 16-byte aligned.
+ *
+ * c2rt_denoise_device needs no uploaded scene.  It takes the stream rules of c2rt_render_hits_device (no host sync, no
+ * event, nothing kept of the stream, the lead device of a multi-device context), enqueues levels + 1 kernels for
+ * levels >= 1 and one for levels == 0, and writes only `out_dev` and `scratch_dev`.
+ *
+ * Statuses, all decided before anything is enqueued or written, each with its own message, in this order.
+ * C2RT_ERR_INVALID_ARG: null context; null `opts`; null `guides`; width or height 0; channels not 1 or 3; sigma_plane
+ * NaN, infinite or <= 0; sigma_colour NaN, infinite or < 0; reserved != 0.  C2RT_ERR_LIMIT: levels >
+ * C2RT_MAX_DENOISE_LEVELS; normal_power_log2 > 7.  C2RT_ERR_INVALID_ARG again: null `node`, `normal` or `p`; null `in`;
+ * null `out`; out == in; out == scratch; in == scratch (both for a non-null scratch); null scratch where
+ * c2rt_denoise_scratch_bytes is not 0; a scratch that is not 16-byte aligned. */
+size_t c2rt_denoise_scratch_bytes(const c2rt_denoise_opts *o);
+int c2rt_denoise_device(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_dev, const c2rt_denoise_opts *o,
+                        const float *in_dev, float *out_dev, void *scratch_dev, void *hip_stream);
+/* The same from and into HOST memory, the scratch the library's own: guides, `in`, `out` and the scratch go through the
+ * context's grow-only staging buffer on the context's own stream, whole (at most 144 B per pixel; nothing is allocated
+ * once the buffer is large enough); blocks until `out` is there.  The same statuses without the scratch's. */
+int c2rt_denoise(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_host, const c2rt_denoise_opts *o, const float *in, float *out);
+
+/* The global-illumination frame in one call, denoised: on the device, the hit planes (node, normal, p, rgb), the shading
+ * planes' `albedo`, the path planes' `indirect` and the filter with albedo and base = rgb; 12 B per pixel come back.
+ * out_rgb[H][W][3] is bit for bit what a caller composes from c2rt_render_hits, c2rt_render_shading, c2rt_render_paths
+ * and c2rt_denoise.  Statuses, in this order: those of c2rt_render_paths without the planes' (a frame call's, the path
+ * options'); null `d`, null `out_rgb`: C2RT_ERR_INVALID_ARG; C2RT_ERR_UNSUPPORTED naming "depth of field", "stereo",
+ * "count_rays", "prepass_bucket", then "strip_world" for opts->strip_world > 1 (0 and 1 both mean the whole frame, as everywhere); d->width / d->height other than the
+ * frame's, d->channels != 3: C2RT_ERR_INVALID_ARG; then c2rt_denoise's for `d`.  Staged whole through the context's
+ * staging buffer (144 B per pixel); blocks until the frame is there. */
+int c2rt_render_paths_denoised(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                               const c2rt_path_opts *g, const c2rt_denoise_opts *d, float *out_rgb);
+
 /* ---- adaptive anti-aliasing: refine only the pixels the edge test flags ----- */
 
 /* tooDifferent's default threshold — rt/color.d:18 */

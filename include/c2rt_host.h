@@ -127,6 +127,11 @@ int c2rt_host_render_gather(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt_ga
  * c2rt_host_settings): as c2rt_host_render_hits is to c2rt_render_hits. */
 int c2rt_host_render_paths(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt_path_opts *g, const c2rt_path_planes *planes);
 
+/* The denoised global-illumination frame of the scene's own camera at its frame size (c2rt_render_paths_denoised:
+ * `out_rgb` frame_height x frame_width x 3 floats; `g` and `d` as there, d->width / d->height the scene's frame size): as
+ * c2rt_host_render_hits is to c2rt_render_hits. */
+int c2rt_host_render_paths_denoised(c2rt_ctx *ctx, c2rt_host_scene *scene, const c2rt_path_opts *g, const c2rt_denoise_opts *d, float *out_rgb);
+
 /* Renderer.renderRT with adaptive anti-aliasing (c2rt_render_frame_adaptive) for the scene's own camera at its frame
  * size, with the reference's threshold (C2RT_AA_THRESHOLD_REF) and C2RT_TAPS_REF5 whatever the AA setting: uploads the
  * scene if needed and calls beginFrame.  `out_rgb`: frameWidth * frameHeight * 3 floats; `needs_aa` (nullable):

@@ -254,6 +254,33 @@ extern (C) nothrow @nogc
                                      const c2rt_path_planes* planes_dev, void* hip_stream);
     int c2rt_trace_rays_paths(c2rt_ctx*, const c2rt_ray* rays, ulong n, const c2rt_path_opts*,
                               const c2rt_path_planes* planes_host);
+    /// denoise: edge-aware a-trous filter (5x5 B3-spline, taps 2^l pixels apart at level l) of a Monte-Carlo plane, guided
+    /// by the hit planes' node, normal and p; full-frame planes, fp32 arithmetic fixed by include/c2rt.h
+    enum C2RT_MAX_DENOISE_LEVELS = 8;
+    struct c2rt_denoise_guides
+    {
+        const(int)* node;           /// required: the hit planes' node, < 0: no hit
+        const(double)* normal;      /// required: [3] per pixel
+        const(double)* p;           /// required: [3] per pixel
+        const(float)* albedo;       /// nullable: [channels] per pixel, multiplied into the result
+        const(float)* base;         /// nullable: [channels] per pixel, added to the result
+    }
+    struct c2rt_denoise_opts
+    {
+        uint width, height;         /// the whole frame
+        uint levels;                /// 0 .. C2RT_MAX_DENOISE_LEVELS
+        uint channels;              /// 1 | 3
+        uint normal_power_log2;     /// 0 .. 7
+        float sigma_plane;          /// finite, > 0
+        float sigma_colour;         /// finite, >= 0; 0: no colour term
+        uint reserved;              /// 0
+    }
+    size_t c2rt_denoise_scratch_bytes(const c2rt_denoise_opts*);
+    int c2rt_denoise_device(c2rt_ctx*, const c2rt_denoise_guides* guides_dev, const c2rt_denoise_opts*, const float* in_dev,
+                            float* out_dev, void* scratch_dev, void* hip_stream);
+    int c2rt_denoise(c2rt_ctx*, const c2rt_denoise_guides* guides_host, const c2rt_denoise_opts*, const float* in_, float* out_);
+    int c2rt_render_paths_denoised(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_path_opts*,
+                                   const c2rt_denoise_opts*, float* out_rgb);
     enum float C2RT_AA_THRESHOLD_REF = 0.1f; /// tooDifferent's default
     int c2rt_render_frame_adaptive_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
                                           float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
