@@ -27,6 +27,7 @@ MAX_RAYS = 1 << 28
 MAX_HIT_LAYERS = 16
 MAX_SAMPLE_TAPS = 16
 MAX_DENOISE_LEVELS = 8
+MAX_TEMPORAL_AGE = 65535
 AA_THRESHOLD_REF = 0.1     # C2RT_AA_THRESHOLD_REF (0.1f: passed as a C float)
 
 _i32p = C.POINTER(C.c_int32)
@@ -263,6 +264,39 @@ class DenoiseOpts(C.Structure):
     ]
 
 
+class TemporalOpts(C.Structure):
+    """c2rt_temporal_opts: the whole frame's size, channels (1 | 3), the age at which the running mean stops growing
+    (1 .. 65535), the normal and plane tests of a history tap"""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("max_age", C.c_uint32),
+        ("min_normal_dot", C.c_float),
+        ("max_plane_dist", C.c_float),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class TemporalGuides(C.Structure):
+    """c2rt_temporal_guides: node, normal and p of the CURRENT frame's hit planes, all required; host or device memory,
+    by entry point"""
+    _fields_ = [
+        ("node", C.c_void_p),
+        ("normal", C.c_void_p),
+        ("p", C.c_void_p),
+    ]
+
+
+class TemporalPlanes(C.Structure):
+    """c2rt_temporal_planes: one nullable pointer per output plane (host or device memory, by entry point)"""
+    _fields_ = [
+        ("colour", C.c_void_p),
+        ("variance", C.c_void_p),
+        ("age", C.c_void_p),
+    ]
+
+
 class ScenePose(C.Structure):
     """c2rt_scene_pose: new transforms ([n_nodes][30] doubles) and light values for some nodes / lights of the uploaded scene"""
     _fields_ = [
@@ -379,6 +413,10 @@ C2RT_SYMBOLS = {
     "c2rt_denoise_device": (C.c_int, [_VP, C.POINTER(DenoiseGuides), C.POINTER(DenoiseOpts), _VP, _VP, _VP, _VP]),
     "c2rt_denoise": (C.c_int, [_VP, C.POINTER(DenoiseGuides), C.POINTER(DenoiseOpts), _VP, _VP]),
     "c2rt_render_paths_denoised": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(PathOpts), C.POINTER(DenoiseOpts), _VP]),
+    "c2rt_temporal_history_bytes": (C.c_size_t, [C.POINTER(TemporalOpts)]),
+    "c2rt_temporal_accumulate_device": (C.c_int, [_VP, _CAM_P, C.POINTER(TemporalGuides), C.POINTER(TemporalOpts), _VP, _VP, _VP, C.POINTER(TemporalPlanes), _VP]),
+    "c2rt_temporal_accumulate": (C.c_int, [_VP, _CAM_P, C.POINTER(TemporalGuides), C.POINTER(TemporalOpts), _VP, _VP, _VP, C.POINTER(TemporalPlanes)]),
+    "c2rt_render_paths_sequence": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.POINTER(PathOpts), C.POINTER(TemporalOpts), C.POINTER(DenoiseOpts), _VP]),
     "c2rt_render_frame_adaptive_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frame_adaptive": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frames_adaptive_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),

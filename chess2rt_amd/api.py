@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (CameraFrame, DenoiseGuides, DenoiseOpts, GatherOpts, GatherPlanes, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
-                   ScenePose, Segment, ShadePlanes, TapTable, TraceResult)
+                   ScenePose, Segment, ShadePlanes, TapTable, TemporalGuides, TemporalOpts, TemporalPlanes, TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
 RAY_HIT_DTYPE = np.dtype({
@@ -138,6 +138,28 @@ def denoise_scratch_bytes(width, height, channels=3, levels=5, normal_power_log2
     to fp32, 32 B per pixel, and for levels > 1 one ping-pong plane); 0 for levels == 0 and for options it would refuse."""
     o = _denoise_opts(width, height, channels, levels, normal_power_log2, sigma_plane, sigma_colour)
     return int(_abi.load_library().c2rt_denoise_scratch_bytes(C.byref(o)))
+
+
+# Context.temporalAccumulate's defaults: the running mean grows to 32 samples; a history tap counts within 25 degrees of
+# the pixel's normal and a tenth of a world unit of its tangent plane
+TEMPORAL_MAX_AGE = 32
+TEMPORAL_MIN_NORMAL_DOT = 0.9
+TEMPORAL_MAX_PLANE_DIST = 0.1
+# c2rt_temporal_planes: plane name -> dtype ("colour" has the input's channels, the others one value per pixel)
+TEMPORAL_PLANES = {"colour": np.float32, "variance": np.float32, "age": np.uint32}
+
+
+def _temporal_opts(width, height, channels, max_age, min_normal_dot, max_plane_dist):
+    return TemporalOpts(width=int(width), height=int(height), channels=int(channels), max_age=int(max_age), min_normal_dot=float(min_normal_dot),
+                        max_plane_dist=float(max_plane_dist))
+
+
+def temporal_history_bytes(width, height, channels=3, max_age=TEMPORAL_MAX_AGE, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT,
+                           max_plane_dist=TEMPORAL_MAX_PLANE_DIST):
+    """c2rt_temporal_history_bytes: the size of one history of Context.temporalAccumulate / temporalAccumulateDevice,
+    width * height * (32 + 4 * channels + 8); 0 for options the library would refuse."""
+    o = _temporal_opts(width, height, channels, max_age, min_normal_dot, max_plane_dist)
+    return int(_abi.load_library().c2rt_temporal_history_bytes(C.byref(o)))
 
 
 def makePose(nodes=None, lights=None):
@@ -912,6 +934,83 @@ class Context:
         d = _denoise_opts(opts.width, opts.height, 3, levels, normal_power_log2, sigma_plane, sigma_colour)
         out = np.empty((opts.height, opts.width, 3), dtype=np.float32)
         self._check(self._lib.c2rt_render_paths_denoised(self._h, C.byref(cam), C.byref(opts), C.byref(g), C.byref(d), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def temporalAccumulate(self, guides, image, prev_cam=None, history=None, max_age=TEMPORAL_MAX_AGE, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT,
+                           max_plane_dist=TEMPORAL_MAX_PLANE_DIST, planes=("colour", "variance", "age")):
+        """Temporal accumulation of a Monte-Carlo plane (c2rt_temporal_accumulate).  `guides`: a dict with the CURRENT
+        frame's node (H, W), normal and p (H, W, 3), e.g. what renderHits returns for the whole frame; `image`: (H, W, 3)
+        float32, or (H, W) / (H, W, 1) for one channel.  `history`: the bytes-like history the previous call returned and
+        `prev_cam` that call's camera; both None for the first frame.  Every pixel's point is projected into `prev_cam`,
+        the history is fetched there from the taps on the same node, within `min_normal_dot` of its normal and
+        `max_plane_dist` of its tangent plane, and `image` is folded into a running mean of at most `max_age` samples.
+        Returns ({plane: array} for the `planes` asked for — colour of `image`'s shape, variance float32 and age uint32
+        (H, W) — and the new history, a uint8 array of temporal_history_bytes(...))."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim not in (2, 3):
+            raise ValueError("temporalAccumulate: image of shape %r (expected (H, W), (H, W, 1) or (H, W, 3))" % (image.shape,))
+        h, w = image.shape[:2]
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        keep = [np.ascontiguousarray(guides["node"], dtype=np.int32), np.ascontiguousarray(guides["normal"], dtype=np.float64),
+                np.ascontiguousarray(guides["p"], dtype=np.float64)]
+        for a, shape, name in zip(keep, ((h, w), (h, w, 3), (h, w, 3)), ("node", "normal", "p")):
+            if a.shape != shape:
+                raise ValueError("temporalAccumulate: guide %s of shape %r (expected %r)" % (name, a.shape, shape))
+        g = TemporalGuides(node=keep[0].ctypes.data, normal=keep[1].ctypes.data, p=keep[2].ctypes.data)
+        o = _temporal_opts(w, h, ch, max_age, min_normal_dot, max_plane_dist)
+        nbytes = w * h * (32 + 4 * ch + 8)
+        prev = None
+        if history is not None:
+            prev = np.ascontiguousarray(np.frombuffer(history, dtype=np.uint8))
+            if prev.size != nbytes:
+                raise ValueError("temporalAccumulate: history of %d bytes (expected %d)" % (prev.size, nbytes))
+        out, pl = {}, TemporalPlanes()
+        for n in planes:
+            if n not in TEMPORAL_PLANES:
+                raise ValueError("unknown temporal plane %r (one of %s)" % (n, ", ".join(TEMPORAL_PLANES)))
+            out[n] = np.empty(image.shape if n == "colour" else (h, w), dtype=TEMPORAL_PLANES[n])
+            setattr(pl, n, out[n].ctypes.data)
+        new = np.empty(nbytes, dtype=np.uint8)
+        self._check(self._lib.c2rt_temporal_accumulate(self._h, None if prev_cam is None else C.byref(prev_cam), C.byref(g), C.byref(o),
+                                                       image.ctypes.data_as(C.c_void_p), None if prev is None else prev.ctypes.data_as(C.c_void_p),
+                                                       new.ctypes.data_as(C.c_void_p), C.byref(pl)))
+        return out, new
+
+    def temporalAccumulateDevice(self, ptrs, width, height, in_ptr, history_prev_ptr, history_out_ptr, planes=None, prev_cam=None, channels=3,
+                                 max_age=TEMPORAL_MAX_AGE, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT, max_plane_dist=TEMPORAL_MAX_PLANE_DIST, stream=0):
+        """Enqueue the accumulation on `stream` over device memory (c2rt_temporal_accumulate_device): `ptrs` maps node,
+        normal and p to device pointers of the current frame's planes, `planes` colour, variance and age to the outputs
+        wanted (None: the history alone); the histories are temporal_history_bytes(...) bytes each, 16-byte aligned,
+        history_prev_ptr 0 for the first frame.  One kernel, no sync; writes only history_out_ptr and `planes`."""
+        g = TemporalGuides()
+        for n, ptr in dict(ptrs).items():
+            if n not in ("node", "normal", "p"):
+                raise ValueError("unknown temporal guide %r (one of node, normal, p)" % (n,))
+            setattr(g, n, ptr or None)
+        pl = TemporalPlanes()
+        for n, ptr in dict(planes or {}).items():
+            if n not in TEMPORAL_PLANES:
+                raise ValueError("unknown temporal plane %r (one of %s)" % (n, ", ".join(TEMPORAL_PLANES)))
+            setattr(pl, n, ptr or None)
+        o = _temporal_opts(width, height, channels, max_age, min_normal_dot, max_plane_dist)
+        self._check(self._lib.c2rt_temporal_accumulate_device(self._h, None if prev_cam is None else C.byref(prev_cam), C.byref(g), C.byref(o),
+                                                              C.c_void_p(in_ptr or None), C.c_void_p(history_prev_ptr or None),
+                                                              C.c_void_p(history_out_ptr or None), C.byref(pl), C.c_void_p(stream)))
+
+    def renderPathsSequence(self, cams, opts, paths, bounces, seed=0, max_age=TEMPORAL_MAX_AGE, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT,
+                            max_plane_dist=TEMPORAL_MAX_PLANE_DIST, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE, sigma_colour=0.0):
+        """A global-illumination sequence in one call (c2rt_render_paths_sequence): for each camera of `cams` renderHits'
+        node, normal, p and rgb, renderShading's albedo, renderPaths' indirect with seed + i, temporalAccumulate against
+        the previous camera and history, and denoise(..., albedo=albedo, base=rgb), chained on the device; (n, height,
+        width, 3) float32, bit for bit that composition."""
+        cams = list(cams)
+        arr = (CameraFrame * max(len(cams), 1))(*cams)
+        g = _path_opts(paths, bounces, seed)
+        t = _temporal_opts(opts.width, opts.height, 3, max_age, min_normal_dot, max_plane_dist)
+        d = _denoise_opts(opts.width, opts.height, 3, levels, normal_power_log2, sigma_plane, sigma_colour)
+        out = np.empty((len(cams), opts.height, opts.width, 3), dtype=np.float32)
+        self._check(self._lib.c2rt_render_paths_sequence(self._h, arr, len(cams), C.byref(opts), C.byref(g), C.byref(t), C.byref(d),
+                                                         out.ctypes.data_as(C.c_void_p)))
         return out
 
     def testVisibility(self, segments):

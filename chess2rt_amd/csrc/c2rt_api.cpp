@@ -26,6 +26,7 @@
 
 #include "c2rt_query.h"
 #include "c2rt_denoise.h"
+#include "c2rt_temporal.h"
 #include "scene_plan.h"
 
 using namespace c2rt;
@@ -1917,8 +1918,9 @@ int c2rt_denoise(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_host, const c2
     return C2RT_OK;
 }
 
-int c2rt_render_paths_denoised(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
-                               const c2rt_denoise_opts *d, float *out_rgb)
+/* every refusal of c2rt_render_paths_denoised, in the documented order (c2rt_render_paths_sequence starts with them) */
+static int check_paths_denoised(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
+                                const c2rt_denoise_opts *d, const float *out_rgb)
 {
     if (const int st = check_frame_args(ctx, cam, opts)) return st;
     if (const int st = Family<c2rt_path_planes>::check_opts(ctx, pg)) return st;
@@ -1931,7 +1933,13 @@ int c2rt_render_paths_denoised(c2rt_ctx *ctx, const c2rt_camera_frame *cam, cons
         return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise options for %u x %u pixels, the frame has %u x %u", (unsigned)d->width, (unsigned)d->height,
                     (unsigned)opts->width, (unsigned)opts->height);
     if (d->channels != 3) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise channels is %u: a frame has 3", (unsigned)d->channels);
-    if (const int st = check_denoise_opts(ctx, d)) return st;
+    return check_denoise_opts(ctx, d);
+}
+
+int c2rt_render_paths_denoised(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
+                               const c2rt_denoise_opts *d, float *out_rgb)
+{
+    if (const int st = check_paths_denoised(ctx, cam, opts, pg, d, out_rgb)) return st;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RenderParams p;
     hit_params(ctx, cam, opts, p);
@@ -1962,6 +1970,210 @@ int c2rt_render_paths_denoised(c2rt_ctx *ctx, const c2rt_camera_frame *cam, cons
     if (const int st = denoise_enqueue(ctx, g, *d, paths.indirect, reinterpret_cast<float *>(dev + off[6]), bytes[7] ? dev + off[7] : nullptr, ctx->stream))
         return st;
     HIP_TRY(ctx, hipMemcpyAsync(out_rgb, dev + off[6], bytes[6], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return C2RT_OK;
+}
+
+/* ---- temporal accumulation: reprojection of the previous frame's history (c2rt_temporal.hip) -------------------------- */
+
+/* the options' own refusals, in the documented order (`ctx` null: the status alone) */
+static int check_temporal_opts(c2rt_ctx *ctx, const c2rt_temporal_opts *o)
+{
+    if (!o->width || !o->height) return fail(ctx, C2RT_ERR_INVALID_ARG, "temporal frame of %u x %u pixels: both must be above 0", (unsigned)o->width, (unsigned)o->height);
+    if (o->channels != 1 && o->channels != 3) return fail(ctx, C2RT_ERR_INVALID_ARG, "temporal channels is %u: 1 or 3", (unsigned)o->channels);
+    if (!std::isfinite(o->min_normal_dot) || !(o->min_normal_dot >= 0) || !(o->min_normal_dot < 1))
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "min_normal_dot %g: finite, at least 0 and below 1", (double)o->min_normal_dot);
+    if (!std::isfinite(o->max_plane_dist) || !(o->max_plane_dist > 0))
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "max_plane_dist %g: a finite length above 0", (double)o->max_plane_dist);
+    if (o->reserved[0] != 0 || o->reserved[1] != 0)
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "c2rt_temporal_opts.reserved is %u, %u: must be 0", (unsigned)o->reserved[0], (unsigned)o->reserved[1]);
+    if (o->max_age == 0 || o->max_age > (uint32_t)C2RT_MAX_TEMPORAL_AGE)
+        return fail(ctx, C2RT_ERR_LIMIT, "max_age is %u (1 .. %u)", (unsigned)o->max_age, (unsigned)C2RT_MAX_TEMPORAL_AGE);
+    return C2RT_OK;
+}
+
+/* the contract's "per call, on the host" for the previous camera; returns det */
+static double temporal_camera(const c2rt_camera_frame &prev, const c2rt_temporal_opts &o, TemporalCamera &k)
+{
+    double A[3], U[3], V[3];
+    for (int c = 0; c < 3; ++c) {
+        k.pos[c] = prev.pos[c];
+        A[c] = prev.up_left[c] - prev.pos[c];
+        U[c] = prev.up_right[c] - prev.up_left[c];
+        V[c] = prev.down_left[c] - prev.up_left[c];
+    }
+    const auto cross = [](const double *a, const double *b, double *out) {
+        out[0] = a[1] * b[2] - a[2] * b[1];
+        out[1] = a[2] * b[0] - a[0] * b[2];
+        out[2] = a[0] * b[1] - a[1] * b[0];
+    };
+    cross(U, V, k.na);
+    cross(V, A, k.nb);
+    cross(A, U, k.nc);
+    const double det = (A[0] * k.na[0] + A[1] * k.na[1]) + A[2] * k.na[2];
+    k.wd = (double)o.width;
+    k.hd = (double)o.height;
+    k.det_positive = det > 0 ? 1u : 0u;
+    return det;
+}
+
+static int check_previous_camera(c2rt_ctx *ctx, const c2rt_camera_frame &prev, const c2rt_temporal_opts &o, TemporalCamera &k)
+{
+    const double det = temporal_camera(prev, o, k);
+    if (!std::isfinite(det) || det == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "degenerate previous camera: its corners span no volume with its eye (det %g)", det);
+    return C2RT_OK;
+}
+
+/* every refusal of c2rt_temporal_accumulate_device, in the documented order; aligned false: the host variant, whose
+ * histories are staged; `k`: the previous camera's constants where there is a history */
+static int check_temporal(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *g, const c2rt_temporal_opts *o, const float *in,
+                          const void *history_prev, const void *history_out, const c2rt_temporal_planes *planes, bool aligned, TemporalCamera &k)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (!o) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal options");
+    if (!g) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal guides");
+    if (const int st = check_temporal_opts(ctx, o)) return st;
+    if (!g->node) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: node");
+    if (!g->normal) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: normal");
+    if (!g->p) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: p");
+    if (!in) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal input");
+    if (!history_out) return fail(ctx, C2RT_ERR_INVALID_ARG, "null history out");
+    if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal planes");
+    if (history_prev && !prev_cam) return fail(ctx, C2RT_ERR_INVALID_ARG, "a previous history without its camera: null prev_cam");
+    if (history_prev)
+        if (const int st = check_previous_camera(ctx, *prev_cam, *o, k)) return st;
+    if (history_out == history_prev) return fail(ctx, C2RT_ERR_INVALID_ARG, "history out is the previous history: the caller swaps two");
+    if (planes->colour == in) return fail(ctx, C2RT_ERR_INVALID_ARG, "temporal colour plane is the input");
+    if (aligned && (reinterpret_cast<uintptr_t>(history_out) % 16 != 0 || reinterpret_cast<uintptr_t>(history_prev) % 16 != 0))
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "a history is not 16-byte aligned");
+    return C2RT_OK;
+}
+
+static int temporal_enqueue(c2rt_ctx *ctx, const c2rt_temporal_guides &g, const c2rt_temporal_opts &o, const TemporalCamera *k, const float *in,
+                            const void *history_prev, void *history_out, const c2rt_temporal_planes &planes, void *stream)
+{
+    const int e = launch_temporal(g, o, history_prev ? k : nullptr, in, history_prev, history_out, planes, stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "temporal kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+size_t c2rt_temporal_history_bytes(const c2rt_temporal_opts *o)
+{
+    if (!o || check_temporal_opts(nullptr, o) != C2RT_OK) return 0;
+    return temporal_history_bytes(*o);
+}
+
+int c2rt_temporal_accumulate_device(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_dev, const c2rt_temporal_opts *o,
+                                    const float *in_dev, const void *history_prev_dev, void *history_out_dev, const c2rt_temporal_planes *planes_dev,
+                                    void *hip_stream)
+{
+    TemporalCamera k = {};
+    if (const int st = check_temporal(ctx, prev_cam, guides_dev, o, in_dev, history_prev_dev, history_out_dev, planes_dev, true, k)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return temporal_enqueue(ctx, *guides_dev, *o, &k, in_dev, history_prev_dev, history_out_dev, *planes_dev, hip_stream);
+}
+
+int c2rt_temporal_accumulate(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_host, const c2rt_temporal_opts *o,
+                             const float *in, const void *history_prev, void *history_out, const c2rt_temporal_planes *planes_host)
+{
+    TemporalCamera k = {};
+    if (const int st = check_temporal(ctx, prev_cam, guides_host, o, in, history_prev, history_out, planes_host, false, k)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)o->width * o->height, colour = (size_t)o->channels * sizeof(float), hist = temporal_history_bytes(*o);
+    /* [node | normal | p | in | history_prev | history_out | colour | variance | age], each 256-byte aligned */
+    const void *host[5] = {guides_host->node, guides_host->normal, guides_host->p, in, history_prev};
+    void *back[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, history_out, planes_host->colour, planes_host->variance, planes_host->age};
+    const size_t bytes[9] = {px * 4, px * 24, px * 24, px * colour, history_prev ? hist : 0, hist, planes_host->colour ? px * colour : 0,
+                             planes_host->variance ? px * 4 : 0, planes_host->age ? px * 4 : 0};
+    size_t off[9], at = 0;
+    for (int i = 0; i < 9; ++i) {
+        off[i] = at;
+        at = align256(at + bytes[i]);
+    }
+    /* what may still be in flight where the buffer grows: as for c2rt_denoise — every host variant that wrote the staging
+     * ended in a sync of ctx->stream, hipFree waits for the device, no device variant touches ctx->frame */
+    if (const int e = ensure_staging(ctx, at)) return e;
+    char *dev = reinterpret_cast<char *>(ctx->frame);
+    for (int i = 0; i < 5; ++i)
+        if (bytes[i]) HIP_TRY(ctx, hipMemcpyAsync(dev + off[i], host[i], bytes[i], hipMemcpyHostToDevice, ctx->stream));
+    c2rt_temporal_guides g;
+    g.node = reinterpret_cast<const int32_t *>(dev + off[0]);
+    g.normal = reinterpret_cast<const double *>(dev + off[1]);
+    g.p = reinterpret_cast<const double *>(dev + off[2]);
+    c2rt_temporal_planes planes;
+    planes.colour = bytes[6] ? reinterpret_cast<float *>(dev + off[6]) : nullptr;
+    planes.variance = bytes[7] ? reinterpret_cast<float *>(dev + off[7]) : nullptr;
+    planes.age = bytes[8] ? reinterpret_cast<uint32_t *>(dev + off[8]) : nullptr;
+    if (const int st = temporal_enqueue(ctx, g, *o, &k, reinterpret_cast<const float *>(dev + off[3]), bytes[4] ? dev + off[4] : nullptr, dev + off[5],
+                                        planes, ctx->stream))
+        return st;
+    for (int i = 5; i < 9; ++i)
+        if (bytes[i]) HIP_TRY(ctx, hipMemcpyAsync(back[i], dev + off[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return C2RT_OK;
+}
+
+int c2rt_render_paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
+                               const c2rt_temporal_opts *t, const c2rt_denoise_opts *d, float *out_rgb)
+{
+    if (const int st = check_paths_denoised(ctx, cams, opts, pg, d, out_rgb)) return st;
+    if (n_frames == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "n_frames is 0: a sequence has at least one frame");
+    if (!t) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal options");
+    if (t->width != opts->width || t->height != opts->height)
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "temporal options for %u x %u pixels, the frame has %u x %u", (unsigned)t->width, (unsigned)t->height,
+                    (unsigned)opts->width, (unsigned)opts->height);
+    if (t->channels != 3) return fail(ctx, C2RT_ERR_INVALID_ARG, "temporal channels is %u: a frame has 3", (unsigned)t->channels);
+    if (const int st = check_temporal_opts(ctx, t)) return st;
+    TemporalCamera k = {};
+    for (uint32_t i = 1; i < n_frames; ++i) {
+        if (cams[i].dof) return fail(ctx, C2RT_ERR_UNSUPPORTED, "camera %u: depth of field: a pixel's paths are one ray's, a lens has many per pixel", (unsigned)i);
+        if (cams[i].stereo_separation != 0)
+            return fail(ctx, C2RT_ERR_UNSUPPORTED, "camera %u: stereo: a pixel's paths are one ray's, a stereo camera has two per pixel", (unsigned)i);
+    }
+    for (uint32_t i = 0; i + 1 < n_frames; ++i)
+        if (const int st = check_previous_camera(ctx, cams[i], *t, k)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)opts->width * opts->height, hist = temporal_history_bytes(*t);
+    /* [node | normal | p | rgb | albedo | indirect | out | scratch | history 0 | history 1], each 256-byte aligned; the
+     * accumulated plane the filter reads is the colour plane of the history just written */
+    const size_t bytes[10] = {px * 4, px * 24, px * 24, px * 12, px * 12, px * 12, px * 12, c2rt_denoise_scratch_bytes(d), hist, hist};
+    size_t off[10], at = 0;
+    for (int i = 0; i < 10; ++i) {
+        off[i] = at;
+        at = align256(at + bytes[i]);
+    }
+    /* once, before the first launch: the buffer does not move under the sequence, and the call ends in a sync */
+    if (const int e = ensure_staging(ctx, at)) return e;
+    char *dev = reinterpret_cast<char *>(ctx->frame);
+    c2rt_hit_planes hits = {};
+    hits.node = reinterpret_cast<int32_t *>(dev + off[0]);
+    hits.normal = reinterpret_cast<double *>(dev + off[1]);
+    hits.p = reinterpret_cast<double *>(dev + off[2]);
+    hits.rgb = reinterpret_cast<float *>(dev + off[3]);
+    c2rt_shade_planes shade = {};
+    shade.albedo = reinterpret_cast<float *>(dev + off[4]);
+    c2rt_path_planes paths = {};
+    paths.indirect = reinterpret_cast<float *>(dev + off[5]);
+    const c2rt_temporal_guides tg = {hits.node, hits.normal, hits.p};
+    const c2rt_denoise_guides dg = {hits.node, hits.normal, hits.p, shade.albedo, hits.rgb};
+    const c2rt_temporal_planes none = {};
+    for (uint32_t i = 0; i < n_frames; ++i) {
+        RenderParams p;
+        hit_params(ctx, &cams[i], opts, p);
+        c2rt_path_opts pgi = *pg;
+        pgi.seed = pg->seed + i;
+        int e = launch_plane_rows(p, ctx->plan.csg_levels, kNoOpts, hits, 0, p.local_rows, ctx->stream);
+        if (e == 0) e = launch_plane_rows(p, ctx->plan.csg_levels, kNoOpts, shade, 0, p.local_rows, ctx->stream);
+        if (e == 0) e = launch_plane_rows(p, ctx->plan.csg_levels, pgi, paths, 0, p.local_rows, ctx->stream);
+        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "path sequence, frame %u, plane kernel launch: %s", (unsigned)i, hipGetErrorString((hipError_t)e));
+        char *h_out = dev + off[8 + (i & 1u)], *h_prev = i ? dev + off[8 + ((i - 1) & 1u)] : nullptr;
+        if (i) (void)temporal_camera(cams[i - 1], *t, k);
+        if (const int st = temporal_enqueue(ctx, tg, *t, &k, paths.indirect, h_prev, h_out, none, ctx->stream)) return st;
+        if (const int st = denoise_enqueue(ctx, dg, *d, reinterpret_cast<const float *>(h_out + px * 32), reinterpret_cast<float *>(dev + off[6]),
+                                           bytes[7] ? dev + off[7] : nullptr, ctx->stream))
+            return st;
+        HIP_TRY(ctx, hipMemcpyAsync(out_rgb + (size_t)i * px * 3, dev + off[6], bytes[6], hipMemcpyDeviceToHost, ctx->stream));
+    }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return C2RT_OK;
 }

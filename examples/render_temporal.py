@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""An orbit around a scene as a global-illumination SEQUENCE, frame by frame, with and without history.  Every frame
+draws its own noise (seed + i); without history the speckle of the indirect light dances from frame to frame, with it
+every pixel's world point is projected into the previous camera, the accumulated value is fetched where the surface is
+the same one, and the new sample is folded into a running mean (Context.temporalAccumulate) before the a-trous filter
+runs.  The script writes <stem>_NN_raw.bmp (the filter alone) and <stem>_NN_temporal.bmp (accumulation, then the filter)
+for every frame and prints, per frame, how many pixels found their history and the speckle of the indirect light — the mean
+difference between neighbouring hit pixels — before and after the accumulation.
+
+  python examples/render_temporal.py tests/golden/scenes/lecture5.sdl /tmp/orbit --size 640 480 --frames 8 --paths 4
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import chess2rt_amd as c2
+
+
+def write(path, image):
+    with open(path, "wb") as f:
+        f.write(c2.saveBmp(np.ascontiguousarray(image, dtype=np.float32)))
+    return path
+
+
+def roughness(image, hit):
+    """mean absolute difference between horizontal neighbours that are both hits"""
+    both = hit[:, 1:] & hit[:, :-1]
+    return float(np.abs(image[:, 1:] - image[:, :-1])[both].mean()) if both.any() else 0.0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("scene")
+    ap.add_argument("stem", help="the images are written as <stem>_NN_raw.bmp and <stem>_NN_temporal.bmp")
+    ap.add_argument("--size", type=int, nargs=2, metavar=("W", "H"), default=(640, 480))
+    ap.add_argument("--frames", type=int, default=8)
+    ap.add_argument("--paths", type=int, default=4)
+    ap.add_argument("--step", type=float, nargs=2, metavar=("MOVE", "YAW"), default=(6.0, 2.0),
+                    help="per frame: Camera.move to the right by MOVE, Camera.rotate by -YAW degrees, which keeps the scene's middle in view")
+    ap.add_argument("--max-age", type=int, default=32, help="the running mean stops growing at this many samples")
+    ap.add_argument("--min-normal-dot", type=float, default=0.9)
+    ap.add_argument("--max-plane-dist", type=float, default=0.1)
+    ap.add_argument("--levels", type=int, default=4)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    scene = c2.parseSceneFromFile(args.scene)
+    scene.setFrameSize(*args.size)
+    scene.setAA(False)
+    scene.setDof(False)
+    depth = max(1, min(scene.settings.max_trace_depth, 8))
+    ctx = c2.Context()
+    ctx.uploadScene(scene.desc)
+    opts = scene.renderOpts()
+    prev_cam, history = None, None
+    for i in range(args.frames):
+        cam = scene.beginFrame()
+        hits = ctx.renderHits(cam, opts, planes=("node", "normal", "p", "rgb"))
+        albedo = ctx.renderShading(cam, opts, planes=("albedo",))["albedo"]
+        indirect = ctx.renderPaths(cam, opts, args.paths, depth, seed=args.seed + i, planes=("indirect",))["indirect"]
+        acc, history = ctx.temporalAccumulate(hits, indirect, prev_cam=prev_cam, history=history, max_age=args.max_age,
+                                              min_normal_dot=args.min_normal_dot, max_plane_dist=args.max_plane_dist)
+        frames = {"raw": ctx.denoise(hits, indirect, levels=args.levels, albedo=albedo, base=hits["rgb"]),
+                  "temporal": ctx.denoise(hits, acc["colour"], levels=args.levels, albedo=albedo, base=hits["rgb"])}
+        hit = hits["node"] >= 0
+        found = int((acc["age"] > 1).sum())
+        print("frame %2d: %5.1f %% of the hit pixels found their history, mean age %.1f; neighbour-to-neighbour difference of the indirect light %.4f -> %.4f"
+              % (i, 100.0 * found / max(int(hit.sum()), 1), float(acc["age"][hit].mean()) if hit.any() else 0.0, roughness(indirect, hit),
+                 roughness(acc["colour"], hit)))
+        for k, image in frames.items():
+            write("%s_%02d_%s.bmp" % (args.stem, i, k), image)
+        prev_cam = cam
+        scene.moveCamera(args.step[0], 0.0, 0.0)
+        scene.rotateCamera(-args.step[1], 0.0, 0.0)
+    print("wrote %d frames twice under %s_*" % (args.frames, args.stem))
+
+
+if __name__ == "__main__":
+    main()

@@ -1117,6 +1117,132 @@ int c2rt_denoise(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_host, const c2
 int c2rt_render_paths_denoised(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
                                const c2rt_path_opts *g, const c2rt_denoise_opts *d, float *out_rgb);
 
+/* ---- temporal accumulation: reproject the previous frame's history, fold the new sample into a running mean ---- */
+
+/* Largest max_age; C2RT_ERR_LIMIT beyond (an age is exact in fp32 far beyond it; the bound keeps 1 / N away from 2^-24). */
+#define C2RT_MAX_TEMPORAL_AGE 65535
+
+typedef struct c2rt_temporal_opts {    /* 32 bytes */
+    uint32_t width, height;        /* the WHOLE frame: no strips */
+    uint32_t channels;             /* 1 | 3 */
+    uint32_t max_age;              /* 1 .. C2RT_MAX_TEMPORAL_AGE: the running mean's N stops growing here (1: no accumulation) */
+    float    min_normal_dot;       /* finite, 0 <= . < 1: a history tap counts only if dot(n, n') > this */
+    float    max_plane_dist;       /* finite, > 0: ... and only if it lies this close to the pixel's tangent plane */
+    uint32_t reserved[2];          /* 0 */
+} c2rt_temporal_opts;
+
+typedef struct c2rt_temporal_guides {  /* 24 bytes: the CURRENT frame's hit planes, all required */
+    const int32_t *node;     /* [H][W]     the hit planes' `node`, < 0: no hit */
+    const double  *normal;   /* [H][W][3]  the hit planes' `normal`, exactly as c2rt_render_hits writes it */
+    const double  *p;        /* [H][W][3]  the hit planes' `p` */
+} c2rt_temporal_guides;
+
+typedef struct c2rt_temporal_planes {  /* 24 bytes: the outputs, each nullable */
+    float    *colour;        /* [H][W][channels]  the accumulated plane */
+    float    *variance;      /* [H][W]  temporal variance of the luminance */
+    uint32_t *age;           /* [H][W]  samples behind the pixel: 0 miss, 1 no history, .. max_age */
+} c2rt_temporal_planes;
+
+/* Every pixel's world point `p` is projected into the PREVIOUS camera; the previous call's accumulated value is fetched
+ * there, bilinearly, from the taps that lie on the same surface; the new sample `in` is folded into a running mean whose
+ * count stops at max_age.  The stage traces nothing and needs no uploaded scene.  All planes are full-frame, row-major
+ * [H][W]; `in` and `colour` are float[channels] per pixel.
+ *
+ * The history is the state between two calls.  The caller owns two of them and swaps them; the layout is part of the
+ * contract, planar over px = width * height pixels, c2rt_temporal_history_bytes = px * (32 + 4 * channels + 8) bytes,
+ * 16-byte aligned:
+ *   g0[px]            float4  (nf.x, nf.y, nf.z, the bits of the int32 node)
+ *   g1[px]            float4  (pf.x, pf.y, pf.z, the bits of the uint32 age)
+ *   c[px][channels]   float   the accumulated colour (what `colour` holds)
+ *   m[px]             float2  (M1, M2): the running means of the luminance and of its square
+ * nf and pf are the filter's "per pixel, once" conversions: nf.c = (float)normal.c, pf.c = (float)p.c.
+ *
+ * The arithmetic is the contract — the reprojection in fp64, the gather in fp32, no libm call, no contraction, IEEE
+ * divides, subnormals kept — and tests/temporal_reference.py restates it in numpy to the bit:
+ *
+ *   per call, on the host, in fp64 (they invert Camera.getScreenRay, rt/camera.d:140-145: with p - pos = a A + b U + c V the
+ *   screen position is (W b / a, H c / a), and det cancels out of the quotients):
+ *     A = prev.up_left - prev.pos;  U = prev.up_right - prev.up_left;  V = prev.down_left - prev.up_left
+ *     na = cross(U, V);  nb = cross(V, A);  nc = cross(A, U)        -- cross(a, b).x = a.y*b.z - a.z*b.y, and so on
+ *     det = (A.x*na.x + A.y*na.y) + A.z*na.z;  Wd = (double)width;  Hd = (double)height
+ *
+ *   pixel q = (x, y):
+ *     node[q] < 0 (a miss):  colour = in[q] (the bits); M1 = M2 = variance = +0f; age = 0
+ *     else:
+ *       r.c = p[q].c - prev.pos.c
+ *       ka = (r.x*na.x + r.y*na.y) + r.z*na.z;  kb, kc likewise with nb, nc
+ *       s = det > 0 ? ka : -ka;                                    !(s > 0): NO HISTORY  (behind the camera, at its eye, NaN)
+ *       sx = (kb / ka) * Wd;  sy = (kc / ka) * Hd
+ *       !(sx > -1.0 && sx < Wd && sy > -1.0 && sy < Hd):           NO HISTORY
+ *       x0 = floor(sx); fx = (float)(sx - x0);  y0 = floor(sy); fy = (float)(sy - y0)
+ *       wx = {1f - fx, fx};  wy = {1f - fy, fy}
+ *       sumw = sum.c = s1 = s2 = +0f;  amin = UINT32_MAX
+ *       for j in 0..1: for i in 0..1:               -- this ORDER of the fp32 sums is the contract
+ *         t = (x0 + i, y0 + j); outside the frame: skip
+ *         w = wx[i] * wy[j];                                       !(w > 0): skip   -- zero, NaN, underflow
+ *         the history's node[t] != node[q]: skip
+ *         dn = (nf[q].x*hn.x + nf[q].y*hn.y) + nf[q].z*hn.z;       !(dn > min_normal_dot): skip     -- hn = the history's nf[t]
+ *         d.c = hp.c - pf[q].c;  dp = (nf[q].x*d.x + nf[q].y*d.y) + nf[q].z*d.z                     -- hp = the history's pf[t]
+ *         !(fabsf(dp) <= max_plane_dist): skip
+ *         sumw = sumw + w;  sum.c = sum.c + w * hc.c;  s1 = s1 + w * hM1;  s2 = s2 + w * hM2        -- multiply, then add
+ *         amin = min(amin, the history's age[t])
+ *       !(sumw > 0):                                               NO HISTORY
+ *       h.c = sum.c / sumw;  m1 = s1 / sumw;  m2 = s2 / sumw
+ *       n = min(amin + 1, max_age)  (without wrapping);  a = 1f / (float)n
+ *       colour.c = h.c + (in.c - h.c) * a
+ *       lum = (0.2126f*in.r + 0.7152f*in.g) + 0.0722f*in.b          (one channel: lum = in)
+ *       M1 = m1 + (lum - m1) * a;  M2 = m2 + (lum*lum - m2) * a
+ *       v = M2 - M1*M1;  variance = v > 0 ? v : +0f;  age = n
+ *     NO HISTORY:  colour = in[q] (the bits);  M1 = lum;  M2 = lum*lum;  variance = +0f;  age = 1
+ *   the history out takes (nf, node), (pf, age), colour and (M1, M2) of EVERY pixel, misses included.
+ *   history_prev == NULL (the first frame) makes every hit pixel NO HISTORY; prev_cam may then be null as well.
+ *
+ *   - max_age == 1 passes `in` through (a = 1: colour = h + (in - h), within an ulp of in); a large max_age is the plain
+ *     running mean of everything seen on the surface.
+ *   - A NaN normal or a `p` beyond fp32 drops the taps it makes NaN; a NaN `in` reaches its own pixel now and, through
+ *     the history, the pixels that fetch it later.
+ *   - What is NOT promised: a node moved by c2rt_update_scene between two frames keeps its index and simply fails the
+ *     plane test where it moved far enough — it restarts, nothing follows it.  Posed sequences are out of scope; so is
+ *     any clamp of the history against the new frame's neighbourhood.
+ *
+ * c2rt_temporal_history_bytes: pure host arithmetic, no context; 0 for options c2rt_temporal_accumulate_device refuses.
+ *
+ * c2rt_temporal_accumulate_device takes the stream rules of c2rt_denoise_device (no host sync, no event, nothing kept of
+ * the stream, the lead device of a multi-device context, no uploaded scene), enqueues ONE kernel and writes only
+ * `history_out_dev` and the planes given.  `prev_cam` and `o` are host memory, read before the call returns.
+ *
+ * Statuses, all decided before anything is enqueued or written, each with its own message, in this order.
+ * C2RT_ERR_INVALID_ARG: null context; null `o`; null `guides`; width or height 0; channels not 1 or 3; min_normal_dot NaN,
+ * infinite, < 0 or >= 1; max_plane_dist NaN, infinite or <= 0; reserved != 0.  C2RT_ERR_LIMIT: max_age 0 or above
+ * C2RT_MAX_TEMPORAL_AGE.  C2RT_ERR_INVALID_ARG again: null `node`, `normal` or `p`; null `in`; null `history_out`; null
+ * `planes` (a struct of three null pointers is fine: the history alone); a non-null `history_prev` with a null
+ * `prev_cam`; with a history, det zero or not finite ("degenerate previous camera"); history_out == history_prev;
+ * colour == in; a history (either) that is not 16-byte aligned. */
+size_t c2rt_temporal_history_bytes(const c2rt_temporal_opts *o);
+int c2rt_temporal_accumulate_device(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_dev,
+                                    const c2rt_temporal_opts *o, const float *in_dev, const void *history_prev_dev,
+                                    void *history_out_dev, const c2rt_temporal_planes *planes_dev, void *hip_stream);
+/* The same from and into HOST memory, the histories as host byte blobs of c2rt_temporal_history_bytes: guides, `in`, both
+ * histories and the planes go through the context's grow-only staging buffer on the context's own stream, whole (at most
+ * 188 B per pixel; nothing is allocated once the buffer is large enough); blocks until the planes and `history_out` are
+ * there.  The same statuses; a host history needs no alignment. */
+int c2rt_temporal_accumulate(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_host,
+                             const c2rt_temporal_opts *o, const float *in, const void *history_prev, void *history_out,
+                             const c2rt_temporal_planes *planes_host);
+
+/* A global-illumination SEQUENCE in one call: for each i, on the device, the hit planes of cams[i] (node, normal, p, rgb),
+ * the shading planes' `albedo`, the path planes' `indirect` with seed g->seed + i, the accumulation of `indirect` (prev_cam
+ * = &cams[i - 1] and frame i - 1's history; frame 0 has neither), and the filter of the accumulated plane with albedo and
+ * base = rgb into out_rgb[i]; 12 B per pixel and frame come back.  out_rgb[n_frames][H][W][3] is bit for bit what a caller
+ * composes from c2rt_render_hits, c2rt_render_shading, c2rt_render_paths, c2rt_temporal_accumulate and c2rt_denoise.  The
+ * two histories live in the context's staging buffer beside the frame's planes (248 B per pixel in all, whatever
+ * n_frames); blocks until the last frame is there.  Statuses, in this order: those of c2rt_render_paths_denoised for
+ * cams[0] (null `cams` is its null camera); n_frames == 0: C2RT_ERR_INVALID_ARG; null `t`; t->width / t->height other
+ * than the frame's, t->channels != 3: C2RT_ERR_INVALID_ARG; then the temporal options' own; then, for every later camera,
+ * C2RT_ERR_UNSUPPORTED naming "depth of field" or "stereo", and "degenerate previous camera" for every camera but the last. */
+int c2rt_render_paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
+                               const c2rt_path_opts *g, const c2rt_temporal_opts *t, const c2rt_denoise_opts *d, float *out_rgb);
+
 /* ---- adaptive anti-aliasing: refine only the pixels the edge test flags ----- */
 
 /* tooDifferent's default threshold — rt/color.d:18 */

@@ -281,6 +281,39 @@ extern (C) nothrow @nogc
     int c2rt_denoise(c2rt_ctx*, const c2rt_denoise_guides* guides_host, const c2rt_denoise_opts*, const float* in_, float* out_);
     int c2rt_render_paths_denoised(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_path_opts*,
                                    const c2rt_denoise_opts*, float* out_rgb);
+    /// temporal accumulation: reproject the previous frame's history through the hit planes' p, fold the new sample into a
+    /// running mean; full-frame planes, fp64 reprojection and fp32 gather fixed by include/c2rt.h
+    enum C2RT_MAX_TEMPORAL_AGE = 65535;
+    struct c2rt_temporal_opts
+    {
+        uint width, height;         /// the whole frame
+        uint channels;              /// 1 | 3
+        uint max_age;               /// 1 .. C2RT_MAX_TEMPORAL_AGE
+        float min_normal_dot;       /// finite, 0 <= . < 1
+        float max_plane_dist;       /// finite, > 0
+        uint[2] reserved;           /// 0
+    }
+    struct c2rt_temporal_guides
+    {
+        const(int)* node;           /// the CURRENT frame's hit planes, all required
+        const(double)* normal;      /// [3] per pixel
+        const(double)* p;           /// [3] per pixel
+    }
+    struct c2rt_temporal_planes
+    {
+        float* colour;              /// nullable: [channels] per pixel, the accumulated plane
+        float* variance;            /// nullable: temporal variance of the luminance
+        uint* age;                  /// nullable: 0 miss, 1 no history, .. max_age
+    }
+    size_t c2rt_temporal_history_bytes(const c2rt_temporal_opts*);
+    int c2rt_temporal_accumulate_device(c2rt_ctx*, const c2rt_camera_frame* prev_cam, const c2rt_temporal_guides* guides_dev,
+                                        const c2rt_temporal_opts*, const float* in_dev, const void* history_prev_dev,
+                                        void* history_out_dev, const c2rt_temporal_planes* planes_dev, void* hip_stream);
+    int c2rt_temporal_accumulate(c2rt_ctx*, const c2rt_camera_frame* prev_cam, const c2rt_temporal_guides* guides_host,
+                                 const c2rt_temporal_opts*, const float* in_, const void* history_prev, void* history_out,
+                                 const c2rt_temporal_planes* planes_host);
+    int c2rt_render_paths_sequence(c2rt_ctx*, const c2rt_camera_frame* cams, uint n_frames, const c2rt_render_opts*,
+                                   const c2rt_path_opts*, const c2rt_temporal_opts*, const c2rt_denoise_opts*, float* out_rgb);
     enum float C2RT_AA_THRESHOLD_REF = 0.1f; /// tooDifferent's default
     int c2rt_render_frame_adaptive_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
                                           float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
