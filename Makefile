@@ -53,6 +53,7 @@ KERNELFLAGS_QUERY :=
 # c2rt_denoise (the a-trous filter, c2rt_denoise*): an fp32 stencil that traces nothing and includes none of the trace
 # headers; the arithmetic flags only, none of the code-generation flags above
 # c2rt_temporal (the temporal accumulation, c2rt_temporal_accumulate*): the same — a gather that traces nothing
+# c2rt_denoise_variance (the variance-guided filter, c2rt_denoise_variance*): the same
 CXXFLAGS   := -O2 -std=c++17 -fPIC $(FPFLAGS) -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 CSRC       := chess2rt_amd/csrc
 # development knob: `make VARIANT=name EXTRA_HIPFLAGS=... EXTRA_KERNEL_FLAGS=...` builds chess2rt_amd/libc2rt_name.so
@@ -63,7 +64,7 @@ LIBNAME    := chess2rt_amd/libc2rt$(if $(VARIANT),_$(VARIANT)).so
 
 UNITS      := 0 1 2 3 4 5
 QUERIES    := c2rt_rays c2rt_hit_planes c2rt_layers c2rt_shade_planes c2rt_occlusion c2rt_gather c2rt_paths c2rt_adaptive c2rt_sample_taps
-KOBJS      := $(foreach u,$(UNITS),$(BUILD)/c2rt_kernels_u$(u).o) $(foreach q,$(QUERIES),$(BUILD)/$(q).o) $(BUILD)/c2rt_denoise.o $(BUILD)/c2rt_temporal.o
+KOBJS      := $(foreach u,$(UNITS),$(BUILD)/c2rt_kernels_u$(u).o) $(foreach q,$(QUERIES),$(BUILD)/$(q).o) $(BUILD)/c2rt_denoise.o $(BUILD)/c2rt_temporal.o $(BUILD)/c2rt_denoise_variance.o
 HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/scene.o $(BUILD)/host_api.o
 
 # diagnostics build of the same library: c2rt_api.cpp with the environment hooks compiled in (-DC2RT_DIAG=1), linked
@@ -91,7 +92,10 @@ $(BUILD)/c2rt_denoise.o: $(CSRC)/c2rt_denoise.hip $(CSRC)/c2rt_denoise.h include
 $(BUILD)/c2rt_temporal.o: $(CSRC)/c2rt_temporal.hip $(CSRC)/c2rt_temporal.h include/c2rt.h Makefile | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_KERNEL_FLAGS) -c $< -o $@
 
-$(BUILD)/c2rt_api.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
+$(BUILD)/c2rt_denoise_variance.o: $(CSRC)/c2rt_denoise_variance.hip $(CSRC)/c2rt_denoise_variance.h $(CSRC)/c2rt_denoise.h include/c2rt.h Makefile | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_KERNEL_FLAGS) -c $< -o $@
+
+$(BUILD)/c2rt_api.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_denoise_variance.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -c $< -o $@
 
 # the HIP-free planner (scene validation and packing, per-frame culling decisions)
@@ -104,7 +108,7 @@ $(BUILD)/%.o: $(CSRC)/host/%.cpp $(CSRC)/host/scene.hpp $(CSRC)/host/dsc.hpp inc
 $(LIBNAME): $(KOBJS) $(HOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
-$(BUILD)/c2rt_api_diag.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
+$(BUILD)/c2rt_api_diag.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_denoise_variance.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -DC2RT_DIAG=1 -c $< -o $@
 
 $(DIAGNAME): $(KOBJS) $(BUILD)/c2rt_api_diag.o $(filter-out $(BUILD)/c2rt_api.o,$(HOBJS))
@@ -117,7 +121,7 @@ $(DIAGNAME): $(KOBJS) $(BUILD)/c2rt_api_diag.o $(filter-out $(BUILD)/c2rt_api.o,
 $(BUILD)/c2rt_kernels_u1_stats.o: $(CSRC)/c2rt_kernels.hip $(TRACE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_u1) $(EXTRA_KERNEL_FLAGS) -DC2RT_TILE_STATS=1 -DC2RT_UNIT=1 -c $< -o $@
 
-$(BUILD)/c2rt_api_stats.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
+$(BUILD)/c2rt_api_stats.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_denoise_variance.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -DC2RT_DIAG=1 -DC2RT_TILE_STATS=1 -c $< -o $@
 
 $(STATSNAME): $(filter-out $(BUILD)/c2rt_kernels_u1.o,$(KOBJS)) $(BUILD)/c2rt_kernels_u1_stats.o $(BUILD)/c2rt_api_stats.o $(filter-out $(BUILD)/c2rt_api.o,$(HOBJS))

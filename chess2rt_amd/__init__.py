@@ -5,9 +5,9 @@ the reference's Scene / Camera / Renderer API mirrored in C++
 (include/c2rt_host.h) and exposed here through ctypes.  No CPU fallback.
 """
 from . import _abi
-from ._abi import (CameraFrame, DenoiseGuides, DenoiseOpts, GatherOpts, GatherPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc, ScenePose, Segment,
+from ._abi import (CameraFrame, DenoiseGuides, DenoiseOpts, DenoiseVarianceOpts, GatherOpts, GatherPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc, ScenePose, Segment,
                    ShadePlanes, TapTable, TemporalGuides, TemporalOpts, TemporalPlanes, TraceResult, TAPS_1, TAPS_4, TAPS_REF5)
-from .api import (GATHER_PLANES, OCCLUSION_PLANES, PATH_PLANES, RAY_HIT_DTYPE, SHADE_PLANES, TAPS_REF5_TABLE, TEMPORAL_PLANES, C2rtError, Context, Renderer, Scene, denoise_scratch_bytes, loadBmpImage, makePose, parseSceneFromFile, renderPixel, saveBmp, tap_grid, temporal_history_bytes)
+from .api import (GATHER_PLANES, OCCLUSION_PLANES, PATH_PLANES, RAY_HIT_DTYPE, SHADE_PLANES, TAPS_REF5_TABLE, TEMPORAL_PLANES, C2rtError, Context, Renderer, Scene, denoise_scratch_bytes, denoise_variance_scratch_bytes, loadBmpImage, makePose, parseSceneFromFile, renderPixel, saveBmp, tap_grid, temporal_history_bytes)
 from .sharding import (StripPlan, deinterleave_strips_torch, exchange_strips_p2p, local_rows, plan_strips, render_frame_sharded)
 
 __all__ = [
@@ -17,7 +17,7 @@ __all__ = [
     "OcclusionOpts", "OcclusionPlanes", "OCCLUSION_PLANES",
     "GatherOpts", "GatherPlanes", "GATHER_PLANES",
     "PathOpts", "PathPlanes", "PATH_PLANES",
-    "DenoiseGuides", "DenoiseOpts", "denoise_scratch_bytes",
+    "DenoiseGuides", "DenoiseOpts", "denoise_scratch_bytes", "DenoiseVarianceOpts", "denoise_variance_scratch_bytes",
     "TemporalGuides", "TemporalOpts", "TemporalPlanes", "TEMPORAL_PLANES", "temporal_history_bytes",
     "TAPS_1", "TAPS_4", "TAPS_REF5", "TapTable", "TAPS_REF5_TABLE", "tap_grid",
     "StripPlan", "plan_strips", "local_rows", "render_frame_sharded", "deinterleave_strips_torch", "exchange_strips_p2p",

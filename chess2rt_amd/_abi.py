@@ -27,6 +27,7 @@ MAX_RAYS = 1 << 28
 MAX_HIT_LAYERS = 16
 MAX_SAMPLE_TAPS = 16
 MAX_DENOISE_LEVELS = 8
+MAX_VARIANCE_MIN_AGE = 64
 MAX_TEMPORAL_AGE = 65535
 AA_THRESHOLD_REF = 0.1     # C2RT_AA_THRESHOLD_REF (0.1f: passed as a C float)
 
@@ -264,6 +265,24 @@ class DenoiseOpts(C.Structure):
     ]
 
 
+class DenoiseVarianceOpts(C.Structure):
+    """c2rt_denoise_variance_opts: c2rt_denoise_opts with the colour scale replaced by the luminance term's (sigma_lum
+    local standard deviations, var_floor under the variance) and the age below which a pixel's variance is estimated
+    from its neighbourhood (0 .. 64)"""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("levels", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("normal_power_log2", C.c_uint32),
+        ("sigma_plane", C.c_float),
+        ("sigma_lum", C.c_float),
+        ("var_floor", C.c_float),
+        ("min_age", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class TemporalOpts(C.Structure):
     """c2rt_temporal_opts: the whole frame's size, channels (1 | 3), the age at which the running mean stops growing
     (1 .. 65535), the normal and plane tests of a history tap"""
@@ -417,6 +436,11 @@ C2RT_SYMBOLS = {
     "c2rt_temporal_accumulate_device": (C.c_int, [_VP, _CAM_P, C.POINTER(TemporalGuides), C.POINTER(TemporalOpts), _VP, _VP, _VP, C.POINTER(TemporalPlanes), _VP]),
     "c2rt_temporal_accumulate": (C.c_int, [_VP, _CAM_P, C.POINTER(TemporalGuides), C.POINTER(TemporalOpts), _VP, _VP, _VP, C.POINTER(TemporalPlanes)]),
     "c2rt_render_paths_sequence": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.POINTER(PathOpts), C.POINTER(TemporalOpts), C.POINTER(DenoiseOpts), _VP]),
+    "c2rt_denoise_variance_scratch_bytes": (C.c_size_t, [C.POINTER(DenoiseVarianceOpts)]),
+    "c2rt_denoise_variance_device": (C.c_int, [_VP, C.POINTER(DenoiseGuides), C.POINTER(DenoiseVarianceOpts), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "c2rt_denoise_variance": (C.c_int, [_VP, C.POINTER(DenoiseGuides), C.POINTER(DenoiseVarianceOpts), _VP, _VP, _VP, _VP, _VP]),
+    "c2rt_render_paths_sequence_variance": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.POINTER(PathOpts), C.POINTER(TemporalOpts),
+                                                      C.POINTER(DenoiseVarianceOpts), _VP]),
     "c2rt_render_frame_adaptive_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frame_adaptive": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frames_adaptive_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),

@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (CameraFrame, DenoiseGuides, DenoiseOpts, GatherOpts, GatherPlanes, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
+from ._abi import (CameraFrame, DenoiseGuides, DenoiseOpts, DenoiseVarianceOpts, GatherOpts, GatherPlanes, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
                    ScenePose, Segment, ShadePlanes, TapTable, TemporalGuides, TemporalOpts, TemporalPlanes, TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
@@ -138,6 +138,26 @@ def denoise_scratch_bytes(width, height, channels=3, levels=5, normal_power_log2
     to fp32, 32 B per pixel, and for levels > 1 one ping-pong plane); 0 for levels == 0 and for options it would refuse."""
     o = _denoise_opts(width, height, channels, levels, normal_power_log2, sigma_plane, sigma_colour)
     return int(_abi.load_library().c2rt_denoise_scratch_bytes(C.byref(o)))
+
+
+# Context.denoiseVariance's luminance scale (a tap whose luminance differs by sigma_lum local standard deviations weighs
+# half), the floor under the scaled variance, and the age below which a pixel's variance is estimated from its 7x7
+DENOISE_SIGMA_LUM = 4.0
+DENOISE_VAR_FLOOR = 1e-8
+DENOISE_MIN_AGE = 4
+
+
+def _denoise_variance_opts(width, height, channels, levels, normal_power_log2, sigma_plane, sigma_lum, var_floor, min_age):
+    return DenoiseVarianceOpts(width=int(width), height=int(height), levels=int(levels), channels=int(channels), normal_power_log2=int(normal_power_log2),
+                               sigma_plane=float(sigma_plane), sigma_lum=float(sigma_lum), var_floor=float(var_floor), min_age=int(min_age), reserved=0)
+
+
+def denoise_variance_scratch_bytes(width, height, channels=3, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE, sigma_lum=DENOISE_SIGMA_LUM,
+                                   var_floor=DENOISE_VAR_FLOOR, min_age=DENOISE_MIN_AGE):
+    """c2rt_denoise_variance_scratch_bytes: what Context.denoiseVarianceDevice needs at `scratch_ptr` for these options
+    (the packed guides, the colour ping-pong plane, three variance planes: at most 56 B per pixel); 0 for refused options."""
+    o = _denoise_variance_opts(width, height, channels, levels, normal_power_log2, sigma_plane, sigma_lum, var_floor, min_age)
+    return int(_abi.load_library().c2rt_denoise_variance_scratch_bytes(C.byref(o)))
 
 
 # Context.temporalAccumulate's defaults: the running mean grows to 32 samples; a history tap counts within 25 degrees of
@@ -1011,6 +1031,76 @@ class Context:
         out = np.empty((len(cams), opts.height, opts.width, 3), dtype=np.float32)
         self._check(self._lib.c2rt_render_paths_sequence(self._h, arr, len(cams), C.byref(opts), C.byref(g), C.byref(t), C.byref(d),
                                                          out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def denoiseVariance(self, guides, image, variance, age=None, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE,
+                        sigma_lum=DENOISE_SIGMA_LUM, var_floor=DENOISE_VAR_FLOOR, min_age=DENOISE_MIN_AGE, albedo=None, base=None, variance_out=True):
+        """The a-trous filter steered by the temporal planes (c2rt_denoise_variance).  `guides`, `image`, `albedo` and
+        `base` as for denoise; `variance` (H, W) float32 and `age` (H, W) uint32 or None: temporalAccumulate's planes.  In
+        place of a colour scale a tap is weighed by its luminance difference in units of `sigma_lum` local standard
+        deviations (the 3x3-smoothed variance, plus `var_floor`); the variance is filtered along, and a pixel younger than
+        `min_age` gets a variance estimated from its 7x7 neighbourhood.  Returns (out, variance_out): an array of
+        `image`'s shape and the (H, W) variance after the last level (None with variance_out=False)."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim not in (2, 3):
+            raise ValueError("denoiseVariance: image of shape %r (expected (H, W), (H, W, 1) or (H, W, 3))" % (image.shape,))
+        h, w = image.shape[:2]
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        keep = [np.ascontiguousarray(guides["node"], dtype=np.int32), np.ascontiguousarray(guides["normal"], dtype=np.float64),
+                np.ascontiguousarray(guides["p"], dtype=np.float64), np.ascontiguousarray(variance, dtype=np.float32)]
+        for a, shape, name in zip(keep, ((h, w), (h, w, 3), (h, w, 3), (h, w)), ("node", "normal", "p", "variance")):
+            if a.shape != shape:
+                raise ValueError("denoiseVariance: %s of shape %r (expected %r)" % (name, a.shape, shape))
+        g = DenoiseGuides(node=keep[0].ctypes.data, normal=keep[1].ctypes.data, p=keep[2].ctypes.data)
+        if age is not None:
+            age = np.ascontiguousarray(age, dtype=np.uint32)
+            if age.shape != (h, w):
+                raise ValueError("denoiseVariance: age of shape %r (expected %r)" % (age.shape, (h, w)))
+        for name, a in (("albedo", albedo), ("base", base)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.size != image.size:
+                    raise ValueError("denoiseVariance: %s of shape %r (expected %r)" % (name, a.shape, image.shape))
+                keep.append(a)
+                setattr(g, name, a.ctypes.data)
+        o = _denoise_variance_opts(w, h, ch, levels, normal_power_log2, sigma_plane, sigma_lum, var_floor, min_age)
+        out = np.empty_like(image)
+        vout = np.empty((h, w), dtype=np.float32) if variance_out else None
+        self._check(self._lib.c2rt_denoise_variance(self._h, C.byref(g), C.byref(o), keep[3].ctypes.data_as(C.c_void_p),
+                                                    None if age is None else age.ctypes.data_as(C.c_void_p), image.ctypes.data_as(C.c_void_p),
+                                                    out.ctypes.data_as(C.c_void_p), None if vout is None else vout.ctypes.data_as(C.c_void_p)))
+        return out, vout
+
+    def denoiseVarianceDevice(self, ptrs, width, height, variance_ptr, age_ptr, in_ptr, out_ptr, variance_out_ptr, scratch_ptr, channels=3, levels=5,
+                              normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE, sigma_lum=DENOISE_SIGMA_LUM, var_floor=DENOISE_VAR_FLOOR,
+                              min_age=DENOISE_MIN_AGE, stream=0):
+        """Enqueue the variance-guided filter on `stream` over device memory (c2rt_denoise_variance_device): `ptrs` as for
+        denoiseDevice; age_ptr and variance_out_ptr may be 0; `scratch_ptr`: denoise_variance_scratch_bytes(...) bytes,
+        16-byte aligned (0 where that is 0).  No sync; writes only out_ptr, variance_out_ptr and scratch_ptr."""
+        g = DenoiseGuides()
+        for n, ptr in dict(ptrs).items():
+            if n not in ("node", "normal", "p", "albedo", "base"):
+                raise ValueError("unknown denoise guide %r (one of node, normal, p, albedo, base)" % (n,))
+            setattr(g, n, ptr or None)
+        o = _denoise_variance_opts(width, height, channels, levels, normal_power_log2, sigma_plane, sigma_lum, var_floor, min_age)
+        self._check(self._lib.c2rt_denoise_variance_device(self._h, C.byref(g), C.byref(o), C.c_void_p(variance_ptr or None), C.c_void_p(age_ptr or None),
+                                                           C.c_void_p(in_ptr or None), C.c_void_p(out_ptr or None), C.c_void_p(variance_out_ptr or None),
+                                                           C.c_void_p(scratch_ptr or None), C.c_void_p(stream)))
+
+    def renderPathsSequenceVariance(self, cams, opts, paths, bounces, seed=0, max_age=TEMPORAL_MAX_AGE, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT,
+                                    max_plane_dist=TEMPORAL_MAX_PLANE_DIST, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE,
+                                    sigma_lum=DENOISE_SIGMA_LUM, var_floor=DENOISE_VAR_FLOOR, min_age=DENOISE_MIN_AGE):
+        """renderPathsSequence with the loop closed (c2rt_render_paths_sequence_variance): temporalAccumulate also writes
+        its variance and age planes and the filter is denoiseVariance(..., albedo=albedo, base=rgb), fed by them; (n,
+        height, width, 3) float32, bit for bit that composition."""
+        cams = list(cams)
+        arr = (CameraFrame * max(len(cams), 1))(*cams)
+        g = _path_opts(paths, bounces, seed)
+        t = _temporal_opts(opts.width, opts.height, 3, max_age, min_normal_dot, max_plane_dist)
+        d = _denoise_variance_opts(opts.width, opts.height, 3, levels, normal_power_log2, sigma_plane, sigma_lum, var_floor, min_age)
+        out = np.empty((len(cams), opts.height, opts.width, 3), dtype=np.float32)
+        self._check(self._lib.c2rt_render_paths_sequence_variance(self._h, arr, len(cams), C.byref(opts), C.byref(g), C.byref(t), C.byref(d),
+                                                                  out.ctypes.data_as(C.c_void_p)))
         return out
 
     def testVisibility(self, segments):

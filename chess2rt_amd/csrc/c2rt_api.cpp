@@ -26,6 +26,7 @@
 
 #include "c2rt_query.h"
 #include "c2rt_denoise.h"
+#include "c2rt_denoise_variance.h"
 #include "c2rt_temporal.h"
 #include "scene_plan.h"
 
@@ -1918,21 +1919,29 @@ int c2rt_denoise(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_host, const c2
     return C2RT_OK;
 }
 
-/* every refusal of c2rt_render_paths_denoised, in the documented order (c2rt_render_paths_sequence starts with them) */
-static int check_paths_denoised(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
-                                const c2rt_denoise_opts *d, const float *out_rgb)
+/* every refusal of c2rt_render_paths_denoised ahead of the filter options' own, in the documented order (the sequence
+ * calls start with them); have_opts: the filter's options of either kind are given, (width, height, channels) theirs */
+static int check_paths_filtered(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_path_opts *pg, bool have_opts,
+                                uint32_t width, uint32_t height, uint32_t channels, const float *out_rgb)
 {
     if (const int st = check_frame_args(ctx, cam, opts)) return st;
     if (const int st = Family<c2rt_path_planes>::check_opts(ctx, pg)) return st;
-    if (!d) return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise options");
+    if (!have_opts) return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise options");
     if (!out_rgb) return fail(ctx, C2RT_ERR_INVALID_ARG, "null output");
     if (const int st = check_one_ray_per_pixel(ctx, cam, opts, "paths are", "path")) return st;
     if (opts->strip_world > 1)
         return fail(ctx, C2RT_ERR_UNSUPPORTED, "strip_world is %u: the filter reads its neighbours, it needs the whole frame", (unsigned)opts->strip_world);
-    if (d->width != opts->width || d->height != opts->height)
-        return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise options for %u x %u pixels, the frame has %u x %u", (unsigned)d->width, (unsigned)d->height,
+    if (width != opts->width || height != opts->height)
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise options for %u x %u pixels, the frame has %u x %u", (unsigned)width, (unsigned)height,
                     (unsigned)opts->width, (unsigned)opts->height);
-    if (d->channels != 3) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise channels is %u: a frame has 3", (unsigned)d->channels);
+    if (channels != 3) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise channels is %u: a frame has 3", (unsigned)channels);
+    return C2RT_OK;
+}
+
+static int check_paths_denoised(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
+                                const c2rt_denoise_opts *d, const float *out_rgb)
+{
+    if (const int st = check_paths_filtered(ctx, cam, opts, pg, d != nullptr, d ? d->width : 0, d ? d->height : 0, d ? d->channels : 0, out_rgb)) return st;
     return check_denoise_opts(ctx, d);
 }
 
@@ -2113,10 +2122,121 @@ int c2rt_temporal_accumulate(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, c
     return C2RT_OK;
 }
 
-int c2rt_render_paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
-                               const c2rt_temporal_opts *t, const c2rt_denoise_opts *d, float *out_rgb)
+/* ---- variance-guided denoise: the filter steered by the temporal planes (c2rt_denoise_variance.hip) ---------------------- */
+
+/* the options' own refusals, in the documented order (`ctx` null: the status alone) */
+static int check_denoise_variance_opts(c2rt_ctx *ctx, const c2rt_denoise_variance_opts *o)
 {
-    if (const int st = check_paths_denoised(ctx, cams, opts, pg, d, out_rgb)) return st;
+    if (!o->width || !o->height)
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "variance denoise frame of %u x %u pixels: both must be above 0", (unsigned)o->width, (unsigned)o->height);
+    if (o->channels != 1 && o->channels != 3) return fail(ctx, C2RT_ERR_INVALID_ARG, "variance denoise channels is %u: 1 or 3", (unsigned)o->channels);
+    if (!(o->sigma_plane > 0) || !std::isfinite(o->sigma_plane))
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "sigma_plane %g: a finite length above 0", (double)o->sigma_plane);
+    if (!(o->sigma_lum >= 0) || !std::isfinite(o->sigma_lum))
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "sigma_lum %g: finite and not negative", (double)o->sigma_lum);
+    if (!(o->var_floor > 0) || !std::isfinite(o->var_floor)) return fail(ctx, C2RT_ERR_INVALID_ARG, "var_floor %g: finite and above 0", (double)o->var_floor);
+    if (o->reserved != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "c2rt_denoise_variance_opts.reserved is %u: must be 0", (unsigned)o->reserved);
+    if (o->levels > C2RT_MAX_DENOISE_LEVELS)
+        return fail(ctx, C2RT_ERR_LIMIT, "%u denoise levels (at most %u)", (unsigned)o->levels, (unsigned)C2RT_MAX_DENOISE_LEVELS);
+    if (o->normal_power_log2 > 7) return fail(ctx, C2RT_ERR_LIMIT, "normal_power_log2 is %u (at most 7)", (unsigned)o->normal_power_log2);
+    if (o->min_age > (uint32_t)C2RT_MAX_VARIANCE_MIN_AGE)
+        return fail(ctx, C2RT_ERR_LIMIT, "min_age is %u (at most %u)", (unsigned)o->min_age, (unsigned)C2RT_MAX_VARIANCE_MIN_AGE);
+    return C2RT_OK;
+}
+
+/* every refusal of c2rt_denoise_variance_device, in the documented order; with_scratch false: the host variant, whose
+ * scratch is the library's own */
+static int check_denoise_variance(c2rt_ctx *ctx, const c2rt_denoise_guides *g, const c2rt_denoise_variance_opts *o, const float *variance, const float *in,
+                                  const float *out, const float *variance_out, const void *scratch, bool with_scratch)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (!o) return fail(ctx, C2RT_ERR_INVALID_ARG, "null variance denoise options");
+    if (!g) return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise guides");
+    if (const int st = check_denoise_variance_opts(ctx, o)) return st;
+    if (!g->node) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: node");
+    if (!g->normal) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: normal");
+    if (!g->p) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: p");
+    if (!variance) return fail(ctx, C2RT_ERR_INVALID_ARG, "null variance plane");
+    if (!in) return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise input");
+    if (!out) return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise output");
+    if (out == in) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise output is the input: the filter does not run in place");
+    if (variance_out == variance) return fail(ctx, C2RT_ERR_INVALID_ARG, "variance output is the variance plane: the filter does not run in place");
+    if (!with_scratch) return C2RT_OK;
+    if (scratch && out == scratch) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise output is the scratch");
+    if (scratch && variance_out == scratch) return fail(ctx, C2RT_ERR_INVALID_ARG, "variance output is the scratch");
+    if (!scratch && c2rt_denoise_variance_scratch_bytes(o) != 0)
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "null denoise scratch: these options need %zu bytes", c2rt_denoise_variance_scratch_bytes(o));
+    if (reinterpret_cast<uintptr_t>(scratch) % 16 != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise scratch is not 16-byte aligned");
+    if (scratch && in == scratch) return fail(ctx, C2RT_ERR_INVALID_ARG, "denoise input is the scratch");
+    if (scratch && variance == scratch) return fail(ctx, C2RT_ERR_INVALID_ARG, "variance plane is the scratch");
+    return C2RT_OK;
+}
+
+/* the contract's per-call factors, in fp32, and the launches */
+static int denoise_variance_enqueue(c2rt_ctx *ctx, const c2rt_denoise_guides &g, const c2rt_denoise_variance_opts &o, const float *variance,
+                                    const uint32_t *age, const float *in, float *out, float *variance_out, void *scratch, void *stream)
+{
+    const float inv_plane = 1.0f / o.sigma_plane;
+    const volatile float sl2 = o.sigma_lum * o.sigma_lum;
+    const int e = launch_denoise_variance(g, o, inv_plane, sl2, variance, age, in, out, variance_out, scratch, stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "variance denoise kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+size_t c2rt_denoise_variance_scratch_bytes(const c2rt_denoise_variance_opts *o)
+{
+    if (!o || check_denoise_variance_opts(nullptr, o) != C2RT_OK) return 0;
+    return denoise_variance_scratch_bytes(*o);
+}
+
+int c2rt_denoise_variance_device(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_dev, const c2rt_denoise_variance_opts *o, const float *variance_dev,
+                                 const uint32_t *age_dev, const float *in_dev, float *out_dev, float *variance_out_dev, void *scratch_dev, void *hip_stream)
+{
+    if (const int st = check_denoise_variance(ctx, guides_dev, o, variance_dev, in_dev, out_dev, variance_out_dev, scratch_dev, true)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return denoise_variance_enqueue(ctx, *guides_dev, *o, variance_dev, age_dev, in_dev, out_dev, variance_out_dev, scratch_dev, hip_stream);
+}
+
+int c2rt_denoise_variance(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_host, const c2rt_denoise_variance_opts *o, const float *variance,
+                          const uint32_t *age, const float *in, float *out, float *variance_out)
+{
+    if (const int st = check_denoise_variance(ctx, guides_host, o, variance, in, out, variance_out, nullptr, false)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)o->width * o->height, colour = (size_t)o->channels * sizeof(float);
+    /* [node | normal | p | albedo | base | variance | age | in | out | variance_out | scratch], each 256-byte aligned */
+    const void *host[8] = {guides_host->node, guides_host->normal, guides_host->p, guides_host->albedo, guides_host->base, variance, age, in};
+    const size_t bytes[11] = {px * 4, px * 24, px * 24, guides_host->albedo ? px * colour : 0, guides_host->base ? px * colour : 0, px * 4,
+                              age ? px * 4 : 0, px * colour, px * colour, variance_out ? px * 4 : 0, c2rt_denoise_variance_scratch_bytes(o)};
+    size_t off[11], at = 0;
+    for (int k = 0; k < 11; ++k) {
+        off[k] = at;
+        at = align256(at + bytes[k]);
+    }
+    if (const int e = ensure_staging(ctx, at)) return e;
+    char *dev = reinterpret_cast<char *>(ctx->frame);
+    for (int k = 0; k < 8; ++k)
+        if (bytes[k]) HIP_TRY(ctx, hipMemcpyAsync(dev + off[k], host[k], bytes[k], hipMemcpyHostToDevice, ctx->stream));
+    c2rt_denoise_guides g;
+    g.node = reinterpret_cast<const int32_t *>(dev + off[0]);
+    g.normal = reinterpret_cast<const double *>(dev + off[1]);
+    g.p = reinterpret_cast<const double *>(dev + off[2]);
+    g.albedo = bytes[3] ? reinterpret_cast<const float *>(dev + off[3]) : nullptr;
+    g.base = bytes[4] ? reinterpret_cast<const float *>(dev + off[4]) : nullptr;
+    if (const int st = denoise_variance_enqueue(ctx, g, *o, reinterpret_cast<const float *>(dev + off[5]),
+                                                bytes[6] ? reinterpret_cast<const uint32_t *>(dev + off[6]) : nullptr,
+                                                reinterpret_cast<const float *>(dev + off[7]), reinterpret_cast<float *>(dev + off[8]),
+                                                bytes[9] ? reinterpret_cast<float *>(dev + off[9]) : nullptr, bytes[10] ? dev + off[10] : nullptr, ctx->stream))
+        return st;
+    HIP_TRY(ctx, hipMemcpyAsync(out, dev + off[8], bytes[8], hipMemcpyDeviceToHost, ctx->stream));
+    if (bytes[9]) HIP_TRY(ctx, hipMemcpyAsync(variance_out, dev + off[9], bytes[9], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return C2RT_OK;
+}
+
+/* the two sequence calls: `d` the plain filter's options or `dv` the variance-guided one's, the other null */
+static int paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
+                          const c2rt_temporal_opts *t, const c2rt_denoise_opts *d, const c2rt_denoise_variance_opts *dv, float *out_rgb)
+{
     if (n_frames == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "n_frames is 0: a sequence has at least one frame");
     if (!t) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal options");
     if (t->width != opts->width || t->height != opts->height)
@@ -2134,11 +2254,13 @@ int c2rt_render_paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uin
         if (const int st = check_previous_camera(ctx, cams[i], *t, k)) return st;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)opts->width * opts->height, hist = temporal_history_bytes(*t);
-    /* [node | normal | p | rgb | albedo | indirect | out | scratch | history 0 | history 1], each 256-byte aligned; the
-     * accumulated plane the filter reads is the colour plane of the history just written */
-    const size_t bytes[10] = {px * 4, px * 24, px * 24, px * 12, px * 12, px * 12, px * 12, c2rt_denoise_scratch_bytes(d), hist, hist};
-    size_t off[10], at = 0;
-    for (int i = 0; i < 10; ++i) {
+    /* [node | normal | p | rgb | albedo | indirect | out | scratch | history 0 | history 1 | variance | age], each 256-byte
+     * aligned; the accumulated plane the filter reads is the colour plane of the history just written; the last two for the
+     * variance-guided filter only */
+    const size_t bytes[12] = {px * 4, px * 24, px * 24, px * 12, px * 12, px * 12, px * 12, d ? c2rt_denoise_scratch_bytes(d) : c2rt_denoise_variance_scratch_bytes(dv),
+                              hist, hist, dv ? px * 4 : 0, dv ? px * 4 : 0};
+    size_t off[12], at = 0;
+    for (int i = 0; i < 12; ++i) {
         off[i] = at;
         at = align256(at + bytes[i]);
     }
@@ -2156,7 +2278,11 @@ int c2rt_render_paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uin
     paths.indirect = reinterpret_cast<float *>(dev + off[5]);
     const c2rt_temporal_guides tg = {hits.node, hits.normal, hits.p};
     const c2rt_denoise_guides dg = {hits.node, hits.normal, hits.p, shade.albedo, hits.rgb};
-    const c2rt_temporal_planes none = {};
+    c2rt_temporal_planes tp = {};
+    if (dv) {
+        tp.variance = reinterpret_cast<float *>(dev + off[10]);
+        tp.age = reinterpret_cast<uint32_t *>(dev + off[11]);
+    }
     for (uint32_t i = 0; i < n_frames; ++i) {
         RenderParams p;
         hit_params(ctx, &cams[i], opts, p);
@@ -2168,14 +2294,33 @@ int c2rt_render_paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uin
         if (e != 0) return fail(ctx, C2RT_ERR_HIP, "path sequence, frame %u, plane kernel launch: %s", (unsigned)i, hipGetErrorString((hipError_t)e));
         char *h_out = dev + off[8 + (i & 1u)], *h_prev = i ? dev + off[8 + ((i - 1) & 1u)] : nullptr;
         if (i) (void)temporal_camera(cams[i - 1], *t, k);
-        if (const int st = temporal_enqueue(ctx, tg, *t, &k, paths.indirect, h_prev, h_out, none, ctx->stream)) return st;
-        if (const int st = denoise_enqueue(ctx, dg, *d, reinterpret_cast<const float *>(h_out + px * 32), reinterpret_cast<float *>(dev + off[6]),
-                                           bytes[7] ? dev + off[7] : nullptr, ctx->stream))
+        if (const int st = temporal_enqueue(ctx, tg, *t, &k, paths.indirect, h_prev, h_out, tp, ctx->stream)) return st;
+        const float *acc = reinterpret_cast<const float *>(h_out + px * 32);
+        float *out = reinterpret_cast<float *>(dev + off[6]);
+        void *scratch = bytes[7] ? dev + off[7] : nullptr;
+        if (const int st = d ? denoise_enqueue(ctx, dg, *d, acc, out, scratch, ctx->stream)
+                             : denoise_variance_enqueue(ctx, dg, *dv, tp.variance, tp.age, acc, out, nullptr, scratch, ctx->stream))
             return st;
         HIP_TRY(ctx, hipMemcpyAsync(out_rgb + (size_t)i * px * 3, dev + off[6], bytes[6], hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return C2RT_OK;
+}
+
+int c2rt_render_paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
+                               const c2rt_temporal_opts *t, const c2rt_denoise_opts *d, float *out_rgb)
+{
+    if (const int st = check_paths_denoised(ctx, cams, opts, pg, d, out_rgb)) return st;
+    return paths_sequence(ctx, cams, n_frames, opts, pg, t, d, nullptr, out_rgb);
+}
+
+int c2rt_render_paths_sequence_variance(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
+                                        const c2rt_path_opts *pg, const c2rt_temporal_opts *t, const c2rt_denoise_variance_opts *dv, float *out_rgb)
+{
+    if (const int st = check_paths_filtered(ctx, cams, opts, pg, dv != nullptr, dv ? dv->width : 0, dv ? dv->height : 0, dv ? dv->channels : 0, out_rgb))
+        return st;
+    if (const int st = check_denoise_variance_opts(ctx, dv)) return st;
+    return paths_sequence(ctx, cams, n_frames, opts, pg, t, nullptr, dv, out_rgb);
 }
 
 /* ---- hit layers: every surface along a ray or pixel (c2rt_layers.hip) --------------------------------------------- */

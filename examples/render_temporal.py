@@ -4,7 +4,8 @@ draws its own noise (seed + i); without history the speckle of the indirect ligh
 every pixel's world point is projected into the previous camera, the accumulated value is fetched where the surface is
 the same one, and the new sample is folded into a running mean (Context.temporalAccumulate) before the a-trous filter
 runs.  The script writes <stem>_NN_raw.bmp (the filter alone) and <stem>_NN_temporal.bmp (accumulation, then the filter)
-for every frame and prints, per frame, how many pixels found their history and the speckle of the indirect light — the mean
+for every frame — with --variance also <stem>_NN_variance.bmp, the accumulated plane through the variance-guided filter
+(Context.denoiseVariance, fed by the accumulation's variance and age planes) — and prints, per frame, how many pixels found their history and the speckle of the indirect light — the mean
 difference between neighbouring hit pixels — before and after the accumulation.
 
   python examples/render_temporal.py tests/golden/scenes/lecture5.sdl /tmp/orbit --size 640 480 --frames 8 --paths 4
@@ -45,6 +46,9 @@ def main():
     ap.add_argument("--max-plane-dist", type=float, default=0.1)
     ap.add_argument("--levels", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--variance", action="store_true", help="also write <stem>_NN_variance.bmp: the variance-guided filter of the accumulated plane")
+    ap.add_argument("--sigma-lum", type=float, default=4.0, help="--variance: luminance differences count in local standard deviations times this")
+    ap.add_argument("--min-age", type=int, default=4, help="--variance: pixels younger than this take a spatial variance estimate")
     args = ap.parse_args()
     scene = c2.parseSceneFromFile(args.scene)
     scene.setFrameSize(*args.size)
@@ -64,6 +68,9 @@ def main():
                                               min_normal_dot=args.min_normal_dot, max_plane_dist=args.max_plane_dist)
         frames = {"raw": ctx.denoise(hits, indirect, levels=args.levels, albedo=albedo, base=hits["rgb"]),
                   "temporal": ctx.denoise(hits, acc["colour"], levels=args.levels, albedo=albedo, base=hits["rgb"])}
+        if args.variance:
+            frames["variance"] = ctx.denoiseVariance(hits, acc["colour"], acc["variance"], acc["age"], levels=args.levels, sigma_lum=args.sigma_lum,
+                                                     min_age=args.min_age, albedo=albedo, base=hits["rgb"], variance_out=False)[0]
         hit = hits["node"] >= 0
         found = int((acc["age"] > 1).sum())
         print("frame %2d: %5.1f %% of the hit pixels found their history, mean age %.1f; neighbour-to-neighbour difference of the indirect light %.4f -> %.4f"
@@ -74,7 +81,7 @@ def main():
         prev_cam = cam
         scene.moveCamera(args.step[0], 0.0, 0.0)
         scene.rotateCamera(-args.step[1], 0.0, 0.0)
-    print("wrote %d frames twice under %s_*" % (args.frames, args.stem))
+    print("wrote %d frames %s under %s_*" % (args.frames, "three times" if args.variance else "twice", args.stem))
 
 
 if __name__ == "__main__":

@@ -1243,6 +1243,129 @@ int c2rt_temporal_accumulate(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, c
 int c2rt_render_paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
                                const c2rt_path_opts *g, const c2rt_temporal_opts *t, const c2rt_denoise_opts *d, float *out_rgb);
 
+/* ---- variance-guided denoise: the a-trous filter steered by the temporal stage's variance and age planes ---- */
+
+/* Largest min_age; C2RT_ERR_LIMIT beyond (the boost min_age / age of a young pixel's spatial estimate stays a small number). */
+#define C2RT_MAX_VARIANCE_MIN_AGE 64
+
+typedef struct c2rt_denoise_variance_opts {   /* 40 bytes */
+    uint32_t width, height;        /* the WHOLE frame: no strips */
+    uint32_t levels;               /* 0 .. C2RT_MAX_DENOISE_LEVELS; 0: the variance estimate and the two closing steps alone */
+    uint32_t channels;             /* 1 | 3 */
+    uint32_t normal_power_log2;    /* 0 .. 7, as c2rt_denoise_opts */
+    float    sigma_plane;          /* finite, > 0, as c2rt_denoise_opts */
+    float    sigma_lum;            /* finite, >= 0: luminance differences are measured in local standard deviations times this; 0: no luminance term */
+    float    var_floor;            /* finite, > 0: added to the scaled variance, so that a pixel without variance still divides */
+    uint32_t min_age;              /* 0 .. C2RT_MAX_VARIANCE_MIN_AGE: pixels younger than this get the spatial estimate; 0: none */
+    uint32_t reserved;             /* 0 */
+} c2rt_denoise_variance_opts;
+
+/* c2rt_denoise with the colour term replaced by a LUMINANCE term whose scale is the pixel's own standard deviation: the
+ * caller no longer tunes sigma_colour to a noise level that differs from pixel to pixel, the temporal stage's `variance`
+ * plane says what it is.  The variance is filtered alongside the colour (it is what the next level's term reads), and a
+ * pixel too young for a temporal variance (age < min_age) gets a spatial one from its 7x7 neighbourhood.  The guides are
+ * c2rt_denoise_guides, unchanged.  Beside them:
+ *   variance      [H][W]            float   required   the temporal planes' `variance`
+ *   age           [H][W]            uint32  nullable   the temporal planes' `age`; null, or min_age == 0: no spatial estimate
+ *   in            [H][W][channels]  float   required
+ *   out           [H][W][channels]  float   required
+ *   variance_out  [H][W]            float   nullable   the variance after the last level
+ *
+ * The arithmetic is the contract, in c2rt_denoise's idiom — fp32, no libm call, no exp, no sqrt, no contraction, IEEE
+ * divide, subnormals kept, the order of every sum fixed — and tests/denoise_variance_reference.py restates it in numpy to
+ * the bit.  nf, pf, K, inv_plane, dn, wn, wp and the node test are exactly c2rt_denoise's (above).
+ *
+ *   lum(x) = (0.2126f*x.r + 0.7152f*x.g) + 0.0722f*x.b        (one channel: lum(x) = x; the temporal stage's coefficients)
+ *   per call:  sl2 = sigma_lum * sigma_lum
+ *
+ *   Stage A, the variance estimate V0, pixel q = (x, y):
+ *     node[q] < 0:                                          V0[q] = +0f
+ *     age == NULL, or min_age == 0, or age[q] >= min_age:   V0[q] = variance[q] (the bits)
+ *     else (the spatial estimate, over 7x7 ADJACENT pixels of `in`):
+ *       sumw = s1 = s2 = +0f
+ *       for j in -3..3: for i in -3..3:                     -- this ORDER of the fp32 sums is the contract
+ *         t = (x + i, y + j); outside the frame: skip
+ *         (i, j) == (0, 0): w = 1f                          -- the centre always counts
+ *         else: node[t] != node[q]: skip;  dn as the filter's, !(dn > 0): skip;  wn, wp as the filter's
+ *               w = wn * wp;  !(w > 0): skip
+ *         l = lum(in[t]);  s1 = s1 + w*l;  s2 = s2 + w*(l*l);  sumw = sumw + w
+ *       m1 = s1 / sumw;  m2 = s2 / sumw;  v = m2 - m1*m1;  v = v > 0 ? v : +0f        -- a NaN becomes +0f
+ *       V0[q] = v * ((float)min_age / (float)max(age[q], 1u))
+ *
+ *   Stage B, level l, step s = 1 << l, planes (C, V) to (D, V'), pixel q:
+ *     node[q] < 0:  D[q] = C[q], V'[q] = V[q] (the bits)
+ *     else:
+ *       sigma_lum > 0:
+ *         G = {1/16, 1/8, 1/16;  1/8, 1/4, 1/8;  1/16, 1/8, 1/16};  gs = gw = +0f
+ *         for j in -1..1: for i in -1..1:  t = (x + i, y + j)       -- ADJACENT pixels whatever the step; no node test
+ *           inside the frame:  gs = gs + G[j][i]*V[t];  gw = gw + G[j][i]
+ *         g = gs / gw;  inv_l = 1f / (sl2 * g + var_floor);  lq = lum(C[q])
+ *       sumw = sv = +0f;  sum.c = +0f
+ *       the 25 taps in c2rt_denoise's order, with its skips and its w = ((K[i+2]*K[j+2]) * wn) * wp (no colour term); then
+ *         sigma_lum > 0 (not for the centre):  dl = lum(C[t]) - lq;  w = w * (1f / (1f + (dl*dl) * inv_l))
+ *         !(w > 0): skip
+ *         sum.c = sum.c + w*C[t].c;  sumw = sumw + w;  sv = sv + (w*w)*V[t]
+ *       (the centre always counts, w = K[2]*K[2], in all three sums)
+ *       D[q].c = sum.c / sumw;  V'[q] = sv / (sumw * sumw)
+ *
+ *   Levels 0 .. levels-1 run in order from (`in`, V0).  c2rt_denoise's two closing steps (albedo, base) are fused into the
+ *   last colour store, for every pixel; they do not touch the variance.  `variance_out` is V after the last level; with
+ *   levels == 0 it is V0, and `out` is the two closing steps alone.
+ *
+ *   - A NaN, negative or infinite `variance` reaches exactly the taps this arithmetic says: through g the pixels whose 3x3
+ *     holds it, through sv the pixels that keep it as a tap.
+ *   - A zero or NaN sl2*g + var_floor drops every tap but the centre (inv_l is infinite or NaN, every tap's w zero or NaN).
+ *     A NEGATIVE one — only a negative `variance` makes it — gives x = (dl*dl) * inv_l < 0: a tap with x > -1 keeps a
+ *     factor above 1, x == -1 exactly makes it 1f / +0f = +inf (kept, and sumw infinite), x < -1 makes it negative and the
+ *     tap is dropped.  The arithmetic is followed to the bit either way; a caller who wants sense clamps the variance.
+ *   - variance_out is the variance a sum of INDEPENDENT samples would have.  After level 0 the taps are correlated, and it
+ *     underestimates what is left (on a flat plane of unit-variance noise, 4 levels: 1e-6 against a measured 2.5e-5).  It is
+ *     a relative guide for the next level's term, not an error bar.
+ *
+ * c2rt_denoise_variance_scratch_bytes: pure host arithmetic, no context; 0 for options c2rt_denoise_variance_device would
+ * refuse.  Otherwise width * height * ((levels > 0 || min_age > 0 ? 32 : 0) + (levels > 1 ? 4 * channels : 0) +
+ * (levels > 0 ? 8 : 0) + (levels > 1 ? 4 : 0)): c2rt_denoise's packed guides (the levels read them, and so does the spatial
+ * estimate), its colour ping-pong plane, and behind them the variance planes: V0 and g, the 3x3-blurred variance of the
+ * level about to run, and for levels > 1 a second V to alternate with.  At most 56 B per pixel.  `scratch_dev` must be
+ * 16-byte aligned.
+ *
+ * c2rt_denoise_variance_device takes c2rt_denoise_device's stream rules (no host sync, no event, nothing kept of the
+ * stream, no uploaded scene, the lead device of a multi-device context) and writes only `out_dev`, `variance_out_dev` and
+ * `scratch_dev`.  It enqueues levels + 2 kernels for levels >= 1 (the packing, stage A, one per level) and with
+ * sigma_lum > 0 one more per level (the 3x3 blur of V ahead of it): 2 levels + 2.  For levels == 0 it enqueues the closing
+ * steps' one and ahead of it, only where variance_out is given, stage A and (with `age` and min_age > 0) the packing: 1 to 3.
+ *
+ * Statuses, all decided before anything is enqueued or written, each with its own message, in this order.
+ * C2RT_ERR_INVALID_ARG: null context; null `o`; null `guides`; width or height 0; channels not 1 or 3; sigma_plane NaN,
+ * infinite or <= 0; sigma_lum NaN, infinite or < 0; var_floor NaN, infinite or <= 0; reserved != 0.  C2RT_ERR_LIMIT:
+ * levels > C2RT_MAX_DENOISE_LEVELS; normal_power_log2 > 7; min_age > C2RT_MAX_VARIANCE_MIN_AGE.  C2RT_ERR_INVALID_ARG
+ * again: null `node`, `normal` or `p`; null `variance`; null `in`; null `out`; out == in; variance_out == variance;
+ * out == scratch; variance_out == scratch (both for a non-null scratch); null scratch where
+ * c2rt_denoise_variance_scratch_bytes is not 0; a scratch that is not 16-byte aligned; in == scratch; variance == scratch
+ * (both for a non-null scratch: the packing launch would overwrite the input). */
+size_t c2rt_denoise_variance_scratch_bytes(const c2rt_denoise_variance_opts *o);
+int c2rt_denoise_variance_device(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_dev, const c2rt_denoise_variance_opts *o,
+                                 const float *variance_dev, const uint32_t *age_dev, const float *in_dev, float *out_dev,
+                                 float *variance_out_dev, void *scratch_dev, void *hip_stream);
+/* The same from and into HOST memory, the scratch the library's own: guides, `variance`, `age`, `in`, both outputs and the
+ * scratch go through the context's grow-only staging buffer on the context's own stream, whole (at most 168 B per pixel;
+ * nothing is allocated once the buffer is large enough); blocks until `out` and `variance_out` are there.  The same
+ * statuses without the scratch's. */
+int c2rt_denoise_variance(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_host, const c2rt_denoise_variance_opts *o,
+                          const float *variance, const uint32_t *age, const float *in, float *out, float *variance_out);
+
+/* c2rt_render_paths_sequence with the loop closed: the temporal stage also writes its `variance` and `age` planes, and the
+ * filter is c2rt_denoise_variance, fed by them (no variance_out).  out_rgb[n_frames][H][W][3] is bit for bit what a caller
+ * composes from c2rt_render_hits, c2rt_render_shading, c2rt_render_paths, c2rt_temporal_accumulate and
+ * c2rt_denoise_variance.  The two histories live in the staging buffer beside the frame's planes (268 B per pixel in all,
+ * whatever n_frames; allocated once, before the first launch); blocks until the last frame is there.  Statuses:
+ * c2rt_render_paths_sequence's, in its order, with `dv` in place of `d` ("null denoise options", dv->width / dv->height
+ * other than the frame's, dv->channels != 3, then c2rt_denoise_variance's own for the options).  Strips and multi-device
+ * sharding are refused as there. */
+int c2rt_render_paths_sequence_variance(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
+                                        const c2rt_path_opts *g, const c2rt_temporal_opts *t, const c2rt_denoise_variance_opts *dv,
+                                        float *out_rgb);
+
 /* ---- adaptive anti-aliasing: refine only the pixels the edge test flags ----- */
 
 /* tooDifferent's default threshold — rt/color.d:18 */

@@ -314,6 +314,31 @@ extern (C) nothrow @nogc
                                  const c2rt_temporal_planes* planes_host);
     int c2rt_render_paths_sequence(c2rt_ctx*, const c2rt_camera_frame* cams, uint n_frames, const c2rt_render_opts*,
                                    const c2rt_path_opts*, const c2rt_temporal_opts*, const c2rt_denoise_opts*, float* out_rgb);
+    /// variance-guided denoise: the a-trous filter with a luminance term scaled by the pixel's own standard deviation (the
+    /// temporal planes' variance, filtered along; a spatial 7x7 estimate for pixels younger than min_age); fp32 arithmetic
+    /// fixed by include/c2rt.h
+    enum C2RT_MAX_VARIANCE_MIN_AGE = 64;
+    struct c2rt_denoise_variance_opts
+    {
+        uint width, height;         /// the whole frame
+        uint levels;                /// 0 .. C2RT_MAX_DENOISE_LEVELS
+        uint channels;              /// 1 | 3
+        uint normal_power_log2;     /// 0 .. 7
+        float sigma_plane;          /// finite, > 0
+        float sigma_lum;            /// finite, >= 0; 0: no luminance term
+        float var_floor;            /// finite, > 0
+        uint min_age;               /// 0 .. C2RT_MAX_VARIANCE_MIN_AGE; 0: no spatial estimate
+        uint reserved;              /// 0
+    }
+    size_t c2rt_denoise_variance_scratch_bytes(const c2rt_denoise_variance_opts*);
+    int c2rt_denoise_variance_device(c2rt_ctx*, const c2rt_denoise_guides* guides_dev, const c2rt_denoise_variance_opts*,
+                                     const float* variance_dev, const uint* age_dev, const float* in_dev, float* out_dev,
+                                     float* variance_out_dev, void* scratch_dev, void* hip_stream);
+    int c2rt_denoise_variance(c2rt_ctx*, const c2rt_denoise_guides* guides_host, const c2rt_denoise_variance_opts*,
+                              const float* variance, const uint* age, const float* in_, float* out_, float* variance_out);
+    int c2rt_render_paths_sequence_variance(c2rt_ctx*, const c2rt_camera_frame* cams, uint n_frames, const c2rt_render_opts*,
+                                            const c2rt_path_opts*, const c2rt_temporal_opts*, const c2rt_denoise_variance_opts*,
+                                            float* out_rgb);
     enum float C2RT_AA_THRESHOLD_REF = 0.1f; /// tooDifferent's default
     int c2rt_render_frame_adaptive_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
                                           float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
