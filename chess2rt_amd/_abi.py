@@ -29,6 +29,7 @@ MAX_SAMPLE_TAPS = 16
 MAX_DENOISE_LEVELS = 8
 MAX_VARIANCE_MIN_AGE = 64
 MAX_TEMPORAL_AGE = 65535
+MAX_MOTION_NODES = 16
 AA_THRESHOLD_REF = 0.1     # C2RT_AA_THRESHOLD_REF (0.1f: passed as a C float)
 
 _i32p = C.POINTER(C.c_int32)
@@ -316,6 +317,19 @@ class TemporalPlanes(C.Structure):
     ]
 
 
+class TemporalMotion(C.Structure):
+    """c2rt_temporal_motion: the nodes that moved between the history's frame and the current one (at most
+    MAX_MOTION_NODES), each with the pose the history was made under and the pose of the current guides ([n_nodes][30]
+    doubles, the layout of SceneDesc.node_transform); host memory"""
+    _fields_ = [
+        ("n_nodes", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("node_index", _u32p),
+        ("prev_transform", _f64p),
+        ("cur_transform", _f64p),
+    ]
+
+
 class ScenePose(C.Structure):
     """c2rt_scene_pose: new transforms ([n_nodes][30] doubles) and light values for some nodes / lights of the uploaded scene"""
     _fields_ = [
@@ -436,6 +450,14 @@ C2RT_SYMBOLS = {
     "c2rt_temporal_accumulate_device": (C.c_int, [_VP, _CAM_P, C.POINTER(TemporalGuides), C.POINTER(TemporalOpts), _VP, _VP, _VP, C.POINTER(TemporalPlanes), _VP]),
     "c2rt_temporal_accumulate": (C.c_int, [_VP, _CAM_P, C.POINTER(TemporalGuides), C.POINTER(TemporalOpts), _VP, _VP, _VP, C.POINTER(TemporalPlanes)]),
     "c2rt_render_paths_sequence": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.POINTER(PathOpts), C.POINTER(TemporalOpts), C.POINTER(DenoiseOpts), _VP]),
+    "c2rt_temporal_accumulate_motion_device": (C.c_int, [_VP, _CAM_P, C.POINTER(TemporalGuides), C.POINTER(TemporalOpts), C.POINTER(TemporalMotion), _VP, _VP,
+                                                         _VP, C.POINTER(TemporalPlanes), _VP]),
+    "c2rt_temporal_accumulate_motion": (C.c_int, [_VP, _CAM_P, C.POINTER(TemporalGuides), C.POINTER(TemporalOpts), C.POINTER(TemporalMotion), _VP, _VP, _VP,
+                                                  C.POINTER(TemporalPlanes)]),
+    "c2rt_render_paths_sequence_posed": (C.c_int, [_VP, _CAM_P, _POSE_P, C.c_uint32, _OPTS_P, C.POINTER(PathOpts), C.POINTER(TemporalOpts),
+                                                   C.POINTER(DenoiseOpts), _VP]),
+    "c2rt_render_paths_sequence_posed_variance": (C.c_int, [_VP, _CAM_P, _POSE_P, C.c_uint32, _OPTS_P, C.POINTER(PathOpts), C.POINTER(TemporalOpts),
+                                                            C.POINTER(DenoiseVarianceOpts), _VP]),
     "c2rt_denoise_variance_scratch_bytes": (C.c_size_t, [C.POINTER(DenoiseVarianceOpts)]),
     "c2rt_denoise_variance_device": (C.c_int, [_VP, C.POINTER(DenoiseGuides), C.POINTER(DenoiseVarianceOpts), _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "c2rt_denoise_variance": (C.c_int, [_VP, C.POINTER(DenoiseGuides), C.POINTER(DenoiseVarianceOpts), _VP, _VP, _VP, _VP, _VP]),

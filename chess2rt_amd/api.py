@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _abi
 from ._abi import (CameraFrame, DenoiseGuides, DenoiseOpts, DenoiseVarianceOpts, GatherOpts, GatherPlanes, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
-                   ScenePose, Segment, ShadePlanes, TapTable, TemporalGuides, TemporalOpts, TemporalPlanes, TraceResult)
+                   ScenePose, Segment, ShadePlanes, TapTable, TemporalGuides, TemporalMotion, TemporalOpts, TemporalPlanes, TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
 RAY_HIT_DTYPE = np.dtype({
@@ -180,6 +180,26 @@ def temporal_history_bytes(width, height, channels=3, max_age=TEMPORAL_MAX_AGE, 
     width * height * (32 + 4 * channels + 8); 0 for options the library would refuse."""
     o = _temporal_opts(width, height, channels, max_age, min_normal_dot, max_plane_dist)
     return int(_abi.load_library().c2rt_temporal_history_bytes(C.byref(o)))
+
+
+def makeMotion(motion):
+    """c2rt_temporal_motion from ``motion = {node index: (prev, cur)}``: for every node that moved, the transform the
+    history was made under and the transform of the current guides (30 doubles each, as for makePose).  A TemporalMotion
+    passes through.  Entries keep the order of the dict.  The arrays live as long as the TemporalMotion returned."""
+    if isinstance(motion, TemporalMotion):
+        return motion
+    motion = dict(motion)
+    m = TemporalMotion()
+    if motion:
+        idx = np.array(list(motion), dtype=np.uint32)
+        prev = np.ascontiguousarray([np.asarray(v[0], dtype=np.float64).reshape(30) for v in motion.values()])
+        cur = np.ascontiguousarray([np.asarray(v[1], dtype=np.float64).reshape(30) for v in motion.values()])
+        m.n_nodes = len(idx)
+        m.node_index = idx.ctypes.data_as(_abi._u32p)
+        m.prev_transform = prev.ctypes.data_as(_abi._f64p)
+        m.cur_transform = cur.ctypes.data_as(_abi._f64p)
+        m._keep = [idx, prev, cur]
+    return m
 
 
 def makePose(nodes=None, lights=None):
@@ -957,8 +977,11 @@ class Context:
         return out
 
     def temporalAccumulate(self, guides, image, prev_cam=None, history=None, max_age=TEMPORAL_MAX_AGE, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT,
-                           max_plane_dist=TEMPORAL_MAX_PLANE_DIST, planes=("colour", "variance", "age")):
-        """Temporal accumulation of a Monte-Carlo plane (c2rt_temporal_accumulate).  `guides`: a dict with the CURRENT
+                           max_plane_dist=TEMPORAL_MAX_PLANE_DIST, planes=("colour", "variance", "age"), motion=None):
+        """Temporal accumulation of a Monte-Carlo plane (c2rt_temporal_accumulate; with `motion`,
+        c2rt_temporal_accumulate_motion: ``{node index: (prev, cur)}``, see makeMotion — the pixels of those nodes are
+        carried from the current pose back into the history's before they are reprojected, so that a moved node finds
+        its history; an empty dict is the plain call's bits).  `guides`: a dict with the CURRENT
         frame's node (H, W), normal and p (H, W, 3), e.g. what renderHits returns for the whole frame; `image`: (H, W, 3)
         float32, or (H, W) / (H, W, 1) for one channel.  `history`: the bytes-like history the previous call returned and
         `prev_cam` that call's camera; both None for the first frame.  Every pixel's point is projected into `prev_cam`,
@@ -991,14 +1014,22 @@ class Context:
             out[n] = np.empty(image.shape if n == "colour" else (h, w), dtype=TEMPORAL_PLANES[n])
             setattr(pl, n, out[n].ctypes.data)
         new = np.empty(nbytes, dtype=np.uint8)
-        self._check(self._lib.c2rt_temporal_accumulate(self._h, None if prev_cam is None else C.byref(prev_cam), C.byref(g), C.byref(o),
-                                                       image.ctypes.data_as(C.c_void_p), None if prev is None else prev.ctypes.data_as(C.c_void_p),
-                                                       new.ctypes.data_as(C.c_void_p), C.byref(pl)))
+        cam = None if prev_cam is None else C.byref(prev_cam)
+        prev_p = None if prev is None else prev.ctypes.data_as(C.c_void_p)
+        if motion is None:
+            self._check(self._lib.c2rt_temporal_accumulate(self._h, cam, C.byref(g), C.byref(o), image.ctypes.data_as(C.c_void_p), prev_p,
+                                                           new.ctypes.data_as(C.c_void_p), C.byref(pl)))
+        else:
+            m = makeMotion(motion)
+            self._check(self._lib.c2rt_temporal_accumulate_motion(self._h, cam, C.byref(g), C.byref(o), C.byref(m), image.ctypes.data_as(C.c_void_p), prev_p,
+                                                                  new.ctypes.data_as(C.c_void_p), C.byref(pl)))
         return out, new
 
     def temporalAccumulateDevice(self, ptrs, width, height, in_ptr, history_prev_ptr, history_out_ptr, planes=None, prev_cam=None, channels=3,
-                                 max_age=TEMPORAL_MAX_AGE, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT, max_plane_dist=TEMPORAL_MAX_PLANE_DIST, stream=0):
-        """Enqueue the accumulation on `stream` over device memory (c2rt_temporal_accumulate_device): `ptrs` maps node,
+                                 max_age=TEMPORAL_MAX_AGE, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT, max_plane_dist=TEMPORAL_MAX_PLANE_DIST, stream=0,
+                                 motion=None):
+        """Enqueue the accumulation on `stream` over device memory (c2rt_temporal_accumulate_device; with `motion`, as for
+        temporalAccumulate, c2rt_temporal_accumulate_motion_device — the motion is host memory, read before the call returns): `ptrs` maps node,
         normal and p to device pointers of the current frame's planes, `planes` colour, variance and age to the outputs
         wanted (None: the history alone); the histories are temporal_history_bytes(...) bytes each, 16-byte aligned,
         history_prev_ptr 0 for the first frame.  One kernel, no sync; writes only history_out_ptr and `planes`."""
@@ -1013,9 +1044,16 @@ class Context:
                 raise ValueError("unknown temporal plane %r (one of %s)" % (n, ", ".join(TEMPORAL_PLANES)))
             setattr(pl, n, ptr or None)
         o = _temporal_opts(width, height, channels, max_age, min_normal_dot, max_plane_dist)
-        self._check(self._lib.c2rt_temporal_accumulate_device(self._h, None if prev_cam is None else C.byref(prev_cam), C.byref(g), C.byref(o),
-                                                              C.c_void_p(in_ptr or None), C.c_void_p(history_prev_ptr or None),
-                                                              C.c_void_p(history_out_ptr or None), C.byref(pl), C.c_void_p(stream)))
+        cam = None if prev_cam is None else C.byref(prev_cam)
+        if motion is None:
+            self._check(self._lib.c2rt_temporal_accumulate_device(self._h, cam, C.byref(g), C.byref(o), C.c_void_p(in_ptr or None),
+                                                                  C.c_void_p(history_prev_ptr or None), C.c_void_p(history_out_ptr or None), C.byref(pl),
+                                                                  C.c_void_p(stream)))
+        else:
+            m = makeMotion(motion)
+            self._check(self._lib.c2rt_temporal_accumulate_motion_device(self._h, cam, C.byref(g), C.byref(o), C.byref(m), C.c_void_p(in_ptr or None),
+                                                                         C.c_void_p(history_prev_ptr or None), C.c_void_p(history_out_ptr or None),
+                                                                         C.byref(pl), C.c_void_p(stream)))
 
     def renderPathsSequence(self, cams, opts, paths, bounces, seed=0, max_age=TEMPORAL_MAX_AGE, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT,
                             max_plane_dist=TEMPORAL_MAX_PLANE_DIST, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE, sigma_colour=0.0):
@@ -1031,6 +1069,35 @@ class Context:
         out = np.empty((len(cams), opts.height, opts.width, 3), dtype=np.float32)
         self._check(self._lib.c2rt_render_paths_sequence(self._h, arr, len(cams), C.byref(opts), C.byref(g), C.byref(t), C.byref(d),
                                                          out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def renderPathsSequencePosed(self, cams, poses, opts, paths, bounces, seed=0, max_age=TEMPORAL_MAX_AGE, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT,
+                                 max_plane_dist=TEMPORAL_MAX_PLANE_DIST, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE, sigma_colour=0.0):
+        """renderPathsSequence for a posed animation (c2rt_render_paths_sequence_posed): frame i is the current scene with
+        poses[i] applied — a ScenePose or a (nodes, lights) pair as for renderFramesPosed, each relative to the current
+        scene — seen through cams[i]; the accumulation follows the nodes that moved between two frames
+        (temporalAccumulate's `motion`).  The context's scene is unchanged.  (n, height, width, 3) float32, bit for bit
+        updateScene(poses[i]) + renderHits + renderShading + renderPaths + temporalAccumulate(motion=) + denoise."""
+        arr, parr, n, keep = self._posed_arrays(cams, poses)
+        g = _path_opts(paths, bounces, seed)
+        t = _temporal_opts(opts.width, opts.height, 3, max_age, min_normal_dot, max_plane_dist)
+        d = _denoise_opts(opts.width, opts.height, 3, levels, normal_power_log2, sigma_plane, sigma_colour)
+        out = np.empty((n, opts.height, opts.width, 3), dtype=np.float32)
+        self._check(self._lib.c2rt_render_paths_sequence_posed(self._h, arr, parr, n, C.byref(opts), C.byref(g), C.byref(t), C.byref(d),
+                                                               out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def renderPathsSequencePosedVariance(self, cams, poses, opts, paths, bounces, seed=0, max_age=TEMPORAL_MAX_AGE, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT,
+                                         max_plane_dist=TEMPORAL_MAX_PLANE_DIST, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE,
+                                         sigma_lum=DENOISE_SIGMA_LUM, var_floor=DENOISE_VAR_FLOOR, min_age=DENOISE_MIN_AGE):
+        """renderPathsSequencePosed with renderPathsSequenceVariance's filter (c2rt_render_paths_sequence_posed_variance)."""
+        arr, parr, n, keep = self._posed_arrays(cams, poses)
+        g = _path_opts(paths, bounces, seed)
+        t = _temporal_opts(opts.width, opts.height, 3, max_age, min_normal_dot, max_plane_dist)
+        d = _denoise_variance_opts(opts.width, opts.height, 3, levels, normal_power_log2, sigma_plane, sigma_lum, var_floor, min_age)
+        out = np.empty((n, opts.height, opts.width, 3), dtype=np.float32)
+        self._check(self._lib.c2rt_render_paths_sequence_posed_variance(self._h, arr, parr, n, C.byref(opts), C.byref(g), C.byref(t), C.byref(d),
+                                                                        out.ctypes.data_as(C.c_void_p)))
         return out
 
     def denoiseVariance(self, guides, image, variance, age=None, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE,

@@ -12,6 +12,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cstdint>
@@ -2033,10 +2034,50 @@ static int check_previous_camera(c2rt_ctx *ctx, const c2rt_camera_frame &prev, c
     return C2RT_OK;
 }
 
+/* the contract's "per moved node, on the host": record m of `tm` from the two poses of entry m, in fp64 */
+static void motion_record(uint32_t index, const double *prev, const double *cur, TemporalMotion &tm)
+{
+    const double *Tc = cur, *Ic = cur + 9, *oc = cur + 27, *Tp = prev, *TIp = prev + 18, *op = prev + 27;
+    double *w = tm.rec[tm.n];
+    tm.index[tm.n++] = index;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            w[3 * i + j] = (Ic[3 * i] * Tp[j] + Ic[3 * i + 1] * Tp[3 + j]) + Ic[3 * i + 2] * Tp[6 + j];
+            w[9 + 3 * i + j] = (Tc[i] * TIp[j] + Tc[3 + i] * TIp[3 + j]) + Tc[6 + i] * TIp[6 + j];
+        }
+    for (int c = 0; c < 3; ++c) {
+        w[18 + c] = oc[c];
+        w[21 + c] = op[c];
+    }
+}
+
+/* the refusals c2rt_temporal_accumulate_motion* add, in the documented order, and the records of a list that passes */
+static int check_temporal_motion(c2rt_ctx *ctx, const c2rt_temporal_motion *motion, TemporalMotion &tm)
+{
+    tm.n = 0;
+    if (!motion) return C2RT_OK;
+    if (motion->reserved != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "c2rt_temporal_motion.reserved is %u: must be 0", (unsigned)motion->reserved);
+    if (motion->n_nodes > (uint32_t)C2RT_MAX_MOTION_NODES)
+        return fail(ctx, C2RT_ERR_LIMIT, "%u moved nodes (at most %u)", (unsigned)motion->n_nodes, (unsigned)C2RT_MAX_MOTION_NODES);
+    if (motion->n_nodes == 0) return C2RT_OK;
+    if (!motion->node_index) return fail(ctx, C2RT_ERR_INVALID_ARG, "motion: %u nodes with a null node_index", (unsigned)motion->n_nodes);
+    if (!motion->prev_transform) return fail(ctx, C2RT_ERR_INVALID_ARG, "motion: %u nodes with a null prev_transform", (unsigned)motion->n_nodes);
+    if (!motion->cur_transform) return fail(ctx, C2RT_ERR_INVALID_ARG, "motion: %u nodes with a null cur_transform", (unsigned)motion->n_nodes);
+    for (uint32_t i = 1; i < motion->n_nodes; ++i)
+        for (uint32_t j = 0; j < i; ++j)
+            if (motion->node_index[i] == motion->node_index[j])
+                return fail(ctx, C2RT_ERR_INVALID_ARG, "motion: node_index[%u] = %u is listed twice", (unsigned)i, (unsigned)motion->node_index[i]);
+    for (uint32_t i = 0; i < motion->n_nodes; ++i)
+        motion_record(motion->node_index[i], motion->prev_transform + 30 * (size_t)i, motion->cur_transform + 30 * (size_t)i, tm);
+    return C2RT_OK;
+}
+
 /* every refusal of c2rt_temporal_accumulate_device, in the documented order; aligned false: the host variant, whose
- * histories are staged; `k`: the previous camera's constants where there is a history */
+ * histories are staged; `k`: the previous camera's constants where there is a history; `tm` (nullable: the static calls):
+ * the motion call's refusals behind "null planes", and its records */
 static int check_temporal(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *g, const c2rt_temporal_opts *o, const float *in,
-                          const void *history_prev, const void *history_out, const c2rt_temporal_planes *planes, bool aligned, TemporalCamera &k)
+                          const void *history_prev, const void *history_out, const c2rt_temporal_planes *planes, bool aligned, TemporalCamera &k,
+                          const c2rt_temporal_motion *motion = nullptr, TemporalMotion *tm = nullptr)
 {
     if (!ctx) return C2RT_ERR_INVALID_ARG;
     if (!o) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal options");
@@ -2048,6 +2089,8 @@ static int check_temporal(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, cons
     if (!in) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal input");
     if (!history_out) return fail(ctx, C2RT_ERR_INVALID_ARG, "null history out");
     if (!planes) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal planes");
+    if (tm)
+        if (const int st = check_temporal_motion(ctx, motion, *tm)) return st;
     if (history_prev && !prev_cam) return fail(ctx, C2RT_ERR_INVALID_ARG, "a previous history without its camera: null prev_cam");
     if (history_prev)
         if (const int st = check_previous_camera(ctx, *prev_cam, *o, k)) return st;
@@ -2059,9 +2102,10 @@ static int check_temporal(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, cons
 }
 
 static int temporal_enqueue(c2rt_ctx *ctx, const c2rt_temporal_guides &g, const c2rt_temporal_opts &o, const TemporalCamera *k, const float *in,
-                            const void *history_prev, void *history_out, const c2rt_temporal_planes &planes, void *stream)
+                            const void *history_prev, void *history_out, const c2rt_temporal_planes &planes, void *stream,
+                            const TemporalMotion *tm = nullptr)
 {
-    const int e = launch_temporal(g, o, history_prev ? k : nullptr, in, history_prev, history_out, planes, stream);
+    const int e = launch_temporal(g, o, history_prev ? k : nullptr, in, history_prev, history_out, planes, stream, tm);
     if (e != 0) return fail(ctx, C2RT_ERR_HIP, "temporal kernel launch: %s", hipGetErrorString((hipError_t)e));
     return C2RT_OK;
 }
@@ -2082,11 +2126,21 @@ int c2rt_temporal_accumulate_device(c2rt_ctx *ctx, const c2rt_camera_frame *prev
     return temporal_enqueue(ctx, *guides_dev, *o, &k, in_dev, history_prev_dev, history_out_dev, *planes_dev, hip_stream);
 }
 
-int c2rt_temporal_accumulate(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_host, const c2rt_temporal_opts *o,
-                             const float *in, const void *history_prev, void *history_out, const c2rt_temporal_planes *planes_host)
+int c2rt_temporal_accumulate_motion_device(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_dev,
+                                           const c2rt_temporal_opts *o, const c2rt_temporal_motion *motion, const float *in_dev,
+                                           const void *history_prev_dev, void *history_out_dev, const c2rt_temporal_planes *planes_dev, void *hip_stream)
 {
     TemporalCamera k = {};
-    if (const int st = check_temporal(ctx, prev_cam, guides_host, o, in, history_prev, history_out, planes_host, false, k)) return st;
+    TemporalMotion tm;
+    if (const int st = check_temporal(ctx, prev_cam, guides_dev, o, in_dev, history_prev_dev, history_out_dev, planes_dev, true, k, motion, &tm)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return temporal_enqueue(ctx, *guides_dev, *o, &k, in_dev, history_prev_dev, history_out_dev, *planes_dev, hip_stream, &tm);
+}
+
+/* the two host variants behind their checks: staged whole through the context's staging buffer (`tm` null: the static call) */
+static int temporal_to_host(c2rt_ctx *ctx, const TemporalCamera &k, const c2rt_temporal_guides *guides_host, const c2rt_temporal_opts *o,
+                            const float *in, const void *history_prev, void *history_out, const c2rt_temporal_planes *planes_host, const TemporalMotion *tm)
+{
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)o->width * o->height, colour = (size_t)o->channels * sizeof(float), hist = temporal_history_bytes(*o);
     /* [node | normal | p | in | history_prev | history_out | colour | variance | age], each 256-byte aligned */
@@ -2114,12 +2168,30 @@ int c2rt_temporal_accumulate(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, c
     planes.variance = bytes[7] ? reinterpret_cast<float *>(dev + off[7]) : nullptr;
     planes.age = bytes[8] ? reinterpret_cast<uint32_t *>(dev + off[8]) : nullptr;
     if (const int st = temporal_enqueue(ctx, g, *o, &k, reinterpret_cast<const float *>(dev + off[3]), bytes[4] ? dev + off[4] : nullptr, dev + off[5],
-                                        planes, ctx->stream))
+                                        planes, ctx->stream, tm))
         return st;
     for (int i = 5; i < 9; ++i)
         if (bytes[i]) HIP_TRY(ctx, hipMemcpyAsync(back[i], dev + off[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return C2RT_OK;
+}
+
+int c2rt_temporal_accumulate(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_host, const c2rt_temporal_opts *o,
+                             const float *in, const void *history_prev, void *history_out, const c2rt_temporal_planes *planes_host)
+{
+    TemporalCamera k = {};
+    if (const int st = check_temporal(ctx, prev_cam, guides_host, o, in, history_prev, history_out, planes_host, false, k)) return st;
+    return temporal_to_host(ctx, k, guides_host, o, in, history_prev, history_out, planes_host, nullptr);
+}
+
+int c2rt_temporal_accumulate_motion(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_host, const c2rt_temporal_opts *o,
+                                    const c2rt_temporal_motion *motion, const float *in, const void *history_prev, void *history_out,
+                                    const c2rt_temporal_planes *planes_host)
+{
+    TemporalCamera k = {};
+    TemporalMotion tm;
+    if (const int st = check_temporal(ctx, prev_cam, guides_host, o, in, history_prev, history_out, planes_host, false, k, motion, &tm)) return st;
+    return temporal_to_host(ctx, k, guides_host, o, in, history_prev, history_out, planes_host, &tm);
 }
 
 /* ---- variance-guided denoise: the filter steered by the temporal planes (c2rt_denoise_variance.hip) ---------------------- */
@@ -2233,9 +2305,109 @@ int c2rt_denoise_variance(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_host,
     return C2RT_OK;
 }
 
-/* the two sequence calls: `d` the plain filter's options or `dv` the variance-guided one's, the other null */
+/* The scene states of a posed sequence (c2rt_render_paths_sequence_posed*): the base's posable values, and for frame i
+ * the update that takes the context from frame i - 1's scene (the base's for i == 0) to the base patched by poses[i] —
+ * every node and light either pose names, with its value in frame i's scene — and the motion list of its accumulation. */
+struct PosedSequence {
+    std::vector<double> node_transform, light_pos; /* the base's */
+    std::vector<float> light_color, light_power;
+    std::vector<TemporalMotion> motion;            /* [n_frames]; motion[0] empty */
+
+    struct Step {
+        std::vector<uint32_t> node_index, light_index;
+        std::vector<double> node_transform, light_pos;
+        std::vector<float> light_color, light_power;
+        c2rt_scene_pose pose{};
+    };
+
+    /* `named` in ascending order without repeats: what either pose lists */
+    static std::vector<uint32_t> named(const uint32_t *a, uint32_t na, const uint32_t *b, uint32_t nb)
+    {
+        std::vector<uint32_t> v(a, a + na);
+        v.insert(v.end(), b, b + nb);
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+        return v;
+    }
+    static const double *transform_under(const c2rt_scene_pose *pose, uint32_t node, const std::vector<double> &base)
+    {
+        if (pose)
+            for (uint32_t k = 0; k < pose->n_nodes; ++k)
+                if (pose->node_index[k] == node) return pose->node_transform + 30 * (size_t)k;
+        return &base[30 * (size_t)node];
+    }
+
+    /* the update that names every node and light `from` or `to` names (either may be null) and gives each its value under
+     * `target` (null: the base's).  Frame i: (poses[i - 1], poses[i], poses[i]); the way back: (.., .., null). */
+    void step(const c2rt_scene_pose *from, const c2rt_scene_pose *to, const c2rt_scene_pose *target, Step &s) const
+    {
+        s.node_index = named(from ? from->node_index : nullptr, from ? from->n_nodes : 0, to ? to->node_index : nullptr, to ? to->n_nodes : 0);
+        s.light_index = named(from ? from->light_index : nullptr, from ? from->n_lights : 0, to ? to->light_index : nullptr, to ? to->n_lights : 0);
+        s.node_transform.resize(30 * s.node_index.size());
+        for (size_t k = 0; k < s.node_index.size(); ++k)
+            std::memcpy(&s.node_transform[30 * k], transform_under(target, s.node_index[k], node_transform), 30 * sizeof(double));
+        s.light_pos.resize(3 * s.light_index.size());
+        s.light_color.resize(3 * s.light_index.size());
+        s.light_power.resize(s.light_index.size());
+        for (size_t k = 0; k < s.light_index.size(); ++k) {
+            const size_t l = s.light_index[k];
+            std::memcpy(&s.light_pos[3 * k], &light_pos[3 * l], 3 * sizeof(double));
+            std::memcpy(&s.light_color[3 * k], &light_color[3 * l], 3 * sizeof(float));
+            s.light_power[k] = light_power[l];
+            for (uint32_t j = 0; target && j < target->n_lights; ++j) {
+                if (target->light_index[j] != l) continue;
+                if (target->light_pos) std::memcpy(&s.light_pos[3 * k], target->light_pos + 3 * (size_t)j, 3 * sizeof(double));
+                if (target->light_color) std::memcpy(&s.light_color[3 * k], target->light_color + 3 * (size_t)j, 3 * sizeof(float));
+                if (target->light_power) s.light_power[k] = target->light_power[j];
+            }
+        }
+        s.pose = c2rt_scene_pose{};
+        s.pose.n_nodes = (uint32_t)s.node_index.size();
+        s.pose.node_index = s.node_index.data();
+        s.pose.node_transform = s.node_transform.data();
+        s.pose.n_lights = (uint32_t)s.light_index.size();
+        s.pose.light_index = s.light_index.data();
+        s.pose.light_pos = s.light_pos.data();
+        s.pose.light_color = s.light_color.data();
+        s.pose.light_power = s.light_power.data();
+    }
+};
+
+/* The posed sequence's own refusals, behind the unposed call's, and its plan: the poses checked and planned
+ * (plan_posed_frames: what c2rt_update_scene would answer to each), the motion list of every frame. */
+static int plan_posed_sequence(c2rt_ctx *ctx, const c2rt_scene_pose *poses, uint32_t n_frames, PosedSequence &seq)
+{
+    if (const int st = check_posed_args(ctx, poses, n_frames)) return st;
+    {
+        std::vector<std::unique_ptr<PosedFrame>> posed;
+        if (const int st = plan_posed_frames(ctx, poses, n_frames, posed)) return st;
+    }
+    seq.node_transform = ctx->scene.node_transform;
+    seq.light_pos = ctx->scene.light_pos;
+    seq.light_color = ctx->scene.light_color;
+    seq.light_power = ctx->scene.light_power;
+    seq.motion.assign(n_frames, TemporalMotion{});
+    for (uint32_t i = 1; i < n_frames; ++i) {
+        const c2rt_scene_pose &a = poses[i - 1], &b = poses[i];
+        uint32_t listed = 0;
+        for (const uint32_t node : PosedSequence::named(a.node_index, a.n_nodes, b.node_index, b.n_nodes)) {
+            const double *prev = PosedSequence::transform_under(&a, node, seq.node_transform), *cur = PosedSequence::transform_under(&b, node, seq.node_transform);
+            if (std::memcmp(prev, cur, 30 * sizeof(double)) == 0) continue;
+            if (++listed > (uint32_t)C2RT_MAX_MOTION_NODES) continue;
+            motion_record(node, prev, cur, seq.motion[i]);
+        }
+        if (listed > (uint32_t)C2RT_MAX_MOTION_NODES)
+            return fail(ctx, C2RT_ERR_LIMIT, "frame %u: %u nodes moved since frame %u (at most %u)", (unsigned)i, (unsigned)listed, (unsigned)(i - 1),
+                        (unsigned)C2RT_MAX_MOTION_NODES);
+    }
+    return C2RT_OK;
+}
+
+/* the four sequence calls: `d` the plain filter's options or `dv` the variance-guided one's, the other null; `posed`: the
+ * posed calls, `poses` theirs */
 static int paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
-                          const c2rt_temporal_opts *t, const c2rt_denoise_opts *d, const c2rt_denoise_variance_opts *dv, float *out_rgb)
+                          const c2rt_temporal_opts *t, const c2rt_denoise_opts *d, const c2rt_denoise_variance_opts *dv, float *out_rgb,
+                          const c2rt_scene_pose *poses = nullptr, bool posed = false)
 {
     if (n_frames == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "n_frames is 0: a sequence has at least one frame");
     if (!t) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal options");
@@ -2252,6 +2424,9 @@ static int paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t
     }
     for (uint32_t i = 0; i + 1 < n_frames; ++i)
         if (const int st = check_previous_camera(ctx, cams[i], *t, k)) return st;
+    PosedSequence seq;
+    if (posed)
+        if (const int st = plan_posed_sequence(ctx, poses, n_frames, seq)) return st;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)opts->width * opts->height, hist = temporal_history_bytes(*t);
     /* [node | normal | p | rgb | albedo | indirect | out | scratch | history 0 | history 1 | variance | age], each 256-byte
@@ -2283,7 +2458,7 @@ static int paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t
         tp.variance = reinterpret_cast<float *>(dev + off[10]);
         tp.age = reinterpret_cast<uint32_t *>(dev + off[11]);
     }
-    for (uint32_t i = 0; i < n_frames; ++i) {
+    const auto frame = [&](uint32_t i) -> int {
         RenderParams p;
         hit_params(ctx, &cams[i], opts, p);
         c2rt_path_opts pgi = *pg;
@@ -2294,7 +2469,7 @@ static int paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t
         if (e != 0) return fail(ctx, C2RT_ERR_HIP, "path sequence, frame %u, plane kernel launch: %s", (unsigned)i, hipGetErrorString((hipError_t)e));
         char *h_out = dev + off[8 + (i & 1u)], *h_prev = i ? dev + off[8 + ((i - 1) & 1u)] : nullptr;
         if (i) (void)temporal_camera(cams[i - 1], *t, k);
-        if (const int st = temporal_enqueue(ctx, tg, *t, &k, paths.indirect, h_prev, h_out, tp, ctx->stream)) return st;
+        if (const int st = temporal_enqueue(ctx, tg, *t, &k, paths.indirect, h_prev, h_out, tp, ctx->stream, posed ? &seq.motion[i] : nullptr)) return st;
         const float *acc = reinterpret_cast<const float *>(h_out + px * 32);
         float *out = reinterpret_cast<float *>(dev + off[6]);
         void *scratch = bytes[7] ? dev + off[7] : nullptr;
@@ -2302,7 +2477,32 @@ static int paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t
                              : denoise_variance_enqueue(ctx, dg, *dv, tp.variance, tp.age, acc, out, nullptr, scratch, ctx->stream))
             return st;
         HIP_TRY(ctx, hipMemcpyAsync(out_rgb + (size_t)i * px * 3, dev + off[6], bytes[6], hipMemcpyDeviceToHost, ctx->stream));
+        return C2RT_OK;
+    };
+    if (!posed) {
+        for (uint32_t i = 0; i < n_frames; ++i)
+            if (const int st = frame(i)) return st;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return C2RT_OK;
     }
+    /* posed: the scene follows the frames on the same stream (c2rt_update_scene's own path, update_one) and is put back
+     * behind the last one — also behind a frame that failed, with that frame's status and message.  The way back names
+     * what the last two poses touched: whichever of them the context holds, wholly or in part, it holds the base after. */
+    PosedSequence::Step step;
+    int st = C2RT_OK;
+    const c2rt_scene_pose *before = nullptr, *last = nullptr;
+    for (uint32_t i = 0; i < n_frames && st == C2RT_OK; ++i) {
+        before = last;
+        last = &poses[i];
+        seq.step(before, last, last, step);
+        if ((st = update_one(ctx, &step.pose, ctx->stream)) == C2RT_OK) st = frame(i);
+    }
+    const std::string err = ctx->err;
+    seq.step(before, last, nullptr, step);
+    const int undo = update_one(ctx, &step.pose, ctx->stream);
+    if (st != C2RT_OK) ctx->err = err;
+    else st = undo;
+    if (st != C2RT_OK) return st;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return C2RT_OK;
 }
@@ -2321,6 +2521,24 @@ int c2rt_render_paths_sequence_variance(c2rt_ctx *ctx, const c2rt_camera_frame *
         return st;
     if (const int st = check_denoise_variance_opts(ctx, dv)) return st;
     return paths_sequence(ctx, cams, n_frames, opts, pg, t, nullptr, dv, out_rgb);
+}
+
+int c2rt_render_paths_sequence_posed(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, uint32_t n_frames,
+                                     const c2rt_render_opts *opts, const c2rt_path_opts *pg, const c2rt_temporal_opts *t, const c2rt_denoise_opts *d,
+                                     float *out_rgb)
+{
+    if (const int st = check_paths_denoised(ctx, cams, opts, pg, d, out_rgb)) return st;
+    return paths_sequence(ctx, cams, n_frames, opts, pg, t, d, nullptr, out_rgb, poses, true);
+}
+
+int c2rt_render_paths_sequence_posed_variance(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, uint32_t n_frames,
+                                              const c2rt_render_opts *opts, const c2rt_path_opts *pg, const c2rt_temporal_opts *t,
+                                              const c2rt_denoise_variance_opts *dv, float *out_rgb)
+{
+    if (const int st = check_paths_filtered(ctx, cams, opts, pg, dv != nullptr, dv ? dv->width : 0, dv ? dv->height : 0, dv ? dv->channels : 0, out_rgb))
+        return st;
+    if (const int st = check_denoise_variance_opts(ctx, dv)) return st;
+    return paths_sequence(ctx, cams, n_frames, opts, pg, t, nullptr, dv, out_rgb, poses, true);
 }
 
 /* ---- hit layers: every surface along a ray or pixel (c2rt_layers.hip) --------------------------------------------- */

@@ -25,10 +25,21 @@ struct TemporalCamera {
     uint32_t det_positive; /* det > 0 */
 };
 
+/* The moved nodes of c2rt_temporal_accumulate_motion, as the kernel takes them: the contract's "per moved node, on the
+ * host", composed in fp64 by c2rt_api.cpp and passed by value.  rec[m] = R[9] | N[9] | off_cur[3] | off_prev[3]. */
+constexpr int kMaxMotionNodes = C2RT_MAX_MOTION_NODES;
+struct TemporalMotion {
+    uint32_t n; /* 0 .. kMaxMotionNodes */
+    uint32_t index[kMaxMotionNodes];
+    double rec[kMaxMotionNodes][24];
+};
+
 /* The whole call on `stream`: ONE kernel.  `o` has passed c2rt_temporal_accumulate_device's checks; `cam` and
- * `history_prev` are both null (first frame: every hit pixel restarts) or both given. */
+ * `history_prev` are both null (first frame: every hit pixel restarts) or both given.  `motion` null, empty or without a
+ * history: the kernel of the static call. */
 int launch_temporal(const c2rt_temporal_guides &g, const c2rt_temporal_opts &o, const TemporalCamera *cam, const float *in,
-                    const void *history_prev, void *history_out, const c2rt_temporal_planes &planes, void *stream);
+                    const void *history_prev, void *history_out, const c2rt_temporal_planes &planes, void *stream,
+                    const TemporalMotion *motion = nullptr);
 
 } // namespace c2rt
 #endif

@@ -8,7 +8,13 @@ for every frame — with --variance also <stem>_NN_variance.bmp, the accumulated
 (Context.denoiseVariance, fed by the accumulation's variance and age planes) — and prints, per frame, how many pixels found their history and the speckle of the indirect light — the mean
 difference between neighbouring hit pixels — before and after the accumulation.
 
+--posed NODE DX DY DZ slides one node of the scene by (DX, DY, DZ) per frame (Context.updateScene) while the camera orbits
+— or stands still, with --step 0 0 — and hands the accumulation the node's two poses (temporalAccumulate's `motion`), so
+that the sliding piece keeps its history as the board under it does; the script then also prints how many of the piece's
+pixels found their history, against how many the plain call finds for the same frame.
+
   python examples/render_temporal.py tests/golden/scenes/lecture5.sdl /tmp/orbit --size 640 480 --frames 8 --paths 4
+  python examples/render_temporal.py tests/golden/scenes/lecture5.sdl /tmp/slide --posed 1 4 0 -3 --step 0 0
 """
 import argparse
 import os
@@ -49,6 +55,8 @@ def main():
     ap.add_argument("--variance", action="store_true", help="also write <stem>_NN_variance.bmp: the variance-guided filter of the accumulated plane")
     ap.add_argument("--sigma-lum", type=float, default=4.0, help="--variance: luminance differences count in local standard deviations times this")
     ap.add_argument("--min-age", type=int, default=4, help="--variance: pixels younger than this take a spatial variance estimate")
+    ap.add_argument("--posed", type=float, nargs=4, metavar=("NODE", "DX", "DY", "DZ"),
+                    help="slide node NODE by (DX, DY, DZ) per frame and let the accumulation follow it")
     args = ap.parse_args()
     scene = c2.parseSceneFromFile(args.scene)
     scene.setFrameSize(*args.size)
@@ -59,13 +67,29 @@ def main():
     ctx.uploadScene(scene.desc)
     opts = scene.renderOpts()
     prev_cam, history = None, None
+    node, pose, prev_pose = None, None, None
+    if args.posed:
+        node = int(args.posed[0])
+        desc = scene.desc.contents
+        if not 0 <= node < desc.n_nodes:
+            sys.exit("--posed: the scene has nodes 0 .. %d" % (desc.n_nodes - 1))
+        base = np.ctypeslib.as_array(desc.node_transform, shape=(desc.n_nodes, 30))[node].copy()
     for i in range(args.frames):
         cam = scene.beginFrame()
+        motion = None
+        if args.posed:
+            pose = base.copy()
+            pose[27:30] += i * np.array(args.posed[1:])          # the offset: Transform.translate
+            ctx.updateScene(nodes={node: pose})
+            motion = {node: (prev_pose, pose)} if i else {}
         hits = ctx.renderHits(cam, opts, planes=("node", "normal", "p", "rgb"))
         albedo = ctx.renderShading(cam, opts, planes=("albedo",))["albedo"]
         indirect = ctx.renderPaths(cam, opts, args.paths, depth, seed=args.seed + i, planes=("indirect",))["indirect"]
+        if args.posed and i:
+            plain = ctx.temporalAccumulate(hits, indirect, prev_cam=prev_cam, history=history, max_age=args.max_age, min_normal_dot=args.min_normal_dot,
+                                           max_plane_dist=args.max_plane_dist, planes=("age",))[0]["age"]
         acc, history = ctx.temporalAccumulate(hits, indirect, prev_cam=prev_cam, history=history, max_age=args.max_age,
-                                              min_normal_dot=args.min_normal_dot, max_plane_dist=args.max_plane_dist)
+                                              min_normal_dot=args.min_normal_dot, max_plane_dist=args.max_plane_dist, motion=motion)
         frames = {"raw": ctx.denoise(hits, indirect, levels=args.levels, albedo=albedo, base=hits["rgb"]),
                   "temporal": ctx.denoise(hits, acc["colour"], levels=args.levels, albedo=albedo, base=hits["rgb"])}
         if args.variance:
@@ -76,9 +100,13 @@ def main():
         print("frame %2d: %5.1f %% of the hit pixels found their history, mean age %.1f; neighbour-to-neighbour difference of the indirect light %.4f -> %.4f"
               % (i, 100.0 * found / max(int(hit.sum()), 1), float(acc["age"][hit].mean()) if hit.any() else 0.0, roughness(indirect, hit),
                  roughness(acc["colour"], hit)))
+        if args.posed and i:
+            on = hits["node"] == node
+            print("          node %d: %d pixels, %d found their history through its two poses, %d through the plain call"
+                  % (node, int(on.sum()), int((acc["age"][on] > 1).sum()), int((plain[on] > 1).sum())))
         for k, image in frames.items():
             write("%s_%02d_%s.bmp" % (args.stem, i, k), image)
-        prev_cam = cam
+        prev_cam, prev_pose = cam, pose
         scene.moveCamera(args.step[0], 0.0, 0.0)
         scene.rotateCamera(-args.step[1], 0.0, 0.0)
     print("wrote %d frames %s under %s_*" % (args.frames, "three times" if args.variance else "twice", args.stem))

@@ -1201,9 +1201,10 @@ typedef struct c2rt_temporal_planes {  /* 24 bytes: the outputs, each nullable *
  *     running mean of everything seen on the surface.
  *   - A NaN normal or a `p` beyond fp32 drops the taps it makes NaN; a NaN `in` reaches its own pixel now and, through
  *     the history, the pixels that fetch it later.
- *   - What is NOT promised: a node moved by c2rt_update_scene between two frames keeps its index and simply fails the
- *     plane test where it moved far enough — it restarts, nothing follows it.  Posed sequences are out of scope; so is
- *     any clamp of the history against the new frame's neighbourhood.
+ *   - What is NOT promised: a node moved by c2rt_update_scene between two frames keeps its index and, in THIS call,
+ *     simply fails the plane test where it moved far enough — it restarts, nothing follows it.  Following it is
+ *     c2rt_temporal_accumulate_motion's part, and posed sequences are c2rt_render_paths_sequence_posed*'s (below).  Out
+ *     of scope everywhere: any clamp of the history against the new frame's neighbourhood.
  *
  * c2rt_temporal_history_bytes: pure host arithmetic, no context; 0 for options c2rt_temporal_accumulate_device refuses.
  *
@@ -1229,6 +1230,75 @@ int c2rt_temporal_accumulate_device(c2rt_ctx *ctx, const c2rt_camera_frame *prev
 int c2rt_temporal_accumulate(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_host,
                              const c2rt_temporal_opts *o, const float *in, const void *history_prev, void *history_out,
                              const c2rt_temporal_planes *planes_host);
+
+/* ---- temporal accumulation that follows moved nodes ---- */
+
+/* Most moved nodes of one call; C2RT_ERR_LIMIT beyond. */
+#define C2RT_MAX_MOTION_NODES 16
+
+typedef struct c2rt_temporal_motion {  /* 32 bytes; host memory, read before the call returns */
+    uint32_t n_nodes;                  /* 0 .. C2RT_MAX_MOTION_NODES moved nodes */
+    uint32_t reserved;                 /* 0 */
+    const uint32_t *node_index;        /* [n_nodes], distinct; the values the `node` plane holds */
+    const double   *prev_transform;    /* [n_nodes][30], c2rt_scene_desc::node_transform layout: the pose the HISTORY was made under */
+    const double   *cur_transform;     /* [n_nodes][30]: the pose the current guides were rendered under */
+} c2rt_temporal_motion;
+
+/* c2rt_temporal_accumulate* for a scene whose nodes moved between the two frames (c2rt_update_scene, a posed sequence):
+ * a pixel that lies on a listed node is carried back through the node's motion — out of the current pose into the node's
+ * own space, from there into the previous pose — before it is projected into the previous camera, so that it finds the
+ * history the same piece of surface left, wherever the node was then.  History layout, c2rt_temporal_history_bytes, the
+ * planes and every pixel whose node is not listed are c2rt_temporal_accumulate's, to the bit; a history written by
+ * either call is read by the other.  `motion` NULL or n_nodes == 0: the call IS c2rt_temporal_accumulate* (the same
+ * kernel).  The stage still needs no uploaded scene, allocates nothing and enqueues ONE kernel; the motion records
+ * travel with the launch, as its arguments.
+ *
+ * The arithmetic is the contract, in the terms of c2rt_temporal_accumulate's (no libm call, no contraction, IEEE divides,
+ * subnormals kept); tests/temporal_motion_reference.py restates it in numpy to the bit.  Matrices are row-major 3x3,
+ * M[i][j] = m[3*i + j], and multiply a ROW vector from the right as the reference's mul(v, M) does (Transform.point,
+ * undoPoint, normal: rt/transform.d:57-81).  The library never inverts a matrix: it uses the caller's four parts.
+ *
+ *   per moved node m, on the host, in fp64, from cur = cur_transform[m] and prev = prev_transform[m]:
+ *     Tc = cur.transform;  Ic = cur.inverseTransform;  oc = cur.offset
+ *     Tp = prev.transform;  TIp = prev.transposedInverse;  op = prev.offset
+ *     R[i][j] = (Ic[i][0]*Tp[0][j] + Ic[i][1]*Tp[1][j]) + Ic[i][2]*Tp[2][j]       -- R = Ic . Tp: undoPoint of cur, then point of prev
+ *     N[i][j] = (Tc[0][i]*TIp[0][j] + Tc[1][i]*TIp[1][j]) + Tc[2][i]*TIp[2][j]     -- N = transpose(Tc) . TIp: the normal likewise
+ *
+ *   pixel q whose node[q] is not listed:  c2rt_temporal_accumulate's arithmetic and bits.
+ *   pixel q with node[q] == node_index[m], in fp64:
+ *     e.c  = p[q].c - oc.c
+ *     p'.j = ((e.x*R[0][j] + e.y*R[1][j]) + e.z*R[2][j]) + op.j
+ *     n'.j = (normal[q].x*N[0][j] + normal[q].y*N[1][j]) + normal[q].z*N[2][j]
+ *     r.c = p'.c - prev.pos.c, and the chain of c2rt_temporal_accumulate from there on: ka, kb, kc, s, sx, sy, x0, y0, fx, fy
+ *     pf'.c = (float)p'.c;  nf'.c = (float)n'.c;  l2 = (nf'.x*nf'.x + nf'.y*nf'.y) + nf'.z*nf'.z           -- fp32 from here on
+ *     mn2 = min_normal_dot * min_normal_dot;  mp2 = max_plane_dist * max_plane_dist
+ *     a tap, behind the frame, weight and node tests (the history's node[t] != node[q]: skip, as there):
+ *       dn = (nf'.x*hn.x + nf'.y*hn.y) + nf'.z*hn.z;                !(dn > 0 && dn*dn > mn2 * l2): skip
+ *       d.c = hp.c - pf'.c;  dp = (nf'.x*d.x + nf'.y*d.y) + nf'.z*d.z;   !(dp*dp <= mp2 * l2): skip
+ *     the sums, the running mean, the moments and the planes as there.
+ *   the history out takes the CURRENT (nf, node), (pf, age) of every pixel, as there: n' and p' are never stored.
+ *
+ *   - n' is a unit vector only under a rigid motion, hence the squared tests with n's own length in them and no square
+ *     root; under a rigid motion they are the static call's tests up to rounding.
+ *   - A NaN or an infinity in a listed transform is not refused: it makes the chain of that node's pixels NaN, and they
+ *     take NO HISTORY (age 1); a zero matrix sends every pixel of the node to one point with l2 = 0, and the normal test
+ *     drops every tap.  No other pixel is touched by either.
+ *   - The history lags what it was made of: a light moved between the frames, or the shadow a moved node casts on a
+ *     node that did not move, changes `in` while the old mean is still fetched — the running mean follows at its own
+ *     pace.  A clamp of the history against the new frame is out of scope.
+ *
+ * Statuses: c2rt_temporal_accumulate_device's, in its order, and behind its "null `planes`": motion->reserved != 0:
+ * C2RT_ERR_INVALID_ARG; n_nodes > C2RT_MAX_MOTION_NODES: C2RT_ERR_LIMIT; n_nodes > 0 with a null node_index,
+ * prev_transform or cur_transform: C2RT_ERR_INVALID_ARG; an index listed twice: C2RT_ERR_INVALID_ARG (c2rt_last_error
+ * names the entry).  A motion without a history is fine and ignored.  The device variant keeps the stream rules of
+ * c2rt_temporal_accumulate_device, the host variant the staging of c2rt_temporal_accumulate. */
+int c2rt_temporal_accumulate_motion_device(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_dev,
+                                           const c2rt_temporal_opts *o, const c2rt_temporal_motion *motion, const float *in_dev,
+                                           const void *history_prev_dev, void *history_out_dev, const c2rt_temporal_planes *planes_dev,
+                                           void *hip_stream);
+int c2rt_temporal_accumulate_motion(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_host,
+                                    const c2rt_temporal_opts *o, const c2rt_temporal_motion *motion, const float *in,
+                                    const void *history_prev, void *history_out, const c2rt_temporal_planes *planes_host);
 
 /* A global-illumination SEQUENCE in one call: for each i, on the device, the hit planes of cams[i] (node, normal, p, rgb),
  * the shading planes' `albedo`, the path planes' `indirect` with seed g->seed + i, the accumulation of `indirect` (prev_cam
@@ -1365,6 +1435,28 @@ int c2rt_denoise_variance(c2rt_ctx *ctx, const c2rt_denoise_guides *guides_host,
 int c2rt_render_paths_sequence_variance(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
                                         const c2rt_path_opts *g, const c2rt_temporal_opts *t, const c2rt_denoise_variance_opts *dv,
                                         float *out_rgb);
+
+/* The two sequence calls for a POSED animation: frame i is the context's current scene with poses[i] applied — each pose
+ * relative to the current scene, as in c2rt_render_frames_posed — seen through cams[i]; the context's scene is unchanged
+ * when the call returns.  Per frame, on the context's stream: the pose update (c2rt_update_scene's own path: the base
+ * scene patched by poses[i], planned on the host, the changed tables copied in stream order, nothing allocated), the hit
+ * planes, albedo and `indirect` with seed g->seed + i, c2rt_temporal_accumulate_motion against frame i - 1's camera and
+ * history, and the filter; after the last frame the base pose is put back the same way.  Frame i's motion list (i >= 1):
+ * every node poses[i - 1] or poses[i] names, in ascending order of its index, prev = its transform under poses[i - 1] (the
+ * base's where poses[i - 1] does not name it), cur likewise under poses[i]; an entry whose 60 doubles are bytewise equal
+ * is dropped.  Lights may be posed: the history then lags the lighting (above).  out_rgb[i] is bit for bit what a caller
+ * composes from c2rt_update_scene (the base patched by poses[i]), c2rt_render_hits, c2rt_render_shading,
+ * c2rt_render_paths, c2rt_temporal_accumulate_motion and c2rt_denoise (c2rt_denoise_variance for the second call).
+ * Statuses, all decided before anything is enqueued or changed: those of the unposed call, in its order; null `poses`:
+ * C2RT_ERR_INVALID_ARG; those of c2rt_update_scene for every poses[i], with "frame i: " in front of the message; more than
+ * C2RT_MAX_MOTION_NODES entries in a frame's motion list: C2RT_ERR_LIMIT, naming the frame.  Strips and multi-device
+ * sharding are refused as there. */
+int c2rt_render_paths_sequence_posed(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, uint32_t n_frames,
+                                     const c2rt_render_opts *opts, const c2rt_path_opts *g, const c2rt_temporal_opts *t,
+                                     const c2rt_denoise_opts *d, float *out_rgb);
+int c2rt_render_paths_sequence_posed_variance(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses,
+                                              uint32_t n_frames, const c2rt_render_opts *opts, const c2rt_path_opts *g,
+                                              const c2rt_temporal_opts *t, const c2rt_denoise_variance_opts *dv, float *out_rgb);
 
 /* ---- adaptive anti-aliasing: refine only the pixels the edge test flags ----- */
 

@@ -339,6 +339,31 @@ extern (C) nothrow @nogc
     int c2rt_render_paths_sequence_variance(c2rt_ctx*, const c2rt_camera_frame* cams, uint n_frames, const c2rt_render_opts*,
                                             const c2rt_path_opts*, const c2rt_temporal_opts*, const c2rt_denoise_variance_opts*,
                                             float* out_rgb);
+    /// the accumulation that follows moved nodes: per listed node the pose the history was made under and the pose of the
+    /// current guides ([n][30] doubles, c2rt_scene_desc's node_transform layout); NULL or empty: c2rt_temporal_accumulate
+    enum C2RT_MAX_MOTION_NODES = 16;
+    struct c2rt_temporal_motion
+    {
+        uint n_nodes;               /// 0 .. C2RT_MAX_MOTION_NODES
+        uint reserved;              /// 0
+        const(uint)* node_index;    /// [n_nodes], distinct: the values the node plane holds
+        const(double)* prev_transform;
+        const(double)* cur_transform;
+    }
+    int c2rt_temporal_accumulate_motion_device(c2rt_ctx*, const c2rt_camera_frame* prev_cam, const c2rt_temporal_guides* guides_dev,
+                                               const c2rt_temporal_opts*, const c2rt_temporal_motion*, const float* in_dev,
+                                               const void* history_prev_dev, void* history_out_dev,
+                                               const c2rt_temporal_planes* planes_dev, void* hip_stream);
+    int c2rt_temporal_accumulate_motion(c2rt_ctx*, const c2rt_camera_frame* prev_cam, const c2rt_temporal_guides* guides_host,
+                                        const c2rt_temporal_opts*, const c2rt_temporal_motion*, const float* in_,
+                                        const void* history_prev, void* history_out, const c2rt_temporal_planes* planes_host);
+    /// the two sequence calls with a pose per frame, each relative to the context's scene, which is unchanged afterwards
+    int c2rt_render_paths_sequence_posed(c2rt_ctx*, const c2rt_camera_frame* cams, const c2rt_scene_pose* poses, uint n_frames,
+                                         const c2rt_render_opts*, const c2rt_path_opts*, const c2rt_temporal_opts*,
+                                         const c2rt_denoise_opts*, float* out_rgb);
+    int c2rt_render_paths_sequence_posed_variance(c2rt_ctx*, const c2rt_camera_frame* cams, const c2rt_scene_pose* poses,
+                                                  uint n_frames, const c2rt_render_opts*, const c2rt_path_opts*,
+                                                  const c2rt_temporal_opts*, const c2rt_denoise_variance_opts*, float* out_rgb);
     enum float C2RT_AA_THRESHOLD_REF = 0.1f; /// tooDifferent's default
     int c2rt_render_frame_adaptive_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
                                           float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
