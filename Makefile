@@ -46,6 +46,7 @@ KERNELFLAGS_u5 :=
 # c2rt_occlusion (hemisphere visibility of every hit, c2rt_render_occlusion / c2rt_trace_rays_occlusion),
 # c2rt_gather (one-bounce indirect light of every hit, c2rt_render_gather / c2rt_trace_rays_gather),
 # c2rt_paths (multi-bounce indirect light of every hit, c2rt_render_paths / c2rt_trace_rays_paths),
+# c2rt_paths_counted (the same with a path count per sample, c2rt_render_paths_counted / c2rt_trace_rays_paths_counted),
 # c2rt_adaptive (adaptive anti-aliasing, c2rt_render_frame_adaptive: detection and refinement),
 # c2rt_sample_taps (frames and adaptive refinement over a caller's tap table, c2rt_render_frame_taps); the
 # flags of the frame units were tuned on the frame kernels and have not been measured here
@@ -54,6 +55,7 @@ KERNELFLAGS_QUERY :=
 # headers; the arithmetic flags only, none of the code-generation flags above
 # c2rt_temporal (the temporal accumulation, c2rt_temporal_accumulate*): the same — a gather that traces nothing
 # c2rt_denoise_variance (the variance-guided filter, c2rt_denoise_variance*): the same
+# c2rt_path_counts (the count rule over the temporal history, c2rt_path_counts*): the same
 CXXFLAGS   := -O2 -std=c++17 -fPIC $(FPFLAGS) -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
 CSRC       := chess2rt_amd/csrc
 # development knob: `make VARIANT=name EXTRA_HIPFLAGS=... EXTRA_KERNEL_FLAGS=...` builds chess2rt_amd/libc2rt_name.so
@@ -63,8 +65,8 @@ BUILD      := build$(if $(VARIANT),_$(VARIANT))
 LIBNAME    := chess2rt_amd/libc2rt$(if $(VARIANT),_$(VARIANT)).so
 
 UNITS      := 0 1 2 3 4 5
-QUERIES    := c2rt_rays c2rt_hit_planes c2rt_layers c2rt_shade_planes c2rt_occlusion c2rt_gather c2rt_paths c2rt_adaptive c2rt_sample_taps
-KOBJS      := $(foreach u,$(UNITS),$(BUILD)/c2rt_kernels_u$(u).o) $(foreach q,$(QUERIES),$(BUILD)/$(q).o) $(BUILD)/c2rt_denoise.o $(BUILD)/c2rt_temporal.o $(BUILD)/c2rt_denoise_variance.o
+QUERIES    := c2rt_rays c2rt_hit_planes c2rt_layers c2rt_shade_planes c2rt_occlusion c2rt_gather c2rt_paths c2rt_paths_counted c2rt_adaptive c2rt_sample_taps
+KOBJS      := $(foreach u,$(UNITS),$(BUILD)/c2rt_kernels_u$(u).o) $(foreach q,$(QUERIES),$(BUILD)/$(q).o) $(BUILD)/c2rt_denoise.o $(BUILD)/c2rt_temporal.o $(BUILD)/c2rt_denoise_variance.o $(BUILD)/c2rt_path_counts.o
 HOBJS      := $(BUILD)/c2rt_api.o $(BUILD)/scene_plan.o $(BUILD)/dsc.o $(BUILD)/scene.o $(BUILD)/host_api.o
 
 # diagnostics build of the same library: c2rt_api.cpp with the environment hooks compiled in (-DC2RT_DIAG=1), linked
@@ -85,6 +87,7 @@ $(BUILD)/c2rt_kernels_u%.o: $(CSRC)/c2rt_kernels.hip $(TRACE_DEPS) | $(BUILD)
 
 $(foreach q,$(QUERIES),$(BUILD)/$(q).o): $(BUILD)/%.o: $(CSRC)/%.hip $(CSRC)/c2rt_query.inc $(CSRC)/c2rt_query.h $(TRACE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_QUERY) $(EXTRA_KERNEL_FLAGS) -c $< -o $@
+$(BUILD)/c2rt_paths_counted.o: $(CSRC)/c2rt_paths_counted.h $(CSRC)/c2rt_temporal.h
 
 $(BUILD)/c2rt_denoise.o: $(CSRC)/c2rt_denoise.hip $(CSRC)/c2rt_denoise.h include/c2rt.h Makefile | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_KERNEL_FLAGS) -c $< -o $@
@@ -92,10 +95,13 @@ $(BUILD)/c2rt_denoise.o: $(CSRC)/c2rt_denoise.hip $(CSRC)/c2rt_denoise.h include
 $(BUILD)/c2rt_temporal.o: $(CSRC)/c2rt_temporal.hip $(CSRC)/c2rt_temporal.h include/c2rt.h Makefile | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_KERNEL_FLAGS) -c $< -o $@
 
+$(BUILD)/c2rt_path_counts.o: $(CSRC)/c2rt_path_counts.hip $(CSRC)/c2rt_paths_counted.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_query.h $(CSRC)/c2rt_device.h include/c2rt.h Makefile | $(BUILD)
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_KERNEL_FLAGS) -c $< -o $@
+
 $(BUILD)/c2rt_denoise_variance.o: $(CSRC)/c2rt_denoise_variance.hip $(CSRC)/c2rt_denoise_variance.h $(CSRC)/c2rt_denoise.h include/c2rt.h Makefile | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(EXTRA_KERNEL_FLAGS) -c $< -o $@
 
-$(BUILD)/c2rt_api.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_denoise_variance.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
+$(BUILD)/c2rt_api.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_denoise_variance.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_paths_counted.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -c $< -o $@
 
 # the HIP-free planner (scene validation and packing, per-frame culling decisions)
@@ -108,7 +114,7 @@ $(BUILD)/%.o: $(CSRC)/host/%.cpp $(CSRC)/host/scene.hpp $(CSRC)/host/dsc.hpp inc
 $(LIBNAME): $(KOBJS) $(HOBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lpthread
 
-$(BUILD)/c2rt_api_diag.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_denoise_variance.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
+$(BUILD)/c2rt_api_diag.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_denoise_variance.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_paths_counted.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -DC2RT_DIAG=1 -c $< -o $@
 
 $(DIAGNAME): $(KOBJS) $(BUILD)/c2rt_api_diag.o $(filter-out $(BUILD)/c2rt_api.o,$(HOBJS))
@@ -121,7 +127,7 @@ $(DIAGNAME): $(KOBJS) $(BUILD)/c2rt_api_diag.o $(filter-out $(BUILD)/c2rt_api.o,
 $(BUILD)/c2rt_kernels_u1_stats.o: $(CSRC)/c2rt_kernels.hip $(TRACE_DEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) $(KERNELFLAGS) $(KERNELFLAGS_u1) $(EXTRA_KERNEL_FLAGS) -DC2RT_TILE_STATS=1 -DC2RT_UNIT=1 -c $< -o $@
 
-$(BUILD)/c2rt_api_stats.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_denoise_variance.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
+$(BUILD)/c2rt_api_stats.o: $(CSRC)/c2rt_api.cpp $(CSRC)/c2rt_denoise.h $(CSRC)/c2rt_denoise_variance.h $(CSRC)/c2rt_temporal.h $(CSRC)/c2rt_paths_counted.h $(CSRC)/c2rt_query.h $(CSRC)/scene_plan.h $(CSRC)/c2rt_device.h $(CSRC)/csg_void.h $(CSRC)/ground_certain.h include/c2rt.h | $(BUILD)
 	g++ $(CXXFLAGS) $(EXTRA_HIPFLAGS) -DC2RT_DIAG=1 -DC2RT_TILE_STATS=1 -c $< -o $@
 
 $(STATSNAME): $(filter-out $(BUILD)/c2rt_kernels_u1.o,$(KOBJS)) $(BUILD)/c2rt_kernels_u1_stats.o $(BUILD)/c2rt_api_stats.o $(filter-out $(BUILD)/c2rt_api.o,$(HOBJS))

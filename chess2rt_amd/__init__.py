@@ -5,9 +5,9 @@ the reference's Scene / Camera / Renderer API mirrored in C++
 (include/c2rt_host.h) and exposed here through ctypes.  No CPU fallback.
 """
 from . import _abi
-from ._abi import (CameraFrame, DenoiseGuides, DenoiseOpts, DenoiseVarianceOpts, GatherOpts, GatherPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc, ScenePose, Segment,
+from ._abi import (CameraFrame, DenoiseGuides, DenoiseOpts, DenoiseVarianceOpts, GatherOpts, GatherPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathCountOpts, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc, ScenePose, Segment,
                    ShadePlanes, TapTable, TemporalGuides, TemporalMotion, TemporalOpts, TemporalPlanes, TraceResult, TAPS_1, TAPS_4, TAPS_REF5)
-from .api import (GATHER_PLANES, OCCLUSION_PLANES, PATH_PLANES, RAY_HIT_DTYPE, SHADE_PLANES, TAPS_REF5_TABLE, TEMPORAL_PLANES, C2rtError, Context, Renderer, Scene, denoise_scratch_bytes, denoise_variance_scratch_bytes, loadBmpImage, makeMotion, makePose, parseSceneFromFile, renderPixel, saveBmp, tap_grid, temporal_history_bytes)
+from .api import (GATHER_PLANES, OCCLUSION_PLANES, PATH_PLANES, RAY_HIT_DTYPE, SHADE_PLANES, TAPS_REF5_TABLE, TEMPORAL_PLANES, C2rtError, Context, Renderer, Scene, denoise_scratch_bytes, denoise_variance_scratch_bytes, loadBmpImage, makeMotion, makePose, parseSceneFromFile, paths_counted_scratch_bytes, renderPixel, saveBmp, tap_grid, temporal_history_bytes)
 from .sharding import (StripPlan, deinterleave_strips_torch, exchange_strips_p2p, local_rows, plan_strips, render_frame_sharded)
 
 __all__ = [
@@ -16,7 +16,7 @@ __all__ = [
     "Ray", "Segment", "RayHit", "RAY_HIT_DTYPE", "ShadePlanes", "SHADE_PLANES",
     "OcclusionOpts", "OcclusionPlanes", "OCCLUSION_PLANES",
     "GatherOpts", "GatherPlanes", "GATHER_PLANES",
-    "PathOpts", "PathPlanes", "PATH_PLANES",
+    "PathOpts", "PathPlanes", "PATH_PLANES", "PathCountOpts", "paths_counted_scratch_bytes",
     "DenoiseGuides", "DenoiseOpts", "denoise_scratch_bytes", "DenoiseVarianceOpts", "denoise_variance_scratch_bytes",
     "TemporalGuides", "TemporalMotion", "TemporalOpts", "TemporalPlanes", "TEMPORAL_PLANES", "temporal_history_bytes", "makeMotion",
     "TAPS_1", "TAPS_4", "TAPS_REF5", "TapTable", "TAPS_REF5_TABLE", "tap_grid",

@@ -298,6 +298,20 @@ class TemporalOpts(C.Structure):
     ]
 
 
+class PathCountOpts(C.Structure):
+    """c2rt_path_count_opts: the range of the counts (1 .. 64), the count of a pixel without a history or younger than
+    min_age, the paths asked for per unit of per-path variance, and the count behind the history where no plane says"""
+    _fields_ = [
+        ("min_paths", C.c_uint32),
+        ("max_paths", C.c_uint32),
+        ("young_paths", C.c_uint32),
+        ("min_age", C.c_uint32),
+        ("paths_per_variance", C.c_float),
+        ("prev_paths", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 class TemporalGuides(C.Structure):
     """c2rt_temporal_guides: node, normal and p of the CURRENT frame's hit planes, all required; host or device memory,
     by entry point"""
@@ -463,6 +477,16 @@ C2RT_SYMBOLS = {
     "c2rt_denoise_variance": (C.c_int, [_VP, C.POINTER(DenoiseGuides), C.POINTER(DenoiseVarianceOpts), _VP, _VP, _VP, _VP, _VP]),
     "c2rt_render_paths_sequence_variance": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.POINTER(PathOpts), C.POINTER(TemporalOpts),
                                                       C.POINTER(DenoiseVarianceOpts), _VP]),
+    "c2rt_paths_counted_scratch_bytes": (C.c_size_t, [C.c_uint64]),
+    "c2rt_render_paths_counted_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(PathOpts), _VP, C.POINTER(PathPlanes), _VP, _VP]),
+    "c2rt_render_paths_counted": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.POINTER(PathOpts), _VP, C.POINTER(PathPlanes)]),
+    "c2rt_trace_rays_paths_counted_device": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(PathOpts), _VP, C.POINTER(PathPlanes), _VP, _VP]),
+    "c2rt_trace_rays_paths_counted": (C.c_int, [_VP, _VP, C.c_uint64, C.POINTER(PathOpts), _VP, C.POINTER(PathPlanes)]),
+    "c2rt_path_counts_device": (C.c_int, [_VP, _CAM_P, C.POINTER(TemporalGuides), C.POINTER(TemporalOpts), C.POINTER(PathCountOpts), _VP, _VP, _VP, _VP,
+                                          _VP, _VP]),
+    "c2rt_path_counts": (C.c_int, [_VP, _CAM_P, C.POINTER(TemporalGuides), C.POINTER(TemporalOpts), C.POINTER(PathCountOpts), _VP, _VP, _VP, _VP, _VP]),
+    "c2rt_render_paths_sequence_adaptive": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.POINTER(PathOpts), C.POINTER(TemporalOpts),
+                                                      C.POINTER(DenoiseVarianceOpts), C.POINTER(PathCountOpts), _VP]),
     "c2rt_render_frame_adaptive_device": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frame_adaptive": (C.c_int, [_VP, _CAM_P, _OPTS_P, C.c_float, _VP, _VP, _VP]),
     "c2rt_render_frames_adaptive_device": (C.c_int, [_VP, _CAM_P, C.c_uint32, _OPTS_P, C.c_float, _VP, _VP, _VP]),

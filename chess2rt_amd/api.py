@@ -13,7 +13,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import (CameraFrame, DenoiseGuides, DenoiseOpts, DenoiseVarianceOpts, GatherOpts, GatherPlanes, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
+from ._abi import (CameraFrame, DenoiseGuides, DenoiseOpts, DenoiseVarianceOpts, GatherOpts, GatherPlanes, HitPlanes, HostCamera, HostSettings, OcclusionOpts, OcclusionPlanes, PathCountOpts, PathOpts, PathPlanes, Ray, RayHit, RayStats, RenderOpts, SceneDesc,
                    ScenePose, Segment, ShadePlanes, TapTable, TemporalGuides, TemporalMotion, TemporalOpts, TemporalPlanes, TraceResult)
 
 # c2rt_ray_hit as a structured numpy dtype (the layout of _abi.RayHit / include/c2rt.h: 80 bytes)
@@ -167,6 +167,13 @@ TEMPORAL_MIN_NORMAL_DOT = 0.9
 TEMPORAL_MAX_PLANE_DIST = 0.1
 # c2rt_temporal_planes: plane name -> dtype ("colour" has the input's channels, the others one value per pixel)
 TEMPORAL_PLANES = {"colour": np.float32, "variance": np.float32, "age": np.uint32}
+# Context.pathCounts' defaults: 2 .. 64 paths, 16 where the history is missing or younger than 2 samples, and 2000 paths
+# per unit of per-path luminance variance
+PATH_COUNT_MIN = 2
+PATH_COUNT_MAX = 64
+PATH_COUNT_YOUNG = 16
+PATH_COUNT_MIN_AGE = 2
+PATH_COUNT_PER_VARIANCE = 2000.0
 
 
 def _temporal_opts(width, height, channels, max_age, min_normal_dot, max_plane_dist):
@@ -180,6 +187,24 @@ def temporal_history_bytes(width, height, channels=3, max_age=TEMPORAL_MAX_AGE, 
     width * height * (32 + 4 * channels + 8); 0 for options the library would refuse."""
     o = _temporal_opts(width, height, channels, max_age, min_normal_dot, max_plane_dist)
     return int(_abi.load_library().c2rt_temporal_history_bytes(C.byref(o)))
+
+
+def _path_count_opts(min_paths, max_paths, young_paths, min_age, paths_per_variance, prev_paths):
+    return PathCountOpts(min_paths=min_paths, max_paths=max_paths, young_paths=young_paths, min_age=min_age, paths_per_variance=paths_per_variance,
+                         prev_paths=prev_paths)
+
+
+def paths_counted_scratch_bytes(n_samples):
+    """Bytes of the count-order scratch of the counted path planes' device calls for `n_samples` samples
+    (c2rt_paths_counted_scratch_bytes: 512 + 4 * n_samples rounded up to 16; no context)"""
+    return int(_abi.load_library().c2rt_paths_counted_scratch_bytes(int(n_samples)))
+
+
+def _counts_array(counts, shape, what):
+    counts = np.ascontiguousarray(counts, dtype=np.uint8)
+    if counts.shape != tuple(shape):
+        raise ValueError("%s: counts of shape %r (expected %r)" % (what, counts.shape, tuple(shape)))
+    return counts
 
 
 def makeMotion(motion):
@@ -920,6 +945,100 @@ class Context:
         pl = _PATHS.device(ptrs)
         self._check(self._lib.c2rt_trace_rays_paths_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(g), C.byref(pl), C.c_void_p(stream)))
 
+    def renderPathsCounted(self, cam, opts, counts, paths, bounces, seed=0, planes=tuple(PATH_PLANES)):
+        """renderPaths with a path count per pixel (c2rt_render_paths_counted): `counts` (localRows, width) uint8; pixel i
+        is traced with c = min(counts[i], paths) paths and holds, bit for bit, what renderPaths writes for it with
+        paths = c; c == 0: node and the primary colour only, indirect = bounce = 0."""
+        g = _path_opts(paths, bounces, seed)
+        shape = (self.localRows(opts), opts.width)
+        counts = _counts_array(counts, shape, "renderPathsCounted")
+        pl, out = _PATHS.new(planes, shape)
+        self._check(self._lib.c2rt_render_paths_counted(self._h, C.byref(cam), C.byref(opts), C.byref(g), counts.ctypes.data_as(C.c_void_p), C.byref(pl)))
+        return out
+
+    def renderPathsCountedDevice(self, cam, opts, counts_ptr, paths, bounces, ptrs, seed=0, scratch_ptr=0, stream=0):
+        """Enqueue the counted path planes on `stream` into device memory: `counts_ptr` one byte per pixel, `ptrs` as for
+        renderPathsDevice.  scratch_ptr 0: natural order, one kernel; else paths_counted_scratch_bytes(localRows * width)
+        bytes, 16-byte aligned: count order (a counting sort of the pixels by their count ahead of the path kernel) —
+        the same bits."""
+        g = _path_opts(paths, bounces, seed)
+        pl = _PATHS.device(ptrs)
+        self._check(self._lib.c2rt_render_paths_counted_device(self._h, C.byref(cam), C.byref(opts), C.byref(g), C.c_void_p(counts_ptr or None), C.byref(pl),
+                                                               C.c_void_p(scratch_ptr or None), C.c_void_p(stream)))
+
+    def traceRaysPathsCounted(self, rays, counts, paths, bounces, seed=0, planes=tuple(PATH_PLANES)):
+        """traceRaysPaths with a path count per ray (c2rt_trace_rays_paths_counted): `counts` (n,) uint8."""
+        rays = _rays_array(rays)
+        g = _path_opts(paths, bounces, seed)
+        counts = _counts_array(counts, (rays.shape[0],), "traceRaysPathsCounted")
+        pl, out = _PATHS.new(planes, (rays.shape[0],))
+        self._check(self._lib.c2rt_trace_rays_paths_counted(self._h, rays.ctypes.data_as(C.c_void_p), rays.shape[0], C.byref(g),
+                                                            counts.ctypes.data_as(C.c_void_p), C.byref(pl)))
+        return out
+
+    def traceRaysPathsCountedDevice(self, rays_ptr, n, counts_ptr, paths, bounces, ptrs, seed=0, scratch_ptr=0, stream=0):
+        """Enqueue the counted query on `stream` over device memory: n c2rt_ray at rays_ptr, n bytes at counts_ptr, `ptrs`
+        and scratch_ptr (for n samples) as for renderPathsCountedDevice."""
+        g = _path_opts(paths, bounces, seed)
+        pl = _PATHS.device(ptrs)
+        self._check(self._lib.c2rt_trace_rays_paths_counted_device(self._h, C.c_void_p(rays_ptr or None), int(n), C.byref(g), C.c_void_p(counts_ptr or None),
+                                                                   C.byref(pl), C.c_void_p(scratch_ptr or None), C.c_void_p(stream)))
+
+    def pathCounts(self, guides, prev_cam=None, history=None, prev_counts=None, min_paths=PATH_COUNT_MIN, max_paths=PATH_COUNT_MAX,
+                   young_paths=PATH_COUNT_YOUNG, min_age=PATH_COUNT_MIN_AGE, paths_per_variance=PATH_COUNT_PER_VARIANCE, prev_paths=PATH_COUNT_YOUNG,
+                   channels=3, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT, max_plane_dist=TEMPORAL_MAX_PLANE_DIST, planes=("variance", "age")):
+        """The counts plane of renderPathsCounted for the frame whose hit planes are `guides`, from the PREVIOUS history
+        (c2rt_path_counts): every pixel's point is projected into `prev_cam` and the history's luminance moments, age and
+        — from `prev_counts` (H, W) uint8, or `prev_paths` everywhere — the count its last sample was traced with are
+        gathered as temporalAccumulate gathers them; counts = ceil(variance * previous count * paths_per_variance) within
+        min_paths .. max_paths, `young_paths` without a history or below `min_age`, 0 at a miss.  `channels`: the
+        history's.  Returns {"counts": (H, W) uint8, and of `planes`: "variance" float32, "age" uint32}."""
+        keep = [np.ascontiguousarray(guides["node"], dtype=np.int32), np.ascontiguousarray(guides["normal"], dtype=np.float64),
+                np.ascontiguousarray(guides["p"], dtype=np.float64)]
+        if keep[0].ndim != 2:
+            raise ValueError("pathCounts: guide node of shape %r (expected (H, W))" % (keep[0].shape,))
+        h, w = keep[0].shape
+        for a, shape, name in zip(keep, ((h, w), (h, w, 3), (h, w, 3)), ("node", "normal", "p")):
+            if a.shape != shape:
+                raise ValueError("pathCounts: guide %s of shape %r (expected %r)" % (name, a.shape, shape))
+        g = TemporalGuides(node=keep[0].ctypes.data, normal=keep[1].ctypes.data, p=keep[2].ctypes.data)
+        o = _temporal_opts(w, h, channels, 1, min_normal_dot, max_plane_dist)
+        pc = _path_count_opts(min_paths, max_paths, young_paths, min_age, paths_per_variance, prev_paths)
+        prev = None
+        if history is not None:
+            prev = np.ascontiguousarray(np.frombuffer(history, dtype=np.uint8))
+            if prev.size != w * h * (32 + 4 * channels + 8):
+                raise ValueError("pathCounts: history of %d bytes (expected %d)" % (prev.size, w * h * (32 + 4 * channels + 8)))
+        pcn = None if prev_counts is None else _counts_array(prev_counts, (h, w), "pathCounts")
+        out = {"counts": np.empty((h, w), dtype=np.uint8)}
+        for n in planes:
+            if n not in ("variance", "age"):
+                raise ValueError("unknown path count plane %r (one of variance, age)" % (n,))
+            out[n] = np.empty((h, w), dtype=TEMPORAL_PLANES[n])
+        ptr = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._check(self._lib.c2rt_path_counts(self._h, None if prev_cam is None else C.byref(prev_cam), C.byref(g), C.byref(o), C.byref(pc), ptr(prev),
+                                               ptr(pcn), ptr(out["counts"]), ptr(out.get("variance")), ptr(out.get("age"))))
+        return out
+
+    def pathCountsDevice(self, ptrs, width, height, history_prev_ptr, prev_counts_ptr, counts_ptr, variance_ptr=0, age_ptr=0, prev_cam=None,
+                         min_paths=PATH_COUNT_MIN, max_paths=PATH_COUNT_MAX, young_paths=PATH_COUNT_YOUNG, min_age=PATH_COUNT_MIN_AGE,
+                         paths_per_variance=PATH_COUNT_PER_VARIANCE, prev_paths=PATH_COUNT_YOUNG, channels=3, min_normal_dot=TEMPORAL_MIN_NORMAL_DOT,
+                         max_plane_dist=TEMPORAL_MAX_PLANE_DIST, stream=0):
+        """Enqueue the count rule on `stream` over device memory (c2rt_path_counts_device): `ptrs` maps node, normal and p
+        to the current frame's planes; history_prev_ptr (16-byte aligned; 0: the first frame) and prev_counts_ptr (0:
+        prev_paths everywhere) the previous frame's; width * height bytes at counts_ptr; variance_ptr and age_ptr 0 or
+        float32 / uint32 planes.  One kernel, no sync."""
+        g = TemporalGuides()
+        for n, ptr in dict(ptrs).items():
+            if n not in ("node", "normal", "p"):
+                raise ValueError("unknown temporal guide %r (one of node, normal, p)" % (n,))
+            setattr(g, n, ptr or None)
+        o = _temporal_opts(width, height, channels, 1, min_normal_dot, max_plane_dist)
+        pc = _path_count_opts(min_paths, max_paths, young_paths, min_age, paths_per_variance, prev_paths)
+        self._check(self._lib.c2rt_path_counts_device(self._h, None if prev_cam is None else C.byref(prev_cam), C.byref(g), C.byref(o), C.byref(pc),
+                                                      C.c_void_p(history_prev_ptr or None), C.c_void_p(prev_counts_ptr or None), C.c_void_p(counts_ptr or None),
+                                                      C.c_void_p(variance_ptr or None), C.c_void_p(age_ptr or None), C.c_void_p(stream)))
+
     def denoise(self, guides, image, levels=5, normal_power_log2=5, sigma_plane=DENOISE_SIGMA_PLANE, sigma_colour=0.0, albedo=None, base=None):
         """Edge-aware a-trous filter of a Monte-Carlo plane (c2rt_denoise).  `guides`: a dict with the hit planes' node
         (H, W), normal and p (H, W, 3), e.g. what renderHits returns for the WHOLE frame; `image`: (H, W, 3) float32, or
@@ -1167,6 +1286,25 @@ class Context:
         d = _denoise_variance_opts(opts.width, opts.height, 3, levels, normal_power_log2, sigma_plane, sigma_lum, var_floor, min_age)
         out = np.empty((len(cams), opts.height, opts.width, 3), dtype=np.float32)
         self._check(self._lib.c2rt_render_paths_sequence_variance(self._h, arr, len(cams), C.byref(opts), C.byref(g), C.byref(t), C.byref(d),
+                                                                  out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def renderPathsSequenceAdaptive(self, cams, opts, paths, bounces, seed=0, min_paths=PATH_COUNT_MIN, max_paths=None, young_paths=PATH_COUNT_YOUNG,
+                                    count_min_age=PATH_COUNT_MIN_AGE, paths_per_variance=PATH_COUNT_PER_VARIANCE, max_age=TEMPORAL_MAX_AGE,
+                                    min_normal_dot=TEMPORAL_MIN_NORMAL_DOT, max_plane_dist=TEMPORAL_MAX_PLANE_DIST, levels=5, normal_power_log2=5,
+                                    sigma_plane=DENOISE_SIGMA_PLANE, sigma_lum=DENOISE_SIGMA_LUM, var_floor=DENOISE_VAR_FLOOR, min_age=DENOISE_MIN_AGE):
+        """renderPathsSequenceVariance with the sampler in the loop (c2rt_render_paths_sequence_adaptive): frame 0 is
+        traced with `young_paths` everywhere, frame i > 0 with pathCounts of history i - 1, cams[i - 1] and the counts of
+        frame i - 1, through renderPathsCounted with `paths` as the cap (`max_paths` None: the cap); (n, height, width, 3)
+        float32, bit for bit that composition."""
+        cams = list(cams)
+        arr = (CameraFrame * max(len(cams), 1))(*cams)
+        g = _path_opts(paths, bounces, seed)
+        t = _temporal_opts(opts.width, opts.height, 3, max_age, min_normal_dot, max_plane_dist)
+        d = _denoise_variance_opts(opts.width, opts.height, 3, levels, normal_power_log2, sigma_plane, sigma_lum, var_floor, min_age)
+        pc = _path_count_opts(min_paths, paths if max_paths is None else max_paths, young_paths, count_min_age, paths_per_variance, young_paths)
+        out = np.empty((len(cams), opts.height, opts.width, 3), dtype=np.float32)
+        self._check(self._lib.c2rt_render_paths_sequence_adaptive(self._h, arr, len(cams), C.byref(opts), C.byref(g), C.byref(t), C.byref(d), C.byref(pc),
                                                                   out.ctypes.data_as(C.c_void_p)))
         return out
 

@@ -29,6 +29,7 @@
 #include "c2rt_denoise.h"
 #include "c2rt_denoise_variance.h"
 #include "c2rt_temporal.h"
+#include "c2rt_paths_counted.h"
 #include "scene_plan.h"
 
 using namespace c2rt;
@@ -1539,14 +1540,15 @@ static int copy_back(c2rt_ctx *ctx, const Staging &outs, size_t first, size_t m,
 
 /* The ray faces: n input records (c2rt_ray, c2rt_segment) in chunks of at most `cap`.  launch(p, records_dev, first, m,
  * chunk) enqueues the `what` kernel over m staged records, `first` the index in the caller's array of the first of them,
- * the layer stride of its outputs being `chunk`. */
+ * the layer stride of its outputs being `chunk`.  more_in, more_fixed: bytes per sample and per chunk of further inputs and
+ * scratch behind the chunk's records, which the launch places and stages itself (the counted path planes' counts and order). */
 template <class Launch>
-static int ray_chunks(c2rt_ctx *ctx, const void *in, uint64_t n, uint64_t cap, Staging &outs, const char *what, Launch launch)
+static int ray_chunks(c2rt_ctx *ctx, const void *in, uint64_t n, uint64_t cap, Staging &outs, const char *what, Launch launch, size_t more_in = 0, size_t more_fixed = 0)
 {
     static_assert(sizeof(c2rt_ray) == sizeof(c2rt_segment), "one input record size");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const uint64_t chunk = n < cap ? n : cap;
-    if (const int e = lay_out(ctx, outs, chunk * sizeof(c2rt_ray), chunk)) return e;
+    if (const int e = lay_out(ctx, outs, chunk * (sizeof(c2rt_ray) + more_in) + more_fixed, chunk)) return e;
     c2rt_ray *in_dev = reinterpret_cast<c2rt_ray *>(ctx->frame);
     RenderParams p;
     query_params(ctx, p);
@@ -1563,16 +1565,18 @@ static int ray_chunks(c2rt_ctx *ctx, const void *in, uint64_t n, uint64_t cap, S
 
 /* The frame faces: the local rows of the frame `p` describes in chunks of whole rows, at most kQueryChunk / layers
  * pixels each but one row at least (width <= 2^16: with one layer that is four rows or more).  launch(r0, m, chunk_px)
- * enqueues the `what` kernel over rows [r0, r0 + m) into the staging, whose layers are chunk_px pixels apart. */
+ * enqueues the `what` kernel over rows [r0, r0 + m) into the staging, whose layers are chunk_px pixels apart.  in_per_px,
+ * in_fixed: bytes per pixel and per chunk of inputs and scratch at the head of the buffer, which the launch places and stages
+ * itself (the counted path planes' counts and order). */
 template <class Launch>
-static int row_chunks(c2rt_ctx *ctx, const RenderParams &p, uint32_t layers, Staging &outs, const char *what, Launch launch)
+static int row_chunks(c2rt_ctx *ctx, const RenderParams &p, uint32_t layers, Staging &outs, const char *what, Launch launch, size_t in_per_px = 0, size_t in_fixed = 0)
 {
     const uint32_t rows = p.local_rows, width = p.width;
     uint32_t chunk_rows = (uint32_t)(kQueryChunk / layers / width);
     if (chunk_rows == 0) chunk_rows = 1;
     if (chunk_rows > rows) chunk_rows = rows;
     const size_t chunk_px = (size_t)chunk_rows * width;
-    if (const int e = lay_out(ctx, outs, 0, chunk_px)) return e;
+    if (const int e = lay_out(ctx, outs, in_per_px * chunk_px + in_fixed, chunk_px)) return e;
     for (uint32_t r0 = 0; r0 < rows; r0 += chunk_rows) {
         const uint32_t m = rows - r0 < chunk_rows ? rows - r0 : chunk_rows;
         const int e = launch(r0, m, chunk_px);
@@ -1816,6 +1820,90 @@ int c2rt_trace_rays_paths(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const
     return ray_planes_host(ctx, rays, n, g, planes_host);
 }
 
+/* ---- counted path planes: the path planes with a count per sample (c2rt_paths_counted.hip) ---------------------------- */
+
+/* what the counted calls refuse behind the path call's own, in the documented order; aligned: the _device variants */
+static int check_counts(c2rt_ctx *ctx, const uint8_t *counts, const void *scratch, bool aligned)
+{
+    if (!counts) return fail(ctx, C2RT_ERR_INVALID_ARG, "null counts");
+    if (aligned && reinterpret_cast<uintptr_t>(scratch) % 16 != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "the count-order scratch is not 16-byte aligned");
+    return C2RT_OK;
+}
+
+size_t c2rt_paths_counted_scratch_bytes(uint64_t n_samples) { return counted_scratch_bytes(n_samples); }
+
+int c2rt_render_paths_counted_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_path_opts *g,
+                                     const uint8_t *counts_dev, const c2rt_path_planes *planes_dev, void *scratch_dev, void *hip_stream)
+{
+    if (const int st = check_frame_planes(ctx, cam, opts, g, planes_dev)) return st;
+    if (const int st = check_counts(ctx, counts_dev, scratch_dev, true)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    if (p.local_rows == 0) return C2RT_OK;
+    const int e = launch_counted_rows(p, ctx->plan.csg_levels, *g, counts_dev, *planes_dev, 0, p.local_rows, scratch_dev, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "counted path plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+/* Host variants: the path planes' chunks with the chunk's counts staged beside them — at the head of the buffer for a
+ * frame, behind the rays for a ray call — and behind the counts the scratch of count order, which every chunk runs in: it
+ * took 0.43 to 0.76 of natural order's time on the three uneven planes measured and 1.07 on an even one
+ * (profiles/paths_counted.md).  [counts: chunk bytes | to the next multiple of 16 | counted_scratch_bytes(chunk)] */
+constexpr size_t kCountedPerSample = 1 + 4, kCountedFixed = kCountedHeadBytes + 32;
+static void *counted_scratch(uint8_t *counts_dev, size_t chunk)
+{
+    return reinterpret_cast<void *>((reinterpret_cast<uintptr_t>(counts_dev) + chunk + 15u) & ~(uintptr_t)15u);
+}
+static_assert(15 + kCountedHeadBytes + 15 <= kCountedFixed, "the padding in front of the scratch and the rounding of its order fit what a chunk reserves");
+
+int c2rt_render_paths_counted(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts, const c2rt_path_opts *g, const uint8_t *counts,
+                              const c2rt_path_planes *planes_host)
+{
+    if (const int st = check_frame_planes(ctx, cam, opts, g, planes_host)) return st;
+    if (const int st = check_counts(ctx, counts, nullptr, false)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    hit_params(ctx, cam, opts, p);
+    if (p.local_rows == 0) return C2RT_OK;
+    Staging outs;
+    outs.add_planes(*planes_host);
+    return row_chunks(ctx, p, 1, outs, "counted path plane", [&](uint32_t r0, uint32_t m, size_t chunk_px) {
+        uint8_t *counts_dev = reinterpret_cast<uint8_t *>(ctx->frame);
+        if (const hipError_t e = hipMemcpyAsync(counts_dev, counts + (size_t)r0 * p.width, (size_t)m * p.width, hipMemcpyHostToDevice, ctx->stream)) return (int)e;
+        return launch_counted_rows(p, ctx->plan.csg_levels, *g, counts_dev, outs.planes<c2rt_path_planes>(), r0, m, counted_scratch(counts_dev, chunk_px), ctx->stream);
+    }, kCountedPerSample, kCountedFixed);
+}
+
+int c2rt_trace_rays_paths_counted_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n, const c2rt_path_opts *g, const uint8_t *counts_dev,
+                                         const c2rt_path_planes *planes_dev, void *scratch_dev, void *hip_stream)
+{
+    if (const int st = check_query_args(ctx, rays_dev, n, true)) return st < 0 ? C2RT_OK : st;
+    if (const int st = check_planes(ctx, g, planes_dev)) return st;
+    if (const int st = check_counts(ctx, counts_dev, scratch_dev, true)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RenderParams p;
+    query_params(ctx, p);
+    const int e = launch_counted_rays(p, ctx->plan.csg_levels, rays_dev, n, 0, *g, counts_dev, *planes_dev, scratch_dev, hip_stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "counted path plane kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+int c2rt_trace_rays_paths_counted(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n, const c2rt_path_opts *g, const uint8_t *counts,
+                                  const c2rt_path_planes *planes_host)
+{
+    if (const int st = check_query_args(ctx, rays, n, true)) return st < 0 ? C2RT_OK : st;
+    if (const int st = check_planes(ctx, g, planes_host)) return st;
+    if (const int st = check_counts(ctx, counts, nullptr, false)) return st;
+    Staging outs;
+    outs.add_planes(*planes_host);
+    return ray_chunks(ctx, rays, n, kQueryChunk, outs, "counted path plane", [&](const RenderParams &p, const c2rt_ray *rays_dev, uint64_t first, uint64_t m, uint64_t chunk) {
+        uint8_t *counts_dev = reinterpret_cast<uint8_t *>(ctx->frame) + chunk * sizeof(c2rt_ray);
+        if (const hipError_t e = hipMemcpyAsync(counts_dev, counts + first, m, hipMemcpyHostToDevice, ctx->stream)) return (int)e;
+        return launch_counted_rays(p, ctx->plan.csg_levels, rays_dev, m, first, *g, counts_dev, outs.planes<c2rt_path_planes>(), counted_scratch(counts_dev, chunk), ctx->stream);
+    }, kCountedPerSample, kCountedFixed);
+}
+
 /* ---- denoise: the a-trous filter over full-frame planes (c2rt_denoise.hip) ------------------------------------------- */
 
 /* the options' own refusals, in the documented order (`ctx` null: the status alone) */
@@ -1986,8 +2074,9 @@ int c2rt_render_paths_denoised(c2rt_ctx *ctx, const c2rt_camera_frame *cam, cons
 
 /* ---- temporal accumulation: reprojection of the previous frame's history (c2rt_temporal.hip) -------------------------- */
 
-/* the options' own refusals, in the documented order (`ctx` null: the status alone) */
-static int check_temporal_opts(c2rt_ctx *ctx, const c2rt_temporal_opts *o)
+/* the options' own refusals, in the documented order (`ctx` null: the status alone); check_temporal_frame_opts: all but
+ * max_age's, for the calls that do not accumulate (c2rt_path_counts*) */
+static int check_temporal_frame_opts(c2rt_ctx *ctx, const c2rt_temporal_opts *o)
 {
     if (!o->width || !o->height) return fail(ctx, C2RT_ERR_INVALID_ARG, "temporal frame of %u x %u pixels: both must be above 0", (unsigned)o->width, (unsigned)o->height);
     if (o->channels != 1 && o->channels != 3) return fail(ctx, C2RT_ERR_INVALID_ARG, "temporal channels is %u: 1 or 3", (unsigned)o->channels);
@@ -1997,6 +2086,12 @@ static int check_temporal_opts(c2rt_ctx *ctx, const c2rt_temporal_opts *o)
         return fail(ctx, C2RT_ERR_INVALID_ARG, "max_plane_dist %g: a finite length above 0", (double)o->max_plane_dist);
     if (o->reserved[0] != 0 || o->reserved[1] != 0)
         return fail(ctx, C2RT_ERR_INVALID_ARG, "c2rt_temporal_opts.reserved is %u, %u: must be 0", (unsigned)o->reserved[0], (unsigned)o->reserved[1]);
+    return C2RT_OK;
+}
+
+static int check_temporal_opts(c2rt_ctx *ctx, const c2rt_temporal_opts *o)
+{
+    if (const int st = check_temporal_frame_opts(ctx, o)) return st;
     if (o->max_age == 0 || o->max_age > (uint32_t)C2RT_MAX_TEMPORAL_AGE)
         return fail(ctx, C2RT_ERR_LIMIT, "max_age is %u (1 .. %u)", (unsigned)o->max_age, (unsigned)C2RT_MAX_TEMPORAL_AGE);
     return C2RT_OK;
@@ -2192,6 +2287,102 @@ int c2rt_temporal_accumulate_motion(c2rt_ctx *ctx, const c2rt_camera_frame *prev
     TemporalMotion tm;
     if (const int st = check_temporal(ctx, prev_cam, guides_host, o, in, history_prev, history_out, planes_host, false, k, motion, &tm)) return st;
     return temporal_to_host(ctx, k, guides_host, o, in, history_prev, history_out, planes_host, &tm);
+}
+
+/* ---- path counts: the count rule over the previous history (c2rt_path_counts.hip) --------------------------------------- */
+
+/* the count options' own refusals, in the documented order */
+static int check_path_count_opts(c2rt_ctx *ctx, const c2rt_path_count_opts *pc)
+{
+    const unsigned most = C2RT_MAX_PATHS;
+    if (pc->min_paths == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "min_paths is 0: a pixel traced with no path folds a zero into the temporal mean");
+    if (pc->min_paths > most) return fail(ctx, C2RT_ERR_LIMIT, "min_paths is %u (at most %u)", (unsigned)pc->min_paths, most);
+    if (pc->max_paths < pc->min_paths) return fail(ctx, C2RT_ERR_INVALID_ARG, "max_paths is %u: below min_paths %u", (unsigned)pc->max_paths, (unsigned)pc->min_paths);
+    if (pc->max_paths > most) return fail(ctx, C2RT_ERR_LIMIT, "max_paths is %u (at most %u)", (unsigned)pc->max_paths, most);
+    if (pc->young_paths == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "young_paths is 0: at least one path");
+    if (pc->young_paths > most) return fail(ctx, C2RT_ERR_LIMIT, "young_paths is %u (at most %u)", (unsigned)pc->young_paths, most);
+    if (pc->min_age > (uint32_t)C2RT_MAX_TEMPORAL_AGE) return fail(ctx, C2RT_ERR_LIMIT, "min_age is %u (at most %u)", (unsigned)pc->min_age, (unsigned)C2RT_MAX_TEMPORAL_AGE);
+    if (pc->prev_paths == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "prev_paths is 0: at least one path");
+    if (pc->prev_paths > most) return fail(ctx, C2RT_ERR_LIMIT, "prev_paths is %u (at most %u)", (unsigned)pc->prev_paths, most);
+    if (!std::isfinite(pc->paths_per_variance) || !(pc->paths_per_variance > 0))
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "paths_per_variance %g: finite and above 0", (double)pc->paths_per_variance);
+    if (pc->reserved[0] != 0 || pc->reserved[1] != 0)
+        return fail(ctx, C2RT_ERR_INVALID_ARG, "c2rt_path_count_opts.reserved is %u, %u: must be 0", (unsigned)pc->reserved[0], (unsigned)pc->reserved[1]);
+    return C2RT_OK;
+}
+
+/* every refusal of c2rt_path_counts_device, in the documented order; aligned false: the host variant */
+static int check_path_counts(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *g, const c2rt_temporal_opts *o,
+                             const c2rt_path_count_opts *pc, const void *history_prev, const uint8_t *counts, bool aligned, TemporalCamera &k)
+{
+    if (!ctx) return C2RT_ERR_INVALID_ARG;
+    if (!o) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal options");
+    if (!g) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal guides");
+    if (const int st = check_temporal_frame_opts(ctx, o)) return st;
+    if (!pc) return fail(ctx, C2RT_ERR_INVALID_ARG, "null path count options");
+    if (const int st = check_path_count_opts(ctx, pc)) return st;
+    if (!g->node) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: node");
+    if (!g->normal) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: normal");
+    if (!g->p) return fail(ctx, C2RT_ERR_INVALID_ARG, "null guide: p");
+    if (!counts) return fail(ctx, C2RT_ERR_INVALID_ARG, "null counts");
+    if (history_prev && !prev_cam) return fail(ctx, C2RT_ERR_INVALID_ARG, "a previous history without its camera: null prev_cam");
+    if (history_prev)
+        if (const int st = check_previous_camera(ctx, *prev_cam, *o, k)) return st;
+    if (aligned && reinterpret_cast<uintptr_t>(history_prev) % 16 != 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "a history is not 16-byte aligned");
+    return C2RT_OK;
+}
+
+static int path_counts_enqueue(c2rt_ctx *ctx, const c2rt_temporal_guides &g, const c2rt_temporal_opts &o, const c2rt_path_count_opts &pc,
+                               const TemporalCamera *k, const void *history_prev, const uint8_t *prev_counts, uint8_t *counts, float *variance,
+                               uint32_t *age, void *stream)
+{
+    const int e = launch_path_counts(g, o, pc, history_prev ? k : nullptr, history_prev, prev_counts, counts, variance, age, stream);
+    if (e != 0) return fail(ctx, C2RT_ERR_HIP, "path count kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return C2RT_OK;
+}
+
+int c2rt_path_counts_device(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_dev, const c2rt_temporal_opts *o,
+                            const c2rt_path_count_opts *pc, const void *history_prev_dev, const uint8_t *prev_counts_dev, uint8_t *counts_dev,
+                            float *variance_dev, uint32_t *age_dev, void *hip_stream)
+{
+    TemporalCamera k = {};
+    if (const int st = check_path_counts(ctx, prev_cam, guides_dev, o, pc, history_prev_dev, counts_dev, true, k)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return path_counts_enqueue(ctx, *guides_dev, *o, *pc, &k, history_prev_dev, prev_counts_dev, counts_dev, variance_dev, age_dev, hip_stream);
+}
+
+int c2rt_path_counts(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_host, const c2rt_temporal_opts *o,
+                     const c2rt_path_count_opts *pc, const void *history_prev, const uint8_t *prev_counts, uint8_t *counts, float *variance, uint32_t *age)
+{
+    TemporalCamera k = {};
+    if (const int st = check_path_counts(ctx, prev_cam, guides_host, o, pc, history_prev, counts, false, k)) return st;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t px = (size_t)o->width * o->height;
+    /* [node | normal | p | history_prev | prev_counts | counts | variance | age], each 256-byte aligned, whole */
+    const void *host[5] = {guides_host->node, guides_host->normal, guides_host->p, history_prev, history_prev ? prev_counts : nullptr};
+    void *back[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, counts, variance, age};
+    const size_t bytes[8] = {px * 4, px * 24, px * 24, history_prev ? temporal_history_bytes(*o) : 0, host[4] ? px : 0, px, variance ? px * 4 : 0, age ? px * 4 : 0};
+    size_t off[8], at = 0;
+    for (int i = 0; i < 8; ++i) {
+        off[i] = at;
+        at = align256(at + bytes[i]);
+    }
+    if (const int e = ensure_staging(ctx, at)) return e; /* what may be in flight where it grows: as for c2rt_temporal_accumulate */
+    char *dev = reinterpret_cast<char *>(ctx->frame);
+    for (int i = 0; i < 5; ++i)
+        if (bytes[i]) HIP_TRY(ctx, hipMemcpyAsync(dev + off[i], host[i], bytes[i], hipMemcpyHostToDevice, ctx->stream));
+    c2rt_temporal_guides g;
+    g.node = reinterpret_cast<const int32_t *>(dev + off[0]);
+    g.normal = reinterpret_cast<const double *>(dev + off[1]);
+    g.p = reinterpret_cast<const double *>(dev + off[2]);
+    if (const int st = path_counts_enqueue(ctx, g, *o, *pc, &k, bytes[3] ? dev + off[3] : nullptr, bytes[4] ? reinterpret_cast<const uint8_t *>(dev + off[4]) : nullptr,
+                                           reinterpret_cast<uint8_t *>(dev + off[5]), bytes[6] ? reinterpret_cast<float *>(dev + off[6]) : nullptr,
+                                           bytes[7] ? reinterpret_cast<uint32_t *>(dev + off[7]) : nullptr, ctx->stream))
+        return st;
+    for (int i = 5; i < 8; ++i)
+        if (bytes[i]) HIP_TRY(ctx, hipMemcpyAsync(back[i], dev + off[i], bytes[i], hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return C2RT_OK;
 }
 
 /* ---- variance-guided denoise: the filter steered by the temporal planes (c2rt_denoise_variance.hip) ---------------------- */
@@ -2403,11 +2594,11 @@ static int plan_posed_sequence(c2rt_ctx *ctx, const c2rt_scene_pose *poses, uint
     return C2RT_OK;
 }
 
-/* the four sequence calls: `d` the plain filter's options or `dv` the variance-guided one's, the other null; `posed`: the
- * posed calls, `poses` theirs */
+/* the five sequence calls: `d` the plain filter's options or `dv` the variance-guided one's, the other null; `posed`: the
+ * posed calls, `poses` theirs; `adaptive`: c2rt_render_paths_sequence_adaptive, `pc` its count options */
 static int paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts, const c2rt_path_opts *pg,
                           const c2rt_temporal_opts *t, const c2rt_denoise_opts *d, const c2rt_denoise_variance_opts *dv, float *out_rgb,
-                          const c2rt_scene_pose *poses = nullptr, bool posed = false)
+                          const c2rt_scene_pose *poses = nullptr, bool posed = false, bool adaptive = false, const c2rt_path_count_opts *pc = nullptr)
 {
     if (n_frames == 0) return fail(ctx, C2RT_ERR_INVALID_ARG, "n_frames is 0: a sequence has at least one frame");
     if (!t) return fail(ctx, C2RT_ERR_INVALID_ARG, "null temporal options");
@@ -2427,15 +2618,22 @@ static int paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t
     PosedSequence seq;
     if (posed)
         if (const int st = plan_posed_sequence(ctx, poses, n_frames, seq)) return st;
+    if (adaptive) {
+        if (!pc) return fail(ctx, C2RT_ERR_INVALID_ARG, "null path count options");
+        if (const int st = check_path_count_opts(ctx, pc)) return st;
+        if (pc->max_paths > pg->paths)
+            return fail(ctx, C2RT_ERR_INVALID_ARG, "max_paths is %u: above the cap, paths = %u", (unsigned)pc->max_paths, (unsigned)pg->paths);
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t px = (size_t)opts->width * opts->height, hist = temporal_history_bytes(*t);
-    /* [node | normal | p | rgb | albedo | indirect | out | scratch | history 0 | history 1 | variance | age], each 256-byte
-     * aligned; the accumulated plane the filter reads is the colour plane of the history just written; the last two for the
-     * variance-guided filter only */
-    const size_t bytes[12] = {px * 4, px * 24, px * 24, px * 12, px * 12, px * 12, px * 12, d ? c2rt_denoise_scratch_bytes(d) : c2rt_denoise_variance_scratch_bytes(dv),
-                              hist, hist, dv ? px * 4 : 0, dv ? px * 4 : 0};
-    size_t off[12], at = 0;
-    for (int i = 0; i < 12; ++i) {
+    /* [node | normal | p | rgb | albedo | indirect | out | scratch | history 0 | history 1 | variance | age | counts 0 |
+     * counts 1 | order], each 256-byte aligned; the accumulated plane the filter reads is the colour plane of the history
+     * just written; variance and age for the variance-guided filter only, the two count planes and the count-order scratch
+     * for the adaptive call only */
+    const size_t bytes[15] = {px * 4, px * 24, px * 24, px * 12, px * 12, px * 12, px * 12, d ? c2rt_denoise_scratch_bytes(d) : c2rt_denoise_variance_scratch_bytes(dv),
+                              hist, hist, dv ? px * 4 : 0, dv ? px * 4 : 0, adaptive ? px : 0, adaptive ? px : 0, adaptive ? counted_scratch_bytes(px) : 0};
+    size_t off[15], at = 0;
+    for (int i = 0; i < 15; ++i) {
         off[i] = at;
         at = align256(at + bytes[i]);
     }
@@ -2465,10 +2663,16 @@ static int paths_sequence(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t
         pgi.seed = pg->seed + i;
         int e = launch_plane_rows(p, ctx->plan.csg_levels, kNoOpts, hits, 0, p.local_rows, ctx->stream);
         if (e == 0) e = launch_plane_rows(p, ctx->plan.csg_levels, kNoOpts, shade, 0, p.local_rows, ctx->stream);
-        if (e == 0) e = launch_plane_rows(p, ctx->plan.csg_levels, pgi, paths, 0, p.local_rows, ctx->stream);
-        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "path sequence, frame %u, plane kernel launch: %s", (unsigned)i, hipGetErrorString((hipError_t)e));
         char *h_out = dev + off[8 + (i & 1u)], *h_prev = i ? dev + off[8 + ((i - 1) & 1u)] : nullptr;
         if (i) (void)temporal_camera(cams[i - 1], *t, k);
+        if (adaptive) { /* the frame's counts: young_paths everywhere, or the rule over the history before this frame is folded in */
+            uint8_t *counts = reinterpret_cast<uint8_t *>(dev + off[12 + (i & 1u)]), *counts_prev = reinterpret_cast<uint8_t *>(dev + off[12 + ((i - 1) & 1u)]);
+            if (e == 0 && i == 0) e = (int)hipMemsetAsync(counts, (int)pc->young_paths, px, ctx->stream);
+            if (e == 0 && i != 0) e = launch_path_counts(tg, *t, *pc, &k, h_prev, counts_prev, counts, nullptr, nullptr, ctx->stream);
+            /* frame 0's counts are even: natural order; the rule's are not: count order (profiles/paths_counted.md) */
+            if (e == 0) e = launch_counted_rows(p, ctx->plan.csg_levels, pgi, counts, paths, 0, p.local_rows, i ? dev + off[14] : nullptr, ctx->stream);
+        } else if (e == 0) e = launch_plane_rows(p, ctx->plan.csg_levels, pgi, paths, 0, p.local_rows, ctx->stream);
+        if (e != 0) return fail(ctx, C2RT_ERR_HIP, "path sequence, frame %u, plane kernel launch: %s", (unsigned)i, hipGetErrorString((hipError_t)e));
         if (const int st = temporal_enqueue(ctx, tg, *t, &k, paths.indirect, h_prev, h_out, tp, ctx->stream, posed ? &seq.motion[i] : nullptr)) return st;
         const float *acc = reinterpret_cast<const float *>(h_out + px * 32);
         float *out = reinterpret_cast<float *>(dev + off[6]);
@@ -2521,6 +2725,16 @@ int c2rt_render_paths_sequence_variance(c2rt_ctx *ctx, const c2rt_camera_frame *
         return st;
     if (const int st = check_denoise_variance_opts(ctx, dv)) return st;
     return paths_sequence(ctx, cams, n_frames, opts, pg, t, nullptr, dv, out_rgb);
+}
+
+int c2rt_render_paths_sequence_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
+                                        const c2rt_path_opts *pg, const c2rt_temporal_opts *t, const c2rt_denoise_variance_opts *dv,
+                                        const c2rt_path_count_opts *pc, float *out_rgb)
+{
+    if (const int st = check_paths_filtered(ctx, cams, opts, pg, dv != nullptr, dv ? dv->width : 0, dv ? dv->height : 0, dv ? dv->channels : 0, out_rgb))
+        return st;
+    if (const int st = check_denoise_variance_opts(ctx, dv)) return st;
+    return paths_sequence(ctx, cams, n_frames, opts, pg, t, nullptr, dv, out_rgb, nullptr, false, true, pc);
 }
 
 int c2rt_render_paths_sequence_posed(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses, uint32_t n_frames,

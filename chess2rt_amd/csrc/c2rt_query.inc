@@ -1,6 +1,6 @@
 /*
  * c2rt_query.inc — what the query kernels share (c2rt_rays.hip, c2rt_hit_planes.hip, c2rt_layers.hip,
- * c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_gather.hip, c2rt_paths.hip, c2rt_adaptive.hip, c2rt_sample_taps.hip): a lane traces
+ * c2rt_shade_planes.hip, c2rt_occlusion.hip, c2rt_gather.hip, c2rt_paths.hip, c2rt_paths_counted.hip, c2rt_adaptive.hip, c2rt_sample_taps.hip): a lane traces
  * ONE ray that is not a frame tile's — the caller's, or the camera's through a pixel — with exact:: arithmetic (the probe's choice; bit-equal to what the frames compute), every
  * culling mask all ones (query_ctx, c2rt_trace_shared.inc), no ground-tile shortcut, and a full-capacity CSG hit stack:
  * kCsgFullCap(LEVELS) entries in one launch, which cannot overflow, so there is no retry list and no per-stream scratch.

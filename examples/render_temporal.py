@@ -13,7 +13,14 @@ difference between neighbouring hit pixels — before and after the accumulation
 that the sliding piece keeps its history as the board under it does; the script then also prints how many of the piece's
 pixels found their history, against how many the plain call finds for the same frame.
 
+--adaptive lets the history steer the sampler as well: frame 0 is traced with --young paths per pixel, every later frame
+with the counts Context.pathCounts makes of the previous history (its variance at the point each pixel sees now, times the
+count that variance was sampled with, times --paths-per-variance, within --min-paths .. --paths) through
+Context.renderPathsCounted; the script prints the mean count per frame.  (Not together with --posed: the count rule does not
+follow moved nodes.)
+
   python examples/render_temporal.py tests/golden/scenes/lecture5.sdl /tmp/orbit --size 640 480 --frames 8 --paths 4
+  python examples/render_temporal.py tests/golden/scenes/lecture5.sdl /tmp/adaptive --adaptive --paths 32 --young 8
   python examples/render_temporal.py tests/golden/scenes/lecture5.sdl /tmp/slide --posed 1 4 0 -3 --step 0 0
 """
 import argparse
@@ -57,7 +64,13 @@ def main():
     ap.add_argument("--min-age", type=int, default=4, help="--variance: pixels younger than this take a spatial variance estimate")
     ap.add_argument("--posed", type=float, nargs=4, metavar=("NODE", "DX", "DY", "DZ"),
                     help="slide node NODE by (DX, DY, DZ) per frame and let the accumulation follow it")
+    ap.add_argument("--adaptive", action="store_true", help="trace each pixel with the number of paths its history's variance asks for; --paths is the cap")
+    ap.add_argument("--min-paths", type=int, default=2, help="--adaptive: the fewest paths of a pixel with a history")
+    ap.add_argument("--young", type=int, default=None, help="--adaptive: paths of a pixel without a history (default: --paths)")
+    ap.add_argument("--paths-per-variance", type=float, default=2000.0, help="--adaptive: paths asked for per unit of per-path luminance variance")
     args = ap.parse_args()
+    if args.adaptive and args.posed:
+        sys.exit("--adaptive: the count rule does not follow moved nodes; not together with --posed")
     scene = c2.parseSceneFromFile(args.scene)
     scene.setFrameSize(*args.size)
     scene.setAA(False)
@@ -66,7 +79,8 @@ def main():
     ctx = c2.Context()
     ctx.uploadScene(scene.desc)
     opts = scene.renderOpts()
-    prev_cam, history = None, None
+    prev_cam, history, counts = None, None, None
+    young = min(args.young or args.paths, args.paths)
     node, pose, prev_pose = None, None, None
     if args.posed:
         node = int(args.posed[0])
@@ -84,7 +98,20 @@ def main():
             motion = {node: (prev_pose, pose)} if i else {}
         hits = ctx.renderHits(cam, opts, planes=("node", "normal", "p", "rgb"))
         albedo = ctx.renderShading(cam, opts, planes=("albedo",))["albedo"]
-        indirect = ctx.renderPaths(cam, opts, args.paths, depth, seed=args.seed + i, planes=("indirect",))["indirect"]
+        if args.adaptive:
+            if i == 0:
+                counts = np.full(hits["node"].shape, young, dtype=np.uint8)
+            else:
+                counts = ctx.pathCounts(hits, prev_cam=prev_cam, history=history, prev_counts=counts, min_paths=args.min_paths, max_paths=args.paths,
+                                        young_paths=young, paths_per_variance=args.paths_per_variance, prev_paths=young,
+                                        min_normal_dot=args.min_normal_dot, max_plane_dist=args.max_plane_dist, planes=())["counts"]
+            indirect = ctx.renderPathsCounted(cam, opts, counts, args.paths, depth, seed=args.seed + i, planes=("indirect",))["indirect"]
+            on = hits["node"] >= 0
+            print("frame %2d: %.2f paths per hit pixel (%d .. %d), %.1f %% of them at the cap of %d"
+                  % (i, float(counts[on].mean()) if on.any() else 0.0, int(counts[on].min()) if on.any() else 0, int(counts[on].max()) if on.any() else 0,
+                     100.0 * float((counts[on] >= args.paths).mean()) if on.any() else 0.0, args.paths))
+        else:
+            indirect = ctx.renderPaths(cam, opts, args.paths, depth, seed=args.seed + i, planes=("indirect",))["indirect"]
         if args.posed and i:
             plain = ctx.temporalAccumulate(hits, indirect, prev_cam=prev_cam, history=history, max_age=args.max_age, min_normal_dot=args.min_normal_dot,
                                            max_plane_dist=args.max_plane_dist, planes=("age",))[0]["age"]

@@ -1021,6 +1021,56 @@ int c2rt_trace_rays_paths_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64
 int c2rt_trace_rays_paths(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n,
                           const c2rt_path_opts *g, const c2rt_path_planes *planes_host);
 
+/* ---- counted path planes: a number of paths per sample ----------------------- */
+
+/* The path planes with ONE BYTE per sample beside them that says how many paths the sample gets: `counts`, required —
+ *   camera calls: row-major [local_rows][W], strips as for the planes;  ray calls: [n].
+ * Everything else — sample index, ray, seed, bounces, planes — is the path call's.  With c = min(counts[i], g->paths)
+ * (g->paths is the cap and keeps its range 1 .. C2RT_MAX_PATHS):
+ *
+ *   c >= 1:  every plane of sample i is, BIT FOR BIT, what c2rt_render_paths / c2rt_trace_rays_paths writes for that
+ *            sample with paths = c, the same seed, bounces and sample index: path p of sample idx draws
+ *            rng_key(seed, idx, j) with sample p whatever P is, the fp32 sum is path-major, and indirect = sum / (float)c.
+ *   c == 0:  the sample takes the path contract's "miss, or Beff == 0" line: `node` is still the record's,
+ *            segments = 0, indirect = bounce = +0,+0,+0, radiance = the ray's c2rt_trace_rays rgb; nothing is drawn.
+ *
+ *   - A counts plane whose every value is >= g->paths gives the uniform call's bits.
+ *   - The path planes' rules hold: what is written to a plane does not depend on which others are asked for; `node` alone
+ *     traces no path (and reads no count); a lane of NaNs ends after at most c * Beff segments.
+ *
+ * Launch order.  A wavefront runs as long as its heaviest lane, so one sample at 64 paths among 63 at 2 costs its wave 64
+ * paths' worth of iterations.  The _device variants take `scratch_dev`, nullable:
+ *   null:      natural order — the path call's lane mapping, ONE kernel, nothing else enqueued;
+ *   non-null:  count order — c2rt_paths_counted_scratch_bytes(samples of the call: local_rows * W, or n) bytes, 16-byte
+ *              aligned, written by the call.  A counting sort of the sample indices by c, heaviest class first, is
+ *              enqueued ahead of the path kernel (one memset, three small kernels), and lane i of the path kernel takes
+ *              the i-th sample of that order; a camera call derives the pixel from the index.  The order inside a class
+ *              is left to atomics.  A call of 2^32 samples or more runs in natural order all the same.
+ * Both orders write the same bits: no sample's value depends on where it ran.  Which one is faster depends on how the
+ * counts lie in the plane (profiles/paths_counted.md).
+ *
+ * c2rt_paths_counted_scratch_bytes: pure host arithmetic, no context: 512 + 4 * n_samples rounded up to 16.
+ *
+ * Statuses, all decided before anything is enqueued or written: the path call's own first, in its order (n == 0 of a
+ * ray call is C2RT_OK whatever else is passed); then null `counts`: C2RT_ERR_INVALID_ARG; then, for the _device variants,
+ * a non-null `scratch_dev` that is not 16-byte aligned: C2RT_ERR_INVALID_ARG.
+ *
+ * The stream rules are the path calls'.  The host variants stage the counts of each chunk beside the chunk's planes —
+ * one more byte per sample — with the scratch behind them (4 B per sample and 544 B per chunk) and run every chunk in count
+ * order: on the three uneven planes measured it took 0.43 to 0.76 of natural order's time, on an even plane 1.07
+ * (profiles/paths_counted.md). */
+size_t c2rt_paths_counted_scratch_bytes(uint64_t n_samples);
+int c2rt_render_paths_counted_device(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                                     const c2rt_path_opts *g, const uint8_t *counts_dev, const c2rt_path_planes *planes_dev,
+                                     void *scratch_dev, void *hip_stream);
+int c2rt_render_paths_counted(c2rt_ctx *ctx, const c2rt_camera_frame *cam, const c2rt_render_opts *opts,
+                              const c2rt_path_opts *g, const uint8_t *counts, const c2rt_path_planes *planes_host);
+int c2rt_trace_rays_paths_counted_device(c2rt_ctx *ctx, const c2rt_ray *rays_dev, uint64_t n,
+                                         const c2rt_path_opts *g, const uint8_t *counts_dev, const c2rt_path_planes *planes_dev,
+                                         void *scratch_dev, void *hip_stream);
+int c2rt_trace_rays_paths_counted(c2rt_ctx *ctx, const c2rt_ray *rays, uint64_t n,
+                                  const c2rt_path_opts *g, const uint8_t *counts, const c2rt_path_planes *planes_host);
+
 /* ---- denoise: edge-aware a-trous filter of a Monte-Carlo plane, guided by the hit planes ---- */
 
 /* Most levels of one call; C2RT_ERR_LIMIT beyond (level l taps 2^l pixels apart). */
@@ -1457,6 +1507,87 @@ int c2rt_render_paths_sequence_posed(c2rt_ctx *ctx, const c2rt_camera_frame *cam
 int c2rt_render_paths_sequence_posed_variance(c2rt_ctx *ctx, const c2rt_camera_frame *cams, const c2rt_scene_pose *poses,
                                               uint32_t n_frames, const c2rt_render_opts *opts, const c2rt_path_opts *g,
                                               const c2rt_temporal_opts *t, const c2rt_denoise_variance_opts *dv, float *out_rgb);
+
+/* ---- adaptive path counts: the temporal variance steers the sampler ---------- */
+
+typedef struct c2rt_path_count_opts {   /* 32 bytes */
+    uint32_t min_paths;           /* 1 .. C2RT_MAX_PATHS */
+    uint32_t max_paths;           /* min_paths .. C2RT_MAX_PATHS */
+    uint32_t young_paths;         /* 1 .. C2RT_MAX_PATHS: no history, or younger than min_age */
+    uint32_t min_age;             /* 0 .. C2RT_MAX_TEMPORAL_AGE */
+    float    paths_per_variance;  /* finite, > 0 */
+    uint32_t prev_paths;          /* 1 .. C2RT_MAX_PATHS: the count behind every history pixel where prev_counts is null */
+    uint32_t reserved[2];         /* 0 */
+} c2rt_path_count_opts;
+
+/* How many paths each pixel of a frame should get, decided BEFORE the frame's paths are traced, from what the PREVIOUS
+ * history says about the variance at the point the pixel sees now: the counts plane of c2rt_render_paths_counted.  It is
+ * the first half of c2rt_temporal_accumulate's pixel — the reprojection and the four-tap gather of (M1, M2, age) — without
+ * the fold; nothing is accumulated and no history is written.  The stage traces nothing and needs no uploaded scene.
+ * `guides` are the CURRENT frame's hit planes; of `o`, width, height, channels (the history's layout), min_normal_dot and
+ * max_plane_dist are used and max_age is ignored; `history_prev` (nullable: the first frame) is the history the previous
+ * c2rt_temporal_accumulate call wrote, `prev_cam` its camera; `prev_counts` (nullable, uint8 [H][W]) the counts the
+ * history's LAST sample was traced with.  Outputs: `counts` uint8 [H][W], required; `variance` float [H][W] and `age`
+ * uint32 [H][W], each nullable.
+ *
+ * The arithmetic is the contract, as the temporal stage's is, and tests/path_counts_reference.py restates it in numpy to
+ * the bit:
+ *
+ *   node[q] < 0:                    counts = 0; variance = +0f; age = 0
+ *   else: the temporal contract's pixel, word for word, from `r.c = p[q].c - prev.pos.c` to `!(sumw > 0): NO HISTORY`,
+ *         gathering s1, s2, amin (sum.c is not needed), and beside them
+ *           cprev = max over the KEPT taps of (prev_counts ? prev_counts[t] : prev_paths);  cprev == 0: cprev = 1
+ *     NO HISTORY (also: history_prev == NULL), or amin < min_age:
+ *                                   counts = young_paths; variance = +0f; age = NO HISTORY ? 0 : amin
+ *     else: m1 = s1 / sumw; m2 = s2 / sumw; v = m2 - m1*m1; v = v <= 0 ? +0f : v       -- a NaN stays a NaN (the
+ *                                                                              accumulation's own variance clamps it to +0)
+ *           t = (v * (float)cprev) * paths_per_variance                    -- fp32, two multiplies in this order
+ *           !(t < (float)max_paths):  k = max_paths                        -- NaN and infinity land here: a history
+ *                                                                              with a NaN moment asks for the most
+ *           else: k = (uint32)t (truncation);  if ((float)k < t) k += 1;  k = max(k, min_paths)
+ *           counts = k; variance = v; age = amin
+ *
+ *   - `age` is the history's own (the accumulation of the same frame reports min(age + 1, max_age)); `variance` is the
+ *     gathered one, before this frame's sample is folded in.
+ *   - Why cprev is in the rule: the history's variance is that of the per-frame SAMPLE, a mean over that frame's paths.
+ *     Without the factor the rule is c' = K / c, which oscillates; with it the fixed point is
+ *     c = paths_per_variance * (the variance of one path).  The running moments mix frames traced with different counts,
+ *     so the estimate is exact only once the counts have settled.
+ *   - Why min_paths >= 1: a pixel traced with 0 paths would fold a zero into the temporal mean.
+ *   - Moved nodes (c2rt_temporal_accumulate_motion's list) are not followed: a pixel on a moved node fails the plane test
+ *     here and gets young_paths, which is the safe side.
+ *
+ * Statuses, all decided before anything is enqueued or written, each with its own message, in this order:
+ * c2rt_temporal_accumulate's for the context, `o`, `guides`, the sizes, channels, min_normal_dot, max_plane_dist and
+ * reserved (max_age is not looked at); null `pc`: C2RT_ERR_INVALID_ARG; min_paths 0, max_paths < min_paths, young_paths 0:
+ * C2RT_ERR_INVALID_ARG, and min_paths, max_paths or young_paths above C2RT_MAX_PATHS: C2RT_ERR_LIMIT, field by field in
+ * the struct's order; min_age above C2RT_MAX_TEMPORAL_AGE: C2RT_ERR_LIMIT; prev_paths 0: C2RT_ERR_INVALID_ARG, above
+ * C2RT_MAX_PATHS: C2RT_ERR_LIMIT; paths_per_variance NaN, infinite or <= 0, then reserved != 0: C2RT_ERR_INVALID_ARG; null
+ * `node`, `normal` or `p`; null `counts`; a non-null `history_prev` with a null `prev_cam`; with a history, a degenerate
+ * previous camera; on the device variant a history that is not 16-byte aligned: C2RT_ERR_INVALID_ARG.
+ *
+ * c2rt_path_counts_device takes c2rt_temporal_accumulate_device's stream rules and enqueues ONE kernel.  The host variant
+ * stages everything whole through the context's staging buffer (at most 110 B per pixel) and blocks until the planes are
+ * there; a host history needs no alignment. */
+int c2rt_path_counts_device(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_dev,
+                            const c2rt_temporal_opts *o, const c2rt_path_count_opts *pc, const void *history_prev_dev,
+                            const uint8_t *prev_counts_dev, uint8_t *counts_dev, float *variance_dev, uint32_t *age_dev,
+                            void *hip_stream);
+int c2rt_path_counts(c2rt_ctx *ctx, const c2rt_camera_frame *prev_cam, const c2rt_temporal_guides *guides_host,
+                     const c2rt_temporal_opts *o, const c2rt_path_count_opts *pc, const void *history_prev,
+                     const uint8_t *prev_counts, uint8_t *counts, float *variance, uint32_t *age);
+
+/* c2rt_render_paths_sequence_variance with the sampler in the loop.  Frame 0 is traced with pc->young_paths everywhere,
+ * through the counted call.  Frame i > 0: the hit planes; c2rt_path_counts from history i - 1, cams[i - 1] and the counts
+ * of frame i - 1; c2rt_render_paths_counted with g->paths as the cap and seed g->seed + i; the accumulation; the variance
+ * filter.  out_rgb is bit for bit the composition of the single calls.  The two count planes and the count-order scratch
+ * sit in the staging buffer beside the rest: 6 B per pixel more, 274 in all; frame 0, whose counts are even, runs in natural
+ * order and every later frame in count order.  Statuses:
+ * c2rt_render_paths_sequence_variance's, in its order; then null `pc`; then the count options' own, in c2rt_path_counts'
+ * order; then pc->max_paths > g->paths: C2RT_ERR_INVALID_ARG.  Posed sequences are not part of this call. */
+int c2rt_render_paths_sequence_adaptive(c2rt_ctx *ctx, const c2rt_camera_frame *cams, uint32_t n_frames, const c2rt_render_opts *opts,
+                                        const c2rt_path_opts *g, const c2rt_temporal_opts *t, const c2rt_denoise_variance_opts *dv,
+                                        const c2rt_path_count_opts *pc, float *out_rgb);
 
 /* ---- adaptive anti-aliasing: refine only the pixels the edge test flags ----- */
 

@@ -364,6 +364,45 @@ extern (C) nothrow @nogc
     int c2rt_render_paths_sequence_posed_variance(c2rt_ctx*, const c2rt_camera_frame* cams, const c2rt_scene_pose* poses,
                                                   uint n_frames, const c2rt_render_opts*, const c2rt_path_opts*,
                                                   const c2rt_temporal_opts*, const c2rt_denoise_variance_opts*, float* out_rgb);
+    /// counted path planes: the path planes with one byte per sample that says how many paths it gets, c = min(counts[i],
+    /// paths); a sample at c >= 1 holds the bits of the uniform call at paths = c, a sample at 0 its node and primary colour.
+    /// scratch_dev null: natural order, one kernel; else c2rt_paths_counted_scratch_bytes(samples) bytes, 16-byte aligned:
+    /// the samples sorted by count ahead of the path kernel — the same bits (include/c2rt.h)
+    size_t c2rt_paths_counted_scratch_bytes(ulong n_samples);
+    int c2rt_render_paths_counted_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_path_opts*,
+                                         const ubyte* counts_dev, const c2rt_path_planes* planes_dev, void* scratch_dev,
+                                         void* hip_stream);
+    int c2rt_render_paths_counted(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, const c2rt_path_opts*,
+                                  const ubyte* counts, const c2rt_path_planes* planes_host);
+    int c2rt_trace_rays_paths_counted_device(c2rt_ctx*, const c2rt_ray* rays_dev, ulong n, const c2rt_path_opts*,
+                                             const ubyte* counts_dev, const c2rt_path_planes* planes_dev, void* scratch_dev,
+                                             void* hip_stream);
+    int c2rt_trace_rays_paths_counted(c2rt_ctx*, const c2rt_ray* rays, ulong n, const c2rt_path_opts*, const ubyte* counts,
+                                      const c2rt_path_planes* planes_host);
+    /// path counts: the counts plane of the NEXT frame from the previous history's variance at the point each pixel sees now
+    /// (the accumulation's reprojection and gather without the fold); arithmetic fixed by include/c2rt.h
+    struct c2rt_path_count_opts
+    {
+        uint min_paths;             /// 1 .. C2RT_MAX_PATHS
+        uint max_paths;             /// min_paths .. C2RT_MAX_PATHS
+        uint young_paths;           /// no history, or younger than min_age
+        uint min_age;               /// 0 .. C2RT_MAX_TEMPORAL_AGE
+        float paths_per_variance;   /// finite, > 0
+        uint prev_paths;            /// the count behind every history pixel where prev_counts is null
+        uint[2] reserved;           /// 0
+    }
+    int c2rt_path_counts_device(c2rt_ctx*, const c2rt_camera_frame* prev_cam, const c2rt_temporal_guides* guides_dev,
+                                const c2rt_temporal_opts*, const c2rt_path_count_opts*, const void* history_prev_dev,
+                                const ubyte* prev_counts_dev, ubyte* counts_dev, float* variance_dev, uint* age_dev,
+                                void* hip_stream);
+    int c2rt_path_counts(c2rt_ctx*, const c2rt_camera_frame* prev_cam, const c2rt_temporal_guides* guides_host,
+                         const c2rt_temporal_opts*, const c2rt_path_count_opts*, const void* history_prev,
+                         const ubyte* prev_counts, ubyte* counts, float* variance, uint* age);
+    /// c2rt_render_paths_sequence_variance with the sampler in the loop: frame 0 at young_paths, frame i at the counts the
+    /// rule makes of history i - 1
+    int c2rt_render_paths_sequence_adaptive(c2rt_ctx*, const c2rt_camera_frame* cams, uint n_frames, const c2rt_render_opts*,
+                                            const c2rt_path_opts*, const c2rt_temporal_opts*, const c2rt_denoise_variance_opts*,
+                                            const c2rt_path_count_opts*, float* out_rgb);
     enum float C2RT_AA_THRESHOLD_REF = 0.1f; /// tooDifferent's default
     int c2rt_render_frame_adaptive_device(c2rt_ctx*, const c2rt_camera_frame*, const c2rt_render_opts*, float threshold,
                                           float* out_rgb_dev, ubyte* needs_aa_dev, void* hip_stream);
